@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """bench.py — mel-frames/s of the BiSinger mel-generation hot path on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]          # N > 1 from a bare shell: starts its own N worker processes
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]   # N > 1 from a bare shell: starts its own N workers
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W               # or under torchrun (RANK / LOCAL_RANK / WORLD_SIZE from the env)
+
+A plain run sets up, warms up (W passes), times exactly K passes and prints the record: the headline (`value`, `ms_per_step`) and its
+`roofline`, which is timed live inside those K passes.  Everything else below (`weak_scaling`, `secondary`, `strong_denominator`,
+`range_headroom`, `cpu_baseline`, `parity`) costs runs of its own and is measured only with --full.
+--dump-outputs DIR writes what the last timed pass returned (rank 0's GaussianDiffusion.forward dict, `mel_out` gathered over the ranks) as
+DIR/<key>.npy in float32 / float64 (integer tensors as float64), so that two builds can be compared output for output: the inputs, weights and
+Philox seeds depend on the arguments only.
 
 A "step" = one pass of the hot path over one batch of synthetic utterances already resident in HBM:
 GaussianDiffusion.forward(infer=True) = FastSpeech2-MIDI encoder+decoder, 100 DDPM ancestral sampler steps of the 20-layer
@@ -12,7 +19,7 @@ DiffNet (on-device Philox noise), de-normalisation — and, for N > 1, the RCCL 
 Workloads
   N = 1   BASELINE.json configs[1]: B=16, T=1000, 80 mel, fp32 (the configuration the metric is quoted on).
   N > 1   BASELINE.json configs[3]: B_total = 64 utterances sharded 64/N per GPU ("scaling": "strong"), one RCCL all-gather of
-          the mels per pass; a weak-scaling figure (16 utterances per GPU) is measured after it and attached as `weak_scaling`.
+          the mels per pass; with --full a weak-scaling figure (16 utterances per GPU) is measured after it and attached as `weak_scaling`.
 
 The JSON line also carries
   roofline     : the dominant kernel (the residual stack launch: all 20 layers — and the step tail — per launch), timed live with
@@ -380,6 +387,8 @@ class Workload:
         d = self.d
         out = self.model(d['txt_tokens'], mel2ph=d['mel2ph'], spk_embed=d['spk_embed'], ref_mels=None, infer=True, seed=seed,
                          rows=self.rows if self.world > 1 else None, **self.kw)
+        if getattr(self, 'keep_last', False):           # --dump-outputs: the whole dict the caller receives
+            self.last = out
         if self.emulate:
             return out['mel_out']
         if getattr(self, 'gather_on_host', False):      # --rehearse-one-gpu: gloo through host memory
@@ -405,6 +414,27 @@ def timed(wl, steps, warmup, fence, profile=True):
     if profile:
         net.profile(False)
     return dt, layer_ms, n_layer, mel
+
+
+def dump_outputs(out, mel, path, cap_bytes=60 * 10**6):
+    """--dump-outputs: every tensor of the last timed pass's result dict `out`, with `mel` (the gathered mels) as `mel_out`, written as
+    path/<key>.npy — floating tensors as float32 (float64 stays), integer / bool tensors as float64.  The data stay under `cap_bytes` in all
+    (below 64 MB with the .npy headers): smallest first, an array larger than an equal share of what is left is replaced by a fixed, seeded
+    sample of its flattened elements (the same indices in every run with the same arguments)."""
+    import numpy as np
+    import torch
+    arrs = {k: v for k, v in out.items() if torch.is_tensor(v)}
+    arrs['mel_out'] = mel
+    arrs = {k: (v.float() if v.is_floating_point() and v.dtype != torch.float64 else v.double()).cpu().numpy() for k, v in arrs.items()}
+    os.makedirs(path, exist_ok=True)
+    left = cap_bytes
+    for i, k in enumerate(sorted(arrs, key=lambda k: (arrs[k].nbytes, k))):
+        a, share = arrs[k], left // (len(arrs) - i)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k + '.npy'), a)
+        left -= a.nbytes
 
 
 def secondary_bf16(model, device, fence):
@@ -702,15 +732,20 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline: weak scaling (N > 1); the secondaries, range headroom, CPU baseline and '
+                         'parity replay (N = 1).  A plain run times the headline only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed passes, write what the last one returned as DIR/<name>.npy (float32 / float64, at most 64 MB)')
     ap.add_argument('--cpu-steps', type=int, default=10,
-                    help='0 = no CPU baseline and no parity replay.  Otherwise the baseline is ONE FULL 100-step pass of the oracle at the fastest '
+                    help='(with --full) 0 = no CPU baseline and no parity replay.  Otherwise the baseline is ONE FULL 100-step pass of the oracle at the fastest '
                          'thread count of a short sweep (~40 s), and this is the number of sampler steps of the bounded sample that is run 3 times '
                          'at SURVEY §8(d)\'s thread setting (one socket\'s physical cores) and extrapolated, reported beside it')
     ap.add_argument('--dtype', choices=('f32', 'bf16'), default='f32',
                     help='arithmetic of the fused residual layers of the HEADLINE: f32 = configs[1] (default); bf16 = configs[2] (with --batch 64)')
     ap.add_argument('--batch', type=int, default=None, help='utterances per GPU of the headline (default: 16 at N=1, 64/N at N>1)')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the configs[2] / configs[4] secondaries (N = 1)')
-    ap.add_argument('--no-weak', action='store_true', help='skip the weak-scaling figure (N > 1)')
+    ap.add_argument('--no-secondary', action='store_true', help='(with --full) skip the configs[2] / configs[4] secondaries (N = 1)')
+    ap.add_argument('--no-weak', action='store_true', help='(with --full) skip the weak-scaling figure (N > 1)')
     ap.add_argument('--force-dist', action='store_true', help='initialise RCCL and run the all-gather even with one rank (self-test)')
     ap.add_argument('--rehearse-one-gpu', action='store_true',
                     help='rehearsal of the N > 1 code path on a box with ONE GPU (tests/test_gpu_dist.py): every rank computes on cuda:0, the '
@@ -720,6 +755,8 @@ def main():
                     help='process-management self-test (tests/test_dist_cpu.py): the N workers only rendezvous over gloo on the CPU, '
                          'all-gather their ranks and rank 0 prints a record; measures nothing')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     env_world = int(os.environ.get('WORLD_SIZE', '0') or 0)
     if args.gpus > 1 and env_world != args.gpus:
@@ -781,6 +818,7 @@ def main():
     B_total = B_CFG3_TOTAL if strong else (args.batch or B_CFG1) * world
     wl = Workload(model, device, B_total, rank, world)
     wl.gather_on_host = rehearse
+    wl.keep_last = bool(args.dump_outputs)
     if args.force_dist and world == 1:
         _step = wl.step
 
@@ -795,9 +833,12 @@ def main():
     dt = max_over_ranks(dt)
     assert mel.shape == (B_total, T_FRAMES, N_MEL) and bool(torch.isfinite(mel).all())
     timeouts = model.denoise_fn.handoff_timeouts()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl.last, mel, args.dump_outputs)
+        wl.keep_last, wl.last = False, None
 
     weak = None
-    if world > 1 and strong and not args.no_weak:
+    if args.full and world > 1 and strong and not args.no_weak:
         wl2 = Workload(model, device, B_CFG1 * world, rank, world)
         wl2.gather_on_host = rehearse
         k2 = max(2, min(args.steps, 5))
@@ -844,7 +885,7 @@ def main():
             rec['rehearsal'] = 'every rank on cuda:0, collectives over gloo through host memory: the numbers of this line mean nothing'
         if weak:
             rec['weak_scaling'] = weak
-        if world == 1 and not args.no_secondary and not bf16 and args.batch is None:
+        if args.full and world == 1 and not args.no_secondary and not bf16 and args.batch is None:
             rec['secondary'] = {'bf16_b64': secondary_bf16(model, device, fence), 'e2e_rtf_b1': secondary_e2e(model, device, fence),
                                 'cfg3_rank': secondary_cfg3_rank(model, device, fence),
                                 'captured_sampler': secondary_captured(model, device, fence),
@@ -855,10 +896,10 @@ def main():
                 # configs[1] (B = 16) and must not be divided into them
                 rec['strong_denominator'] = {'B': B_CFG3_TOTAL, 'value': c3['value_b64_one_gpu'], 'ms_per_step': c3['ms_per_step_b64_one_gpu'],
                                              'unit': 'mel-frames/s', 'note': 'configs[3] on ONE GPU: all 64 utterances, same pass as the N > 1 runs'}
-        if world == 1 and not bf16 and not args.no_secondary and args.batch is None:
+        if args.full and world == 1 and not bf16 and not args.no_secondary and args.batch is None:
             # (with the secondaries: the probe runs per-layer launches of the fp32 matrix pipe, which do not belong into a profile of the headline)
             rec['range_headroom'] = range_headroom(model, wl, device)
-        if world == 1 and args.cpu_steps > 0:
+        if args.full and world == 1 and args.cpu_steps > 0:
             base, parity = cpu_baseline_and_parity(model, wl.inp_np, device, args.cpu_steps)
             rec['cpu_baseline'] = base
             rec['parity'] = parity

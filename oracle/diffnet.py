@@ -9,6 +9,8 @@ import math
 import torch
 import torch.nn.functional as F
 
+from . import freq
+
 
 def mish(x):
     return x * torch.tanh(F.softplus(x))
@@ -18,7 +20,7 @@ def sinusoidal_pos_emb(t, dim):
     """net.py:37-44 — evaluated in float32 from the int64 step, cat(sin, cos), divisor half-1."""
     half = dim // 2
     e = math.log(10000) / (half - 1)
-    e = torch.exp(torch.arange(half) * -e)            # float32, as in the reference
+    e = freq.inv_freq(torch.arange(half) * -e)         # float32, as in the reference
     e = t[:, None] * e[None, :]                        # int64 * float32 -> float32
     return torch.cat((e.sin(), e.cos()), dim=-1)
 

@@ -16,6 +16,8 @@ import math
 import torch
 import torch.nn.functional as F
 
+from . import freq
+
 DEFAULT_HP = dict(hidden_size=256, enc_layers=4, dec_layers=4, num_heads=2, enc_ffn_kernel_size=9,
                   dec_ffn_kernel_size=9, dur_predictor_layers=5, dur_predictor_kernel=3,
                   esm_heads=8, rel_pos_max_len=5000)
@@ -26,7 +28,7 @@ def sinusoidal_table(num, dim, padding_idx=0):
     """common_layers.py:124-146 (tensor2tensor layout: [sin | cos], row padding_idx zeroed)."""
     half = dim // 2
     e = math.log(10000) / (half - 1)
-    e = torch.exp(torch.arange(half, dtype=torch.float) * -e)
+    e = freq.inv_freq(torch.arange(half, dtype=torch.float) * -e)
     e = torch.arange(num, dtype=torch.float).unsqueeze(1) * e.unsqueeze(0)
     e = torch.cat([torch.sin(e), torch.cos(e)], dim=1).view(num, -1)
     if padding_idx is not None:
@@ -45,7 +47,7 @@ def rel_pos_table(length, d_model):
     interleaved sin/cos."""
     pe = torch.zeros(length, d_model)
     position = torch.arange(length - 1, -1, -1.0, dtype=torch.float32).unsqueeze(1)
-    div = torch.exp(torch.arange(0, d_model, 2, dtype=torch.float32) * -(math.log(10000.0) / d_model))
+    div = freq.inv_freq(torch.arange(0, d_model, 2, dtype=torch.float32) * -(math.log(10000.0) / d_model))
     pe[:, 0::2] = torch.sin(position * div)
     pe[:, 1::2] = torch.cos(position * div)
     return pe

@@ -115,7 +115,8 @@ def test_bench_n_gt_1_code_path_rehearsed_on_one_gpu():
     record with the part kernel named in `roofline` — is rehearsed here with TWO rank processes on the one GPU of the box
     (--rehearse-one-gpu: collectives over gloo through host memory).  Checks the record's shape, not its numbers."""
     import json
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '1', '--warmup', '1', '--rehearse-one-gpu'],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '1', '--warmup', '1', '--rehearse-one-gpu',
+                        '--full'],
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, (p.stderr or '')[-3000:]
     rec = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][-1])

@@ -3,13 +3,36 @@
 import hashlib
 
 import numpy as np
+import pytest
 import torch
 
 from bisinger_amd import synth
-from oracle import diffnet as odn, diffusion as odf, fs2 as ofs2, hifigan as ohg, melgen as omg
+from oracle import diffnet as odn, diffusion as odf, freq as ofreq, fs2 as ofs2, hifigan as ohg, melgen as omg
 
 torch.set_grad_enabled(False)
 T = torch.from_numpy
+INV_FREQ = ('sinusoidal', 'rel_pos')
+_host_inv_freq = ofreq.inv_freq
+
+
+@pytest.fixture(autouse=True)
+def goldens_inv_freq(gold, monkeypatch):
+    """The oracle with the inverse frequencies of the host that made the goldens (oracle/freq.py): another CPU's float32 exp differs by an
+    ulp here and there, which the position tables multiply by the row index.  test_inv_freq_within_one_ulp holds this host's to them."""
+    g = gold('inv_freq')
+
+    def inv_freq(exponent):
+        for k in INV_FREQ:
+            if np.array_equal(exponent.numpy(), g[k + '.exponent']):
+                return T(g[k + '.value'].copy())
+        return _host_inv_freq(exponent)
+    monkeypatch.setattr(ofreq, 'inv_freq', inv_freq)
+
+
+def test_inv_freq_within_one_ulp(gold):
+    g = gold('inv_freq')
+    for k in INV_FREQ:
+        np.testing.assert_array_max_ulp(_host_inv_freq(T(g[k + '.exponent'])).numpy(), g[k + '.value'], maxulp=1)
 
 
 def sha(*arrays):
