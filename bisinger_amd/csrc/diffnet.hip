@@ -25,6 +25,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "bsg_common.h"
@@ -1034,6 +1035,25 @@ __global__ void plms_step_kernel(const float* __restrict__ x, float* __restrict_
   xo[i] = plms_update(x[i], e0[i], e1 ? e1[i] : 0.f, e2 ? e2[i] : 0.f, e3 ? e3[i] : 0.f, n_hist, k, nullptr);
 }
 
+// ragged batches (bsg_diffnet_prepare_ragged): the same update on the frames t < len[b] of every row only — the padding of xo is left as
+// it was.  grid (ceil(T / 256), M, B)
+__global__ void plms_step_ragged_kernel(const float* __restrict__ x, float* __restrict__ xo, const float* __restrict__ e0,
+                                        const float* __restrict__ e1, const float* __restrict__ e2, const float* __restrict__ e3, PlmsCoef k,
+                                        const int* __restrict__ len, int M, int T) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.z;
+  if (t >= len[b]) return;
+  const long long i = ((long long)b * M + blockIdx.y) * T + t;
+  const int n_hist = e3 ? 3 : e2 ? 2 : e1 ? 1 : 0;
+  xo[i] = plms_update(x[i], e0[i], e1 ? e1[i] : 0.f, e2 ? e2[i] : 0.f, e3 ? e3[i] : 0.f, n_hist, k, nullptr);
+}
+
+// ragged batches: v [B][M][T] = 0 at the frames of each row's padding (t >= len[b]).  grid (ceil(T / 256), M, B)
+__global__ void ragged_zero_pad_kernel(float* __restrict__ v, const int* __restrict__ len, int M, int T) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.z;
+  if (t >= T || t < len[b]) return;
+  v[((long long)b * M + blockIdx.y) * T + t] = 0.f;
+}
+
 }  // namespace
 
 }  // namespace bsg
@@ -1157,6 +1177,14 @@ struct bsg_diffnet {
                                        // workgroups of the two chains can share a CU
   hipStream_t st2 = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  // ragged binding (bsg_diffnet_prepare_ragged): every row of the bound (B, T) decoded at its own frame count
+  bool ragged = false;                 // the bound condition came with row lengths (a plain prepare clears this)
+  bool rg_active = false;              // inside a ragged call: stack_rows / launch_stack take the ragged 16-row launch
+  int occ_stack_varlen = -1;           // resident workgroups per CU of that launch (-1: not queried)
+  int* rg_dev = nullptr;               // [B rounded up to even] row lengths, then the tile tables {row, tile} of every launch group
+  size_t rg_cap = 0;                   // ints rg_dev holds
+  std::vector<int> rg_group_off;       // per launch group: offset of its table (in tiles) behind the lengths ...
+  std::vector<int> rg_group_tiles;     // ... and its tile count
 };
 
 static int dev_alloc(float** p, size_t n) {
@@ -1198,6 +1226,7 @@ extern "C" void bsg_diffnet_destroy(bsg_diffnet* h) {
   if (h->part_zx) (void)hipFree(h->part_zx);
   if (h->part_ix) (void)hipFree(h->part_ix);
   if (h->part_flags) (void)hipFree(h->part_flags);
+  if (h->rg_dev) (void)hipFree(h->rg_dev);
   if (h->apack1q) (void)hipFree(h->apack1q);
   if (h->apack2q) (void)hipFree(h->apack2q);
   if (h->wcond_pack) (void)hipFree(h->wcond_pack);
@@ -1453,6 +1482,7 @@ extern "C" int bsg_diffnet_prepare(bsg_diffnet* h, const float* cond, int32_t B,
   BSG_REQUIRE(B > 0 && T > 0, "diffnet_prepare: B=%d T=%d", B, T);
   BSG_REQUIRE((long long)B * T < (1LL << 31) / (2 * C), "diffnet_prepare: B*T=%lld too large", (long long)B * T);
   hipStream_t st = (hipStream_t)stream;
+  h->ragged = false;   // (bsg_diffnet_prepare_ragged sets it again behind this call)
   const size_t bt = (size_t)B * T;
   if (bt > h->cap_bt) {
     BSG_HIP(hipStreamSynchronize(st));
@@ -1743,6 +1773,13 @@ static int launch_layer(bsg_diffnet* h, int layer, const float* x_in, const long
 // each other, and every workgroup of a launch must be resident: at most occ x CUs workgroups, whole rows only.  It pays when a
 // launch has more workgroups than CUs (two per CU overlap each other's waits); smaller launches keep the channel-split kernels.
 static int stack_rows(bsg_diffnet* h, int B, int T, hipStream_t st) {
+  if (h->rg_active) {   // a ragged call (ragged_launch_ok checked it): the 16-row launch on 64-frame tiles, groups from the bound plan
+    h->stack_is_f43 = false;
+    h->stack_is_h2 = h->stack_q = true;
+    h->stack_nct = 2;
+    h->stack_parts = 0;
+    return B;
+  }
   h->stack_is_f43 = false;
   h->stack_is_h2 = false;
   {
@@ -1866,8 +1903,44 @@ static int next_stack_epoch(bsg_diffnet* h, StackArgs& p) {
   return BSG_OK;
 }
 
+// the ragged form of the 16-row stack launch: one launch per group of the plan bound by bsg_diffnet_prepare_ragged, one after the other on
+// `st`; a workgroup finds its row and tile in the group's table, and every pointer is the bound batch's row 0 (rows are not contiguous
+// inside a group)
+static int launch_stack_ragged(bsg_diffnet* h, const long long* t_dev, int t_uniform, int T, hipStream_t st, unsigned long long* stamps,
+                               const TailArgs* tail) {
+  BSG_REQUIRE(h->ragged && h->rg_dev && h->row_off == 0 && h->cond_q_valid, "ragged stack launch: no ragged plan / conditioner quads bound");
+  const size_t bt = (size_t)h->B * T;
+  const int* tabs = h->rg_dev + ((h->B + 1) & ~1);
+  for (size_t g = 0; g < h->rg_group_tiles.size(); ++g) {
+    StackArgs p{};
+    p.x_in = h->xa;
+    p.skip = h->skip;
+    p.condterm = h->condterm;
+    p.dproj = h->dproj; p.dconv = h->dconv; p.t_dev = t_dev; p.t_uniform = t_uniform;
+    p.apackw = h->apackw; p.apack2 = h->apack2; p.bias_out = h->b_out;
+    p.T = T; p.L = h->L; p.tiles_per_row = cdiv(T, 64);
+    p.ct_stride = (long long)2 * C * (long long)bt;
+    p.n_tiles = h->rg_group_tiles[g]; p.cycle = h->cfg.dilation_cycle_length;
+    BSG_REQUIRE((size_t)p.n_tiles <= h->flags_cap && h->L < 64, "ragged stack launch: %d tiles exceed the exchange array (%zu)", p.n_tiles, h->flags_cap);
+    p.hx = h->hx; p.flags = h->flags; p.status = h->flags + h->flags_cap;
+    TRY(next_stack_epoch(h, p));
+    if (h->inject_giveup > 0) { p.inject = 1; --h->inject_giveup; }
+    p.stamps = stamps && g == 0 ? stamps : nullptr;
+    p.clk = h->prof_on && g == 0 ? h->clk : nullptr;
+    p.apack1s = h->apack1s; p.apack2s = h->apack2s; p.h2_scale = h->h2_scale;
+    p.apack1q = h->apack1q; p.apack2q = h->apack2q;
+    p.condterm_q = h->condterm_q;
+    p.vl_len = h->rg_dev;
+    p.vl_tiles = reinterpret_cast<const int2*>(tabs) + h->rg_group_off[g];
+    TRY(launch_residual_stack_h2q(p, tail, st, 2));
+  }
+  h->last_path = tail ? "stack_h2q_ragged_tail" : "stack_h2q_ragged";
+  return BSG_OK;
+}
+
 static int launch_stack(bsg_diffnet* h, const long long* t_dev, int t_uniform, int B, int T, int rows_per_launch, hipStream_t st,
                         unsigned long long* stamps = nullptr, const TailArgs* tail = nullptr) {
+  if (h->rg_active) return launch_stack_ragged(h, t_dev, t_uniform, T, st, stamps, tail);
   const bool f43 = h->stack_is_f43, h2 = h->stack_is_h2;   // the decision of the stack_rows() call that returned rows_per_launch
   const int nct = h2 ? h->stack_nct : 2;
   const int tpr = cdiv(T, 32 * nct);
@@ -2012,6 +2085,45 @@ static int check_bound(bsg_diffnet* h, int B, int T, const char* who) {
   return BSG_OK;
 }
 
+static bool fused_tail_ok(const bsg_diffnet* h);
+
+// Can the handle's CURRENT state decode the bound ragged batch with the ragged launch?  Not when it was demoted off the 16-row launch
+// (bsg_diffnet_set_h2q / set_h2 / set_split 0 or the process switches BSG_H2 / BSG_H2_Q = 0), in the bf16 configuration, or without the
+// conditioner term's channel quads or the fused step tail.  (The callers then decode the rows one by one.)
+static bool ragged_launch_ok(bsg_diffnet* h) {
+  static int envh2 = -1, env_q = -1;
+  if (envh2 < 0) { const char* e = getenv("BSG_H2"); envh2 = e ? atoi(e) : 1; }
+  if (env_q < 0) { const char* e = getenv("BSG_H2_Q"); env_q = e ? atoi(e) : 1; }
+  if (!h->ragged || !envh2 || !env_q || h->h2_off || h->q_off || h->split_off) return false;
+  if (h->compute != BSG_COMPUTE_F32 || h->prepared_compute != BSG_COMPUTE_F32 || !h->cond_q_valid) return false;
+  if (!h->num_cus || !h->hx || !h->epoch_dev || !h->apack1q || !h->apack2q || !h->dconv || !h->tail_s || h->M > 96 || !fused_tail_ok(h)) return false;
+  if (h->occ_stack_varlen < 0) h->occ_stack_varlen = stack_h2q_varlen_occupancy() >= 1 ? 1 : 0;
+  return h->occ_stack_varlen >= 1;
+}
+
+// entry of a compute call on a ragged binding: refused under stream capture and where the handle has no ragged launch
+static int ragged_enter(bsg_diffnet* h, hipStream_t st, const char* who) {
+  if (!h->ragged) return BSG_OK;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (st) (void)hipStreamIsCapturing(st, &cap);
+  if (cap != hipStreamCaptureStatusNone) {
+    set_error("%s: a ragged batch (bsg_diffnet_prepare_ragged) cannot be captured; run it eagerly", who);
+    return BSG_ESTATE;
+  }
+  if (!ragged_launch_ok(h)) {
+    set_error("%s: the bound ragged batch has no ragged launch in this handle's state (bsg_diffnet_ragged_native = 0): decode its rows one by one", who);
+    return BSG_ESTATE;
+  }
+  return BSG_OK;
+}
+
+// rg_active for the duration of one compute call
+struct RaggedScope {
+  bsg_diffnet* h;
+  explicit RaggedScope(bsg_diffnet* h_) : h(h_) { h->rg_active = h->ragged; }
+  ~RaggedScope() { h->rg_active = false; }
+};
+
 // Does the launch this shape takes read the ROW layout of the conditioner term?  (The 16-row stack launch and the part forms read the quads,
 // the bf16 launches the bf16 quads; everything else — 32-row launch, F(4,3), per-layer and channel-split kernels — the rows.)
 static bool cond_rows_needed(bsg_diffnet* h, int B, int T, hipStream_t st) {
@@ -2049,8 +2161,16 @@ static int forward_impl(bsg_diffnet* h, const float* x, const long long* t_dev, 
     h->prof_launches += h->L;
   }
   if (h->compute == BSG_COMPUTE_BF16) TRY(quad_bf16_to_f32(h->skip_h, h->skip, B, C, T, st));
+  if (h->rg_active) {   // ragged: the stack launch stored no skip sum at a row's padding; the projections below read every frame of B x T
+    hipLaunchKernelGGL(ragged_zero_pad_kernel, dim3(cdiv(T, 256), C, B), dim3(256), 0, st, h->skip, (const int*)h->rg_dev, C, T);
+    BSG_LAUNCH_CHECK();
+  }
   TRY(conv1x1(h->w_skip, h->b_skip, h->skip, h->hid, C, C, B, T, ACT_RELU, st));   // net.py:127-128
   TRY(conv1x1(h->w_fin, h->b_fin, h->hid, eps, h->M, C, B, T, ACT_NONE, st));      // net.py:129
+  if (h->rg_active) {   // ragged: the projections above ran on every frame of B x T; the padding's eps is 0
+    hipLaunchKernelGGL(ragged_zero_pad_kernel, dim3(cdiv(T, 256), h->M, B), dim3(256), 0, st, eps, (const int*)h->rg_dev, h->M, T);
+    BSG_LAUNCH_CHECK();
+  }
   return BSG_OK;
 }
 
@@ -2059,6 +2179,8 @@ extern "C" int bsg_diffnet_forward(bsg_diffnet* h, const float* x, const int64_t
   GuardScope guard_scope(h ? &h->guard : nullptr);
   TRY(check_bound(h, B, T, "diffnet_forward"));
   BSG_REQUIRE(x && t && eps, "diffnet_forward: null argument");
+  TRY(ragged_enter(h, (hipStream_t)stream, "diffnet_forward"));
+  RaggedScope ragged_scope(h);
   TRY(cond_layout_for(h, B, T, (hipStream_t)stream));
   return forward_impl(h, x, (const long long*)t, 0, eps, B, T, (hipStream_t)stream);
 }
@@ -2154,7 +2276,7 @@ static int launch_tail(bsg_diffnet* h, TailArgs& a, float* x, int B, int T, hipS
 static int step_from_xa(bsg_diffnet* h, int t_uniform, TailArgs& a, float* x, int B, int T, hipStream_t st) {
   static int env = -1;
   if (env < 0) { const char* e = getenv("BSG_H2_TAIL"); env = e ? atoi(e) : 1; }
-  const int srows = (h->no_split || h->compute != BSG_COMPUTE_F32 || !env || !h->tail_s || h->M > 96) ? 0 : stack_rows(h, B, T, st);
+  const int srows = (!h->rg_active && (h->no_split || h->compute != BSG_COMPUTE_F32 || !env || !h->tail_s || h->M > 96)) ? 0 : stack_rows(h, B, T, st);
   if (srows && h->stack_is_h2 && !h->stack_parts) {
     const size_t off = (size_t)h->row_off * C * T;
     a.x = x; a.xa_next = h->xa + off;
@@ -2267,6 +2389,8 @@ extern "C" int bsg_ddpm_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
   hipStream_t st = (hipStream_t)stream;
   const long long n = (long long)B * h->M * T;
   BSG_REQUIRE(n % 4 == 0, "ddpm_sample: B*M*T must be a multiple of 4");
+  TRY(ragged_enter(h, st, "ddpm_sample"));
+  RaggedScope ragged_scope(h);
   TRY(cond_layout_for(h, B, T, st));
   const long long n4 = n / 4;
   const unsigned long long quad0 = (unsigned long long)row0 * h->M * T / 4;
@@ -2286,7 +2410,7 @@ extern "C" int bsg_ddpm_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
   // fused loop: [in-projection once] -> per step: 20 residual layers -> step_tail_kernel (skip projection, output
   // projection, sampler update, next step's in-projection)
   SubBatch subs[2];
-  const int n_sub = n_steps > 0 ? dual_fork(h, B, T, st, subs) : 1;
+  const int n_sub = n_steps > 0 && !h->rg_active ? dual_fork(h, B, T, st, subs) : 1;
   if (n_sub == 1) subs[0] = SubBatch{0, B, st};
   int rc = BSG_OK;
   for (int u = 0; u < n_sub && rc == BSG_OK; ++u)
@@ -2371,6 +2495,10 @@ extern "C" int bsg_diffnet_uses_handoffs(bsg_diffnet* h, int32_t B, int32_t T, i
     int dev = 0;
     BSG_HIP(hipGetDevice(&dev));
     BSG_HIP(hipDeviceGetAttribute(&h->num_cus, hipDeviceAttributeMultiprocessorCount, dev));
+  }
+  if (h->ragged && h->B == B && h->T == T && ragged_launch_ok(h)) {   // the bound ragged batch: its stack launch hands edges between tiles
+    *uses = 1;
+    return BSG_OK;
   }
   // conservative: any launch shape for which a channel-split (pair / 4-way) or the stack launch may be chosen
   const long long tiles = (long long)B * cdiv(T, 32);
@@ -2551,8 +2679,17 @@ extern "C" int bsg_plms_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
   hipStream_t st = (hipStream_t)stream;
   const size_t n = (size_t)B * h->M * T;
   BSG_REQUIRE(h->xpred, "plms_sample: history buffers missing (bsg_diffnet_prepare allocates them)");
+  TRY(ragged_enter(h, st, "plms_sample"));
+  RaggedScope ragged_scope(h);
   TRY(cond_layout_for(h, B, T, st));
   const dim3 grid(cdiv((long long)n, 256)), block(256);
+  // the unfused update (first iteration); ragged: on each row's own frames only
+  auto plms_step = [&](const float* xi, float* xo, const float* e0, const float* e1, const float* e2, const float* e3, const PlmsCoef& k) {
+    if (h->rg_active)
+      hipLaunchKernelGGL(plms_step_ragged_kernel, dim3(cdiv(T, 256), h->M, B), dim3(256), 0, st, xi, xo, e0, e1, e2, e3, k, (const int*)h->rg_dev, h->M, T);
+    else
+      hipLaunchKernelGGL(plms_step_kernel, grid, block, 0, st, xi, xo, e0, e1, e2, e3, k, (long long)n);
+  };
   const bool fused = fused_tail_ok(h);
   // history ring: hist[0] = newest
   float* hist[4] = {h->eps_hist[0], h->eps_hist[1], h->eps_hist[2], h->eps_hist[3]};
@@ -2569,7 +2706,10 @@ extern "C" int bsg_plms_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
     if (n_hist > 0 && fused) {
       // fused iteration: h->xa already holds the in-projection of x (left by the previous iteration); the tail projects the skip
       // sum to eps, stores it to the history slot, applies the multistep update to x and projects the new x for the next one
-      if (n_sub == 0) n_sub = dual_fork(h, B, T, st, subs);   // the first fused iteration forks the two half-batch chains
+      if (n_sub == 0) {   // the first fused iteration forks the two half-batch chains (not for a ragged batch: one chain of its launch groups)
+        if (h->rg_active) { subs[0] = SubBatch{0, B, st}; n_sub = 1; }
+        else n_sub = dual_fork(h, B, T, st, subs);
+      }
       for (int u = 0; u < n_sub && rc == BSG_OK; ++u) {
         const size_t mo = (size_t)subs[u].off * h->M * T;
         h->row_off = subs[u].off;
@@ -2589,24 +2729,27 @@ extern "C" int bsg_plms_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
     TRY(forward_impl(h, x, nullptr, i, e_new, B, T, st));
     if (n_hist == 0) {
       c.inv = 1.f;
-      hipLaunchKernelGGL(plms_step_kernel, grid, block, 0, st, (const float*)x, h->xpred, (const float*)e_new,
-                         (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, c, (long long)n);
+      // ragged: the predictor below writes x_pred on each row's frames only; its padding takes x's (finite, the caller's), which the
+      // input projection of the second evaluation reads
+      if (h->rg_active) BSG_HIP(hipMemcpyAsync(h->xpred, x, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+      plms_step((const float*)x, h->xpred, (const float*)e_new,
+                         (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, c);
       TRY(forward_impl(h, h->xpred, nullptr, ip, h->eps, B, T, st));
       c.w0 = 1.f; c.inv = 2.f;
-      hipLaunchKernelGGL(plms_step_kernel, grid, block, 0, st, (const float*)x, x, (const float*)e_new, (const float*)h->eps,
-                         (const float*)nullptr, (const float*)nullptr, c, (long long)n);
+      plms_step((const float*)x, x, (const float*)e_new, (const float*)h->eps,
+                         (const float*)nullptr, (const float*)nullptr, c);
     } else if (n_hist == 1) {
       c.w0 = 3.f; c.inv = 2.f;
-      hipLaunchKernelGGL(plms_step_kernel, grid, block, 0, st, (const float*)x, x, (const float*)e_new, (const float*)hist[0],
-                         (const float*)nullptr, (const float*)nullptr, c, (long long)n);
+      plms_step((const float*)x, x, (const float*)e_new, (const float*)hist[0],
+                         (const float*)nullptr, (const float*)nullptr, c);
     } else if (n_hist == 2) {
       c.w0 = 23.f; c.w1 = -16.f; c.w2 = 5.f; c.inv = 12.f;
-      hipLaunchKernelGGL(plms_step_kernel, grid, block, 0, st, (const float*)x, x, (const float*)e_new, (const float*)hist[0],
-                         (const float*)hist[1], (const float*)nullptr, c, (long long)n);
+      plms_step((const float*)x, x, (const float*)e_new, (const float*)hist[0],
+                         (const float*)hist[1], (const float*)nullptr, c);
     } else {
       c.w0 = 55.f; c.w1 = -59.f; c.w2 = 37.f; c.w3 = -9.f; c.inv = 24.f;
-      hipLaunchKernelGGL(plms_step_kernel, grid, block, 0, st, (const float*)x, x, (const float*)e_new, (const float*)hist[0],
-                         (const float*)hist[1], (const float*)hist[2], c, (long long)n);
+      plms_step((const float*)x, x, (const float*)e_new, (const float*)hist[0],
+                         (const float*)hist[1], (const float*)hist[2], c);
     }
     BSG_LAUNCH_CHECK();
     if (fused && i - interval >= 0) TRY(conv1x1(h->w_in, h->b_in, x, h->xa, C, h->M, B, T, ACT_RELU, st));   // for the fused iterations
@@ -2637,6 +2780,90 @@ extern "C" int bsg_plms_step(const float* x, float* x_out, const float* e0, cons
   hipLaunchKernelGGL(plms_step_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, x, x_out, e0, n_hist >= 1 ? e1 : nullptr,
                      n_hist >= 2 ? e2 : nullptr, n_hist >= 3 ? e3 : nullptr, c, (long long)n);
   BSG_LAUNCH_CHECK();
+  return BSG_OK;
+}
+
+// ---- ragged batches (ABI v8) -----------------------------------------------------------------------------------------------------
+// First-fit decreasing of whole rows (ceil(len / tile_frames) tiles each) into launch groups of at most `cus` tiles: rows by tile count,
+// longest first (ties: lower row first), each into the first group it fits.  A group's tiles run as one launch; the groups one after another.
+extern "C" int bsg_ragged_plan(const int32_t* lens, int32_t B, int32_t tile_frames, int32_t cus, int32_t* group_of_row, int32_t* n_groups) {
+  BSG_REQUIRE(lens && group_of_row && n_groups && B > 0 && tile_frames > 0 && cus > 0, "ragged_plan: bad argument");
+  std::vector<int> order(B), tiles(B);
+  for (int b = 0; b < B; ++b) {
+    BSG_REQUIRE(lens[b] > 0, "ragged_plan: row %d has %d frames", b, lens[b]);
+    tiles[b] = cdiv(lens[b], tile_frames);
+    BSG_REQUIRE(tiles[b] <= cus, "ragged_plan: row %d of %d frames takes %d tiles of %d frames; a launch group holds %d (one per CU)", b, lens[b],
+                tiles[b], tile_frames, cus);
+    order[b] = b;
+  }
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return tiles[a] > tiles[b]; });
+  std::vector<int> fill;
+  for (int b : order) {
+    size_t g = 0;
+    while (g < fill.size() && fill[g] + tiles[b] > cus) ++g;
+    if (g == fill.size()) fill.push_back(0);
+    fill[g] += tiles[b];
+    group_of_row[b] = (int32_t)g;
+  }
+  *n_groups = (int32_t)fill.size();
+  return BSG_OK;
+}
+
+extern "C" int bsg_diffnet_prepare_ragged(bsg_diffnet* h, const float* cond, const int32_t* lens, int32_t B, int32_t T, void* stream) {
+  BSG_REQUIRE(h && cond && lens, "diffnet_prepare_ragged: null argument");
+  BSG_REQUIRE(B > 0 && T > 0, "diffnet_prepare_ragged: B=%d T=%d", B, T);
+  hipStream_t st = (hipStream_t)stream;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (st) (void)hipStreamIsCapturing(st, &cap);
+  if (cap != hipStreamCaptureStatusNone) {
+    set_error("diffnet_prepare_ragged: a ragged batch cannot be bound or decoded under stream capture");
+    return BSG_ESTATE;
+  }
+  if (h->compute != BSG_COMPUTE_F32) {
+    set_error("diffnet_prepare_ragged: ragged batches need the fp32 configuration (the bf16 one, bsg_diffnet_set_compute BF16, has no ragged launch)");
+    return BSG_ESTATE;
+  }
+  for (int b = 0; b < B; ++b) BSG_REQUIRE(lens[b] >= 1 && lens[b] <= T, "diffnet_prepare_ragged: row %d has %d frames (1..T=%d)", b, lens[b], T);
+  if (!h->num_cus) {
+    int dev = 0;
+    BSG_HIP(hipGetDevice(&dev));
+    BSG_HIP(hipDeviceGetAttribute(&h->num_cus, hipDeviceAttributeMultiprocessorCount, dev));
+  }
+  std::vector<int32_t> grp(B);
+  int32_t ng = 0;
+  TRY(bsg_ragged_plan(lens, B, 64, h->num_cus, grp.data(), &ng));
+  TRY(bsg_diffnet_prepare(h, cond, B, T, stream));
+  // [lengths, padded to an even count][tables]: group after group, each row's tiles contiguous and in order
+  const int bpad = (B + 1) & ~1;
+  std::vector<int> host(bpad, 0);
+  for (int b = 0; b < B; ++b) host[b] = lens[b];
+  h->rg_group_off.assign(ng, 0);
+  h->rg_group_tiles.assign(ng, 0);
+  int off = 0;
+  for (int g = 0; g < ng; ++g) {
+    h->rg_group_off[g] = off;
+    for (int b = 0; b < B; ++b) {
+      if (grp[b] != g) continue;
+      for (int j = 0; j < cdiv(lens[b], 64); ++j) { host.push_back(b); host.push_back(j); ++off; }
+    }
+    h->rg_group_tiles[g] = off - h->rg_group_off[g];
+  }
+  BSG_HIP(hipStreamSynchronize(st));   // (the previous binding's tables may still be read by launches in flight)
+  if (host.size() > h->rg_cap) {
+    if (h->rg_dev) (void)hipFree(h->rg_dev);
+    h->rg_dev = nullptr;
+    h->rg_cap = 0;
+    BSG_HIP(hipMalloc((void**)&h->rg_dev, host.size() * sizeof(int)));
+    h->rg_cap = host.size();
+  }
+  BSG_HIP(hipMemcpy(h->rg_dev, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice));
+  h->ragged = true;
+  return BSG_OK;
+}
+
+extern "C" int bsg_diffnet_ragged_native(bsg_diffnet* h, int32_t B, int32_t T, int32_t* native) {
+  BSG_REQUIRE(h && native, "diffnet_ragged_native: null argument");
+  *native = h->ragged && h->B == B && h->T == T && ragged_launch_ok(h) ? 1 : 0;
   return BSG_OK;
 }
 

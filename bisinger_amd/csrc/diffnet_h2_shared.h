@@ -104,7 +104,8 @@ __device__ __forceinline__ void tail_gemm_h2(f32x16 (&c)[NC], rsrc_t rs, int vfr
 // of x (DDPM or PLMS), and the next evaluation's input projection (net.py:126-129, shallow_diffusion_tts.py:149-201).  32-row matrix tiles
 // over NCT column tiles of 32 frames whatever the layout of the launch's layer loop was: everything it reads is in LDS or HBM.
 template <int NCT>
-__device__ __forceinline__ void h2_fused_tail(const TailArgs& a, unsigned* status, char* xs, char* zs, int b, int t0, int T, int L, int tid, int wave,
+// T is the row stride of every [B][.][T] tensor, Tl the row's frame count (T but in a ragged launch): frames at or beyond Tl are not stored
+__device__ __forceinline__ void h2_fused_tail(const TailArgs& a, unsigned* status, char* xs, char* zs, int b, int t0, int T, int Tl, int L, int tid, int wave,
                                               int& range_flag) {
   constexpr int NT = 32 * NCT, XP = h2_xp(NCT), ZP = h2_zp(NCT);
   const int lane = tid & 63, l31 = lane & 31, lh = lane >> 5;
@@ -115,7 +116,7 @@ __device__ __forceinline__ void h2_fused_tail(const TailArgs& a, unsigned* statu
 #pragma unroll
   for (int ct = 0; ct < NCT; ++ct) {
     const int col = t0 + 32 * ct + l31;
-    col_ok[ct] = col < T;
+    col_ok[ct] = col < Tl;
     vst[ct] = (lh * 4 * T + col) * 4;
   }
   auto range_check = [&](unsigned worst) {
@@ -190,8 +191,8 @@ __device__ __forceinline__ void h2_fused_tail(const TailArgs& a, unsigned* statu
   if (wave < 3 * NCT) {
     const int rt = wave % 3, ct2 = wave / 3;
     const int col = t0 + 32 * ct2 + l31;
-    const bool cok = col < T;
-    const int vc = (lh * 4 * T + (cok ? col : T - 1)) * 4, vs = (lh * 4 * T + col) * 4;
+    const bool cok = col < Tl;
+    const int vc = (lh * 4 * T + (cok ? col : Tl - 1)) * 4, vs = (lh * 4 * T + col) * 4;
     const rsrc_t rs_wo = mk_rsrc(a.wo_s, 2 * 96 * C * 2);
     const rsrc_t rs_bf = mk_rsrc(a.b_fin, 96 * 4);
     const rsrc_t rs_xx = mk_rsrc(a.x + (long long)b * M * T, (unsigned)M * T * 4);
@@ -242,7 +243,7 @@ __device__ __forceinline__ void h2_fused_tail(const TailArgs& a, unsigned* statu
           float nz = nv[r];
           if (lds_noise) nz = *reinterpret_cast<const float*>(xs + (HALO + 32 * ct2 + l31) * ROWB + 192 + 4 * m);
           else if (!a.noise && a.k.sigma != 0.f)
-            nz = philox_normal1(a.seed, a.stream, a.quad_row0 + ((unsigned long long)b * M + m) * T + (cok ? col : T - 1));
+            nz = philox_normal1(a.seed, a.stream, a.quad_row0 + ((unsigned long long)b * M + m) * T + (cok ? col : Tl - 1));
           float x0 = __fsub_rn(__fmul_rn(a.k.recip, xv[r]), __fmul_rn(a.k.recipm1, ev));
           x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
           const float mean = __fadd_rn(__fmul_rn(a.k.pc1, x0), __fmul_rn(a.k.pc2, xv[r]));

@@ -163,8 +163,17 @@ __device__ __forceinline__ void mfma_pipe_q(f32x4q (&c)[4][NQ], f16x8 (&A)[NS][8
   }
 }
 
+// DIAG = Q_VARLEN: not a timing experiment but the RAGGED form (bsg_diffnet_prepare_ragged), arithmetic as DIAG = 0.  (A parameter of its
+// own would rename every instantiation, and a shared __forceinline__ body under two kernels measurably changed the register allocation of
+// the existing ones; as a value of DIAG the product instantiations compile exactly as before.)  A workgroup takes its (row, column tile)
+// from the launch's tile table p.vl_tiles — a row's tiles are contiguous there, so the neighbours stay at tile_id -/+ 1 — and the row's own
+// frame count p.vl_len[b] is the boundary wherever T was one (right neighbour, stored columns, halo, the right-end mask of the step term,
+// the tail).  T stays the row stride.
+constexpr int Q_VARLEN = 7;
+
 template <bool FAIRB, bool TAIL, int NCT, int DIAG = 0, int NS = 2>
 __global__ __launch_bounds__(512, 2) void residual_stack_q_kernel(StackArgs p, TailArgs a) {
+  constexpr bool VARLEN = DIAG == Q_VARLEN;
   constexpr int NT = 32 * NCT, NQ = 2 * NCT, XP = h2_xp(NCT), ZP = h2_zp(NCT);   // frames / column tiles of 16 per workgroup; bytes per plane
   extern __shared__ __attribute__((aligned(16))) char lds_raw[];
   char* xs = lds_raw;                  // [2 planes][NT + 16 frames][528 B]: hi / lo of x + d_l, frames t0-8 .. t0+NT+7
@@ -180,10 +189,20 @@ __global__ __launch_bounds__(512, 2) void residual_stack_q_kernel(StackArgs p, T
   const int n16 = lane & 15, q4 = lane >> 4;
   auto fo = [](int ct) { return 16 * ct; };   // frame of column tile ct, column n16: fo(ct) + n16
   const int tpr = p.tiles_per_row, L = p.L, T = p.T;
-  const int b = tile_id / tpr, j = tile_id - b * tpr;
+  int b, j, Tl = T, tprl = tpr;   // Tl: frames of this row (the boundary); tprl: its tiles
+  if constexpr (VARLEN) {
+    const int2 e = p.vl_tiles[tile_id];
+    b = e.x;
+    j = e.y;
+    Tl = p.vl_len[b];
+    tprl = (Tl + NT - 1) / NT;
+  } else {
+    b = tile_id / tpr;
+    j = tile_id - b * tpr;
+  }
   const int t0 = j * NT;
   const int tb = p.t_dev ? (int)p.t_dev[b] : p.t_uniform;
-  const bool has_left = j > 0, has_right = j + 1 < tpr;
+  const bool has_left = j > 0, has_right = j + 1 < tprl;
 
   const unsigned plane = (unsigned)C * T * 4;
   const rsrc_t rs_x = mk_rsrc(p.x_in + (long long)b * C * T, plane);
@@ -195,7 +214,7 @@ __global__ __launch_bounds__(512, 2) void residual_stack_q_kernel(StackArgs p, T
   const int col0 = t0 + n16;
   const int vbase = (q4 * 4 * T + col0) * 4;       // fp32 [rows][T]: row q4 * 4 (+ the uniform row offset), frame col0
   const int vqbase = (q4 * T + col0) * 16;         // channel-quad order [rows / 4][T][4]: quad q4, frame col0
-  auto col_ok = [&](int ct) { return col0 + 16 * ct < T; };
+  auto col_ok = [&](int ct) { return col0 + 16 * ct < Tl; };
   auto vcol = [&](int ct) { return vbase + 64 * ct; };
   auto vquad = [&](int ct) { return vqbase + 256 * ct; };
   // row tiles (of 16) inside a plane of a k-step slab: gate / residual rows 2w, 2w + 1; filter / skip rows 16 + 2w, 17 + 2w
@@ -267,7 +286,7 @@ __global__ __launch_bounds__(512, 2) void residual_stack_q_kernel(StackArgs p, T
   // lack a tap (the reference pads x + d with zeros): its D_0 / D_2 is taken out again where the accumulators are initialised, fetched THERE —
   // one exposed L2 round trip per layer on two tiles of a row; requested early like dA, its 16 registers were live on every tile from the
   // image phase to the next layer's top and put 30 spilled registers back into the layer loop (164.5 k against 175.8 k mel-frames/s)
-  const bool first_tile = !has_left, last_tile = t0 + NT + HALO > T;   // (a tile whose right neighbour holds fewer frames than a dilation lacks right taps too)
+  const bool first_tile = !has_left, last_tile = t0 + NT + HALO > Tl;   // (a tile whose right neighbour holds fewer frames than a dilation lacks right taps too)
   f32x4 dA[4];   // [2 half + rt]
   auto dconv_request = [&](int l) {
     const rsrc_t rs_d = mk_rsrc(p.dconv + ((long long)tb * L + l) * (4 * 2 * C), 4 * 2 * C * 4);
@@ -300,7 +319,7 @@ __global__ __launch_bounds__(512, 2) void residual_stack_q_kernel(StackArgs p, T
 #pragma unroll
             for (int ct = 0; ct < NQ; ++ct) {
               const int f = col0 + 16 * ct;
-              const float m = (side == 0 ? f < dil : f + dil >= T) ? -s1 : 0.f;
+              const float m = (side == 0 ? f < dil : f + dil >= Tl) ? -s1 : 0.f;
 #pragma unroll
               for (int i = 0; i < 4; ++i) y[2 * h + rt][ct][i] = __builtin_fmaf(m, de[i], y[2 * h + rt][ct][i]);
             }
@@ -311,7 +330,7 @@ __global__ __launch_bounds__(512, 2) void residual_stack_q_kernel(StackArgs p, T
   // image core (frames t0 .. t0+NT-1, this wave's 32 channels) = hi / lo of x, zero beyond T (the conv pads with zeros)
   // xr16 = 16 x (the caller folds the factor into the product that forms x); a tile whose 64 frames all lie inside the utterance — all but the
   // last of a row — skips the masks of the frames beyond T
-  const bool all_cols = t0 + NT <= T;   // (wave-uniform)
+  const bool all_cols = t0 + NT <= Tl;   // (wave-uniform)
   auto write_core = [&](const float (&xr16)[NQ][2][4]) {
     unsigned worst = 0;
 #pragma unroll
@@ -348,7 +367,7 @@ __global__ __launch_bounds__(512, 2) void residual_stack_q_kernel(StackArgs p, T
     const int hf = tid & 15, hc = tid >> 4;   // 16 halo frames x 32 chunks of 8 channels
     const int th = hf < 8 ? t0 - HALO + hf : t0 + NT - 8 + hf;
     const int hrow = hf < 8 ? hf : NT + hf;
-    const bool hok = th >= 0 && th < T;
+    const bool hok = th >= 0 && th < Tl;
     float hv[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) hv[k] = XSCALE * ldf(rs_x, hok ? ((8 * hc + k) * T + th) * 4 : 0, 0);
@@ -618,12 +637,18 @@ __global__ __launch_bounds__(512, 2) void residual_stack_q_kernel(StackArgs p, T
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt) {
           const HiLo s0 = split2(sk[ct][rt][0] * rdiv, sk[ct][rt][1] * rdiv), s1_ = split2(sk[ct][rt][2] * rdiv, sk[ct][rt][3] * rdiv);
+          u32x2 wh = u32x2{s0.hi, s1_.hi}, wl = u32x2{s0.lo, s1_.lo};
+          // ragged: the frames of the row's padding hold whatever the caller's condition had there — zero rows, so that the tail's
+          // projections of those (never stored) frames stay finite and raise no range event
+          if constexpr (VARLEN) {
+            if (!all_cols && !col_ok(ct)) { wh = u32x2{0u, 0u}; wl = u32x2{0u, 0u}; }
+          }
           char* dst = xs + (HALO + n16 + fo(ct)) * ROWB + (cw + 16 * rt) * 2;
-          *reinterpret_cast<u32x2*>(dst) = u32x2{s0.hi, s1_.hi};
-          *reinterpret_cast<u32x2*>(dst + XP) = u32x2{s0.lo, s1_.lo};
+          *reinterpret_cast<u32x2*>(dst) = wh;
+          *reinterpret_cast<u32x2*>(dst + XP) = wl;
         }
     }
-    h2_fused_tail<NCT>(a, p.status, xs, zs, b, t0, T, L, tid, wave, range_flag);
+    h2_fused_tail<NCT>(a, p.status, xs, zs, b, t0, T, Tl, L, tid, wave, range_flag);
   }
 }
 #undef BSG_MFMA_Q
@@ -696,9 +721,41 @@ static int h2q_launch(const StackArgs& p, const TailArgs* tail, hipStream_t st) 
   return BSG_OK;
 }
 
+// the ragged form (p.vl_tiles set): 64-frame tiles, time-sliced issue priority (the default form's arithmetic, whatever BSG_H2Q_FAIR says)
+static int h2q_launch_varlen(const StackArgs& p, const TailArgs* tail, hipStream_t st) {
+  const dim3 grid(8 * cdiv(p.n_tiles, 8)), block(512);
+  const TailArgs a = tail ? *tail : TailArgs{};
+  const size_t lds = h2_lds(2);
+  static bool attr = false;
+  if (!attr) {
+    BSG_HIP(hipFuncSetAttribute((const void*)residual_stack_q_kernel<true, false, 2, Q_VARLEN, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    BSG_HIP(hipFuncSetAttribute((const void*)residual_stack_q_kernel<true, true, 2, Q_VARLEN, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    attr = true;
+  }
+  if (tail) hipLaunchKernelGGL((residual_stack_q_kernel<true, true, 2, Q_VARLEN, 2>), grid, block, lds, st, p, a);
+  else hipLaunchKernelGGL((residual_stack_q_kernel<true, false, 2, Q_VARLEN, 2>), grid, block, lds, st, p, a);
+  BSG_LAUNCH_CHECK();
+  return BSG_OK;
+}
+
+// resident workgroups per CU (0 on error) of the ragged form
+int stack_h2q_varlen_occupancy() {
+  int o = 0;
+  const int lds = (int)h2_lds(2);
+  if (hipFuncSetAttribute((const void*)residual_stack_q_kernel<true, false, 2, Q_VARLEN, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
+      hipFuncSetAttribute((const void*)residual_stack_q_kernel<true, true, 2, Q_VARLEN, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, (const void*)residual_stack_q_kernel<true, true, 2, Q_VARLEN, 2>, 512, lds) != hipSuccess)
+    return 0;
+  return o;
+}
+
 // the arguments of launch_residual_stack_h2 (diffnet_h2.hip); p.apack1q / p.apack2q must hold the 16-row weight fragments
 int launch_residual_stack_h2q(const StackArgs& p, const TailArgs* tail, hipStream_t st, int nct) {
   BSG_REQUIRE(p.apack1q && p.apack2q && p.dconv, "16-row stack launch: the 16-row weight fragments / the step-term table are missing");
+  if (p.vl_tiles) {
+    BSG_REQUIRE(nct == 2 && p.vl_len, "16-row stack launch: the ragged form takes 64-frame tiles and the row lengths");
+    return h2q_launch_varlen(p, tail, st);
+  }
   const int ns = ring_depth(nct);
   if (nct == 1) return ns == 2 ? h2q_launch<1, 2>(p, tail, st) : h2q_launch<1, NS_DEEP_32>(p, tail, st);
   return ns == 2 ? h2q_launch<2, 2>(p, tail, st) : h2q_launch<2, NS_DEEP_64>(p, tail, st);

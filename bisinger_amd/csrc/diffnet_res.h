@@ -81,6 +81,9 @@ struct StackArgs {
   unsigned* pflags;       // [2][n_tiles][P parts]: [0] image flags (layers prepared), [1] z flags
   unsigned long long* stamps;   // diagnostic (bsg_diffnet_debug_stack_stamps) or null: [n_tiles][L][8] s_memrealtime at the phase boundaries
   unsigned long long* clk;      // null, or [4]: tile 0 stores s_memtime / s_memrealtime at its start and end (sustained shader clock, bench.py)
+  // ragged launch (residual_stack_q_kernel<.., VARLEN = true>, bsg_diffnet_prepare_ragged); null otherwise
+  const int2* vl_tiles;   // [n_tiles] {row of the bound batch, column tile in the row}: each row's tiles contiguous, in order
+  const int* vl_len;      // [B] frames of every row of the bound batch (<= T, the row stride)
 };
 
 // Launch epoch in device memory (StackArgs::epoch): taken at entry by every workgroup ...
@@ -112,6 +115,7 @@ int stack_bf16_occupancy();   // resident workgroups per CU of residual_stack_bf
 // workgroup per CU; grid = p.n_tiles rounded up to 8
 int stack_h2_occupancy(int nct);   // nct = column tiles of 32 frames per workgroup (1 or 2)
 int stack_h2q_occupancy(int nct);  // the 16-row-tile form of the same launch (diffnet_h2q.hip)
+int stack_h2q_varlen_occupancy();   // its ragged form (64-frame tiles; resident workgroups per CU, 0 on error)
 // part forms on 16-row matrix tiles: `parts` workgroups (on as many CUs of one XCD) per tile of 32 nct frames, each C / parts channels:
 // (4, 1) quad of a 32-frame tile, (4, 2) quad of a 64-frame tile, (2, 2) pair of a 64-frame tile (8 waves); p.n_tiles tiles -> grid of 8 parts ceil(n_tiles / 8) workgroups, all resident
 int launch_residual_part_h2(const StackArgs& p, hipStream_t st, int parts, int nct);

@@ -7,7 +7,7 @@ The modules below only *hold* parameters; all arithmetic happens in libbisinger_
 (csrc/diffnet.hip) through the C ABI of include/bisinger_hip.h.  No CPU/eager fallback exists.
 """
 import math
-from ctypes import POINTER, byref, c_void_p, cast
+from ctypes import POINTER, byref, c_int32, c_void_p, cast
 
 import torch
 import torch.nn as nn
@@ -79,6 +79,7 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         self._h = None
         self._h_key = None
         self._bound = None
+        self._lengths = None     # row lengths of a ragged binding (prepare(cond, lengths))
 
     # ------------------------------------------------------------------ handle management
     def handle(self):
@@ -148,8 +149,10 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         except Exception:
             pass
 
-    def prepare(self, cond):
-        """Bind ``cond`` [B,H,T]: hoists every layer's conditioner projection out of the step loop."""
+    def prepare(self, cond, lengths=None):
+        """Bind ``cond`` [B,H,T]: hoists every layer's conditioner projection out of the step loop.
+        ``lengths`` (B ints, 1..T): a ragged batch — the calls that follow decode row b on its first lengths[b] frames only, as if it were
+        alone at T = lengths[b] (include/bisinger_hip.h bsg_diffnet_prepare_ragged; INTEGRATION.md "Ragged batches")."""
         h = self.handle()
         # a range event of a split-fp16 launch was a property of the condition bound then: with another condition the handle tries the faster
         # launch again — unless this is the repeated pass of an outer guarded call (GaussianDiffusion.forward recomputes cond: a NEW tensor with
@@ -165,37 +168,78 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         cond = cond.contiguous().float()
         B, H, T = cond.shape
         assert H == self.encoder_hidden
+        lens = None if lengths is None else ragged_lens(lengths, B, T)
         with torch.cuda.device(cond.device):
-            _lib.check(_lib.load().bsg_diffnet_prepare(h, _lib.ptr(cond), B, T, _lib.stream_ptr()), 'bsg_diffnet_prepare')
+            if lens is None:
+                _lib.check(_lib.load().bsg_diffnet_prepare(h, _lib.ptr(cond), B, T, _lib.stream_ptr()), 'bsg_diffnet_prepare')
+            else:
+                _lib.check(_lib.load().bsg_diffnet_prepare_ragged(h, _lib.ptr(cond), (c_int32 * B)(*lens), B, T, _lib.stream_ptr()),
+                           'bsg_diffnet_prepare_ragged')
         self._bound = (cond, cond._version, B, T)      # strong reference: the allocator cannot hand this address to another tensor
+        self._lengths = lens
         return B, T
 
-    def _ensure_bound(self, cond):
-        """Skip the hoisted conditioner work only when ``cond`` IS the tensor bound last (same object, not modified since).
-        Keying on the address would be wrong: the caching allocator gives a freed block to the next same-size tensor."""
+    def _ensure_bound(self, cond, lengths=None):
+        """Skip the hoisted conditioner work only when ``cond`` IS the tensor bound last (same object, not modified since) with the same
+        row lengths.  Keying on the address would be wrong: the caching allocator gives a freed block to the next same-size tensor."""
         b = self._bound
+        lens = None if lengths is None else ragged_lens(lengths, cond.shape[0], cond.shape[2])
         if (self._h is None or self._key() != self._h_key or b is None or b[0] is not cond or b[1] != cond._version
-                or not cond.is_contiguous() or cond.dtype != torch.float32):
-            self.prepare(cond)
+                or not cond.is_contiguous() or cond.dtype != torch.float32 or getattr(self, '_lengths', None) != lens):
+            self.prepare(cond, lengths)
             if cond.is_contiguous() and cond.dtype == torch.float32:
                 self._bound = (cond, cond._version, cond.shape[0], cond.shape[2])
 
     # ------------------------------------------------------------------ reference call contract
     @torch.no_grad()
-    def forward(self, spec, diffusion_step, cond):
-        """spec [B,1,M,T], diffusion_step [B] int64, cond [B,H,T] -> [B,1,M,T]   (net.py:107-130)."""
+    def forward(self, spec, diffusion_step, cond, lengths=None):
+        """spec [B,1,M,T], diffusion_step [B] int64, cond [B,H,T] -> [B,1,M,T]   (net.py:107-130).
+        ``lengths`` (B ints): a ragged batch (prepare()): row b's eps on frames < lengths[b] is the row's alone at T = lengths[b]; 0 beyond."""
         B, _, M, T = spec.shape
-        self._ensure_bound(cond)
+        self._ensure_bound(cond, lengths)
         x = spec[:, 0].contiguous().float()
         t = diffusion_step.to(device=x.device, dtype=torch.long).contiguous()
         eps = torch.empty_like(x)
+        lens = self._lengths
 
         def run():
             with torch.cuda.device(x.device):
-                _lib.check(_lib.load().bsg_diffnet_forward(self._h, _lib.ptr(x), _lib.ptr(t), _lib.ptr(eps), B, T,
-                                                           _lib.stream_ptr()), 'bsg_diffnet_forward')
+                if lens is None or self.ragged_native(B, T):
+                    _lib.check(_lib.load().bsg_diffnet_forward(self._h, _lib.ptr(x), _lib.ptr(t), _lib.ptr(eps), B, T,
+                                                               _lib.stream_ptr()), 'bsg_diffnet_forward')
+                    return
+
+                def one(b, n):
+                    xb, tb = x[b:b + 1, :, :n].contiguous(), t[b:b + 1].contiguous()
+                    eb = torch.empty_like(xb)
+                    _lib.check(_lib.load().bsg_diffnet_forward(self._h, _lib.ptr(xb), _lib.ptr(tb), _lib.ptr(eb), 1, n,
+                                                               _lib.stream_ptr()), 'bsg_diffnet_forward')
+                    eps[b, :, :n] = eb[0]
+                    eps[b, :, n:] = 0
+                self.rows_one_by_one(one)
         self.guarded(run, B, T)
         return eps[:, None, :, :]
+
+    # ------------------------------------------------------------------ ragged batches
+    def ragged_native(self, B, T):
+        """True when the handle's current state decodes the bound ragged (B, T) batch with the ragged launch (bsg_diffnet_ragged_native):
+        not after a demotion off the 16-row stack launch (range event, give-up), not in the bf16 configuration."""
+        n = c_int32()
+        _lib.check(_lib.load().bsg_diffnet_ragged_native(self._h, B, T, byref(n)), 'bsg_diffnet_ragged_native')
+        return bool(n.value)
+
+    def rows_one_by_one(self, one):
+        """The fallback of a ragged call without the ragged launch: ``one(b, n)`` for every row, with row b's condition alone bound at
+        T = n = lengths[b] through the plain launches; the ragged binding is restored behind the last row."""
+        cond, lens = self._bound[0], self._lengths
+        lib = _lib.load()
+        B, _, T = cond.shape
+        for b, n in enumerate(lens):
+            cb = cond[b:b + 1, :, :n].contiguous()
+            _lib.check(lib.bsg_diffnet_prepare(self._h, _lib.ptr(cb), 1, n, _lib.stream_ptr()), 'bsg_diffnet_prepare')
+            one(b, n)
+        _lib.check(lib.bsg_diffnet_prepare_ragged(self._h, _lib.ptr(cond), (c_int32 * B)(*lens), B, T, _lib.stream_ptr()),
+                   'bsg_diffnet_prepare_ragged')
 
     # ------------------------------------------------------------------ hand-off health, checked in the SAME call
     def uses_handoffs(self, B, T):
@@ -253,7 +297,7 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
 
         def again():
             if self._bound is not None:
-                self.prepare(self._bound[0])
+                self.prepare(self._bound[0], getattr(self, '_lengths', None))
             if restore is not None:
                 restore()
         _lib.range_guarded(lambda: self._guarded_handoffs(run, B, T, restore), 'DiffNet', on_retry=again, device=self, owners=(self,))
@@ -465,6 +509,30 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
                                                               _lib.ptr(skip), B, T, _lib.stream_ptr()),
                        'bsg_diffnet_residual_layer')
         return out
+
+
+def ragged_lens(lengths, B, T):
+    """``lengths`` (a sequence or a tensor of B ints) -> tuple of B Python ints in 1..T, or ValueError."""
+    lens = tuple(int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths))
+    if len(lens) != B:
+        raise ValueError(f'lengths: {len(lens)} values for a batch of {B} rows')
+    bad = [(b, n) for b, n in enumerate(lens) if not 1 <= n <= T]
+    if bad:
+        raise ValueError(f'lengths: row {bad[0][0]} has {bad[0][1]} frames (1..T={T})')
+    return lens
+
+
+def ragged_plan(lengths, cus, tile_frames=64):
+    """The packing of a ragged batch (bsg_ragged_plan, the one its launch uses): -> (launch group of every row, number of groups).  Whole
+    rows of ceil(len / tile_frames) tiles, first-fit decreasing into groups of at most ``cus`` tiles.  Host only; ValueError for a row that
+    does not fit one group."""
+    lens = [int(v) for v in lengths]
+    B = len(lens)
+    grp, n = (c_int32 * max(B, 1))(), c_int32()
+    rc = _lib.load().bsg_ragged_plan((c_int32 * max(B, 1))(*lens), B, int(tile_frames), int(cus), grp, byref(n))
+    if rc != 0:
+        raise ValueError(_lib.load().bsg_last_error().decode())
+    return list(grp)[:B], n.value
 
 
 def _fft(hp):

@@ -39,6 +39,20 @@ def cosine_beta_schedule(timesteps, s=0.008):
 
 beta_schedule = {'cosine': cosine_beta_schedule, 'linear': linear_beta_schedule}
 
+
+def ragged_lengths(mel2ph):
+    """Frames of every row of a ragged batch: (mel2ph > 0).sum(-1) as a list of ints.  ValueError unless the non-zeros of each row are a
+    prefix (frames 0 .. len-1) and every row has at least one frame."""
+    nz = torch.as_tensor(mel2ph) > 0
+    lens = nz.sum(-1)
+    prefix = torch.arange(nz.shape[-1], device=nz.device)[None, :] < lens[:, None]
+    bad = (nz != prefix).any(-1) | (lens == 0)
+    if bool(bad.any()):
+        b = int(bad.nonzero()[0, 0])
+        raise ValueError(f'ragged batch: row {b} of mel2ph is not one run of frames from frame 0 (non-zero prefix, then zeros) '
+                         f'or has no frame; its frames cannot be decoded at their own length')
+    return [int(v) for v in lens.tolist()]
+
 _SCHED_KEYS = ('sqrt_recip_alphas_cumprod', 'sqrt_recipm1_alphas_cumprod', 'posterior_mean_coef1',
                'posterior_mean_coef2', 'alphas_cumprod')
 
@@ -104,19 +118,31 @@ class GaussianDiffusion(nn.Module):
 
     # ------------------------------------------------------------------ samplers
     @torch.no_grad()
-    def sample(self, cond, x, noise=None, seed=0, row0=0, B_total=None, n_steps=None):
-        """Run the inference loop (:258-267) from ``x`` ([B,1,M,T], modified in place) under ``cond`` [B,H,T]."""
+    def sample(self, cond, x, noise=None, seed=0, row0=0, B_total=None, n_steps=None, lengths=None):
+        """Run the inference loop (:258-267) from ``x`` ([B,1,M,T], modified in place) under ``cond`` [B,H,T].
+        ``lengths`` (B ints): a ragged batch — row b is decoded on its first lengths[b] frames as if it were alone at T = lengths[b], and x
+        beyond is left as given (INTEGRATION.md "Ragged batches").  Philox draws keep their index (global row, padded stride T), so a
+        row's frames see the draws of the padded batch; the row-by-row fallback (a handle without the ragged launch:
+        DiffNet.ragged_native) runs each row at T = lengths[b] and so draws other values — supplied ``noise`` gives the same result on
+        both paths."""
         lib = _lib.load()
         B, _, M, T = x.shape
         assert x.is_contiguous() and x.dtype == torch.float32
         if hparams.get('pndm_speedup') and (n_steps is not None or noise is not None):
             raise ValueError('sample(): the PLMS loop (pndm_speedup) is deterministic after x_T and always runs the whole '
                              'schedule; n_steps / noise only apply to the DDPM loop')
-        self.denoise_fn.prepare(cond)
+        from .diffnet import DiffNet
+        if lengths is None:
+            self.denoise_fn.prepare(cond)
+        elif not isinstance(self.denoise_fn, DiffNet):
+            raise NotImplementedError('sample(lengths=...): ragged batches need the WaveNet denoiser (DiffNet)')
+        else:
+            if self.denoise_fn.compute_dtype in ('bf16', 'bfloat16'):
+                raise _lib.BsgError('sample(lengths=...): the bf16 configuration has no ragged launch; use fp32 or padded batches')
+            self.denoise_fn.prepare(cond, lengths)
         s, _keep = self._schedule()
         h = self.denoise_fn._h
         t = self.K_step
-        from .diffnet import DiffNet
         if not isinstance(self.denoise_fn, DiffNet):
             # any other denoise_fn (DIFF_DECODERS['fft']): the reference loops (:258-267) step by step — the denoiser through its own
             # kernels, the update of x through the generic step entries (bsg_ddpm_step / bsg_plms_step)
@@ -174,7 +200,20 @@ class GaussianDiffusion(nn.Module):
 
         def run():
             with torch.cuda.device(x.device):
-                if hparams.get('pndm_speedup'):
+                if lengths is not None and not self.denoise_fn.ragged_native(B, T):
+                    # no ragged launch in the handle's state: every row alone at T = lengths[b] (Philox draws differ, see above)
+                    def one(b, nf):
+                        xb = x[b:b + 1, :, :, :nf].contiguous()
+                        if hparams.get('pndm_speedup'):
+                            _lib.check(lib.bsg_plms_sample(h, byref(s), _lib.ptr(xb), t, int(hparams['pndm_speedup']), 1, nf,
+                                                           _lib.stream_ptr()), 'bsg_plms_sample')
+                        else:
+                            nb = None if noise is None else noise[:, b:b + 1, :, :nf].contiguous()
+                            _lib.check(lib.bsg_ddpm_sample(h, byref(s), _lib.ptr(xb), _lib.ptr(nb), seed, t - 1, n, 1, nf, row0 + b,
+                                                           B if B_total is None else B_total, _lib.stream_ptr()), 'bsg_ddpm_sample')
+                        x[b:b + 1, :, :, :nf] = xb
+                    self.denoise_fn.rows_one_by_one(one)
+                elif hparams.get('pndm_speedup'):
                     _lib.check(lib.bsg_plms_sample(h, byref(s), _lib.ptr(x), t, int(hparams['pndm_speedup']), B, T,
                                                    _lib.stream_ptr()), 'bsg_plms_sample')
                 else:
@@ -217,7 +256,7 @@ class GaussianDiffusion(nn.Module):
     # ------------------------------------------------------------------ reference forward (:230-273)
     @torch.no_grad()
     def forward(self, txt_tokens, mel2ph=None, spk_embed=None, ref_mels=None, f0=None, uv=None, energy=None,
-                infer=False, noise=None, seed=None, rows=None, **kwargs):
+                infer=False, noise=None, seed=None, rows=None, ragged=False, **kwargs):
         """Extensions over the reference signature: ``noise`` (supplied draws, parity mode), ``seed`` (Philox
         key, default hparams['seed']) and ``rows`` (slice of the batch this process generates; outputs then
         have len(rows) rows and reproduce the same rows of the unsharded call — SURVEY.md §8e).
@@ -225,17 +264,21 @@ class GaussianDiffusion(nn.Module):
         4 * B * ceil(T/64) <= CUs, 32-frame tiles up to one launch group, 64-frame tiles beyond).  The 32- and 64-frame forms sum in the
         same order (sharded rows were bit-identical to the unsharded run at every shape tested, e.g. 8 of 64 rows at T=1000); the part
         forms order GEMM1's k-steps differently and add the conditioner term last (1e-6 on the mel).  ``BSG_H2_PART=0`` makes the
-        arithmetic of a row independent of the batch around it."""
+        arithmetic of a row independent of the batch around it.
+        ``ragged=True``: every row is decoded at its own length, lengths = (mel2ph > 0).sum(-1) of the given or predicted ``mel2ph``
+        (ragged_lengths: ValueError unless its non-zeros are a prefix of each row); ``mel_out`` is 0 beyond.  Not with ``rows``."""
         if not infer:
             raise NotImplementedError('training (p_losses) is outside the accelerated hot path (SURVEY.md §8)')
+        if ragged and rows is not None:
+            raise NotImplementedError('forward(ragged=True, rows=...): sharded ragged batches are not supported')
         # one range guard around the whole call (FS2, the conditioner projections, the sampler): an operand beyond the fp16 range of the
         # split-fp16 GEMMs repeats all of it with THAT handle (FS2's or the denoiser's) on the fp32 matrix pipe (_lib.range_guarded; the nested
         # guards register their handles with this one and leave the check to it)
         return _lib.range_guarded(lambda: self._forward_infer(txt_tokens, mel2ph, spk_embed, ref_mels, f0, uv, energy, noise, seed, rows,
-                                                              **kwargs), 'GaussianDiffusion.forward', device=self,
+                                                              ragged=ragged, **kwargs), 'GaussianDiffusion.forward', device=self,
                                   owners=tuple(m for m in (self.fs2, self.denoise_fn) if isinstance(m, _lib.GemmGuarded)))
 
-    def _forward_infer(self, txt_tokens, mel2ph, spk_embed, ref_mels, f0, uv, energy, noise, seed, rows, **kwargs):
+    def _forward_infer(self, txt_tokens, mel2ph, spk_embed, ref_mels, f0, uv, energy, noise, seed, rows, ragged=False, **kwargs):
         B_total = txt_tokens.shape[0]
         row0 = 0
         if rows is not None:
@@ -273,7 +316,12 @@ class GaussianDiffusion(nn.Module):
                 _lib.check(lib.bsg_mel_start(_lib.ptr(ret['mel_out'].contiguous()), _lib.ptr(smin), _lib.ptr(smax), _lib.ptr(draw0),
                                              float(self.sqrt_alphas_cumprod[t - 1]), float(self.sqrt_one_minus_alphas_cumprod[t - 1]),
                                              _lib.ptr(x), B, M, T, _lib.stream_ptr()), 'bsg_mel_start')
-        x = self.sample(cond, x, noise=None if hparams.get('pndm_speedup') else steps, seed=seed, row0=row0, B_total=B_total)
+        lengths = None
+        if ragged:
+            mel2ph = ret['mel2ph'] if mel2ph is None else mel2ph      # (the predicted one also masks mel_out below)
+            lengths = ragged_lengths(mel2ph)
+        x = self.sample(cond, x, noise=None if hparams.get('pndm_speedup') else steps, seed=seed, row0=row0, B_total=B_total,
+                        lengths=lengths)
         out = torch.empty(B, T, M, device=cond.device)
         m2p = None if mel2ph is None else mel2ph.to(device=cond.device, dtype=torch.long).contiguous()
         with torch.cuda.device(cond.device):

@@ -206,11 +206,12 @@ class DiffSingerE2EInfer(BaseSVSInfer):
             self.pe.eval()
         return model
 
-    def _generate(self, sample, seed=None):
+    def _generate(self, sample, seed=None, ragged=False):
+        kw = {'ragged': True} if ragged else {}
         with torch.no_grad():
             output = self.model(sample['txt_tokens'], spk_embed=sample.get('spk_ids'), ref_mels=None, infer=True,
                                 pitch_midi=sample['pitch_midi'], midi_dur=sample['midi_dur'], is_slur=sample['is_slur'],
-                                lang=sample['lang'], speechsing=sample['speechsing'], seed=seed)
+                                lang=sample['lang'], speechsing=sample['speechsing'], seed=seed, **kw)
         return output
 
     def forward_model(self, inp, seed=None):
@@ -233,10 +234,11 @@ class DiffSingerE2EInfer(BaseSVSInfer):
         new[1:] = (d[1:] != d[:-1]) | (p[1:] != p[:-1])
         return int(np.ceil(d[new].sum() * hparams['audio_sample_rate'] / hparams['hop_size']))
 
-    def _generate_wavs(self, items, seed):
-        """One padded batch -> (list of trimmed waveforms, frames per item, padded frame count T)."""
+    def _generate_wavs(self, items, seed, ragged=False):
+        """One padded batch -> (list of trimmed waveforms, frames per item, padded frame count T).  ``ragged``: the mel decoder runs every
+        row at its own length (GaussianDiffusion.forward(ragged=True)); the vocoder still runs the padded batch."""
         sample = self.collate(items)
-        output = self._generate(sample, seed)
+        output = self._generate(sample, seed, ragged)
         mel, mel2ph = output['mel_out'], output['mel2ph']
         hop = int(np.prod(self.vocoder.h['upsample_rates']))
         if hparams.get('use_nsf'):                                   # the shipped M4Singer set-up: PitchExtractor f0 -> NSF source
@@ -248,7 +250,7 @@ class DiffSingerE2EInfer(BaseSVSInfer):
         n_frames = (mel2ph > 0).sum(-1).tolist()
         return [wav[i, :n * hop].cpu().numpy() for i, n in enumerate(n_frames)], n_frames, int(mel.shape[1])
 
-    def forward_batch(self, items, seed=None, max_frames=None, max_sentences=None):
+    def forward_batch(self, items, seed=None, max_frames=None, max_sentences=None, ragged=False):
         """Batched generation: list of items -> list of 1-D waveforms (in the order given), each trimmed to its utterance.
 
         With ``max_frames`` (budget on padded frames per batch: rows x longest row) and/or ``max_sentences`` the items are
@@ -258,17 +260,27 @@ class DiffSingerE2EInfer(BaseSVSInfer):
 
         NB (reference quirk kept): ESM attends over the batch axis (common_layers.py:853), so a row's result depends on
         the rows it is batched with — the unit of reproducibility (and of the oracle in the tests) is the BUCKET.
-        ``self.last_batch_stats`` reports the buckets and the padded-frame waste with and without bucketing."""
+        ``self.last_batch_stats`` reports the buckets and the padded-frame waste with and without bucketing.
+
+        ``ragged=True``: buckets by ``max_sentences`` only (``max_frames`` is refused: a ragged bucket computes no padding), and the mel
+        decoder runs every row at its own length, whole rows packed into launch groups of one 64-frame tile per CU
+        (GaussianDiffusion.forward(ragged=True)); ``last_batch_stats`` adds ``launch_groups`` and ``tiles`` of those launches."""
         est = [self.estimate_frames(it) for it in items]
+        if ragged and max_frames is not None:
+            raise ValueError('forward_batch(ragged=True): buckets by max_sentences only; max_frames budgets padded frames')
         if max_frames is None and max_sentences is None:
             buckets = [list(range(len(items)))]
         else:
             buckets = bucket_by_size(est, max_frames, max_sentences)
         wavs, frames = [None] * len(items), [0] * len(items)
-        padded = 0
+        padded = groups = tiles = 0
         for b in buckets:
-            w, nf, T = self._generate_wavs([items[i] for i in b], seed)
+            w, nf, T = self._generate_wavs([items[i] for i in b], seed, ragged)
             padded += T * len(b)
+            if ragged:
+                from .diffnet import ragged_plan
+                groups += ragged_plan(nf, torch.cuda.get_device_properties(self.device).multi_processor_count)[1]
+                tiles += sum(-(-n // 64) for n in nf)
             for i, wi, ni in zip(b, w, nf):
                 wavs[i], frames[i] = wi, ni
         real = int(sum(frames))
@@ -276,6 +288,8 @@ class DiffSingerE2EInfer(BaseSVSInfer):
         self.last_batch_stats = {
             'buckets': buckets, 'estimated_frames': est, 'frames': frames, 'real_frames': real, 'padded_frames': padded,
             'waste': 1.0 - real / max(padded, 1), 'padded_frames_single_batch': one, 'waste_single_batch': 1.0 - real / max(one, 1)}
+        if ragged:
+            self.last_batch_stats.update(launch_groups=groups, tiles=tiles)
         return wavs
 
 

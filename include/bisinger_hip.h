@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define BSG_ABI_VERSION 7
+#define BSG_ABI_VERSION 8
 
 #define BSG_OK 0
 #define BSG_EINVAL (-22)  /* bad argument / shape the kernels do not support            */
@@ -78,6 +78,23 @@ int bsg_diffnet_prepare(bsg_diffnet* h, const float* cond, int32_t B, int32_t T,
 /* eps = DiffNet(x, t, cond bound by prepare).  x, eps: [B,M,T] (the reference's [B,1,M,T]); t: [B] i64. */
 int bsg_diffnet_forward(bsg_diffnet* h, const float* x, const int64_t* t, float* eps, int32_t B,
                         int32_t T, void* stream);
+
+/* ABI v8, ragged batches: every row at its own length, no padding semantics.
+ * bsg_diffnet_prepare_ragged binds cond [B,H,T] (as bsg_diffnet_prepare, which it calls) together with lens (HOST [B], 1 <= lens[b] <= T).
+ *   The bsg_diffnet_forward / bsg_ddpm_sample / bsg_plms_sample calls that follow at this (B,T) decode row b on frames [0, lens[b]) as if it
+ *   were alone at T = lens[b]: nothing of frames >= lens[b] is read by a frame below it.  T stays the row stride of x, eps, noise and cond.
+ *   eps is 0 at frames >= lens[b]; the samplers leave x there as the caller gave it.  Philox draws keep their index (global row, stride T).
+ *   Whole rows are packed into launch groups of at most one 64-frame tile per CU (bsg_ragged_plan); the groups run one after another on
+ *   `stream`.  BSG_EINVAL for a row longer than one group; BSG_ESTATE under stream capture (binding and calls) and for a bf16 handle.
+ *   A plain bsg_diffnet_prepare clears the ragged binding.
+ * bsg_diffnet_ragged_native: *native = 1 when the handle's CURRENT state has the ragged launch for the bound (B,T) — not after
+ *   bsg_diffnet_set_h2q / set_h2 / set_split(h, 0), not in the bf16 configuration.  With 0 the compute calls above return BSG_ESTATE on a
+ *   ragged binding: the caller decodes the rows one by one (bisinger_amd/diffnet.py does).
+ * bsg_ragged_plan: the packing, a pure host function (no device needed): row b of lens[b] frames takes ceil(lens[b] / tile_frames) tiles;
+ *   first-fit decreasing into groups of at most `cus` tiles; group_of_row [B] receives each row's group (0-based, launch order). */
+int bsg_diffnet_prepare_ragged(bsg_diffnet* h, const float* cond, const int32_t* lens, int32_t B, int32_t T, void* stream);
+int bsg_diffnet_ragged_native(bsg_diffnet* h, int32_t B, int32_t T, int32_t* native);
+int bsg_ragged_plan(const int32_t* lens, int32_t B, int32_t tile_frames, int32_t cus, int32_t* group_of_row, int32_t* n_groups);
 
 /* Per-layer fused residual block alone (net.py:66-78), exported for unit tests and micro-benchmarks:
  * x_in [B,C,T], t [B] -> x_out [B,C,T]; skip [B,C,T] is read-modify-written unless layer == 0
