@@ -1179,8 +1179,10 @@ struct bsg_diffnet {
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   // ragged binding (bsg_diffnet_prepare_ragged): every row of the bound (B, T) decoded at its own frame count
   bool ragged = false;                 // the bound condition came with row lengths (a plain prepare clears this)
-  bool rg_active = false;              // inside a ragged call: stack_rows / launch_stack take the ragged 16-row launch
+  bool rg_active = false;              // inside a ragged call: stack_rows / launch_stack take the ragged 16-row launch (bf16 configuration:
+                                       // stack_rows_bf16 / launch_stack_bf16 the ragged bf16 stack launch, launch_tail the ragged bf16 tail)
   int occ_stack_varlen = -1;           // resident workgroups per CU of that launch (-1: not queried)
+  int occ_stack_bf16_varlen = -1;      // the same for the ragged bf16 stack launch
   int* rg_dev = nullptr;               // [B rounded up to even] row lengths, then the tile tables {row, tile} of every launch group
   size_t rg_cap = 0;                   // ints rg_dev holds
   std::vector<int> rg_group_off;       // per launch group: offset of its table (in tiles) behind the lengths ...
@@ -1774,6 +1776,7 @@ static int launch_layer(bsg_diffnet* h, int layer, const float* x_in, const long
 // launch has more workgroups than CUs (two per CU overlap each other's waits); smaller launches keep the channel-split kernels.
 static int stack_rows(bsg_diffnet* h, int B, int T, hipStream_t st) {
   if (h->rg_active) {   // a ragged call (ragged_launch_ok checked it): the 16-row launch on 64-frame tiles, groups from the bound plan
+    if (h->compute != BSG_COMPUTE_F32) return 0;   // (the bf16 configuration: stack_rows_bf16)
     h->stack_is_f43 = false;
     h->stack_is_h2 = h->stack_q = true;
     h->stack_nct = 2;
@@ -2033,6 +2036,7 @@ static int stack_rows_bf16(bsg_diffnet* h, int B, int T, hipStream_t st) {
   if (!env || h->compute != BSG_COMPUTE_BF16 || h->split_off || !h->num_cus || !h->hx || !h->epoch_dev) return 0;
   (void)st;
   if (h->occ_stack_h < 0) h->occ_stack_h = stack_bf16_occupancy() >= 1 ? 1 : 0;
+  if (h->rg_active) return h->occ_stack_h >= 1 ? B : 0;   // a ragged call (ragged_launch_ok checked it): groups from the bound plan
   const int tpr = cdiv(T, 64);
   const long long slots = (long long)h->occ_stack_h * h->num_cus;
   if (h->occ_stack_h < 1 || tpr > slots) return 0;
@@ -2041,8 +2045,40 @@ static int stack_rows_bf16(bsg_diffnet* h, int B, int T, hipStream_t st) {
   return rows;
 }
 
+// the ragged form of the bf16 stack launch: one launch per group of the plan bound by bsg_diffnet_prepare_ragged, one after the other on
+// `st`; a workgroup finds its row and tile in the group's table, and every pointer is the bound batch's row 0
+static int launch_stack_bf16_ragged(bsg_diffnet* h, const long long* t_dev, int t_uniform, int T, hipStream_t st, unsigned long long* stamps) {
+  BSG_REQUIRE(h->ragged && h->rg_dev && h->row_off == 0, "ragged bf16 stack launch: no ragged plan bound");
+  const size_t bt = (size_t)h->B * T;
+  const int* tabs = h->rg_dev + ((h->B + 1) & ~1);
+  for (size_t g = 0; g < h->rg_group_tiles.size(); ++g) {
+    StackArgs p{};
+    p.x_in = h->xa;
+    p.skip = h->skip;
+    p.skip_h = h->skip_h;
+    p.condterm_h = h->condterm_h;
+    p.dproj = h->dproj; p.t_dev = t_dev; p.t_uniform = t_uniform;
+    p.apack1h = h->apack1h; p.apack2h = h->apack2h; p.bias_out = h->b_out;
+    p.T = T; p.L = h->L; p.tiles_per_row = cdiv(T, 64);
+    p.ct_stride = (long long)2 * C * (long long)bt;
+    p.n_tiles = h->rg_group_tiles[g]; p.cycle = h->cfg.dilation_cycle_length;
+    BSG_REQUIRE((size_t)p.n_tiles <= h->flags_cap && h->L < 64, "ragged bf16 stack launch: %d tiles exceed the exchange array (%zu)", p.n_tiles, h->flags_cap);
+    p.hx = h->hx; p.flags = h->flags; p.status = h->flags + h->flags_cap;
+    TRY(next_stack_epoch(h, p));
+    if (h->inject_giveup > 0) { p.inject = 1; --h->inject_giveup; }
+    p.stamps = stamps && g == 0 ? stamps : nullptr;
+    p.clk = h->prof_on && g == 0 ? h->clk : nullptr;
+    p.vl_len = h->rg_dev;
+    p.vl_tiles = reinterpret_cast<const int2*>(tabs) + h->rg_group_off[g];
+    TRY(launch_residual_stack_bf16(p, st));
+  }
+  h->last_path = "stack_bf16_ragged";
+  return BSG_OK;
+}
+
 static int launch_stack_bf16(bsg_diffnet* h, const long long* t_dev, int t_uniform, int B, int T, int rows_per_launch, hipStream_t st,
                              unsigned long long* stamps = nullptr) {
+  if (h->rg_active) return launch_stack_bf16_ragged(h, t_dev, t_uniform, T, st, stamps);
   const int tpr = cdiv(T, 64);
   const size_t bt = (size_t)h->B * T;
   for (int r0 = 0; r0 < B; r0 += rows_per_launch) {
@@ -2087,14 +2123,27 @@ static int check_bound(bsg_diffnet* h, int B, int T, const char* who) {
 
 static bool fused_tail_ok(const bsg_diffnet* h);
 
-// Can the handle's CURRENT state decode the bound ragged batch with the ragged launch?  Not when it was demoted off the 16-row launch
-// (bsg_diffnet_set_h2q / set_h2 / set_split 0 or the process switches BSG_H2 / BSG_H2_Q = 0), in the bf16 configuration, or without the
-// conditioner term's channel quads or the fused step tail.  (The callers then decode the rows one by one.)
+static bool bf16_tail_on(const bsg_diffnet* h);
+
+// Can the handle's CURRENT state decode the bound ragged batch with the ragged launch?  fp32 configuration: not when it was demoted off the
+// 16-row launch (bsg_diffnet_set_h2q / set_h2 / set_split 0 or the process switches BSG_H2 / BSG_H2_Q = 0), or without the conditioner
+// term's channel quads or the fused step tail.  bf16 configuration: not without the bf16 stack launch (BSG_STACK_BF16=0, set_split 0) or
+// the bf16 step tail (BSG_TAIL_BF16=0).  (The callers then decode the rows one by one.)
 static bool ragged_launch_ok(bsg_diffnet* h) {
+  if (!h->ragged) return false;
+  if (h->compute == BSG_COMPUTE_BF16) {
+    static int env_stack = -1;
+    if (env_stack < 0) { const char* e = getenv("BSG_STACK_BF16"); env_stack = e ? atoi(e) : 1; }
+    if (!env_stack || h->split_off || h->prepared_compute != BSG_COMPUTE_BF16) return false;
+    if (!h->num_cus || !h->hx || !h->epoch_dev || h->M > 96 || !bf16_tail_on(h) || !fused_tail_ok(h)) return false;
+    if (h->occ_stack_h < 0) h->occ_stack_h = stack_bf16_occupancy() >= 1 ? 1 : 0;
+    if (h->occ_stack_bf16_varlen < 0) h->occ_stack_bf16_varlen = stack_bf16_varlen_occupancy() >= 1 ? 1 : 0;
+    return h->occ_stack_h >= 1 && h->occ_stack_bf16_varlen >= 1;
+  }
   static int envh2 = -1, env_q = -1;
   if (envh2 < 0) { const char* e = getenv("BSG_H2"); envh2 = e ? atoi(e) : 1; }
   if (env_q < 0) { const char* e = getenv("BSG_H2_Q"); env_q = e ? atoi(e) : 1; }
-  if (!h->ragged || !envh2 || !env_q || h->h2_off || h->q_off || h->split_off) return false;
+  if (!envh2 || !env_q || h->h2_off || h->q_off || h->split_off) return false;
   if (h->compute != BSG_COMPUTE_F32 || h->prepared_compute != BSG_COMPUTE_F32 || !h->cond_q_valid) return false;
   if (!h->num_cus || !h->hx || !h->epoch_dev || !h->apack1q || !h->apack2q || !h->dconv || !h->tail_s || h->M > 96 || !fused_tail_ok(h)) return false;
   if (h->occ_stack_varlen < 0) h->occ_stack_varlen = stack_h2q_varlen_occupancy() >= 1 ? 1 : 0;
@@ -2237,6 +2286,12 @@ static bool fused_tail_ok(const bsg_diffnet* h) {
   return h->ws_pack != nullptr && (h->MP == 80 || h->MP == 96) && !getenv("BSG_NO_FUSED_TAIL");
 }
 
+// the bf16-operand configuration runs its step tail's projections on bf16 MFMAs (step_tail_bf16_kernel; BSG_TAIL_BF16=0: the fp32 tail)
+static bool bf16_tail_on(const bsg_diffnet* h) {
+  const char* tail_env = getenv("BSG_TAIL_BF16");
+  return h->compute == BSG_COMPUTE_BF16 && !(tail_env && atoi(tail_env) == 0) && h->tail_h;
+}
+
 // step_tail_kernel: skip projection, output projection, sampler update of x (DDPM, or PLMS when a.plms_hist > 0) and the next
 // evaluation's in-projection into h->xa; the caller fills the sampler-specific fields of `a`
 static int launch_tail(bsg_diffnet* h, TailArgs& a, float* x, int B, int T, hipStream_t st) {
@@ -2254,11 +2309,17 @@ static int launch_tail(bsg_diffnet* h, TailArgs& a, float* x, int B, int T, hipS
   a.x = x; a.xa_next = h->xa + off;
   a.ws_pack = h->ws_pack; a.wo_pack = h->wo_pack; a.wi_pack = h->wi_pack; a.b_skip = h->b_skip; a.b_fin = h->b_fin96; a.b_in = h->b_in;
   a.B = B; a.T = T; a.M = h->M; a.tiles_per_row = cdiv(T, 32);
-  const char* tail_env = getenv("BSG_TAIL_BF16");   // "0": the fp32 tail also in the bf16-operand configuration
-  if (h->compute == BSG_COMPUTE_BF16 && !(tail_env && atoi(tail_env) == 0) && h->tail_h) {   // bf16-operand configuration: the projections on bf16 MFMAs too
+  if (bf16_tail_on(h)) {   // bf16-operand configuration: the projections on bf16 MFMAs too
     a.ws_h = h->tail_h; a.wo_h = h->tail_h + C * C; a.wi_h = h->tail_h + C * C + 96 * C;
+    if (h->rg_active) {   // ragged: one launch over the tiles of every launch group's table (they follow the row lengths in rg_dev)
+      BSG_REQUIRE(h->row_off == 0 && h->rg_dev, "ragged bf16 step tail: no ragged plan bound");
+      int n_tiles = 0;
+      for (int t : h->rg_group_tiles) n_tiles += t;
+      return launch_step_tail_bf16_ragged(a, reinterpret_cast<const int2*>(h->rg_dev + ((h->B + 1) & ~1)), h->rg_dev, n_tiles, st);
+    }
     return launch_step_tail_bf16(a, st);
   }
+  BSG_REQUIRE(!h->rg_active, "step tail: a ragged call needs the bf16 tail in the bf16 configuration");
   const dim3 grid(B * a.tiles_per_row), block(512);
   if (a.plms_hist) {
     if (h->MP == 80) hipLaunchKernelGGL((step_tail_kernel<80, true>), grid, block, tail_lds, st, a);
@@ -2817,10 +2878,6 @@ extern "C" int bsg_diffnet_prepare_ragged(bsg_diffnet* h, const float* cond, con
   if (st) (void)hipStreamIsCapturing(st, &cap);
   if (cap != hipStreamCaptureStatusNone) {
     set_error("diffnet_prepare_ragged: a ragged batch cannot be bound or decoded under stream capture");
-    return BSG_ESTATE;
-  }
-  if (h->compute != BSG_COMPUTE_F32) {
-    set_error("diffnet_prepare_ragged: ragged batches need the fp32 configuration (the bf16 one, bsg_diffnet_set_compute BF16, has no ragged launch)");
     return BSG_ESTATE;
   }
   for (int b = 0; b < B; ++b) BSG_REQUIRE(lens[b] >= 1 && lens[b] <= T, "diffnet_prepare_ragged: row %d has %d frames (1..T=%d)", b, lens[b], T);

@@ -399,8 +399,13 @@ __device__ __forceinline__ void mfma_pipe_bf8(f32x16& c00, f32x16& c10, f32x16& 
   }
 }
 
-template <bool FAIRB>
-__global__ __launch_bounds__(512, 2) void residual_stack_bf16_kernel(StackArgs p) {
+// VARLEN: the RAGGED form (bsg_diffnet_prepare_ragged), arithmetic as VARLEN = false.  A workgroup takes its (row, column tile) from the
+// launch's tile table p.vl_tiles — a row's tiles are contiguous there, so the neighbours stay at tile_id -/+ 1 — and the row's own frame count
+// p.vl_len[b] is the boundary wherever T was one (right neighbour, loaded / stored columns, halo, image core).  T stays the row stride.
+// (The body is shared by two kernels so that the product kernel keeps its name; residual_stack_bf16_kernel<true> compiles to the same
+// VGPRs, SGPRs, scratch and occupancy as when it held the body itself — only its SGPR spills to VGPR lanes went from 31 to 29.)
+template <bool FAIRB, bool VARLEN>
+__device__ __forceinline__ void residual_stack_bf16_body(StackArgs p) {
   extern __shared__ __attribute__((aligned(16))) char lds_raw[];
   char* xs = lds_raw;              // [80 frames][528 B]: bf16(x + d_l), frames t0-8 .. t0+71
   char* zs = lds_raw + XS_BYTES;   // [64 frames][528 B]: gated activation
@@ -415,10 +420,20 @@ __global__ __launch_bounds__(512, 2) void residual_stack_bf16_kernel(StackArgs p
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, lh = lane >> 5;
   const int tpr = p.tiles_per_row, L = p.L, T = p.T;
-  const int b = tile_id / tpr, j = tile_id - b * tpr;
+  int b, j, Tl = T, tprl = tpr;   // Tl: frames of this row (the boundary); tprl: its tiles
+  if constexpr (VARLEN) {
+    const int2 e = p.vl_tiles[tile_id];
+    b = e.x;
+    j = e.y;
+    Tl = p.vl_len[b];
+    tprl = (Tl + NT - 1) / NT;
+  } else {
+    b = tile_id / tpr;
+    j = tile_id - b * tpr;
+  }
   const int t0 = j * NT;
   const int tb = p.t_dev ? (int)p.t_dev[b] : p.t_uniform;
-  const bool has_left = j > 0, has_right = j + 1 < tpr;
+  const bool has_left = j > 0, has_right = j + 1 < tprl;
 
   const unsigned plane = (unsigned)C * T * 4;
   const rsrc_t rs_x = mk_rsrc(p.x_in + (long long)b * C * T, plane);
@@ -428,10 +443,10 @@ __global__ __launch_bounds__(512, 2) void residual_stack_bf16_kernel(StackArgs p
 #pragma unroll
   for (int ct = 0; ct < 2; ++ct) {
     const int col = t0 + 32 * ct + l31;
-    col_ok[ct] = col < T;
-    vcol[ct] = (lh * 4 * T + (col_ok[ct] ? col : T - 1)) * 4;
+    col_ok[ct] = col < Tl;
+    vcol[ct] = (lh * 4 * T + (col_ok[ct] ? col : Tl - 1)) * 4;
     vst[ct] = (lh * 4 * T + col) * 4;
-    vq[ct] = (lh * T + (col_ok[ct] ? col : T - 1)) * 8;
+    vq[ct] = (lh * T + (col_ok[ct] ? col : Tl - 1)) * 8;
   }
   const int sa_g = wave * 1024, sa_f = (8 + wave) * 1024;   // gate / filter row tile inside a k-step slab
   const int sb_r = wave * 1024, sb_s = (8 + wave) * 1024;   // residual / skip row tile
@@ -466,7 +481,7 @@ __global__ __launch_bounds__(512, 2) void residual_stack_bf16_kernel(StackArgs p
       yf1[4 * g] = bf16_lo(f1[0]); yf1[4 * g + 1] = bf16_hi(f1[0]); yf1[4 * g + 2] = bf16_lo(f1[1]); yf1[4 * g + 3] = bf16_hi(f1[1]);
     }
   };
-  // xs core (frames t0 .. t0+63, this wave's 32 channels) = bf16(x + d_l), zero beyond T (the conv pads x + d)
+  // xs core (frames t0 .. t0+63, this wave's 32 channels) = bf16(x + d_l), zero beyond T (ragged: beyond Tl; the conv pads x + d)
   auto write_core = [&]() {   // d of the layer being prepared is in dtab (written a phase earlier, behind a barrier)
     float dv[16];
 #pragma unroll
@@ -495,7 +510,7 @@ __global__ __launch_bounds__(512, 2) void residual_stack_bf16_kernel(StackArgs p
     const int hf = tid & 15, hc = tid >> 4;   // 16 halo frames x 32 chunks of 8 channels
     const int th = hf < 8 ? t0 - HALO + hf : t0 + NT - 8 + hf;
     const int hrow = hf < 8 ? hf : NT + hf;
-    const bool hok = th >= 0 && th < T;
+    const bool hok = th >= 0 && th < Tl;
     float hv[8], hd[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -683,6 +698,16 @@ __global__ __launch_bounds__(512, 2) void residual_stack_bf16_kernel(StackArgs p
   }
 }
 
+template <bool FAIRB>
+__global__ __launch_bounds__(512, 2) void residual_stack_bf16_kernel(StackArgs p) {
+  residual_stack_bf16_body<FAIRB, false>(p);
+}
+
+// the ragged form: p.vl_tiles / p.vl_len set (time-sliced issue priority, as the padded launch)
+__global__ __launch_bounds__(512, 2) void residual_stack_bf16_varlen_kernel(StackArgs p) {
+  residual_stack_bf16_body<true, true>(p);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Step tail of the bf16-operand configuration, one 64-frame tile per workgroup (the fp32 tail, diffnet.hip step_tail_kernel, is the
 // model; same sampler arithmetic, shared through diffnet_tail.h):
@@ -697,17 +722,31 @@ __global__ __launch_bounds__(512, 2) void residual_stack_bf16_kernel(StackArgs p
 constexpr int XIN_ROWB = 2 * 96 + 16;   // updated-x image row: 96 bf16 + 16 B pad = 208 B (52 dwords: conflict-free ds_read_b128)
 constexpr int TAIL_LDS = NT * ROWB + NT * XIN_ROWB;
 
-template <bool PLMS>
-__global__ __launch_bounds__(512, 4) void step_tail_bf16_kernel(TailArgs a) {
+// VARLEN: the ragged form (bsg_diffnet_prepare_ragged), arithmetic as VARLEN = false.  Workgroup i takes its (row, column tile) from
+// vl_tiles[i] — one launch covers the tiles of every launch group's table — and the row's frame count Tl = vl_len[b] is the boundary: the
+// skip sum is staged as 0 at frames >= Tl (the stack stored none there: the workspace holds stale values), and eps, x and e_new are stored
+// at frames < Tl only.  Philox indices keep the padded stride T.  The next input projection may write xa's padding (the stack never
+// reads it); the updated x it projects is 0 there.  (Two kernels over one body, as residual_stack_bf16_body.  `a` by value: taken by
+// reference, the body moved step_tail_bf16_kernel's register allocation — 128 VGPRs instead of 126 for PLMS.)
+template <bool PLMS, bool VARLEN>
+__device__ __forceinline__ void step_tail_bf16_body(TailArgs a, const int2* __restrict__ vl_tiles, const int* __restrict__ vl_len) {
   extern __shared__ __attribute__((aligned(16))) char lds_raw[];
   char* ss = lds_raw;               // [64 frames][528 B]: s, then h
   char* xin = lds_raw + NT * ROWB;  // [64 frames][208 B]: updated x (rows >= M zero)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, lh = lane >> 5;
-  const int b = blockIdx.x / a.tiles_per_row;
-  const int t0 = (blockIdx.x - b * a.tiles_per_row) * NT;
   const int T = a.T, M = a.M;
+  int b, t0, Tl = T;
+  if constexpr (VARLEN) {
+    const int2 e = vl_tiles[blockIdx.x];
+    b = e.x;
+    t0 = e.y * NT;
+    Tl = vl_len[b];
+  } else {
+    b = blockIdx.x / a.tiles_per_row;
+    t0 = (blockIdx.x - b * a.tiles_per_row) * NT;
+  }
   const rsrc_t rs_ws = mk_rsrc(a.ws_h, C * C * 2);
   const rsrc_t rs_wo = mk_rsrc(a.wo_h, 96 * C * 2);
   const rsrc_t rs_wi = mk_rsrc(a.wi_h, C * 96 * 2);
@@ -726,8 +765,8 @@ __global__ __launch_bounds__(512, 4) void step_tail_bf16_kernel(TailArgs a) {
 #pragma unroll
     for (int k = 0; k < 8; ++k) {   // 64 quads x 64 frames, one 8-byte load per item, lanes = consecutive frames
       const int q = 8 * k + wave, t = t0 + lane;
-      v[k] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rs_sh, t < T ? t * 8 : 0, q * T * 8, 0));
-      if (t >= T) v[k] = u32x2{0u, 0u};
+      v[k] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rs_sh, t < Tl ? t * 8 : 0, q * T * 8, 0));
+      if (t >= Tl) v[k] = u32x2{0u, 0u};
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k) *reinterpret_cast<u32x2*>(ss + lane * ROWB + (8 * k + wave) * 8) = v[k];
@@ -768,8 +807,8 @@ __global__ __launch_bounds__(512, 4) void step_tail_bf16_kernel(TailArgs a) {
   // ---- eps = W_out h + b and the sampler update, fp32, on the 3 row tiles that cover the M mel bins -----------------------------
   if (wave < 6) {
     const int col = t0 + 32 * ct2 + l31;
-    const bool col_ok = col < T;
-    const int vcol = (lh * 4 * T + (col_ok ? col : T - 1)) * 4, vst = (lh * 4 * T + col) * 4;
+    const bool col_ok = col < Tl;
+    const int vcol = (lh * 4 * T + (col_ok ? col : Tl - 1)) * 4, vst = (lh * 4 * T + col) * 4;
     const rsrc_t rs_x = mk_rsrc(a.x + (long long)b * M * T, (unsigned)M * T * 4);
     const rsrc_t rs_n = mk_rsrc(a.noise ? a.noise + (long long)b * M * T : a.x, a.noise ? (unsigned)M * T * 4 : 0u);
     f32x16 e;
@@ -816,13 +855,16 @@ __global__ __launch_bounds__(512, 4) void step_tail_bf16_kernel(TailArgs a) {
         } else {
           float nz = nv[r];
           if (!a.noise && a.k.sigma != 0.f)
-            nz = philox_normal1(a.seed, a.stream, a.quad_row0 + ((unsigned long long)b * M + m) * T + (col_ok ? col : T - 1));
+            nz = philox_normal1(a.seed, a.stream, a.quad_row0 + ((unsigned long long)b * M + m) * T + (col_ok ? col : Tl - 1));
           float x0 = __fsub_rn(__fmul_rn(a.k.recip, xv[r]), __fmul_rn(a.k.recipm1, e[r]));
           x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
           const float mean = __fadd_rn(__fmul_rn(a.k.pc1, x0), __fmul_rn(a.k.pc2, xv[r]));
           o[r] = __fadd_rn(mean, __fmul_rn(a.k.sigma, nz));
         }
         if (col_ok) stf(o[r], rs_x, vst, (32 * rt + acc_row0(r)) * rowT);
+        if constexpr (VARLEN) {
+          if (!col_ok) o[r] = 0.f;
+        }
       }
     }
 #pragma unroll
@@ -859,6 +901,16 @@ __global__ __launch_bounds__(512, 4) void step_tail_bf16_kernel(TailArgs a) {
       for (int r = 0; r < 16; ++r) stf(fmaxf(hh[r], 0.f), rs_xa, vst, (32 * wave + acc_row0(r)) * rowT);
     }
   }
+}
+
+template <bool PLMS>
+__global__ __launch_bounds__(512, 4) void step_tail_bf16_kernel(TailArgs a) {
+  step_tail_bf16_body<PLMS, false>(a, nullptr, nullptr);
+}
+
+template <bool PLMS>
+__global__ __launch_bounds__(512, 4) void step_tail_bf16_varlen_kernel(TailArgs a, const int2* __restrict__ vl_tiles, const int* __restrict__ vl_len) {
+  step_tail_bf16_body<PLMS, true>(a, vl_tiles, vl_len);
 }
 
 __global__ void f32_to_quad_bf16_kernel(const float* __restrict__ src, unsigned short* __restrict__ dst, int rows, int T) {
@@ -907,6 +959,15 @@ int launch_step_tail_bf16(const TailArgs& a_in, hipStream_t st) {
   return BSG_OK;
 }
 
+// ragged form: one workgroup per entry of the tile table `tiles` (n_tiles entries, every launch group's), row lengths `len`
+int launch_step_tail_bf16_ragged(const TailArgs& a, const int2* tiles, const int* len, int n_tiles, hipStream_t st) {
+  BSG_REQUIRE(tiles && len && n_tiles > 0, "ragged bf16 step tail: no tile table");
+  if (a.plms_hist) hipLaunchKernelGGL(step_tail_bf16_varlen_kernel<true>, dim3(n_tiles), dim3(512), TAIL_LDS, st, a, tiles, len);
+  else hipLaunchKernelGGL(step_tail_bf16_varlen_kernel<false>, dim3(n_tiles), dim3(512), TAIL_LDS, st, a, tiles, len);
+  BSG_LAUNCH_CHECK();
+  return BSG_OK;
+}
+
 int stack_bf16_occupancy() {
   const size_t lds = XS_BYTES + ZS_BYTES + 3 * C * 4;
   int o = 0;
@@ -916,8 +977,25 @@ int stack_bf16_occupancy() {
   return o;
 }
 
+// resident workgroups per CU (0 on error) of the ragged form
+int stack_bf16_varlen_occupancy() {
+  const size_t lds = XS_BYTES + ZS_BYTES + 3 * C * 4;
+  int o = 0;
+  if (hipFuncSetAttribute((const void*)residual_stack_bf16_varlen_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, (const void*)residual_stack_bf16_varlen_kernel, 512, lds) != hipSuccess)
+    return 0;
+  return o;
+}
+
+// p.vl_tiles set: the ragged form (p.vl_len the row lengths; stack_bf16_varlen_occupancy() has set its LDS attribute)
 int launch_residual_stack_bf16(const StackArgs& p, hipStream_t st) {
   const size_t lds = XS_BYTES + ZS_BYTES + 3 * C * 4;
+  if (p.vl_tiles) {
+    BSG_REQUIRE(p.vl_len, "bf16 stack launch: the ragged form needs the row lengths");
+    hipLaunchKernelGGL(residual_stack_bf16_varlen_kernel, dim3(8 * cdiv(p.n_tiles, 8)), dim3(512), lds, st, p);
+    BSG_LAUNCH_CHECK();
+    return BSG_OK;
+  }
   hipLaunchKernelGGL(residual_stack_bf16_kernel<true>, dim3(8 * cdiv(p.n_tiles, 8)), dim3(512), lds, st, p);
   BSG_LAUNCH_CHECK();
   return BSG_OK;

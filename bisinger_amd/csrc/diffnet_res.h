@@ -81,7 +81,7 @@ struct StackArgs {
   unsigned* pflags;       // [2][n_tiles][P parts]: [0] image flags (layers prepared), [1] z flags
   unsigned long long* stamps;   // diagnostic (bsg_diffnet_debug_stack_stamps) or null: [n_tiles][L][8] s_memrealtime at the phase boundaries
   unsigned long long* clk;      // null, or [4]: tile 0 stores s_memtime / s_memrealtime at its start and end (sustained shader clock, bench.py)
-  // ragged launch (residual_stack_q_kernel<.., VARLEN = true>, bsg_diffnet_prepare_ragged); null otherwise
+  // ragged launch (residual_stack_q_kernel<.., VARLEN = true>, residual_stack_bf16_varlen_kernel; bsg_diffnet_prepare_ragged); null otherwise
   const int2* vl_tiles;   // [n_tiles] {row of the bound batch, column tile in the row}: each row's tiles contiguous, in order
   const int* vl_len;      // [B] frames of every row of the bound batch (<= T, the row stride)
 };
@@ -110,6 +110,7 @@ __device__ __forceinline__ void stack_epoch_done(const StackArgs& p, unsigned fb
 // bf16 stack launch: 64-frame tiles, one workgroup per CU (see diffnet_bf16.hip); grid = p.n_tiles rounded up to 8
 int launch_residual_stack_bf16(const StackArgs& p, hipStream_t st);
 int stack_bf16_occupancy();   // resident workgroups per CU of residual_stack_bf16_kernel (0 on error)
+int stack_bf16_varlen_occupancy();   // its ragged form (p.vl_tiles set: launch_residual_stack_bf16 takes it)
 
 // fp32 stack launch on the 16-bit matrix pipe: operands split exactly into hi + lo fp16 terms (diffnet_h2.hip); 64-frame tiles, one
 // workgroup per CU; grid = p.n_tiles rounded up to 8

@@ -117,5 +117,7 @@ int h2_tail_pack(const float* ws, const float* wo96, const float* wi96, unsigned
 
 // bf16-operand form of the fused step tail (diffnet_bf16.hip): 64-frame tiles, skip sum read as bf16 channel quads (a.skip_h)
 int launch_step_tail_bf16(const TailArgs& a, hipStream_t st);
+// the ragged form: one workgroup per entry {row, 64-frame tile} of `tiles` (n_tiles, every launch group's); `len` [B] the rows' frame counts
+int launch_step_tail_bf16_ragged(const TailArgs& a, const int2* tiles, const int* len, int n_tiles, hipStream_t st);
 
 }  // namespace bsg

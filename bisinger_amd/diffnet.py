@@ -222,8 +222,9 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
 
     # ------------------------------------------------------------------ ragged batches
     def ragged_native(self, B, T):
-        """True when the handle's current state decodes the bound ragged (B, T) batch with the ragged launch (bsg_diffnet_ragged_native):
-        not after a demotion off the 16-row stack launch (range event, give-up), not in the bf16 configuration."""
+        """True when the handle's current state decodes the bound ragged (B, T) batch with the ragged launch (bsg_diffnet_ragged_native).
+        fp32: the ragged 16-row stack launch, not after a demotion off it (range event, give-up).  bf16: the ragged bf16 stack launch and
+        bf16 step tail, not with BSG_STACK_BF16=0 or BSG_TAIL_BF16=0 and not after a split demotion (give-up)."""
         n = c_int32()
         _lib.check(_lib.load().bsg_diffnet_ragged_native(self._h, B, T, byref(n)), 'bsg_diffnet_ragged_native')
         return bool(n.value)

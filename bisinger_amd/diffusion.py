@@ -137,8 +137,6 @@ class GaussianDiffusion(nn.Module):
         elif not isinstance(self.denoise_fn, DiffNet):
             raise NotImplementedError('sample(lengths=...): ragged batches need the WaveNet denoiser (DiffNet)')
         else:
-            if self.denoise_fn.compute_dtype in ('bf16', 'bfloat16'):
-                raise _lib.BsgError('sample(lengths=...): the bf16 configuration has no ragged launch; use fp32 or padded batches')
             self.denoise_fn.prepare(cond, lengths)
         s, _keep = self._schedule()
         h = self.denoise_fn._h

@@ -85,10 +85,12 @@ int bsg_diffnet_forward(bsg_diffnet* h, const float* x, const int64_t* t, float*
  *   were alone at T = lens[b]: nothing of frames >= lens[b] is read by a frame below it.  T stays the row stride of x, eps, noise and cond.
  *   eps is 0 at frames >= lens[b]; the samplers leave x there as the caller gave it.  Philox draws keep their index (global row, stride T).
  *   Whole rows are packed into launch groups of at most one 64-frame tile per CU (bsg_ragged_plan); the groups run one after another on
- *   `stream`.  BSG_EINVAL for a row longer than one group; BSG_ESTATE under stream capture (binding and calls) and for a bf16 handle.
+ *   `stream`.  BSG_EINVAL for a row longer than one group; BSG_ESTATE under stream capture (binding and calls).  Both configurations:
+ *   fp32 (the ragged 16-row stack launch) and bf16 (bsg_diffnet_set_compute BF16: the ragged bf16 stack launch and bf16 step tail).
  *   A plain bsg_diffnet_prepare clears the ragged binding.
  * bsg_diffnet_ragged_native: *native = 1 when the handle's CURRENT state has the ragged launch for the bound (B,T) — not after
- *   bsg_diffnet_set_h2q / set_h2 / set_split(h, 0), not in the bf16 configuration.  With 0 the compute calls above return BSG_ESTATE on a
+ *   bsg_diffnet_set_h2q / set_h2 / set_split(h, 0) (fp32), not after set_split(h, 0) or with BSG_STACK_BF16=0 / BSG_TAIL_BF16=0 (bf16).
+ *   With 0 the compute calls above return BSG_ESTATE on a
  *   ragged binding: the caller decodes the rows one by one (bisinger_amd/diffnet.py does).
  * bsg_ragged_plan: the packing, a pure host function (no device needed): row b of lens[b] frames takes ceil(lens[b] / tile_frames) tiles;
  *   first-fit decreasing into groups of at most `cus` tiles; group_of_row [B] receives each row's group (0-based, launch order). */

@@ -3,13 +3,14 @@ a ragged request list, three ways —
   padded    one batch padded to its longest row;
   bucketed  length buckets of max_sentences = 16 rows (bucket_by_size, as DiffSingerE2EInfer.forward_batch(max_sentences=16)), each padded
             to its own longest row, run one after another;
-  ragged    one batch, every row at its own length (lengths=..., the ragged 16-row stack launch).
+  ragged    one batch, every row at its own length (lengths=..., the ragged 16-row stack launch; --dtype bf16: the ragged bf16 stack
+            launch and bf16 step tail).
 Launch groups: the padded / bucketed batches run whole rows of ceil(T / 64) tiles, floor(CUs / tiles) rows per group; the ragged batch the
 plan of bsg_ragged_plan.  Waste: padded frames computed for nothing.  Prints one JSON line per configuration:
   B = 64, lengths RandomState(0).randint(250, 1001)  (the request list of DESIGN section 4)
   B = 20 x T = 777                                  (uniform rows: 19 + 1 rows per group either way)
 
-    python tools/bench_ragged.py [--steps K] [--warmup W]
+    python tools/bench_ragged.py [--steps K] [--warmup W] [--dtype {fp32,bf16}]
 """
 import argparse
 import json
@@ -25,6 +26,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=3, help='timed passes per mode')
     ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--dtype', choices=('fp32', 'bf16'), default='fp32', help='the decoder configuration (bf16: diff_compute_dtype bf16)')
     args = ap.parse_args()
     sys.argv = sys.argv[:1]
     import numpy as np
@@ -35,6 +37,7 @@ def main():
     torch.set_grad_enabled(False)
     dev = torch.device('cuda', 0)
     model = bench.build_model(dev)
+    model.denoise_fn.set_compute(args.dtype)
     cus = torch.cuda.get_device_properties(0).multi_processor_count
 
     def groups_padded(B, T):
@@ -72,7 +75,7 @@ def main():
         for m in modes.values():
             m['real_mel_frames_per_s'] = real / m['s_per_pass']
         r = modes['ragged']['real_mel_frames_per_s']
-        print(json.dumps({'config': name, 'B': B, 'T_max': T, 'real_frames': real, 'tiles': int(sum(-(-n // 64) for n in lens)), 'cus': cus,
+        print(json.dumps({'config': name, 'dtype': args.dtype, 'B': B, 'T_max': T, 'real_frames': real, 'tiles': int(sum(-(-n // 64) for n in lens)), 'cus': cus,
                           'ddpm_steps': model.K_step, 'modes': modes,
                           'ragged_speedup': {k: r / v['real_mel_frames_per_s'] for k, v in modes.items() if k != 'ragged'}}), flush=True)
 
