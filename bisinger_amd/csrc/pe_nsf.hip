@@ -156,58 +156,54 @@ struct SineArgs {
 };
 
 // one workgroup per (harmonic, utterance); thread k owns samples [k*S, (k+1)*S)
+//
+// The reference's phase is cumsum(rad + shift) (:67-74): the first cumsum C = cumsum(rad) finds the steps where C passes an integer,
+// and shift subtracts 1 there, so phase_i = C_i - (an integer).  Only sin(2 pi phase) is used, so every integer is exact to drop: the
+// phase is carried as frac(C_i) in [0, 1), in fp64.  In fp32, sums over a thread's S = T*hop/256 samples and a phase that is not
+// reduced lose resolution as T grows: up to 14 % of the sine amplitude at T = 4000 (tests/test_gpu_f2_fullsize.py).  rad is formed in
+// fp64 too, once per frame: its fp32 rounding (f0 * (h+1) / sr) is a relative error that all hop samples of the frame repeat.
 __global__ __launch_bounds__(256) void sine_source_kernel(SineArgs a) {
-  __shared__ float sh[256];
+  __shared__ double sh[256];
   const int hh = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const long long L = (long long)a.T * a.hop;
   const long long S = (L + 255) / 256;
   const long long i0 = tid * S, i1 = (i0 + S < L) ? i0 + S : L;
-  const float mult = (float)(hh + 1);
-  const float ri = hh == 0 ? 0.f : a.rand_ini[(long long)b * a.NH + hh];
+  const double mult = (double)(hh + 1);
+  const double sr = (double)a.sr;
   const float* f0 = a.f0 + (long long)b * a.T;
-  auto rad_at = [&](long long i) {
-    const float f = f0[i / a.hop] * mult;                 // f0_buf = f0 * (idx + 2)          :112-116
-    float r = fmodf(f / a.sr, 1.0f);                       // (f0 / sr) % 1                    :50
-    if (i == 0) r += ri;                                   // initial phase noise              :57
-    return r;
+  auto rad_of = [&](long long t) {                          // (f0 * (idx + 1) / sr) % 1        :50, :112-116
+    const double r = (double)f0[t] * mult / sr;
+    return r - floor(r);
   };
-  auto excl_scan = [&](float v) {                          // exclusive prefix over the 256 threads
-    __syncthreads();
-    sh[tid] = v;
-    __syncthreads();
-    float acc = 0.f;
-    for (int k = 0; k < tid; ++k) acc += sh[k];
-    return acc;
-  };
-  // level 1: cumsum(rad) -> where it wraps past an integer                                        :67-71
-  float s = 0.f;
-  for (long long i = i0; i < i1; ++i) s += rad_at(i);
-  float c = excl_scan(s);
-  // level 2: cumsum(rad + shift), shift = -1 at every wrap; first the per-thread partial sums
-  float prev = fmodf(c, 1.0f);          // tmp_over_one at i0 - 1 (c = cumsum up to i0-1)
-  float run = c, part = 0.f;
-  for (long long i = i0; i < i1; ++i) {
-    const float r = rad_at(i);
-    run += r;
-    const float cur = fmodf(run, 1.0f);
-    part += (i > 0 && cur - prev < 0.f) ? r - 1.0f : r;
-    prev = cur;
+  // level 1: this thread's share of cumsum(rad), reduced mod 1
+  double s = 0.0;
+  for (long long i = i0; i < i1;) {
+    const long long t = i / a.hop;
+    const long long e = (t + 1) * a.hop < i1 ? (t + 1) * a.hop : i1;
+    s += rad_of(t) * (double)(e - i);
+    i = e;
   }
-  float phase = excl_scan(part);
-  prev = fmodf(c, 1.0f);
-  run = c;
+  sh[tid] = s - floor(s);
+  __syncthreads();
+  // exclusive prefix over the threads; the initial phase noise rides on rad[0] (:53-57), i.e. on every later C_i
+  double p = hh == 0 ? 0.0 : (double)a.rand_ini[(long long)b * a.NH + hh];
+  for (int k = 0; k < tid; ++k) p += sh[k];
+  p -= floor(p);
+  // level 2: phase_i = frac(C_i), one subtraction per wrap
   float* out = a.sw + ((long long)b * a.NH + hh) * L;
   const float* nz = a.noise + (long long)b * L * a.NH + hh;
-  for (long long i = i0; i < i1; ++i) {
-    const float r = rad_at(i);
-    run += r;
-    const float cur = fmodf(run, 1.0f);
-    phase += (i > 0 && cur - prev < 0.f) ? r - 1.0f : r;
-    prev = cur;
-    const float sine = sinf(phase * 2.0f * 3.14159265358979323846f) * a.sine_amp;      // :73-74, :119
-    const float uv = f0[i / a.hop] > 0.f ? 1.f : 0.f;                                  // :42-43
-    const float namp = uv * a.noise_std + (1.f - uv) * a.sine_amp / 3.f;               // :129
-    out[i] = sine * uv + namp * nz[i * a.NH];                                          // :130-134
+  for (long long i = i0; i < i1;) {
+    const long long t = i / a.hop;
+    const long long e = (t + 1) * a.hop < i1 ? (t + 1) * a.hop : i1;
+    const double r = rad_of(t);
+    const float uv = f0[t] > 0.f ? 1.f : 0.f;                                         // :42-43
+    const float namp = uv * a.noise_std + (1.f - uv) * a.sine_amp / 3.f;              // :129
+    for (; i < e; ++i) {
+      p += r;
+      if (p >= 1.0) p -= 1.0;
+      const float sine = sinf((float)p * 2.0f * 3.14159265358979323846f) * a.sine_amp;   // :73-74, :119
+      out[i] = sine * uv + namp * nz[i * a.NH];                                          // :130-134
+    }
   }
 }
 
@@ -487,6 +483,20 @@ extern "C" int bsg_pitchext_forward(bsg_pitchext* h, const float* mel, float* pi
   hipLaunchKernelGGL(f0_denorm_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, st, (const float*)pred, h->keep, f0, rows, h->cfg.use_uv);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
+}
+
+extern "C" int bsg_nsf_source(const float* f0, const float* rand_ini, const float* noise, const float* lin_w, const float* lin_b, float* har,
+                              float* sines, int32_t B, int32_t T, int32_t hop, int32_t NH, int32_t sample_rate, void* stream) {
+  BSG_REQUIRE(f0 && rand_ini && noise && lin_w && lin_b && har && B > 0 && T > 0 && hop > 0 && NH > 0 && sample_rate > 0,
+              "nsf_source: bad argument (B=%d T=%d hop=%d NH=%d sample_rate=%d)", B, T, hop, NH, sample_rate);
+  hipStream_t st = (hipStream_t)stream;
+  if (sines) return nsf_launch_source(f0, rand_ini, noise, lin_w, lin_b, sines, har, B, T, hop, NH, (float)sample_rate, st);
+  float* tmp = nullptr;
+  BSG_HIP(hipMalloc((void**)&tmp, (size_t)B * T * hop * NH * sizeof(float)));
+  int rc = nsf_launch_source(f0, rand_ini, noise, lin_w, lin_b, tmp, har, B, T, hop, NH, (float)sample_rate, st);
+  if (rc == BSG_OK && hipStreamSynchronize(st) != hipSuccess) rc = BSG_EHIP;
+  (void)hipFree(tmp);
+  return rc;
 }
 
 namespace bsg {

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define BSG_ABI_VERSION 8
+#define BSG_ABI_VERSION 9
 
 #define BSG_OK 0
 #define BSG_EINVAL (-22)  /* bad argument / shape the kernels do not support            */
@@ -370,6 +370,13 @@ int bsg_hifigan_forward(bsg_hifigan* h, const float* mel, float* wav, int32_t B,
  * noise [B, T*hop, harmonic_num+1] N(0,1) (torch.randn_like, source.py:130). */
 int bsg_hifigan_forward_nsf(bsg_hifigan* h, const float* mel, const float* f0, const float* rand_ini, const float* noise,
                             float* wav, int32_t B, int32_t T, void* stream);
+
+/* ABI v9, building block exported for unit tests: the NSF harmonic source alone (source.py:352-399 as bsg_hifigan_forward_nsf runs it).
+ * f0 [B,T], rand_ini [B,NH], noise [B,T*hop,NH] as there; lin_w [NH], lin_b [1] = m_source.l_linear.{weight,bias}.
+ * har [B,T*hop] = tanh(l_linear(sine_waves)).  sines (may be NULL): [B][NH][T*hop], the per-harmonic sine_waves (sines * uv + noise,
+ * :130-134) before the merge.  With sines NULL a workspace is allocated and `stream` is synchronised before returning. */
+int bsg_nsf_source(const float* f0, const float* rand_ini, const float* noise, const float* lin_w, const float* lin_b, float* har,
+                   float* sines, int32_t B, int32_t T, int32_t hop, int32_t NH, int32_t sample_rate, void* stream);
 
 /* PitchExtractor: mel [B,T,n_mel] -> pitch_pred [B,T,2] (may be NULL) and f0_denorm_pred [B,T]
  * (modules/fastspeech/pe.py:120-149; pitch_norm 'log', pitch_type 'frame').  dev_weights in PitchExtractor.state_dict()

@@ -11,10 +11,8 @@ import torch.nn.functional as F
 from .hifigan import DEFAULT_CFG, LRELU_SLOPE, fold_weight_norm
 
 
-def sine_source(sd, f0, rand_ini, noise, sr, hop, prefix='m_source.', harmonic_num=8, sine_amp=0.1, noise_std=0.003,
-                dtype=torch.float32):
-    """f0 [B,T] -> harmonic source [B,1,T*hop]."""
-    g = lambda k: sd[prefix + k].to(dtype)
+def sine_waves(f0, rand_ini, noise, sr, hop, harmonic_num=8, sine_amp=0.1, noise_std=0.003, dtype=torch.float32):
+    """f0 [B,T] -> the per-harmonic sine_waves [B,T*hop,harmonic_num+1] before the merge (SineGen.forward)."""
     f0 = f0.to(dtype)
     f0u = f0[:, :, None].repeat_interleave(hop, dim=1)                     # Upsample(nearest), hifigan.py:147
     mult = torch.arange(1, harmonic_num + 2, dtype=dtype)
@@ -30,8 +28,15 @@ def sine_source(sd, f0, rand_ini, noise, sr, hop, prefix='m_source.', harmonic_n
     sines = torch.sin(torch.cumsum(rad + shift, dim=1) * 2 * np.pi) * sine_amp   # :73-74, :119
     uv = (f0u > 0).to(dtype)                                                # :42-43
     noise_amp = uv * noise_std + (1 - uv) * sine_amp / 3                    # :129
-    sine_waves = sines * uv + noise_amp * noise.to(dtype)                   # :130-134
-    merged = torch.tanh(F.linear(sine_waves, g('l_linear.weight'), g('l_linear.bias')))   # :391
+    return sines * uv + noise_amp * noise.to(dtype)                         # :130-134
+
+
+def sine_source(sd, f0, rand_ini, noise, sr, hop, prefix='m_source.', harmonic_num=8, sine_amp=0.1, noise_std=0.003,
+                dtype=torch.float32):
+    """f0 [B,T] -> harmonic source [B,1,T*hop]."""
+    g = lambda k: sd[prefix + k].to(dtype)
+    sw = sine_waves(f0, rand_ini, noise, sr, hop, harmonic_num, sine_amp, noise_std, dtype)
+    merged = torch.tanh(F.linear(sw, g('l_linear.weight'), g('l_linear.bias')))   # :391
     return merged.transpose(1, 2)
 
 
