@@ -742,7 +742,7 @@ __global__ __launch_bounds__(WIDE ? 1024 : 1024 / NPART, 4) void residual_split_
 // ------------------------------------------------------------------------------------------------
 // Stack launches: all L residual layers of a group of rows in ONE launch with the residual stream on chip (diffnet_h2.hip: split-fp16
 // form, the fp32 default; diffnet_f43.hip: Winograd F(4,3) on the fp32 matrix pipe; diffnet_bf16.hip: bf16-operand configuration; the
-// host side — stack_rows / launch_stack — is below).  (The first form, a F(2,3) kernel with two 32-frame workgroups per CU, lived here
+// host side — plan_stack / launch_stack — is below).  (The first form, a F(2,3) kernel with two 32-frame workgroups per CU, lived here
 // in the first half of round 2; it was 3 % slower than two chains of per-layer launches, was superseded by the forms above and removed.)
 // The hand-off protocol all of them share: per layer the only inter-workgroup traffic is the 8-frame edge of the new conv image that
 // each of the two neighbour tiles needs as its halo (dilation <= 8): published write-through (sc1) into an exchange array that is
@@ -1139,15 +1139,10 @@ struct bsg_diffnet {
   unsigned long long* clk = nullptr;   // [4] s_memtime / s_memrealtime at the start and end of tile 0 of the last profiled stack launch
   int occ_stack_h = -1;                // the same for residual_stack_bf16_kernel
   int occ_stack43 = -1;                // the same for residual_stack_f43_kernel
-  bool stack_is_f43 = false;           // the last stack_rows() chose the F(4,3) stack launch
-  bool stack_is_h2 = false;            // ... the split-fp16 stack launch (diffnet_h2.hip)
   bool h2_off = false;                 // bsg_diffnet_set_h2(h, 0): this handle multiplies on the fp32 matrix pipe only
   bool q_off = false;                  // bsg_diffnet_set_h2q(h, 0): the 32-row stack launch (|x + d| < 60000) instead of the 16-row one (|x| < 3750)
   int occ_stack_h2q[3] = {-1, -1, -1}; // the same for residual_stack_q_kernel (16-row matrix tiles, diffnet_h2q.hip)
-  bool stack_q = false;                // the stack launch of the current shape runs on 16-row matrix tiles
   int occ_stack_h2[3] = {-1, -1, -1};  // resident workgroups per CU of residual_stack_h2_kernel<.., NCT> by NCT (-1: not queried)
-  int stack_nct = 2;                   // column tiles of 32 frames per workgroup the last stack_rows() chose for the split-fp16 launch
-  int stack_parts = 0;                 // ... a part form (diffnet_h2.hip residual_part_h2_kernel): workgroups per tile (4 / 2), else 0
   int occ_part[3] = {-1, -1, -1};      // resident workgroups per CU: [1] / [2] quad of 32- / 64-frame tiles, [0] pair of 64-frame tiles (-1: not queried)
   unsigned short *apack1q = nullptr, *apack2q = nullptr;   // the split-fp16 weights once more as 16-row fragments (part forms)
   unsigned short* part_zx = nullptr;   // part forms: exchange slots of the z parts [tiles][P][2 planes][tile frames][C/P] fp16
@@ -1179,8 +1174,8 @@ struct bsg_diffnet {
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   // ragged binding (bsg_diffnet_prepare_ragged): every row of the bound (B, T) decoded at its own frame count
   bool ragged = false;                 // the bound condition came with row lengths (a plain prepare clears this)
-  bool rg_active = false;              // inside a ragged call: stack_rows / launch_stack take the ragged 16-row launch (bf16 configuration:
-                                       // stack_rows_bf16 / launch_stack_bf16 the ragged bf16 stack launch, launch_tail the ragged bf16 tail)
+  bool rg_active = false;              // inside a ragged call: plan_stack plans the ragged 16-row launch (bf16 configuration: the ragged
+                                       // bf16 stack launch, and launch_tail takes the ragged bf16 tail)
   int occ_stack_varlen = -1;           // resident workgroups per CU of that launch (-1: not queried)
   int occ_stack_bf16_varlen = -1;      // the same for the ragged bf16 stack launch
   int* rg_dev = nullptr;               // [B rounded up to even] row lengths, then the tile tables {row, tile} of every launch group
@@ -1637,7 +1632,7 @@ extern "C" int bsg_diffnet_prepare(bsg_diffnet* h, const float* cond, int32_t B,
 }
 
 // GEMM1 of the residual block: BSG_WINO unset = 2: Winograd F(2,3) kernels, and the F(4,3) stack launch (diffnet_f43.hip) for launches
-// that fill the chip with 64-frame tiles (stack_rows; BSG_STACK43=2: for any shape); 1: F(2,3) only; 0: the direct K=768 form
+// that fill the chip with 64-frame tiles (plan_stack; BSG_STACK43=2: for any shape); 1: F(2,3) only; 0: the direct K=768 form
 static int wino_env() {
   static int v = -1;
   if (v < 0) { const char* e = getenv("BSG_WINO"); v = e ? atoi(e) : 2; }
@@ -1771,20 +1766,56 @@ static int launch_layer(bsg_diffnet* h, int layer, const float* x_in, const long
   return BSG_OK;
 }
 
-// rows per launch group (0: the stack launch is not used for this shape).  A tile row is ceil(T/32) workgroups that wait for
-// each other, and every workgroup of a launch must be resident: at most occ x CUs workgroups, whole rows only.  It pays when a
-// launch has more workgroups than CUs (two per CU overlap each other's waits); smaller launches keep the channel-split kernels.
-static int stack_rows(bsg_diffnet* h, int B, int T, hipStream_t st) {
-  if (h->rg_active) {   // a ragged call (ragged_launch_ok checked it): the 16-row launch on 64-frame tiles, groups from the bound plan
-    if (h->compute != BSG_COMPUTE_F32) return 0;   // (the bf16 configuration: stack_rows_bf16)
-    h->stack_is_f43 = false;
-    h->stack_is_h2 = h->stack_q = true;
-    h->stack_nct = 2;
-    h->stack_parts = 0;
-    return B;
+// The stack launch of a call: which form runs the L residual layers, and how the batch splits into launch groups.  plan_stack() decides
+// it from the shape and the handle's state and writes nothing on the handle but its occupancy memos (occ_*), so a query
+// (bsg_diffnet_uses_handoffs) and the launch it predicts agree; every compute entry plans once and hands the plan to the launches.
+enum StackForm {
+  STACK_NONE,   // no stack launch: one launch per layer (launch_layer)
+  STACK_F43,    // Winograd F(4,3) on the fp32 matrix pipe (diffnet_f43.hip)
+  STACK_H2,     // split-fp16, 32-row matrix tiles (residual_stack_h2_kernel, diffnet_h2.hip)
+  STACK_H2Q,    // split-fp16, 16-row matrix tiles (residual_stack_q_kernel, diffnet_h2q.hip)
+  STACK_PART,   // split-fp16 part form: several workgroups per tile (residual_part_h2_kernel, diffnet_h2.hip)
+  STACK_BF16,   // bf16-operand configuration (diffnet_bf16.hip)
+};
+
+struct StackPlan {
+  StackForm form = STACK_NONE;
+  int nct = 2;          // column tiles of 32 frames per workgroup: tiles of 32 * nct frames (F(4,3), bf16: 64)
+  int parts = 0;        // STACK_PART: workgroups per tile (4: quads, 2: pairs)
+  int rows = 0;         // rows per launch group
+  bool ragged = false;  // a ragged call: one launch per group of the plan bound by bsg_diffnet_prepare_ragged (rows = B)
+};
+
+// A tile row is ceil(T / (32 nct)) workgroups that wait for each other, and every workgroup of a launch must be resident: at most
+// occ x CUs workgroups, whole rows only.  It pays when a launch has more workgroups than CUs (two per CU overlap each other's waits);
+// smaller launches keep the channel-split kernels.  The half-batch chains of a large batch (dual_fork: no_split) take per-layer launches.
+static StackPlan plan_stack(bsg_diffnet* h, int B, int T, hipStream_t st) {
+  StackPlan plan;
+  if (h->no_split) return plan;
+  if (h->compute == BSG_COMPUTE_BF16) {
+    // bf16-operand configuration: the stack launch (the default; BSG_STACK_BF16=0 selects per-layer launches).  64-frame tiles, one
+    // workgroup per CU (256 registers per wave), whole rows per launch group.  Measured on one box, ms per 100-step pass at T=1000,
+    // stack / per-layer: B=1 43.2 / 56.4, B=16 58.2 / 87.8, B=32 109.7 / 133.3, B=64 213.8 / 237.3 (tools/bench_small.py with
+    // BSG_DTYPE=bf16).  Per layer and tile ~21.5 us, of which the two GEMMs' MFMAs are ~7.  Whether it is taken
+    // does not depend on B.
+    static int env = -1;
+    if (env < 0) { const char* e = getenv("BSG_STACK_BF16"); env = e ? atoi(e) : 1; }
+    if (!env || h->split_off || !h->num_cus || !h->hx || !h->epoch_dev) return plan;
+    if (h->occ_stack_h < 0) h->occ_stack_h = stack_bf16_occupancy() >= 1 ? 1 : 0;
+    const int tpr = cdiv(T, 64);
+    const long long slots = (long long)h->occ_stack_h * h->num_cus;
+    if (h->rg_active) {   // a ragged call (ragged_launch_ok checked it): groups from the bound plan
+      if (h->occ_stack_h >= 1) { plan.form = STACK_BF16; plan.rows = B; plan.ragged = true; }
+    } else if (h->occ_stack_h >= 1 && tpr <= slots) {
+      plan.form = STACK_BF16;
+      plan.rows = slots / tpr < B ? (int)(slots / tpr) : B;
+    }
+    return plan;
   }
-  h->stack_is_f43 = false;
-  h->stack_is_h2 = false;
+  if (h->rg_active) {   // a ragged call (ragged_launch_ok checked it): the 16-row launch on 64-frame tiles, groups from the bound plan
+    plan.form = STACK_H2Q; plan.rows = B; plan.ragged = true;
+    return plan;
+  }
   {
     // split-fp16 form (diffnet_h2.hip): fp32 operands as hi + lo fp16 terms on the 16-bit matrix pipe; 64-frame tiles, one workgroup per
     // CU, whole rows per launch group, every batch size.  BSG_H2=0 / bsg_diffnet_set_h2(h, 0): off (the kernels of the fp32 matrix pipe)
@@ -1805,7 +1836,6 @@ static int stack_rows(bsg_diffnet* h, int B, int T, hipStream_t st) {
       if (env_nct < 0) { const char* e = getenv("BSG_H2_NCT"); env_nct = e ? atoi(e) : 0; }
       int nct = (long long)B * cdiv(T, 32) > h->num_cus ? 2 : 1;
       if (env_nct == 1 || env_nct == 2) nct = env_nct;
-      h->stack_parts = 0;
       {
         // part forms (residual_part_h2_kernel): several workgroups on as many CUs of an XCD share a tile, each a part of the channels and of
         // the weight stream; the whole batch in one launch.  Quads of 32-frame tiles while B * ceil(T / 32) <= CUs / 4 (one or two utterances
@@ -1817,49 +1847,40 @@ static int stack_rows(bsg_diffnet* h, int B, int T, hipStream_t st) {
         if (env_part < 0) { const char* e = getenv("BSG_H2_PART"); env_part = e ? atoi(e) : 1; }
         if (env_quad < 0) { const char* e = getenv("BSG_H2_QUAD"); env_quad = e ? atoi(e) : 1; }
         if (env_quad64 < 0) { const char* e = getenv("BSG_H2_QUAD64"); env_quad64 = e ? atoi(e) : 1; }
-        auto take_quad = [&](int pn) {
-          if (h->occ_part[pn] < 0) h->occ_part[pn] = part_h2_occupancy(4, pn) >= 1 ? 1 : 0;
-          if (h->occ_part[pn] < 1) return false;
-          h->stack_is_h2 = true;
-          h->stack_nct = pn;
-          h->stack_parts = 4;
+        // occ_part: [1] / [2] quads of 32- / 64-frame tiles, [0] pairs of 64-frame tiles
+        auto part = [&](int parts, int pn) {
+          int& occ = h->occ_part[parts == 4 ? pn : 0];
+          if (occ < 0) occ = part_h2_occupancy(parts, pn) >= 1 ? 1 : 0;
+          if (occ < 1) return false;
+          plan.form = STACK_PART; plan.parts = parts; plan.nct = pn; plan.rows = B;
           return true;
         };
         const long long t32 = (long long)B * cdiv(T, 32), t64 = (long long)B * cdiv(T, 64);
         const bool part_bufs = !capturing || (size_t)(2 * t64) <= h->part_cap;   // (sized in 32-frame tile equivalents; 2 t64 >= t32)
         if (env_part && !h->parts_off && env_nct == 0 && h->apack1q && part_bufs) {
-          if (env_quad && 4 * 8 * cdiv(t32, 8) <= h->num_cus && take_quad(1)) return B;
-          if (env_quad64 && 4 * 8 * cdiv(t64, 8) <= h->num_cus && take_quad(2)) return B;
+          if (env_quad && 4 * 8 * cdiv(t32, 8) <= h->num_cus && part(4, 1)) return plan;
+          if (env_quad64 && 4 * 8 * cdiv(t64, 8) <= h->num_cus && part(4, 2)) return plan;
           static int env_pair64 = -1;
           if (env_pair64 < 0) { const char* e = getenv("BSG_H2_PAIR64"); env_pair64 = e ? atoi(e) : 1; }
-          if (env_pair64 && 2 * 8 * cdiv(t64, 8) <= h->num_cus) {
-            if (h->occ_part[0] < 0) h->occ_part[0] = part_h2_occupancy(2, 2) >= 1 ? 1 : 0;
-            if (h->occ_part[0] >= 1) {
-              h->stack_is_h2 = true;
-              h->stack_nct = 2;
-              h->stack_parts = 2;
-              return B;
-            }
-          }
+          if (env_pair64 && 2 * 8 * cdiv(t64, 8) <= h->num_cus && part(2, 2)) return plan;
         }
       }
       // 16-row matrix tiles (residual_stack_q_kernel, diffnet_h2q.hip; round 5): the same launch with every product a v_mfma_f32_16x16x32_f16 —
       // the same matrix cycles, but the chip holds a higher clock under that shape.  BSG_H2_Q=0: the 32-row form (residual_stack_h2_kernel)
       static int env_q = -1;
       if (env_q < 0) { const char* e = getenv("BSG_H2_Q"); env_q = e ? atoi(e) : 1; }
-      h->stack_q = false;
+      bool q = false;
       if (env_q && !h->q_off && h->apack1q && h->apack2q) {
         if (h->occ_stack_h2q[nct] < 0) h->occ_stack_h2q[nct] = stack_h2q_occupancy(nct) >= 1 ? 1 : 0;
-        h->stack_q = h->occ_stack_h2q[nct] >= 1;
+        q = h->occ_stack_h2q[nct] >= 1;
       }
-      if (!h->stack_q && h->occ_stack_h2[nct] < 0) h->occ_stack_h2[nct] = stack_h2_occupancy(nct) >= 1 ? 1 : 0;
+      if (!q && h->occ_stack_h2[nct] < 0) h->occ_stack_h2[nct] = stack_h2_occupancy(nct) >= 1 ? 1 : 0;
       const int tpr = cdiv(T, 32 * nct);
-      if ((h->stack_q || h->occ_stack_h2[nct] >= 1) && tpr <= h->num_cus) {
-        int rows = h->num_cus / tpr;
-        if (rows > B) rows = B;
-        h->stack_is_h2 = true;
-        h->stack_nct = nct;
-        return rows;
+      if ((q || h->occ_stack_h2[nct] >= 1) && tpr <= h->num_cus) {
+        plan.form = q ? STACK_H2Q : STACK_H2;
+        plan.nct = nct;
+        plan.rows = h->num_cus / tpr < B ? h->num_cus / tpr : B;
+        return plan;
       }
     }
   }
@@ -1873,236 +1894,155 @@ static int stack_rows(bsg_diffnet* h, int B, int T, hipStream_t st) {
       if (h->occ_stack43 < 0) h->occ_stack43 = stack_f43_occupancy() >= 1 ? 1 : 0;
       const int tpr43 = cdiv(T, 64);
       if (h->occ_stack43 >= 1 && tpr43 <= h->num_cus) {
-        int rows43 = h->num_cus / tpr43;
-        if (rows43 > B) rows43 = B;
+        const int rows43 = h->num_cus / tpr43 < B ? h->num_cus / tpr43 : B;
         const int groups = cdiv(B, rows43);
         if (env43 == 2 || (long long)B * tpr43 * 10 >= (long long)groups * h->num_cus * 9) {   // BSG_STACK43=2: any shape (tests)
-          h->stack_is_f43 = true;
-          return rows43;
+          plan.form = STACK_F43;
+          plan.rows = rows43;
         }
       }
     }
   }
-  return 0;
+  return plan;
 }
 
-// flag values of one stack launch: launch epoch x 64 + layers published (L < 64)
-// The launch epoch of the handle's flags lives in device memory (round 4: a captured launch can be replayed): every workgroup reads it at
-// entry, the last one through its layers advances it and, before the 32-bit flag values could come round to a slot that was last written
-// long ago (a large tile index after > 2^25 launches of smaller batches), zeroes the flags and starts the epochs again (diffnet_res.h).
-static int next_stack_epoch(bsg_diffnet* h, StackArgs& p) {
+// bsg_diffnet_last_path of a stack launch
+static const char* stack_path(const StackPlan& plan, bool tail) {
+  switch (plan.form) {
+    case STACK_F43: return "stack_f43";
+    case STACK_H2: return tail ? "stack_h2_tail" : "stack_h2";
+    case STACK_H2Q: return plan.ragged ? (tail ? "stack_h2q_ragged_tail" : "stack_h2q_ragged") : tail ? "stack_h2q_tail" : "stack_h2q";
+    case STACK_PART: return plan.parts == 2 ? "stack_h2_pair64" : plan.nct == 2 ? "stack_h2_quad64" : "stack_h2_quad";
+    case STACK_BF16: return plan.ragged ? "stack_bf16_ragged" : "stack_bf16";
+    default: return "none";
+  }
+}
+
+// the part forms' exchange buffers, grown to `need32` 32-frame tile equivalents (slots scale with the tile width); a shape's first eager
+// call allocates them, a captured one cannot
+static int grow_part_bufs(bsg_diffnet* h, size_t need32, hipStream_t st) {
+  if (need32 <= h->part_cap) return BSG_OK;
+  hipStreamCaptureStatus capst = hipStreamCaptureStatusNone;
+  if (st) (void)hipStreamIsCapturing(st, &capst);
+  BSG_REQUIRE(capst == hipStreamCaptureStatusNone, "part launch: the exchange buffers of this shape are allocated by its first eager call; run it once before capturing");
+  BSG_HIP(hipStreamSynchronize(st));
+  if (h->part_zx) (void)hipFree(h->part_zx);
+  if (h->part_ix) (void)hipFree(h->part_ix);
+  if (h->part_flags) (void)hipFree(h->part_flags);
+  h->part_zx = nullptr; h->part_ix = nullptr; h->part_flags = nullptr; h->part_cap = 0;
+  const size_t cap = (size_t)h->num_cus > need32 ? (size_t)h->num_cus : need32;
+  const size_t tile_bytes = (size_t)2 * 32 * C * sizeof(unsigned short);   // all parts of a 32-frame tile: 2 planes x 32 frames x C fp16 = 32 KB
+  BSG_HIP(hipMalloc((void**)&h->part_zx, cap * tile_bytes));
+  BSG_HIP(hipMalloc((void**)&h->part_ix, 2 * cap * tile_bytes));
+  BSG_HIP(hipMalloc((void**)&h->part_flags, 2 * cap * 4 * sizeof(unsigned)));
+  BSG_HIP(hipMemsetAsync(h->part_flags, 0, 2 * cap * 4 * sizeof(unsigned), st));   // flag values are launch epoch x 64 + layer: monotonic
+  h->part_cap = cap;
+  return BSG_OK;
+}
+
+// The arguments of launch group g: rows [r0, r0 + nb) of this call's batch (r0 = g x plan.rows), or group g of the bound ragged plan —
+// a workgroup then finds its row and tile in the group's table, and every pointer is the bound batch's row 0 (rows are not contiguous
+// inside a group).
+// Flag values of one stack launch: launch epoch x 64 + layers published (L < 64).  The launch epoch of the handle's flags lives in device
+// memory (round 4: a captured launch can be replayed): every workgroup reads it at entry, the last one through its layers advances it and,
+// before the 32-bit flag values could come round to a slot that was last written long ago (a large tile index after > 2^25 launches of
+// smaller batches), zeroes the flags and starts the epochs again (diffnet_res.h).
+static int stack_args(bsg_diffnet* h, const StackPlan& plan, int g, const long long* t_dev, int t_uniform, int B, int T, hipStream_t st,
+                      unsigned long long* stamps, StackArgs& p) {
+  const int tpr = cdiv(T, 32 * plan.nct);
+  const int r0 = plan.ragged ? 0 : g * plan.rows;
+  const int nb = B - r0 < plan.rows ? B - r0 : plan.rows;
+  const size_t row = (size_t)h->row_off + r0;
+  p = StackArgs{};
+  p.x_in = h->xa + row * C * T;
+  p.skip = h->skip + row * C * T;
+  p.dproj = h->dproj; p.t_dev = t_dev ? t_dev + r0 : nullptr; p.t_uniform = t_uniform;
+  p.bias_out = h->b_out;
+  p.T = T; p.L = h->L; p.tiles_per_row = tpr;
+  p.ct_stride = (long long)2 * C * h->B * T;   // bound batch: per-layer stride of the conditioner term
+  p.n_tiles = plan.ragged ? h->rg_group_tiles[g] : nb * tpr; p.cycle = h->cfg.dilation_cycle_length;
+  BSG_REQUIRE((size_t)p.n_tiles <= h->flags_cap && h->L < 64, "stack launch: %d tiles exceed the exchange array (%zu)", p.n_tiles, h->flags_cap);
+  p.hx = h->hx; p.flags = h->flags; p.status = h->flags + h->flags_cap;
   BSG_REQUIRE(h->epoch_dev, "stack launch: no launch epoch (bsg_diffnet_prepare allocates it)");
   p.epoch = h->epoch_dev;
   p.fbase = 0;
   p.flag_words = (int)h->flags_cap;
   p.pflag_words = 0;   // part forms: set with p.pflags
-  // the flags a wrapping launch zeroes: BOTH arrays of the handle, whichever form wraps (a part launch that has to grow the part arrays
-  // replaces them below, zeroed, and updates these two)
+  // the flags a wrapping launch zeroes: BOTH arrays of the handle, whichever form wraps (a part launch replaces these with its own below)
   p.wrap_pflags = h->part_flags;
   p.wrap_pflag_words = h->part_flags ? (int)(2 * h->part_cap * 4) : 0;
   static int env_old = -1;   // BSG_DEBUG_WRAP_R04=1: round 4's behaviour (only a PART launch zeroes the part flags at a wrap) — the negative control of tests/test_gpu_handoff.py
   if (env_old < 0) { const char* e = getenv("BSG_DEBUG_WRAP_R04"); env_old = e ? atoi(e) : 0; }
   if (env_old) { p.wrap_pflags = nullptr; p.wrap_pflag_words = 0; }
-  return BSG_OK;
-}
-
-// the ragged form of the 16-row stack launch: one launch per group of the plan bound by bsg_diffnet_prepare_ragged, one after the other on
-// `st`; a workgroup finds its row and tile in the group's table, and every pointer is the bound batch's row 0 (rows are not contiguous
-// inside a group)
-static int launch_stack_ragged(bsg_diffnet* h, const long long* t_dev, int t_uniform, int T, hipStream_t st, unsigned long long* stamps,
-                               const TailArgs* tail) {
-  BSG_REQUIRE(h->ragged && h->rg_dev && h->row_off == 0 && h->cond_q_valid, "ragged stack launch: no ragged plan / conditioner quads bound");
-  const size_t bt = (size_t)h->B * T;
-  const int* tabs = h->rg_dev + ((h->B + 1) & ~1);
-  for (size_t g = 0; g < h->rg_group_tiles.size(); ++g) {
-    StackArgs p{};
-    p.x_in = h->xa;
-    p.skip = h->skip;
-    p.condterm = h->condterm;
-    p.dproj = h->dproj; p.dconv = h->dconv; p.t_dev = t_dev; p.t_uniform = t_uniform;
-    p.apackw = h->apackw; p.apack2 = h->apack2; p.bias_out = h->b_out;
-    p.T = T; p.L = h->L; p.tiles_per_row = cdiv(T, 64);
-    p.ct_stride = (long long)2 * C * (long long)bt;
-    p.n_tiles = h->rg_group_tiles[g]; p.cycle = h->cfg.dilation_cycle_length;
-    BSG_REQUIRE((size_t)p.n_tiles <= h->flags_cap && h->L < 64, "ragged stack launch: %d tiles exceed the exchange array (%zu)", p.n_tiles, h->flags_cap);
-    p.hx = h->hx; p.flags = h->flags; p.status = h->flags + h->flags_cap;
-    TRY(next_stack_epoch(h, p));
-    if (h->inject_giveup > 0) { p.inject = 1; --h->inject_giveup; }
-    p.stamps = stamps && g == 0 ? stamps : nullptr;
-    p.clk = h->prof_on && g == 0 ? h->clk : nullptr;
-    p.apack1s = h->apack1s; p.apack2s = h->apack2s; p.h2_scale = h->h2_scale;
-    p.apack1q = h->apack1q; p.apack2q = h->apack2q;
-    p.condterm_q = h->condterm_q;
+  const bool part = plan.form == STACK_PART;
+  if (h->inject_giveup > 0) { p.inject = 1; --h->inject_giveup; }
+  else if (h->inject_xcc > 0 && part) { p.inject = 2; --h->inject_xcc; }
+  else if (h->inject_nowait > 0 && part) { p.inject = 3; --h->inject_nowait; }
+  p.stamps = stamps && g == 0 ? stamps : nullptr;
+  p.clk = h->prof_on && g == 0 ? h->clk : nullptr;
+  if (plan.ragged) {
     p.vl_len = h->rg_dev;
-    p.vl_tiles = reinterpret_cast<const int2*>(tabs) + h->rg_group_off[g];
-    TRY(launch_residual_stack_h2q(p, tail, st, 2));
+    p.vl_tiles = reinterpret_cast<const int2*>(h->rg_dev + ((h->B + 1) & ~1)) + h->rg_group_off[g];   // the tables follow the lengths
   }
-  h->last_path = tail ? "stack_h2q_ragged_tail" : "stack_h2q_ragged";
-  return BSG_OK;
-}
-
-static int launch_stack(bsg_diffnet* h, const long long* t_dev, int t_uniform, int B, int T, int rows_per_launch, hipStream_t st,
-                        unsigned long long* stamps = nullptr, const TailArgs* tail = nullptr) {
-  if (h->rg_active) return launch_stack_ragged(h, t_dev, t_uniform, T, st, stamps, tail);
-  const bool f43 = h->stack_is_f43, h2 = h->stack_is_h2;   // the decision of the stack_rows() call that returned rows_per_launch
-  const int nct = h2 ? h->stack_nct : 2;
-  const int tpr = cdiv(T, 32 * nct);
-  const size_t bt = (size_t)h->B * T;   // bound batch: per-layer stride of the conditioner term
-  for (int r0 = 0; r0 < B; r0 += rows_per_launch) {
-    const int nb = B - r0 < rows_per_launch ? B - r0 : rows_per_launch;
-    const size_t row = (size_t)h->row_off + r0;
-    StackArgs p{};
-    p.x_in = h->xa + row * C * T;
-    p.skip = h->skip + row * C * T;
-    p.condterm = h->condterm + row * 2 * C * T;
-    p.dproj = h->dproj; p.dconv = h->dconv; p.t_dev = t_dev ? t_dev + r0 : nullptr; p.t_uniform = t_uniform;
-    p.apackw = h->apackw; p.apack2 = h->apack2; p.bias_out = h->b_out;
-    p.T = T; p.L = h->L; p.tiles_per_row = tpr;
-    p.ct_stride = (long long)2 * C * (long long)bt;
-    p.n_tiles = nb * tpr; p.cycle = h->cfg.dilation_cycle_length;
-    BSG_REQUIRE((size_t)p.n_tiles <= h->flags_cap && h->L < 64, "stack launch: %d tiles exceed the exchange array (%zu)", p.n_tiles, h->flags_cap);
-    p.hx = h->hx; p.flags = h->flags; p.status = h->flags + h->flags_cap;
-    TRY(next_stack_epoch(h, p));
-    if (h->inject_giveup > 0) { p.inject = 1; --h->inject_giveup; }
-    else if (h->inject_xcc > 0 && h2 && h->stack_parts) { p.inject = 2; --h->inject_xcc; }
-    else if (h->inject_nowait > 0 && h2 && h->stack_parts) { p.inject = 3; --h->inject_nowait; }
-    p.stamps = stamps && r0 == 0 ? stamps : nullptr;
-    p.clk = h->prof_on && r0 == 0 ? h->clk : nullptr;
-    if (stamps) { const char* e = getenv("BSG_STAMP_MODE"); p.stamp_mode = e ? atoi(e) : 0; }
-    if (h2 && h->stack_parts) {
-      BSG_REQUIRE(!tail && nb == B, "part launch: whole batch, no fused tail");
-      p.apack1s = h->apack1s; p.apack2s = h->apack2s; p.h2_scale = h->h2_scale;
-      const size_t need32 = (size_t)p.n_tiles * nct;   // slots scale with the tile width: size the buffers in 32-frame tile equivalents
-      if (need32 > h->part_cap) {
-        hipStreamCaptureStatus capst = hipStreamCaptureStatusNone;
-        if (st) (void)hipStreamIsCapturing(st, &capst);
-        BSG_REQUIRE(capst == hipStreamCaptureStatusNone, "part launch: the exchange buffers of this shape are allocated by its first eager call; run it once before capturing");
-        BSG_HIP(hipStreamSynchronize(st));
-        if (h->part_zx) (void)hipFree(h->part_zx);
-        if (h->part_ix) (void)hipFree(h->part_ix);
-        if (h->part_flags) (void)hipFree(h->part_flags);
-        h->part_zx = nullptr; h->part_ix = nullptr; h->part_flags = nullptr; h->part_cap = 0;
-        const size_t cap = (size_t)h->num_cus > need32 ? (size_t)h->num_cus : need32;
-        const size_t tile_bytes = (size_t)2 * 32 * C * sizeof(unsigned short);   // all parts of a 32-frame tile: 2 planes x 32 frames x C fp16 = 32 KB
-        BSG_HIP(hipMalloc((void**)&h->part_zx, cap * tile_bytes));
-        BSG_HIP(hipMalloc((void**)&h->part_ix, 2 * cap * tile_bytes));
-        BSG_HIP(hipMalloc((void**)&h->part_flags, 2 * cap * 4 * sizeof(unsigned)));
-        BSG_HIP(hipMemsetAsync(h->part_flags, 0, 2 * cap * 4 * sizeof(unsigned), st));   // flag values are launch epoch x 64 + layer: monotonic
-        h->part_cap = cap;
-      }
-      p.zx = h->part_zx; p.ix = h->part_ix; p.pflags = h->part_flags;
-      p.pflag_words = (int)(2 * h->part_cap * 4);
-      p.wrap_pflags = h->part_flags; p.wrap_pflag_words = p.pflag_words;   // (also under BSG_DEBUG_WRAP_R04: a part launch always zeroed its own)
-      p.apack1q = h->apack1q; p.apack2q = h->apack2q;
-      p.condterm_q = h->cond_q_valid ? h->condterm_q + row * 2 * C * T : nullptr;
-      TRY(launch_residual_part_h2(p, st, h->stack_parts, nct));
-    } else if (h2) {
-      p.apack1s = h->apack1s; p.apack2s = h->apack2s; p.h2_scale = h->h2_scale;
-      p.apack1q = h->apack1q; p.apack2q = h->apack2q;
-      p.condterm_q = h->stack_q && h->cond_q_valid ? h->condterm_q + row * 2 * C * T : nullptr;
-      if (tail) {   // the step tail in the same launch: its tensors start at this launch group's first row
-        TailArgs a = *tail;
-        const size_t mo = (size_t)r0 * h->M * T;
-        a.x += mo; a.xa_next += (size_t)r0 * C * T; a.quad_row0 += mo;
-        if (a.noise) a.noise += mo;
-        if (a.e_new) a.e_new += mo;
-        if (a.h1) a.h1 += mo;
-        if (a.h2) a.h2 += mo;
-        if (a.h3) a.h3 += mo;
-        TRY(h->stack_q ? launch_residual_stack_h2q(p, &a, st, nct) : launch_residual_stack_h2(p, &a, st, nct));
-      } else {
-        TRY(h->stack_q ? launch_residual_stack_h2q(p, nullptr, st, nct) : launch_residual_stack_h2(p, nullptr, st, nct));
-      }
-    } else if (f43) {
-      p.apackw43 = h->apackw43;
-      TRY(launch_residual_stack_f43(p, st));
-    } else {
-      set_error("stack launch: no launch form selected");
-      return BSG_ESTATE;
-    }
-  }
-  BSG_REQUIRE(!tail || h2, "stack launch: a fused tail needs the split-fp16 form");
-  h->last_path = h2 ? (h->stack_parts == 2 ? "stack_h2_pair64" : h->stack_parts ? (h->stack_nct == 2 ? "stack_h2_quad64" : "stack_h2_quad") : h->stack_q ? (tail ? "stack_h2q_tail" : "stack_h2q") : tail ? "stack_h2_tail" : "stack_h2") : "stack_f43";
-  return BSG_OK;
-}
-
-// bf16-operand configuration: the stack launch (the default; BSG_STACK_BF16=0 selects per-layer launches).  64-frame tiles, one
-// workgroup per CU (256 registers per wave), whole rows per launch group.  Measured on one box, ms per 100-step pass at T=1000,
-// stack / per-layer: B=1 43.2 / 56.4, B=16 58.2 / 87.8, B=32 109.7 / 133.3, B=64 213.8 / 237.3 (tools/bench_small.py with
-// BSG_DTYPE=bf16).  Per layer and tile ~21.5 us, of which the two GEMMs' MFMAs are ~7.
-static int stack_rows_bf16(bsg_diffnet* h, int B, int T, hipStream_t st) {
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("BSG_STACK_BF16"); env = e ? atoi(e) : 1; }
-  if (!env || h->compute != BSG_COMPUTE_BF16 || h->split_off || !h->num_cus || !h->hx || !h->epoch_dev) return 0;
-  (void)st;
-  if (h->occ_stack_h < 0) h->occ_stack_h = stack_bf16_occupancy() >= 1 ? 1 : 0;
-  if (h->rg_active) return h->occ_stack_h >= 1 ? B : 0;   // a ragged call (ragged_launch_ok checked it): groups from the bound plan
-  const int tpr = cdiv(T, 64);
-  const long long slots = (long long)h->occ_stack_h * h->num_cus;
-  if (h->occ_stack_h < 1 || tpr > slots) return 0;
-  int rows = (int)(slots / tpr);
-  if (rows > B) rows = B;
-  return rows;
-}
-
-// the ragged form of the bf16 stack launch: one launch per group of the plan bound by bsg_diffnet_prepare_ragged, one after the other on
-// `st`; a workgroup finds its row and tile in the group's table, and every pointer is the bound batch's row 0
-static int launch_stack_bf16_ragged(bsg_diffnet* h, const long long* t_dev, int t_uniform, int T, hipStream_t st, unsigned long long* stamps) {
-  BSG_REQUIRE(h->ragged && h->rg_dev && h->row_off == 0, "ragged bf16 stack launch: no ragged plan bound");
-  const size_t bt = (size_t)h->B * T;
-  const int* tabs = h->rg_dev + ((h->B + 1) & ~1);
-  for (size_t g = 0; g < h->rg_group_tiles.size(); ++g) {
-    StackArgs p{};
-    p.x_in = h->xa;
-    p.skip = h->skip;
-    p.skip_h = h->skip_h;
-    p.condterm_h = h->condterm_h;
-    p.dproj = h->dproj; p.t_dev = t_dev; p.t_uniform = t_uniform;
-    p.apack1h = h->apack1h; p.apack2h = h->apack2h; p.bias_out = h->b_out;
-    p.T = T; p.L = h->L; p.tiles_per_row = cdiv(T, 64);
-    p.ct_stride = (long long)2 * C * (long long)bt;
-    p.n_tiles = h->rg_group_tiles[g]; p.cycle = h->cfg.dilation_cycle_length;
-    BSG_REQUIRE((size_t)p.n_tiles <= h->flags_cap && h->L < 64, "ragged bf16 stack launch: %d tiles exceed the exchange array (%zu)", p.n_tiles, h->flags_cap);
-    p.hx = h->hx; p.flags = h->flags; p.status = h->flags + h->flags_cap;
-    TRY(next_stack_epoch(h, p));
-    if (h->inject_giveup > 0) { p.inject = 1; --h->inject_giveup; }
-    p.stamps = stamps && g == 0 ? stamps : nullptr;
-    p.clk = h->prof_on && g == 0 ? h->clk : nullptr;
-    p.vl_len = h->rg_dev;
-    p.vl_tiles = reinterpret_cast<const int2*>(tabs) + h->rg_group_off[g];
-    TRY(launch_residual_stack_bf16(p, st));
-  }
-  h->last_path = "stack_bf16_ragged";
-  return BSG_OK;
-}
-
-static int launch_stack_bf16(bsg_diffnet* h, const long long* t_dev, int t_uniform, int B, int T, int rows_per_launch, hipStream_t st,
-                             unsigned long long* stamps = nullptr) {
-  if (h->rg_active) return launch_stack_bf16_ragged(h, t_dev, t_uniform, T, st, stamps);
-  const int tpr = cdiv(T, 64);
-  const size_t bt = (size_t)h->B * T;
-  for (int r0 = 0; r0 < B; r0 += rows_per_launch) {
-    const int nb = B - r0 < rows_per_launch ? B - r0 : rows_per_launch;
-    const size_t row = (size_t)h->row_off + r0;
-    StackArgs p{};
-    p.x_in = h->xa + row * C * T;
-    p.skip = h->skip + row * C * T;
+  if (plan.form == STACK_BF16) {
     p.skip_h = h->skip_h + row * C * T;
     p.condterm_h = h->condterm_h + row * 2 * C * T;
-    p.dproj = h->dproj; p.t_dev = t_dev ? t_dev + r0 : nullptr; p.t_uniform = t_uniform;
-    p.apack1h = h->apack1h; p.apack2h = h->apack2h; p.bias_out = h->b_out;
-    p.T = T; p.L = h->L; p.tiles_per_row = tpr;
-    p.ct_stride = (long long)2 * C * (long long)bt;
-    p.n_tiles = nb * tpr; p.cycle = h->cfg.dilation_cycle_length;
-    BSG_REQUIRE((size_t)p.n_tiles <= h->flags_cap && h->L < 64, "bf16 stack launch: %d tiles exceed the exchange array (%zu)", p.n_tiles, h->flags_cap);
-    p.hx = h->hx; p.flags = h->flags; p.status = h->flags + h->flags_cap;
-    TRY(next_stack_epoch(h, p));
-    if (h->inject_giveup > 0) { p.inject = 1; --h->inject_giveup; }
-    p.stamps = stamps && r0 == 0 ? stamps : nullptr;
-    p.clk = h->prof_on && r0 == 0 ? h->clk : nullptr;
-    TRY(launch_residual_stack_bf16(p, st));
+    p.apack1h = h->apack1h; p.apack2h = h->apack2h;
+    return BSG_OK;
   }
-  h->last_path = "stack_bf16";
+  p.condterm = h->condterm + row * 2 * C * T;
+  p.dconv = h->dconv; p.apackw = h->apackw; p.apack2 = h->apack2;
+  if (stamps) { const char* e = getenv("BSG_STAMP_MODE"); p.stamp_mode = e ? atoi(e) : 0; }
+  if (plan.form == STACK_F43) {
+    p.apackw43 = h->apackw43;
+    return BSG_OK;
+  }
+  p.apack1s = h->apack1s; p.apack2s = h->apack2s; p.h2_scale = h->h2_scale;
+  p.apack1q = h->apack1q; p.apack2q = h->apack2q;
+  p.condterm_q = plan.form != STACK_H2 && h->cond_q_valid ? h->condterm_q + row * 2 * C * T : nullptr;
+  if (part) {
+    TRY(grow_part_bufs(h, (size_t)p.n_tiles * plan.nct, st));
+    p.zx = h->part_zx; p.ix = h->part_ix; p.pflags = h->part_flags;
+    p.pflag_words = (int)(2 * h->part_cap * 4);
+    p.wrap_pflags = h->part_flags; p.wrap_pflag_words = p.pflag_words;   // (also under BSG_DEBUG_WRAP_R04: a part launch always zeroed its own)
+  }
+  return BSG_OK;
+}
+
+// the planned stack launch of rows [h->row_off, h->row_off + B): its launch groups one after the other on `st`; `tail`: the sampler
+// step's tail in the same launch (split-fp16 forms)
+static int launch_stack(bsg_diffnet* h, const StackPlan& plan, const long long* t_dev, int t_uniform, int B, int T, hipStream_t st,
+                        unsigned long long* stamps = nullptr, const TailArgs* tail = nullptr) {
+  BSG_REQUIRE(plan.form != STACK_NONE && plan.rows > 0, "stack launch: no launch form selected");
+  BSG_REQUIRE(!tail || plan.form == STACK_H2 || plan.form == STACK_H2Q, "stack launch: a fused tail needs the split-fp16 form");
+  BSG_REQUIRE(plan.form != STACK_PART || (!tail && plan.rows >= B), "part launch: whole batch, no fused tail");
+  BSG_REQUIRE(!plan.ragged || (h->ragged && h->rg_dev && h->row_off == 0 && (plan.form == STACK_BF16 || h->cond_q_valid)),
+              "ragged stack launch: no ragged plan / conditioner quads bound");
+  const int groups = plan.ragged ? (int)h->rg_group_tiles.size() : cdiv(B, plan.rows);
+  for (int g = 0; g < groups; ++g) {
+    StackArgs p;
+    TRY(stack_args(h, plan, g, t_dev, t_uniform, B, T, st, stamps, p));
+    TailArgs a{};
+    if (tail) {   // the step tail in the same launch: its tensors start at this launch group's first row
+      a = *tail;
+      const size_t r0 = plan.ragged ? 0 : (size_t)g * plan.rows;
+      const size_t mo = r0 * h->M * T;
+      a.x += mo; a.xa_next += r0 * C * T; a.quad_row0 += mo;
+      if (a.noise) a.noise += mo;
+      if (a.e_new) a.e_new += mo;
+      if (a.h1) a.h1 += mo;
+      if (a.h2) a.h2 += mo;
+      if (a.h3) a.h3 += mo;
+    }
+    switch (plan.form) {
+      case STACK_F43: TRY(launch_residual_stack_f43(p, st)); break;
+      case STACK_H2: TRY(launch_residual_stack_h2(p, tail ? &a : nullptr, st, plan.nct)); break;
+      case STACK_H2Q: TRY(launch_residual_stack_h2q(p, tail ? &a : nullptr, st, plan.nct)); break;
+      case STACK_PART: TRY(launch_residual_part_h2(p, st, plan.parts, plan.nct)); break;
+      default: TRY(launch_residual_stack_bf16(p, st)); break;
+    }
+  }
+  h->last_path = stack_path(plan, tail != nullptr);
   return BSG_OK;
 }
 
@@ -2175,40 +2115,44 @@ struct RaggedScope {
 
 // Does the launch this shape takes read the ROW layout of the conditioner term?  (The 16-row stack launch and the part forms read the quads,
 // the bf16 launches the bf16 quads; everything else — 32-row launch, F(4,3), per-layer and channel-split kernels — the rows.)
-static bool cond_rows_needed(bsg_diffnet* h, int B, int T, hipStream_t st) {
+static bool cond_rows_needed(const bsg_diffnet* h, const StackPlan& plan) {
   if (h->compute == BSG_COMPUTE_BF16) return false;
-  const int srows = h->no_split ? 0 : stack_rows(h, B, T, st);
-  return !(srows && h->stack_is_h2 && h->cond_q_valid && (h->stack_parts || h->stack_q));
+  return !((plan.form == STACK_H2Q || plan.form == STACK_PART) && h->cond_q_valid);
 }
-static int cond_layout_for(bsg_diffnet* h, int B, int T, hipStream_t st) {
-  return cond_rows_needed(h, B, T, st) ? ensure_cond_rows(h, st) : BSG_OK;
+static int cond_layout_for(bsg_diffnet* h, const StackPlan& plan, hipStream_t st) {
+  return cond_rows_needed(h, plan) ? ensure_cond_rows(h, st) : BSG_OK;
 }
 
-// eps = DiffNet(x, t); t either per-row on the device or uniform
-static int forward_impl(bsg_diffnet* h, const float* x, const long long* t_dev, int t_uniform, float* eps, int B, int T,
-                        hipStream_t st) {
-  TRY(conv1x1(h->w_in, h->b_in, x, h->xa, C, h->M, B, T, ACT_RELU, st));  // net.py:116-118
-  float* cur = h->xa;
-  float* nxt = h->xb;
+// The L residual layers of one evaluation of rows [h->row_off, h->row_off + B): input h->xa (the in-projection of x), output the skip sum
+// in h->skip(_h).  The planned stack launch — with the sampler step's tail inside it when `tail` is given — or one launch per layer.
+static int run_layers(bsg_diffnet* h, const StackPlan& plan, const long long* t_dev, int t_uniform, int B, int T, hipStream_t st,
+                      const TailArgs* tail = nullptr) {
   const bool prof = h->prof_on && h->prof_used + 2 <= h->prof_ev.size();
   if (prof) BSG_HIP(hipEventRecord(h->prof_ev[h->prof_used], st));
-  const int srows = stack_rows(h, B, T, st);
-  const int hrows = stack_rows_bf16(h, B, T, st);
-  if (hrows) {
-    TRY(launch_stack_bf16(h, t_dev, t_uniform, B, T, hrows, st));
-  } else if (srows) {
-    TRY(launch_stack(h, t_dev, t_uniform, B, T, srows, st));
+  if (plan.form != STACK_NONE) {
+    TRY(launch_stack(h, plan, t_dev, t_uniform, B, T, st, nullptr, tail));
   } else {
+    const size_t off = (size_t)h->row_off * C * T;
+    float* cur = h->xa + off;
+    float* nxt = h->xb + off;
     for (int l = 0; l < h->L; ++l) {
-      TRY(launch_layer(h, l, cur, t_dev, t_uniform, nxt, h->skip, B, T, st));
+      TRY(launch_layer(h, l, cur, t_dev, t_uniform, nxt, h->skip + off, B, T, st));
       float* tmp = cur; cur = nxt; nxt = tmp;
     }
   }
   if (prof) {
     BSG_HIP(hipEventRecord(h->prof_ev[h->prof_used + 1], st));
     h->prof_used += 2;
-    h->prof_launches += h->L;
+    h->prof_launches += h->L;   // layer-equivalents (a stack launch runs L layers in one kernel; a fused tail is ~1 % of its FLOPs)
   }
+  return BSG_OK;
+}
+
+// eps = DiffNet(x, t); t either per-row on the device or uniform
+static int forward_impl(bsg_diffnet* h, const StackPlan& plan, const float* x, const long long* t_dev, int t_uniform, float* eps, int B, int T,
+                        hipStream_t st) {
+  TRY(conv1x1(h->w_in, h->b_in, x, h->xa, C, h->M, B, T, ACT_RELU, st));  // net.py:116-118
+  TRY(run_layers(h, plan, t_dev, t_uniform, B, T, st));
   if (h->compute == BSG_COMPUTE_BF16) TRY(quad_bf16_to_f32(h->skip_h, h->skip, B, C, T, st));
   if (h->rg_active) {   // ragged: the stack launch stored no skip sum at a row's padding; the projections below read every frame of B x T
     hipLaunchKernelGGL(ragged_zero_pad_kernel, dim3(cdiv(T, 256), C, B), dim3(256), 0, st, h->skip, (const int*)h->rg_dev, C, T);
@@ -2230,8 +2174,9 @@ extern "C" int bsg_diffnet_forward(bsg_diffnet* h, const float* x, const int64_t
   BSG_REQUIRE(x && t && eps, "diffnet_forward: null argument");
   TRY(ragged_enter(h, (hipStream_t)stream, "diffnet_forward"));
   RaggedScope ragged_scope(h);
-  TRY(cond_layout_for(h, B, T, (hipStream_t)stream));
-  return forward_impl(h, x, (const long long*)t, 0, eps, B, T, (hipStream_t)stream);
+  const StackPlan plan = plan_stack(h, B, T, (hipStream_t)stream);
+  TRY(cond_layout_for(h, plan, (hipStream_t)stream));
+  return forward_impl(h, plan, x, (const long long*)t, 0, eps, B, T, (hipStream_t)stream);
 }
 
 extern "C" int bsg_diffnet_residual_layer(bsg_diffnet* h, int32_t layer, const float* x_in, const int64_t* t, float* x_out,
@@ -2251,33 +2196,6 @@ static int check_schedule(const bsg_schedule* s, const char* who, bool plms) {
                s->posterior_mean_coef2 && s->sigma)) {
     set_error("%s: schedule array missing", who);
     return BSG_EINVAL;
-  }
-  return BSG_OK;
-}
-
-// the 20 residual layers of one evaluation, input h->xa (the in-projection of x), output = the skip sum in h->skip(_h)
-static int layers_from_xa(bsg_diffnet* h, int t_uniform, int B, int T, hipStream_t st) {
-  const size_t off = (size_t)h->row_off * C * T;
-  float* cur = h->xa + off;
-  float* nxt = h->xb + off;
-  const bool prof = h->prof_on && h->prof_used + 2 <= h->prof_ev.size();
-  if (prof) BSG_HIP(hipEventRecord(h->prof_ev[h->prof_used], st));
-  const int srows = h->no_split ? 0 : stack_rows(h, B, T, st);
-  const int hrows = stack_rows_bf16(h, B, T, st);
-  if (hrows) {
-    TRY(launch_stack_bf16(h, nullptr, t_uniform, B, T, hrows, st));
-  } else if (srows) {
-    TRY(launch_stack(h, nullptr, t_uniform, B, T, srows, st));
-  } else {
-    for (int l = 0; l < h->L; ++l) {
-      TRY(launch_layer(h, l, cur, nullptr, t_uniform, nxt, h->skip + off, B, T, st));
-      float* tmp = cur; cur = nxt; nxt = tmp;
-    }
-  }
-  if (prof) {
-    BSG_HIP(hipEventRecord(h->prof_ev[h->prof_used + 1], st));
-    h->prof_used += 2;
-    h->prof_launches += h->L;   // layer-equivalents (the stack launch runs L layers in one kernel)
   }
   return BSG_OK;
 }
@@ -2333,29 +2251,22 @@ static int launch_tail(bsg_diffnet* h, TailArgs& a, float* x, int B, int T, hipS
 }
 
 // One sampler step from the in-projected x in h->xa: the residual stack, then the tail (`a` carries the sampler-specific fields).  When
-// the stack runs as the split-fp16 launch, the tail runs inside it (one launch per step; BSG_H2_TAIL=0: two launches).
-static int step_from_xa(bsg_diffnet* h, int t_uniform, TailArgs& a, float* x, int B, int T, hipStream_t st) {
+// the stack runs as the split-fp16 launch, the tail runs inside it (one launch per step; BSG_H2_TAIL=0: two launches).  A ragged call
+// always fuses it (ragged_launch_ok checked the tail's weights).
+static int step_from_xa(bsg_diffnet* h, const StackPlan& plan, int t_uniform, TailArgs& a, float* x, int B, int T, hipStream_t st) {
   static int env = -1;
   if (env < 0) { const char* e = getenv("BSG_H2_TAIL"); env = e ? atoi(e) : 1; }
-  const int srows = (!h->rg_active && (h->no_split || h->compute != BSG_COMPUTE_F32 || !env || !h->tail_s || h->M > 96)) ? 0 : stack_rows(h, B, T, st);
-  if (srows && h->stack_is_h2 && !h->stack_parts) {
+  const bool h2_tail = plan.ragged || (env && h->tail_s && h->M <= 96);
+  if (h2_tail && (plan.form == STACK_H2 || plan.form == STACK_H2Q)) {
     const size_t off = (size_t)h->row_off * C * T;
     a.x = x; a.xa_next = h->xa + off;
     a.b_skip = h->b_skip; a.b_fin = h->b_fin96; a.b_in = h->b_in;
     a.B = B; a.T = T; a.M = h->M; a.tiles_per_row = cdiv(T, 64);
     a.ws_s = h->tail_s; a.wo_s = h->tail_s + 2 * C * C; a.wi_s = h->tail_s + 2 * C * C + 2 * 96 * C; a.tail_scale = h->tail_scale;
-    const bool prof = h->prof_on && h->prof_used + 2 <= h->prof_ev.size();
-    if (prof) BSG_HIP(hipEventRecord(h->prof_ev[h->prof_used], st));
-    TRY(launch_stack(h, nullptr, t_uniform, B, T, srows, st, nullptr, &a));
-    if (prof) {
-      BSG_HIP(hipEventRecord(h->prof_ev[h->prof_used + 1], st));
-      h->prof_used += 2;
-      h->prof_launches += h->L;   // layer-equivalents; the launch also carries the step tail (~1 % of its FLOPs)
-    }
-    return BSG_OK;
+    return run_layers(h, plan, nullptr, t_uniform, B, T, st, &a);
   }
-  TRY(layers_from_xa(h, t_uniform, B, T, st));
-  if (srows && h->stack_is_h2 && h->stack_parts && strncmp(h->last_path, "stack_h2_", 9) == 0) {
+  TRY(run_layers(h, plan, nullptr, t_uniform, B, T, st));
+  if (h2_tail && plan.form == STACK_PART) {
     // behind a part launch: the tail on the 16-bit matrix pipe too (step_tail_h2_kernel; BSG_H2_TAIL=0: the fp32-pipe tail)
     const size_t off = (size_t)h->row_off * C * T;
     a.skip = h->skip + off; a.skip_h = nullptr;
@@ -2369,19 +2280,20 @@ static int step_from_xa(bsg_diffnet* h, int t_uniform, TailArgs& a, float* x, in
   return launch_tail(h, a, x, B, T, st);
 }
 
-struct SubBatch { int off, B; hipStream_t st; };
+struct SubBatch { int off, B; hipStream_t st; StackPlan plan; };
 
 // Two half-batches on two streams.  One launch per layer puts all workgroups of the chip in the same phase (they stage, hit
 // the gate and drain together, and the younger of the two workgroups of a CU finishes alone); two independent launch chains
 // drift apart and fill each other's gaps: measured 239.6 -> 226.5 ms per 100 steps at B=16, T=1000 (+5.8 %), +4.0 % at B=32,
 // +9.9 % at B=12, +1.2 % at B=64, +4 % for the bf16 form at B=64; four chains are worse (a CU only holds two of these
 // workgroups).  On one of the boxes measured the two chains brought no gain (and no loss).  BSG_DUAL=0 disables.
-// Returns the number of sub-batches (1 or 2) and, for 2, forks the second stream off `st`.
-static int dual_fork(bsg_diffnet* h, int B, int T, hipStream_t st, SubBatch (&subs)[2]) {
+// Returns the number of sub-batches (1 or 2) and, for 2, forks the second stream off `st` and plans each half in the launch state it
+// runs under.  `plan`: the whole batch's.
+static int dual_fork(bsg_diffnet* h, const StackPlan& plan, int B, int T, hipStream_t st, SubBatch (&subs)[2]) {
   static int dual_env = -1;
   if (dual_env < 0) { const char* e = getenv("BSG_DUAL"); dual_env = e ? atoi(e) : 1; }
-  subs[0] = SubBatch{0, B, st};
-  subs[1] = SubBatch{0, 0, nullptr};
+  subs[0] = SubBatch{0, B, st, plan};
+  subs[1] = SubBatch{0, 0, nullptr, StackPlan{}};
   const long long tiles = (long long)B * cdiv(T, 32);
   const bool big = tiles > h->num_cus;
   // 129..256 tiles (B = 5..8): two chains of channel-split launches (each workgroup half the matrix work, two per CU, one of each
@@ -2406,7 +2318,7 @@ static int dual_fork(bsg_diffnet* h, int B, int T, hipStream_t st, SubBatch (&su
     }
     small = ok && cus <= (double)h->num_cus;
   }
-  const bool dual = dual_env && B >= 2 && use_wino() && !stack_rows(h, B, T, st) && !stack_rows_bf16(h, B, T, st) && (big || small);
+  const bool dual = dual_env && B >= 2 && use_wino() && plan.form == STACK_NONE && (big || small);
   if (!dual) return 1;
   if (!h->st2) {
     if (hipStreamCreateWithFlags(&h->st2, hipStreamNonBlocking) != hipSuccess ||
@@ -2415,10 +2327,10 @@ static int dual_fork(bsg_diffnet* h, int B, int T, hipStream_t st, SubBatch (&su
       return 1;
   }
   if (hipEventRecord(h->ev_fork, st) != hipSuccess || hipStreamWaitEvent(h->st2, h->ev_fork, 0) != hipSuccess) return 1;
-  subs[0] = SubBatch{0, B / 2, st};
-  subs[1] = SubBatch{B / 2, B - B / 2, h->st2};
   h->no_split = big;
   h->split_small_lds = small;
+  subs[0] = SubBatch{0, B / 2, st, plan_stack(h, B / 2, T, st)};
+  subs[1] = SubBatch{B / 2, B - B / 2, h->st2, plan_stack(h, B - B / 2, T, h->st2)};
   return 2;
 }
 
@@ -2452,14 +2364,15 @@ extern "C" int bsg_ddpm_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
   BSG_REQUIRE(n % 4 == 0, "ddpm_sample: B*M*T must be a multiple of 4");
   TRY(ragged_enter(h, st, "ddpm_sample"));
   RaggedScope ragged_scope(h);
-  TRY(cond_layout_for(h, B, T, st));
+  const StackPlan plan = plan_stack(h, B, T, st);
+  TRY(cond_layout_for(h, plan, st));
   const long long n4 = n / 4;
   const unsigned long long quad0 = (unsigned long long)row0 * h->M * T / 4;
   const bool fused = fused_tail_ok(h);
   if (!fused) {
     for (int k = 0; k < n_steps; ++k) {
       const int i = t_start - k;
-      TRY(forward_impl(h, x, nullptr, i, h->eps, B, T, st));
+      TRY(forward_impl(h, plan, x, nullptr, i, h->eps, B, T, st));
       StepCoef c{s->sqrt_recip_alphas_cumprod[i], s->sqrt_recipm1_alphas_cumprod[i], s->posterior_mean_coef1[i],
                  s->posterior_mean_coef2[i], s->sigma[i]};
       hipLaunchKernelGGL(ddpm_step_kernel, dim3(cdiv(n4, 256)), dim3(256), 0, st, x, (const float*)h->eps,
@@ -2471,8 +2384,8 @@ extern "C" int bsg_ddpm_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
   // fused loop: [in-projection once] -> per step: 20 residual layers -> step_tail_kernel (skip projection, output
   // projection, sampler update, next step's in-projection)
   SubBatch subs[2];
-  const int n_sub = n_steps > 0 && !h->rg_active ? dual_fork(h, B, T, st, subs) : 1;
-  if (n_sub == 1) subs[0] = SubBatch{0, B, st};
+  const int n_sub = n_steps > 0 && !h->rg_active ? dual_fork(h, plan, B, T, st, subs) : 1;
+  if (n_sub == 1) subs[0] = SubBatch{0, B, st, plan};
   int rc = BSG_OK;
   for (int u = 0; u < n_sub && rc == BSG_OK; ++u)
     rc = conv1x1(h->w_in, h->b_in, x + (size_t)subs[u].off * h->M * T, h->xa + (size_t)subs[u].off * C * T, C, h->M, subs[u].B, T, ACT_RELU,
@@ -2487,7 +2400,7 @@ extern "C" int bsg_ddpm_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
                      s->posterior_mean_coef2[i], s->sigma[i]};
       a.seed = seed; a.quad_row0 = (unsigned long long)(row0 + subs[u].off) * h->M * T; a.stream = (unsigned)(i + 1);
       a.do_head = k + 1 < n_steps;
-      rc = step_from_xa(h, i, a, x + (size_t)subs[u].off * h->M * T, subs[u].B, T, subs[u].st);
+      rc = step_from_xa(h, subs[u].plan, i, a, x + (size_t)subs[u].off * h->M * T, subs[u].B, T, subs[u].st);
     }
   }
   rc = dual_join(h, n_sub, st, rc);
@@ -2564,7 +2477,7 @@ extern "C" int bsg_diffnet_uses_handoffs(bsg_diffnet* h, int32_t B, int32_t T, i
   // conservative: any launch shape for which a channel-split (pair / 4-way) or the stack launch may be chosen
   const long long tiles = (long long)B * cdiv(T, 32);
   const bool split = h->compute == BSG_COMPUTE_F32 && use_wino() && split_env() && !h->split_off && h->num_cus && tiles <= h->num_cus;
-  *uses = (split || stack_rows(h, B, T, nullptr) > 0 || stack_rows_bf16(h, B, T, nullptr) > 0) ? 1 : 0;
+  *uses = (split || plan_stack(h, B, T, nullptr).form != STACK_NONE) ? 1 : 0;
   return BSG_OK;
 }
 
@@ -2639,15 +2552,11 @@ extern "C" int bsg_diffnet_debug_stack_stamps(bsg_diffnet* h, int32_t t_uniform,
   GuardScope guard_scope(h ? &h->guard : nullptr);
   TRY(check_bound(h, B, T, "diffnet_debug_stack_stamps"));
   BSG_REQUIRE(stamps, "diffnet_debug_stack_stamps: null stamps");
-  TRY(cond_layout_for(h, B, T, (hipStream_t)stream));
-  if (h->compute == BSG_COMPUTE_BF16) {
-    const int hrows = stack_rows_bf16(h, B, T, (hipStream_t)stream);
-    BSG_REQUIRE(hrows >= B, "diffnet_debug_stack_stamps: (B=%d,T=%d) does not run as one bf16 stack launch", B, T);
-    return launch_stack_bf16(h, nullptr, t_uniform, B, T, hrows, (hipStream_t)stream, (unsigned long long*)stamps);
-  }
-  const int rows = stack_rows(h, B, T, (hipStream_t)stream);
-  BSG_REQUIRE(rows >= B, "diffnet_debug_stack_stamps: (B=%d,T=%d) does not run as one stack launch", B, T);
-  return launch_stack(h, nullptr, t_uniform, B, T, rows, (hipStream_t)stream, (unsigned long long*)stamps);
+  const StackPlan plan = plan_stack(h, B, T, (hipStream_t)stream);
+  TRY(cond_layout_for(h, plan, (hipStream_t)stream));
+  BSG_REQUIRE(plan.form != STACK_NONE && plan.rows >= B, "diffnet_debug_stack_stamps: (B=%d,T=%d) does not run as one %sstack launch", B, T,
+              h->compute == BSG_COMPUTE_BF16 ? "bf16 " : "");
+  return launch_stack(h, plan, nullptr, t_uniform, B, T, (hipStream_t)stream, (unsigned long long*)stamps);
 }
 
 extern "C" const char* bsg_diffnet_last_path(bsg_diffnet* h) { return h ? h->last_path : "none"; }
@@ -2742,7 +2651,8 @@ extern "C" int bsg_plms_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
   BSG_REQUIRE(h->xpred, "plms_sample: history buffers missing (bsg_diffnet_prepare allocates them)");
   TRY(ragged_enter(h, st, "plms_sample"));
   RaggedScope ragged_scope(h);
-  TRY(cond_layout_for(h, B, T, st));
+  const StackPlan plan = plan_stack(h, B, T, st);
+  TRY(cond_layout_for(h, plan, st));
   const dim3 grid(cdiv((long long)n, 256)), block(256);
   // the unfused update (first iteration); ragged: on each row's own frames only
   auto plms_step = [&](const float* xi, float* xo, const float* e0, const float* e1, const float* e2, const float* e3, const PlmsCoef& k) {
@@ -2768,8 +2678,8 @@ extern "C" int bsg_plms_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
       // fused iteration: h->xa already holds the in-projection of x (left by the previous iteration); the tail projects the skip
       // sum to eps, stores it to the history slot, applies the multistep update to x and projects the new x for the next one
       if (n_sub == 0) {   // the first fused iteration forks the two half-batch chains (not for a ragged batch: one chain of its launch groups)
-        if (h->rg_active) { subs[0] = SubBatch{0, B, st}; n_sub = 1; }
-        else n_sub = dual_fork(h, B, T, st, subs);
+        if (h->rg_active) { subs[0] = SubBatch{0, B, st, plan}; n_sub = 1; }
+        else n_sub = dual_fork(h, plan, B, T, st, subs);
       }
       for (int u = 0; u < n_sub && rc == BSG_OK; ++u) {
         const size_t mo = (size_t)subs[u].off * h->M * T;
@@ -2780,14 +2690,14 @@ extern "C" int bsg_plms_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
         else if (n_hist == 2) { a.pk.w0 = 23.f; a.pk.w1 = -16.f; a.pk.w2 = 5.f; a.pk.inv = 12.f; }
         else { a.pk.w0 = 55.f; a.pk.w1 = -59.f; a.pk.w2 = 37.f; a.pk.w3 = -9.f; a.pk.inv = 24.f; }
         a.do_head = i - interval >= 0;
-        rc = step_from_xa(h, i, a, x + mo, subs[u].B, T, subs[u].st);
+        rc = step_from_xa(h, subs[u].plan, i, a, x + mo, subs[u].B, T, subs[u].st);
       }
       if (rc != BSG_OK) break;
       hist[3] = hist[2]; hist[2] = hist[1]; hist[1] = hist[0]; hist[0] = e_new;
       if (n_hist < 3) ++n_hist;
       continue;
     }
-    TRY(forward_impl(h, x, nullptr, i, e_new, B, T, st));
+    TRY(forward_impl(h, plan, x, nullptr, i, e_new, B, T, st));
     if (n_hist == 0) {
       c.inv = 1.f;
       // ragged: the predictor below writes x_pred on each row's frames only; its padding takes x's (finite, the caller's), which the
@@ -2795,7 +2705,7 @@ extern "C" int bsg_plms_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
       if (h->rg_active) BSG_HIP(hipMemcpyAsync(h->xpred, x, n * sizeof(float), hipMemcpyDeviceToDevice, st));
       plms_step((const float*)x, h->xpred, (const float*)e_new,
                          (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, c);
-      TRY(forward_impl(h, h->xpred, nullptr, ip, h->eps, B, T, st));
+      TRY(forward_impl(h, plan, h->xpred, nullptr, ip, h->eps, B, T, st));
       c.w0 = 1.f; c.inv = 2.f;
       plms_step((const float*)x, x, (const float*)e_new, (const float*)h->eps,
                          (const float*)nullptr, (const float*)nullptr, c);

@@ -33,7 +33,7 @@ PAIR = net.last_path() in ('stack_h2_quad', 'stack_h2_quad64', 'stack_h2_pair64'
 NTILE = 64 if DT == 'bf16' or F43 or H2 else 32
 if PAIR:
     NTILE = 64 if net.last_path().endswith('64') else 32
-if H2:   # the split-fp16 launch picks 32-frame tiles when the 64-frame ones would fill at most half of the CUs (stack_rows, diffnet.hip)
+if H2:   # the split-fp16 launch picks 32-frame tiles when the 64-frame ones would fill at most half of the CUs (plan_stack, diffnet.hip)
     nct = int(os.environ.get('BSG_H2_NCT', '0')) or (2 if B * ((T + 63) // 64) * 2 > 256 else 1)
     NTILE = 32 * nct
 tiles, L = B * ((T + NTILE - 1) // NTILE), 20
