@@ -15,7 +15,10 @@
 //     (SGPR operands of v_fma): the inner loop is one ds_read_b32 per CO_BLK FMAs;
 //   * bias, residual add, the MRF sum / num_kernels and tanh are fused epilogues.
 #include <math.h>
+#include <stdarg.h>
+#include <stdio.h>
 
+#include <string>
 #include <vector>
 
 #include "bsg_common.h"
@@ -27,6 +30,12 @@ using f32x2 = __attribute__((ext_vector_type(2))) float;
 // samples per lane TT (stride 256) is a template parameter: 4 when the launch fills the chip anyway, 2 or 1 for short
 // inputs (B = 1), where 1024-sample tiles leave most CUs without a workgroup
 constexpr int CI_CHUNK = 8;
+
+// the tile variant of the last launch, written by the launcher that chose it; hifigan_run() copies it into the handle's launch record
+// (bsg_hifigan_last_path).  Host side only.
+thread_local const char* hg_variant = "";
+template <int N>
+constexpr const char* tt_name() { return N == 8 ? "TT8" : N == 4 ? "TT4" : N == 2 ? "TT2" : "TT1"; }
 
 struct ConvArgs {
   const float* x;      // [B][Cin][L]
@@ -708,6 +717,7 @@ template <int K, int TT>
 int launch_conv_kt(const ConvArgs& a, int B, hipStream_t st) {
   constexpr int TILE = 256 * TT;
   const size_t lds = (size_t)CI_CHUNK * (TILE + (K - 1) * a.dil) * sizeof(float);
+  hg_variant = tt_name<TT>();
   if (a.Cout >= 16) {
     dim3 grid(cdiv(a.L, TILE), cdiv(a.Cout, 16), B);
     hipLaunchKernelGGL((conv1d_kernel<K, 16, TT>), grid, dim3(256), lds, st, a);
@@ -733,6 +743,7 @@ template <int TT>
 int launch_convT_t(const ConvArgs& a, int B, hipStream_t st) {
   constexpr int TILE = 256 * TT;
   const size_t lds = (size_t)CI_CHUNK * (TILE + 1) * sizeof(float);
+  hg_variant = tt_name<TT>();
   if (a.Cout >= 16) hipLaunchKernelGGL((conv1d_kernel<2, 16, TT>), dim3(cdiv(a.Lq, TILE), cdiv(a.Cout, 16), B * a.n_phase), dim3(256), lds, st, a);
   else hipLaunchKernelGGL((conv1d_kernel<2, 8, TT>), dim3(cdiv(a.Lq, TILE), cdiv(a.Cout, 8), B * a.n_phase), dim3(256), lds, st, a);
   BSG_LAUNCH_CHECK();
@@ -754,6 +765,7 @@ int launch_pair_t(const PairArgs& a, int B, hipStream_t st) {
     BSG_HIP(hipFuncSetAttribute((const void*)resblock_pair_kernel<K, C, TT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = true;
   }
+  hg_variant = tt_name<TT>();
   hipLaunchKernelGGL((resblock_pair_kernel<K, C, TT>), dim3(cdiv(a.L, POUT), B), dim3(256), lds, st, a);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
@@ -1035,6 +1047,7 @@ int launch_pair_h2_t(const PairArgs& a, int B, hipStream_t st) {
     BSG_HIP(hipFuncSetAttribute((const void*)resblock_pair_h2_kernel<K, C, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = lds;
   }
+  hg_variant = NB == 2 ? "NB2" : "NB1";
   hipLaunchKernelGGL((resblock_pair_h2_kernel<K, C, NB>), dim3(cdiv(a.L, POUT), B), dim3(256), lds, st, a);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
@@ -1347,6 +1360,7 @@ int launch_pair_h16_t(const PairArgs& a, int B, hipStream_t st) {
     BSG_HIP(hipFuncSetAttribute((const void*)resblock_pair_h16_kernel<K, C, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = lds;
   }
+  hg_variant = NB == 2 ? "NB2" : "NB1";
   hipLaunchKernelGGL((resblock_pair_h16_kernel<K, C, NB>), dim3(cdiv(a.L, POUT), B), dim3(256), lds, st, a);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
@@ -1534,6 +1548,7 @@ int launch_chain_h16_t(const ChainArgs& a, int B, hipStream_t st) {
     BSG_HIP(hipFuncSetAttribute((const void*)resblock_chain_h16_kernel<K, C, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = lds;
   }
+  hg_variant = NC == 8 ? "NC8" : "NC4";
   hipLaunchKernelGGL((resblock_chain_h16_kernel<K, C, NC>), dim3(cdiv(a.L, pout), B), dim3(256), lds, st, a);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
@@ -1581,6 +1596,7 @@ int launch_pair_mfma_t(const PairArgs& a, int B, hipStream_t st) {
     BSG_HIP(hipFuncSetAttribute((const void*)resblock_pair_mfma_kernel<K, C, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = lds;
   }
+  hg_variant = NB == 2 ? "NB2" : "NB1";
   hipLaunchKernelGGL((resblock_pair_mfma_kernel<K, C, NB>), dim3(cdiv(a.L, POUT), B), dim3(256), lds, st, a);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
@@ -1679,7 +1695,19 @@ struct bsg_hifigan {
   bool h2_ok = true;
   unsigned short* planes = nullptr;       // activation planes of the gemm_h2w products (hi, then lo)
   size_t planes_cap = 0;                  // halfs
+  std::string path;                       // the launches of the last forward (bsg_hifigan_last_path)
 };
+
+// One token "<site>:<form>[/<tile variant>]" per launch, appended at the branch that launched (never derived from the thresholds again).
+__attribute__((format(printf, 2, 3))) static void path_add(bsg_hifigan* h, const char* fmt, ...) {
+  char tok[64];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(tok, sizeof tok, fmt, ap);
+  va_end(ap);
+  if (!h->path.empty()) h->path += ' ';
+  h->path += tok;
+}
 
 extern "C" void bsg_hifigan_destroy(bsg_hifigan* h) {
   if (!h) return;
@@ -1987,8 +2015,10 @@ static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, 
     g.Wn = p.cout; g.taps = p.k; g.tap_shift0 = -(p.k / 2); g.act_is_a = 0; g.C = x; g.ldc = T; g.sC = (long long)p.cout * T; g.bias = p.b;
     g.alpha = 1.f; g.act_fn = ACT_NONE; g.batch = B;
     TRY(launch_gemm_h2w(g, st));
+    path_add(h, "pre:h2w");
   } else {
     TRY(run_conv(h->pre, mel, x, B, T, 1, 1.0f, nullptr, nullptr, 1.0f, 0, st));            // conv_pre :150
+    path_add(h, "pre:conv/%s", hg_variant);
   }
   int L = T;
   float* cur = x;
@@ -2011,6 +2041,7 @@ static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, 
       g.Wn = up.cout * 8; g.taps = 2; g.tap_shift0 = -1; g.act_is_a = 0; g.C = t.y; g.ldc = Lout; g.sC = (long long)up.cout * Lout; g.bias = up.b;
       g.alpha = 1.f; g.act_fn = ACT_NONE; g.batch = B; g.up_u = 8; g.up_p = t.p; g.up_lout = Lout;
       TRY(launch_gemm_h2w(g, st));
+      path_add(h, "up%d:h2w", i);
     } else if (up_env && t.u == 2 && up.k == 4 && t.p == 1 && (up.cout == 16 || up.cout == 8) && (long long)cdiv(Lout, 1024) * B >= 512 &&
                !getenv("BSG_NO_UP2")) {   // (single utterances: 125 workgroups of this form are slower than the phase-per-block form, 38 against 28 us)
       UpArgs ua{};
@@ -2019,6 +2050,7 @@ static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, 
       if (up.cout == 16) hipLaunchKernelGGL(upsample2_kernel<16>, grid, dim3(256), 0, st, ua);
       else hipLaunchKernelGGL(upsample2_kernel<8>, grid, dim3(256), 0, st, ua);
       BSG_LAUNCH_CHECK();
+      path_add(h, "up%d:up2", i);
     } else if (up.wpu && up_env && t.p * 2 == t.u && (long long)cdiv(L + 1, 256) * cdiv(up.cout, 8) * B >= 512) {   // short inputs: the phase-per-block form has u x the workgroups
       // all phases of a position in one lane: contiguous stores (upsample_kernel)
       UpArgs ua{};
@@ -2028,6 +2060,7 @@ static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, 
       else if (t.u == 4) hipLaunchKernelGGL(upsample_kernel<4>, grid, dim3(256), 0, st, ua);
       else hipLaunchKernelGGL(upsample_kernel<2>, grid, dim3(256), 0, st, ua);
       BSG_LAUNCH_CHECK();
+      path_add(h, "up%d:upk", i);
     } else if (up.wpk && !getenv("BSG_NO_POLYPHASE")) {
       // polyphase form: u interleaved 2-tap convolutions over the input positions (weights wave-uniform -> scalar loads)
       ConvArgs a{};
@@ -2036,15 +2069,18 @@ static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, 
       a.n_phase = t.u; a.ph_off = -t.p; a.Lq = L + 1; a.Lout = Lout;
       a.w_phase_stride = (long long)cdiv(up.cout, up.cout >= 16 ? 16 : 8) * up.cin * 2 * (up.cout >= 16 ? 16 : 8);
       TRY(launch_convT(a, B, st));
+      path_add(h, "up%d:poly/%s", i, hg_variant);
     } else {
       if (up.cout >= 16) hipLaunchKernelGGL(conv_transpose1d_kernel<16>, dim3(cdiv(Lout, 256), cdiv(up.cout, 16), B), dim3(256), 0, st, t);
       else hipLaunchKernelGGL(conv_transpose1d_kernel<8>, dim3(cdiv(Lout, 256), cdiv(up.cout, 8), B), dim3(256), 0, st, t);
       BSG_LAUNCH_CHECK();
+      path_add(h, "up%d:convT", i);
     }
     if (har) {   // x = x + LayerNorm_C(relu(noise_conv_i(har_source)))                       (hifigan.py:154-160)
       const ConvW& nc = h->noise_convs[i];
       const int stride = i + 1 < c.n_ups ? nc.k / 2 : 1;
       TRY(nsf_launch_source_add(t.y, har, nc.w, nc.b, B, nc.cout, Lout, Lh, nc.k, stride, i + 1 < c.n_ups ? stride / 2 : 0, st));
+      path_add(h, "src%d:add", i);
     }
     float* xin = t.y;                       // stage input (after upsampling)
     float* sum = (xin == x ? xs : x);       // MRF running sum / stage output
@@ -2075,6 +2111,7 @@ static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, 
             ca.w1[m] = c1.wp16c; ca.b1[m] = c1.b; ca.w2[m] = c2.wp16c; ca.b2[m] = c2.b; ca.dil[m] = c.resblock_dilations[j][m];
           }
           TRY(launch_chain_h16(ca, f1.k, f1.cout, B, st));
+          path_add(h, "rb%d.%d:chain/%s", i, j, hg_variant);
           continue;
         }
       }
@@ -2086,6 +2123,7 @@ static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, 
           // ResBlock2 (hifigan.py:70-91): x = conv_d(lrelu(x)) + x per dilation; the MRF sum / mean in the last one's epilogue (:161-167)
           TRY(run_conv(c1, y, dst, B, L, c.resblock_dilations[j][m], slope, y, (last && j > 0) ? sum : nullptr,
                        (last && j == c.n_kernels - 1) ? (float)c.n_kernels : 1.0f, 0, st));
+          path_add(h, "rb%d.%d.%d:conv/%s", i, j, m, hg_variant);
           y = dst;
           continue;
         }
@@ -2110,21 +2148,27 @@ static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, 
           if (mfma_env && h16_env && h2_env && h->h2_ok && c1.wp16 && c2.wp16 && gemm_split_enabled()) {
             pa.w1 = c1.wp16; pa.w2 = c2.wp16; pa.range_events = gemm_range_counter();
             TRY(launch_pair_h16(pa, c1.k, c1.cout, B, st));
+            path_add(h, "rb%d.%d.%d:pair_h16/%s", i, j, m, hg_variant);
           } else if (use_mfma && h2_env && h->h2_ok && c1.wps && c2.wps && gemm_split_enabled()) {
             pa.w1 = c1.wps; pa.w2 = c2.wps; pa.range_events = gemm_range_counter();
             TRY(launch_pair_h2(pa, c1.k, c1.cout, B, st));
+            path_add(h, "rb%d.%d.%d:pair_h2/%s", i, j, m, hg_variant);
           } else if (use_mfma) {
             pa.w1 = c1.wpm; pa.w2 = c2.wpm;
             TRY(launch_pair_mfma(pa, c1.k, c1.cout, B, st));
+            path_add(h, "rb%d.%d.%d:pair_mfma/%s", i, j, m, hg_variant);
           } else {
             TRY(launch_pair(pa, c1.k, c1.cout, B, st));
+            path_add(h, "rb%d.%d.%d:pair_valu/%s", i, j, m, hg_variant);
           }
           y = dst;
           continue;
         }
         TRY(run_conv(c1, y, tmp, B, L, c.resblock_dilations[j][m], slope, nullptr, nullptr, 1.0f, 0, st));     // :56-57
+        path_add(h, "rb%d.%d.%d:conv1/%s", i, j, m, hg_variant);
         TRY(run_conv(c2, tmp, dst, B, L, 1, slope, y, (last && j > 0) ? sum : nullptr,
                      (last && j == c.n_kernels - 1) ? (float)c.n_kernels : 1.0f, 0, st));                     // :58-60, :161-167
+        path_add(h, "rb%d.%d.%d:conv2/%s", i, j, m, hg_variant);
         y = dst;
       }
     }
@@ -2133,8 +2177,10 @@ static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, 
   if (h->post.cin == 8 && h->post.k == 7 && !getenv("BSG_NO_CONV_POST")) {
     hipLaunchKernelGGL(conv_post_kernel<8>, dim3(cdiv(L, 1024), B), dim3(256), 0, st, (const float*)cur, (const float*)h->post.w, (const float*)h->post.b, wav, L, 0.01f);
     BSG_LAUNCH_CHECK();
+    path_add(h, "post:post4");
   } else {
     TRY(run_conv(h->post, cur, wav, B, L, 1, 0.01f, nullptr, nullptr, 1.0f, 1, st));          // :169-171 (default slope 0.01)
+    path_add(h, "post:conv/%s", hg_variant);
   }
   return BSG_OK;
 }
@@ -2142,6 +2188,7 @@ static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, 
 extern "C" int bsg_hifigan_forward(bsg_hifigan* h, const float* mel, float* wav, int32_t B, int32_t T, void* stream) {
   GuardScope guard_scope(h ? &h->guard : nullptr);
   BSG_REQUIRE(h && !h->cfg.use_nsf, "hifigan_forward: this generator was created with the NSF source; call bsg_hifigan_forward_nsf");
+  h->path.clear();
   return hifigan_run(h, mel, wav, B, T, stream, nullptr, 0);
 }
 
@@ -2150,6 +2197,7 @@ extern "C" int bsg_hifigan_forward_nsf(bsg_hifigan* h, const float* mel, const f
   GuardScope guard_scope(h ? &h->guard : nullptr);
   BSG_REQUIRE(h && h->cfg.use_nsf, "hifigan_forward_nsf: generator created without the NSF source");
   BSG_REQUIRE(mel && f0 && rand_ini && noise && wav && B > 0 && T > 0, "hifigan_forward_nsf: bad argument");
+  h->path.clear();
   hipStream_t st = (hipStream_t)stream;
   int hop = 1;
   for (int i = 0; i < h->cfg.n_ups; ++i) hop *= h->cfg.upsample_rates[i];
@@ -2167,8 +2215,13 @@ extern "C" int bsg_hifigan_forward_nsf(bsg_hifigan* h, const float* mel, const f
     h->cap_src = need;
   }
   TRY(nsf_launch_source(f0, rand_ini, noise, h->src_w, h->src_b, h->sw_tmp, h->har, B, T, hop, NH, (float)h->cfg.sample_rate, st));
+  path_add(h, "src:nsf");
   return hifigan_run(h, mel, wav, B, T, stream, h->har, L);
 }
+
+// The launches of the last bsg_hifigan_forward[_nsf] of this handle, one token per launch in launch order ("none" before the first).  The
+// string is the handle's: valid until the handle's next forward or its destruction.
+extern "C" const char* bsg_hifigan_last_path(bsg_hifigan* h) { return h && !h->path.empty() ? h->path.c_str() : "none"; }
 
 namespace bsg {
 Guard* guard_of_hifigan(void* h) { return &static_cast<bsg_hifigan*>(h)->guard; }

@@ -193,6 +193,12 @@ class HifiGanGenerator(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         except Exception:
             pass
 
+    def last_path(self):
+        """The launches of the last forward, one token per launch in launch order (include/bisinger_hip.h, bsg_hifigan_last_path):
+        'pre:h2w up0:h2w rb0.0.0:pair_h2/NB1 ... up2:upk rb2.2:chain/NC8 up3:up2 ... post:post4'; 'none' before the first forward.  After
+        a forward that the range guard repeated it names the repeat."""
+        return _lib.load().bsg_hifigan_last_path(self._h).decode() if self._h is not None else 'none'
+
     @torch.no_grad()
     def forward(self, x, f0=None, rand_ini=None, noise=None, seed=0):
         """x [B,80,T] (, f0 [B,T]) -> [B,1,T*hop]   (hifigan.py:144-173).

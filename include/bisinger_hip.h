@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define BSG_ABI_VERSION 9
+#define BSG_ABI_VERSION 10
 
 #define BSG_OK 0
 #define BSG_EINVAL (-22)  /* bad argument / shape the kernels do not support            */
@@ -370,6 +370,15 @@ int bsg_hifigan_forward(bsg_hifigan* h, const float* mel, float* wav, int32_t B,
  * noise [B, T*hop, harmonic_num+1] N(0,1) (torch.randn_like, source.py:130). */
 int bsg_hifigan_forward_nsf(bsg_hifigan* h, const float* mel, const float* f0, const float* rand_ini, const float* noise,
                             float* wav, int32_t B, int32_t T, void* stream);
+/* ABI v10: the launches of the handle's last bsg_hifigan_forward[_nsf], one token "<site>:<form>[/<tile variant>]" per launch in launch
+ * order, separated by blanks; "none" before the first forward.  Each token is written at the branch that launched, so it names what ran,
+ * not what the thresholds would choose.  Sites: src (NSF source), pre, up<i>, src<i> (NSF source add of stage i), rb<i>.<j> (a whole
+ * ResBlock in one launch) or rb<i>.<j>.<m> (its m-th convolution pair / convolution), post.  Forms: h2w (pre-split GEMM), conv, conv1,
+ * conv2 (conv1d_kernel, /TT1 /TT2 /TT4 = samples per lane), up2 (upsample2_kernel), upk (upsample_kernel), poly (polyphase conv1d_kernel,
+ * /TT*), convT (conv_transpose1d_kernel), chain (resblock_chain_h16_kernel, /NC4 /NC8), pair_h16, pair_h2, pair_mfma (/NB1 /NB2),
+ * pair_valu (resblock_pair_kernel, /TT*), post4 (conv_post_kernel), nsf, add.  The string belongs to the handle: it is valid until the
+ * handle's next forward or its destruction.  A forward that fails leaves the launches made up to the failure. */
+const char* bsg_hifigan_last_path(bsg_hifigan* h);
 
 /* ABI v9, building block exported for unit tests: the NSF harmonic source alone (source.py:352-399 as bsg_hifigan_forward_nsf runs it).
  * f0 [B,T], rand_ini [B,NH], noise [B,T*hop,NH] as there; lin_w [NH], lin_b [1] = m_source.l_linear.{weight,bias}.

@@ -30,6 +30,11 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_lib.declared_symbols()) == syms
 
 
+def test_hifigan_last_path_without_a_forward():
+    """bsg_hifigan_last_path names launches; a null handle has made none (the GPU side: tests/test_gpu_hifigan_shapes.py)."""
+    assert _lib.load().bsg_hifigan_last_path(None) == b'none'
+
+
 def test_product_path_fails_loudly_without_library(monkeypatch, tmp_path):
     import pytest
     monkeypatch.setattr(_lib, '_lib', None)
