@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'lib', 'libbisinger_hip.so')
 if os.environ.get('BSG_LIB'):      # development: an alternative build of the same ABI (kernel experiments)
     LIB_PATH = os.environ['BSG_LIB']
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class BsgError(RuntimeError):
@@ -108,6 +108,10 @@ _SIGS = {
     'bsg_hifigan_forward': (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     'bsg_hifigan_forward_nsf': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     'bsg_hifigan_last_path': (c_char_p, [c_void_p]),
+    'bsg_fs2midi_last_path': (c_char_p, [c_void_p]),
+    'bsg_fftden_last_path': (c_char_p, [c_void_p]),
+    'bsg_fs2midi_debug_poison_workspace': (c_int32, [c_void_p, c_void_p]),
+    'bsg_fftden_debug_poison_workspace': (c_int32, [c_void_p, c_void_p]),
     'bsg_nsf_source': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                  c_int32, c_void_p]),
     'bsg_pitchext_n_weights': (c_int32, [POINTER(PitchextCfg)]),

@@ -73,6 +73,15 @@ class FFT(FFTBlocks, _lib.HandleOwner, _lib.GemmGuarded):
         except Exception:
             pass
 
+    def last_path(self):
+        """The launch forms of the last forward's FFT stack ('den.' tokens; include/bisinger_hip.h, bsg_fs2midi_last_path); 'none' before it."""
+        return _lib.load().bsg_fftden_last_path(self._h).decode() if self._h is not None else 'none'
+
+    def poison_workspace(self):
+        """Test hook (bsg_fftden_debug_poison_workspace): NaN bytes over every activation workspace of the handle."""
+        with torch.cuda.device(next(self.parameters()).device):
+            _lib.check(_lib.load().bsg_fftden_debug_poison_workspace(self.handle(), _lib.stream_ptr()), 'bsg_fftden_debug_poison_workspace')
+
     def prepare(self, cond):
         h = self.handle()
         cond = cond.contiguous().float()

@@ -70,6 +70,7 @@ struct GemmArgs {
   long long sRS;
   int batch;
   unsigned* range_events;   // set by launch_gemm: the counter of the handle in whose call the product runs (gemm_range_counter())
+  const char** form_out;    // optional, host side only: launch_gemm stores the name of the form it launched (a string literal) for the caller's launch record
 };
 int launch_gemm(const GemmArgs& g, hipStream_t st);
 // the split-fp16 forms (gemm.hip, fs2.hip flash attention): true while products are formed on the 16-bit matrix pipe (BSG_GEMM_SPLIT,
@@ -145,6 +146,8 @@ struct H2wArgs {
   int qkv_T, qkv_Tp, qkv_H;
   unsigned short* vt;
   long long vt_plane;
+  const char** form_out;       // optional, host side only: launch_gemm_h2w stores the tile height and ring it launched ("h2w/64/ring8", a string literal) for the
+                               // caller's launch record
   int no_direct;               // set by launch_gemm_h2w (BSG_H2W_DIRECT=0): the [feature][frame] output through the LDS image even where the accumulators could be stored directly
 };
 bool h2w_supports(int rows, int Wn, int K, int taps, int lda);

@@ -16,6 +16,7 @@
 // and simplicity; the unfused attention materialises the [B*H,T,T] score matrix in HBM.
 #include <math.h>
 
+#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -1074,7 +1075,18 @@ struct bsg_fs2midi {
   bool h2w_ok = false;
   int last_token_rows = 0;   // rows (utterances x tokens) the last encode ran its encoder on; rows of the last FFT stack (bsg_fs2midi_last_rows)
   int last_stack_rows = 0;
+  std::string path;          // the launch forms of the last encode and of the decode after it (bsg_fs2midi_last_path, bsg_fftden_last_path)
+  size_t path_enc_len = 0;   // where the encode's tokens end: a decode replaces what follows
 };
+
+// One token per launch FORM, appended at the branch that launched (never derived from the thresholds again): "<stack>.<site>:<form>", in
+// launch order; a form that a stack launches again (every layer, as a rule) is named once.
+static void path_add(bsg_fs2midi* h, const char* tag, const char* tok) {
+  const std::string full = std::string(tag) + tok;
+  if ((" " + h->path + " ").find(" " + full + " ") != std::string::npos) return;
+  if (!h->path.empty()) h->path += ' ';
+  h->path += full;
+}
 
 static int fs2_alloc(bsg_fs2midi* h, float** p, size_t n) {
   BSG_HIP(hipMalloc((void**)p, n * sizeof(float)));
@@ -1269,12 +1281,29 @@ static int ensure_scores(bsg_fs2midi* h, size_t scores, hipStream_t st) {
   return BSG_OK;
 }
 
+// launch_gemm / launch_gemm_h2w with the form they picked added to the handle's launch record under `tag`
+static int gemm_rec(bsg_fs2midi* h, const char* tag, GemmArgs& g, hipStream_t st) {
+  const char* form = nullptr;
+  g.form_out = &form;
+  const int rc = launch_gemm(g, st);
+  if (form) path_add(h, tag, form);
+  return rc;
+}
+static int h2w_rec(bsg_fs2midi* h, const char* tag, H2wArgs& g, hipStream_t st) {
+  const char* form = nullptr;
+  g.form_out = &form;
+  const int rc = launch_gemm_h2w(g, st);
+  if (form) path_add(h, tag, form);
+  return rc;
+}
+
 static int linear(const float* X, const float* W, const float* bias, float* Y, long long rows, int N, int K, int act,
-                  const float* R, const float* rowscale, hipStream_t st, float alpha = 1.f, int alpha_ncols = 0) {
+                  const float* R, const float* rowscale, hipStream_t st, float alpha = 1.f, int alpha_ncols = 0,
+                  bsg_fs2midi* rec = nullptr, const char* tag = "") {
   GemmArgs g{};
   g.A = X; g.B = W; g.C = Y; g.M = (int)rows; g.N = N; g.K = K; g.lda = K; g.ldb = K; g.ldc = N; g.trans_b = 1; g.taps = 1;
   g.bias_n = bias; g.alpha = alpha; g.alpha_ncols = alpha_ncols; g.act = act; g.R = R; g.ldr = N; g.rowscale = rowscale; g.batch = 1;
-  return launch_gemm(g, st);
+  return rec ? gemm_rec(rec, tag, g, st) : launch_gemm(g, st);
 }
 
 static int ln(const float* x, const float* w, const float* b, float* y, const float* rowscale, long long rows, float eps, hipStream_t st) {
@@ -1291,21 +1320,23 @@ static int ln_planes(const float* x, const float* w, const float* b, unsigned sh
   return BSG_OK;
 }
 // y[rows][N] = epi(planes[rows][K] W^T): Linear through gemm_h2w_kernel (W pre-split); `planes_out`: the result as planes [2][rows][N] instead
-static int linear_h2w(const unsigned short* planes, const H2wWeights& W, int N, const float* bias, float* Y, unsigned short* planes_out, long long rows,
+static int linear_h2w(bsg_fs2midi* h, const char* tag, const unsigned short* planes, const H2wWeights& W, int N, const float* bias, float* Y, unsigned short* planes_out, long long rows,
                       int act, const float* R, const float* rowscale, hipStream_t st, float alpha = 1.f, int alpha_ncols = 0,
                       long long act_plane = 0) {
   H2wArgs g{};
   g.act = planes; g.act_plane = act_plane ? act_plane : rows * W.K; g.lda = W.K; g.wpack = W.pack; g.rows = (int)rows; g.K = W.K; g.Wn = W.Wn; g.taps = 1;
   g.act_is_a = 1; g.C = Y; g.ldc = N; g.out = planes_out; g.out_plane = rows * N; g.ldo = N; g.bias = bias; g.alpha = alpha;
   g.alpha_ncols = alpha_ncols; g.act_fn = act; g.R = R; g.ldr = N; g.rowscale = rowscale; g.batch = 1;
-  return launch_gemm_h2w(g, st);
+  return h2w_rec(h, tag, g, st);
 }
 
 // EncSALayer x FFTBlocks tail (common_layers.py:706-730, tts_modules.py:298-305); x [B*T, H] in place
 static int fft_stack(bsg_fs2midi* h, const std::vector<FftLayerW>& layers, const float* lnw, const float* lnb, int ksz,
-                     float* x, const float* keep, int B, int T, hipStream_t st) {
+                     float* x, const float* keep, int B, int T, hipStream_t st, const char* tag) {
   const long long rows = (long long)B * T;
   h->last_stack_rows = (int)rows;
+  const std::string gemm_tag_s = std::string(tag) + "gemm:", attn_tag_s = std::string(tag) + "attn:", qkv_tag_s = std::string(tag) + "qkv:";
+  const char *gtag = gemm_tag_s.c_str(), *atag = attn_tag_s.c_str(), *qtag = qkv_tag_s.c_str();
   const int heads = h->cfg.num_heads, hd = H / heads;
   const float qscale = (float)sqrt(1.0 / (double)hd);
   static int env_h2w = -1;   // BSG_GEMM_H2W=0: gemm_split_kernel (operands split while staged) instead of the pre-split GEMMs
@@ -1351,9 +1382,11 @@ static int fft_stack(bsg_fs2midi* h, const std::vector<FftLayerW>& layers, const
         g.act = ap; g.act_plane = rows * H; g.lda = H; g.wpack = L.p_in.pack; g.rows = (int)rows; g.K = H; g.Wn = 3 * H; g.taps = 1; g.act_is_a = 1;
         g.out = fp; g.out_plane = rows * 2 * H; g.ldo = 2 * H; g.alpha = qscale; g.alpha_ncols = H; g.act_fn = ACT_NONE; g.batch = 1;
         g.qkv_T = T; g.qkv_Tp = Tp; g.qkv_H = H; g.vt = h->w_ffn ? reinterpret_cast<unsigned short*>(h->w_ffn) : nullptr; g.vt_plane = vplane;
-        TRY(launch_gemm_h2w(g, st));
+        TRY(h2w_rec(h, gtag, g, st));
+        path_add(h, qtag, "fused");
       } else {
-        TRY(linear_h2w(ap, L.p_in, 3 * H, nullptr, h->w_qkv, nullptr, rows, ACT_NONE, nullptr, nullptr, st, qscale, H));
+        TRY(linear_h2w(h, gtag, ap, L.p_in, 3 * H, nullptr, h->w_qkv, nullptr, rows, ACT_NONE, nullptr, nullptr, st, qscale, H));
+        path_add(h, qtag, use_planes ? "split_kernel" : "h2w");
       }
       if (use_planes) {
         if (!qkv_fused) {
@@ -1382,19 +1415,25 @@ static int fft_stack(bsg_fs2midi* h, const std::vector<FftLayerW>& layers, const
           }
         }
         hipLaunchKernelGGL(flash_attn_planes_kernel<2>, dim3(cdiv(T, 64), B * heads, ks), dim3(128), FLP_LDS, st, (const _Float16*)qk, rows * 2 * H, (const _Float16*)vt, vplane, (const unsigned*)km, T, Tp, heads, reinterpret_cast<_Float16*>(ap), rows * H, H, gemm_range_counter(), h->w_fsk, h->w_fcnt);
-      } else if (wg4 >= 512) hipLaunchKernelGGL(flash_attn_split_kernel<4>, dim3(cdiv(T, 128), B * heads), dim3(256), 0, st, (const float*)h->w_qkv, keep, (float*)nullptr, T, heads, 3 * H, H, gemm_range_counter(), reinterpret_cast<_Float16*>(ap), rows * H);
-      else hipLaunchKernelGGL(flash_attn_split_kernel<2>, dim3(cdiv(T, 64), B * heads), dim3(128), 0, st, (const float*)h->w_qkv, keep, (float*)nullptr, T, heads, 3 * H, H, gemm_range_counter(), reinterpret_cast<_Float16*>(ap), rows * H);
+        path_add(h, atag, ks == 1 ? "planes/ks1" : ks == 2 ? "planes/ks2" : ks == 4 ? "planes/ks4" : ks == 8 ? "planes/ks8" : "planes/ks16+");
+      } else if (wg4 >= 512) {
+        hipLaunchKernelGGL(flash_attn_split_kernel<4>, dim3(cdiv(T, 128), B * heads), dim3(256), 0, st, (const float*)h->w_qkv, keep, (float*)nullptr, T, heads, 3 * H, H, gemm_range_counter(), reinterpret_cast<_Float16*>(ap), rows * H);
+        path_add(h, atag, "split/nw4");
+      } else {
+        hipLaunchKernelGGL(flash_attn_split_kernel<2>, dim3(cdiv(T, 64), B * heads), dim3(128), 0, st, (const float*)h->w_qkv, keep, (float*)nullptr, T, heads, 3 * H, H, gemm_range_counter(), reinterpret_cast<_Float16*>(ap), rows * H);
+        path_add(h, atag, "split/nw2");
+      }
       BSG_LAUNCH_CHECK();
-      TRY(linear_h2w(ap, L.p_out, H, nullptr, h->w_b, nullptr, rows, ACT_NONE, x, keep, st));   // x1 = (x + attn) * keep
+      TRY(linear_h2w(h, gtag, ap, L.p_out, H, nullptr, h->w_b, nullptr, rows, ACT_NONE, x, keep, st));   // x1 = (x + attn) * keep
       TRY(ln_planes(h->w_b, L.ln2w, L.ln2b, ap, rows, 1e-5f, st));
       {
         H2wArgs g{};   // Conv1d(H -> 4H, k, SAME) * k^-1/2 -> GELU, written as the planes the second Linear reads
         g.act = ap; g.act_plane = rows * H; g.lda = H; g.sAct = (long long)T * H; g.wpack = L.p_ffn1.pack; g.rows = T; g.K = H; g.Wn = 4 * H;
         g.taps = ksz; g.tap_shift0 = -(ksz / 2); g.act_is_a = 1; g.out = fp; g.out_plane = rows * 4 * H; g.ldo = 4 * H; g.sO = (long long)T * 4 * H;
         g.bias = L.ffn1b; g.alpha = (float)pow((double)ksz, -0.5); g.act_fn = ACT_GELU; g.batch = B;
-        TRY(launch_gemm_h2w(g, st));
+        TRY(h2w_rec(h, gtag, g, st));
       }
-      TRY(linear_h2w(fp, L.p_ffn2, H, L.ffn2b, x, nullptr, rows, ACT_NONE, h->w_b, keep, st));   // x = (x1 + ffn) * keep
+      TRY(linear_h2w(h, gtag, fp, L.p_ffn2, H, L.ffn2b, x, nullptr, rows, ACT_NONE, h->w_b, keep, st));   // x = (x1 + ffn) * keep
     }
     TRY(ln(x, lnw, lnb, x, keep, rows, 1e-5f, st));
     return BSG_OK;
@@ -1402,17 +1441,28 @@ static int fft_stack(bsg_fs2midi* h, const std::vector<FftLayerW>& layers, const
   for (const FftLayerW& L : layers) {
     // --- self attention ---
     TRY(ln(x, L.ln1w, L.ln1b, h->w_a, nullptr, rows, 1e-5f, st));
-    TRY(linear(h->w_a, L.in_proj, nullptr, h->w_qkv, rows, 3 * H, H, ACT_NONE, nullptr, nullptr, st, qscale, H));
+    TRY(linear(h->w_a, L.in_proj, nullptr, h->w_qkv, rows, 3 * H, H, ACT_NONE, nullptr, nullptr, st, qscale, H, h, gtag));
+    path_add(h, qtag, "gemm");
     if (hd == 128 && !getenv("BSG_NO_FLASH_ATTN")) {
       // fused attention: no [B*heads, T, T] score tensor (flash_attn_kernel); 2 waves per workgroup when 4 would leave CUs idle
       const long long wg4 = (long long)cdiv(T, 128) * B * heads;
       static int fsplit = -1;   // BSG_FLASH_SPLIT=0: the fp32-MFMA form even while the GEMMs run split-fp16
       if (fsplit < 0) { const char* e = getenv("BSG_FLASH_SPLIT"); fsplit = e ? atoi(e) : 1; }
       if (fsplit && gemm_split_enabled()) {
-        if (wg4 >= 512) hipLaunchKernelGGL(flash_attn_split_kernel<4>, dim3(cdiv(T, 128), B * heads), dim3(256), 0, st, (const float*)h->w_qkv, keep, h->w_a, T, heads, 3 * H, H, gemm_range_counter(), (_Float16*)nullptr, 0LL);
-        else hipLaunchKernelGGL(flash_attn_split_kernel<2>, dim3(cdiv(T, 64), B * heads), dim3(128), 0, st, (const float*)h->w_qkv, keep, h->w_a, T, heads, 3 * H, H, gemm_range_counter(), (_Float16*)nullptr, 0LL);
-      } else if (wg4 >= 512) hipLaunchKernelGGL(flash_attn_kernel<4>, dim3(cdiv(T, 128), B * heads), dim3(256), 0, st, (const float*)h->w_qkv, keep, h->w_a, T, heads, 3 * H, H);
-      else hipLaunchKernelGGL(flash_attn_kernel<2>, dim3(cdiv(T, 64), B * heads), dim3(128), 0, st, (const float*)h->w_qkv, keep, h->w_a, T, heads, 3 * H, H);
+        if (wg4 >= 512) {
+          hipLaunchKernelGGL(flash_attn_split_kernel<4>, dim3(cdiv(T, 128), B * heads), dim3(256), 0, st, (const float*)h->w_qkv, keep, h->w_a, T, heads, 3 * H, H, gemm_range_counter(), (_Float16*)nullptr, 0LL);
+          path_add(h, atag, "split/nw4");
+        } else {
+          hipLaunchKernelGGL(flash_attn_split_kernel<2>, dim3(cdiv(T, 64), B * heads), dim3(128), 0, st, (const float*)h->w_qkv, keep, h->w_a, T, heads, 3 * H, H, gemm_range_counter(), (_Float16*)nullptr, 0LL);
+          path_add(h, atag, "split/nw2");
+        }
+      } else if (wg4 >= 512) {
+        hipLaunchKernelGGL(flash_attn_kernel<4>, dim3(cdiv(T, 128), B * heads), dim3(256), 0, st, (const float*)h->w_qkv, keep, h->w_a, T, heads, 3 * H, H);
+        path_add(h, atag, "flash/nw4");
+      } else {
+        hipLaunchKernelGGL(flash_attn_kernel<2>, dim3(cdiv(T, 64), B * heads), dim3(128), 0, st, (const float*)h->w_qkv, keep, h->w_a, T, heads, 3 * H, H);
+        path_add(h, atag, "flash/nw2");
+      }
       BSG_LAUNCH_CHECK();
     } else {
       TRY(ensure_scores(h, (size_t)B * heads * T * T, st));
@@ -1422,20 +1472,21 @@ static int fft_stack(bsg_fs2midi* h, const std::vector<FftLayerW>& layers, const
       g.trans_b = 1; g.taps = 1; g.alpha = 1.f; g.batch = B * heads; g.batch2 = heads;
       g.sA = (long long)T * 3 * H; g.sA2 = hd; g.sB = (long long)T * 3 * H; g.sB2 = hd;
       g.sC = (long long)heads * T * T; g.sC2 = (long long)T * T;
-      TRY(launch_gemm(g, st));
+      TRY(gemm_rec(h, gtag, g, st));
       }
       hipLaunchKernelGGL(masked_softmax_kernel, dim3((unsigned)((long long)B * heads * T)), dim3(256), 0, st, h->w_scores, keep, T, T, heads);
       BSG_LAUNCH_CHECK();
+      path_add(h, atag, "softmax");
       {
       GemmArgs g{};   // O[b,:,h] = P V
       g.A = h->w_scores; g.B = h->w_qkv + 2 * H; g.C = h->w_a; g.M = T; g.N = hd; g.K = T; g.lda = T; g.ldb = 3 * H; g.ldc = H;
       g.trans_b = 0; g.taps = 1; g.alpha = 1.f; g.batch = B * heads; g.batch2 = heads;
       g.sA = (long long)heads * T * T; g.sA2 = (long long)T * T; g.sB = (long long)T * 3 * H; g.sB2 = hd;
       g.sC = (long long)T * H; g.sC2 = hd;
-      TRY(launch_gemm(g, st));
+      TRY(gemm_rec(h, gtag, g, st));
       }
     }
-    TRY(linear(h->w_a, L.out_proj, nullptr, h->w_b, rows, H, H, ACT_NONE, x, keep, st));   // x1 = (x + attn) * keep
+    TRY(linear(h->w_a, L.out_proj, nullptr, h->w_b, rows, H, H, ACT_NONE, x, keep, st, 1.f, 0, h, gtag));   // x1 = (x + attn) * keep
     // --- conv FFN ---
     TRY(ln(h->w_b, L.ln2w, L.ln2b, h->w_a, nullptr, rows, 1e-5f, st));
     {
@@ -1444,9 +1495,9 @@ static int fft_stack(bsg_fs2midi* h, const std::vector<FftLayerW>& layers, const
       g.trans_b = 1; g.taps = ksz; g.tap_shift0 = -(ksz / 2); g.sTapB = (long long)4 * H * H;
       g.bias_n = L.ffn1b; g.alpha = (float)pow((double)ksz, -0.5); g.act = ACT_GELU; g.batch = B;
       g.sA = (long long)T * H; g.sC = (long long)T * 4 * H;
-      TRY(launch_gemm(g, st));
+      TRY(gemm_rec(h, gtag, g, st));
     }
-    TRY(linear(h->w_ffn, L.ffn2, L.ffn2b, x, rows, H, 4 * H, ACT_NONE, h->w_b, keep, st));   // x = (x1 + ffn) * keep
+    TRY(linear(h->w_ffn, L.ffn2, L.ffn2b, x, rows, H, 4 * H, ACT_NONE, h->w_b, keep, st, 1.f, 0, h, gtag));   // x = (x1 + ffn) * keep
   }
   TRY(ln(x, lnw, lnb, x, keep, rows, 1e-5f, st));
   return BSG_OK;
@@ -1487,16 +1538,17 @@ static int encode_impl(bsg_fs2midi* h, const int64_t* txt, const int64_t* pitch_
     TRY(ln_planes(lange, h->esm_ln1w, h->esm_ln1b, ap, rows, 1e-5f, st));
     float* q = h->w_qkv;                // [lrows][H]
     float* kvp = h->w_qkv + rows * H;   // [rows][2H]: K | V
-    TRY(linear_h2w(fp + off * H, h->p_esm_q, H, h->esm_in_b, q, nullptr, lrows, ACT_NONE, nullptr, nullptr, st, 1.f, 0, rows * H));
-    TRY(linear_h2w(ap, h->p_esm_kv, 2 * H, h->esm_in_b + H, kvp, nullptr, rows, ACT_NONE, nullptr, nullptr, st));
+    TRY(linear_h2w(h, "esm.gemm:", fp + off * H, h->p_esm_q, H, h->esm_in_b, q, nullptr, lrows, ACT_NONE, nullptr, nullptr, st, 1.f, 0, rows * H));
+    TRY(linear_h2w(h, "esm.gemm:", ap, h->p_esm_kv, 2 * H, h->esm_in_b + H, kvp, nullptr, rows, ACT_NONE, nullptr, nullptr, st));
     hipLaunchKernelGGL(esm_attention_wave_kernel, dim3(cdiv(Tt * 8, 4)), dim3(256), 0, st, (const float*)q, (const float*)kvp, (const float*)(kvp + H), H,
                        2 * H, (float*)nullptr, reinterpret_cast<_Float16*>(ap), lrows * H, B, nb, Tt, 8, (float)sqrt(1.0 / 32.0), gemm_range_counter());
     BSG_LAUNCH_CHECK();
+    path_add(h, "esm:", "wave");
     float* Mo = h->w_c;
-    TRY(linear_h2w(ap, h->p_esm_out, H, h->esm_out_b, Mo, nullptr, lrows, ACT_NONE, lange + off * H, nullptr, st));   // Mo = out_proj + LP
+    TRY(linear_h2w(h, "esm.gemm:", ap, h->p_esm_out, H, h->esm_out_b, Mo, nullptr, lrows, ACT_NONE, lange + off * H, nullptr, st));   // Mo = out_proj + LP
     TRY(ln_planes(Mo, h->esm_ln2w, h->esm_ln2b, ap, lrows, 1e-5f, st));
-    TRY(linear_h2w(ap, h->p_esm_f0, H, h->esm_f0b, nullptr, fp, lrows, ACT_RELU, nullptr, nullptr, st));
-    TRY(linear_h2w(fp, h->p_esm_f2, H, h->esm_f2b, h->w_a, nullptr, lrows, ACT_NONE, Mo, nullptr, st));          // Fo = ffn + Mo
+    TRY(linear_h2w(h, "esm.gemm:", ap, h->p_esm_f0, H, h->esm_f0b, nullptr, fp, lrows, ACT_RELU, nullptr, nullptr, st));
+    TRY(linear_h2w(h, "esm.gemm:", fp, h->p_esm_f2, H, h->esm_f2b, h->w_a, nullptr, lrows, ACT_NONE, Mo, nullptr, st));          // Fo = ffn + Mo
   } else {
   hipLaunchKernelGGL(embed_tokens_kernel, rg, rb, 0, st, (const long long*)txt, (const long long*)lang, h->Etok, h->Elang, x0, lange, rows, sq,
                      (_Float16*)nullptr, (_Float16*)nullptr, (unsigned*)nullptr);
@@ -1507,23 +1559,24 @@ static int encode_impl(bsg_fs2midi* h, const int64_t* txt, const int64_t* pitch_
   float* q = h->w_qkv;                     // [lrows][H]
   float* k = h->w_qkv + rows * H;          // [rows][H]
   float* v = h->w_qkv + 2 * rows * H;
-  TRY(linear(x0 + off * H, h->esm_in_w, h->esm_in_b, q, lrows, H, H, ACT_NONE, nullptr, nullptr, st));
-  TRY(linear(lpn, h->esm_in_w + (size_t)H * H, h->esm_in_b + H, k, rows, H, H, ACT_NONE, nullptr, nullptr, st));
-  TRY(linear(lpn, h->esm_in_w + (size_t)2 * H * H, h->esm_in_b + 2 * H, v, rows, H, H, ACT_NONE, nullptr, nullptr, st));
+  TRY(linear(x0 + off * H, h->esm_in_w, h->esm_in_b, q, lrows, H, H, ACT_NONE, nullptr, nullptr, st, 1.f, 0, h, "esm.gemm:"));
+  TRY(linear(lpn, h->esm_in_w + (size_t)H * H, h->esm_in_b + H, k, rows, H, H, ACT_NONE, nullptr, nullptr, st, 1.f, 0, h, "esm.gemm:"));
+  TRY(linear(lpn, h->esm_in_w + (size_t)2 * H * H, h->esm_in_b + 2 * H, v, rows, H, H, ACT_NONE, nullptr, nullptr, st, 1.f, 0, h, "esm.gemm:"));
   float* att = h->w_a;   // lpn is dead once k, v exist
   {
     const long long total = lrows * 8;
     hipLaunchKernelGGL(esm_attention_kernel<32>, dim3(cdiv(total, 128)), dim3(128), 0, st, (const float*)q, (const float*)k,
                        (const float*)v, att, B, nb, Tt, 8, (float)sqrt(1.0 / 32.0));
     BSG_LAUNCH_CHECK();
+    path_add(h, "esm:", "thread");
   }
   float* Mo = h->w_c;
-  TRY(linear(att, h->esm_out_w, h->esm_out_b, Mo, lrows, H, H, ACT_NONE, lange + off * H, nullptr, st));       // Mo = out_proj + LP
+  TRY(linear(att, h->esm_out_w, h->esm_out_b, Mo, lrows, H, H, ACT_NONE, lange + off * H, nullptr, st, 1.f, 0, h, "esm.gemm:"));       // Mo = out_proj + LP
   float* t1 = h->w_a;
   float* t2 = h->w_qkv;   // (q, k, v are dead; w_b still holds the lang embedding of every row)
   TRY(ln(Mo, h->esm_ln2w, h->esm_ln2b, t1, nullptr, lrows, 1e-5f, st));
-  TRY(linear(t1, h->esm_f0w, h->esm_f0b, t2, lrows, H, H, ACT_RELU, nullptr, nullptr, st));
-  TRY(linear(t2, h->esm_f2w, h->esm_f2b, h->w_a, lrows, H, H, ACT_NONE, Mo, nullptr, st));      // Fo = ffn + Mo
+  TRY(linear(t1, h->esm_f0w, h->esm_f0b, t2, lrows, H, H, ACT_RELU, nullptr, nullptr, st, 1.f, 0, h, "esm.gemm:"));
+  TRY(linear(t2, h->esm_f2w, h->esm_f2b, h->w_a, lrows, H, H, ACT_NONE, Mo, nullptr, st, 1.f, 0, h, "esm.gemm:"));      // Fo = ffn + Mo
   }
   // ---- sum of embeddings, *sqrt(H) + reversed positional table, mask (the rows asked for; row0 * Tt is a multiple of Tt: the position of a
   // row inside its utterance is unchanged)
@@ -1532,7 +1585,7 @@ static int encode_impl(bsg_fs2midi* h, const int64_t* txt, const int64_t* pitch_
                      (const long long*)pitch_midi + off, midi_dur + off, (const long long*)is_slur + off, h->Emidi, h->Wdur, h->bdur, h->Eslur,
                      h->rel_table, x, h->w_keep, lrows, Tt, sq);
   BSG_LAUNCH_CHECK();
-  TRY(fft_stack(h, h->enc, h->enc_lnw, h->enc_lnb, h->cfg.enc_ffn_kernel_size, x, h->w_keep, nb, Tt, st));
+  TRY(fft_stack(h, h->enc, h->enc_lnw, h->enc_lnb, h->cfg.enc_ffn_kernel_size, x, h->w_keep, nb, Tt, st, "enc."));
   BSG_HIP(hipMemcpyAsync(enc_out, x, lrows * H * sizeof(float), hipMemcpyDeviceToDevice, st));
   if (dur) {
     // duration predictor (tts_modules.py:108-133) on (enc + spk) * keep
@@ -1563,7 +1616,10 @@ extern "C" int bsg_fs2midi_encode(bsg_fs2midi* h, const int64_t* txt, const int6
   BSG_REQUIRE(h && txt && pitch_midi && midi_dur && is_slur && lang && spk_id && enc_out, "fs2midi_encode: null argument");
   BSG_REQUIRE(B > 0 && Tt > 0 && Tt <= h->cfg.n_rel, "fs2midi_encode: B=%d T_txt=%d (rel-pos table has %d rows)", B, Tt, h->cfg.n_rel);
   BSG_REQUIRE((dur_xs == nullptr) == (dur == nullptr), "fs2midi_encode: dur_xs and dur go together");
-  return encode_impl(h, txt, pitch_midi, midi_dur, is_slur, lang, spk_id, B, Tt, 0, B, enc_out, dur_xs, dur, (hipStream_t)stream);
+  h->path.clear();
+  const int rc = encode_impl(h, txt, pitch_midi, midi_dur, is_slur, lang, spk_id, B, Tt, 0, B, enc_out, dur_xs, dur, (hipStream_t)stream);
+  h->path_enc_len = h->path.size();
+  return rc;
 }
 
 extern "C" int bsg_fs2midi_encode_rows(bsg_fs2midi* h, const int64_t* txt, const int64_t* pitch_midi, const float* midi_dur,
@@ -1574,7 +1630,10 @@ extern "C" int bsg_fs2midi_encode_rows(bsg_fs2midi* h, const int64_t* txt, const
   BSG_REQUIRE(B > 0 && Tt > 0 && Tt <= h->cfg.n_rel, "fs2midi_encode_rows: B=%d T_txt=%d (rel-pos table has %d rows)", B, Tt, h->cfg.n_rel);
   BSG_REQUIRE(row0 >= 0 && n_rows > 0 && row0 + n_rows <= B, "fs2midi_encode_rows: rows [%d, %d) of a batch of %d", row0, row0 + n_rows, B);
   BSG_REQUIRE((dur_xs == nullptr) == (dur == nullptr), "fs2midi_encode_rows: dur_xs and dur go together");
-  return encode_impl(h, txt, pitch_midi, midi_dur, is_slur, lang, spk_id, B, Tt, row0, n_rows, enc_out, dur_xs, dur, (hipStream_t)stream);
+  h->path.clear();
+  const int rc = encode_impl(h, txt, pitch_midi, midi_dur, is_slur, lang, spk_id, B, Tt, row0, n_rows, enc_out, dur_xs, dur, (hipStream_t)stream);
+  h->path_enc_len = h->path.size();
+  return rc;
 }
 
 extern "C" int bsg_fs2midi_last_rows(const bsg_fs2midi* h, int32_t* token_rows, int32_t* stack_rows) {
@@ -1582,6 +1641,29 @@ extern "C" int bsg_fs2midi_last_rows(const bsg_fs2midi* h, int32_t* token_rows, 
   *token_rows = h->last_token_rows;
   *stack_rows = h->last_stack_rows;
   return BSG_OK;
+}
+
+extern "C" const char* bsg_fs2midi_last_path(bsg_fs2midi* h) { return h && !h->path.empty() ? h->path.c_str() : "none"; }
+
+// Test hook: every activation workspace of the handle, at its current capacity, filled with 0xFF bytes (a NaN as fp16 and as fp32) — data
+// that a correct kernel never lets into a result.  Not the arrival counters of the key split (they must stay zero between launches), not
+// the position words, not weights.
+static int poison_ws(bsg_fs2midi* h, hipStream_t st) {
+  const size_t r = h->cap_rows;
+  const struct { void* p; size_t bytes; } ws[] = {
+      {h->w_x, r * H * sizeof(float)},       {h->w_a, r * H * sizeof(float)},       {h->w_b, r * H * sizeof(float)},
+      {h->w_c, r * H * sizeof(float)},       {h->w_qkv, r * 3 * H * sizeof(float)}, {h->w_ffn, r * 4 * H * sizeof(float)},
+      {h->w_keep, r * sizeof(float)},        {h->w_ap, 2 * r * H * sizeof(unsigned short)},
+      {h->w_fp, 2 * r * 4 * H * sizeof(unsigned short)},
+      {h->w_scores, h->cap_scores * sizeof(float)},                                 {h->w_fsk, h->cap_fsk * sizeof(float)}};
+  for (const auto& w : ws)
+    if (w.p && w.bytes) BSG_HIP(hipMemsetAsync(w.p, 0xFF, w.bytes, st));
+  return BSG_OK;
+}
+
+extern "C" int bsg_fs2midi_debug_poison_workspace(bsg_fs2midi* h, void* stream) {
+  BSG_REQUIRE(h, "fs2midi_debug_poison_workspace: null handle");
+  return poison_ws(h, (hipStream_t)stream);
 }
 
 extern "C" int bsg_length_regulator(const int64_t* dur, const int64_t* txt, int64_t* mel2ph, int32_t B, int32_t Tt, int32_t T,
@@ -1600,6 +1682,7 @@ extern "C" int bsg_fs2midi_decode(bsg_fs2midi* h, const float* enc_out, const in
   BSG_REQUIRE(h && enc_out && mel2ph && spk_id && speechsing && decoder_inp, "fs2midi_decode: null argument");
   BSG_REQUIRE(B > 0 && Tt > 0 && T > 0 && T < h->cfg.n_pos, "fs2midi_decode: B=%d T_txt=%d T=%d (position table has %d rows)", B, Tt, T, h->cfg.n_pos);
   hipStream_t st = (hipStream_t)stream;
+  h->path.resize(h->path_enc_len);   // the record keeps the encode this decode follows
   const long long rows = (long long)B * T;
   TRY(ensure_ws(h, (size_t)rows, mel_out ? (size_t)B * h->cfg.num_heads * T * T : 0, st));
   const dim3 rg(cdiv(rows, 4)), rb(256);
@@ -1613,7 +1696,7 @@ extern "C" int bsg_fs2midi_decode(bsg_fs2midi* h, const float* enc_out, const in
   BSG_LAUNCH_CHECK();
   hipLaunchKernelGGL(decoder_entry_kernel, rg, rb, 0, st, x, (const int*)h->w_pos, h->dec_table, h->dec_alpha, h->w_keep, rows, h->cfg.n_pos);
   BSG_LAUNCH_CHECK();
-  TRY(fft_stack(h, h->dec, h->dec_lnw, h->dec_lnb, h->cfg.dec_ffn_kernel_size, x, h->w_keep, B, T, st));
+  TRY(fft_stack(h, h->dec, h->dec_lnw, h->dec_lnb, h->cfg.dec_ffn_kernel_size, x, h->w_keep, B, T, st, "dec."));
   // mel_out = Linear(H -> M)(x) * (mel2ph > 0)                                        (fastspeech/fs2.py:236-240)
   TRY(linear(x, h->mel_w, h->mel_b, mel_out, rows, h->cfg.out_dims, H, ACT_NONE, nullptr, nullptr, st));
   // ... * tgt_nonpadding, which comes from mel2ph (not from the decoder's own |x| test)
@@ -1766,6 +1849,7 @@ extern "C" int bsg_fftden_forward(bsg_fftden* h, const float* x, const int64_t* 
   hipStream_t st = (hipStream_t)stream;
   const long long rows = (long long)B * T;
   bsg_fs2midi* c = h->core;
+  c->path.clear();
   // x [B][M][T] -> [B*T][M]; xp = input_projection                                        (:57-58)
   hipLaunchKernelGGL(transpose_brc_kernel, dim3(cdiv(T, 32), cdiv(h->M, 32), B), dim3(256), 0, st, x, h->xT, h->M, T);
   BSG_LAUNCH_CHECK();
@@ -1792,10 +1876,25 @@ extern "C" int bsg_fftden_forward(bsg_fftden* h, const float* x, const int64_t* 
   BSG_LAUNCH_CHECK();
   hipLaunchKernelGGL(decoder_entry_kernel, rg, rb, 0, st, xs, (const int*)c->w_pos, h->table, h->alpha, c->w_keep, rows, h->n_pos);
   BSG_LAUNCH_CHECK();
-  TRY(fft_stack(c, h->layers, h->lnw, h->lnb, h->ksz, xs, c->w_keep, B, T, st));
+  TRY(fft_stack(c, h->layers, h->lnw, h->lnb, h->ksz, xs, c->w_keep, B, T, st, "den."));
   TRY(linear(xs, h->mel_w, h->mel_b, h->mel, rows, h->M, H, ACT_NONE, nullptr, nullptr, st));       // get_mel_out (:98)
   hipLaunchKernelGGL(transpose_brc_kernel, dim3(cdiv(h->M, 32), cdiv(T, 32), B), dim3(256), 0, st, (const float*)h->mel, eps, T, h->M);
   BSG_LAUNCH_CHECK();
+  return BSG_OK;
+}
+
+extern "C" const char* bsg_fftden_last_path(bsg_fftden* h) { return h && h->core && !h->core->path.empty() ? h->core->path.c_str() : "none"; }
+
+// as bsg_fs2midi_debug_poison_workspace, plus this handle's own per-call buffers (not `condpart`: bsg_fftden_prepare's result is an input of
+// every forward)
+extern "C" int bsg_fftden_debug_poison_workspace(bsg_fftden* h, void* stream) {
+  BSG_REQUIRE(h && h->core, "fftden_debug_poison_workspace: null handle");
+  hipStream_t st = (hipStream_t)stream;
+  TRY(poison_ws(h->core, st));
+  float* own[] = {h->xT, h->xp, h->te, h->tvec};
+  for (float* p : own)
+    if (p && h->cap) BSG_HIP(hipMemsetAsync(p, 0xFF, h->cap * H * sizeof(float), st));
+  if (h->mel && h->cap) BSG_HIP(hipMemsetAsync(h->mel, 0xFF, h->cap * h->M * sizeof(float), st));
   return BSG_OK;
 }
 

@@ -652,12 +652,15 @@ int launch_gemm(const GemmArgs& g_in, hipStream_t st) {
     if (gemm_split_enabled()) {
       const long long wgs = (long long)cdiv(g.N, FBN) * cdiv(g.M, 128) * g.batch;
       const bool sm = wgs < 3 * 256;
+      if (g.form_out) *g.form_out = sm ? "gemm_split/64" : "gemm_split/128";
       if (g.trans_b) return sm ? launch_split<64, true>(g, st) : launch_split<128, true>(g, st);
       return sm ? launch_split<64, false>(g, st) : launch_split<128, false>(g, st);
     }
+    if (g.form_out) *g.form_out = small ? "gemm_fast/64" : "gemm_fast/128";
     if (g.trans_b) return small ? launch_fast<64, 16, true>(g, st) : launch_fast<128, 16, true>(g, st);
     return small ? launch_fast<64, 16, false>(g, st) : launch_fast<128, 16, false>(g, st);
   }
+  if (g.form_out) *g.form_out = "gemm_f32";
   dim3 grid(cdiv(g.N, BN), cdiv(g.M, BM), g.batch);
   if (g.trans_b)
     hipLaunchKernelGGL(gemm_f32_kernel<true>, grid, dim3(256), 0, st, g);

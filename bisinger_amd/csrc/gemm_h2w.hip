@@ -506,6 +506,9 @@ int h2w_launch(const H2wArgs& g, hipStream_t st) {
   }
   hipLaunchKernelGGL((gemm_h2w_kernel<ACT_IS_A, MI, KK, NS>), dim3(nwg), dim3(256), lds, st, g);
   BSG_LAUNCH_CHECK();
+  // what was launched, for the caller's launch record: tile height, then the weight ring (KK = 16: the 256-deep slices of the 32-row tiles)
+  if (g.form_out) *g.form_out = KK == 16 ? "h2w/32/deep" : MI == 1 ? (NS == 16 ? "h2w/32/ring16" : NS == 8 ? "h2w/32/ring8" : "h2w/32/ring4")
+                              : MI == 2 ? (NS == 8 ? "h2w/64/ring8" : "h2w/64/ring4") : "h2w/128/ring4";
   return BSG_OK;
 }
 

@@ -307,6 +307,17 @@ class FastSpeech2MIDI(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         _lib.check(_lib.load().bsg_fs2midi_last_rows(self._h if self._h is not None else self.handle(), byref(a), byref(b)), 'bsg_fs2midi_last_rows')
         return a.value, b.value
 
+    def last_path(self):
+        """The launch forms of the last encode and of the decode after it, as blank-separated tokens in launch order
+        (include/bisinger_hip.h, bsg_fs2midi_last_path): 'esm:wave enc.qkv:fused enc.attn:planes/ks2 enc.gemm:h2w/32/deep ... dec. ...';
+        'none' before the first call.  Test introspection."""
+        return _lib.load().bsg_fs2midi_last_path(self._h).decode() if self._h is not None else 'none'
+
+    def poison_workspace(self):
+        """Test hook (bsg_fs2midi_debug_poison_workspace): NaN bytes over every activation workspace of the handle."""
+        with torch.cuda.device(next(self.parameters()).device):
+            _lib.check(_lib.load().bsg_fs2midi_debug_poison_workspace(self.handle(), _lib.stream_ptr()), 'bsg_fs2midi_debug_poison_workspace')
+
     @torch.no_grad()
     def regulate(self, enc):
         """LengthRegulator on the predicted durations (tts_modules.py:161-191); one host sync, as in the

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define BSG_ABI_VERSION 10
+#define BSG_ABI_VERSION 11
 
 #define BSG_OK 0
 #define BSG_EINVAL (-22)  /* bad argument / shape the kernels do not support            */
@@ -304,6 +304,28 @@ int bsg_fs2midi_encode_rows(bsg_fs2midi* h, const int64_t* txt, const int64_t* p
  * (encoder or decoder) — how a test sees that a rank's front did not encode the other ranks' utterances. */
 int bsg_fs2midi_last_rows(const bsg_fs2midi* h, int32_t* token_rows, int32_t* stack_rows);
 
+/* ABI v11: the launch forms of the handle's last bsg_fs2midi_encode[_rows] and of the last bsg_fs2midi_decode after it, as tokens separated
+ * by blanks in launch order; "none" for a null handle or before the first call.  A token is written at the branch that launched, so it
+ * names what ran, not what the thresholds would choose; a form that a stack launches again (in every layer, as a rule) is named once.
+ * An encode starts the record anew; a decode replaces the tokens of the decode before it.
+ *   esm:wave | esm:thread                              esm_attention_wave_kernel | esm_attention_kernel<32>
+ *   <s>.qkv:fused | split_kernel | h2w | gemm          Q / K / V^T planes from the QKV product's own epilogue | fp32 QKV + qkv_split_kernel |
+ *                                                      fp32 QKV of the pre-split GEMM | of launch_gemm
+ *   <s>.attn:planes/ks<n>                              flash_attn_planes_kernel<2>, the keys over n workgroups
+ *   <s>.attn:split/nw2 | split/nw4 | flash/nw2 | flash/nw4 | softmax
+ *                                                      flash_attn_split_kernel<NW> | flash_attn_kernel<NW> | score tensor + masked_softmax_kernel
+ *   <s>.gemm:h2w/<32|64|128>/<ring4|ring8|ring16|deep> gemm_h2w_kernel: rows per tile, steps of the weight ring (deep: 256-deep slices)
+ *   <s>.gemm:gemm_split/<64|128> | gemm_fast/<64|128> | gemm_f32
+ *                                                      launch_gemm: split-fp16 | fp32 matrix pipe | the unaligned form
+ * with <s> = esm (the ESM's Linear layers), enc, dec (the FFT stacks); bsg_fftden_last_path: den, cleared by every bsg_fftden_forward.
+ * The string belongs to the handle: valid until its next call or its destruction. */
+const char* bsg_fs2midi_last_path(bsg_fs2midi* h);
+
+/* ABI v11, test hook: fills every activation workspace of the handle, at its current capacity, with 0xFF bytes (NaN as fp16 and as fp32)
+ * on `stream` — stale data that no result may depend on (tests/test_gpu_fs2_shapes.py).  Weights, the key split's arrival counters and,
+ * for bsg_fftden, the result of bsg_fftden_prepare are left alone. */
+int bsg_fs2midi_debug_poison_workspace(bsg_fs2midi* h, void* stream);
+
 /* mel2ph [B,T] from dur [B,T_txt] (padded tokens, txt == 0, count 0 when txt != NULL); T = max_b sum(dur). */
 int bsg_length_regulator(const int64_t* dur, const int64_t* txt, int64_t* mel2ph, int32_t B, int32_t T_txt,
                          int32_t T, void* stream);
@@ -328,6 +350,9 @@ int bsg_fftden_create(bsg_fftden** out, int32_t in_dims, int32_t n_layers, int32
 void bsg_fftden_destroy(bsg_fftden* h);
 int bsg_fftden_prepare(bsg_fftden* h, const float* cond, int32_t B, int32_t T, void* stream);
 int bsg_fftden_forward(bsg_fftden* h, const float* x, const int64_t* t, float* eps, int32_t B, int32_t T, void* stream);
+/* ABI v11: as bsg_fs2midi_last_path / bsg_fs2midi_debug_poison_workspace, for the stack of the last bsg_fftden_forward ("den." tokens) */
+const char* bsg_fftden_last_path(bsg_fftden* h);
+int bsg_fftden_debug_poison_workspace(bsg_fftden* h, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * HiFi-GAN generator forward (mel -> waveform).

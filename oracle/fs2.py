@@ -221,6 +221,7 @@ def fs2_forward(sd, inp, prefix='fs2.', hp=None, skip_decoder=False, dtype=torch
         # rows); everything frame-level is per-row, so only this rank's rows continue
         enc, spk, style, mel2ph = enc[rows], spk[rows], style[rows], mel2ph[rows]
     ret['mel2ph'] = mel2ph
+    ret['enc_out'] = enc      # the encoder's output (of `rows`), what bsg_fs2midi_encode returns: for the tests of the token-level front
     dec_in = F.pad(enc, [0, 0, 1, 0])
     dec_in = torch.gather(dec_in, 1, mel2ph[..., None].repeat([1, 1, H]))
     tgt_keep = (mel2ph > 0).to(dtype)[:, :, None]

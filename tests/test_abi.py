@@ -35,6 +35,13 @@ def test_hifigan_last_path_without_a_forward():
     assert _lib.load().bsg_hifigan_last_path(None) == b'none'
 
 
+def test_fs2_last_path_without_a_call():
+    """bsg_fs2midi_last_path / bsg_fftden_last_path name launch forms; a null handle has launched nothing (the GPU side:
+    tests/test_gpu_fs2_shapes.py)."""
+    assert _lib.load().bsg_fs2midi_last_path(None) == b'none'
+    assert _lib.load().bsg_fftden_last_path(None) == b'none'
+
+
 def test_product_path_fails_loudly_without_library(monkeypatch, tmp_path):
     import pytest
     monkeypatch.setattr(_lib, '_lib', None)
