@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'lib', 'libbisinger_hip.so')
 if os.environ.get('BSG_LIB'):      # development: an alternative build of the same ABI (kernel experiments)
     LIB_PATH = os.environ['BSG_LIB']
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 class BsgError(RuntimeError):
@@ -118,6 +118,9 @@ _SIGS = {
     'bsg_pitchext_create': (c_int32, [POINTER(c_void_p), POINTER(PitchextCfg), POINTER(c_void_p), c_int32, c_void_p, c_void_p]),
     'bsg_pitchext_destroy': (None, [c_void_p]),
     'bsg_pitchext_forward': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
+    'bsg_wavden_create': (c_int32, [POINTER(c_void_p), c_int32, c_int32, c_int32, c_void_p]),
+    'bsg_wavden_destroy': (None, [c_void_p]),
+    'bsg_wavden_forward': (c_int32, [c_void_p, c_void_p, c_void_p, POINTER(c_int32), c_int32, c_int32, c_float, c_void_p]),
     'bsg_weight_norm_fold': (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     'bsg_gemm_f32': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                c_int32, c_int32, c_int32, c_int64, c_int64, c_int64, c_int32, c_void_p]),

@@ -234,9 +234,10 @@ class DiffSingerE2EInfer(BaseSVSInfer):
         new[1:] = (d[1:] != d[:-1]) | (p[1:] != p[:-1])
         return int(np.ceil(d[new].sum() * hparams['audio_sample_rate'] / hparams['hop_size']))
 
-    def _generate_wavs(self, items, seed, ragged=False):
+    def _generate_wavs(self, items, seed, ragged=False, denoise_c=None):
         """One padded batch -> (list of trimmed waveforms, frames per item, padded frame count T).  ``ragged``: the mel decoder runs every
-        row at its own length (GaussianDiffusion.forward(ragged=True)); the vocoder still runs the padded batch."""
+        row at its own length (GaussianDiffusion.forward(ragged=True)); the vocoder still runs the padded batch.  ``denoise_c`` > 0: the
+        padded batch of waveforms goes through ONE launch of the spectral post-filter (vocoders.denoise), every row at its own length."""
         sample = self.collate(items)
         output = self._generate(sample, seed, ragged)
         mel, mel2ph = output['mel_out'], output['mel2ph']
@@ -248,9 +249,12 @@ class DiffSingerE2EInfer(BaseSVSInfer):
         else:
             wav = self.vocoder(mel.transpose(2, 1))[:, 0]
         n_frames = (mel2ph > 0).sum(-1).tolist()
+        if denoise_c is not None and denoise_c > 0:
+            from .vocoders import denoise
+            wav = denoise(wav.contiguous(), v=denoise_c, lengths=[n * hop for n in n_frames])
         return [wav[i, :n * hop].cpu().numpy() for i, n in enumerate(n_frames)], n_frames, int(mel.shape[1])
 
-    def forward_batch(self, items, seed=None, max_frames=None, max_sentences=None, ragged=False):
+    def forward_batch(self, items, seed=None, max_frames=None, max_sentences=None, ragged=False, denoise_c=None):
         """Batched generation: list of items -> list of 1-D waveforms (in the order given), each trimmed to its utterance.
 
         With ``max_frames`` (budget on padded frames per batch: rows x longest row) and/or ``max_sentences`` the items are
@@ -264,7 +268,11 @@ class DiffSingerE2EInfer(BaseSVSInfer):
 
         ``ragged=True``: buckets by ``max_sentences`` only (``max_frames`` is refused: a ragged bucket computes no padding), and the mel
         decoder runs every row at its own length, whole rows packed into launch groups of one 64-frame tile per CU
-        (GaussianDiffusion.forward(ragged=True)); ``last_batch_stats`` adds ``launch_groups`` and ``tiles`` of those launches."""
+        (GaussianDiffusion.forward(ragged=True)); ``last_batch_stats`` adds ``launch_groups`` and ``tiles`` of those launches.
+
+        ``denoise_c`` > 0: the reference's ``vocoder_denoise_c`` post-filter (vocoders.denoise) with that value, on each bucket's padded batch
+        of waveforms in one launch, every row at its own length, before the rows are trimmed and copied out.  None (default): not applied
+        (``forward_model`` never applies it: the reference's live entry point ignores the key)."""
         est = [self.estimate_frames(it) for it in items]
         if ragged and max_frames is not None:
             raise ValueError('forward_batch(ragged=True): buckets by max_sentences only; max_frames budgets padded frames')
@@ -275,7 +283,7 @@ class DiffSingerE2EInfer(BaseSVSInfer):
         wavs, frames = [None] * len(items), [0] * len(items)
         padded = groups = tiles = 0
         for b in buckets:
-            w, nf, T = self._generate_wavs([items[i] for i in b], seed, ragged)
+            w, nf, T = self._generate_wavs([items[i] for i in b], seed, ragged, denoise_c)
             padded += T * len(b)
             if ragged:
                 from .diffnet import ragged_plan

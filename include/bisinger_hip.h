@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define BSG_ABI_VERSION 11
+#define BSG_ABI_VERSION 12
 
 #define BSG_OK 0
 #define BSG_EINVAL (-22)  /* bad argument / shape the kernels do not support            */
@@ -430,6 +430,26 @@ int bsg_pitchext_create(bsg_pitchext** out, const bsg_pitchext_cfg* cfg, const v
                         const float* pos_table, void* stream);
 void bsg_pitchext_destroy(bsg_pitchext* h);
 int bsg_pitchext_forward(bsg_pitchext* h, const float* mel, float* pitch_pred, float* f0, int32_t B, int32_t T, void* stream);
+
+/* ABI v12: the spectral post-filter of the vocoder output, hparams['vocoder_denoise_c'] (vocoders/hifigan.py:66-69 -> vocoders/vocoder_utils.py:7-15:
+ * librosa.stft(center, zero padding, periodic Hann of win_size points) -> |S| - v clipped at 0 with the phase kept -> librosa.istft), as one
+ * launch for a batch (csrc/wavden.hip).  NOT the FFT-transformer denoiser of the diffusion model, which is bsg_fftden_*.
+ *   bsg_wavden_create   accepted (fft_size, hop_size, win_size): fft_size 512 or 1024, hop_size = fft_size / 4, fft_size / 2 <= win_size <= fft_size
+ *                       (every BiSinger chain is (512, 128, 512), configs/tts/base.yaml (1024, 256, 1024)).  Anything else: BSG_EINVAL and a message
+ *                       naming the accepted set, before any device call.  Builds the two transform bases (float64 on the host) and uploads them
+ *                       on `stream`, which it waits for.
+ *   bsg_wavden_forward  wav, out: device [B][stride] fp32.  n: HOST array of B sample counts, read during the call (NULL: every row has `stride`
+ *                       samples).  Row b is filtered as if it were alone at length n[b]: samples at and beyond n[b] are never read, its
+ *                       result does not depend on the other rows (bit for bit), out is written up to `stride`: hop_size * (n[b] / hop_size)
+ *                       filtered samples, then zeros.  v >= 0 is the magnitude subtracted from every bin.  `out` must not overlap `wav`
+ *                       (BSG_EINVAL): not in place.  B < 1, stride < 1, v < 0 or not finite, n[b] outside 0 .. stride: BSG_EINVAL, checked before
+ *                       the handle is looked at.  No allocation, no wait, no device-side communication between workgroups: capturable; the
+ *                       lengths are baked into a captured launch.  All products run on the fp32 matrix pipe: there is no operand range, no
+ *                       status word and nothing to repeat. */
+typedef struct bsg_wavden bsg_wavden;
+int bsg_wavden_create(bsg_wavden** out, int32_t n_fft, int32_t hop, int32_t win, void* stream);
+void bsg_wavden_destroy(bsg_wavden* h);
+int bsg_wavden_forward(bsg_wavden* h, const float* wav, float* out, const int32_t* n, int32_t B, int32_t stride, float v, void* stream);
 
 /* w[d0,...] = g[d0] * v[d0,...] / ||v[d0,...]||   (remove_weight_norm, hifigan.py:175-182) */
 int bsg_weight_norm_fold(const float* g, const float* v, float* w, int32_t dim0, int32_t inner, void* stream);
