@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'lib', 'libbisinger_hip.so')
 if os.environ.get('BSG_LIB'):      # development: an alternative build of the same ABI (kernel experiments)
     LIB_PATH = os.environ['BSG_LIB']
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 class BsgError(RuntimeError):
@@ -38,6 +38,13 @@ class HifiganCfg(Structure):
 
 class PitchextCfg(Structure):
     _fields_ = [(n, c_int32) for n in ('hidden_size', 'n_mel', 'conv_layers', 'predictor_layers', 'predictor_kernel', 'use_uv', 'n_pos')]
+
+
+class PwgCfg(Structure):
+    _fields_ = [(n, c_int32) for n in ('in_channels', 'out_channels', 'kernel_size', 'layers', 'stacks', 'residual_channels', 'gate_channels',
+                                       'skip_channels', 'aux_channels', 'aux_context_window', 'bias', 'use_causal_conv', 'upsample_net',
+                                       'interpolate_nearest', 'freq_axis_kernel_size', 'n_scales')] + \
+               [('upsample_scales', c_int32 * 8), ('use_pitch_embed', c_int32), ('n_pitch', c_int32), ('hop_size', c_int32)]
 
 
 class Schedule(Structure):
@@ -121,6 +128,12 @@ _SIGS = {
     'bsg_wavden_create': (c_int32, [POINTER(c_void_p), c_int32, c_int32, c_int32, c_void_p]),
     'bsg_wavden_destroy': (None, [c_void_p]),
     'bsg_wavden_forward': (c_int32, [c_void_p, c_void_p, c_void_p, POINTER(c_int32), c_int32, c_int32, c_float, c_void_p]),
+    'bsg_pwg_n_weights': (c_int32, [POINTER(PwgCfg)]),
+    'bsg_pwg_create': (c_int32, [POINTER(c_void_p), POINTER(PwgCfg), POINTER(c_void_p), c_int32, c_void_p]),
+    'bsg_pwg_destroy': (None, [c_void_p]),
+    'bsg_pwg_forward': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_void_p]),
+    'bsg_pwg_last_path': (c_char_p, [c_void_p]),
+    'bsg_pwg_debug_poison_workspace': (c_int32, [c_void_p, c_void_p]),
     'bsg_weight_norm_fold': (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     'bsg_gemm_f32': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                c_int32, c_int32, c_int32, c_int64, c_int64, c_int64, c_int32, c_void_p]),

@@ -1,10 +1,16 @@
-"""Vocoder registry + the HiFi-GAN wrapper — vocoders/base_vocoder.py:6-40 and vocoders/hifigan.py:17-69.
+"""Vocoder registry + the HiFi-GAN and Parallel WaveGAN wrappers — vocoders/base_vocoder.py:6-40, vocoders/hifigan.py:17-69 and
+vocoders/pwg.py:18-105.
 
 ``register_vocoder`` / ``get_vocoder_cls(hparams)`` (short name, or the reference's dotted path
 ``vocoders.hifigan.HifiGAN``), ``BaseVocoder.spec2wav(mel[T,80]) -> wav[T*hop]``.  ``HifiGAN`` loads
 ``<vocoder_ckpt>/config.yaml`` + the newest ``model_ckpt_steps_*.ckpt`` (``['state_dict']['model_gen']``, weight-norm
 layout, strict) — or, when there is no config.yaml, the original release's ``config.json`` + ``generator_v1``
-(``['generator']``) — folds the weight norm and runs the generator on the HIP kernels.  PWG is out of scope.
+(``['generator']``) — folds the weight norm and runs the generator on the HIP kernels.
+
+``PWG`` (``vocoder: pwg``, the default of configs/tts/base.yaml) loads ``<vocoder_ckpt>/config.yaml`` + the newest
+``model_ckpt_steps_*.ckpt`` (``['state_dict']`` keys ``model_gen.*``, not strict) or, with ``vocoder_ckpt == ''``, the official release's
+files under ``wavegan_pretrained/`` (``['model']['generator']`` + mean / scale statistics), and runs ``ParallelWaveGANGenerator`` on the
+kernels of csrc/pwg.hip.  Its ``wav2spec`` / ``wav2mfcc`` are data preparation and stay ``NotImplementedError``.
 
 ``denoise(wav, v)`` is the spectral post-filter behind ``hparams['vocoder_denoise_c']`` (vocoders/vocoder_utils.py:7-15: STFT, ``|S| - v``
 clipped at 0 with the phase kept, inverse STFT).  The reference runs it through librosa on the host; here it is one fused HIP launch
@@ -159,3 +165,116 @@ class HifiGAN(BaseVocoder):
         if hparams.get('vocoder_denoise_c', 0.0) > 0:                  # vocoders/hifigan.py:66-69, on the device tensor
             y = denoise(y, v=hparams['vocoder_denoise_c'])
         return y.cpu().numpy()
+
+
+def f0_to_coarse(f0):
+    """utils/pitch_utils.py:15-31 on the host (numpy): f0 in Hz -> one of 255 mel-spaced bins 1 .. 255 (1: unvoiced or below 50 Hz)."""
+    f0_bin, f0_min, f0_max = 256, 50.0, 1100.0
+    mel_min, mel_max = 1127 * np.log(1 + f0_min / 700), 1127 * np.log(1 + f0_max / 700)
+    f0_mel = 1127 * np.log(1 + np.asarray(f0, np.float64) / 700)
+    f0_mel = np.where(f0_mel > 0, (f0_mel - mel_min) * (f0_bin - 2) / (mel_max - mel_min) + 1, f0_mel)
+    return np.rint(np.clip(f0_mel, 1, f0_bin - 1)).astype(np.int64)
+
+
+class _Scaler:
+    """sklearn's StandardScaler.transform for given statistics, in numpy: (x - mean) / scale."""
+
+    def __init__(self, mean, scale):
+        self.mean_, self.scale_ = np.asarray(mean, np.float64), np.asarray(scale, np.float64)
+
+    def transform(self, x):
+        return ((np.asarray(x, np.float64) - self.mean_) / self.scale_).astype(np.float32)
+
+
+def _read_hdf5(path, name):
+    try:
+        import h5py
+    except ImportError as e:
+        raise RuntimeError(f'{path}: hdf5 statistics (config format "hdf5") need h5py, which is not installed; convert them to npy '
+                           f'([mean, scale]) and set format: "npy"') from e
+    with h5py.File(path, 'r') as f:
+        return f[name][()]
+
+
+def load_pwg_model(config_path, checkpoint_path, stats_path, device=None):
+    """vocoders/pwg.py:18-52: config.yaml['generator_params'] + either the official release's checkpoint (['model']['generator'], strict,
+    with mean / scale statistics in hdf5 or npy) or a trainer checkpoint (['state_dict'] keys model_gen.*, not strict, no scaler);
+    then the fold.  -> (model, scaler or None, config, device)."""
+    import yaml
+    from .pwg import ParallelWaveGANGenerator
+    with open(config_path) as f:
+        config = yaml.safe_load(f)
+    device = device or torch.device('cuda')
+    model = ParallelWaveGANGenerator(**config['generator_params'])
+    ckpt_dict = torch.load(checkpoint_path, map_location='cpu')
+    if 'state_dict' not in ckpt_dict:      # official vocoder
+        model.load_state_dict(ckpt_dict['model']['generator'])
+        fmt = 'npy' if str(stats_path).endswith('.npy') else config['format']      # the reader follows the file that is there
+        if fmt == 'hdf5':
+            scaler = _Scaler(_read_hdf5(stats_path, 'mean'), _read_hdf5(stats_path, 'scale'))
+        elif fmt == 'npy':
+            st = np.load(stats_path)
+            scaler = _Scaler(st[0], st[1])
+        else:
+            raise ValueError('support only hdf5 or npy format.')
+    else:                                  # custom PWG vocoder: the trainer's state dict holds the generator under model_gen.
+        sd = {k[len('model_gen.'):]: v for k, v in ckpt_dict['state_dict'].items() if k.startswith('model_gen.')}
+        model.load_state_dict(sd, strict=False)
+        scaler = None
+    model = model.eval().to(device)
+    model.remove_weight_norm()
+    print(f'| Loaded model parameters from {checkpoint_path}.')
+    print(f'| PWG device: {device}.')
+    return model, scaler, config, device
+
+
+@register_vocoder
+class PWG(BaseVocoder):
+    def __init__(self, device=None):
+        import glob
+        import re
+        if hparams['vocoder_ckpt'] == '':      # vocoders/pwg.py:58-69: the pretrained LJSpeech release
+            base_dir = 'wavegan_pretrained'
+            ckpts = glob.glob(f'{base_dir}/checkpoint-*steps.pkl')
+            assert ckpts, f'no checkpoint-*steps.pkl under {base_dir}'
+            ckpt = sorted(ckpts, key=lambda x: int(re.findall(r'checkpoint-(\d+)steps\.pkl$', x)[0]))[-1]
+            print('| load PWG: ', ckpt)
+            stats = f'{base_dir}/stats.h5'
+            if not os.path.exists(stats) and os.path.exists(f'{base_dir}/stats.npy'):      # the npy form of the same statistics
+                stats = f'{base_dir}/stats.npy'
+            self.model, self.scaler, self.config, self.device = load_pwg_model(f'{base_dir}/config.yaml', ckpt, stats, device)
+        else:                                  # :70-82: a trained checkpoint directory; its scaler is not used
+            base_dir = hparams['vocoder_ckpt']
+            print(base_dir)
+            ckpt = latest_ckpt(base_dir)
+            assert ckpt, f'no model_ckpt_steps_*.ckpt under {base_dir}'
+            print('| load PWG: ', ckpt)
+            self.scaler = None
+            self.model, _, self.config, self.device = load_pwg_model(f'{base_dir}/config.yaml', ckpt, f'{base_dir}/stats.h5', device)
+
+    def spec2wav(self, mel, **kwargs):
+        """vocoders/pwg.py:84-105: mel [T,80] (, f0 [T]) -> wav [T*hop].  ``z`` [T*hop]: the noise, supplied; otherwise it is drawn on the
+        device from the Philox stream of ``seed`` (default hparams['seed'])."""
+        config = self.config
+        w = config['generator_params']['aux_context_window']
+        c = np.asarray(mel)
+        if self.scaler is not None:
+            c = self.scaler.transform(c)
+        with torch.no_grad():
+            T = c.shape[0]
+            c = np.pad(c, ((w, w), (0, 0)), 'edge')
+            c = torch.as_tensor(c, dtype=torch.float32).unsqueeze(0).transpose(2, 1).contiguous().to(self.device)
+            p = kwargs.get('f0')
+            if p is not None:
+                p = f0_to_coarse(np.asarray(p))
+                p = torch.as_tensor(np.pad(np.asarray(p), ((w, w),), 'edge')[None, :], dtype=torch.int64).to(self.device)
+            z = kwargs.get('z')
+            if z is not None:
+                z = torch.as_tensor(np.asarray(z), dtype=torch.float32).view(1, 1, T * config['hop_size']).to(self.device)
+            seed = kwargs.get('seed')
+            y = self.model(z, c, p, seed=int(hparams.get('seed', 1234) if seed is None else seed)).view(-1)
+        return y.cpu().numpy()
+
+    @staticmethod
+    def wav2mfcc(wav_fn):
+        raise NotImplementedError('analysis (wav -> mfcc) is data preparation, outside the hot path')

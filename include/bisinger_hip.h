@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define BSG_ABI_VERSION 12
+#define BSG_ABI_VERSION 13
 
 #define BSG_OK 0
 #define BSG_EINVAL (-22)  /* bad argument / shape the kernels do not support            */
@@ -450,6 +450,55 @@ typedef struct bsg_wavden bsg_wavden;
 int bsg_wavden_create(bsg_wavden** out, int32_t n_fft, int32_t hop, int32_t win, void* stream);
 void bsg_wavden_destroy(bsg_wavden* h);
 int bsg_wavden_forward(bsg_wavden* h, const float* wav, float* out, const int32_t* n, int32_t B, int32_t stride, float v, void* stream);
+
+/* ABI v13: the Parallel WaveGAN generator, `vocoder: pwg` (modules/parallel_wavegan/models/parallel_wavegan.py:18-201 with
+ * layers/residual_block.py:39-129 and layers/upsample.py:125-183; vocoders/pwg.py:18-105), csrc/pwg.hip.  One residual layer is one launch:
+ * the dilated convolution, the aux term, the gate, both 1 x 1 products and the skip sum, all products on the fp32 matrix pipe (exact f32:
+ * no operand range, no status word, nothing to repeat, and no entry in the bsg_handle_* guard family).
+ *   bsg_pwg_create   dev_weights: bsg_pwg_n_weights(cfg) device pointers in the order of the generator's state dict AFTER remove_weight_norm()
+ *                    (a folded convolution lists its bias before its weight):
+ *                      first_conv.{bias[64], weight[64,1,1]}, upsample_net.conv_in.weight[80,80,2w+1],
+ *                      upsample_net.upsample.up_layers.{1,3,..}.weight[1,1,1,2s+1] (one per scale),
+ *                      conv_layers.i.{conv.bias[128], conv.weight[128,64,3], conv1x1_aux.weight[128,80,1], conv1x1_out.bias[64],
+ *                      conv1x1_out.weight[64,64,1], conv1x1_skip.bias[64], conv1x1_skip.weight[64,64,1]} for every layer,
+ *                      last_conv_layers.1.{bias[64], weight[64,64,1]}, last_conv_layers.3.{bias[1], weight[1,64,1]},
+ *                      and with use_pitch_embed pitch_embed.weight[n_pitch,80], c_proj.weight[80,160], c_proj.bias[80].
+ *                    Accepted: in = out = 1 channel, kernel_size 3, non-causal, residual = skip = 64, gate = 128, aux = 80, bias,
+ *                    ConvInUpsampleNetwork with the nearest stretch and freq_axis_kernel_size 1, layers % stacks == 0, the product of
+ *                    upsample_scales == hop_size.  Anything else: BSG_EINVAL with a message naming the value, before any device call.
+ *                    Copies and packs the weights (waits for `stream`).
+ *   bsg_pwg_forward  c [B][80][T + 2 w] (the caller edge-padded the mel by w = aux_context_window frames), pitch [B][T + 2 w] int64 (coarse
+ *                    pitch, required with use_pitch_embed, NULL without), z and y [B][1][T hop].  z == NULL: z is drawn from the Philox
+ *                    family of bsg_philox_normal, stream id 0x505747, key `seed`, element b T hop + t (B T hop must be a multiple of 4).
+ *                    Row b does not depend on the other rows, bit for bit.  Workspaces grow when (B, T) exceed what the handle has seen
+ *                    (then, and only then, the call waits for `stream` and allocates: not inside a capture); otherwise it only enqueues.
+ *                    A pitch index outside 0 .. n_pitch - 1 is clamped to that range (torch's embedding raises; the call cannot look at
+ *                    device data without a wait).  Like every handle here, a bsg_pwg is single-stream: the growth waits for `stream`
+ *                    only, so a forward of the same handle still in flight on another stream would lose its buffers.
+ *   bsg_pwg_n_weights  the length of dev_weights that create expects for cfg (221, 224 with use_pitch_embed, for the 30-layer config).
+ *   bsg_pwg_last_path  the launches of the handle's last forward in launch order, separated by blanks: [pitch] conv_in up<i>:x<scale> ..
+ *                    [philox] first layer<i>:f32/d<dilation> .. tail; "none" for a null handle or before the first forward.
+ *   bsg_pwg_debug_poison_workspace  test hook: fills the workspaces, at their current capacity, with 0xFF bytes (NaN) on `stream`. */
+typedef struct bsg_pwg bsg_pwg;
+typedef struct {
+  int32_t in_channels, out_channels, kernel_size, layers, stacks;
+  int32_t residual_channels, gate_channels, skip_channels, aux_channels, aux_context_window;
+  int32_t bias, use_causal_conv;
+  int32_t upsample_net;          /* 0: ConvInUpsampleNetwork; any other network: another code */
+  int32_t interpolate_nearest;   /* 1: upsample_params['interpolate_mode'] == 'nearest' */
+  int32_t freq_axis_kernel_size;
+  int32_t n_scales;
+  int32_t upsample_scales[8];
+  int32_t use_pitch_embed;
+  int32_t n_pitch;               /* rows of pitch_embed (300) */
+  int32_t hop_size;              /* config['hop_size']: samples per mel frame */
+} bsg_pwg_cfg;
+int bsg_pwg_n_weights(const bsg_pwg_cfg* cfg);
+int bsg_pwg_create(bsg_pwg** out, const bsg_pwg_cfg* cfg, const void* const* dev_weights, int32_t n_weights, void* stream);
+void bsg_pwg_destroy(bsg_pwg* h);
+int bsg_pwg_forward(bsg_pwg* h, const float* z, const float* c, const int64_t* pitch, float* y, int32_t B, int32_t T, uint64_t seed, void* stream);
+const char* bsg_pwg_last_path(bsg_pwg* h);
+int bsg_pwg_debug_poison_workspace(bsg_pwg* h, void* stream);
 
 /* w[d0,...] = g[d0] * v[d0,...] / ||v[d0,...]||   (remove_weight_norm, hifigan.py:175-182) */
 int bsg_weight_norm_fold(const float* g, const float* v, float* w, int32_t dim0, int32_t inner, void* stream);
