@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'lib', 'libbisinger_hip.so')
 if os.environ.get('BSG_LIB'):      # development: an alternative build of the same ABI (kernel experiments)
     LIB_PATH = os.environ['BSG_LIB']
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 class BsgError(RuntimeError):
@@ -83,6 +83,7 @@ _SIGS = {
     'bsg_mel_start': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     'bsg_mel_finish': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     'bsg_diffnet_last_path': (c_char_p, [c_void_p]),
+    'bsg_diffnet_last_launch': (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32)]),
     'bsg_diffnet_clock_read': (c_int32, [c_void_p, POINTER(c_double), POINTER(c_double)]),
     'bsg_diffnet_debug_stack_stamps': (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     'bsg_diffnet_status': (c_int32, [c_void_p, POINTER(c_int32)]),

@@ -1151,6 +1151,8 @@ struct bsg_diffnet {
   size_t part_cap = 0;                 // 32-frame tile equivalents the exchange buffers are sized for
   int num_cus = 0;
   const char* last_path = "none";      // form of the last residual-layer launch (bsg_diffnet_last_path)
+  int last_chains = 0;                 // launch chains of the last sampler call: 2 = the half-batch chains of dual_fork (bsg_diffnet_last_launch)
+  int last_groups = 0;                 // launch groups of the last stack launch (0: the last launch was no stack launch)
   // channel-split launch for small batches (residual_split_kernel)
   float* apack2w = nullptr;            // [L][2C*C] output projection packed for 16x16x4 MFMAs
   float* zbuf = nullptr;               // [tiles][C][32] z exchange scratch
@@ -1726,6 +1728,7 @@ static int launch_layer(bsg_diffnet* h, int layer, const float* x_in, const long
     else hipLaunchKernelGGL((residual_split_kernel<false, 2>), dim3(2 * B * a.tiles_per_row), dim3(512), slds, st, s);
     BSG_LAUNCH_CHECK();
     h->last_path = mode == 2 ? "wide" : mode == 4 ? "split4" : "split2";
+    h->last_groups = 0;
     return BSG_OK;
   }
   if (h->compute == BSG_COMPUTE_BF16) {
@@ -1737,6 +1740,7 @@ static int launch_layer(bsg_diffnet* h, int layer, const float* x_in, const long
     if (ext && !a.first) TRY(f32_to_quad_bf16(skip, h->skip_h, B, C, T, st));
     TRY(launch_residual_layer_bf16(a, st));
     h->last_path = "bf16";
+    h->last_groups = 0;
     if (ext) TRY(quad_bf16_to_f32(h->skip_h, skip, B, C, T, st));
     return BSG_OK;
   }
@@ -1763,6 +1767,7 @@ static int launch_layer(bsg_diffnet* h, int layer, const float* x_in, const long
   }
   BSG_LAUNCH_CHECK();
   h->last_path = "layer";
+  h->last_groups = 0;
   return BSG_OK;
 }
 
@@ -2043,6 +2048,7 @@ static int launch_stack(bsg_diffnet* h, const StackPlan& plan, const long long* 
     }
   }
   h->last_path = stack_path(plan, tail != nullptr);
+  h->last_groups = groups;
   return BSG_OK;
 }
 
@@ -2337,6 +2343,7 @@ static int dual_fork(bsg_diffnet* h, const StackPlan& plan, int B, int T, hipStr
 // joins the second stream back into `st` (also after an error, so that the caller's stream stays ordered after everything
 // that was enqueued on the second one) and restores the handle's launch state
 static int dual_join(bsg_diffnet* h, int n_sub, hipStream_t st, int rc) {
+  h->last_chains = n_sub == 2 ? 2 : 1;
   h->row_off = 0;
   h->no_split = false;
   h->split_small_lds = false;
@@ -2353,6 +2360,7 @@ extern "C" int bsg_ddpm_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
                                void* stream) {
   GuardScope guard_scope(h ? &h->guard : nullptr);
   TRY(check_bound(h, B, T, "ddpm_sample"));
+  h->last_chains = 1;   // this call's count from here on: the unfused loop and an early return never reach dual_join
   TRY(check_schedule(s, "ddpm_sample", false));
   BSG_REQUIRE(x, "ddpm_sample: null x");
   BSG_REQUIRE(t_start < s->num_timesteps && t_start < h->cfg.max_steps && n_steps >= 0 && t_start - n_steps + 1 >= 0,
@@ -2560,6 +2568,12 @@ extern "C" int bsg_diffnet_debug_stack_stamps(bsg_diffnet* h, int32_t t_uniform,
 }
 
 extern "C" const char* bsg_diffnet_last_path(bsg_diffnet* h) { return h ? h->last_path : "none"; }
+extern "C" int bsg_diffnet_last_launch(bsg_diffnet* h, int32_t* chains, int32_t* groups) {
+  BSG_REQUIRE(h && chains && groups, "diffnet_last_launch: null argument");
+  *chains = h->last_chains;
+  *groups = h->last_groups;
+  return BSG_OK;
+}
 
 extern "C" int bsg_diffnet_clock_read(bsg_diffnet* h, double* shader_mhz, double* span_us) {
   BSG_REQUIRE(h && shader_mhz && span_us, "diffnet_clock_read: null argument");
@@ -2643,6 +2657,7 @@ extern "C" int bsg_plms_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
                                int32_t T, void* stream) {
   GuardScope guard_scope(h ? &h->guard : nullptr);
   TRY(check_bound(h, B, T, "plms_sample"));
+  h->last_chains = 1;   // this call's count from here on: the unfused loop and an early return never reach dual_join
   TRY(check_schedule(s, "plms_sample", true));
   BSG_REQUIRE(x && interval > 0 && K_step > 0 && K_step <= s->num_timesteps && K_step <= h->cfg.max_steps,
               "plms_sample: K_step=%d interval=%d schedule=%d", K_step, interval, s->num_timesteps);

@@ -476,8 +476,18 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         _lib.check(_lib.load().bsg_diffnet_profile(self.handle(), int(enable)), 'bsg_diffnet_profile')
 
     def last_path(self):
-        """Form of the last residual-layer launch: 'stack', 'layer', 'split2', 'split4', 'wide', 'bf16' or 'none'."""
+        """Form of the last residual-layer launch.  Stack launches (all layers in one launch): 'stack_h2_quad', 'stack_h2_quad64',
+        'stack_h2_pair64' (a tile as 4 / 4 / 2 workgroups), 'stack_h2q' / 'stack_h2' (16- / 32-row split-fp16 launch), 'stack_f43',
+        'stack_bf16'; '_tail' behind a name: the sampler's step tail ran inside the launch; '_ragged': a ragged batch.  Per-layer
+        launches: 'layer', 'split2', 'split4', 'wide', 'bf16'.  'none' before the first launch."""
         return _lib.load().bsg_diffnet_last_path(self._h if self._h is not None else self.handle()).decode()      # (a query of the handle that exists: no look at the weights)
+
+    def last_launch(self):
+        """-> (launch chains of the last sampler call: 2 = the two half-batch chains, launch groups of the last stack launch or 0)."""
+        chains, groups = c_int32(), c_int32()
+        _lib.check(_lib.load().bsg_diffnet_last_launch(self._h if self._h is not None else self.handle(), byref(chains), byref(groups)),
+                   'bsg_diffnet_last_launch')
+        return chains.value, groups.value
 
     def handoff_timeouts(self):
         """Hand-off health: spins that gave up and were not yet taken (0 unless a workgroup was not resident). Synchronises."""

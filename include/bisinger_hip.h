@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define BSG_ABI_VERSION 13
+#define BSG_ABI_VERSION 14
 
 #define BSG_OK 0
 #define BSG_EINVAL (-22)  /* bad argument / shape the kernels do not support            */
@@ -214,10 +214,16 @@ int bsg_diffnet_set_parts(bsg_diffnet* h, int32_t enable);
 /* Test hook (ABI v6): sets the device-side launch epoch of the handle's stack / part launches (hand-off flag values are epoch x 64 + layer;
  * the epoch restarts at 1, with every flag array of the handle zeroed, once it reaches 2^25).  Waits for `stream`.  epoch >= 1. */
 int bsg_diffnet_debug_set_epoch(bsg_diffnet* h, uint32_t epoch, void* stream);
-/* Name of the form the last residual-layer launch on the handle took: "stack" (all L layers in one launch with the residual
- * stream on chip), "layer" (one launch per layer, one workgroup per tile), "split2" / "split4" (a tile as 2 / 4 workgroups),
- * "wide" (one 16-wave workgroup per tile), "bf16", or "none".  Static string. */
+/* Name of the form the last residual-layer launch on the handle took.  All L layers in one launch with the residual stream on chip:
+ * "stack_h2_quad" / "stack_h2_quad64" / "stack_h2_pair64" (a tile as 4 / 4 / 2 workgroups), "stack_h2q" / "stack_h2" (16- / 32-row
+ * split-fp16 launch), "stack_f43", "stack_bf16"; "_tail" behind a name: the sampler's step tail ran inside the launch; "_ragged": a
+ * ragged batch.  One launch per layer: "layer" (one workgroup per tile), "split2" / "split4" (a tile as 2 / 4 workgroups), "wide" (one
+ * 16-wave workgroup per tile), "bf16".  "none" before the first launch.  Static string. */
 const char* bsg_diffnet_last_path(bsg_diffnet* h);
+/* ABI v14: what last_path does not say.  chains: launch chains of the handle's last bsg_ddpm_sample / bsg_plms_sample (2: the two
+ * half-batch chains on two streams, 1: one chain or a call that returned before its loop ended, 0: no sampler call yet); groups: launch groups of whole rows of the last stack launch
+ * (0: the last residual-layer launch was no stack launch).  Host state only: no wait, no launch. */
+int bsg_diffnet_last_launch(bsg_diffnet* h, int32_t* chains, int32_t* groups);
 /* Shader clock the chip held over the last PROFILED stack launch (bsg_diffnet_profile on): tile 0 of the launch stores s_memtime (shader
  * clocks) and s_memrealtime (100 MHz) at its start and end; shader_mhz = their ratio, span_us = the launch's in-kernel span.  Synchronous
  * copy; 0 when no profiled stack launch has run (ABI v4). */

@@ -21,8 +21,8 @@ def sinusoidal_pos_emb(t, dim):
     half = dim // 2
     e = math.log(10000) / (half - 1)
     e = freq.inv_freq(torch.arange(half) * -e)         # float32, as in the reference
-    e = t[:, None] * e[None, :]                        # int64 * float32 -> float32
-    return torch.cat((e.sin(), e.cos()), dim=-1)
+    e = t.cpu()[:, None] * e[None, :]                  # int64 * float32 -> float32 (on the host, wherever t lives: the same bits)
+    return torch.cat((e.sin(), e.cos()), dim=-1).to(t.device)
 
 
 def step_embedding(sd, t, C, prefix='', dtype=torch.float32):
@@ -31,6 +31,20 @@ def step_embedding(sd, t, C, prefix='', dtype=torch.float32):
     e = sinusoidal_pos_emb(t, C).to(dtype)
     h = mish(F.linear(e, g('mlp.0.weight'), g('mlp.0.bias')))
     return F.linear(h, g('mlp.2.weight'), g('mlp.2.bias'))
+
+
+def _conv1d(x, w, b=None, padding=0, dilation=1, matmul=None):
+    """F.conv1d — what the reference runs — except on a GPU, where the convolution libraries have no float64 form: there it is ONE
+    matrix product over the stacked taps, the same sums, in float32 too (tests/test_gpu_plms_shapes.py holds the float64 result to
+    the CPU's to 1e-12)."""
+    if not (x.is_cuda if matmul is None else matmul):      # (matmul=True: the GPU's branch on the CPU, for tests/test_oracle_golden.py)
+        return F.conv1d(x, w, b, padding=padding, dilation=dilation)
+    K = w.shape[-1]
+    xp = F.pad(x, (padding, padding)) if padding else x
+    Lo = xp.shape[-1] - dilation * (K - 1)
+    xs = xp if K == 1 else torch.cat([xp[:, :, k * dilation:k * dilation + Lo] for k in range(K)], dim=1)      # [B, K Cin, Lo], tap-major
+    y = torch.matmul(w.permute(0, 2, 1).reshape(w.shape[0], -1), xs)
+    return y if b is None else y + b[None, :, None]
 
 
 def _bf16(x):
@@ -55,12 +69,12 @@ def residual_block(sd, p, x, cond, d, dilation, dtype=torch.float32, operand_bf1
         res, skip = torch.chunk(y, 2, dim=1)
         return (x + res) / math.sqrt(2.0), skip
     dp = F.linear(d, g('diffusion_projection.weight'), g('diffusion_projection.bias')).unsqueeze(-1)
-    c = F.conv1d(cond, g('conditioner_projection.weight'), g('conditioner_projection.bias'))
-    y = F.conv1d(x + dp, g('dilated_conv.weight'), g('dilated_conv.bias'),
-                 padding=dilation, dilation=dilation) + c
+    c = _conv1d(cond, g('conditioner_projection.weight'), g('conditioner_projection.bias'))
+    y = _conv1d(x + dp, g('dilated_conv.weight'), g('dilated_conv.bias'),
+                padding=dilation, dilation=dilation) + c
     gate, filt = torch.chunk(y, 2, dim=1)
     y = torch.sigmoid(gate) * torch.tanh(filt)
-    y = F.conv1d(y, g('output_projection.weight'), g('output_projection.bias'))
+    y = _conv1d(y, g('output_projection.weight'), g('output_projection.bias'))
     res, skip = torch.chunk(y, 2, dim=1)
     return (x + res) / math.sqrt(2.0), skip
 
@@ -83,7 +97,7 @@ def diffnet_forward(sd, spec, t, cond, prefix='', n_layers=20, cycle=4, dtype=to
     if in_bf16:
         x = F.relu(F.conv1d(_bf16(x), _bf16(g('input_projection.weight')), g('input_projection.bias')))
     else:
-        x = F.relu(F.conv1d(x, g('input_projection.weight'), g('input_projection.bias')))
+        x = F.relu(_conv1d(x, g('input_projection.weight'), g('input_projection.bias')))
     d = step_embedding(sd, t, x.shape[1], prefix, dtype)
     if operand_bf16:
         run = None
@@ -105,6 +119,6 @@ def diffnet_forward(sd, spec, t, cond, prefix='', n_layers=20, cycle=4, dtype=to
         x = F.relu(F.conv1d(_bf16(x), _bf16(g('skip_projection.weight')), g('skip_projection.bias')))
         x = F.conv1d(_bf16(x), _bf16(g('output_projection.weight')), g('output_projection.bias'))
     else:
-        x = F.relu(F.conv1d(x, g('skip_projection.weight'), g('skip_projection.bias')))
-        x = F.conv1d(x, g('output_projection.weight'), g('output_projection.bias'))
+        x = F.relu(_conv1d(x, g('skip_projection.weight'), g('skip_projection.bias')))
+        x = _conv1d(x, g('output_projection.weight'), g('output_projection.bias'))
     return x[:, None, :, :]

@@ -100,7 +100,7 @@ def plms_sample(sch, denoise, x_T, K_step, interval):
     ``max(t-interval, 0)`` (:189); all rows share the same t in the inference loop, so the
     well-defined batched meaning used here (and by the HIP path) is the element-wise clamp,
     which reduces to the reference for B=1."""
-    ac_all = sch['alphas_cumprod']
+    ac_all = sch['alphas_cumprod'].to(x_T.device)      # (x_T on a GPU: the float64 evaluation of a large shape, the same arithmetic)
 
     def get_x_pred(x, noise_t, t):
         dt = x.dtype
@@ -116,7 +116,7 @@ def plms_sample(sch, denoise, x_T, K_step, interval):
     B = x.shape[0]
     hist = deque(maxlen=4)
     for i in reversed(range(0, K_step, interval)):
-        t = torch.full((B,), i, dtype=torch.long)
+        t = torch.full((B,), i, dtype=torch.long, device=x.device)
         eps = denoise(x, t)
         if len(hist) == 0:
             x_pred = get_x_pred(x, eps, t)

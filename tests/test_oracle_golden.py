@@ -334,3 +334,79 @@ def test_r4_resblock2_and_plms_over_the_fft_denoiser(gold, sd_spec):
     xT = torch.from_numpy(rs.standard_normal((1, 1, 80, 40)).astype(np.float32))
     x0 = odf.plms_sample(odf.make_schedule(100, 'linear', 0.06), lambda x_, t_: ocd.fft_denoiser_forward(fsd, x_, t_, cond), xT, 100, 5)
     assert float((x0 - torch.from_numpy(g['plmsfft.x0'])).abs().max()) <= 5e-5
+
+
+def test_plms_schedule_edges(gold, gd_sd):
+    """tools/make_golden_plms_edges.py: the reference's own p_sample_plms loop over its WaveNet denoiser (formula weights, B = 1, T = 32,
+    100-step schedule) at the (K_step, interval) pairs that tests/test_gpu_plms_shapes.py runs on the GPU: one to four iterations (history
+    depth 0 .. 3), an interval that does not divide K_step, a K_step that is no multiple of it.  The bar of `plms5` is 2e-4 on the mel; the
+    measured figure is 0.0 at every pair (the oracle runs the reference's operations), and the fp32 trajectory's own deviation from
+    float64 is 3.5e-6 at 100 / 5, so the bar here is 4 x that: 1.5e-5 on values of up to 16.4.  The last iteration of every loop is at
+    i = 0 and leaves x as it is (a_prev = a_t), so (10, 5) pins the first iteration only and (20, 5) the blends of one and two entries.
+    (5, 5) and (3, 5) have no golden: their only iteration is at i = 0, where the reference's `max(t - interval, 0)` is the int 0 and its
+    denoiser raises.  a_prev = a_t there, so x_delta = 0 x (...): the oracle must return x_T bit for bit."""
+    from tests import plms_cases as pc
+    g = gold('plms_edges')
+    xT, cond = pc.golden_inputs()
+    den = lambda x_, t_: odn.diffnet_forward(gd_sd, x_, t_, cond, 'denoise_fn.')
+    sch = odf.make_schedule(100, 'linear', 0.06)
+    seen = set()
+    for K_step, interval in pc.EDGES + [pc.MAIN[1:]]:
+        x0 = odf.plms_sample(sch, den, xT, K_step, interval)
+        key = f'x0.{K_step}_{interval}'
+        if K_step <= interval:
+            assert key not in g.files and torch.equal(x0, xT), key
+            continue
+        seen.add(key)
+        dev = float(np.abs(x0.numpy() - g[key]).max())
+        print(f'plms edges {K_step} / {interval}: oracle vs reference {dev:.3e}')
+        assert dev <= 1.5e-5, (key, dev)
+        assert float(np.abs(g[key] - xT.numpy()).max()) > 1e-2, key      # the loop moved x: the golden is no copy of x_T
+    assert seen == set(g.files)
+    assert np.array_equal(g['x0.98_5'], g['x0.100_5'])                  # the same iterations: i = 95 .. 0
+    assert not np.array_equal(g['x0.100_7'], g['x0.100_5'])
+
+
+def test_plms_yardsticks_are_recorded(gd_sd):
+    """tests/golden/plms_yardsticks.json (tools/plms_yardsticks.py) holds the fp32 oracle trajectory's deviation from the float64 one for
+    every case that tests/plms_cases.cpu_cases() names, so that every bar of tests/test_gpu_plms_shapes.py exists before a kernel runs; one
+    cheap case is computed again here and must agree with the record to a factor of 4 (the figure is rounding noise: another host's
+    convolutions sum in another order), which ties the file to this oracle, these weights and these inputs."""
+    from tests import plms_cases as pc
+    yard = pc.load_yardsticks()
+    for setting, B, Tn, ragged in pc.cpu_cases():
+        name = pc.case_name(B, Tn, pc.ragged_lengths() if ragged else None)
+        assert name in yard[pc.setting_name(setting)], (setting, name)
+    for setting in [pc.MAIN, pc.SHIPPED] + pc.EDGE_SETTINGS:
+        single = setting[1] <= setting[2]          # one iteration at i = 0: x stays x_T in every arithmetic, so the bar is 0
+        assert (pc.bar(setting, yard) == 0.0) == single, setting
+    setting, (B, Tn) = (100, 10, 5), (3, 77)
+    x, cond = pc.inputs(B, Tn)
+    want = pc.trajectory(gd_sd, x, cond, setting, torch.float64)
+    dev = pc.deviations(pc.trajectory(gd_sd, x, cond, setting, torch.float32), want)
+    rec = yard[pc.setting_name(setting)][pc.case_name(B, Tn)]
+    print(f'yardstick {setting} {B}x{Tn}: {dev[0]:.3e} now, {rec[0]:.3e} recorded')
+    assert rec[0] / 4 <= dev[0] <= rec[0] * 4
+    assert abs(float(np.abs(want).max()) - rec[3]) <= 1e-3 * rec[3]
+
+
+def test_oracle_conv_as_matmul_equals_conv1d():
+    """oracle.diffnet._conv1d evaluates a convolution on a GPU as one matrix product over the stacked taps (the convolution libraries have
+    no float64 form there); the same branch, forced on the CPU, against F.conv1d: K = 1 and 3, dilation 1 .. 8 with `same` padding, rows
+    shorter and longer than the halo, with and without bias.  float64 to 1e-12 (sums of 768 products of N(0, 1) values), float32 to 2e-4."""
+    import torch.nn.functional as F
+    rs = np.random.RandomState(5)
+    for K, dils in ((1, (1,)), (3, (1, 2, 4, 8))):
+        for d in dils:
+            for Tn in (1, 2, 5, 8, 9, 17, 40):
+                for B in (1, 3):
+                    x = T(rs.standard_normal((B, 256, Tn)))
+                    w = T(rs.standard_normal((96, 256, K)))
+                    b = T(rs.standard_normal(96)) if (Tn + d) % 2 else None
+                    pad = d * (K // 2)
+                    for dt, tol in ((torch.float64, 1e-12), (torch.float32, 2e-4)):
+                        xx, ww, bb = x.to(dt), w.to(dt), None if b is None else b.to(dt)
+                        got = odn._conv1d(xx, ww, bb, padding=pad, dilation=d, matmul=True)
+                        want = F.conv1d(xx, ww, bb, padding=pad, dilation=d)
+                        assert got.shape == want.shape == (B, 96, Tn)
+                        assert float((got - want).abs().max()) <= tol, (K, d, Tn, B, dt)
