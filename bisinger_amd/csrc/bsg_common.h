@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include "../../include/bisinger_hip.h"
 
@@ -37,6 +38,12 @@ using f32x16 = __attribute__((ext_vector_type(16))) float;
 __device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// an integer switch of the environment, or `dflt` while it is unset (host side; callers read it once and keep the value)
+static inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
 
 // Activation codes shared by the GEMM epilogue.
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_MISH = 3 };

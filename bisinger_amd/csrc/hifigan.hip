@@ -19,6 +19,7 @@
 #include <stdio.h>
 
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "bsg_common.h"
@@ -31,11 +32,24 @@ using f32x2 = __attribute__((ext_vector_type(2))) float;
 // inputs (B = 1), where 1024-sample tiles leave most CUs without a workgroup
 constexpr int CI_CHUNK = 8;
 
-// the tile variant of the last launch, written by the launcher that chose it; hifigan_run() copies it into the handle's launch record
-// (bsg_hifigan_last_path).  Host side only.
-thread_local const char* hg_variant = "";
-template <int N>
-constexpr const char* tt_name() { return N == 8 ? "TT8" : N == 4 ? "TT4" : N == 2 ? "TT2" : "TT1"; }
+// The run-time switches of this file (environment), read on first use and never again.  Host side only.
+struct HgSwitches {
+  int h2w = env_int("BSG_HG_H2W", 1);         // 0: conv_pre and the u = 8 transposed convolutions on the vector pipe (conv1d_kernel / upsample_kernel)
+  int split = env_int("BSG_HG_SPLIT", 1);     // 0: the fp32-MFMA / vector forms of the ResBlock pairs even while the GEMMs run split-fp16, and conv_pre and the u = 8
+                                              // stages off the 16-bit pipe as well: the switch means the WHOLE vocoder on fp32 products
+  int up = env_int("BSG_HG_UP", 1);           // 0: no upsample2_kernel / upsample_kernel (the polyphase conv1d form or the gather kernel)
+  int chain = env_int("BSG_HG_CHAIN", 1);     // 0: the 8- / 16-channel ResBlock1 pair by pair instead of one resblock_chain_h16_kernel launch
+  int mfma = env_int("BSG_HG_MFMA", 1);       // 0: every ResBlock pair on the vector pipe
+  int h16 = env_int("BSG_HG_H16", 1);         // 0: the VALU pairs for 8 / 16 channels
+  int fused = env_int("BSG_HG_FUSED", 1);     // 0: every pair as two conv1d_kernel launches; 2: the fused pair at every length
+  int acc = env_int("BSG_HG_ACC", 16);        // accumulators per thread (C TT) of resblock_pair_kernel: 16 measured best (13.6 vs 16.9 ms per forward at 64: occupancy)
+  int h16_c8 = env_int("BSG_HG_H16_C8", 11);  // 8-channel pairs on the 16-row matrix form: 11 = only K = 11, 0 = never, 1 = every K (pair_h16_supported)
+  int chain_nc = env_int("BSG_HG_CHAIN_NC", 0);            // 4 / 8: force the chain's tile width
+  bool no_up2 = getenv("BSG_NO_UP2") != nullptr;           // set: no upsample2_kernel
+  bool no_polyphase = getenv("BSG_NO_POLYPHASE") != nullptr;   // set: the gather kernel instead of the polyphase conv1d form
+  bool no_conv_post = getenv("BSG_NO_CONV_POST") != nullptr;   // set: conv_post on conv1d_kernel instead of conv_post_kernel
+};
+const HgSwitches& hg_switches() { static const HgSwitches s; return s; }
 
 struct ConvArgs {
   const float* x;      // [B][Cin][L]
@@ -717,7 +731,6 @@ template <int K, int TT>
 int launch_conv_kt(const ConvArgs& a, int B, hipStream_t st) {
   constexpr int TILE = 256 * TT;
   const size_t lds = (size_t)CI_CHUNK * (TILE + (K - 1) * a.dil) * sizeof(float);
-  hg_variant = tt_name<TT>();
   if (a.Cout >= 16) {
     dim3 grid(cdiv(a.L, TILE), cdiv(a.Cout, 16), B);
     hipLaunchKernelGGL((conv1d_kernel<K, 16, TT>), grid, dim3(256), lds, st, a);
@@ -730,11 +743,9 @@ int launch_conv_kt(const ConvArgs& a, int B, hipStream_t st) {
 }
 
 template <int K>
-int launch_conv_k(const ConvArgs& a, int B, hipStream_t st) {
-  // workgroups at 1024 samples per workgroup; below ~2 per CU (256 CUs) use shorter tiles
-  const long long wgs4 = (long long)cdiv(a.L, 1024) * cdiv(a.Cout, a.Cout >= 16 ? 16 : 8) * B;
-  if (wgs4 >= 512) return launch_conv_kt<K, 4>(a, B, st);
-  if (wgs4 >= 256) return launch_conv_kt<K, 2>(a, B, st);
+int launch_conv_k(const ConvArgs& a, int tt, int B, hipStream_t st) {
+  if (tt == 4) return launch_conv_kt<K, 4>(a, B, st);
+  if (tt == 2) return launch_conv_kt<K, 2>(a, B, st);
   return launch_conv_kt<K, 1>(a, B, st);
 }
 
@@ -743,17 +754,33 @@ template <int TT>
 int launch_convT_t(const ConvArgs& a, int B, hipStream_t st) {
   constexpr int TILE = 256 * TT;
   const size_t lds = (size_t)CI_CHUNK * (TILE + 1) * sizeof(float);
-  hg_variant = tt_name<TT>();
   if (a.Cout >= 16) hipLaunchKernelGGL((conv1d_kernel<2, 16, TT>), dim3(cdiv(a.Lq, TILE), cdiv(a.Cout, 16), B * a.n_phase), dim3(256), lds, st, a);
   else hipLaunchKernelGGL((conv1d_kernel<2, 8, TT>), dim3(cdiv(a.Lq, TILE), cdiv(a.Cout, 8), B * a.n_phase), dim3(256), lds, st, a);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
 }
-int launch_convT(const ConvArgs& a, int B, hipStream_t st) {
-  const long long wgs4 = (long long)cdiv(a.Lq, 1024) * cdiv(a.Cout, a.Cout >= 16 ? 16 : 8) * B * a.n_phase;
-  if (wgs4 >= 512) return launch_convT_t<4>(a, B, st);
-  if (wgs4 >= 256) return launch_convT_t<2>(a, B, st);
+int launch_convT(const ConvArgs& a, int tt, int B, hipStream_t st) {
+  if (tt == 4) return launch_convT_t<4>(a, B, st);
+  if (tt == 2) return launch_convT_t<2>(a, B, st);
   return launch_convT_t<1>(a, B, st);
+}
+
+// Run-time (K, C) -> f(<K>, <C>) for K in {3, 7, 11} and C in Cs, as std::integral_constant arguments of a generic lambda; HG_NO_KERNEL if (K, C) is not in that set.
+constexpr int HG_NO_KERNEL = 1;
+template <int K, int... Cs, class F>
+int dispatch_c(int C, F& f) {
+  int rc = HG_NO_KERNEL;
+  (void)((C == Cs && ((rc = f(std::integral_constant<int, K>{}, std::integral_constant<int, Cs>{})), true)) || ...);
+  return rc;
+}
+template <int... Cs, class F>
+int dispatch_kc(int K, int C, F f) {
+  switch (K) {
+    case 3: return dispatch_c<3, Cs...>(C, f);
+    case 7: return dispatch_c<7, Cs...>(C, f);
+    case 11: return dispatch_c<11, Cs...>(C, f);
+    default: return HG_NO_KERNEL;
+  }
 }
 
 template <int K, int C, int TT>
@@ -765,31 +792,17 @@ int launch_pair_t(const PairArgs& a, int B, hipStream_t st) {
     BSG_HIP(hipFuncSetAttribute((const void*)resblock_pair_kernel<K, C, TT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = true;
   }
-  hg_variant = tt_name<TT>();
   hipLaunchKernelGGL((resblock_pair_kernel<K, C, TT>), dim3(cdiv(a.L, POUT), B), dim3(256), lds, st, a);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
 }
-// positions per thread: as many as the 64-accumulator budget allows (C TT <= 64), fewer while the launch would leave CUs idle
+// tt positions per thread (pair_valu_tt): only the widths within the 64-accumulator budget (C TT <= 64) are built
 template <int K, int C>
-int launch_pair_kc(const PairArgs& a, int B, hipStream_t st) {
-  auto wgs = [&](int tt) { return (long long)cdiv(a.L, 256 * tt - (K - 1)) * B; };
-  static int cap = -1;
-  if (cap < 0) { const char* e = getenv("BSG_HG_ACC"); cap = e ? atoi(e) : 16; }   // accumulators per thread (C TT): 16 measured best (13.6 vs 16.9 ms per forward at 64: occupancy)
-  if constexpr (C * 8 <= 64) { if (C * 8 <= cap && wgs(8) >= 512) return launch_pair_t<K, C, 8>(a, B, st); }
-  if constexpr (C * 4 <= 64) { if (C * 4 <= cap && wgs(4) >= 512) return launch_pair_t<K, C, 4>(a, B, st); }
-  if constexpr (C * 2 <= 64) { if (C * 2 <= cap && wgs(2) >= 512) return launch_pair_t<K, C, 2>(a, B, st); }
+int launch_pair_kc(const PairArgs& a, int tt, int B, hipStream_t st) {
+  if constexpr (C * 8 <= 64) { if (tt == 8) return launch_pair_t<K, C, 8>(a, B, st); }
+  if constexpr (C * 4 <= 64) { if (tt == 4) return launch_pair_t<K, C, 4>(a, B, st); }
+  if constexpr (C * 2 <= 64) { if (tt == 2) return launch_pair_t<K, C, 2>(a, B, st); }
   return launch_pair_t<K, C, 1>(a, B, st);
-}
-template <int K>
-int launch_pair_k(const PairArgs& a, int C, int B, hipStream_t st) {
-  switch (C) {
-    case 8: return launch_pair_kc<K, 8>(a, B, st);
-    case 16: return launch_pair_kc<K, 16>(a, B, st);
-    case 32: return launch_pair_kc<K, 32>(a, B, st);
-    case 64: return launch_pair_kc<K, 64>(a, B, st);
-    default: return BSG_EINVAL;
-  }
 }
 // ------------------------------------------------------------------------------------------------
 // The same fused pair with every product on the 16-bit matrix pipe (split-fp16: gemm.hip / diffnet_h2.hip have the argument).  Weights
@@ -1047,26 +1060,15 @@ int launch_pair_h2_t(const PairArgs& a, int B, hipStream_t st) {
     BSG_HIP(hipFuncSetAttribute((const void*)resblock_pair_h2_kernel<K, C, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = lds;
   }
-  hg_variant = NB == 2 ? "NB2" : "NB1";
   hipLaunchKernelGGL((resblock_pair_h2_kernel<K, C, NB>), dim3(cdiv(a.L, POUT), B), dim3(256), lds, st, a);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
 }
-template <int K, int C>
-int launch_pair_h2_kc(const PairArgs& a, int B, hipStream_t st) {
-  if ((long long)cdiv(a.L, 256 - (K - 1)) * B >= 256) return launch_pair_h2_t<K, C, 2>(a, B, st);
-  return launch_pair_h2_t<K, C, 1>(a, B, st);
-}
-int launch_pair_h2(const PairArgs& a, int K, int C, int B, hipStream_t st) {
-  if (C == 32) {
-    if (K == 3) return launch_pair_h2_kc<3, 32>(a, B, st);
-    if (K == 7) return launch_pair_h2_kc<7, 32>(a, B, st);
-    if (K == 11) return launch_pair_h2_kc<11, 32>(a, B, st);
-  } else if (C == 64) {
-    if (K == 3) return launch_pair_h2_kc<3, 64>(a, B, st);
-    if (K == 7) return launch_pair_h2_kc<7, 64>(a, B, st);
-    if (K == 11) return launch_pair_h2_kc<11, 64>(a, B, st);
-  }
+int launch_pair_h2(const PairArgs& a, int K, int C, int nb, int B, hipStream_t st) {
+  const int rc = dispatch_kc<32, 64>(K, C, [&](auto k, auto c) {
+    return nb == 2 ? launch_pair_h2_t<k.value, c.value, 2>(a, B, st) : launch_pair_h2_t<k.value, c.value, 1>(a, B, st);
+  });
+  if (rc != HG_NO_KERNEL) return rc;
   set_error("hifigan: no split-fp16 pair kernel for K=%d C=%d", K, C);
   return BSG_EINVAL;
 }
@@ -1360,27 +1362,15 @@ int launch_pair_h16_t(const PairArgs& a, int B, hipStream_t st) {
     BSG_HIP(hipFuncSetAttribute((const void*)resblock_pair_h16_kernel<K, C, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = lds;
   }
-  hg_variant = NB == 2 ? "NB2" : "NB1";
   hipLaunchKernelGGL((resblock_pair_h16_kernel<K, C, NB>), dim3(cdiv(a.L, POUT), B), dim3(256), lds, st, a);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
 }
-template <int K, int C>
-int launch_pair_h16_kc(const PairArgs& a, int B, hipStream_t st) {
-  if ((long long)cdiv(a.L, 256 - (K - 1)) * B >= 256) return launch_pair_h16_t<K, C, 2>(a, B, st);
-  return launch_pair_h16_t<K, C, 1>(a, B, st);
-}
-int launch_pair_h16(const PairArgs& a, int K, int C, int B, hipStream_t st) {
-  if (C == 16) {
-    if (K == 3) return launch_pair_h16_kc<3, 16>(a, B, st);
-    if (K == 7) return launch_pair_h16_kc<7, 16>(a, B, st);
-    if (K == 11) return launch_pair_h16_kc<11, 16>(a, B, st);
-  }
-  if (C == 8) {
-    if (K == 3) return launch_pair_h16_kc<3, 8>(a, B, st);
-    if (K == 7) return launch_pair_h16_kc<7, 8>(a, B, st);
-    if (K == 11) return launch_pair_h16_kc<11, 8>(a, B, st);
-  }
+int launch_pair_h16(const PairArgs& a, int K, int C, int nb, int B, hipStream_t st) {
+  const int rc = dispatch_kc<16, 8>(K, C, [&](auto k, auto c) {
+    return nb == 2 ? launch_pair_h16_t<k.value, c.value, 2>(a, B, st) : launch_pair_h16_t<k.value, c.value, 1>(a, B, st);
+  });
+  if (rc != HG_NO_KERNEL) return rc;
   set_error("hifigan: no 16-row split-fp16 pair kernel for K=%d, C=%d", K, C);
   return BSG_EINVAL;
 }
@@ -1389,9 +1379,9 @@ int launch_pair_h16(const PairArgs& a, int K, int C, int B, hipStream_t st) {
 // staging and residual prefetch: 176 / 160 / 120 us — ahead for K = 11 only, which is what the default takes.)
 // BSG_HG_H16_C8: 8-channel pairs on the 16-row matrix form — default 11 = only K = 11 (176 against 195 us; K = 7 / 3 are faster on the vector
 // pipe: 146 / 93 against 160 / 120 us), 0 = never, 1 = every K
-static int h16_c8() { static int v = -1; if (v < 0) { const char* e = getenv("BSG_HG_H16_C8"); v = e ? atoi(e) : 11; } return v; }
 bool pair_h16_supported(int K, int C) {
-  return (K == 3 || K == 7 || K == 11) && (C == 16 || (C == 8 && (h16_c8() == 1 || (h16_c8() == 11 && K == 11))));
+  const int c8 = hg_switches().h16_c8;
+  return (K == 3 || K == 7 || K == 11) && (C == 16 || (C == 8 && (c8 == 1 || (c8 == 11 && K == 11))));
 }
 
 
@@ -1548,39 +1538,21 @@ int launch_chain_h16_t(const ChainArgs& a, int B, hipStream_t st) {
     BSG_HIP(hipFuncSetAttribute((const void*)resblock_chain_h16_kernel<K, C, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = lds;
   }
-  hg_variant = NC == 8 ? "NC8" : "NC4";
   hipLaunchKernelGGL((resblock_chain_h16_kernel<K, C, NC>), dim3(cdiv(a.L, pout), B), dim3(256), lds, st, a);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
 }
-// the tile width by the number of tiles: 512 positions while that leaves >= 2 workgroups per CU, else 256 (more, smaller workgroups)
 bool chain_h16_supported(int K, int C, int n_pairs, const int* dil) {
   if (!((K == 3 || K == 7 || K == 11) && (C == 16 || C == 8)) || n_pairs < 1 || n_pairs > 3) return false;
   int ht = 0, dmax = 1;
   for (int m = 0; m < n_pairs; ++m) { ht += (K - 1) / 2 * (dil[m] + 1); dmax = dil[m] > dmax ? dil[m] : dmax; }
   return 2 * ht <= 128 && (size_t)2 * (512 + (K - 1) * dmax) * 2 * C <= 80 * 1024;   // >= half of a 256-position tile is output; two workgroups per CU
 }
-template <int K, int C>
-int launch_chain_h16_kc(const ChainArgs& a, int B, hipStream_t st) {
-  int ht = 0;
-  for (int m = 0; m < a.n_pairs; ++m) ht += (K - 1) / 2 * (a.dil[m] + 1);
-  static int nc_env = -1;   // BSG_HG_CHAIN_NC = 4 / 8: force the tile width
-  if (nc_env < 0) { const char* e = getenv("BSG_HG_CHAIN_NC"); nc_env = e ? atoi(e) : 0; }
-  const bool wide = nc_env ? nc_env == 8 : (long long)cdiv(a.L, 512 - 2 * ht) * B >= 512;
-  if (wide) return launch_chain_h16_t<K, C, 8>(a, B, st);
-  return launch_chain_h16_t<K, C, 4>(a, B, st);
-}
-int launch_chain_h16(const ChainArgs& a, int K, int C, int B, hipStream_t st) {
-  if (C == 16) {
-    if (K == 3) return launch_chain_h16_kc<3, 16>(a, B, st);
-    if (K == 7) return launch_chain_h16_kc<7, 16>(a, B, st);
-    if (K == 11) return launch_chain_h16_kc<11, 16>(a, B, st);
-  }
-  if (C == 8) {
-    if (K == 3) return launch_chain_h16_kc<3, 8>(a, B, st);
-    if (K == 7) return launch_chain_h16_kc<7, 8>(a, B, st);
-    if (K == 11) return launch_chain_h16_kc<11, 8>(a, B, st);
-  }
+int launch_chain_h16(const ChainArgs& a, int K, int C, int nc, int B, hipStream_t st) {
+  const int rc = dispatch_kc<16, 8>(K, C, [&](auto k, auto c) {
+    return nc == 8 ? launch_chain_h16_t<k.value, c.value, 8>(a, B, st) : launch_chain_h16_t<k.value, c.value, 4>(a, B, st);
+  });
+  if (rc != HG_NO_KERNEL) return rc;
   set_error("hifigan: no ResBlock chain kernel for K=%d, C=%d", K, C);
   return BSG_EINVAL;
 }
@@ -1596,46 +1568,29 @@ int launch_pair_mfma_t(const PairArgs& a, int B, hipStream_t st) {
     BSG_HIP(hipFuncSetAttribute((const void*)resblock_pair_mfma_kernel<K, C, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = lds;
   }
-  hg_variant = NB == 2 ? "NB2" : "NB1";
   hipLaunchKernelGGL((resblock_pair_mfma_kernel<K, C, NB>), dim3(cdiv(a.L, POUT), B), dim3(256), lds, st, a);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
 }
-template <int K, int C>
-int launch_pair_mfma_kc(const PairArgs& a, int B, hipStream_t st) {
-  // 256 positions per workgroup unless that leaves CUs without one (single utterances): then 128
-  if ((long long)cdiv(a.L, 256 - (K - 1)) * B >= 256) return launch_pair_mfma_t<K, C, 2>(a, B, st);
-  return launch_pair_mfma_t<K, C, 1>(a, B, st);
-}
-int launch_pair_mfma(const PairArgs& a, int K, int C, int B, hipStream_t st) {
-  if (C == 32) {
-    if (K == 3) return launch_pair_mfma_kc<3, 32>(a, B, st);
-    if (K == 7) return launch_pair_mfma_kc<7, 32>(a, B, st);
-    if (K == 11) return launch_pair_mfma_kc<11, 32>(a, B, st);
-  } else if (C == 64) {
-    if (K == 3) return launch_pair_mfma_kc<3, 64>(a, B, st);
-    if (K == 7) return launch_pair_mfma_kc<7, 64>(a, B, st);
-    if (K == 11) return launch_pair_mfma_kc<11, 64>(a, B, st);
-  }
-  return BSG_EINVAL;
+int launch_pair_mfma(const PairArgs& a, int K, int C, int nb, int B, hipStream_t st) {
+  const int rc = dispatch_kc<32, 64>(K, C, [&](auto k, auto c) {
+    return nb == 2 ? launch_pair_mfma_t<k.value, c.value, 2>(a, B, st) : launch_pair_mfma_t<k.value, c.value, 1>(a, B, st);
+  });
+  return rc != HG_NO_KERNEL ? rc : BSG_EINVAL;
 }
 bool pair_mfma_supported(int K, int C) { return (K == 3 || K == 7 || K == 11) && (C == 32 || C == 64); }
 bool pair_supported(int K, int C) { return (K == 3 || K == 7 || K == 11) && (C == 8 || C == 16 || C == 32 || C == 64); }
-int launch_pair(const PairArgs& a, int K, int C, int B, hipStream_t st) {
-  switch (K) {
-    case 3: return launch_pair_k<3>(a, C, B, st);
-    case 7: return launch_pair_k<7>(a, C, B, st);
-    case 11: return launch_pair_k<11>(a, C, B, st);
-    default: return BSG_EINVAL;
-  }
+int launch_pair(const PairArgs& a, int K, int C, int tt, int B, hipStream_t st) {
+  const int rc = dispatch_kc<8, 16, 32, 64>(K, C, [&](auto k, auto c) { return launch_pair_kc<k.value, c.value>(a, tt, B, st); });
+  return rc != HG_NO_KERNEL ? rc : BSG_EINVAL;
 }
 
-int launch_conv(const ConvArgs& a, int K, int B, hipStream_t st) {
+int launch_conv(const ConvArgs& a, int K, int tt, int B, hipStream_t st) {
   switch (K) {
-    case 3: return launch_conv_k<3>(a, B, st);
-    case 5: return launch_conv_k<5>(a, B, st);      // ResBlock2 configurations (HiFi-GAN V3: kernels 3, 5, 7)
-    case 7: return launch_conv_k<7>(a, B, st);
-    case 11: return launch_conv_k<11>(a, B, st);
+    case 3: return launch_conv_k<3>(a, tt, B, st);
+    case 5: return launch_conv_k<5>(a, tt, B, st);      // ResBlock2 configurations (HiFi-GAN V3: kernels 3, 5, 7)
+    case 7: return launch_conv_k<7>(a, tt, B, st);
+    case 11: return launch_conv_k<11>(a, tt, B, st);
     default: set_error("hifigan: conv kernel size %d not built (3, 5, 7, 11)", K); return BSG_EINVAL;
   }
 }
@@ -1674,6 +1629,19 @@ struct ConvW {
   int h2w_kp = 0;         // input channels padded to a multiple of 64 in the activation planes
 };
 
+// The forward as a plan: one HgStep per launch, in launch order (plan_hifigan).  hifigan_run() launches the steps one by one and appends each
+// to the launch record once it has been launched, so the token and the launch come from the same plan entry.
+enum HgSite : uint8_t { HG_PRE, HG_UP, HG_SRC, HG_RB, HG_POST };
+// one value per form token of bsg_hifigan_last_path, in the order of HG_FORM_NAME
+enum HgForm : uint8_t { HG_H2W, HG_CONV, HG_UP2, HG_UPK, HG_POLY, HG_CONVT, HG_ADD, HG_CHAIN, HG_PAIR_H16, HG_PAIR_H2, HG_PAIR_MFMA, HG_PAIR_VALU, HG_CONV1, HG_CONV2, HG_POST4 };
+static const char* const HG_FORM_NAME[] = {"h2w", "conv", "up2", "upk", "poly", "convT", "add", "chain", "pair_h16", "pair_h2", "pair_mfma", "pair_valu", "conv1", "conv2", "post4"};
+struct HgStep {
+  HgSite site;
+  HgForm form;
+  int8_t var;       // tile variant, decided by the plan: TT (conv, poly, pair_valu, conv1, conv2), NB (pair_h16 / _h2 / _mfma), NC (chain); 0: the form has none
+  int8_t i, j, m;   // stage, ResBlock of the stage, dilation (-1: the whole ResBlock)
+};
+
 struct bsg_hifigan {
   bsg_hifigan_cfg cfg;
   Guard guard;   // this handle's range-event word and split-fp16 switch
@@ -1696,17 +1664,24 @@ struct bsg_hifigan {
   unsigned short* planes = nullptr;       // activation planes of the gemm_h2w products (hi, then lo)
   size_t planes_cap = 0;                  // halfs
   std::string path;                       // the launches of the last forward (bsg_hifigan_last_path)
+  std::vector<HgStep> steps;              // room for the plan of a forward (plan_hifigan), sized at create
 };
 
-// One token "<site>:<form>[/<tile variant>]" per launch, appended at the branch that launched (never derived from the thresholds again).
-__attribute__((format(printf, 2, 3))) static void path_add(bsg_hifigan* h, const char* fmt, ...) {
-  char tok[64];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(tok, sizeof tok, fmt, ap);
-  va_end(ap);
+// One token "<site>:<form>[/<tile variant>]" per launch, spelled from the plan entry that has just been launched (the thresholds are
+// evaluated once, in plan_hifigan).
+static void path_token(bsg_hifigan* h, const char* tok) {
   if (!h->path.empty()) h->path += ' ';
   h->path += tok;
+}
+static void path_add(bsg_hifigan* h, const HgStep& s) {
+  static const char* const SITE[] = {"pre", "up%d", "src%d", "rb%d.%d", "post"};   // by HgSite
+  char site[24], tok[64];
+  if (s.site == HG_RB && s.m >= 0) snprintf(site, sizeof site, "rb%d.%d.%d", s.i, s.j, s.m);
+  else snprintf(site, sizeof site, SITE[s.site], s.i, s.j);
+  const char* kind = s.form == HG_CHAIN ? "NC" : s.form == HG_PAIR_H16 || s.form == HG_PAIR_H2 || s.form == HG_PAIR_MFMA ? "NB" : "TT";
+  if (s.var) snprintf(tok, sizeof tok, "%s:%s/%s%d", site, HG_FORM_NAME[s.form], kind, s.var);
+  else snprintf(tok, sizeof tok, "%s:%s", site, HG_FORM_NAME[s.form]);
+  path_token(h, tok);
 }
 
 extern "C" void bsg_hifigan_destroy(bsg_hifigan* h) {
@@ -1951,6 +1926,7 @@ extern "C" int bsg_hifigan_create(bsg_hifigan** out, const bsg_hifigan_cfg* cfg,
         if ((rc = pack_conv(h, c, st, cfg->resblock != 2)) != BSG_OK) return fail(rc);   // (the fused pair forms are ResBlock1's)
       }
   }
+  h->steps.resize(2 + 2 * (size_t)cfg->n_ups * (1 + (size_t)cfg->n_kernels * cfg->n_dil));   // pre, post; per stage up, src and two launches per pair
   h->post.cout = 1; h->post.cin = C0 >> cfg->n_ups; h->post.k = 7;
   if ((rc = take_conv(h, h->post, w, 1, h->post.cin * 7, st)) != BSG_OK) return fail(rc);
   if ((rc = pack_conv(h, h->post, st)) != BSG_OK) return fail(rc);
@@ -1966,12 +1942,117 @@ extern "C" int bsg_hifigan_create(bsg_hifigan** out, const bsg_hifigan_cfg* cfg,
   return BSG_OK;
 }
 
-static int run_conv(const ConvW& c, const float* x, float* y, int B, int L, int dil, float in_slope, const float* res,
+// Which launch runs at each site: plan_hifigan().  It reads the handle, the switches and the shape, writes nothing on the handle, launches and
+// allocates nothing.  Every threshold is a workgroup count of the shape (never the box's CU count): a shape has the same plan on every box.
+// conv1d_kernel: samples per lane by the workgroups at 1024 samples per workgroup; below ~2 per CU (256 CUs) shorter tiles
+static int conv_tt(int L, int Cout, long long rows) {
+  const long long wgs4 = (long long)cdiv(L, 1024) * cdiv(Cout, Cout >= 16 ? 16 : 8) * rows;
+  return wgs4 >= 512 ? 4 : wgs4 >= 256 ? 2 : 1;
+}
+// resblock_pair_kernel: positions per thread, as many as the accumulator budget allows (C TT <= 64 and <= BSG_HG_ACC), fewer while the launch would leave CUs idle
+static int pair_valu_tt(int K, int C, int L, int B) {
+  for (int tt = 8; tt > 1; tt >>= 1)
+    if (C * tt <= 64 && C * tt <= hg_switches().acc && (long long)cdiv(L, 256 * tt - (K - 1)) * B >= 512) return tt;
+  return 1;
+}
+// resblock_chain_h16_kernel: the tile width by the number of tiles: 512 positions (NC8) while that leaves >= 2 workgroups per CU, else 256 (NC4: more, smaller workgroups)
+static int chain_nc(int K, int n_pairs, const int* dil, int L, int B) {
+  int ht = 0;
+  for (int m = 0; m < n_pairs; ++m) ht += (K - 1) / 2 * (dil[m] + 1);
+  const int forced = hg_switches().chain_nc;
+  return (forced ? forced == 8 : (long long)cdiv(L, 512 - 2 * ht) * B >= 512) ? 8 : 4;
+}
+
+static int plan_hifigan(const bsg_hifigan* h, int B, int T, bool nsf, HgStep* out) {
+  const bsg_hifigan_cfg& c = h->cfg;
+  const HgSwitches& sw = hg_switches();
+  int n = 0;
+  auto add = [&](HgSite site, HgForm form, int var = 0, int i = 0, int j = 0, int m = -1) { out[n++] = HgStep{site, form, (int8_t)var, (int8_t)i, (int8_t)j, (int8_t)m}; };
+  // split-fp16 products allowed on this handle in this call: not switched off (BSG_HG_SPLIT), every packed weight inside the fp16 range
+  // (h2_ok), and the range guard has not demoted the call
+  const bool split_ok = sw.split && h->h2_ok && gemm_split_enabled();
+  const bool h2w_ok = sw.h2w && split_ok;               // ... for conv_pre and the u = 8 stages (gemm_h2w)
+  const bool h16_ok = sw.mfma && sw.h16 && split_ok;    // ... for 8 / 16 channels (pair_h16, chain)
+
+  // conv_pre: a 7-tap product on the pre-split GEMM, else conv1d_kernel
+  if (h2w_ok && h->pre.h2w.ok && h2w_supports(T, h->pre.cout, h->pre.h2w_kp, h->pre.k, h->pre.h2w_kp)) add(HG_PRE, HG_H2W);
+  else add(HG_PRE, HG_CONV, conv_tt(T, h->pre.cout, B));
+  int L = T;
+  for (int i = 0; i < c.n_ups; ++i) {
+    const ConvW& up = h->ups[i];
+    const int u = c.upsample_rates[i], p = (up.k - u) / 2, Lout = L * u;
+    if (h2w_ok && up.h2w.ok && u == 8 && p == 4 && h2w_supports(L + 1, up.cout * 8, up.cin, 2, up.cin)) {
+      add(HG_UP, HG_H2W, 0, i);
+    } else if (sw.up && !sw.no_up2 && u == 2 && up.k == 4 && p == 1 && (up.cout == 16 || up.cout == 8) && (long long)cdiv(Lout, 1024) * B >= 512) {
+      add(HG_UP, HG_UP2, 0, i);   // (single utterances: 125 workgroups of this form are slower than the phase-per-block form, 38 against 28 us)
+    } else if (sw.up && up.wpu && p * 2 == u && (long long)cdiv(L + 1, 256) * cdiv(up.cout, 8) * B >= 512) {
+      add(HG_UP, HG_UPK, 0, i);   // all phases of a position in one lane (short inputs: the phase-per-block form below has u x the workgroups)
+    } else if (up.wpk && !sw.no_polyphase) {
+      add(HG_UP, HG_POLY, conv_tt(L + 1, up.cout, (long long)B * u), i);   // u interleaved 2-tap convolutions, blockIdx.z = (batch row, phase)
+    } else {
+      add(HG_UP, HG_CONVT, 0, i);
+    }
+    if (nsf) add(HG_SRC, HG_ADD, 0, i);
+    L = Lout;
+    for (int j = 0; j < c.n_kernels; ++j) {
+      const ConvW* rb1 = &h->rb1[((size_t)i * c.n_kernels + j) * c.n_dil];
+      const ConvW* rb2 = c.resblock != 2 ? &h->rb2[((size_t)i * c.n_kernels + j) * c.n_dil] : nullptr;
+      const int K = rb1[0].k, C = rb1[0].cout;
+      // chain allowed for this ResBlock: a ResBlock1 of 8 / 16 channels whose halo fits the tile, every conv packed for it with one kernel size
+      bool chain = sw.chain && h16_ok && rb2 && c.n_dil <= 3 && chain_h16_supported(K, C, c.n_dil, c.resblock_dilations[j]);
+      for (int m = 0; chain && m < c.n_dil; ++m) chain = rb1[m].wp16c && rb2[m].wp16c && rb1[m].k == K && rb2[m].k == K;
+      if (chain) { add(HG_RB, HG_CHAIN, chain_nc(K, c.n_dil, c.resblock_dilations[j], L, B), i, j); continue; }
+      for (int m = 0; m < c.n_dil; ++m) {
+        const ConvW& c1 = rb1[m];
+        if (!rb2) { add(HG_RB, HG_CONV, conv_tt(L, c1.cout, B), i, j, m); continue; }   // ResBlock2: one conv1d_kernel launch per dilation
+        const ConvW& c2 = rb2[m];
+        // workgroups of a fused pair at 256 positions each.  Fused (one HBM round trip instead of two and a half) unless the launch would leave
+        // most CUs without a workgroup (< 128; the matrix forms at every length); 256 positions per workgroup (NB2) unless that leaves CUs
+        // without one (single utterances): then 128 (NB1)
+        const long long pair_wgs = (long long)cdiv(L, 256 - (c1.k - 1)) * B;
+        const int nb = pair_wgs >= 256 ? 2 : 1;
+        const bool use_mfma = sw.mfma && c1.wpm && c2.wpm;
+        if (!(sw.fused && c1.wpc && c2.wpc && (use_mfma || pair_wgs >= 128 || sw.fused == 2))) {
+          add(HG_RB, HG_CONV1, conv_tt(L, c1.cout, B), i, j, m);
+          add(HG_RB, HG_CONV2, conv_tt(L, c2.cout, B), i, j, m);
+        } else if (h16_ok && c1.wp16 && c2.wp16) {
+          add(HG_RB, HG_PAIR_H16, nb, i, j, m);
+        } else if (use_mfma && split_ok && c1.wps && c2.wps) {
+          add(HG_RB, HG_PAIR_H2, nb, i, j, m);
+        } else if (use_mfma) {
+          add(HG_RB, HG_PAIR_MFMA, nb, i, j, m);
+        } else {
+          add(HG_RB, HG_PAIR_VALU, pair_valu_tt(c1.k, c1.cout, L, B), i, j, m);
+        }
+      }
+    }
+  }
+  if (h->post.cin == 8 && h->post.k == 7 && !sw.no_conv_post) add(HG_POST, HG_POST4);
+  else add(HG_POST, HG_CONV, conv_tt(L, h->post.cout, B));
+  return n;
+}
+
+static int run_conv(const ConvW& c, const float* x, float* y, int tt, int B, int L, int dil, float in_slope, const float* res,
                     const float* acc_in, float out_div, int out_tanh, hipStream_t st) {
   ConvArgs a{};
   a.x = x; a.w = c.wpk; a.bias = c.b; a.y = y; a.res = res; a.acc_in = acc_in; a.out_div = out_div; a.in_slope = in_slope;
   a.out_tanh = out_tanh; a.Cin = c.cin; a.Cout = c.cout; a.L = L; a.dil = dil; a.pad = (c.k * dil - dil) / 2;
-  return launch_conv(a, c.k, B, st);
+  return launch_conv(a, c.k, tt, B, st);
+}
+
+// conv_pre :150 / a u = 8 transposed convolution on the matrix pipe (gemm_h2w): lrelu(src) as planes [rows][Kp] (rows >= Lin: the rest zero),
+// ONE `taps`-tap product with the pre-split weight rows; up_u = 8: the rows are (co, phase), stored phase-interleaved (H2wArgs::up_u)
+static int run_h2w(bsg_hifigan* h, const ConvW& c, const float* src, float* dst, int B, int Lin, int rows, int taps, float slope, int up_u, int up_p,
+                   hipStream_t st) {
+  const long long n = (long long)B * rows * c.h2w_kp;
+  const int Lout = up_u ? Lin * up_u : Lin;
+  TRY(ensure_planes(h, (size_t)2 * n, st));
+  TRY(h2w_split_transposed_lrelu(src, h->planes, h->planes + n, B, c.cin, c.h2w_kp, Lin, rows, slope, st));
+  H2wArgs g{};
+  g.act = h->planes; g.act_plane = n; g.lda = c.h2w_kp; g.sAct = (long long)rows * c.h2w_kp; g.wpack = c.h2w.pack; g.rows = rows; g.K = c.h2w_kp;
+  g.Wn = up_u ? c.cout * up_u : c.cout; g.taps = taps; g.tap_shift0 = up_u ? -1 : -(taps / 2); g.act_is_a = 0; g.C = dst; g.ldc = Lout;
+  g.sC = (long long)c.cout * Lout; g.bias = c.b; g.alpha = 1.f; g.act_fn = ACT_NONE; g.batch = B; g.up_u = up_u; g.up_p = up_p; g.up_lout = up_u ? Lout : 0;
+  return launch_gemm_h2w(g, st);
 }
 
 static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, int32_t T, void* stream, const float* har, long long Lh) {
@@ -1997,190 +2078,113 @@ static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, 
     for (float*& p : h->buf) BSG_HIP(hipMalloc((void**)&p, need * sizeof(float)));
     h->cap = need;
   }
+  const int n_steps = plan_hifigan(h, B, T, har != nullptr, h->steps.data());
+  // The stage buffers: x holds conv_pre's output and then every stage's output (the MRF running sum), xs the stage's input (the upsampled
+  // tensor, plus the source term); inside a ResBlock the running tensor y moves xs -> ya -> yb -> ... and lands in x with the last pair;
+  // tmp is the conv1 output of an unfused pair.
   float *x = h->buf[0], *ya = h->buf[1], *yb = h->buf[2], *tmp = h->buf[3], *xs = h->buf[4];
   const float slope = 0.1f;   // LRELU_SLOPE, hifigan.py:11
-  static int h2w_env = -1;   // BSG_HG_H2W=0: conv_pre and the u = 8 transposed convolutions on the vector pipe (conv1d_kernel / upsample_kernel)
-  if (h2w_env < 0) { const char* e = getenv("BSG_HG_H2W"); h2w_env = e ? atoi(e) : 1; }
-  static int hg_split_env = -1;   // BSG_HG_SPLIT=0 (the fp32-MFMA / vector forms of the ResBlock pairs) takes these two off the 16-bit pipe as well: the switch
-  if (hg_split_env < 0) { const char* e = getenv("BSG_HG_SPLIT"); hg_split_env = e ? atoi(e) : 1; }   // means the WHOLE vocoder on fp32 products
-  const bool h2w_on = h2w_env && hg_split_env && h->h2_ok && gemm_split_enabled();
-  if (h2w_on && h->pre.h2w.ok && h2w_supports(T, h->pre.cout, h->pre.h2w_kp, h->pre.k, h->pre.h2w_kp)) {
-    // conv_pre :150 as a 7-tap product of the mel planes [T][n_mel padded to 128] with the pre-split weights; output [C0][T]
-    const ConvW& p = h->pre;
-    const long long n = (long long)B * T * p.h2w_kp;
-    TRY(ensure_planes(h, (size_t)2 * n, st));
-    TRY(h2w_split_transposed_lrelu(mel, h->planes, h->planes + n, B, p.cin, p.h2w_kp, T, T, 1.0f, st));
-    H2wArgs g{};
-    g.act = h->planes; g.act_plane = n; g.lda = p.h2w_kp; g.sAct = (long long)T * p.h2w_kp; g.wpack = p.h2w.pack; g.rows = T; g.K = p.h2w_kp;
-    g.Wn = p.cout; g.taps = p.k; g.tap_shift0 = -(p.k / 2); g.act_is_a = 0; g.C = x; g.ldc = T; g.sC = (long long)p.cout * T; g.bias = p.b;
-    g.alpha = 1.f; g.act_fn = ACT_NONE; g.batch = B;
-    TRY(launch_gemm_h2w(g, st));
-    path_add(h, "pre:h2w");
-  } else {
-    TRY(run_conv(h->pre, mel, x, B, T, 1, 1.0f, nullptr, nullptr, 1.0f, 0, st));            // conv_pre :150
-    path_add(h, "pre:conv/%s", hg_variant);
-  }
+  const float* y = xs;
   int L = T;
-  float* cur = x;
-  for (int i = 0; i < c.n_ups; ++i) {
-    const ConvW& up = h->ups[i];
-    ConvTArgs t{};
-    t.x = cur; t.w = up.w; t.bias = up.b; t.y = (cur == x ? xs : x); t.in_slope = slope; t.Cin = up.cin; t.Cout = up.cout;
-    t.Lin = L; t.K = up.k; t.u = c.upsample_rates[i]; t.p = (up.k - c.upsample_rates[i]) / 2;
-    const int Lout = L * t.u;
-    static int up_env = -1;
-    if (up_env < 0) { const char* e = getenv("BSG_HG_UP"); up_env = e ? atoi(e) : 1; }
-    if (h2w_on && up.h2w.ok && t.u == 8 && t.p == 4 && h2w_supports(L + 1, up.cout * 8, up.cin, 2, up.cin)) {
-      // the transposed convolution on the matrix pipe: lrelu(x) as planes [L + 1][Cin] (row L zero), ONE 2-tap product with the (co, phase) weight
-      // rows, stored phase-interleaved (H2wArgs::up_u)
-      const long long n = (long long)B * (L + 1) * up.cin;
-      TRY(ensure_planes(h, (size_t)2 * n, st));
-      TRY(h2w_split_transposed_lrelu(cur, h->planes, h->planes + n, B, up.cin, up.cin, L, L + 1, slope, st));
-      H2wArgs g{};
-      g.act = h->planes; g.act_plane = n; g.lda = up.cin; g.sAct = (long long)(L + 1) * up.cin; g.wpack = up.h2w.pack; g.rows = L + 1; g.K = up.cin;
-      g.Wn = up.cout * 8; g.taps = 2; g.tap_shift0 = -1; g.act_is_a = 0; g.C = t.y; g.ldc = Lout; g.sC = (long long)up.cout * Lout; g.bias = up.b;
-      g.alpha = 1.f; g.act_fn = ACT_NONE; g.batch = B; g.up_u = 8; g.up_p = t.p; g.up_lout = Lout;
-      TRY(launch_gemm_h2w(g, st));
-      path_add(h, "up%d:h2w", i);
-    } else if (up_env && t.u == 2 && up.k == 4 && t.p == 1 && (up.cout == 16 || up.cout == 8) && (long long)cdiv(Lout, 1024) * B >= 512 &&
-               !getenv("BSG_NO_UP2")) {   // (single utterances: 125 workgroups of this form are slower than the phase-per-block form, 38 against 28 us)
-      UpArgs ua{};
-      ua.x = cur; ua.w = up.w; ua.bias = up.b; ua.y = t.y; ua.slope = slope; ua.Cin = up.cin; ua.Cout = up.cout; ua.Lin = L; ua.p = t.p;
-      const dim3 grid(cdiv(Lout, 1024), 1, B);
-      if (up.cout == 16) hipLaunchKernelGGL(upsample2_kernel<16>, grid, dim3(256), 0, st, ua);
-      else hipLaunchKernelGGL(upsample2_kernel<8>, grid, dim3(256), 0, st, ua);
+  for (int n = 0; n < n_steps; ++n) {
+    const HgStep& s = h->steps[n];
+    const int i = s.i, j = s.j, m = s.m;
+    if (s.site == HG_PRE) {
+      if (s.form == HG_H2W) TRY(run_h2w(h, h->pre, mel, x, B, T, T, h->pre.k, 1.0f, 0, 0, st));
+      else TRY(run_conv(h->pre, mel, x, s.var, B, T, 1, 1.0f, nullptr, nullptr, 1.0f, 0, st));            // conv_pre :150
+    } else if (s.site == HG_POST) {
+      if (s.form == HG_POST4) hipLaunchKernelGGL(conv_post_kernel<8>, dim3(cdiv(L, 1024), B), dim3(256), 0, st, (const float*)x, (const float*)h->post.w, (const float*)h->post.b, wav, L, 0.01f);
+      else TRY(run_conv(h->post, x, wav, s.var, B, L, 1, 0.01f, nullptr, nullptr, 1.0f, 1, st));          // :169-171 (default slope 0.01)
       BSG_LAUNCH_CHECK();
-      path_add(h, "up%d:up2", i);
-    } else if (up.wpu && up_env && t.p * 2 == t.u && (long long)cdiv(L + 1, 256) * cdiv(up.cout, 8) * B >= 512) {   // short inputs: the phase-per-block form has u x the workgroups
-      // all phases of a position in one lane: contiguous stores (upsample_kernel)
-      UpArgs ua{};
-      ua.x = cur; ua.w = up.wpu; ua.bias = up.b; ua.y = t.y; ua.slope = slope; ua.Cin = up.cin; ua.Cout = up.cout; ua.Lin = L; ua.p = t.p;
-      const dim3 grid(cdiv(L + 1, 256), cdiv(up.cout, 8), B);
-      if (t.u == 8) hipLaunchKernelGGL(upsample_kernel<8>, grid, dim3(256), 0, st, ua);
-      else if (t.u == 4) hipLaunchKernelGGL(upsample_kernel<4>, grid, dim3(256), 0, st, ua);
-      else hipLaunchKernelGGL(upsample_kernel<2>, grid, dim3(256), 0, st, ua);
-      BSG_LAUNCH_CHECK();
-      path_add(h, "up%d:upk", i);
-    } else if (up.wpk && !getenv("BSG_NO_POLYPHASE")) {
-      // polyphase form: u interleaved 2-tap convolutions over the input positions (weights wave-uniform -> scalar loads)
-      ConvArgs a{};
-      a.x = cur; a.w = up.wpk; a.bias = up.b; a.y = t.y; a.out_div = 1.0f; a.in_slope = slope;
-      a.Cin = up.cin; a.Cout = up.cout; a.L = L; a.dil = 1; a.pad = 1;
-      a.n_phase = t.u; a.ph_off = -t.p; a.Lq = L + 1; a.Lout = Lout;
-      a.w_phase_stride = (long long)cdiv(up.cout, up.cout >= 16 ? 16 : 8) * up.cin * 2 * (up.cout >= 16 ? 16 : 8);
-      TRY(launch_convT(a, B, st));
-      path_add(h, "up%d:poly/%s", i, hg_variant);
-    } else {
-      if (up.cout >= 16) hipLaunchKernelGGL(conv_transpose1d_kernel<16>, dim3(cdiv(Lout, 256), cdiv(up.cout, 16), B), dim3(256), 0, st, t);
-      else hipLaunchKernelGGL(conv_transpose1d_kernel<8>, dim3(cdiv(Lout, 256), cdiv(up.cout, 8), B), dim3(256), 0, st, t);
-      BSG_LAUNCH_CHECK();
-      path_add(h, "up%d:convT", i);
-    }
-    if (har) {   // x = x + LayerNorm_C(relu(noise_conv_i(har_source)))                       (hifigan.py:154-160)
+    } else if (s.site == HG_SRC) {   // x = x + LayerNorm_C(relu(noise_conv_i(har_source)))                       (hifigan.py:154-160)
       const ConvW& nc = h->noise_convs[i];
       const int stride = i + 1 < c.n_ups ? nc.k / 2 : 1;
-      TRY(nsf_launch_source_add(t.y, har, nc.w, nc.b, B, nc.cout, Lout, Lh, nc.k, stride, i + 1 < c.n_ups ? stride / 2 : 0, st));
-      path_add(h, "src%d:add", i);
-    }
-    float* xin = t.y;                       // stage input (after upsampling)
-    float* sum = (xin == x ? xs : x);       // MRF running sum / stage output
-    L = Lout;
-    for (int j = 0; j < c.n_kernels; ++j) {
-      const int r = i * c.n_kernels + j;
-      const float* y = xin;
-      {
-        // a whole ResBlock1 of 8 / 16 channels in one launch (resblock_chain_h16_kernel; BSG_HG_CHAIN=0: pair by pair)
-        static int chain_env = -1, split_env = -1, mfma_env2 = -1, h16_env2 = -1;
-        if (chain_env < 0) { const char* e = getenv("BSG_HG_CHAIN"); chain_env = e ? atoi(e) : 1; }
-        if (split_env < 0) { const char* e = getenv("BSG_HG_SPLIT"); split_env = e ? atoi(e) : 1; }
-        if (mfma_env2 < 0) { const char* e = getenv("BSG_HG_MFMA"); mfma_env2 = e ? atoi(e) : 1; }
-        if (h16_env2 < 0) { const char* e = getenv("BSG_HG_H16"); h16_env2 = e ? atoi(e) : 1; }
-        const ConvW& f1 = h->rb1[(size_t)r * c.n_dil];
-        bool chain = chain_env && split_env && mfma_env2 && h16_env2 && c.resblock != 2 && h->h2_ok && gemm_split_enabled() && c.n_dil <= 3 &&
-                     chain_h16_supported(f1.k, f1.cout, c.n_dil, c.resblock_dilations[j]);
-        for (int m = 0; chain && m < c.n_dil; ++m)
-          chain = h->rb1[(size_t)r * c.n_dil + m].wp16c && h->rb2[(size_t)r * c.n_dil + m].wp16c && h->rb1[(size_t)r * c.n_dil + m].k == f1.k &&
-                  h->rb2[(size_t)r * c.n_dil + m].k == f1.k;
-        if (chain) {
+      TRY(nsf_launch_source_add(xs, har, nc.w, nc.b, B, nc.cout, L, Lh, nc.k, stride, i + 1 < c.n_ups ? stride / 2 : 0, st));
+    } else if (s.site == HG_UP) {
+      const ConvW& up = h->ups[i];
+      const int u = c.upsample_rates[i], p = (up.k - u) / 2, Lout = L * u;
+      UpArgs ua{};
+      ua.x = x; ua.w = s.form == HG_UPK ? up.wpu : up.w; ua.bias = up.b; ua.y = xs; ua.slope = slope; ua.Cin = up.cin; ua.Cout = up.cout; ua.Lin = L; ua.p = p;
+      switch (s.form) {
+        case HG_H2W: TRY(run_h2w(h, up, x, xs, B, L, L + 1, 2, slope, 8, p, st)); break;
+        case HG_UP2:
+          if (up.cout == 16) hipLaunchKernelGGL(upsample2_kernel<16>, dim3(cdiv(Lout, 1024), 1, B), dim3(256), 0, st, ua);
+          else hipLaunchKernelGGL(upsample2_kernel<8>, dim3(cdiv(Lout, 1024), 1, B), dim3(256), 0, st, ua);
+          break;
+        case HG_UPK: {
+          const dim3 grid(cdiv(L + 1, 256), cdiv(up.cout, 8), B);
+          if (u == 8) hipLaunchKernelGGL(upsample_kernel<8>, grid, dim3(256), 0, st, ua);
+          else if (u == 4) hipLaunchKernelGGL(upsample_kernel<4>, grid, dim3(256), 0, st, ua);
+          else hipLaunchKernelGGL(upsample_kernel<2>, grid, dim3(256), 0, st, ua);
+          break;
+        }
+        case HG_POLY: {   // the weights are wave-uniform -> scalar loads
+          ConvArgs a{};
+          a.x = x; a.w = up.wpk; a.bias = up.b; a.y = xs; a.out_div = 1.0f; a.in_slope = slope;
+          a.Cin = up.cin; a.Cout = up.cout; a.L = L; a.dil = 1; a.pad = 1;
+          a.n_phase = u; a.ph_off = -p; a.Lq = L + 1; a.Lout = Lout;
+          a.w_phase_stride = (long long)cdiv(up.cout, up.cout >= 16 ? 16 : 8) * up.cin * 2 * (up.cout >= 16 ? 16 : 8);
+          TRY(launch_convT(a, s.var, B, st));
+          break;
+        }
+        default: {
+          ConvTArgs t{};
+          t.x = x; t.w = up.w; t.bias = up.b; t.y = xs; t.in_slope = slope; t.Cin = up.cin; t.Cout = up.cout; t.Lin = L; t.K = up.k; t.u = u; t.p = p;
+          if (up.cout >= 16) hipLaunchKernelGGL(conv_transpose1d_kernel<16>, dim3(cdiv(Lout, 256), cdiv(up.cout, 16), B), dim3(256), 0, st, t);
+          else hipLaunchKernelGGL(conv_transpose1d_kernel<8>, dim3(cdiv(Lout, 256), cdiv(up.cout, 8), B), dim3(256), 0, st, t);
+        }
+      }
+      BSG_LAUNCH_CHECK();
+      L = Lout;
+    } else {   // a ResBlock, or one (dilated conv, conv) pair of it: the MRF sum / mean in the epilogue of the ResBlock's last launch (:161-167)
+      const size_t r = ((size_t)i * c.n_kernels + j) * c.n_dil + (m < 0 ? 0 : m);
+      const ConvW& c1 = h->rb1[r];
+      const ConvW* c2 = c.resblock != 2 ? &h->rb2[r] : nullptr;
+      const bool last = m < 0 || m == c.n_dil - 1;
+      if (m <= 0) y = xs;
+      float* dst = last ? x : (y == ya ? yb : ya);
+      const float* acc_in = (last && j > 0) ? x : nullptr;
+      const float out_div = (last && j == c.n_kernels - 1) ? (float)c.n_kernels : 1.0f;
+      const int dil = c.resblock_dilations[j][m < 0 ? 0 : m];
+      PairArgs pa{};
+      pa.x = y; pa.b1 = c1.b; pa.y = dst; pa.acc_in = acc_in; pa.out_div = out_div; pa.slope = slope; pa.L = L; pa.dil = dil;
+      if (c2) pa.b2 = c2->b;
+      switch (s.form) {
+        case HG_CHAIN: {   // a whole ResBlock1 of 8 / 16 channels in one launch (resblock_chain_h16_kernel)
           ChainArgs ca{};
-          ca.x = xin; ca.y = sum; ca.acc_in = j > 0 ? sum : nullptr; ca.out_div = j == c.n_kernels - 1 ? (float)c.n_kernels : 1.0f;
-          ca.slope = slope; ca.L = L; ca.n_pairs = c.n_dil; ca.range_events = gemm_range_counter();
-          for (int m = 0; m < c.n_dil; ++m) {
-            const ConvW& c1 = h->rb1[(size_t)r * c.n_dil + m];
-            const ConvW& c2 = h->rb2[(size_t)r * c.n_dil + m];
-            ca.w1[m] = c1.wp16c; ca.b1[m] = c1.b; ca.w2[m] = c2.wp16c; ca.b2[m] = c2.b; ca.dil[m] = c.resblock_dilations[j][m];
+          ca.x = xs; ca.y = x; ca.acc_in = acc_in; ca.out_div = out_div; ca.slope = slope; ca.L = L; ca.n_pairs = c.n_dil; ca.range_events = gemm_range_counter();
+          for (int q = 0; q < c.n_dil; ++q) {
+            ca.w1[q] = h->rb1[r + q].wp16c; ca.b1[q] = h->rb1[r + q].b; ca.w2[q] = h->rb2[r + q].wp16c; ca.b2[q] = h->rb2[r + q].b;
+            ca.dil[q] = c.resblock_dilations[j][q];
           }
-          TRY(launch_chain_h16(ca, f1.k, f1.cout, B, st));
-          path_add(h, "rb%d.%d:chain/%s", i, j, hg_variant);
-          continue;
+          TRY(launch_chain_h16(ca, c1.k, c1.cout, s.var, B, st));
+          break;
         }
+        case HG_CONV:   // ResBlock2 (hifigan.py:70-91): x = conv_d(lrelu(x)) + x per dilation
+          TRY(run_conv(c1, y, dst, s.var, B, L, dil, slope, y, acc_in, out_div, 0, st));
+          break;
+        case HG_PAIR_H16:
+          pa.w1 = c1.wp16; pa.w2 = c2->wp16; pa.range_events = gemm_range_counter();
+          TRY(launch_pair_h16(pa, c1.k, c1.cout, s.var, B, st));
+          break;
+        case HG_PAIR_H2:
+          pa.w1 = c1.wps; pa.w2 = c2->wps; pa.range_events = gemm_range_counter();
+          TRY(launch_pair_h2(pa, c1.k, c1.cout, s.var, B, st));
+          break;
+        case HG_PAIR_MFMA:
+          pa.w1 = c1.wpm; pa.w2 = c2->wpm;
+          TRY(launch_pair_mfma(pa, c1.k, c1.cout, s.var, B, st));
+          break;
+        case HG_PAIR_VALU:
+          pa.w1 = c1.wpc; pa.w2 = c2->wpc;
+          TRY(launch_pair(pa, c1.k, c1.cout, s.var, B, st));
+          break;
+        case HG_CONV1: TRY(run_conv(c1, y, tmp, s.var, B, L, dil, slope, nullptr, nullptr, 1.0f, 0, st)); break;     // :56-57
+        default: TRY(run_conv(*c2, tmp, dst, s.var, B, L, 1, slope, y, acc_in, out_div, 0, st));                      // conv2 :58-60
       }
-      for (int m = 0; m < c.n_dil; ++m) {
-        const bool last = m == c.n_dil - 1;
-        const ConvW& c1 = h->rb1[(size_t)r * c.n_dil + m];
-        float* dst = last ? sum : (y == ya ? yb : ya);
-        if (c.resblock == 2) {
-          // ResBlock2 (hifigan.py:70-91): x = conv_d(lrelu(x)) + x per dilation; the MRF sum / mean in the last one's epilogue (:161-167)
-          TRY(run_conv(c1, y, dst, B, L, c.resblock_dilations[j][m], slope, y, (last && j > 0) ? sum : nullptr,
-                       (last && j == c.n_kernels - 1) ? (float)c.n_kernels : 1.0f, 0, st));
-          path_add(h, "rb%d.%d.%d:conv/%s", i, j, m, hg_variant);
-          y = dst;
-          continue;
-        }
-        const ConvW& c2 = h->rb2[(size_t)r * c.n_dil + m];
-        static int fused_env = -1;
-        if (fused_env < 0) { const char* e = getenv("BSG_HG_FUSED"); fused_env = e ? atoi(e) : 1; }
-        // fused pair (one HBM round trip instead of two and a half) unless the launch would leave most CUs without a workgroup
-        const long long pair_wgs = (long long)cdiv(L, 256 - (c1.k - 1)) * B;
-        static int mfma_env = -1;
-        if (mfma_env < 0) { const char* e = getenv("BSG_HG_MFMA"); mfma_env = e ? atoi(e) : 1; }
-        const bool use_mfma = mfma_env && c1.wpm && c2.wpm;
-        if (fused_env && c1.wpc && c2.wpc && (use_mfma || pair_wgs >= 128 || fused_env == 2)) {
-          PairArgs pa{};
-          pa.x = y; pa.w1 = c1.wpc; pa.b1 = c1.b; pa.w2 = c2.wpc; pa.b2 = c2.b; pa.y = dst;
-          pa.acc_in = (last && j > 0) ? sum : nullptr;
-          pa.out_div = (last && j == c.n_kernels - 1) ? (float)c.n_kernels : 1.0f;
-          pa.slope = slope; pa.L = L; pa.dil = c.resblock_dilations[j][m];
-          static int h2_env = -1;   // BSG_HG_SPLIT=0: the fp32-MFMA form even while the GEMMs run split-fp16
-          if (h2_env < 0) { const char* e = getenv("BSG_HG_SPLIT"); h2_env = e ? atoi(e) : 1; }
-          static int h16_env = -1;  // BSG_HG_H16=0: the VALU pairs for 8 / 16 channels
-          if (h16_env < 0) { const char* e = getenv("BSG_HG_H16"); h16_env = e ? atoi(e) : 1; }
-          if (mfma_env && h16_env && h2_env && h->h2_ok && c1.wp16 && c2.wp16 && gemm_split_enabled()) {
-            pa.w1 = c1.wp16; pa.w2 = c2.wp16; pa.range_events = gemm_range_counter();
-            TRY(launch_pair_h16(pa, c1.k, c1.cout, B, st));
-            path_add(h, "rb%d.%d.%d:pair_h16/%s", i, j, m, hg_variant);
-          } else if (use_mfma && h2_env && h->h2_ok && c1.wps && c2.wps && gemm_split_enabled()) {
-            pa.w1 = c1.wps; pa.w2 = c2.wps; pa.range_events = gemm_range_counter();
-            TRY(launch_pair_h2(pa, c1.k, c1.cout, B, st));
-            path_add(h, "rb%d.%d.%d:pair_h2/%s", i, j, m, hg_variant);
-          } else if (use_mfma) {
-            pa.w1 = c1.wpm; pa.w2 = c2.wpm;
-            TRY(launch_pair_mfma(pa, c1.k, c1.cout, B, st));
-            path_add(h, "rb%d.%d.%d:pair_mfma/%s", i, j, m, hg_variant);
-          } else {
-            TRY(launch_pair(pa, c1.k, c1.cout, B, st));
-            path_add(h, "rb%d.%d.%d:pair_valu/%s", i, j, m, hg_variant);
-          }
-          y = dst;
-          continue;
-        }
-        TRY(run_conv(c1, y, tmp, B, L, c.resblock_dilations[j][m], slope, nullptr, nullptr, 1.0f, 0, st));     // :56-57
-        path_add(h, "rb%d.%d.%d:conv1/%s", i, j, m, hg_variant);
-        TRY(run_conv(c2, tmp, dst, B, L, 1, slope, y, (last && j > 0) ? sum : nullptr,
-                     (last && j == c.n_kernels - 1) ? (float)c.n_kernels : 1.0f, 0, st));                     // :58-60, :161-167
-        path_add(h, "rb%d.%d.%d:conv2/%s", i, j, m, hg_variant);
-        y = dst;
-      }
+      if (s.form != HG_CONV1) y = dst;
     }
-    cur = sum;
-  }
-  if (h->post.cin == 8 && h->post.k == 7 && !getenv("BSG_NO_CONV_POST")) {
-    hipLaunchKernelGGL(conv_post_kernel<8>, dim3(cdiv(L, 1024), B), dim3(256), 0, st, (const float*)cur, (const float*)h->post.w, (const float*)h->post.b, wav, L, 0.01f);
-    BSG_LAUNCH_CHECK();
-    path_add(h, "post:post4");
-  } else {
-    TRY(run_conv(h->post, cur, wav, B, L, 1, 0.01f, nullptr, nullptr, 1.0f, 1, st));          // :169-171 (default slope 0.01)
-    path_add(h, "post:conv/%s", hg_variant);
+    path_add(h, s);
   }
   return BSG_OK;
 }
@@ -2215,7 +2219,7 @@ extern "C" int bsg_hifigan_forward_nsf(bsg_hifigan* h, const float* mel, const f
     h->cap_src = need;
   }
   TRY(nsf_launch_source(f0, rand_ini, noise, h->src_w, h->src_b, h->sw_tmp, h->har, B, T, hop, NH, (float)h->cfg.sample_rate, st));
-  path_add(h, "src:nsf");
+  path_token(h, "src:nsf");
   return hifigan_run(h, mel, wav, B, T, stream, h->har, L);
 }
 

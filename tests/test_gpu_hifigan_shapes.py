@@ -8,8 +8,11 @@ VALU / generic forms under them.  tests/test_gpu_hifigan.py reaches a third of t
   * the shapes are chosen so that every form of the default path runs, several of them with a partial last tile (T % 4 != 0: the stage
     lengths 128 T and 256 T are no multiples of the 1024-sample tiles of upsample2_kernel and conv_post_kernel) and four with rows shorter
     than every halo (T = 1, 2, 3, 5: stage 1 is 8 samples long at T = 1 while the K = 11, d = 5 convolution reaches 25 to each side);
-  * WHICH form ran is read from bsg_hifigan_last_path (one token per launch, written at the branch that launched), never restated from the
-    thresholds: test_default_path_covers_every_launch_form fails and names the form if a retuned threshold moves a shape off a kernel;
+  * WHICH form ran is read from bsg_hifigan_last_path (one token per launch, spelled from the plan entry that was launched: the launch and
+    its token come from the same entry of plan_hifigan, so no threshold is evaluated a second time), never restated from the thresholds:
+    test_default_path_covers_every_launch_form fails and names the form if a retuned threshold moves a shape off a kernel;
+  * the fallback forms and the other generators also compare last_path with the record of tests/golden/hifigan_paths.json (the strings of
+    the commit before hifigan_run was split into plan and launch; tests/test_gpu_hifigan_paths.py);
   * the reference is oracle.hifigan.hifigan_forward(dtype=float64); the fp32 oracle's own deviation from it is printed as the yardstick;
   * the deviation is taken over the whole batch and, separately, over the first and last 256 samples of every row, where padding, halos
     and partial tiles live; both meet the same bar;
@@ -73,6 +76,7 @@ import torch
 from bisinger_amd import _lib, synth
 from oracle import hifigan as ohg, nsf as onsf
 from tests.test_gpu_f2_fullsize import notes_f0, nsf  # noqa: F401  (nsf: the module-scoped NSF generator fixture of that file)
+from tests.test_gpu_hifigan_paths import load_golden
 from tests.util import ROOT
 
 pytestmark = pytest.mark.gpu
@@ -320,6 +324,7 @@ def test_fallback_forms_vs_fp64(tmp_path, plain):
         np.save(f + '.mel.npy', _plain_ref(sd, cfg, B, T)['mel'])
         files.append(f)
     default = {s: _default_case(plain, *s)[0] for s in SHORT_LIST}
+    gold = load_golden()['forms']
     for name, (env, check, *check_union) in FORMS.items():
         seen = []
         res = subprocess.run([sys.executable, '-c', CHILD, name] + files, env=dict(os.environ, **env), capture_output=True, text=True, timeout=300)
@@ -336,6 +341,7 @@ def test_fallback_forms_vs_fp64(tmp_path, plain):
             print(f"\nhifigan {name} {B}x{T}: hip {rec['dev']:.2e} edge {rec['edge']:.2e} | fp32 oracle {ref['dev32']:.2e} edge {ref['edge32']:.2e} | "
                   f"{r['path']}")
             check(rec['tokens'])
+            assert r['path'] == gold[name][f'{B}x{T}'], (name, B, T, r['path'], gold[name][f'{B}x{T}'])
             seen.append(rec['tokens'])
             _assert_parity(f'{name} {B}x{T}', rec, ref, B, T)
             if name in BIT_IDENTICAL:
@@ -385,6 +391,7 @@ def test_nsf_generator_vs_fp64(B, T, nsf):  # noqa: F811
     assert rec['tokens'][0] == 'src:nsf' and [t for t in rec['tokens'] if t.endswith(':add')] == [f'src{i}:add' for i in range(4)], path
     if B * T >= 1024:
         assert 'up2:upk' in rec['tokens'] and 'up3:upk' in rec['tokens'], path      # what the size was chosen for
+    assert path == load_golden()['nsf'][f'{B}x{T}'], path
 
 
 @pytest.fixture(scope='module')
@@ -417,4 +424,5 @@ def test_resblock2_generator_vs_fp64(B, T, rb2):
     _assert_parity(f'rb2 {B}x{T}', rec, ref, B, T)
     # 3 stages x 3 ResBlock2 x 2 dilations, one conv1d_kernel launch each
     assert len(_rb(rec['tokens'], range(3))) == 18 and _forms(_rb(rec['tokens'], range(3))) == {'conv'}, path
+    assert path == load_golden()['rb2'][f'{B}x{T}'], path
 
