@@ -410,3 +410,75 @@ def test_oracle_conv_as_matmul_equals_conv1d():
                         want = F.conv1d(xx, ww, bb, padding=pad, dilation=d)
                         assert got.shape == want.shape == (B, 96, Tn)
                         assert float((got - want).abs().max()) <= tol, (K, d, Tn, B, dt)
+
+
+def test_bf16_yardsticks_are_recorded():
+    """tests/golden/bf16_yardsticks.json (tools/make_golden_bf16_yardsticks.py) names every case of tests/bf16_cases.all_cases() with exactly
+    the classes that have a frame, so that every bar of tests/test_gpu_bf16_shapes.py exists before a kernel runs.  Three cases are
+    computed again, every class and both statistics.  The roundings' own cost is no noise: it must agree with the record to 2 %.  The
+    yardstick is flip noise (another host's convolutions sum in another order, and other operands flip; on the host that wrote the
+    record it repeats to the recorded digits): at L = 5 and 20, where every class holds many flips, each figure must agree to a factor
+    of 2; at L = 1, where a class holds a few flips or none, the `all` figures to a factor of 4 (the margin itself) and no class may
+    exceed the setting's pooled figure by more than that."""
+    from tests import bf16_cases as bc
+    yard = bc.load_yardsticks()
+    assert set(yard) == {bc.name(c) for c in bc.all_cases()}
+    for c in bc.all_cases():
+        assert set(yard[bc.name(c)]) == set(bc.masks_of(c)), bc.name(c)
+    for c in (bc.Case('eval', 5, 2, 200), bc.Case('eval', 20, 3, 129), bc.Case('eval', 1, 3, 129)):
+        now, rec = bc.yardstick(bc.state_dict(c.L), c), yard[bc.name(c)]
+        pooled = [b / bc.MARGIN for b in bc.bars(c, yard)['all']]
+        for k in rec:
+            print(f"bf16 yardstick {bc.name(c)} {k}: now {now[k]['yard'][0]:.3e} / {now[k]['yard'][1]:.3e}, recorded {rec[k]['yard'][0]:.3e} / "
+                  f"{rec[k]['yard'][1]:.3e}; cost now {now[k]['cost'][0]:.3e} / {now[k]['cost'][1]:.3e}, recorded {rec[k]['cost'][0]:.3e} / {rec[k]['cost'][1]:.3e}")
+            for i in (0, 1):
+                assert abs(now[k]['cost'][i] - rec[k]['cost'][i]) <= 0.02 * rec[k]['cost'][i], (bc.name(c), k, i)
+                if c.L >= 5:
+                    assert rec[k]['yard'][i] / 2 <= now[k]['yard'][i] <= rec[k]['yard'][i] * 2, (bc.name(c), k, i)
+                else:
+                    assert now[k]['yard'][i] <= 4 * pooled[i], (bc.name(c), k, i)
+                    assert k != 'all' or rec[k]['yard'][i] / 4 <= now[k]['yard'][i] <= rec[k]['yard'][i] * 4, (bc.name(c), k, i)
+
+
+def test_bf16_position_classes():
+    """Every class a case is about has a frame, start / end / seam / interior partition the valid frames, and no case drops more than
+    the classes that are empty by the rule: `start` takes the frames of a row of at most 8 (T = 1: `end` coincides with `start`, and
+    `start` keeps the frame), `end` what `start` left of the last 8, `seam` first exists at T = 65 (frame 56; frame 64 is `end`'s),
+    `interior` at T = 17."""
+    from tests import bf16_cases as bc
+    for c in bc.all_cases():
+        m, lens = bc.masks_of(c), bc.lengths_of(c)
+        assert all(k in m for k in bc.about(c)), (bc.name(c), sorted(m))
+        n = [c.T] * c.B if lens is None else lens
+        want = {'start', 'all'} | ({'end'} if max(n) > 8 else set()) | ({'seam'} if max(n) >= 65 else set())
+        want |= ({'interior'} if max(n) >= 17 else set()) | ({'group'} if c.kind == 'group' else set())
+        assert set(m) == want, (bc.name(c), sorted(m), sorted(want))
+        part = sum(m[k].astype(int) for k in ('start', 'end', 'seam', 'interior') if k in m)
+        assert np.array_equal(part, m['all'].astype(int)), bc.name(c)
+        assert m['all'].sum() == sum(n)
+    m = bc.class_masks(1, 200)
+    assert m['start'][0].nonzero()[0].tolist() == list(range(8)) and m['end'][0].nonzero()[0].tolist() == list(range(192, 200))
+    assert m['seam'][0].nonzero()[0].tolist() == list(range(56, 72)) + list(range(120, 136)) + list(range(184, 192))
+    g = bc.masks_of(bc.GROUP)['group']
+    assert g.any(axis=1).nonzero()[0].tolist() == list(bc.GROUP_ROWS) and g[list(bc.GROUP_ROWS)].all()
+
+
+@pytest.mark.parametrize('L,layer', [(2, 1), (5, 3), (20, 3)])
+def test_bf16_bars_catch_a_one_frame_halo_slip(L, layer):
+    """What keeps the bars of tests/test_gpu_bf16_shapes.py honest: the float64 emulation with a one-frame slip of the halo planted before
+    layer 3 (dilation 8; column 64 k - 1 replaced by column 64 k - 2; at L = 2 before layer 1, the first exchanged halo) at 2 x 200 must
+    exceed the file's bar in the `seam` class, the only one that holds a slipped column, by at least 2 x on both statistics.  With the slip
+    off the restated forward is diffnet_forward bit for bit."""
+    from tests import bf16_cases as bc
+    c = bc.Case('eval', L, 2, 200)
+    sd, inp, masks = bc.state_dict(L), bc.inputs(c), bc.masks_of(c)
+    want = bc.emulate(sd, c, inp, torch.float64)
+    fwd = bc.slipped_forward(layer)
+    assert np.array_equal(bc.emulate(sd, c, inp, torch.float64, forward=lambda *a, **k: fwd(*a, slip=False, **k)), want)
+    dev, bars = bc.stats(bc.emulate(sd, c, inp, torch.float64, forward=fwd), want, masks), bc.bars(c)
+    holds = [k for k in ('start', 'end', 'seam', 'interior') if any(masks[k][0, t] for t in bc.slipped_columns(c.T))]
+    assert holds == ['seam']
+    for k in masks:
+        print(f'halo slip L={L} {k}: rms {dev[k][0]:.2e} (bar {bars[k][0]:.2e}), frame_max {dev[k][1]:.2e} (bar {bars[k][1]:.2e})')
+    for k in holds:
+        assert dev[k][0] >= 2 * bars[k][0] and dev[k][1] >= 2 * bars[k][1], (k, dev[k], bars[k])
