@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'lib', 'libbisinger_hip.so')
 if os.environ.get('BSG_LIB'):      # development: an alternative build of the same ABI (kernel experiments)
     LIB_PATH = os.environ['BSG_LIB']
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 class BsgError(RuntimeError):
@@ -45,6 +45,17 @@ class PwgCfg(Structure):
                                        'skip_channels', 'aux_channels', 'aux_context_window', 'bias', 'use_causal_conv', 'upsample_net',
                                        'interpolate_nearest', 'freq_axis_kernel_size', 'n_scales')] + \
                [('upsample_scales', c_int32 * 8), ('use_pitch_embed', c_int32), ('n_pitch', c_int32), ('hop_size', c_int32)]
+
+
+class GemmDesc(Structure):
+    """bsg_gemm_desc (include/bisinger_hip.h): every argument of the generic GEMM, for the test entry bsg_gemm_ex."""
+    _fields_ = [('A', c_void_p), ('B', c_void_p), ('C', c_void_p), ('M', c_int32), ('N', c_int32), ('K', c_int32),
+                ('lda', c_int32), ('ldb', c_int32), ('ldc', c_int32), ('sA', c_int64), ('sB', c_int64), ('sC', c_int64),
+                ('batch2', c_int32), ('sA2', c_int64), ('sB2', c_int64), ('sC2', c_int64), ('trans_b', c_int32),
+                ('taps', c_int32), ('tap_shift0', c_int32), ('sTapB', c_int64), ('bias_m', c_void_p), ('bias_n', c_void_p),
+                ('sBiasN', c_int64), ('alpha', c_float), ('alpha_ncols', c_int32), ('act', c_int32),
+                ('post_scale_n', c_void_p), ('post_shift_n', c_void_p), ('R', c_void_p), ('ldr', c_int32), ('sR', c_int64),
+                ('rowscale', c_void_p), ('sRS', c_int64), ('batch', c_int32)]
 
 
 class Schedule(Structure):
@@ -138,6 +149,7 @@ _SIGS = {
     'bsg_weight_norm_fold': (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     'bsg_gemm_f32': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                c_int32, c_int32, c_int32, c_int64, c_int64, c_int64, c_int32, c_void_p]),
+    'bsg_gemm_ex': (c_int32, [POINTER(GemmDesc), c_int32, POINTER(c_char_p), c_void_p]),
     'bsg_gemm_set_split': (c_int32, [c_int32]),
     'bsg_diffnet_set_h2': (c_int32, [c_void_p, c_int32]),
     'bsg_diffnet_set_h2q': (c_int32, [c_void_p, c_int32]),

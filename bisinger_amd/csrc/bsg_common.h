@@ -78,6 +78,8 @@ struct GemmArgs {
   int batch;
   unsigned* range_events;   // set by launch_gemm: the counter of the handle in whose call the product runs (gemm_range_counter())
   const char** form_out;    // optional, host side only: launch_gemm stores the name of the form it launched (a string literal) for the caller's launch record
+  int force_form;           // TEST HOOK (bsg_gemm_ex only; every other caller leaves it 0 = dispatch): 1 gemm_split/64, 2 gemm_split/128,
+                            // 3 gemm_fast/64, 4 gemm_fast/128, 5 gemm_f32; 1-4 on a problem that fails the alignment rule is BSG_EINVAL
 };
 int launch_gemm(const GemmArgs& g, hipStream_t st);
 // the split-fp16 forms (gemm.hip, fs2.hip flash attention): true while products are formed on the 16-bit matrix pipe (BSG_GEMM_SPLIT,

@@ -635,23 +635,30 @@ bool gemm_split_enabled() {
   return g_split != 0 && (!tl_guard || tl_guard->split != 0);
 }
 
+// the fast and split kernels move 16-byte pieces: every operand row and every batch / tap offset must keep 16-byte alignment
+static bool gemm_aligned(const GemmArgs& g) {
+  auto al4 = [](long long v) { return (v & 3) == 0; };
+  return al4(g.K) && al4(g.lda) && al4(g.ldb) && al4(g.sA) && al4(g.sA2) && al4(g.sB) && al4(g.sB2) && al4(g.sTapB) &&
+         (g.trans_b || al4(g.N)) && (((uintptr_t)g.A | (uintptr_t)g.B) & 15) == 0;
+}
+
 int launch_gemm(const GemmArgs& g_in, hipStream_t st) {
   GemmArgs g = g_in;
   g.range_events = gemm_range_counter();
   BSG_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0 && g.batch > 0 && g.taps > 0, "gemm: empty problem M=%d N=%d K=%d batch=%d", g.M, g.N, g.K, g.batch);
   BSG_REQUIRE(g.batch <= 65535, "gemm: batch %d > 65535", g.batch);
-  // the fast kernel moves 16-byte pieces: every operand row and every batch / tap offset must keep 16-byte alignment
-  auto al4 = [](long long v) { return (v & 3) == 0; };
-  const bool aligned = al4(g.K) && al4(g.lda) && al4(g.ldb) && al4(g.sA) && al4(g.sA2) && al4(g.sB) && al4(g.sB2) && al4(g.sTapB) &&
-                       (g.trans_b || al4(g.N)) && (((uintptr_t)g.A | (uintptr_t)g.B) & 15) == 0;
-  if (aligned) {
+  const bool aligned = gemm_aligned(g);
+  const int force = g.force_form;   // test hook (bsg_gemm_ex): 0 everywhere else
+  BSG_REQUIRE(force >= 0 && force <= 5, "gemm: force_form %d outside 0..5", force);
+  BSG_REQUIRE(!(force >= 1 && force <= 4) || aligned, "gemm: force_form %d needs a 16-byte aligned problem", force);
+  if (force ? force <= 4 : aligned) {
     // 64-row tiles when 128-row tiles would not give every CU two workgroups (e.g. [16000 x 256] outputs: 250 -> 500 workgroups)
     const long long wg128 = (long long)cdiv(g.N, FBN) * cdiv(g.M, 128) * g.batch;
-    const bool small = wg128 < 2 * 256;
+    const bool small = force ? force == 3 : wg128 < 2 * 256;
     // BSG_GEMM_SPLIT=0 / bsg_gemm_set_split(0): multiply on the fp32 matrix pipe (gemm_fast_kernel) instead of the split-fp16 form
-    if (gemm_split_enabled()) {
+    if (force ? force <= 2 : gemm_split_enabled()) {
       const long long wgs = (long long)cdiv(g.N, FBN) * cdiv(g.M, 128) * g.batch;
-      const bool sm = wgs < 3 * 256;
+      const bool sm = force ? force == 1 : wgs < 3 * 256;
       if (g.form_out) *g.form_out = sm ? "gemm_split/64" : "gemm_split/128";
       if (g.trans_b) return sm ? launch_split<64, true>(g, st) : launch_split<128, true>(g, st);
       return sm ? launch_split<64, false>(g, st) : launch_split<128, false>(g, st);
@@ -681,6 +688,34 @@ extern "C" int bsg_gemm_f32(const float* A, const float* Bm, float* C, const flo
   g.sA = strideA; g.sB = strideB; g.sC = strideC; g.trans_b = trans_b; g.taps = 1; g.tap_shift0 = 0; g.sTapB = 0;
   g.bias_m = bias_m; g.bias_n = bias_n; g.alpha = 1.f; g.act = relu ? bsg::ACT_RELU : bsg::ACT_NONE;
   g.batch = batch;
+  return bsg::launch_gemm(g, (hipStream_t)stream);
+}
+
+// Test entry that reaches all of launch_gemm (ABI v15): every operand, stride, tap, batch and epilogue field, and the form to launch.
+// Every refusal is BSG_EINVAL with a message, before any device call.
+extern "C" int bsg_gemm_ex(const bsg_gemm_desc* d, int32_t force_form, const char** form, void* stream) {
+  BSG_REQUIRE(d, "gemm_ex: null descriptor");
+  BSG_REQUIRE(d->A && d->B && d->C, "gemm_ex: null operand (A %p, B %p, C %p)", (const void*)d->A, (const void*)d->B, (const void*)d->C);
+  BSG_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0 && d->batch > 0 && d->taps > 0 && d->batch2 >= 0,
+              "gemm_ex: non-positive dimension (M=%d N=%d K=%d batch=%d taps=%d batch2=%d)", d->M, d->N, d->K, d->batch, d->taps, d->batch2);
+  BSG_REQUIRE(d->batch <= 65535, "gemm_ex: batch %d > 65535", d->batch);
+  BSG_REQUIRE(d->batch2 <= 1 || d->batch % d->batch2 == 0, "gemm_ex: batch %d is no multiple of batch2 %d", d->batch, d->batch2);
+  BSG_REQUIRE(d->lda > 0 && d->ldb > 0 && d->ldc > 0, "gemm_ex: non-positive leading dimension (lda=%d ldb=%d ldc=%d)", d->lda, d->ldb, d->ldc);
+  BSG_REQUIRE(d->act >= bsg::ACT_NONE && d->act <= bsg::ACT_MISH, "gemm_ex: activation %d outside 0..3", d->act);
+  BSG_REQUIRE(!d->post_scale_n == !d->post_shift_n, "gemm_ex: post_scale_n and post_shift_n go together");
+  BSG_REQUIRE(!d->R || d->ldr > 0, "gemm_ex: R without ldr");
+  BSG_REQUIRE(force_form >= 0 && force_form <= 5, "gemm_ex: force_form %d outside 0..5", force_form);
+  bsg::GemmArgs g{};
+  g.A = d->A; g.B = d->B; g.C = d->C; g.M = d->M; g.N = d->N; g.K = d->K; g.lda = d->lda; g.ldb = d->ldb; g.ldc = d->ldc;
+  g.sA = d->sA; g.sB = d->sB; g.sC = d->sC; g.batch2 = d->batch2; g.sA2 = d->sA2; g.sB2 = d->sB2; g.sC2 = d->sC2;
+  g.trans_b = d->trans_b ? 1 : 0; g.taps = d->taps; g.tap_shift0 = d->tap_shift0; g.sTapB = d->sTapB;
+  g.bias_m = d->bias_m; g.bias_n = d->bias_n; g.sBiasN = d->sBiasN; g.alpha = d->alpha; g.alpha_ncols = d->alpha_ncols; g.act = d->act;
+  g.post_scale_n = d->post_scale_n; g.post_shift_n = d->post_shift_n; g.R = d->R; g.ldr = d->ldr; g.sR = d->sR;
+  g.rowscale = d->rowscale; g.sRS = d->sRS; g.batch = d->batch;
+  g.form_out = form; g.force_form = force_form;
+  BSG_REQUIRE(!(force_form >= 1 && force_form <= 4) || bsg::gemm_aligned(g),
+              "gemm_ex: force_form %d needs a 16-byte aligned problem (K, lda, ldb, the batch and tap strides of A and B multiples of 4, "
+              "N too unless trans_b, A and B on 16-byte boundaries)", force_form);
   return bsg::launch_gemm(g, (hipStream_t)stream);
 }
 

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define BSG_ABI_VERSION 14
+#define BSG_ABI_VERSION 15
 
 #define BSG_OK 0
 #define BSG_EINVAL (-22)  /* bad argument / shape the kernels do not support            */
@@ -517,6 +517,46 @@ int bsg_gemm_f32(const float* A, const float* Bm, float* C, const float* bias_m,
                  int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb, int32_t ldc, int32_t trans_b,
                  int32_t batch, int64_t strideA, int64_t strideB, int64_t strideC, int32_t relu,
                  void* stream);
+
+/* ABI v15, test entry that reaches ALL of the generic GEMM (csrc/gemm.hip launch_gemm): bsg_gemm_desc mirrors its arguments,
+ *   C[z] = rowscale[zo][i] * ( post( act( alpha' * ( sum_tap A[z][i + tap_shift0 + tap][:] . B_tap[z] + bias_n[zo][j] + bias_m[i] ) ) ) + R[zo][i][j] )
+ * with A rows outside [0, M) of the same batch item read as zero, alpha' = alpha on columns < alpha_ncols (0: all columns) and 1 elsewhere,
+ * post(v) = v * post_scale_n[j] + post_shift_n[j].  z = 0 .. batch-1; with batch2 > 1, z = zo * batch2 + zi and an operand's offset is
+ * zo * s + zi * s2 (bias_n, R and rowscale move with zo only); otherwise zo = z.  Strides and leading dimensions count elements.
+ *   force_form  0: dispatch as every other caller; 1 gemm_split/64, 2 gemm_split/128, 3 gemm_fast/64, 4 gemm_fast/128, 5 gemm_f32.
+ *               1-4 need the 16-byte alignment rule of those kernels (K, lda, ldb, sA, sA2, sB, sB2, sTapB multiples of 4, N too
+ *               unless trans_b, A and B on 16-byte boundaries): BSG_EINVAL otherwise
+ *   form        NULL, or receives the name of the form that was launched (a string literal)
+ * BSG_EINVAL with a message, before any device call: a null A, B or C, a non-positive dimension, post_scale_n without post_shift_n (or
+ * the reverse), R without ldr, a force_form outside 0..5, a forced aligned form on an unaligned problem. */
+typedef struct {
+  const float* A;
+  const float* B;
+  float* C;
+  int32_t M, N, K;
+  int32_t lda, ldb, ldc;
+  int64_t sA, sB, sC;           /* batch strides of the outer batch index */
+  int32_t batch2;               /* inner batch count (0 / 1: none) */
+  int64_t sA2, sB2, sC2;
+  int32_t trans_b;              /* 1: B is [N,K] row-major; 0: B is [K,N] row-major */
+  int32_t taps, tap_shift0;     /* conv as GEMM over shifted A rows: A row = i + tap_shift0 + tap */
+  int64_t sTapB;                /* B offset per tap */
+  const float* bias_m;          /* per output row, or NULL */
+  const float* bias_n;          /* per output column, or NULL */
+  int64_t sBiasN;               /* batch stride of bias_n (0: shared) */
+  float alpha;
+  int32_t alpha_ncols;
+  int32_t act;                  /* 0 none, 1 ReLU, 2 GELU (erf), 3 Mish */
+  const float* post_scale_n;    /* both or neither */
+  const float* post_shift_n;
+  const float* R;               /* residual, or NULL */
+  int32_t ldr;
+  int64_t sR;
+  const float* rowscale;        /* or NULL */
+  int64_t sRS;
+  int32_t batch;
+} bsg_gemm_desc;
+int bsg_gemm_ex(const bsg_gemm_desc* d, int32_t force_form, const char** form, void* stream);
 
 /* The GEMMs outside the residual stack form fp32 products on the 16-bit matrix pipe from hi + lo fp16 splits of both operands
  * (csrc/gemm.hip gemm_split_kernel; fp32-grade, |operand| < 4062).  A staged operand outside that range is counted instead of being

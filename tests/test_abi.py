@@ -77,3 +77,41 @@ def test_create_refuses_channel_counts_other_than_256_with_a_message():
     assert rc != 0 and h.value is None
     msg = lib.bsg_last_error().decode()
     assert '192' in msg and '256' in msg, msg
+
+
+def test_gemm_ex_refuses_bad_descriptors_with_a_message():
+    """bsg_gemm_ex (the test entry that reaches all of launch_gemm): every refusal is BSG_EINVAL with a message, before any device call —
+    checked here without a GPU."""
+    from ctypes import byref, c_char_p
+    lib = _lib.load()
+
+    def desc(**kw):
+        d = _lib.GemmDesc(A=0x1000, B=0x2000, C=0x3000, M=8, N=8, K=8, lda=8, ldb=8, ldc=8, trans_b=1, taps=1, alpha=1.0, batch=1)
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return d
+
+    def refused(d, force, *words):
+        form = c_char_p()
+        rc = lib.bsg_gemm_ex(byref(d) if d is not None else None, force, byref(form), None)
+        assert rc == -22 and form.value is None, (rc, form.value)
+        msg = lib.bsg_last_error().decode()
+        assert msg.startswith('gemm_ex:') and all(w in msg for w in words), msg
+
+    refused(None, 0, 'null descriptor')
+    for name in 'ABC':
+        refused(desc(**{name: None}), 0, 'null operand')
+    for name in ('M', 'N', 'K', 'batch', 'taps'):
+        refused(desc(**{name: 0}), 0, 'non-positive', f'{name}=0')
+        refused(desc(**{name: -3}), 5, 'non-positive', f'{name}=-3')
+    refused(desc(post_scale_n=0x4000), 0, 'post_scale_n', 'post_shift_n')
+    refused(desc(post_shift_n=0x4000), 0, 'post_scale_n', 'post_shift_n')
+    refused(desc(R=0x4000), 0, 'R without ldr')
+    for force in (-1, 6):
+        refused(desc(), force, 'force_form', str(force))
+    # the alignment rule of the split / fast kernels: K, lda, ldb, the A / B strides multiples of 4, N too unless trans_b, 16-byte bases
+    unaligned = [dict(K=6), dict(lda=9), dict(ldb=10), dict(sA=66), dict(sB=65), dict(sA2=2), dict(sB2=7), dict(sTapB=1),
+                 dict(A=0x1004), dict(B=0x2008), dict(trans_b=0, N=6)]
+    for kw in unaligned:
+        for force in (1, 2, 3, 4):
+            refused(desc(**kw), force, 'force_form', 'aligned')

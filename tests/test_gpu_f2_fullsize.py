@@ -13,7 +13,8 @@ import yaml
 
 from bisinger_amd import _lib, synth
 from oracle import nsf as onsf, pe as ope
-from tests.util import ROOT, use_config
+from tests import pe_cases
+from tests.util import ROOT
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
@@ -63,25 +64,14 @@ def nsf(sd_spec):
 @pytest.fixture(scope='module')
 def pitch_ext(sd_spec):
     """PitchExtractor on formula weights of seed 11 with tests/test_gpu_f2.py's running statistics."""
-    hp = use_config()
-    hp.update(pitch_type='frame', use_uv=True, pitch_norm='log')
-    from bisinger_amd.pe import PitchExtractor
-    pe = PitchExtractor()
-    spec = OrderedDict((k, tuple(s)) for k, s in sd_spec['PitchExtractor'])
-    w = synth.synth_state_dict(spec, seed=11)
-    for k in spec:
-        if k.endswith('running_var'):
-            w[k] = (0.5 + np.abs(w[k]) * 5).astype(np.float32)
-        if k.endswith('running_mean'):
-            w[k] = (w[k] * 3).astype(np.float32)
-    pe.load_state_dict({k: torch.from_numpy(v) for k, v in w.items()}, strict=False)
-    pe = pe.cuda()
-    return pe, {k: v.detach().cpu() for k, v in pe.state_dict().items()}
+    pe = pe_cases.pitch_extractor(sd_spec).cuda()
+    return pe, pe_cases.cpu_state_dict(pe)
 
 
-def hip_source(f0, rand_ini, noise, lin_w, lin_b):
-    """bsg_nsf_source: (har [B,L], sines [B,NH,L]) as float64 numpy."""
+def hip_source(f0, rand_ini, noise, lin_w, lin_b, HOP=HOP):
+    """bsg_nsf_source: (har [B,L], sines [B,NH,L]) as float64 numpy; NH from rand_ini."""
     B, T = f0.shape
+    NH = rand_ini.shape[1]
     L = T * HOP
     dev = torch.device('cuda')
     f0_d, ri_d, nz_d = (torch.from_numpy(a).to(dev).contiguous() for a in (f0, rand_ini, noise))
@@ -110,21 +100,27 @@ def test_nsf_source_vs_fp64(B, T, nsf):
     if B > 1:
         f0[1] = SR / 4
         f0[2] = 0
-    rand_ini = rs.uniform(0, 1, size=(B, NH)).astype(np.float32)
-    noise = rs.standard_normal((B, T * HOP, NH)).astype(np.float32)
-    lin_w, lin_b = sd['m_source.l_linear.weight'], sd['m_source.l_linear.bias']
-    har, sines = hip_source(f0, rand_ini, noise, lin_w, lin_b)
+    _check_source(f'nsf_source B={B} T={T}', rs, f0, sd, HOP, NH)
+
+
+def _check_source(tag, rs, f0, sd, hop, nh):
+    """bsg_nsf_source on f0 [B, T] at `hop` samples per frame and `nh` harmonics against oracle.nsf.sine_waves in float64."""
+    B, T = f0.shape
+    rand_ini = rs.uniform(0, 1, size=(B, nh)).astype(np.float32)
+    noise = rs.standard_normal((B, T * hop, nh)).astype(np.float32)
+    lin_w, lin_b = sd['m_source.l_linear.weight'][:, :nh].contiguous(), sd['m_source.l_linear.bias']
+    har, sines = hip_source(f0, rand_ini, noise, lin_w, lin_b, hop)
     assert np.isfinite(har).all() and np.isfinite(sines).all()
-    dev = np.zeros(NH)
-    dev32 = np.zeros(NH)
+    dev = np.zeros(nh)
+    dev32 = np.zeros(nh)
     dev_har = dev32_har = 0.0
     for b in range(B):        # the oracle one row at a time: at T = 4000 a row is 9 x 1 024 000 samples
-        args = (torch.from_numpy(f0[b:b + 1]), torch.from_numpy(rand_ini[b:b + 1]), torch.from_numpy(noise[b:b + 1]), SR, HOP)
+        args = (torch.from_numpy(f0[b:b + 1]), torch.from_numpy(rand_ini[b:b + 1]), torch.from_numpy(noise[b:b + 1]), SR, hop, nh - 1)
         w64 = onsf.sine_waves(*args, dtype=F64)
-        w32 = onsf.sine_waves(*args, dtype=F32).double()
+        w32 = onsf.sine_waves(*args, dtype=F32)
         h64 = torch.tanh(torch.nn.functional.linear(w64, lin_w.double(), lin_b.double()))[0, :, 0].numpy()
-        h32 = onsf.sine_source(sd, *args, dtype=F32)[0, 0].double().numpy()
-        w64, w32 = w64[0].T.numpy(), w32[0].T.numpy()
+        h32 = torch.tanh(torch.nn.functional.linear(w32, lin_w, lin_b))[0, :, 0].double().numpy()      # oracle.nsf.sine_source in fp32
+        w64, w32 = w64[0].T.numpy(), w32.double()[0].T.numpy()
         dev = np.maximum(dev, np.abs(sines[b] - w64).max(1))
         dev32 = np.maximum(dev32, np.abs(w32 - w64).max(1))
         dev_har = max(dev_har, _maxabs(har[b], h64))
@@ -133,13 +129,27 @@ def test_nsf_source_vs_fp64(B, T, nsf):
     bar = np.maximum(2 * dev32, 2e-4)
     # merged: the per-harmonic floor through l_linear (tanh' <= 1)
     bar_har = max(2 * dev32_har, 2e-4 * max(1.0, float(lin_w.abs().sum())))
-    print(f'nsf_source B={B} T={T}: per harmonic hip {np.array2string(dev, precision=2)} fp32 oracle {np.array2string(dev32, precision=2)}; '
+    print(f'{tag}: per harmonic hip {np.array2string(dev, precision=2)} fp32 oracle {np.array2string(dev32, precision=2)}; '
           f'merged hip {dev_har:.2e} fp32 oracle {dev32_har:.2e}')
     assert (dev <= bar).all(), (dev, bar)
     assert dev_har <= bar_har, (dev_har, bar_har)
     # the kernel forms rad and carries the phase in fp64: only its fp32 sin, noise term and store round (a phase carried in fp32, or
     # rad rounded to fp32 as the fp32 oracle does, is 1e-5 .. 1e-4 off here)
     assert dev.max() <= 1e-6 and dev_har <= 1e-6, (dev, dev_har)
+
+
+# hop != 256: a thread's share S = ceil(T * hop / 256) samples no longer ends on a frame boundary, and L is no multiple of 256.
+# (3, 100): L = 300, S = 2, threads 150 .. 255 empty; (7, 300): the PWG hop, S = 9 over frames of 300; hop = 1: every sample its own
+# frame, L = 255 (S = 1, one thread empty), L = 257 (S = 2, the last thread's share is one sample) and L = 5; NH = 1 and 2 harmonics.
+@pytest.mark.parametrize('T,hop,nh', [(3, 100, 9), (7, 300, 9), (255, 1, 9), (257, 1, 1), (5, 1, 2)])
+def test_nsf_source_odd_hops_vs_fp64(T, hop, nh, nsf):
+    _, sd, _ = nsf
+    rs = np.random.RandomState(T * 1000 + hop + nh)
+    f0 = np.zeros((3, T), np.float32)
+    f0[0] = notes_f0(rs, T) if T > 16 else np.resize(np.float32([0, 440, 523.25, 0, 87.3, 1046.5, 330]), T)
+    f0[1] = SR / 4
+    f0[2, T // 2:] = 220.0        # unvoiced, then voiced from the middle frame on
+    _check_source(f'nsf_source T={T} hop={hop} NH={nh}', rs, f0, sd, hop, nh)
 
 
 @pytest.mark.parametrize('B', [1, 8])
