@@ -1167,18 +1167,12 @@ struct bsg_diffnet {
   // residency of the split kernels on this handle's device (workgroups per CU; -1 = not queried yet): pair / 4-way form with the
   // padded LDS size (one workgroup per CU by construction) and with the plain size (two chains share a CU), 16-wave form
   int occ2 = -1, occ4 = -1, occw = -1, occ2s = -1, occ4s = -1;
-  // two half-batches on two streams (bsg_ddpm_sample): rows [row_off, row_off + B_sub) of the bound batch
-  int row_off = 0;                     // row offset the launch helpers add to the handle's buffers
-  bool no_split = false;               // half-batch launches of a large batch use the regular one-workgroup-per-tile kernel
-  bool split_small_lds = false;        // half-batch launches of a small batch: split kernels without the LDS padding, so that
-                                       // workgroups of the two chains can share a CU
+  // two half-batches on two streams (dual_fork): the second stream and the events that fork and join it
   hipStream_t st2 = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   // ragged binding (bsg_diffnet_prepare_ragged): every row of the bound (B, T) decoded at its own frame count
   bool ragged = false;                 // the bound condition came with row lengths (a plain prepare clears this)
-  bool rg_active = false;              // inside a ragged call: plan_stack plans the ragged 16-row launch (bf16 configuration: the ragged
-                                       // bf16 stack launch, and launch_tail takes the ragged bf16 tail)
-  int occ_stack_varlen = -1;           // resident workgroups per CU of that launch (-1: not queried)
+  int occ_stack_varlen = -1;           // resident workgroups per CU of the ragged 16-row stack launch (-1: not queried)
   int occ_stack_bf16_varlen = -1;      // the same for the ragged bf16 stack launch
   int* rg_dev = nullptr;               // [B rounded up to even] row lengths, then the tile tables {row, tile} of every launch group
   size_t rg_cap = 0;                   // ints rg_dev holds
@@ -1556,10 +1550,9 @@ extern "C" int bsg_diffnet_prepare(bsg_diffnet* h, const float* cond, int32_t B,
   }
   h->cond_q_valid = false;
   h->cond_rows_valid = false;
-  static int env_h2w = -1;   // BSG_GEMM_H2W=0: gemm_split_kernel (operands split while staged) instead of the pre-split GEMM
-  if (env_h2w < 0) { const char* e = getenv("BSG_GEMM_H2W"); env_h2w = e ? atoi(e) : 1; }
+  const DnSwitches& sw = dn_switches();
   bool bf16_direct = false;
-  const bool h2w = env_h2w && h->cond_h2w_ok && gemm_split_enabled() && h2w_supports(T, 2 * C, C, 1, C) && (long long)h->L * B <= 65535;
+  const bool h2w = sw.gemm_h2w && h->cond_h2w_ok && gemm_split_enabled() && h2w_supports(T, 2 * C, C, 1, C) && (long long)h->L * B <= 65535;
   if (h2w) {
     // All L projections of all B rows as ONE launch on the 16-bit matrix pipe with pre-split operands (gemm_h2w.hip): cond is transposed and
     // split once into hi / lo fp16 planes [B][T][H]; the weights were split at create; batch index z = l B + b writes condterm[l][b] =
@@ -1575,9 +1568,7 @@ extern "C" int bsg_diffnet_prepare(bsg_diffnet* h, const float* cond, int32_t B,
     TRY(h2w_split_transposed(cond, h->cond_planes, h->cond_planes + bt * C, B, C, T, st));
     // the 16-row stack launch (diffnet_h2q.hip) loads the term as channel quads: the same epilogue stores it once more in that order
     // (BSG_H2_Q=0 / BSG_COND_QUAD=0: not)
-    static int env_cq = -1;
-    if (env_cq < 0) { const char* e = getenv("BSG_COND_QUAD"); const char* q = getenv("BSG_H2_Q"); env_cq = (e ? atoi(e) : 1) && (q ? atoi(q) : 1); }
-    bool want_q = env_cq && h->compute == BSG_COMPUTE_F32 && h->apack1q && !h->h2_off && !h->split_off;
+    bool want_q = sw.cond_quad && sw.h2_q && h->compute == BSG_COMPUTE_F32 && h->apack1q && !h->h2_off && !h->split_off;
     if (want_q && bt > h->cap_cond_q) {
       BSG_HIP(hipStreamSynchronize(st));
       if (h->condterm_q) (void)hipFree(h->condterm_q);
@@ -1597,14 +1588,10 @@ extern "C" int bsg_diffnet_prepare(bsg_diffnet* h, const float* cond, int32_t B,
     g.Cq = want_q ? h->condterm_q : nullptr;
     // bf16-operand configuration: the epilogue rounds the term to bf16 quads itself and writes NO fp32 copy (until round 5 the 2.6 GB of fp32 at
     // B = 64 went to HBM and 20 conversion launches read them back; BSG_COND_BF16_DIRECT=0: that form)
-    static int env_hd = -1;
-    if (env_hd < 0) { const char* e = getenv("BSG_COND_BF16_DIRECT"); env_hd = e ? atoi(e) : 1; }
-    bf16_direct = env_hd && h->compute == BSG_COMPUTE_BF16 && h->condterm_h;
+    bf16_direct = sw.cond_bf16_direct && h->compute == BSG_COMPUTE_BF16 && h->condterm_h;
     g.Ch = bf16_direct ? h->condterm_h : nullptr;
     // ONE layout per pass: the rows only when neither the quads nor the bf16 quads are written (BSG_COND_ROWS=1: the rows as well, round 5's way)
-    static int env_rows = -1;
-    if (env_rows < 0) { const char* e = getenv("BSG_COND_ROWS"); env_rows = e ? atoi(e) : 0; }
-    const bool rows_now = env_rows || !(want_q || bf16_direct);
+    const bool rows_now = sw.cond_rows || !(want_q || bf16_direct);
     if (rows_now) TRY(alloc_cond_rows(h, bt, st));
     h->cond_rows_valid = rows_now;
     g.act = h->cond_planes; g.act_plane = (long long)bt * C; g.lda = C; g.sAct = (long long)T * C; g.wpack = h->wcond_pack;
@@ -1635,12 +1622,7 @@ extern "C" int bsg_diffnet_prepare(bsg_diffnet* h, const float* cond, int32_t B,
 
 // GEMM1 of the residual block: BSG_WINO unset = 2: Winograd F(2,3) kernels, and the F(4,3) stack launch (diffnet_f43.hip) for launches
 // that fill the chip with 64-frame tiles (plan_stack; BSG_STACK43=2: for any shape); 1: F(2,3) only; 0: the direct K=768 form
-static int wino_env() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("BSG_WINO"); v = e ? atoi(e) : 2; }
-  return v;
-}
-static bool use_wino() { return wino_env() != 0; }
+static bool use_wino() { return dn_switches().wino != 0; }
 
 // A pair of workgroups per tile pays (a z exchange through L2) only when single workgroups would leave CUs idle: measured on
 // MI355X at T=1000, B = 1 / 2 / 4 (32 / 64 / 128 tiles): 63 -> 41, 64 -> 42, 65 -> 47 us per layer; B = 6 (192 tiles): 68 -> 70.
@@ -1651,12 +1633,6 @@ static bool use_wino() { return wino_env() != 0; }
 // of them on one CU while others stay empty; asking for more than half of the CU's 160 KB of LDS (only 48 KB are used) makes
 // that impossible.
 static constexpr size_t kSplitLds = 84 * 1024;
-
-static int split_env() {
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("BSG_SPLIT"); env = e ? atoi(e) : 1; }
-  return env;
-}
 
 static void query_split_occupancy(bsg_diffnet* h) {
   const int lds = C * 48 * (int)sizeof(float);
@@ -1674,26 +1650,77 @@ static void query_split_occupancy(bsg_diffnet* h) {
   h->occw = occ_of((const void*)residual_split_kernel<true, 1>, 1024, (size_t)lds);
 }
 
-static int use_split(bsg_diffnet* h, int B, int T) {   // 0: regular launch; 1 / 4: 2 / 4 workgroups per tile; 2: one 16-wave workgroup per tile
-  const int env = split_env();
-  if (!env || h->split_off || !h->num_cus || !h->zbuf) return 0;
+// The launches of a call: which form runs the L residual layers, and how the batch splits into launch groups.  plan_stack() decides it
+// from the shape, the handle's state and what the plan is for (PlanScope), and writes nothing on the handle but its occupancy memos
+// (occ_*), so a query (bsg_diffnet_uses_handoffs, ragged_launch_ok) and the launch it predicts agree; every compute entry plans once and
+// hands the plan to the launches, which read nothing else about the call.
+enum StackForm {
+  STACK_NONE,   // no stack launch: one launch per layer (launch_layer), of the form in StackPlan::layer
+  STACK_F43,    // Winograd F(4,3) on the fp32 matrix pipe (diffnet_f43.hip)
+  STACK_H2,     // split-fp16, 32-row matrix tiles (residual_stack_h2_kernel, diffnet_h2.hip)
+  STACK_H2Q,    // split-fp16, 16-row matrix tiles (residual_stack_q_kernel, diffnet_h2q.hip)
+  STACK_PART,   // split-fp16 part form: several workgroups per tile (residual_part_h2_kernel, diffnet_h2.hip)
+  STACK_BF16,   // bf16-operand configuration (diffnet_bf16.hip)
+};
+
+enum LayerForm {   // (bsg_diffnet_last_path)
+  LAYER_PLAIN,    // "layer": residual_layer_kernel, one workgroup per 32-frame tile
+  LAYER_SPLIT2,   // "split2": residual_split_kernel<false, 2>, a pair of workgroups per tile, each half of the channels
+  LAYER_SPLIT4,   // "split4": residual_split_kernel<false, 4>
+  LAYER_WIDE,     // "wide": residual_split_kernel<true, 1>, one 16-wave workgroup per tile
+  LAYER_BF16,     // "bf16": bf16-operand configuration (launch_residual_layer_bf16)
+};
+
+enum PlanScope {
+  PLAN_WHOLE,        // the whole batch of a call
+  PLAN_HALF_BIG,     // half of a batch of more tiles than CUs (dual_fork): per-layer launches of the one-workgroup-per-tile kernel
+  PLAN_HALF_SMALL,   // half of a smaller batch (dual_fork): the channel-split kernels without the LDS padding, so that workgroups of the
+                     // two chains can share a CU
+  PLAN_RAGGED,       // the bound ragged batch: its ragged stack launch, or STACK_NONE where the handle's state has none
+};
+
+struct StackPlan {
+  StackForm form = STACK_NONE;
+  int nct = 2;          // column tiles of 32 frames per workgroup: tiles of 32 * nct frames (F(4,3), bf16: 64)
+  int parts = 0;        // STACK_PART: workgroups per tile (4: quads, 2: pairs)
+  int rows = 0;         // rows per launch group
+  bool ragged = false;  // a ragged call: one launch per group of the plan bound by bsg_diffnet_prepare_ragged (rows = B)
+  LayerForm layer = LAYER_PLAIN;   // STACK_NONE: the form of the per-layer launches
+  bool small_lds = false;          // ... and the pair / 4-way form at the un-padded LDS size (PLAN_HALF_SMALL)
+  int row0 = 0;         // the launches work on rows [row0, row0 + B) of the bound batch (the second half-batch chain of dual_fork)
+};
+
+// the channel-split form of a per-layer launch of B x T (LAYER_PLAIN: none); small_lds: at the un-padded LDS size
+static LayerForm use_split(bsg_diffnet* h, int B, int T, bool small_lds) {
+  const int env = dn_switches().split;
+  if (!env || h->split_off || !h->num_cus || !h->zbuf) return LAYER_PLAIN;
   const long long tiles = (long long)B * cdiv(T, 32);
-  if ((size_t)tiles > h->split_cap) return 0;
+  if ((size_t)tiles > h->split_cap) return LAYER_PLAIN;
   if (h->occ2 < 0) query_split_occupancy(h);
   // residency is what makes a hand-off terminate: every workgroup of the launch (and, for two chains sharing CUs, of both
   // launches: dual_fork checks that sum) must fit the device at the LDS size actually launched
-  const int o4 = h->split_small_lds ? h->occ4s : h->occ4, o2 = h->split_small_lds ? h->occ2s : h->occ2;
-  if (4 * tiles <= h->num_cus && env != 2 && o4 >= 1) return 4;   // BSG_SPLIT=2: no 4-way split (A/B measurements)
-  if (2 * tiles <= h->num_cus) return o2 >= 1 ? 1 : 0;
-  if (tiles <= h->num_cus && env != 3) return h->occw >= 1 ? 2 : 0;   // BSG_SPLIT=3: pair form only (A/B measurements)
-  return 0;
+  const int o4 = small_lds ? h->occ4s : h->occ4, o2 = small_lds ? h->occ2s : h->occ2;
+  if (4 * tiles <= h->num_cus && env != 2 && o4 >= 1) return LAYER_SPLIT4;   // BSG_SPLIT=2: no 4-way split (A/B measurements)
+  if (2 * tiles <= h->num_cus) return o2 >= 1 ? LAYER_SPLIT2 : LAYER_PLAIN;
+  if (tiles <= h->num_cus && env != 3) return h->occw >= 1 ? LAYER_WIDE : LAYER_PLAIN;   // BSG_SPLIT=3: pair form only (A/B measurements)
+  return LAYER_PLAIN;
 }
 
-static int launch_layer(bsg_diffnet* h, int layer, const float* x_in, const long long* t_dev, int t_uniform, float* x_out,
+// The per-layer launch of B x T rows: what a plan without a stack form runs, and all that the entries of ONE layer plan
+// (bsg_diffnet_residual_layer, bsg_diffnet_debug_stamps: they never take a stack launch).  The channel-split kernels are F(2,3) forms of
+// the fp32 configuration and carry no stamps; the half of a big batch keeps the one-workgroup-per-tile kernel.
+static void plan_layer(bsg_diffnet* h, StackPlan& plan, int B, int T, PlanScope scope, bool stamps = false) {
+  plan.small_lds = scope == PLAN_HALF_SMALL;
+  if (h->compute == BSG_COMPUTE_BF16) plan.layer = LAYER_BF16;
+  else plan.layer = !stamps && use_wino() && scope != PLAN_HALF_BIG ? use_split(h, B, T, plan.small_lds) : LAYER_PLAIN;
+}
+
+// one layer of rows [plan.row0, plan.row0 + B) in the form plan.layer
+static int launch_layer(bsg_diffnet* h, const StackPlan& plan, int layer, const float* x_in, const long long* t_dev, int t_uniform, float* x_out,
                         float* skip, int B, int T, hipStream_t st, unsigned long long* stamps = nullptr) {
   ResArgs a{};
   a.x_in = x_in; a.x_out = x_out; a.skip = skip;
-  a.condterm = h->condterm + ((size_t)layer * h->B + h->row_off) * 2 * C * (size_t)T;   // [L][B bound][2C][T], this launch's rows
+  a.condterm = h->condterm + ((size_t)layer * h->B + plan.row0) * 2 * C * (size_t)T;   // [L][B bound][2C][T], this launch's rows
   a.dproj = h->dproj; a.t_dev = t_dev; a.t_uniform = t_uniform;
   a.apack1 = h->apack1 + (size_t)layer * 2 * C * 3 * C;
   a.apack2 = h->apack2 + (size_t)layer * 2 * C * C;
@@ -1707,36 +1734,36 @@ static int launch_layer(bsg_diffnet* h, int layer, const float* x_in, const long
   a.first = layer == 0;
   a.skip_div = layer == h->L - 1 ? sqrtf((float)h->L) : 1.0f;
   a.stamps = stamps;
-  if (h->compute == BSG_COMPUTE_F32 && !stamps && use_wino() && !h->no_split && use_split(h, B, T)) {
+  const LayerForm form = plan.layer;
+  if (form == LAYER_SPLIT2 || form == LAYER_SPLIT4 || form == LAYER_WIDE) {
     // small launch: a pair of workgroups per tile, each half of the channels (residual_split_kernel)
     SplitArgs s{};
     a.tiles_per_row = cdiv(T, 32);
     s.base = a;
     s.apack2w = h->apack2w + (size_t)layer * 2 * C * C;
     // exchange tiles and flags of this launch's rows (two half-batch chains may be in flight at once)
-    const size_t tile0 = (size_t)h->row_off * a.tiles_per_row;
+    const size_t tile0 = (size_t)plan.row0 * a.tiles_per_row;
     s.zbuf = h->zbuf + tile0 * C * 32;
     s.flags = h->split_flags + tile0 * 16;
     s.status = h->split_flags + 16 * h->split_cap;
     if (++h->split_epoch == 0) h->split_epoch = 1;
     s.epoch = h->split_epoch;
-    const int mode = use_split(h, B, T);
-    if (h->inject_giveup > 0 && mode != 2) { s.inject = 1; --h->inject_giveup; }
-    const size_t slds = h->split_small_lds ? (size_t)C * 48 * sizeof(float) : kSplitLds;
-    if (mode == 2) hipLaunchKernelGGL((residual_split_kernel<true, 1>), dim3(B * a.tiles_per_row), dim3(1024), (size_t)C * 48 * sizeof(float), st, s);
-    else if (mode == 4) hipLaunchKernelGGL((residual_split_kernel<false, 4>), dim3(4 * B * a.tiles_per_row), dim3(256), slds, st, s);
+    if (h->inject_giveup > 0 && form != LAYER_WIDE) { s.inject = 1; --h->inject_giveup; }
+    const size_t slds = plan.small_lds ? (size_t)C * 48 * sizeof(float) : kSplitLds;
+    if (form == LAYER_WIDE) hipLaunchKernelGGL((residual_split_kernel<true, 1>), dim3(B * a.tiles_per_row), dim3(1024), (size_t)C * 48 * sizeof(float), st, s);
+    else if (form == LAYER_SPLIT4) hipLaunchKernelGGL((residual_split_kernel<false, 4>), dim3(4 * B * a.tiles_per_row), dim3(256), slds, st, s);
     else hipLaunchKernelGGL((residual_split_kernel<false, 2>), dim3(2 * B * a.tiles_per_row), dim3(512), slds, st, s);
     BSG_LAUNCH_CHECK();
-    h->last_path = mode == 2 ? "wide" : mode == 4 ? "split4" : "split2";
+    h->last_path = form == LAYER_WIDE ? "wide" : form == LAYER_SPLIT4 ? "split4" : "split2";
     h->last_groups = 0;
     return BSG_OK;
   }
-  if (h->compute == BSG_COMPUTE_BF16) {
+  if (form == LAYER_BF16) {
     // the running skip sum lives in h->skip_h (bf16); a caller-supplied fp32 buffer (the unit-test hook) is converted
     // in and out around the launch
-    a.condterm_h = h->condterm_h + ((size_t)layer * h->B + h->row_off) * 2 * C * (size_t)T;
-    a.skip_h = h->skip_h + (size_t)h->row_off * C * T;
-    const bool ext = skip != h->skip + (size_t)h->row_off * C * T;
+    a.condterm_h = h->condterm_h + ((size_t)layer * h->B + plan.row0) * 2 * C * (size_t)T;
+    a.skip_h = h->skip_h + (size_t)plan.row0 * C * T;
+    const bool ext = skip != h->skip + (size_t)plan.row0 * C * T;
     if (ext && !a.first) TRY(f32_to_quad_bf16(skip, h->skip_h, B, C, T, st));
     TRY(launch_residual_layer_bf16(a, st));
     h->last_path = "bf16";
@@ -1771,74 +1798,57 @@ static int launch_layer(bsg_diffnet* h, int layer, const float* x_in, const long
   return BSG_OK;
 }
 
-// The stack launch of a call: which form runs the L residual layers, and how the batch splits into launch groups.  plan_stack() decides
-// it from the shape and the handle's state and writes nothing on the handle but its occupancy memos (occ_*), so a query
-// (bsg_diffnet_uses_handoffs) and the launch it predicts agree; every compute entry plans once and hands the plan to the launches.
-enum StackForm {
-  STACK_NONE,   // no stack launch: one launch per layer (launch_layer)
-  STACK_F43,    // Winograd F(4,3) on the fp32 matrix pipe (diffnet_f43.hip)
-  STACK_H2,     // split-fp16, 32-row matrix tiles (residual_stack_h2_kernel, diffnet_h2.hip)
-  STACK_H2Q,    // split-fp16, 16-row matrix tiles (residual_stack_q_kernel, diffnet_h2q.hip)
-  STACK_PART,   // split-fp16 part form: several workgroups per tile (residual_part_h2_kernel, diffnet_h2.hip)
-  STACK_BF16,   // bf16-operand configuration (diffnet_bf16.hip)
-};
-
-struct StackPlan {
-  StackForm form = STACK_NONE;
-  int nct = 2;          // column tiles of 32 frames per workgroup: tiles of 32 * nct frames (F(4,3), bf16: 64)
-  int parts = 0;        // STACK_PART: workgroups per tile (4: quads, 2: pairs)
-  int rows = 0;         // rows per launch group
-  bool ragged = false;  // a ragged call: one launch per group of the plan bound by bsg_diffnet_prepare_ragged (rows = B)
-};
-
 // A tile row is ceil(T / (32 nct)) workgroups that wait for each other, and every workgroup of a launch must be resident: at most
 // occ x CUs workgroups, whole rows only.  It pays when a launch has more workgroups than CUs (two per CU overlap each other's waits);
-// smaller launches keep the channel-split kernels.  The half-batch chains of a large batch (dual_fork: no_split) take per-layer launches.
-static StackPlan plan_stack(bsg_diffnet* h, int B, int T, hipStream_t st) {
-  StackPlan plan;
-  if (h->no_split) return plan;
+// smaller launches keep the channel-split kernels.  `ragged`: the ragged stack launch of the bound batch (bsg_diffnet_prepare_ragged), if
+// the handle's state has one.  Leaves plan.form = STACK_NONE where no stack launch runs.
+static void stack_form(bsg_diffnet* h, StackPlan& plan, int B, int T, hipStream_t st, bool ragged) {
+  const DnSwitches& sw = dn_switches();
   if (h->compute == BSG_COMPUTE_BF16) {
     // bf16-operand configuration: the stack launch (the default; BSG_STACK_BF16=0 selects per-layer launches).  64-frame tiles, one
     // workgroup per CU (256 registers per wave), whole rows per launch group.  Measured on one box, ms per 100-step pass at T=1000,
     // stack / per-layer: B=1 43.2 / 56.4, B=16 58.2 / 87.8, B=32 109.7 / 133.3, B=64 213.8 / 237.3 (tools/bench_small.py with
     // BSG_DTYPE=bf16).  Per layer and tile ~21.5 us, of which the two GEMMs' MFMAs are ~7.  Whether it is taken
     // does not depend on B.
-    static int env = -1;
-    if (env < 0) { const char* e = getenv("BSG_STACK_BF16"); env = e ? atoi(e) : 1; }
-    if (!env || h->split_off || !h->num_cus || !h->hx || !h->epoch_dev) return plan;
+    if (!sw.stack_bf16 || h->split_off || !h->num_cus || !h->hx || !h->epoch_dev) return;
     if (h->occ_stack_h < 0) h->occ_stack_h = stack_bf16_occupancy() >= 1 ? 1 : 0;
     const int tpr = cdiv(T, 64);
     const long long slots = (long long)h->occ_stack_h * h->num_cus;
-    if (h->rg_active) {   // a ragged call (ragged_launch_ok checked it): groups from the bound plan
-      if (h->occ_stack_h >= 1) { plan.form = STACK_BF16; plan.rows = B; plan.ragged = true; }
+    if (ragged) {   // residual_stack_bf16_varlen_kernel: groups from the bound plan
+      if (h->occ_stack_bf16_varlen < 0) h->occ_stack_bf16_varlen = stack_bf16_varlen_occupancy() >= 1 ? 1 : 0;
+      if (h->occ_stack_h >= 1 && h->occ_stack_bf16_varlen >= 1) { plan.form = STACK_BF16; plan.rows = B; plan.ragged = true; }
     } else if (h->occ_stack_h >= 1 && tpr <= slots) {
       plan.form = STACK_BF16;
       plan.rows = slots / tpr < B ? (int)(slots / tpr) : B;
     }
-    return plan;
+    return;
   }
-  if (h->rg_active) {   // a ragged call (ragged_launch_ok checked it): the 16-row launch on 64-frame tiles, groups from the bound plan
-    plan.form = STACK_H2Q; plan.rows = B; plan.ragged = true;
-    return plan;
+  if (ragged) {
+    // the ragged form of the 16-row launch on 64-frame tiles, groups from the bound plan.  Not on a handle that was demoted off the 16-row
+    // launch (bsg_diffnet_set_h2q / set_h2 / set_split 0, or the process switches BSG_H2 / BSG_H2_Q = 0), and it reads the conditioner
+    // term's channel quads only
+    if (sw.h2 && sw.h2_q && !h->h2_off && !h->q_off && !h->split_off && h->num_cus && h->hx && h->epoch_dev && h->apack1q && h->apack2q &&
+        h->dconv && h->cond_q_valid) {
+      if (h->occ_stack_varlen < 0) h->occ_stack_varlen = stack_h2q_varlen_occupancy() >= 1 ? 1 : 0;
+      if (h->occ_stack_varlen >= 1) { plan.form = STACK_H2Q; plan.rows = B; plan.ragged = true; }
+    }
+    return;
   }
   {
     // split-fp16 form (diffnet_h2.hip): fp32 operands as hi + lo fp16 terms on the 16-bit matrix pipe; 64-frame tiles, one workgroup per
     // CU, whole rows per launch group, every batch size.  BSG_H2=0 / bsg_diffnet_set_h2(h, 0): off (the kernels of the fp32 matrix pipe)
-    static int envh2 = -1;
-    if (envh2 < 0) { const char* e = getenv("BSG_H2"); envh2 = e ? atoi(e) : 1; }
     // (round 4: the launch epoch of the flags lives in device memory, so these launches can be captured and replayed; only the part forms'
     // exchange buffers must exist already — their first eager call allocates them)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (st) (void)hipStreamIsCapturing(st, &cap);
     const bool capturing = cap != hipStreamCaptureStatusNone;
-    if (envh2 && !h->h2_off && h->compute == BSG_COMPUTE_F32 && !h->split_off && h->num_cus && h->hx && h->apack1s && h->epoch_dev) {
+    if (sw.h2 && !h->h2_off && h->compute == BSG_COMPUTE_F32 && !h->split_off && h->num_cus && h->hx && h->apack1s && h->epoch_dev) {
       // tile width: 32 frames (one column tile per workgroup) while those tiles fit ONE launch group, else 64 frames (two column tiles:
       // half the weight stream per frame).  ms per 100-step pass at T = 1000 on one box (tools/bench_small.py), 32-frame / 64-frame /
       // fp32-pipe kernels (BSG_H2=0):  B=1 55 / 70 / 60,  B=2 53 / 70 / 64,  B=4 52 / 70 / 84,  B=6 56 / 74 / 119,  B=8 69 / 76 / 132,
       // B=10 115 / 80 / 187,  B=12 113 / 87 / 198,  B=16 134 / 103 / 200 — so the launch is taken for every batch size (BSG_H2_NCT=1 / 2
       // forces a width)
-      static int env_nct = -1;
-      if (env_nct < 0) { const char* e = getenv("BSG_H2_NCT"); env_nct = e ? atoi(e) : 0; }
+      const int env_nct = sw.h2_nct;
       int nct = (long long)B * cdiv(T, 32) > h->num_cus ? 2 : 1;
       if (env_nct == 1 || env_nct == 2) nct = env_nct;
       {
@@ -1848,10 +1858,6 @@ static StackPlan plan_stack(bsg_diffnet* h, int B, int T, hipStream_t st) {
         // B * ceil(T / 64) <= CUs / 2 (B <= 8).  ms per 100-step pass at T = 1000, one workgroup per tile / part form: B=1 54.5 / 24.1,
         // B=2 52.6 / 25.4, B=3 52.0 / 32.0, B=4 51.5 / 35.0, B=5 54.8 / 46.0, B=6 57.1 / 49.6, B=8 69.1 / 59.4.  BSG_H2_PART=0: none
         // (BSG_H2_QUAD=0 / BSG_H2_QUAD64=0 / BSG_H2_PAIR64=0: not that form)
-        static int env_part = -1, env_quad = -1, env_quad64 = -1;
-        if (env_part < 0) { const char* e = getenv("BSG_H2_PART"); env_part = e ? atoi(e) : 1; }
-        if (env_quad < 0) { const char* e = getenv("BSG_H2_QUAD"); env_quad = e ? atoi(e) : 1; }
-        if (env_quad64 < 0) { const char* e = getenv("BSG_H2_QUAD64"); env_quad64 = e ? atoi(e) : 1; }
         // occ_part: [1] / [2] quads of 32- / 64-frame tiles, [0] pairs of 64-frame tiles
         auto part = [&](int parts, int pn) {
           int& occ = h->occ_part[parts == 4 ? pn : 0];
@@ -1862,20 +1868,16 @@ static StackPlan plan_stack(bsg_diffnet* h, int B, int T, hipStream_t st) {
         };
         const long long t32 = (long long)B * cdiv(T, 32), t64 = (long long)B * cdiv(T, 64);
         const bool part_bufs = !capturing || (size_t)(2 * t64) <= h->part_cap;   // (sized in 32-frame tile equivalents; 2 t64 >= t32)
-        if (env_part && !h->parts_off && env_nct == 0 && h->apack1q && part_bufs) {
-          if (env_quad && 4 * 8 * cdiv(t32, 8) <= h->num_cus && part(4, 1)) return plan;
-          if (env_quad64 && 4 * 8 * cdiv(t64, 8) <= h->num_cus && part(4, 2)) return plan;
-          static int env_pair64 = -1;
-          if (env_pair64 < 0) { const char* e = getenv("BSG_H2_PAIR64"); env_pair64 = e ? atoi(e) : 1; }
-          if (env_pair64 && 2 * 8 * cdiv(t64, 8) <= h->num_cus && part(2, 2)) return plan;
+        if (sw.h2_part && !h->parts_off && env_nct == 0 && h->apack1q && part_bufs) {
+          if (sw.h2_quad && 4 * 8 * cdiv(t32, 8) <= h->num_cus && part(4, 1)) return;
+          if (sw.h2_quad64 && 4 * 8 * cdiv(t64, 8) <= h->num_cus && part(4, 2)) return;
+          if (sw.h2_pair64 && 2 * 8 * cdiv(t64, 8) <= h->num_cus && part(2, 2)) return;
         }
       }
       // 16-row matrix tiles (residual_stack_q_kernel, diffnet_h2q.hip; round 5): the same launch with every product a v_mfma_f32_16x16x32_f16 —
       // the same matrix cycles, but the chip holds a higher clock under that shape.  BSG_H2_Q=0: the 32-row form (residual_stack_h2_kernel)
-      static int env_q = -1;
-      if (env_q < 0) { const char* e = getenv("BSG_H2_Q"); env_q = e ? atoi(e) : 1; }
       bool q = false;
-      if (env_q && !h->q_off && h->apack1q && h->apack2q) {
+      if (sw.h2_q && !h->q_off && h->apack1q && h->apack2q) {
         if (h->occ_stack_h2q[nct] < 0) h->occ_stack_h2q[nct] = stack_h2q_occupancy(nct) >= 1 ? 1 : 0;
         q = h->occ_stack_h2q[nct] >= 1;
       }
@@ -1885,16 +1887,15 @@ static StackPlan plan_stack(bsg_diffnet* h, int B, int T, hipStream_t st) {
         plan.form = q ? STACK_H2Q : STACK_H2;
         plan.nct = nct;
         plan.rows = h->num_cus / tpr < B ? h->num_cus / tpr : B;
-        return plan;
+        return;
       }
     }
   }
-  if (wino_env() == 2) {
+  if (sw.wino == 2) {
     // F(4,3) form (diffnet_f43.hip): 64-frame tiles, one workgroup per CU, whole rows per launch group; BSG_STACK43=0 keeps per-layer
     // launches.  A launch group takes the same time whatever part of the chip it fills, so the form is taken when the groups are
     // >= 90 % full (B = 15, 16, 29..32, .. at T = 1000): it is ~6 % faster than two chains of per-layer F(2,3) launches, not more.
-    static int env43 = -1;
-    if (env43 < 0) { const char* e = getenv("BSG_STACK43"); env43 = e ? atoi(e) : 1; }
+    const int env43 = sw.stack43;
     if (env43 && h->compute == BSG_COMPUTE_F32 && !h->split_off && h->num_cus && h->hx && h->epoch_dev) {
       if (h->occ_stack43 < 0) h->occ_stack43 = stack_f43_occupancy() >= 1 ? 1 : 0;
       const int tpr43 = cdiv(T, 64);
@@ -1908,6 +1909,12 @@ static StackPlan plan_stack(bsg_diffnet* h, int B, int T, hipStream_t st) {
       }
     }
   }
+}
+
+static StackPlan plan_stack(bsg_diffnet* h, int B, int T, hipStream_t st, PlanScope scope = PLAN_WHOLE) {
+  StackPlan plan;
+  if (scope != PLAN_HALF_BIG) stack_form(h, plan, B, T, st, scope == PLAN_RAGGED);
+  if (plan.form == STACK_NONE && scope != PLAN_RAGGED) plan_layer(h, plan, B, T, scope);
   return plan;
 }
 
@@ -1957,7 +1964,7 @@ static int stack_args(bsg_diffnet* h, const StackPlan& plan, int g, const long l
   const int tpr = cdiv(T, 32 * plan.nct);
   const int r0 = plan.ragged ? 0 : g * plan.rows;
   const int nb = B - r0 < plan.rows ? B - r0 : plan.rows;
-  const size_t row = (size_t)h->row_off + r0;
+  const size_t row = (size_t)plan.row0 + r0;
   p = StackArgs{};
   p.x_in = h->xa + row * C * T;
   p.skip = h->skip + row * C * T;
@@ -1976,9 +1983,7 @@ static int stack_args(bsg_diffnet* h, const StackPlan& plan, int g, const long l
   // the flags a wrapping launch zeroes: BOTH arrays of the handle, whichever form wraps (a part launch replaces these with its own below)
   p.wrap_pflags = h->part_flags;
   p.wrap_pflag_words = h->part_flags ? (int)(2 * h->part_cap * 4) : 0;
-  static int env_old = -1;   // BSG_DEBUG_WRAP_R04=1: round 4's behaviour (only a PART launch zeroes the part flags at a wrap) — the negative control of tests/test_gpu_handoff.py
-  if (env_old < 0) { const char* e = getenv("BSG_DEBUG_WRAP_R04"); env_old = e ? atoi(e) : 0; }
-  if (env_old) { p.wrap_pflags = nullptr; p.wrap_pflag_words = 0; }
+  if (dn_switches().debug_wrap_r04) { p.wrap_pflags = nullptr; p.wrap_pflag_words = 0; }
   const bool part = plan.form == STACK_PART;
   if (h->inject_giveup > 0) { p.inject = 1; --h->inject_giveup; }
   else if (h->inject_xcc > 0 && part) { p.inject = 2; --h->inject_xcc; }
@@ -1997,7 +2002,7 @@ static int stack_args(bsg_diffnet* h, const StackPlan& plan, int g, const long l
   }
   p.condterm = h->condterm + row * 2 * C * T;
   p.dconv = h->dconv; p.apackw = h->apackw; p.apack2 = h->apack2;
-  if (stamps) { const char* e = getenv("BSG_STAMP_MODE"); p.stamp_mode = e ? atoi(e) : 0; }
+  if (stamps) p.stamp_mode = live_stamp_mode();
   if (plan.form == STACK_F43) {
     p.apackw43 = h->apackw43;
     return BSG_OK;
@@ -2014,14 +2019,14 @@ static int stack_args(bsg_diffnet* h, const StackPlan& plan, int g, const long l
   return BSG_OK;
 }
 
-// the planned stack launch of rows [h->row_off, h->row_off + B): its launch groups one after the other on `st`; `tail`: the sampler
+// the planned stack launch of rows [plan.row0, plan.row0 + B): its launch groups one after the other on `st`; `tail`: the sampler
 // step's tail in the same launch (split-fp16 forms)
 static int launch_stack(bsg_diffnet* h, const StackPlan& plan, const long long* t_dev, int t_uniform, int B, int T, hipStream_t st,
                         unsigned long long* stamps = nullptr, const TailArgs* tail = nullptr) {
   BSG_REQUIRE(plan.form != STACK_NONE && plan.rows > 0, "stack launch: no launch form selected");
   BSG_REQUIRE(!tail || plan.form == STACK_H2 || plan.form == STACK_H2Q, "stack launch: a fused tail needs the split-fp16 form");
   BSG_REQUIRE(plan.form != STACK_PART || (!tail && plan.rows >= B), "part launch: whole batch, no fused tail");
-  BSG_REQUIRE(!plan.ragged || (h->ragged && h->rg_dev && h->row_off == 0 && (plan.form == STACK_BF16 || h->cond_q_valid)),
+  BSG_REQUIRE(!plan.ragged || (h->ragged && h->rg_dev && plan.row0 == 0 && (plan.form == STACK_BF16 || h->cond_q_valid)),
               "ragged stack launch: no ragged plan / conditioner quads bound");
   const int groups = plan.ragged ? (int)h->rg_group_tiles.size() : cdiv(B, plan.rows);
   for (int g = 0; g < groups; ++g) {
@@ -2071,29 +2076,14 @@ static bool fused_tail_ok(const bsg_diffnet* h);
 
 static bool bf16_tail_on(const bsg_diffnet* h);
 
-// Can the handle's CURRENT state decode the bound ragged batch with the ragged launch?  fp32 configuration: not when it was demoted off the
-// 16-row launch (bsg_diffnet_set_h2q / set_h2 / set_split 0 or the process switches BSG_H2 / BSG_H2_Q = 0), or without the conditioner
-// term's channel quads or the fused step tail.  bf16 configuration: not without the bf16 stack launch (BSG_STACK_BF16=0, set_split 0) or
-// the bf16 step tail (BSG_TAIL_BF16=0).  (The callers then decode the rows one by one.)
+// Can the handle's CURRENT state decode the bound ragged batch with the ragged launch?  When its ragged plan has a stack launch
+// (stack_form: the conditions of the launch itself) and the step tail that launch needs exists: the fused tail's packed weights
+// (BSG_NO_FUSED_TAIL unset), in the fp32 configuration the split-fp16 tail inside the launch, in the bf16 configuration the bf16 step tail
+// (BSG_TAIL_BF16=0: none).  (The callers otherwise decode the rows one by one.)
 static bool ragged_launch_ok(bsg_diffnet* h) {
-  if (!h->ragged) return false;
-  if (h->compute == BSG_COMPUTE_BF16) {
-    static int env_stack = -1;
-    if (env_stack < 0) { const char* e = getenv("BSG_STACK_BF16"); env_stack = e ? atoi(e) : 1; }
-    if (!env_stack || h->split_off || h->prepared_compute != BSG_COMPUTE_BF16) return false;
-    if (!h->num_cus || !h->hx || !h->epoch_dev || h->M > 96 || !bf16_tail_on(h) || !fused_tail_ok(h)) return false;
-    if (h->occ_stack_h < 0) h->occ_stack_h = stack_bf16_occupancy() >= 1 ? 1 : 0;
-    if (h->occ_stack_bf16_varlen < 0) h->occ_stack_bf16_varlen = stack_bf16_varlen_occupancy() >= 1 ? 1 : 0;
-    return h->occ_stack_h >= 1 && h->occ_stack_bf16_varlen >= 1;
-  }
-  static int envh2 = -1, env_q = -1;
-  if (envh2 < 0) { const char* e = getenv("BSG_H2"); envh2 = e ? atoi(e) : 1; }
-  if (env_q < 0) { const char* e = getenv("BSG_H2_Q"); env_q = e ? atoi(e) : 1; }
-  if (!envh2 || !env_q || h->h2_off || h->q_off || h->split_off) return false;
-  if (h->compute != BSG_COMPUTE_F32 || h->prepared_compute != BSG_COMPUTE_F32 || !h->cond_q_valid) return false;
-  if (!h->num_cus || !h->hx || !h->epoch_dev || !h->apack1q || !h->apack2q || !h->dconv || !h->tail_s || h->M > 96 || !fused_tail_ok(h)) return false;
-  if (h->occ_stack_varlen < 0) h->occ_stack_varlen = stack_h2q_varlen_occupancy() >= 1 ? 1 : 0;
-  return h->occ_stack_varlen >= 1;
+  if (!h->ragged || h->prepared_compute != h->compute || h->M > 96 || !fused_tail_ok(h)) return false;
+  if (h->compute == BSG_COMPUTE_BF16 ? !bf16_tail_on(h) : !h->tail_s) return false;
+  return plan_stack(h, h->B, h->T, nullptr, PLAN_RAGGED).form != STACK_NONE;
 }
 
 // entry of a compute call on a ragged binding: refused under stream capture and where the handle has no ragged launch
@@ -2112,13 +2102,6 @@ static int ragged_enter(bsg_diffnet* h, hipStream_t st, const char* who) {
   return BSG_OK;
 }
 
-// rg_active for the duration of one compute call
-struct RaggedScope {
-  bsg_diffnet* h;
-  explicit RaggedScope(bsg_diffnet* h_) : h(h_) { h->rg_active = h->ragged; }
-  ~RaggedScope() { h->rg_active = false; }
-};
-
 // Does the launch this shape takes read the ROW layout of the conditioner term?  (The 16-row stack launch and the part forms read the quads,
 // the bf16 launches the bf16 quads; everything else — 32-row launch, F(4,3), per-layer and channel-split kernels — the rows.)
 static bool cond_rows_needed(const bsg_diffnet* h, const StackPlan& plan) {
@@ -2129,7 +2112,7 @@ static int cond_layout_for(bsg_diffnet* h, const StackPlan& plan, hipStream_t st
   return cond_rows_needed(h, plan) ? ensure_cond_rows(h, st) : BSG_OK;
 }
 
-// The L residual layers of one evaluation of rows [h->row_off, h->row_off + B): input h->xa (the in-projection of x), output the skip sum
+// The L residual layers of one evaluation of rows [plan.row0, plan.row0 + B): input h->xa (the in-projection of x), output the skip sum
 // in h->skip(_h).  The planned stack launch — with the sampler step's tail inside it when `tail` is given — or one launch per layer.
 static int run_layers(bsg_diffnet* h, const StackPlan& plan, const long long* t_dev, int t_uniform, int B, int T, hipStream_t st,
                       const TailArgs* tail = nullptr) {
@@ -2138,11 +2121,11 @@ static int run_layers(bsg_diffnet* h, const StackPlan& plan, const long long* t_
   if (plan.form != STACK_NONE) {
     TRY(launch_stack(h, plan, t_dev, t_uniform, B, T, st, nullptr, tail));
   } else {
-    const size_t off = (size_t)h->row_off * C * T;
+    const size_t off = (size_t)plan.row0 * C * T;
     float* cur = h->xa + off;
     float* nxt = h->xb + off;
     for (int l = 0; l < h->L; ++l) {
-      TRY(launch_layer(h, l, cur, t_dev, t_uniform, nxt, h->skip + off, B, T, st));
+      TRY(launch_layer(h, plan, l, cur, t_dev, t_uniform, nxt, h->skip + off, B, T, st));
       float* tmp = cur; cur = nxt; nxt = tmp;
     }
   }
@@ -2160,13 +2143,13 @@ static int forward_impl(bsg_diffnet* h, const StackPlan& plan, const float* x, c
   TRY(conv1x1(h->w_in, h->b_in, x, h->xa, C, h->M, B, T, ACT_RELU, st));  // net.py:116-118
   TRY(run_layers(h, plan, t_dev, t_uniform, B, T, st));
   if (h->compute == BSG_COMPUTE_BF16) TRY(quad_bf16_to_f32(h->skip_h, h->skip, B, C, T, st));
-  if (h->rg_active) {   // ragged: the stack launch stored no skip sum at a row's padding; the projections below read every frame of B x T
+  if (plan.ragged) {   // ragged: the stack launch stored no skip sum at a row's padding; the projections below read every frame of B x T
     hipLaunchKernelGGL(ragged_zero_pad_kernel, dim3(cdiv(T, 256), C, B), dim3(256), 0, st, h->skip, (const int*)h->rg_dev, C, T);
     BSG_LAUNCH_CHECK();
   }
   TRY(conv1x1(h->w_skip, h->b_skip, h->skip, h->hid, C, C, B, T, ACT_RELU, st));   // net.py:127-128
   TRY(conv1x1(h->w_fin, h->b_fin, h->hid, eps, h->M, C, B, T, ACT_NONE, st));      // net.py:129
-  if (h->rg_active) {   // ragged: the projections above ran on every frame of B x T; the padding's eps is 0
+  if (plan.ragged) {   // ragged: the projections above ran on every frame of B x T; the padding's eps is 0
     hipLaunchKernelGGL(ragged_zero_pad_kernel, dim3(cdiv(T, 256), h->M, B), dim3(256), 0, st, eps, (const int*)h->rg_dev, h->M, T);
     BSG_LAUNCH_CHECK();
   }
@@ -2179,8 +2162,7 @@ extern "C" int bsg_diffnet_forward(bsg_diffnet* h, const float* x, const int64_t
   TRY(check_bound(h, B, T, "diffnet_forward"));
   BSG_REQUIRE(x && t && eps, "diffnet_forward: null argument");
   TRY(ragged_enter(h, (hipStream_t)stream, "diffnet_forward"));
-  RaggedScope ragged_scope(h);
-  const StackPlan plan = plan_stack(h, B, T, (hipStream_t)stream);
+  const StackPlan plan = plan_stack(h, B, T, (hipStream_t)stream, h->ragged ? PLAN_RAGGED : PLAN_WHOLE);
   TRY(cond_layout_for(h, plan, (hipStream_t)stream));
   return forward_impl(h, plan, x, (const long long*)t, 0, eps, B, T, (hipStream_t)stream);
 }
@@ -2192,7 +2174,9 @@ extern "C" int bsg_diffnet_residual_layer(bsg_diffnet* h, int32_t layer, const f
   BSG_REQUIRE(x_in && t && x_out && skip && x_in != x_out, "diffnet_residual_layer: null or aliased argument");
   BSG_REQUIRE(layer >= 0 && layer < h->L, "diffnet_residual_layer: layer %d out of range", layer);
   if (h->compute == BSG_COMPUTE_F32) TRY(ensure_cond_rows(h, (hipStream_t)stream));
-  return launch_layer(h, layer, x_in, (const long long*)t, 0, x_out, skip, B, T, (hipStream_t)stream);
+  StackPlan plan;
+  plan_layer(h, plan, B, T, PLAN_WHOLE);
+  return launch_layer(h, plan, layer, x_in, (const long long*)t, 0, x_out, skip, B, T, (hipStream_t)stream);
 }
 
 static int check_schedule(const bsg_schedule* s, const char* who, bool plms) {
@@ -2207,18 +2191,26 @@ static int check_schedule(const bsg_schedule* s, const char* who, bool plms) {
 }
 
 static bool fused_tail_ok(const bsg_diffnet* h) {
-  return h->ws_pack != nullptr && (h->MP == 80 || h->MP == 96) && !getenv("BSG_NO_FUSED_TAIL");
+  return h->ws_pack != nullptr && (h->MP == 80 || h->MP == 96) && !live_no_fused_tail();
 }
 
 // the bf16-operand configuration runs its step tail's projections on bf16 MFMAs (step_tail_bf16_kernel; BSG_TAIL_BF16=0: the fp32 tail)
 static bool bf16_tail_on(const bsg_diffnet* h) {
-  const char* tail_env = getenv("BSG_TAIL_BF16");
-  return h->compute == BSG_COMPUTE_BF16 && !(tail_env && atoi(tail_env) == 0) && h->tail_h;
+  return h->compute == BSG_COMPUTE_BF16 && live_tail_bf16() && h->tail_h;
+}
+
+// What every step tail takes for rows [row0, row0 + B) on tiles of `tile` frames: x, the next evaluation's in-projection, the biases and
+// the shape; h2: the tails on the 16-bit matrix pipe, their split-fp16 weights and scales too
+static void tail_fields(const bsg_diffnet* h, TailArgs& a, int row0, int tile, bool h2, float* x, int B, int T) {
+  a.x = x; a.xa_next = h->xa + (size_t)row0 * C * T;
+  a.b_skip = h->b_skip; a.b_fin = h->b_fin96; a.b_in = h->b_in;
+  a.B = B; a.T = T; a.M = h->M; a.tiles_per_row = cdiv(T, tile);
+  if (h2) { a.ws_s = h->tail_s; a.wo_s = h->tail_s + 2 * C * C; a.wi_s = h->tail_s + 2 * C * C + 2 * 96 * C; a.tail_scale = h->tail_scale; }
 }
 
 // step_tail_kernel: skip projection, output projection, sampler update of x (DDPM, or PLMS when a.plms_hist > 0) and the next
 // evaluation's in-projection into h->xa; the caller fills the sampler-specific fields of `a`
-static int launch_tail(bsg_diffnet* h, TailArgs& a, float* x, int B, int T, hipStream_t st) {
+static int launch_tail(bsg_diffnet* h, const StackPlan& plan, TailArgs& a, float* x, int B, int T, hipStream_t st) {
   static bool tail_attr = false;
   const size_t tail_lds = (size_t)(C * 32 + 96 * 32) * sizeof(float);
   if (!tail_attr) {
@@ -2228,22 +2220,21 @@ static int launch_tail(bsg_diffnet* h, TailArgs& a, float* x, int B, int T, hipS
     BSG_HIP(hipFuncSetAttribute((const void*)step_tail_kernel<96, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tail_lds));
     tail_attr = true;
   }
-  const size_t off = (size_t)h->row_off * C * T;
+  const size_t off = (size_t)plan.row0 * C * T;
   a.skip = h->skip + off; a.skip_h = h->compute == BSG_COMPUTE_BF16 ? h->skip_h + off : nullptr;
-  a.x = x; a.xa_next = h->xa + off;
-  a.ws_pack = h->ws_pack; a.wo_pack = h->wo_pack; a.wi_pack = h->wi_pack; a.b_skip = h->b_skip; a.b_fin = h->b_fin96; a.b_in = h->b_in;
-  a.B = B; a.T = T; a.M = h->M; a.tiles_per_row = cdiv(T, 32);
+  tail_fields(h, a, plan.row0, 32, false, x, B, T);
+  a.ws_pack = h->ws_pack; a.wo_pack = h->wo_pack; a.wi_pack = h->wi_pack;
   if (bf16_tail_on(h)) {   // bf16-operand configuration: the projections on bf16 MFMAs too
     a.ws_h = h->tail_h; a.wo_h = h->tail_h + C * C; a.wi_h = h->tail_h + C * C + 96 * C;
-    if (h->rg_active) {   // ragged: one launch over the tiles of every launch group's table (they follow the row lengths in rg_dev)
-      BSG_REQUIRE(h->row_off == 0 && h->rg_dev, "ragged bf16 step tail: no ragged plan bound");
+    if (plan.ragged) {   // ragged: one launch over the tiles of every launch group's table (they follow the row lengths in rg_dev)
+      BSG_REQUIRE(plan.row0 == 0 && h->rg_dev, "ragged bf16 step tail: no ragged plan bound");
       int n_tiles = 0;
       for (int t : h->rg_group_tiles) n_tiles += t;
       return launch_step_tail_bf16_ragged(a, reinterpret_cast<const int2*>(h->rg_dev + ((h->B + 1) & ~1)), h->rg_dev, n_tiles, st);
     }
     return launch_step_tail_bf16(a, st);
   }
-  BSG_REQUIRE(!h->rg_active, "step tail: a ragged call needs the bf16 tail in the bf16 configuration");
+  BSG_REQUIRE(!plan.ragged, "step tail: a ragged call needs the bf16 tail in the bf16 configuration");
   const dim3 grid(B * a.tiles_per_row), block(512);
   if (a.plms_hist) {
     if (h->MP == 80) hipLaunchKernelGGL((step_tail_kernel<80, true>), grid, block, tail_lds, st, a);
@@ -2260,53 +2251,42 @@ static int launch_tail(bsg_diffnet* h, TailArgs& a, float* x, int B, int T, hipS
 // the stack runs as the split-fp16 launch, the tail runs inside it (one launch per step; BSG_H2_TAIL=0: two launches).  A ragged call
 // always fuses it (ragged_launch_ok checked the tail's weights).
 static int step_from_xa(bsg_diffnet* h, const StackPlan& plan, int t_uniform, TailArgs& a, float* x, int B, int T, hipStream_t st) {
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("BSG_H2_TAIL"); env = e ? atoi(e) : 1; }
-  const bool h2_tail = plan.ragged || (env && h->tail_s && h->M <= 96);
+  const bool h2_tail = plan.ragged || (dn_switches().h2_tail && h->tail_s && h->M <= 96);
   if (h2_tail && (plan.form == STACK_H2 || plan.form == STACK_H2Q)) {
-    const size_t off = (size_t)h->row_off * C * T;
-    a.x = x; a.xa_next = h->xa + off;
-    a.b_skip = h->b_skip; a.b_fin = h->b_fin96; a.b_in = h->b_in;
-    a.B = B; a.T = T; a.M = h->M; a.tiles_per_row = cdiv(T, 64);
-    a.ws_s = h->tail_s; a.wo_s = h->tail_s + 2 * C * C; a.wi_s = h->tail_s + 2 * C * C + 2 * 96 * C; a.tail_scale = h->tail_scale;
+    tail_fields(h, a, plan.row0, 64, true, x, B, T);
     return run_layers(h, plan, nullptr, t_uniform, B, T, st, &a);
   }
   TRY(run_layers(h, plan, nullptr, t_uniform, B, T, st));
   if (h2_tail && plan.form == STACK_PART) {
     // behind a part launch: the tail on the 16-bit matrix pipe too (step_tail_h2_kernel; BSG_H2_TAIL=0: the fp32-pipe tail)
-    const size_t off = (size_t)h->row_off * C * T;
-    a.skip = h->skip + off; a.skip_h = nullptr;
-    a.x = x; a.xa_next = h->xa + off;
-    a.b_skip = h->b_skip; a.b_fin = h->b_fin96; a.b_in = h->b_in;
-    a.B = B; a.T = T; a.M = h->M; a.tiles_per_row = cdiv(T, 32);
-    a.ws_s = h->tail_s; a.wo_s = h->tail_s + 2 * C * C; a.wi_s = h->tail_s + 2 * C * C + 2 * 96 * C; a.tail_scale = h->tail_scale;
+    a.skip = h->skip + (size_t)plan.row0 * C * T; a.skip_h = nullptr;
+    tail_fields(h, a, plan.row0, 32, true, x, B, T);
     a.status = h->flags + h->flags_cap;
     return launch_step_tail_h2(a, st);
   }
-  return launch_tail(h, a, x, B, T, st);
+  return launch_tail(h, plan, a, x, B, T, st);
 }
 
-struct SubBatch { int off, B; hipStream_t st; StackPlan plan; };
+struct SubBatch { int B; hipStream_t st; StackPlan plan; };   // rows [plan.row0, plan.row0 + B) of the batch on stream st
 
 // Two half-batches on two streams.  One launch per layer puts all workgroups of the chip in the same phase (they stage, hit
 // the gate and drain together, and the younger of the two workgroups of a CU finishes alone); two independent launch chains
 // drift apart and fill each other's gaps: measured 239.6 -> 226.5 ms per 100 steps at B=16, T=1000 (+5.8 %), +4.0 % at B=32,
 // +9.9 % at B=12, +1.2 % at B=64, +4 % for the bf16 form at B=64; four chains are worse (a CU only holds two of these
 // workgroups).  On one of the boxes measured the two chains brought no gain (and no loss).  BSG_DUAL=0 disables.
-// Returns the number of sub-batches (1 or 2) and, for 2, forks the second stream off `st` and plans each half in the launch state it
-// runs under.  `plan`: the whole batch's.
+// Returns the number of sub-batches (1 or 2) and, for 2, forks the second stream off `st` and plans each half for what it is (PlanScope).
+// `plan`: the whole batch's.
 static int dual_fork(bsg_diffnet* h, const StackPlan& plan, int B, int T, hipStream_t st, SubBatch (&subs)[2]) {
-  static int dual_env = -1;
-  if (dual_env < 0) { const char* e = getenv("BSG_DUAL"); dual_env = e ? atoi(e) : 1; }
-  subs[0] = SubBatch{0, B, st, plan};
-  subs[1] = SubBatch{0, 0, nullptr, StackPlan{}};
+  const int dual_env = dn_switches().dual, split_env = dn_switches().split;
+  subs[0] = SubBatch{B, st, plan};
+  subs[1] = SubBatch{0, nullptr, StackPlan{}};
   const long long tiles = (long long)B * cdiv(T, 32);
   const bool big = tiles > h->num_cus;
   // 129..256 tiles (B = 5..8): two chains of channel-split launches (each workgroup half the matrix work, two per CU, one of each
   // chain) instead of one chain of 16-wave workgroups
   // (measured per 100 steps at T=1000: B=5 130.5 -> 105.9 ms, B=6 133.5 -> 120.4, B=8 135.9 -> 133.8; BSG_DUAL=2: big batches only)
   // 65..128 tiles (B = 3, 4): two chains of 4-way split launches: B=3 89.0 -> 83.8 ms, B=4 93.3 -> 90.6
-  bool small = dual_env != 2 && !big && 4 * tiles > h->num_cus && h->compute == BSG_COMPUTE_F32 && split_env() && !h->split_off;
+  bool small = dual_env != 2 && !big && 4 * tiles > h->num_cus && h->compute == BSG_COMPUTE_F32 && split_env && !h->split_off;
   if (small) {
     // two chains of split launches share CUs (un-padded LDS): all workgroups of BOTH launches must be resident at once, or a
     // polling workgroup could wait for a partner that cannot start.  Per half: parts x tiles workgroups of 1024/parts threads.
@@ -2315,7 +2295,7 @@ static int dual_fork(bsg_diffnet* h, const StackPlan& plan, int B, int T, hipStr
     bool ok = true;
     for (int half = 0; half < 2; ++half) {
       const long long th = (long long)(half ? B - B / 2 : B / 2) * cdiv(T, 32);
-      const int parts = 4 * th <= h->num_cus && split_env() != 2 ? 4 : 2 * th <= h->num_cus ? 2 : 0;
+      const int parts = 4 * th <= h->num_cus && split_env != 2 ? 4 : 2 * th <= h->num_cus ? 2 : 0;
       int occ = parts == 4 ? h->occ4s : h->occ2s;
       const int cap = parts == 4 ? 3 : 2;   // 48 KB of LDS each -> 3 per CU; 8 waves of 128 VGPRs -> 2 per CU
       if (occ > cap) occ = cap;
@@ -2333,20 +2313,17 @@ static int dual_fork(bsg_diffnet* h, const StackPlan& plan, int B, int T, hipStr
       return 1;
   }
   if (hipEventRecord(h->ev_fork, st) != hipSuccess || hipStreamWaitEvent(h->st2, h->ev_fork, 0) != hipSuccess) return 1;
-  h->no_split = big;
-  h->split_small_lds = small;
-  subs[0] = SubBatch{0, B / 2, st, plan_stack(h, B / 2, T, st)};
-  subs[1] = SubBatch{B / 2, B - B / 2, h->st2, plan_stack(h, B - B / 2, T, h->st2)};
+  const PlanScope half = big ? PLAN_HALF_BIG : PLAN_HALF_SMALL;
+  subs[0] = SubBatch{B / 2, st, plan_stack(h, B / 2, T, st, half)};
+  subs[1] = SubBatch{B - B / 2, h->st2, plan_stack(h, B - B / 2, T, h->st2, half)};
+  subs[1].plan.row0 = B / 2;
   return 2;
 }
 
 // joins the second stream back into `st` (also after an error, so that the caller's stream stays ordered after everything
-// that was enqueued on the second one) and restores the handle's launch state
+// that was enqueued on the second one) and records the call's chain count
 static int dual_join(bsg_diffnet* h, int n_sub, hipStream_t st, int rc) {
   h->last_chains = n_sub == 2 ? 2 : 1;
-  h->row_off = 0;
-  h->no_split = false;
-  h->split_small_lds = false;
   if (n_sub == 2) {
     hipError_t e1 = hipEventRecord(h->ev_join, h->st2);
     hipError_t e2 = hipStreamWaitEvent(st, h->ev_join, 0);
@@ -2371,8 +2348,7 @@ extern "C" int bsg_ddpm_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
   const long long n = (long long)B * h->M * T;
   BSG_REQUIRE(n % 4 == 0, "ddpm_sample: B*M*T must be a multiple of 4");
   TRY(ragged_enter(h, st, "ddpm_sample"));
-  RaggedScope ragged_scope(h);
-  const StackPlan plan = plan_stack(h, B, T, st);
+  const StackPlan plan = plan_stack(h, B, T, st, h->ragged ? PLAN_RAGGED : PLAN_WHOLE);
   TRY(cond_layout_for(h, plan, st));
   const long long n4 = n / 4;
   const unsigned long long quad0 = (unsigned long long)row0 * h->M * T / 4;
@@ -2392,23 +2368,23 @@ extern "C" int bsg_ddpm_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
   // fused loop: [in-projection once] -> per step: 20 residual layers -> step_tail_kernel (skip projection, output
   // projection, sampler update, next step's in-projection)
   SubBatch subs[2];
-  const int n_sub = n_steps > 0 && !h->rg_active ? dual_fork(h, plan, B, T, st, subs) : 1;
-  if (n_sub == 1) subs[0] = SubBatch{0, B, st, plan};
+  const int n_sub = n_steps > 0 && !plan.ragged ? dual_fork(h, plan, B, T, st, subs) : 1;
+  if (n_sub == 1) subs[0] = SubBatch{B, st, plan};
   int rc = BSG_OK;
   for (int u = 0; u < n_sub && rc == BSG_OK; ++u)
-    rc = conv1x1(h->w_in, h->b_in, x + (size_t)subs[u].off * h->M * T, h->xa + (size_t)subs[u].off * C * T, C, h->M, subs[u].B, T, ACT_RELU,
-                 subs[u].st);
+    rc = conv1x1(h->w_in, h->b_in, x + (size_t)subs[u].plan.row0 * h->M * T, h->xa + (size_t)subs[u].plan.row0 * C * T, C, h->M, subs[u].B,
+                 T, ACT_RELU, subs[u].st);
   for (int k = 0; k < n_steps && rc == BSG_OK; ++k) {
     const int i = t_start - k;
     for (int u = 0; u < n_sub && rc == BSG_OK; ++u) {
-      h->row_off = subs[u].off;
+      const size_t mo = (size_t)subs[u].plan.row0 * h->M * T;   // this half's first element of x
       TailArgs a{};
-      a.noise = noise ? noise + (long long)k * n + (long long)subs[u].off * h->M * T : nullptr;
+      a.noise = noise ? noise + (long long)k * n + (long long)mo : nullptr;
       a.k = StepCoef{s->sqrt_recip_alphas_cumprod[i], s->sqrt_recipm1_alphas_cumprod[i], s->posterior_mean_coef1[i],
                      s->posterior_mean_coef2[i], s->sigma[i]};
-      a.seed = seed; a.quad_row0 = (unsigned long long)(row0 + subs[u].off) * h->M * T; a.stream = (unsigned)(i + 1);
+      a.seed = seed; a.quad_row0 = (unsigned long long)(row0 + subs[u].plan.row0) * h->M * T; a.stream = (unsigned)(i + 1);
       a.do_head = k + 1 < n_steps;
-      rc = step_from_xa(h, subs[u].plan, i, a, x + (size_t)subs[u].off * h->M * T, subs[u].B, T, subs[u].st);
+      rc = step_from_xa(h, subs[u].plan, i, a, x + mo, subs[u].B, T, subs[u].st);
     }
   }
   rc = dual_join(h, n_sub, st, rc);
@@ -2429,7 +2405,9 @@ extern "C" int bsg_diffnet_debug_stamps(bsg_diffnet* h, int32_t layer, const flo
   BSG_REQUIRE(x_in && t && x_out && skip && stamps && x_in != x_out, "diffnet_debug_stamps: null or aliased argument");
   BSG_REQUIRE(layer >= 0 && layer < h->L, "diffnet_debug_stamps: layer %d out of range", layer);
   if (h->compute == BSG_COMPUTE_F32) TRY(ensure_cond_rows(h, (hipStream_t)stream));
-  return launch_layer(h, layer, x_in, (const long long*)t, 0, x_out, skip, B, T, (hipStream_t)stream, (unsigned long long*)stamps);
+  StackPlan plan;
+  plan_layer(h, plan, B, T, PLAN_WHOLE, true);   // stamps: the un-split kernel
+  return launch_layer(h, plan, layer, x_in, (const long long*)t, 0, x_out, skip, B, T, (hipStream_t)stream, (unsigned long long*)stamps);
 }
 
 extern "C" int bsg_diffnet_status(bsg_diffnet* h, int32_t* handoff_timeouts) {
@@ -2482,9 +2460,12 @@ extern "C" int bsg_diffnet_uses_handoffs(bsg_diffnet* h, int32_t B, int32_t T, i
     *uses = 1;
     return BSG_OK;
   }
-  // conservative: any launch shape for which a channel-split (pair / 4-way) or the stack launch may be chosen
+  // The stack launch: the whole batch's plan says it.  The channel-split (pair / 4-way) launches: conservative, any shape of at most one
+  // tile per CU while they are on.  That is more than the plan's split2 / split4: in the 16-wave window the whole batch's per-layer form
+  // hands nothing over, but a sampler call runs it as two half-batch chains of split launches (dual_fork), and a handle asked before
+  // prepare allocated the exchange scratch has no split form yet.
   const long long tiles = (long long)B * cdiv(T, 32);
-  const bool split = h->compute == BSG_COMPUTE_F32 && use_wino() && split_env() && !h->split_off && h->num_cus && tiles <= h->num_cus;
+  const bool split = h->compute == BSG_COMPUTE_F32 && use_wino() && dn_switches().split && !h->split_off && h->num_cus && tiles <= h->num_cus;
   *uses = (split || plan_stack(h, B, T, nullptr).form != STACK_NONE) ? 1 : 0;
   return BSG_OK;
 }
@@ -2653,6 +2634,15 @@ extern "C" int bsg_philox_normal(float* x, int64_t n, uint64_t seed, uint32_t st
   return BSG_OK;
 }
 
+// the multistep blend of the newest noise prediction with n_hist older ones (p_sample_plms :168-201): 0: the prediction itself,
+// 1: (3 e0 - e1) / 2, 2: (23 e0 - 16 e1 + 5 e2) / 12, 3: (55 e0 - 59 e1 + 37 e2 - 9 e3) / 24
+static void plms_blend(int n_hist, PlmsCoef& c) {
+  if (n_hist <= 0) { c.inv = 1.f; }
+  else if (n_hist == 1) { c.w0 = 3.f; c.inv = 2.f; }
+  else if (n_hist == 2) { c.w0 = 23.f; c.w1 = -16.f; c.w2 = 5.f; c.inv = 12.f; }
+  else { c.w0 = 55.f; c.w1 = -59.f; c.w2 = 37.f; c.w3 = -9.f; c.inv = 24.f; }
+}
+
 extern "C" int bsg_plms_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, int32_t K_step, int32_t interval, int32_t B,
                                int32_t T, void* stream) {
   GuardScope guard_scope(h ? &h->guard : nullptr);
@@ -2665,13 +2655,12 @@ extern "C" int bsg_plms_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
   const size_t n = (size_t)B * h->M * T;
   BSG_REQUIRE(h->xpred, "plms_sample: history buffers missing (bsg_diffnet_prepare allocates them)");
   TRY(ragged_enter(h, st, "plms_sample"));
-  RaggedScope ragged_scope(h);
-  const StackPlan plan = plan_stack(h, B, T, st);
+  const StackPlan plan = plan_stack(h, B, T, st, h->ragged ? PLAN_RAGGED : PLAN_WHOLE);
   TRY(cond_layout_for(h, plan, st));
   const dim3 grid(cdiv((long long)n, 256)), block(256);
   // the unfused update (first iteration); ragged: on each row's own frames only
   auto plms_step = [&](const float* xi, float* xo, const float* e0, const float* e1, const float* e2, const float* e3, const PlmsCoef& k) {
-    if (h->rg_active)
+    if (plan.ragged)
       hipLaunchKernelGGL(plms_step_ragged_kernel, dim3(cdiv(T, 256), h->M, B), dim3(256), 0, st, xi, xo, e0, e1, e2, e3, k, (const int*)h->rg_dev, h->M, T);
     else
       hipLaunchKernelGGL(plms_step_kernel, grid, block, 0, st, xi, xo, e0, e1, e2, e3, k, (long long)n);
@@ -2693,17 +2682,14 @@ extern "C" int bsg_plms_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
       // fused iteration: h->xa already holds the in-projection of x (left by the previous iteration); the tail projects the skip
       // sum to eps, stores it to the history slot, applies the multistep update to x and projects the new x for the next one
       if (n_sub == 0) {   // the first fused iteration forks the two half-batch chains (not for a ragged batch: one chain of its launch groups)
-        if (h->rg_active) { subs[0] = SubBatch{0, B, st, plan}; n_sub = 1; }
+        if (plan.ragged) { subs[0] = SubBatch{B, st, plan}; n_sub = 1; }
         else n_sub = dual_fork(h, plan, B, T, st, subs);
       }
       for (int u = 0; u < n_sub && rc == BSG_OK; ++u) {
-        const size_t mo = (size_t)subs[u].off * h->M * T;
-        h->row_off = subs[u].off;
+        const size_t mo = (size_t)subs[u].plan.row0 * h->M * T;
         TailArgs a{};
         a.plms_hist = n_hist; a.pk = c; a.e_new = e_new + mo; a.h1 = hist[0] + mo; a.h2 = hist[1] + mo; a.h3 = hist[2] + mo;
-        if (n_hist == 1) { a.pk.w0 = 3.f; a.pk.inv = 2.f; }
-        else if (n_hist == 2) { a.pk.w0 = 23.f; a.pk.w1 = -16.f; a.pk.w2 = 5.f; a.pk.inv = 12.f; }
-        else { a.pk.w0 = 55.f; a.pk.w1 = -59.f; a.pk.w2 = 37.f; a.pk.w3 = -9.f; a.pk.inv = 24.f; }
+        plms_blend(n_hist, a.pk);
         a.do_head = i - interval >= 0;
         rc = step_from_xa(h, subs[u].plan, i, a, x + mo, subs[u].B, T, subs[u].st);
       }
@@ -2713,29 +2699,20 @@ extern "C" int bsg_plms_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
       continue;
     }
     TRY(forward_impl(h, plan, x, nullptr, i, e_new, B, T, st));
+    plms_blend(n_hist, c);
     if (n_hist == 0) {
-      c.inv = 1.f;
       // ragged: the predictor below writes x_pred on each row's frames only; its padding takes x's (finite, the caller's), which the
       // input projection of the second evaluation reads
-      if (h->rg_active) BSG_HIP(hipMemcpyAsync(h->xpred, x, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+      if (plan.ragged) BSG_HIP(hipMemcpyAsync(h->xpred, x, n * sizeof(float), hipMemcpyDeviceToDevice, st));
       plms_step((const float*)x, h->xpred, (const float*)e_new,
                          (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, c);
       TRY(forward_impl(h, plan, h->xpred, nullptr, ip, h->eps, B, T, st));
       c.w0 = 1.f; c.inv = 2.f;
       plms_step((const float*)x, x, (const float*)e_new, (const float*)h->eps,
                          (const float*)nullptr, (const float*)nullptr, c);
-    } else if (n_hist == 1) {
-      c.w0 = 3.f; c.inv = 2.f;
-      plms_step((const float*)x, x, (const float*)e_new, (const float*)hist[0],
-                         (const float*)nullptr, (const float*)nullptr, c);
-    } else if (n_hist == 2) {
-      c.w0 = 23.f; c.w1 = -16.f; c.w2 = 5.f; c.inv = 12.f;
-      plms_step((const float*)x, x, (const float*)e_new, (const float*)hist[0],
-                         (const float*)hist[1], (const float*)nullptr, c);
     } else {
-      c.w0 = 55.f; c.w1 = -59.f; c.w2 = 37.f; c.w3 = -9.f; c.inv = 24.f;
-      plms_step((const float*)x, x, (const float*)e_new, (const float*)hist[0],
-                         (const float*)hist[1], (const float*)hist[2], c);
+      plms_step((const float*)x, x, (const float*)e_new, (const float*)hist[0], n_hist >= 2 ? (const float*)hist[1] : nullptr,
+                n_hist >= 3 ? (const float*)hist[2] : nullptr, c);
     }
     BSG_LAUNCH_CHECK();
     if (fused && i - interval >= 0) TRY(conv1x1(h->w_in, h->b_in, x, h->xa, C, h->M, B, T, ACT_RELU, st));   // for the fused iterations
@@ -2758,11 +2735,8 @@ extern "C" int bsg_plms_step(const float* x, float* x_out, const float* e0, cons
   PlmsCoef c{};
   c.a_t = s->alphas_cumprod[t];
   c.a_prev = s->alphas_cumprod[t_prev];
-  c.inv = 1.f;
   if (n_hist == 1 && avg) { c.w0 = 1.f; c.inv = 2.f; }
-  else if (n_hist == 1) { c.w0 = 3.f; c.inv = 2.f; }
-  else if (n_hist == 2) { c.w0 = 23.f; c.w1 = -16.f; c.w2 = 5.f; c.inv = 12.f; }
-  else if (n_hist == 3) { c.w0 = 55.f; c.w1 = -59.f; c.w2 = 37.f; c.w3 = -9.f; c.inv = 24.f; }
+  else plms_blend(n_hist, c);
   hipLaunchKernelGGL(plms_step_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, x, x_out, e0, n_hist >= 1 ? e1 : nullptr,
                      n_hist >= 2 ? e2 : nullptr, n_hist >= 3 ? e3 : nullptr, c, (long long)n);
   BSG_LAUNCH_CHECK();

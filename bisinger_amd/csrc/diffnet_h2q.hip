@@ -683,9 +683,9 @@ static int h2q_launch(const StackArgs& p, const TailArgs* tail, hipStream_t st) 
   const dim3 grid(8 * cdiv(p.n_tiles, 8)), block(512);
   const TailArgs a = tail ? *tail : TailArgs{};
   const size_t lds = h2_lds(NCT);
-  static int diag = -1;   // BSG_H2Q_DIAG=1 / 2 / 3 / 4 / 5 / 6: timing experiments on the launches of 64-frame tiles (1: no weight reloads, 2: no operand reads either; 3: a stamp per pass;
-                          // round 6, the buckets outside the GEMM phases: 4: no conditioner-term loads, 5: a two-instruction gate, 6: no hand-off and no publish — all but 3: wrong results)
-  if (diag < 0) { const char* e = getenv("BSG_H2Q_DIAG"); diag = e ? atoi(e) : 0; }
+  // BSG_H2Q_DIAG=1 / 2 / 3 / 4 / 5 / 6: timing experiments on the launches of 64-frame tiles (1: no weight reloads, 2: no operand reads either; 3: a stamp per pass;
+  // round 6, the buckets outside the GEMM phases: 4: no conditioner-term loads, 5: a two-instruction gate, 6: no hand-off and no publish — all but 3: wrong results)
+  const int diag = dn_switches().h2q_diag;
   if constexpr (NCT == 2) {
     if (diag) {
       auto go = [&](auto kt, auto kn) {
@@ -704,9 +704,7 @@ static int h2q_launch(const StackArgs& p, const TailArgs* tail, hipStream_t st) 
       return BSG_OK;
     }
   }
-  static int fair = -1;   // BSG_H2Q_FAIR=0: no time-sliced issue priority between the two waves of a SIMD
-  if (fair < 0) { const char* e = getenv("BSG_H2Q_FAIR"); fair = e ? atoi(e) : 1; }
-  if (!fair) {
+  if (!dn_switches().h2q_fair) {   // BSG_H2Q_FAIR=0: no time-sliced issue priority between the two waves of a SIMD
     static bool attr = false;
     if (!attr) {
       BSG_HIP(hipFuncSetAttribute((const void*)residual_stack_q_kernel<false, false, NCT, 0, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

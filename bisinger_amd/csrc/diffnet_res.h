@@ -193,5 +193,37 @@ __device__ __forceinline__ void stf(float v, rsrc_t r, int voff, int soff) {
 // uniform part of acc_row(): register r of a 32x32 accumulator covers row (r&3) + 8*(r>>2) (+ 4 for lanes >= 32)
 __device__ __forceinline__ constexpr int acc_row0(int r) { return (r & 3) + 8 * (r >> 2); }
 
+// The run-time switches of the denoiser (diffnet.hip, diffnet_h2q.hip; environment), read on first use and never again.  Host side only.
+struct DnSwitches {
+  int gemm_h2w = env_int("BSG_GEMM_H2W", 1);                  // 0: the conditioner projections on gemm_split_kernel (operands split while staged) instead of the pre-split GEMM
+  int cond_quad = env_int("BSG_COND_QUAD", 1);                // 0: prepare writes no channel-quad copy of the conditioner term (nor under BSG_H2_Q=0)
+  int cond_bf16_direct = env_int("BSG_COND_BF16_DIRECT", 1);  // 0: bf16 configuration: the term as fp32 rows first, converted to bf16 quads by 20 launches
+  int cond_rows = env_int("BSG_COND_ROWS", 0);                // 1: prepare writes the row layout of the term as well as the quads (round 5's way)
+  int wino = env_int("BSG_WINO", 2);                          // GEMM1 of the residual block: 2: Winograd F(2,3) kernels and the F(4,3) stack launch; 1: F(2,3) only; 0: the direct K=768 form
+  int split = env_int("BSG_SPLIT", 1);                        // 0: no channel-split / 16-wave launches; 2: no 4-way split; 3: pair form only (A/B measurements)
+  int stack_bf16 = env_int("BSG_STACK_BF16", 1);              // 0: bf16 configuration on per-layer launches
+  int h2 = env_int("BSG_H2", 1);                              // 0: no split-fp16 launches (the kernels of the fp32 matrix pipe)
+  int h2_nct = env_int("BSG_H2_NCT", 0);                      // 1 / 2: force 32- / 64-frame tiles of the split-fp16 stack launch (and no part forms)
+  int h2_part = env_int("BSG_H2_PART", 1);                    // 0: no part forms
+  int h2_quad = env_int("BSG_H2_QUAD", 1);                    // 0: no quads of 32-frame tiles
+  int h2_quad64 = env_int("BSG_H2_QUAD64", 1);                // 0: no quads of 64-frame tiles
+  int h2_pair64 = env_int("BSG_H2_PAIR64", 1);                // 0: no pairs of 64-frame tiles
+  int h2_q = env_int("BSG_H2_Q", 1);                          // 0: the 32-row stack launch (residual_stack_h2_kernel) instead of the 16-row one
+  int stack43 = env_int("BSG_STACK43", 1);                    // 0: no F(4,3) stack launch; 2: at any shape (tests)
+  int h2_tail = env_int("BSG_H2_TAIL", 1);                    // 0: the step tail as its own launch behind a split-fp16 stack / part launch
+  int dual = env_int("BSG_DUAL", 1);                          // 0: no half-batch chains; 2: for big batches only
+  int debug_wrap_r04 = env_int("BSG_DEBUG_WRAP_R04", 0);      // 1: round 4's behaviour (only a PART launch zeroes the part flags at a wrap): the negative control of tests/test_gpu_handoff.py
+  int h2q_diag = env_int("BSG_H2Q_DIAG", 0);                  // 1 .. 6: timing experiments on the 16-row launches of 64-frame tiles (diffnet_h2q.hip h2q_launch; all but 3: wrong results)
+  int h2q_fair = env_int("BSG_H2Q_FAIR", 1);                  // 0: no time-sliced issue priority between the two waves of a SIMD
+};
+inline const DnSwitches& dn_switches() { static const DnSwitches s; return s; }
+
+// Three switches are NOT cached: they are read again on every call, because tests flip them between calls of one process
+// (monkeypatch.setenv of BSG_NO_FUSED_TAIL in tests/test_gpu_sampler.py and of BSG_TAIL_BF16 in tests/test_gpu_bf16.py); BSG_STAMP_MODE
+// (tools/stack_stamps.py, tools/wave_stamps.py) has always been read per stamped launch and stays so.
+inline bool live_no_fused_tail() { return getenv("BSG_NO_FUSED_TAIL") != nullptr; }   // set to anything: the samplers' unfused loops
+inline bool live_tail_bf16() { return env_int("BSG_TAIL_BF16", 1) != 0; }              // 0: bf16 configuration with the fp32 step tail
+inline int live_stamp_mode() { return env_int("BSG_STAMP_MODE", 0); }                  // stamp contents of the debug stack launch (0 | 2 | 3 | 5)
+
 
 }  // namespace bsg

@@ -39,7 +39,9 @@ def _model():
     return m.cuda().eval()
 
 
-@pytest.mark.parametrize('B', [1, 16])     # T=320: 10 tiles (4-way split, one chain) / 160 tiles (two chains of pair-split launches)
+@pytest.mark.parametrize('B', [1, 16])     # T=320: 10 / 160 tiles of 32 frames.  Which launch each runs is read from last_path below (by default
+                                           # B=16 takes the split-fp16 stack launch; its two chains of pair-split launches are what
+                                           # tests/test_gpu_dual_small.py runs, under BSG_H2=0 BSG_WINO=1)
 def test_injected_giveup_self_heals_in_the_same_call(B):
     T = 320
     rs = np.random.RandomState(7)
