@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'lib', 'libbisinger_hip.so')
 if os.environ.get('BSG_LIB'):      # development: an alternative build of the same ABI (kernel experiments)
     LIB_PATH = os.environ['BSG_LIB']
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 class BsgError(RuntimeError):
@@ -26,6 +26,14 @@ class Fs2Cfg(Structure):
     _fields_ = [(n, c_int32) for n in ('hidden_size', 'vocab', 'enc_layers', 'dec_layers', 'num_heads',
                                        'enc_ffn_kernel_size', 'dec_ffn_kernel_size', 'out_dims', 'dur_layers',
                                        'dur_kernel', 'spk_rows', 'esm_heads', 'n_pos', 'n_rel')]
+
+
+class Fs2XCfg(Structure):
+    """bsg_fs2_cfg (ABI v16): the old fields, the front and the pitch adaptor."""
+    _fields_ = [('base', Fs2Cfg)] + [(n, c_int32) for n in ('front', 'use_pitch_embed', 'pitch_layers', 'pitch_kernel', 'use_uv', 'n_pitch_pos')]
+
+
+FS2_FRONT_MIDI, FS2_FRONT_PLAIN = 0, 1
 
 
 class HifiganCfg(Structure):
@@ -128,6 +136,11 @@ _SIGS = {
     'bsg_hifigan_forward_nsf': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     'bsg_hifigan_last_path': (c_char_p, [c_void_p]),
     'bsg_fs2midi_last_path': (c_char_p, [c_void_p]),
+    'bsg_fs2_n_weights': (c_int32, [POINTER(Fs2XCfg)]),
+    'bsg_fs2_create': (c_int32, [POINTER(c_void_p), POINTER(Fs2XCfg), POINTER(c_void_p), c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'bsg_fs2_encode_plain': (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'bsg_fs2_decode': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'bsg_fftden_last_path': (c_char_p, [c_void_p]),
     'bsg_fs2midi_debug_poison_workspace': (c_int32, [c_void_p, c_void_p]),
     'bsg_fftden_debug_poison_workspace': (c_int32, [c_void_p, c_void_p]),

@@ -923,8 +923,8 @@ __global__ void add_spk_kernel(const float* __restrict__ enc, const long long* _
   const int lane = threadIdx.x & 63;
   const int b = (int)(row / Tt);
   f32x4 e = reinterpret_cast<const f32x4*>(enc + row * H)[lane];
-  const f32x4 s = reinterpret_cast<const f32x4*>(Espk + spk_id[b] * H)[lane];
-  e = (e + s) * keep[row];
+  if (Espk) e = e + reinterpret_cast<const f32x4*>(Espk + spk_id[b] * H)[lane];   // (no speaker table: the plain front's spk_embed = 0)
+  e = e * keep[row];
   reinterpret_cast<f32x4*>(out + row * H)[lane] = e;
 }
 
@@ -940,10 +940,10 @@ __global__ void gather_frames_kernel(const float* __restrict__ enc, const long l
   const long long ph = mel2ph[row];
   f32x4 e = {0.f, 0.f, 0.f, 0.f};
   if (ph > 0 && ph <= Tt) e = reinterpret_cast<const f32x4*>(enc + ((long long)b * Tt + (ph - 1)) * H)[lane];
-  const f32x4 s = reinterpret_cast<const f32x4*>(Espk + spk_id[b] * H)[lane];
-  const f32x4 st = reinterpret_cast<const f32x4*>(Estyle + style_id[b] * H)[lane];
+  if (Espk) e = e + reinterpret_cast<const f32x4*>(Espk + spk_id[b] * H)[lane];       // (the plain front: no style row, possibly no speaker table)
+  if (Estyle) e = e + reinterpret_cast<const f32x4*>(Estyle + style_id[b] * H)[lane];
   const float kp = ph > 0 ? 1.f : 0.f;
-  e = ((e + s) + st) * kp;
+  e = e * kp;
   reinterpret_cast<f32x4*>(out + row * H)[lane] = e;
 }
 
@@ -1033,6 +1033,147 @@ __global__ void mask_rows_by_index_kernel(float* __restrict__ x, const long long
   if (idx[i / width] <= 0) x[i] = 0.f;
 }
 
+// ---- plain FastSpeech2 front (FastspeechEncoder.forward_embedding, tts_modules.py:342-349) -------------------------------------------
+// x = (sqrt(H) * E_tok[txt] + table[pos]) * keep with pos = the count of non-pad tokens up to and including this one (make_positions of the
+// token ids, utils/__init__.py:146-158; pad id 0 -> row 0 of the table, which is zero) and keep = (txt != 0) (FFTBlocks :297).  One wave per
+// token: it counts the non-pad tokens before it with ballots over 64-token pieces of its utterance (8-byte reads, T_txt is a few hundred).
+__global__ void token_front_kernel(const long long* __restrict__ txt, const float* __restrict__ Etok, const float* __restrict__ table,
+                                   float* __restrict__ x, float* __restrict__ keep, long long rows, int Tt, float scale, int n_pos, int vocab) {
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int lane = threadIdx.x & 63;
+  const long long b = row / Tt;
+  const int j = (int)(row - b * Tt);
+  const long long* __restrict__ tb = txt + b * Tt;
+  int cnt = 0;
+  for (int t0 = 0; t0 <= j; t0 += 64) {
+    const int t = t0 + lane;
+    cnt += __popcll(__ballot(t <= j && tb[t] != 0));
+  }
+  long long tok = tb[j];
+  const float kp = tok != 0 ? 1.f : 0.f;
+  int p = tok != 0 ? cnt : 0;
+  p = p < n_pos ? p : n_pos - 1;
+  tok = tok < 0 ? 0 : tok < vocab ? tok : vocab - 1;   // an id outside the table is clamped (torch raises): no read out of bounds
+  const f32x4 e = reinterpret_cast<const f32x4*>(Etok + tok * H)[lane];
+  const f32x4 pv = reinterpret_cast<const f32x4*>(table + (long long)p * H)[lane];
+  f32x4 o;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) o[c] = __fadd_rn(__fmul_rn(scale, e[c]), pv[c]) * kp;
+  reinterpret_cast<f32x4*>(x + row * H)[lane] = o;
+  if (lane == 0) keep[row] = kp;
+}
+
+// ---- frame-level pitch adaptor (FastSpeech2.add_pitch, fastspeech/fs2.py:201-234; PitchPredictor, tts_modules.py:224-237) -------------
+// pitch_inp[b,t] = (pad(enc)[b, mel2ph[b,t]] + spk[b]) * (mel2ph > 0)  (fs2.py:139); its first channel decides the position (make_positions
+// of xs[..., 0], tts_modules.py:230): one wave per utterance scans the frames in 64-frame pieces, as decoder_positions_kernel does.
+// a speaker / style id outside its table is clamped (torch raises): the new kernels never read out of bounds
+__device__ __forceinline__ long long clamp_id(long long i, int n) { return i < 0 ? 0 : i < n ? i : n - 1; }
+__device__ __forceinline__ float pitch_inp0(const float* __restrict__ enc, const long long* __restrict__ mel2ph, const float* __restrict__ spk,
+                                            long long b, long long row, int Tt) {
+  const long long ph = mel2ph[row];
+  float e = 0.f;
+  if (ph > 0 && ph <= Tt) e = enc[(b * Tt + (ph - 1)) * H];
+  if (spk) e = e + spk[0];
+  return e * (ph > 0 ? 1.f : 0.f);
+}
+__global__ void pitch_positions_kernel(const float* __restrict__ enc, const long long* __restrict__ mel2ph,
+                                       const long long* __restrict__ spk_id, const float* __restrict__ Espk, int* __restrict__ pos, int T,
+                                       int Tt, int spk_rows) {
+  const int b = blockIdx.x, lane = threadIdx.x;   // 64 threads
+  const float* spk = Espk ? Espk + clamp_id(spk_id[b], spk_rows) * H : nullptr;
+  int carry = 0;
+  for (int t0 = 0; t0 < T; t0 += 64) {
+    const int t = t0 + lane;
+    bool nz = false;
+    if (t < T) nz = pitch_inp0(enc, mel2ph, spk, b, (long long)b * T + t, Tt) != 0.f;
+    const unsigned long long bal = __ballot(nz);
+    const int pre = __popcll(bal & ((1ull << lane) - 1ull)) + (nz ? 1 : 0);
+    if (t < T) pos[(long long)b * T + t] = nz ? carry + pre : 0;
+    carry += __popcll(bal);
+  }
+}
+// x = pitch_inp + alpha * table[pos]: the predictor's input, one wave per frame.  Padded frames (pitch_inp == 0) take row 0 of the table (zero).
+__global__ void pitch_entry_kernel(const float* __restrict__ enc, const long long* __restrict__ mel2ph, const long long* __restrict__ spk_id,
+                                   const float* __restrict__ Espk, const int* __restrict__ pos, const float* __restrict__ table,
+                                   const float* __restrict__ alpha, float* __restrict__ x, long long rows, int T, int Tt, int n_pos, int spk_rows) {
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int lane = threadIdx.x & 63;
+  const long long b = row / T;
+  const long long ph = mel2ph[row];
+  f32x4 e = {0.f, 0.f, 0.f, 0.f};
+  if (ph > 0 && ph <= Tt) e = reinterpret_cast<const f32x4*>(enc + (b * Tt + (ph - 1)) * H)[lane];
+  if (Espk) e = e + reinterpret_cast<const f32x4*>(Espk + clamp_id(spk_id[b], spk_rows) * H)[lane];
+  e = e * (ph > 0 ? 1.f : 0.f);
+  int p = pos[row];
+  p = p < n_pos ? p : n_pos - 1;
+  const f32x4 pe = reinterpret_cast<const f32x4*>(table + (long long)p * H)[lane];
+  const float a = alpha[0];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) e[c] = __fadd_rn(e[c], __fmul_rn(a, pe[c]));
+  reinterpret_cast<f32x4*>(x + row * H)[lane] = e;
+}
+
+// f0_to_coarse (utils/pitch_utils.py:22-31) with the reference's fp32 operation order; a NaN (which the reference's own assert refuses) takes bin 1
+__device__ __forceinline__ long long f0_coarse_bin(float f0) {
+  const float mel_min = 77.75496616579426f;   // 1127 ln(1 + 50 / 700), rounded to fp32 as the reference's Python scalar is
+  const float mel_span = 986.6532669978451f;  // 1127 ln(1 + 1100 / 700) - mel_min
+  float m = __fmul_rn(1127.0f, logf(__fadd_rn(1.0f, __fdiv_rn(f0, 700.0f))));
+  if (m > 0.f) m = __fadd_rn(__fdiv_rn(__fmul_rn(__fsub_rn(m, mel_min), 254.0f), mel_span), 1.0f);
+  if (!(m > 1.0f)) m = 1.0f;
+  if (m > 255.0f) m = 255.0f;
+  return (long long)__fadd_rn(m, 0.5f);
+}
+
+// The adaptor's frame-level tail, one wave per frame (4 channels per lane):
+//   the LAST predictor layer's LayerNorm (eps 1e-12) of the ReLU-ed convolution `c`, Linear(256 -> 2) as two shuffle-reduced dots -> pitch_pred;
+//   f0 = supplied or pred[0], uv = supplied or pred[1] > 0 (use_uv);  f0_denorm = 2^f0, 0 where uv or padded;  bin = f0_to_coarse(f0_denorm);
+//   decoder_inp = (((pad(enc)[mel2ph] + pitch_embed[bin]) + spk) + style) * (mel2ph > 0)                              (fs2.py:142-146, midi :181-189)
+// pitch_pred, f0_denorm and bins may each be NULL.
+__global__ void pitch_tail_kernel(const float* __restrict__ c, const float* __restrict__ lnw, const float* __restrict__ lnb,
+                                  const float* __restrict__ lin_w, const float* __restrict__ lin_b, const float* __restrict__ f0_in,
+                                  const float* __restrict__ uv_in, int use_uv, const float* __restrict__ enc,
+                                  const long long* __restrict__ mel2ph, const long long* __restrict__ spk_id,
+                                  const long long* __restrict__ style_id, const float* __restrict__ Espk, const float* __restrict__ Estyle,
+                                  const float* __restrict__ Epitch, float* __restrict__ pitch_pred, float* __restrict__ f0_denorm,
+                                  long long* __restrict__ bins, float* __restrict__ out, long long rows, int T, int Tt, int spk_rows) {
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int lane = threadIdx.x & 63;
+  const long long b = row / T;
+  const f32x4 v = reinterpret_cast<const f32x4*>(c + row * H)[lane];
+  const float mean = wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.0f / H);
+  const float d0 = v[0] - mean, d1 = v[1] - mean, d2 = v[2] - mean, d3 = v[3] - mean;
+  const float var = wave_sum(d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3) * (1.0f / H);
+  const float rstd = 1.0f / sqrtf(var + 1e-12f);
+  const f32x4 wv = reinterpret_cast<const f32x4*>(lnw)[lane], bv = reinterpret_cast<const f32x4*>(lnb)[lane];
+  const f32x4 y = {d0 * rstd * wv[0] + bv[0], d1 * rstd * wv[1] + bv[1], d2 * rstd * wv[2] + bv[2], d3 * rstd * wv[3] + bv[3]};
+  const f32x4 w0 = reinterpret_cast<const f32x4*>(lin_w)[lane], w1 = reinterpret_cast<const f32x4*>(lin_w + H)[lane];
+  const float p0 = wave_sum(y[0] * w0[0] + y[1] * w0[1] + y[2] * w0[2] + y[3] * w0[3]) + lin_b[0];
+  const float p1 = wave_sum(y[0] * w1[0] + y[1] * w1[1] + y[2] * w1[2] + y[3] * w1[3]) + lin_b[1];
+  const long long ph = mel2ph[row];
+  const float f0 = f0_in ? f0_in[row] : p0;
+  const bool unvoiced = use_uv && (uv_in ? uv_in[row] > 0.f : p1 > 0.f);
+  float fd = exp2f(f0);
+  if (unvoiced || ph == 0) fd = 0.f;
+  const long long bin = f0_coarse_bin(fd);
+  if (lane == 0) {
+    // (the reference's f0[pitch_padding] = 0, fs2.py:230, writes through its view of pitch_pred when f0 is the predicted one: the
+    // returned pitch_pred[..., 0] is 0 on padded frames then, and untouched with a supplied f0)
+    if (pitch_pred) { pitch_pred[2 * row] = (!f0_in && ph == 0) ? 0.f : p0; pitch_pred[2 * row + 1] = p1; }
+    if (f0_denorm) f0_denorm[row] = fd;
+    if (bins) bins[row] = bin;
+  }
+  f32x4 e = {0.f, 0.f, 0.f, 0.f};
+  if (ph > 0 && ph <= Tt) e = reinterpret_cast<const f32x4*>(enc + (b * Tt + (ph - 1)) * H)[lane];
+  e = e + reinterpret_cast<const f32x4*>(Epitch + bin * H)[lane];
+  if (Espk) e = e + reinterpret_cast<const f32x4*>(Espk + clamp_id(spk_id[b], spk_rows) * H)[lane];
+  if (Estyle) e = e + reinterpret_cast<const f32x4*>(Estyle + clamp_id(style_id[b], 3) * H)[lane];
+  e = e * (ph > 0 ? 1.f : 0.f);
+  reinterpret_cast<f32x4*>(out + row * H)[lane] = e;
+}
+
 }  // namespace
 }  // namespace bsg
 
@@ -1061,7 +1202,12 @@ struct bsg_fs2midi {
   float *esm_in_w, *esm_in_b, *esm_out_w, *esm_out_b, *esm_f0w, *esm_f0b, *esm_f2w, *esm_f2b, *esm_ln1w, *esm_ln1b, *esm_ln2w, *esm_ln2b;
   H2wWeights p_esm_q, p_esm_kv, p_esm_out, p_esm_f0, p_esm_f2;   // the ESM's Linear layers as pre-split fragments (K and V projections as one product)
   float *enc_lnw, *enc_lnb, *Emidi, *Wdur, *bdur, *Eslur, *Elang, *Estyle;
-  float *dec_table, *rel_table;
+  float *dec_table, *rel_table;   // rel_table: the token-level position table (plain front: the sinusoidal table the tokens index)
+  // bsg_fs2_create (ABI v16): the front and the frame-level pitch adaptor; bsg_fs2midi_create leaves the defaults
+  int front = BSG_FS2_FRONT_MIDI;
+  int use_pitch = 0, pitch_layers = 0, pitch_kernel = 0, use_uv = 0, n_pitch_pos = 0;
+  float *Epitch = nullptr, *pit_alpha = nullptr, *pit_lin_w = nullptr, *pit_lin_b = nullptr, *pit_table = nullptr;
+  std::vector<float*> pit_conv, pit_convb, pit_lnw, pit_lnb;
   // workspace
   size_t cap_rows = 0, cap_scores = 0;
   float *w_x = nullptr, *w_a = nullptr, *w_b = nullptr, *w_qkv = nullptr, *w_ffn = nullptr, *w_keep = nullptr, *w_scores = nullptr;
@@ -1153,7 +1299,75 @@ static int load_fft_layers(bsg_fs2midi* h, std::vector<FftLayerW>& out, const vo
   return BSG_OK;
 }
 
-static int fs2_create_impl(bsg_fs2midi* h, const void* const* w, const float* dec_table, const float* rel_table, hipStream_t st) {
+// pitch_embed.weight, pitch_predictor.{pos_embed_alpha, conv.l.1.{weight,bias}, conv.l.3.{weight,bias}, linear.{weight,bias},
+// embed_positions._float_tensor}  (fastspeech/fs2.py:55-81, tts_modules.py:194-222)
+static int load_pitch(bsg_fs2midi* h, const void* const* w, int& i, hipStream_t st) {
+  const int L = h->pitch_layers;
+  TRY(fs2_copy(h, &h->Epitch, w[i++], (size_t)300 * H, st));
+  TRY(fs2_copy(h, &h->pit_alpha, w[i++], 1, st));
+  h->pit_conv.resize(L); h->pit_convb.resize(L); h->pit_lnw.resize(L); h->pit_lnb.resize(L);
+  for (int l = 0; l < L; ++l) {
+    TRY(fs2_conv(h, &h->pit_conv[l], w[i++], H, H, h->pitch_kernel, st));
+    TRY(fs2_copy(h, &h->pit_convb[l], w[i++], H, st));
+    TRY(fs2_copy(h, &h->pit_lnw[l], w[i++], H, st));
+    TRY(fs2_copy(h, &h->pit_lnb[l], w[i++], H, st));
+  }
+  TRY(fs2_copy(h, &h->pit_lin_w, w[i++], (size_t)2 * H, st));
+  TRY(fs2_copy(h, &h->pit_lin_b, w[i++], 2, st));
+  i++;  // pitch_predictor.embed_positions._float_tensor: placeholder buffer of the reference
+  return BSG_OK;
+}
+
+static int load_dur(bsg_fs2midi* h, const void* const* w, int& i, hipStream_t st) {
+  const bsg_fs2midi_cfg& c = h->cfg;
+  h->dur_conv.resize(c.dur_layers); h->dur_convb.resize(c.dur_layers); h->dur_lnw.resize(c.dur_layers); h->dur_lnb.resize(c.dur_layers);
+  for (int l = 0; l < c.dur_layers; ++l) {
+    TRY(fs2_conv(h, &h->dur_conv[l], w[i++], H, H, c.dur_kernel, st));
+    TRY(fs2_copy(h, &h->dur_convb[l], w[i++], H, st));
+    TRY(fs2_copy(h, &h->dur_lnw[l], w[i++], H, st));
+    TRY(fs2_copy(h, &h->dur_lnb[l], w[i++], H, st));
+  }
+  TRY(fs2_copy(h, &h->dur_lin_w, w[i++], H, st));
+  TRY(fs2_copy(h, &h->dur_lin_b, w[i++], 1, st));
+  return BSG_OK;
+}
+
+// The plain FastSpeech2 (fastspeech/fs2.py:24-89) in state_dict() order: encoder_embed_tokens, encoder.{layers, layer_norm, embed_tokens
+// (alias), embed_positions._float_tensor}, decoder.{pos_embed_alpha, embed_positions._float_tensor, layers, layer_norm}, mel_out,
+// [spk_embed_proj], dur_predictor, [pitch_embed, pitch_predictor]
+static int fs2_create_plain(bsg_fs2midi* h, const void* const* w, const float* dec_table, const float* tok_table, const float* pitch_table,
+                            hipStream_t st) {
+  const bsg_fs2midi_cfg& c = h->cfg;
+  int i = 0;
+  TRY(fs2_copy(h, &h->Etok, w[i++], (size_t)c.vocab * H, st));
+  TRY(load_fft_layers(h, h->enc, w + i, c.enc_layers, c.enc_ffn_kernel_size, st));
+  i += 10 * c.enc_layers;
+  TRY(fs2_copy(h, &h->enc_lnw, w[i++], H, st));
+  TRY(fs2_copy(h, &h->enc_lnb, w[i++], H, st));
+  i += 2;  // encoder.embed_tokens (alias of encoder_embed_tokens), encoder.embed_positions._float_tensor
+  TRY(fs2_copy(h, &h->dec_alpha, w[i++], 1, st));
+  i++;     // decoder.embed_positions._float_tensor
+  TRY(load_fft_layers(h, h->dec, w + i, c.dec_layers, c.dec_ffn_kernel_size, st));
+  i += 10 * c.dec_layers;
+  TRY(fs2_copy(h, &h->dec_lnw, w[i++], H, st));
+  TRY(fs2_copy(h, &h->dec_lnb, w[i++], H, st));
+  TRY(fs2_copy(h, &h->mel_w, w[i++], (size_t)c.out_dims * H, st));
+  TRY(fs2_copy(h, &h->mel_b, w[i++], c.out_dims, st));
+  if (c.spk_rows > 0) TRY(fs2_copy(h, &h->Espk, w[i++], (size_t)c.spk_rows * H, st));
+  TRY(load_dur(h, w, i, st));
+  if (h->use_pitch) TRY(load_pitch(h, w, i, st));
+  TRY(fs2_copy(h, &h->dec_table, dec_table, (size_t)c.n_pos * H, st));
+  TRY(fs2_copy(h, &h->rel_table, tok_table, (size_t)c.n_rel * H, st));
+  if (h->use_pitch) TRY(fs2_copy(h, &h->pit_table, pitch_table, (size_t)h->n_pitch_pos * H, st));
+  unsigned bad = 0;
+  BSG_HIP(hipMemcpyAsync(&bad, h->pack_bad, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  BSG_HIP(hipStreamSynchronize(st));
+  h->h2w_ok = bad == 0 && c.enc_ffn_kernel_size <= 17 && c.dec_ffn_kernel_size <= 17;
+  return BSG_OK;
+}
+
+static int fs2_create_impl(bsg_fs2midi* h, const void* const* w, const float* dec_table, const float* rel_table, hipStream_t st,
+                           const float* pitch_table = nullptr) {
   const bsg_fs2midi_cfg& c = h->cfg;
   int i = 0;
   TRY(fs2_copy(h, &h->Etok, w[i++], (size_t)c.vocab * H, st));
@@ -1175,6 +1389,7 @@ static int fs2_create_impl(bsg_fs2midi* h, const void* const* w, const float* de
   }
   TRY(fs2_copy(h, &h->dur_lin_w, w[i++], H, st));
   TRY(fs2_copy(h, &h->dur_lin_b, w[i++], 1, st));
+  if (h->use_pitch) TRY(load_pitch(h, w, i, st));
   TRY(fs2_copy(h, &h->esm_in_w, w[i++], (size_t)3 * H * H, st));
   TRY(fs2_copy(h, &h->esm_in_b, w[i++], 3 * H, st));
   TRY(fs2_copy(h, &h->esm_out_w, w[i++], (size_t)H * H, st));
@@ -1205,6 +1420,7 @@ static int fs2_create_impl(bsg_fs2midi* h, const void* const* w, const float* de
   TRY(fs2_copy(h, &h->Estyle, w[i++], (size_t)3 * H, st));
   TRY(fs2_copy(h, &h->dec_table, dec_table, (size_t)c.n_pos * H, st));
   TRY(fs2_copy(h, &h->rel_table, rel_table, (size_t)c.n_rel * H, st));
+  if (h->use_pitch) TRY(fs2_copy(h, &h->pit_table, pitch_table, (size_t)h->n_pitch_pos * H, st));
   unsigned bad = 0;
   BSG_HIP(hipMemcpyAsync(&bad, h->pack_bad, sizeof(unsigned), hipMemcpyDeviceToHost, st));
   BSG_HIP(hipStreamSynchronize(st));
@@ -1234,6 +1450,64 @@ extern "C" int bsg_fs2midi_create(bsg_fs2midi** out, const bsg_fs2midi_cfg* cfg,
   h->cfg = *cfg;
   int rc = guard_init(&h->guard, (hipStream_t)stream);
   if (rc == BSG_OK) rc = fs2_create_impl(h, dev_weights, dec_pos_table, rel_pos_table, (hipStream_t)stream);
+  if (rc != BSG_OK) {
+    bsg_fs2midi_destroy(h);
+    return rc;
+  }
+  *out = h;
+  return BSG_OK;
+}
+
+// every refusal of bsg_fs2_create / bsg_fs2_n_weights, before any device call
+static int fs2_cfg_check(const bsg_fs2_cfg* cfg, const char* who) {
+  BSG_REQUIRE(cfg, "%s: null config", who);
+  const bsg_fs2midi_cfg& b = cfg->base;
+  BSG_REQUIRE(cfg->front == BSG_FS2_FRONT_MIDI || cfg->front == BSG_FS2_FRONT_PLAIN, "%s: front=%d (0 = MIDI + ESM, 1 = plain)", who, cfg->front);
+  BSG_REQUIRE(b.hidden_size == H, "%s: hidden_size=%d; kernels are built for 256", who, b.hidden_size);
+  BSG_REQUIRE(b.num_heads > 0 && H % b.num_heads == 0 && (H / b.num_heads) % 4 == 0, "%s: num_heads=%d", who, b.num_heads);
+  BSG_REQUIRE(cfg->front == BSG_FS2_FRONT_PLAIN || b.esm_heads == 8, "%s: esm_heads=%d (the reference fixes 8, fs2.py:83)", who, b.esm_heads);
+  BSG_REQUIRE(b.enc_layers > 0 && b.dec_layers > 0 && b.dur_layers > 0 && b.vocab > 0 && b.out_dims > 0 && b.out_dims % 4 == 0 && b.n_pos > 1 &&
+                  b.n_rel > 0,
+              "%s: bad config", who);
+  BSG_REQUIRE(cfg->front == BSG_FS2_FRONT_PLAIN ? b.spk_rows >= 0 : b.spk_rows > 0, "%s: spk_rows=%d (0 = no speaker table: the plain front only)",
+              who, b.spk_rows);
+  BSG_REQUIRE(b.enc_ffn_kernel_size % 2 == 1 && b.dec_ffn_kernel_size % 2 == 1 && b.dur_kernel % 2 == 1, "%s: SAME padding needs odd kernels", who);
+  BSG_REQUIRE(cfg->use_pitch_embed == 0 || cfg->use_pitch_embed == 1, "%s: use_pitch_embed=%d", who, cfg->use_pitch_embed);
+  if (cfg->use_pitch_embed) {
+    BSG_REQUIRE(cfg->pitch_layers > 0 && cfg->pitch_layers <= 16, "%s: pitch_layers=%d (1 .. 16)", who, cfg->pitch_layers);
+    BSG_REQUIRE(cfg->pitch_kernel > 0 && cfg->pitch_kernel % 2 == 1 && cfg->pitch_kernel <= 31, "%s: pitch_kernel=%d (odd, at most 31: SAME padding)",
+                who, cfg->pitch_kernel);
+    BSG_REQUIRE(cfg->use_uv == 0 || cfg->use_uv == 1, "%s: use_uv=%d", who, cfg->use_uv);
+    BSG_REQUIRE(cfg->n_pitch_pos > 1, "%s: n_pitch_pos=%d rows of the pitch position table", who, cfg->n_pitch_pos);
+  }
+  return BSG_OK;
+}
+
+extern "C" int bsg_fs2_n_weights(const bsg_fs2_cfg* cfg) {
+  TRY(fs2_cfg_check(cfg, "fs2_n_weights"));
+  const bsg_fs2midi_cfg& b = cfg->base;
+  const int pitch = cfg->use_pitch_embed ? 1 + 1 + 4 * cfg->pitch_layers + 2 + 1 : 0;
+  if (cfg->front == BSG_FS2_FRONT_MIDI) return bsg_fs2midi_n_weights(&b) + pitch;
+  return 1 + 10 * b.enc_layers + 2 + 2 + 2 + 10 * b.dec_layers + 2 + 2 + (b.spk_rows > 0 ? 1 : 0) + 4 * b.dur_layers + 2 + pitch;
+}
+
+extern "C" int bsg_fs2_create(bsg_fs2midi** out, const bsg_fs2_cfg* cfg, const void* const* dev_weights, int32_t n_weights,
+                              const float* dec_pos_table, const float* tok_pos_table, const float* pitch_pos_table, void* stream) {
+  TRY(fs2_cfg_check(cfg, "fs2_create"));
+  BSG_REQUIRE(out && dev_weights && dec_pos_table && tok_pos_table, "fs2_create: null argument");
+  BSG_REQUIRE(!cfg->use_pitch_embed || pitch_pos_table, "fs2_create: use_pitch_embed without a pitch position table");
+  const int want = bsg_fs2_n_weights(cfg);
+  BSG_REQUIRE(n_weights == want, "fs2_create: expected %d weight tensors, got %d", want, n_weights);
+  for (int i = 0; i < n_weights; ++i) BSG_REQUIRE(dev_weights[i] != nullptr, "fs2_create: weight %d is null", i);
+  bsg_fs2midi* h = new bsg_fs2midi();
+  h->cfg = cfg->base;
+  h->front = cfg->front;
+  h->use_pitch = cfg->use_pitch_embed;
+  if (h->use_pitch) { h->pitch_layers = cfg->pitch_layers; h->pitch_kernel = cfg->pitch_kernel; h->use_uv = cfg->use_uv; h->n_pitch_pos = cfg->n_pitch_pos; }
+  int rc = guard_init(&h->guard, (hipStream_t)stream);
+  if (rc == BSG_OK)
+    rc = h->front == BSG_FS2_FRONT_MIDI ? fs2_create_impl(h, dev_weights, dec_pos_table, tok_pos_table, (hipStream_t)stream, pitch_pos_table)
+                                        : fs2_create_plain(h, dev_weights, dec_pos_table, tok_pos_table, pitch_pos_table, (hipStream_t)stream);
   if (rc != BSG_OK) {
     bsg_fs2midi_destroy(h);
     return rc;
@@ -1503,6 +1777,30 @@ static int fft_stack(bsg_fs2midi* h, const std::vector<FftLayerW>& layers, const
   return BSG_OK;
 }
 
+// duration predictor (tts_modules.py:108-133) on (x + spk) * keep for the nb utterances of x (their keep in w_keep); spk_id: these rows'
+static int dur_predict(bsg_fs2midi* h, const float* x, const int64_t* spk_id, int32_t nb, int32_t Tt, float* dur_xs, int64_t* dur, hipStream_t st) {
+  const long long lrows = (long long)nb * Tt;
+  const dim3 lg(cdiv(lrows, 4)), rb(256);
+  // duration predictor (tts_modules.py:108-133) on (enc + spk) * keep
+  float* a = h->w_a;
+  float* b = h->w_b;
+  hipLaunchKernelGGL(add_spk_kernel, lg, rb, 0, st, (const float*)x, (const long long*)spk_id, h->Espk, h->w_keep, a, lrows, Tt);
+  BSG_LAUNCH_CHECK();
+  const int ks = h->cfg.dur_kernel;
+  for (int l = 0; l < h->cfg.dur_layers; ++l) {
+    GemmArgs g{};
+    g.A = a; g.B = h->dur_conv[l]; g.C = b; g.M = Tt; g.N = H; g.K = H; g.lda = H; g.ldb = H; g.ldc = H; g.trans_b = 1;
+    g.taps = ks; g.tap_shift0 = -(ks / 2); g.sTapB = (long long)H * H; g.bias_n = h->dur_convb[l]; g.alpha = 1.f;
+    g.act = ACT_RELU; g.batch = nb; g.sA = (long long)Tt * H; g.sC = (long long)Tt * H;
+    TRY(launch_gemm(g, st));
+    TRY(ln(b, h->dur_lnw[l], h->dur_lnb[l], a, h->w_keep, lrows, 1e-12f, st));
+  }
+  TRY(linear(a, h->dur_lin_w, h->dur_lin_b, dur_xs, lrows, 1, H, ACT_NONE, nullptr, h->w_keep, st));
+  hipLaunchKernelGGL(dur_from_log_kernel, dim3(cdiv(lrows, 256)), dim3(256), 0, st, (const float*)dur_xs, (long long*)dur, lrows);
+  BSG_LAUNCH_CHECK();
+  return BSG_OK;
+}
+
 // Token-level front for the batch rows [row0, row0 + nb) of a batch of B utterances.  Only the ESM couples rows (it attends over the BATCH
 // axis, common_layers.py:853), and only through K / V = projections of LN(lang_embed[lang]) of every row (:850-853): the other rows
 // contribute their `lang` ints and nothing else.  So K / V are projected for all B rows, and everything else — Q, the attention's queries,
@@ -1587,25 +1885,7 @@ static int encode_impl(bsg_fs2midi* h, const int64_t* txt, const int64_t* pitch_
   BSG_LAUNCH_CHECK();
   TRY(fft_stack(h, h->enc, h->enc_lnw, h->enc_lnb, h->cfg.enc_ffn_kernel_size, x, h->w_keep, nb, Tt, st, "enc."));
   BSG_HIP(hipMemcpyAsync(enc_out, x, lrows * H * sizeof(float), hipMemcpyDeviceToDevice, st));
-  if (dur) {
-    // duration predictor (tts_modules.py:108-133) on (enc + spk) * keep
-    float* a = h->w_a;
-    float* b = h->w_b;
-    hipLaunchKernelGGL(add_spk_kernel, lg, rb, 0, st, (const float*)x, (const long long*)spk_id + row0, h->Espk, h->w_keep, a, lrows, Tt);
-    BSG_LAUNCH_CHECK();
-    const int ks = h->cfg.dur_kernel;
-    for (int l = 0; l < h->cfg.dur_layers; ++l) {
-      GemmArgs g{};
-      g.A = a; g.B = h->dur_conv[l]; g.C = b; g.M = Tt; g.N = H; g.K = H; g.lda = H; g.ldb = H; g.ldc = H; g.trans_b = 1;
-      g.taps = ks; g.tap_shift0 = -(ks / 2); g.sTapB = (long long)H * H; g.bias_n = h->dur_convb[l]; g.alpha = 1.f;
-      g.act = ACT_RELU; g.batch = nb; g.sA = (long long)Tt * H; g.sC = (long long)Tt * H;
-      TRY(launch_gemm(g, st));
-      TRY(ln(b, h->dur_lnw[l], h->dur_lnb[l], a, h->w_keep, lrows, 1e-12f, st));
-    }
-    TRY(linear(a, h->dur_lin_w, h->dur_lin_b, dur_xs, lrows, 1, H, ACT_NONE, nullptr, h->w_keep, st));
-    hipLaunchKernelGGL(dur_from_log_kernel, dim3(cdiv(lrows, 256)), dim3(256), 0, st, (const float*)dur_xs, (long long*)dur, lrows);
-    BSG_LAUNCH_CHECK();
-  }
+  if (dur) TRY(dur_predict(h, x, spk_id ? spk_id + row0 : nullptr, nb, Tt, dur_xs, dur, st));
   return BSG_OK;
 }
 
@@ -1614,6 +1894,7 @@ extern "C" int bsg_fs2midi_encode(bsg_fs2midi* h, const int64_t* txt, const int6
                                   float* enc_out, float* dur_xs, int64_t* dur, void* stream) {
   GuardScope guard_scope(h ? &h->guard : nullptr);
   BSG_REQUIRE(h && txt && pitch_midi && midi_dur && is_slur && lang && spk_id && enc_out, "fs2midi_encode: null argument");
+  BSG_REQUIRE(h->front == BSG_FS2_FRONT_MIDI, "fs2midi_encode: the handle has the plain front (bsg_fs2_encode_plain)");
   BSG_REQUIRE(B > 0 && Tt > 0 && Tt <= h->cfg.n_rel, "fs2midi_encode: B=%d T_txt=%d (rel-pos table has %d rows)", B, Tt, h->cfg.n_rel);
   BSG_REQUIRE((dur_xs == nullptr) == (dur == nullptr), "fs2midi_encode: dur_xs and dur go together");
   h->path.clear();
@@ -1627,6 +1908,7 @@ extern "C" int bsg_fs2midi_encode_rows(bsg_fs2midi* h, const int64_t* txt, const
                                        int32_t row0, int32_t n_rows, float* enc_out, float* dur_xs, int64_t* dur, void* stream) {
   GuardScope guard_scope(h ? &h->guard : nullptr);
   BSG_REQUIRE(h && txt && pitch_midi && midi_dur && is_slur && lang && spk_id && enc_out, "fs2midi_encode_rows: null argument");
+  BSG_REQUIRE(h->front == BSG_FS2_FRONT_MIDI, "fs2midi_encode_rows: the handle has the plain front (bsg_fs2_encode_plain)");
   BSG_REQUIRE(B > 0 && Tt > 0 && Tt <= h->cfg.n_rel, "fs2midi_encode_rows: B=%d T_txt=%d (rel-pos table has %d rows)", B, Tt, h->cfg.n_rel);
   BSG_REQUIRE(row0 >= 0 && n_rows > 0 && row0 + n_rows <= B, "fs2midi_encode_rows: rows [%d, %d) of a batch of %d", row0, row0 + n_rows, B);
   BSG_REQUIRE((dur_xs == nullptr) == (dur == nullptr), "fs2midi_encode_rows: dur_xs and dur go together");
@@ -1634,6 +1916,34 @@ extern "C" int bsg_fs2midi_encode_rows(bsg_fs2midi* h, const int64_t* txt, const
   const int rc = encode_impl(h, txt, pitch_midi, midi_dur, is_slur, lang, spk_id, B, Tt, row0, n_rows, enc_out, dur_xs, dur, (hipStream_t)stream);
   h->path_enc_len = h->path.size();
   return rc;
+}
+
+// The plain front (fastspeech/fs2.py:100-129): token embedding + positions in one launch, the FFT encoder, the duration predictor.  Nothing
+// couples the utterances of a batch, so the rows [row0, row0 + n_rows) are simply the rows that run.
+extern "C" int bsg_fs2_encode_plain(bsg_fs2midi* h, const int64_t* txt, const int64_t* spk_id, int32_t B, int32_t Tt, int32_t row0,
+                                    int32_t n_rows, float* enc_out, float* dur_xs, int64_t* dur, void* stream) {
+  GuardScope guard_scope(h ? &h->guard : nullptr);
+  BSG_REQUIRE(h && txt && enc_out, "fs2_encode_plain: null argument");
+  BSG_REQUIRE(h->front == BSG_FS2_FRONT_PLAIN, "fs2_encode_plain: the handle has the MIDI front (bsg_fs2midi_encode)");
+  BSG_REQUIRE((spk_id != nullptr) == (h->cfg.spk_rows > 0), "fs2_encode_plain: spk_id goes with a speaker table (spk_rows=%d)", h->cfg.spk_rows);
+  BSG_REQUIRE(B > 0 && Tt > 0 && Tt < h->cfg.n_rel, "fs2_encode_plain: B=%d T_txt=%d (position table has %d rows)", B, Tt, h->cfg.n_rel);
+  BSG_REQUIRE(row0 >= 0 && n_rows > 0 && row0 + n_rows <= B, "fs2_encode_plain: rows [%d, %d) of a batch of %d", row0, row0 + n_rows, B);
+  BSG_REQUIRE((dur_xs == nullptr) == (dur == nullptr), "fs2_encode_plain: dur_xs and dur go together");
+  hipStream_t st = (hipStream_t)stream;
+  h->path.clear();
+  const long long lrows = (long long)n_rows * Tt, off = (long long)row0 * Tt;
+  TRY(ensure_ws(h, (size_t)lrows, 0, st));
+  h->last_token_rows = (int)lrows;
+  float* x = h->w_c;
+  hipLaunchKernelGGL(token_front_kernel, dim3(cdiv(lrows, 4)), dim3(256), 0, st, (const long long*)txt + off, h->Etok, h->rel_table, x, h->w_keep,
+                     lrows, Tt, sqrtf((float)H), h->cfg.n_rel, h->cfg.vocab);
+  BSG_LAUNCH_CHECK();
+  path_add(h, "tok:", "front");
+  TRY(fft_stack(h, h->enc, h->enc_lnw, h->enc_lnb, h->cfg.enc_ffn_kernel_size, x, h->w_keep, n_rows, Tt, st, "enc."));
+  BSG_HIP(hipMemcpyAsync(enc_out, x, lrows * H * sizeof(float), hipMemcpyDeviceToDevice, st));
+  if (dur) TRY(dur_predict(h, x, spk_id ? spk_id + row0 : nullptr, n_rows, Tt, dur_xs, dur, st));
+  h->path_enc_len = h->path.size();
+  return BSG_OK;
 }
 
 extern "C" int bsg_fs2midi_last_rows(const bsg_fs2midi* h, int32_t* token_rows, int32_t* stack_rows) {
@@ -1675,20 +1985,70 @@ extern "C" int bsg_length_regulator(const int64_t* dur, const int64_t* txt, int6
   return BSG_OK;
 }
 
-extern "C" int bsg_fs2midi_decode(bsg_fs2midi* h, const float* enc_out, const int64_t* mel2ph, const int64_t* spk_id,
-                                  const int64_t* speechsing, int32_t B, int32_t Tt, int32_t T, float* decoder_inp,
-                                  float* mel_out, void* stream) {
-  GuardScope guard_scope(h ? &h->guard : nullptr);
-  BSG_REQUIRE(h && enc_out && mel2ph && spk_id && speechsing && decoder_inp, "fs2midi_decode: null argument");
-  BSG_REQUIRE(B > 0 && Tt > 0 && T > 0 && T < h->cfg.n_pos, "fs2midi_decode: B=%d T_txt=%d T=%d (position table has %d rows)", B, Tt, T, h->cfg.n_pos);
-  hipStream_t st = (hipStream_t)stream;
+// The pitch adaptor in front of the decoder: scan + entry (positions), per predictor layer the k-tap convolution as a K-segmented GEMM with
+// bias + ReLU in its epilogue and (but for the last layer) a LayerNorm launch — NO mask between the layers (tts_modules.py:233-234: padded
+// frames carry bias-driven values into the last real frames through the taps) — and pitch_tail_kernel.
+static int pitch_adaptor(bsg_fs2midi* h, const float* enc_out, const int64_t* mel2ph, const int64_t* spk_id, const int64_t* speechsing,
+                         const float* f0, const float* uv, int32_t B, int32_t Tt, int32_t T, float* pitch_pred, float* f0_denorm,
+                         int64_t* pitch_bin, float* decoder_inp, hipStream_t st) {
+  const long long rows = (long long)B * T;
+  const dim3 rg(cdiv(rows, 4)), rb(256);
+  float *cur = h->w_a, *cv = h->w_b;
+  int n_launch = 0;   // counted where each launch is made: the record's last token
+  hipLaunchKernelGGL(pitch_positions_kernel, dim3(B), dim3(64), 0, st, enc_out, (const long long*)mel2ph, (const long long*)spk_id, h->Espk,
+                     h->w_pos, T, Tt, h->cfg.spk_rows);
+  BSG_LAUNCH_CHECK();
+  path_add(h, "pit.", "pos");
+  ++n_launch;
+  hipLaunchKernelGGL(pitch_entry_kernel, rg, rb, 0, st, enc_out, (const long long*)mel2ph, (const long long*)spk_id, h->Espk,
+                     (const int*)h->w_pos, h->pit_table, h->pit_alpha, cur, rows, T, Tt, h->n_pitch_pos, h->cfg.spk_rows);
+  BSG_LAUNCH_CHECK();
+  path_add(h, "pit.", "entry");
+  ++n_launch;
+  const int ks = h->pitch_kernel, L = h->pitch_layers;
+  for (int l = 0; l < L; ++l) {
+    GemmArgs g{};
+    g.A = cur; g.B = h->pit_conv[l]; g.C = cv; g.M = T; g.N = H; g.K = H; g.lda = H; g.ldb = H; g.ldc = H; g.trans_b = 1;
+    g.taps = ks; g.tap_shift0 = -(ks / 2); g.sTapB = (long long)H * H; g.bias_n = h->pit_convb[l]; g.alpha = 1.f;
+    g.act = ACT_RELU; g.batch = B; g.sA = (long long)T * H; g.sC = (long long)T * H;
+    TRY(gemm_rec(h, "pit.gemm:", g, st));
+    ++n_launch;
+    if (l + 1 < L) {
+      TRY(ln(cv, h->pit_lnw[l], h->pit_lnb[l], cur, nullptr, rows, 1e-12f, st));
+      path_add(h, "pit.", "ln");
+      ++n_launch;
+    }
+  }
+  hipLaunchKernelGGL(pitch_tail_kernel, rg, rb, 0, st, (const float*)cv, h->pit_lnw[L - 1], h->pit_lnb[L - 1], h->pit_lin_w, h->pit_lin_b, f0, uv,
+                     h->use_uv, enc_out, (const long long*)mel2ph, (const long long*)spk_id, (const long long*)speechsing, h->Espk, h->Estyle,
+                     h->Epitch, pitch_pred, f0_denorm, (long long*)pitch_bin, decoder_inp, rows, T, Tt, h->cfg.spk_rows);
+  BSG_LAUNCH_CHECK();
+  path_add(h, "pit.", "tail");
+  ++n_launch;
+  path_add(h, "pit.launches:", std::to_string(n_launch).c_str());
+  return BSG_OK;
+}
+
+static int decode_impl(bsg_fs2midi* h, const char* who, const float* enc_out, const int64_t* mel2ph, const int64_t* spk_id,
+                       const int64_t* speechsing, const float* f0, const float* uv, int32_t B, int32_t Tt, int32_t T, float* pitch_pred,
+                       float* f0_denorm, int64_t* pitch_bin, float* decoder_inp, float* mel_out, hipStream_t st) {
+  BSG_REQUIRE(h && enc_out && mel2ph && decoder_inp, "%s: null argument", who);
+  BSG_REQUIRE((spk_id != nullptr) == (h->Espk != nullptr), "%s: spk_id goes with a speaker table (spk_rows=%d)", who, h->cfg.spk_rows);
+  BSG_REQUIRE((speechsing != nullptr) == (h->front == BSG_FS2_FRONT_MIDI), "%s: speechsing goes with the MIDI front", who);
+  BSG_REQUIRE(B > 0 && Tt > 0 && T > 0 && T < h->cfg.n_pos, "%s: B=%d T_txt=%d T=%d (position table has %d rows)", who, B, Tt, T, h->cfg.n_pos);
+  BSG_REQUIRE(h->use_pitch || (!f0 && !uv && !pitch_pred && !f0_denorm && !pitch_bin), "%s: f0 / uv / pitch outputs on a handle without use_pitch_embed", who);
+  BSG_REQUIRE(!h->use_pitch || T < h->n_pitch_pos, "%s: T=%d (pitch position table has %d rows)", who, T, h->n_pitch_pos);
   h->path.resize(h->path_enc_len);   // the record keeps the encode this decode follows
   const long long rows = (long long)B * T;
   TRY(ensure_ws(h, (size_t)rows, mel_out ? (size_t)B * h->cfg.num_heads * T * T : 0, st));
   const dim3 rg(cdiv(rows, 4)), rb(256);
-  hipLaunchKernelGGL(gather_frames_kernel, rg, rb, 0, st, enc_out, (const long long*)mel2ph, (const long long*)spk_id,
-                     (const long long*)speechsing, h->Espk, h->Estyle, decoder_inp, rows, T, Tt);
-  BSG_LAUNCH_CHECK();
+  if (h->use_pitch) {
+    TRY(pitch_adaptor(h, enc_out, mel2ph, spk_id, speechsing, f0, uv, B, Tt, T, pitch_pred, f0_denorm, pitch_bin, decoder_inp, st));
+  } else {
+    hipLaunchKernelGGL(gather_frames_kernel, rg, rb, 0, st, enc_out, (const long long*)mel2ph, (const long long*)spk_id,
+                       (const long long*)speechsing, h->Espk, h->Estyle, decoder_inp, rows, T, Tt);
+    BSG_LAUNCH_CHECK();
+  }
   if (!mel_out) return BSG_OK;   // skip_decoder
   float* x = h->w_x;
   BSG_HIP(hipMemcpyAsync(x, decoder_inp, rows * H * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -1704,6 +2064,23 @@ extern "C" int bsg_fs2midi_decode(bsg_fs2midi* h, const float* enc_out, const in
                      (const long long*)mel2ph, rows, h->cfg.out_dims);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
+}
+
+extern "C" int bsg_fs2midi_decode(bsg_fs2midi* h, const float* enc_out, const int64_t* mel2ph, const int64_t* spk_id,
+                                  const int64_t* speechsing, int32_t B, int32_t Tt, int32_t T, float* decoder_inp,
+                                  float* mel_out, void* stream) {
+  GuardScope guard_scope(h ? &h->guard : nullptr);
+  // (spk_id / speechsing: required on a MIDI handle, NULL where a plain-front handle has no such table — decode_impl says which)
+  return decode_impl(h, "fs2midi_decode", enc_out, mel2ph, spk_id, speechsing, nullptr, nullptr, B, Tt, T, nullptr, nullptr, nullptr, decoder_inp,
+                     mel_out, (hipStream_t)stream);
+}
+
+extern "C" int bsg_fs2_decode(bsg_fs2midi* h, const float* enc_out, const int64_t* mel2ph, const int64_t* spk_id, const int64_t* speechsing,
+                              const float* f0, const float* uv, int32_t B, int32_t Tt, int32_t T, float* pitch_pred, float* f0_denorm,
+                              int64_t* pitch_bin, float* decoder_inp, float* mel_out, void* stream) {
+  GuardScope guard_scope(h ? &h->guard : nullptr);
+  return decode_impl(h, "fs2_decode", enc_out, mel2ph, spk_id, speechsing, f0, uv, B, Tt, T, pitch_pred, f0_denorm, pitch_bin, decoder_inp, mel_out,
+                     (hipStream_t)stream);
 }
 
 

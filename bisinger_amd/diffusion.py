@@ -66,7 +66,8 @@ class GaussianDiffusion(nn.Module):
             from .fs2 import FastSpeech2MIDI
             self.fs2 = FastSpeech2MIDI(phone_encoder, out_dims)
         else:
-            raise NotImplementedError('only the MIDI front (use_midi: true) is on the BiSinger path (SURVEY.md §8)')
+            from .fs2 import FastSpeech2
+            self.fs2 = FastSpeech2(phone_encoder, out_dims)      # usr/diff/shallow_diffusion_tts.py:76-79
         self.mel_bins = out_dims
         if betas is not None:
             betas = betas.detach().cpu().numpy() if isinstance(betas, torch.Tensor) else betas

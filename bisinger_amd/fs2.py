@@ -1,5 +1,7 @@
 """``FastSpeech2MIDI`` — drop-in for modules/diffsinger_midi/fs2.py:80-197 (+ the base
-modules/fastspeech/fs2.py:24-89 constructor), inference direction, on HIP kernels.
+modules/fastspeech/fs2.py:24-89 constructor), inference direction, on HIP kernels — and ``FastSpeech2``, the plain front the
+reference builds when ``use_midi`` is absent or false (modules/fastspeech/fs2.py:24-240; usr/diff/shallow_diffusion_tts.py:76-79),
+both with the frame-level pitch adaptor of ``use_pitch_embed: true`` (add_pitch, fs2.py:188-234).
 
 The sub-modules below reproduce the reference's module tree so that ``state_dict()`` has exactly the
 reference's 143 ``fs2.*`` entries (names, shapes, order — including the two aliased sub-trees
@@ -181,69 +183,148 @@ class DurationPredictor(_Holder):
         self.linear = nn.Linear(n_chans, 1)
 
 
-class FastSpeech2MIDI(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
-    GUARD_KIND = 'fs2midi'
+class PitchPredictor(_Holder):
+    """tts_modules.py:194-237 (odim = 2, padding SAME): state_dict order pos_embed_alpha, conv.i.1.*, conv.i.3.*, linear.*,
+    embed_positions._float_tensor."""
 
-    def __init__(self, dictionary, out_dims=None):
+    def __init__(self, idim, n_layers, n_chans, kernel_size):
         super().__init__()
+        self.kernel_size, self.n_layers = kernel_size, n_layers
+        self.conv = nn.ModuleList()
+        for i in range(n_layers):
+            self.conv.append(nn.Sequential(
+                nn.ConstantPad1d(((kernel_size - 1) // 2, (kernel_size - 1) // 2), 0),
+                nn.Conv1d(idim if i == 0 else n_chans, n_chans, kernel_size, stride=1, padding=0),
+                nn.ReLU(), PredictorLayerNorm(n_chans), nn.Dropout(hparams['predictor_dropout'])))
+        self.linear = nn.Linear(n_chans, 2)
+        self.embed_positions = SinusoidalPositionalEmbedding(idim, 0, init_size=4096)
+        self.pos_embed_alpha = nn.Parameter(torch.Tensor([1]))
+
+
+class FastspeechEncoder(FFTBlocks):
+    """tts_modules.py:312-349 without rel_pos: sqrt(H) * embed_tokens + SinusoidalPositionalEmbedding over the non-pad tokens."""
+
+    def __init__(self, embed_tokens):
+        super().__init__(hparams['hidden_size'], hparams['enc_layers'], hparams['enc_ffn_kernel_size'],
+                         hparams['num_heads'], use_pos_embed=False)
+        self.embed_tokens = embed_tokens
+        self.embed_scale = math.sqrt(hparams['hidden_size'])
+        self.padding_idx = 0
+        self.embed_positions = SinusoidalPositionalEmbedding(hparams['hidden_size'], 0, init_size=DEFAULT_MAX_TARGET_POSITIONS)
+
+
+def _refuse(key, what):
+    raise NotImplementedError(f"{key}: {what} (INTEGRATION.md, 'The pitch adaptor and the plain front')")
+
+
+def check_fs2_hparams(hp, plain):
+    """The configurations neither front executes: NotImplementedError naming the key, at construction."""
+    if hp.get('encoder_type', 'fft') != 'fft':
+        _refuse('encoder_type', f"{hp['encoder_type']!r}: only the 'fft' encoder is built")
+    if hp.get('decoder_type', 'fft') != 'fft':
+        _refuse('decoder_type', f"{hp['decoder_type']!r}: only the 'fft' decoder is built")
+    if hp.get('use_energy_embed'):
+        _refuse('use_energy_embed', 'the energy embedding is not built')
+    if hp.get('use_spk_embed'):
+        _refuse('use_spk_embed', 'the speaker-embedding projection is not built; use_spk_id or no speaker')
+    if hp.get('use_split_spk_id'):
+        _refuse('use_split_spk_id', 'split speaker tables are not built')
+    if plain and hp.get('rel_pos'):
+        _refuse('rel_pos', 'the plain front is built with the sinusoidal token positions only')
+    if hp.get('use_pitch_embed'):
+        if hp.get('pitch_type', 'frame') != 'frame':
+            _refuse('pitch_type', f"{hp['pitch_type']!r}: only the frame-level adaptor ('frame') is built")
+        if hp.get('pitch_ar'):
+            _refuse('pitch_ar', 'the autoregressive pitch predictor is not built')
+        if hp.get('pitch_norm', 'log') != 'log':
+            _refuse('pitch_norm', f"{hp['pitch_norm']!r}: only 'log' is built")
+
+
+class _FastSpeech2Base(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
+    """What FastSpeech2MIDI and FastSpeech2 share: the handle (one type for both fronts, bsg_fs2_create), the frame-level part and the
+    reference's forward."""
+    GUARD_KIND = 'fs2midi'
+    FRONT = _lib.FS2_FRONT_MIDI
+
+    def _init_base(self, dictionary, out_dims):
+        """fastspeech/fs2.py:27-81 in the reference's registration order, without the encoder (the subclass adds its own)."""
         hp = hparams
-        assert hp['encoder_type'] == 'fft' and hp['decoder_type'] == 'fft'
-        assert hp['use_spk_id'] and not hp['use_spk_embed'] and not hp.get('use_split_spk_id'), \
-            'BiSinger path: use_spk_id speaker table (SURVEY.md §8)'
-        assert not hp['use_pitch_embed'] and not hp['use_energy_embed'], \
-            'pitch/energy predictors are not executed by any BiSinger config (SURVEY.md §2 row 5)'
-        assert hp['ffn_act'] == 'gelu' and hp['ffn_padding'] == 'SAME' and hp['use_pos_embed'] and hp.get('rel_pos')
         self.dictionary = dictionary
         self.padding_idx = dictionary.pad()
         self.enc_layers, self.dec_layers = hp['enc_layers'], hp['dec_layers']
         self.hidden_size = H = hp['hidden_size']
+        self.use_pitch_embed = bool(hp.get('use_pitch_embed'))
+        self.use_uv = bool(hp.get('use_uv', True))
         self.encoder_embed_tokens = Embedding(len(dictionary), H, self.padding_idx)
+
+    def _init_tail(self, out_dims):
+        hp = hparams
+        H = self.hidden_size
         self.decoder = FastspeechDecoder()
         self.out_dims = out_dims if out_dims is not None else hp['audio_num_mel_bins']
         self.mel_out = Linear(H, self.out_dims, bias=True)
-        self.spk_embed_proj = Embedding(hp['num_spk'] + 1, H)
+        if hp.get('use_spk_id'):
+            self.spk_embed_proj = Embedding(hp['num_spk'] + 1, H)
         ph = hp['predictor_hidden'] if hp['predictor_hidden'] > 0 else H
+        if ph != H:
+            _refuse('predictor_hidden', f'{ph}: the predictor kernels are built for hidden_size channels')
         self.dur_predictor = DurationPredictor(H, hp['dur_predictor_layers'], ph, hp['dur_predictor_kernel'])
-        self.esm = ESM(d_model=H, nhead=8)
-        self.encoder = FastspeechMIDIEncoder(self.esm, self.encoder_embed_tokens)
-        self.midi_embed = Embedding(300, H, self.padding_idx)
-        self.midi_dur_layer = Linear(1, H)
-        self.is_slur_embed = Embedding(2, H)
-        self.lang_embed = Embedding(2, H)
-        self.style_embed = Embedding(3, H)
+        if self.use_pitch_embed:
+            self.pitch_embed = Embedding(300, H, self.padding_idx)
+            self.pitch_predictor = PitchPredictor(H, hp['predictor_layers'], ph, hp['predictor_kernel'])
         self._h = None
         self._h_key = None
 
     # ------------------------------------------------------------------ handle management
+    def _token_table(self):
+        raise NotImplementedError
+
     def handle(self):
         key = self._key()
         if self._h is not None and key == self._h_key:
             return self._h
         self.release()
+        name = type(self).__name__
         ws = [p.detach() for p in self._weights()]
         for p in ws:
             if not p.is_cuda:
-                raise _lib.BsgError('FastSpeech2MIDI parameters must live on the GPU (model.cuda()); there is no CPU path')
+                raise _lib.BsgError(f'{name} parameters must live on the GPU (model.cuda()); there is no CPU path')
             if p.dtype != torch.float32 or not p.is_contiguous():
-                raise _lib.BsgError('FastSpeech2MIDI parameters must be contiguous float32')
+                raise _lib.BsgError(f'{name} parameters must be contiguous float32')
         hp = hparams
         lib = _lib.load()
         self._n_pos = max(DEFAULT_MAX_TARGET_POSITIONS, int(hp.get('max_frames', 5000))) + 2
-        self._n_rel = self.encoder.embed_positions.max_len
-        cfg = _lib.Fs2Cfg(self.hidden_size, self.encoder_embed_tokens.num_embeddings, self.enc_layers, self.dec_layers,
-                          hp['num_heads'], hp['enc_ffn_kernel_size'], hp['dec_ffn_kernel_size'], self.out_dims,
-                          hp['dur_predictor_layers'], hp['dur_predictor_kernel'], self.spk_embed_proj.num_embeddings, 8,
-                          self._n_pos, self._n_rel)
-        assert lib.bsg_fs2midi_n_weights(byref(cfg)) == len(ws)
         dev = ws[0].device
+        tok_table = self._token_table().to(dev).contiguous()
+        self._n_rel = tok_table.shape[0]
+        spk_rows = self.spk_embed_proj.num_embeddings if hasattr(self, 'spk_embed_proj') else 0
+        base = _lib.Fs2Cfg(self.hidden_size, self.encoder_embed_tokens.num_embeddings, self.enc_layers, self.dec_layers,
+                           hp['num_heads'], hp['enc_ffn_kernel_size'], hp['dec_ffn_kernel_size'], self.out_dims,
+                           len(self.dur_predictor.conv), self.dur_predictor.kernel_size, spk_rows, 8, self._n_pos, self._n_rel)
         dec_table = self.decoder.embed_positions.table(self._n_pos).to(dev).contiguous()
-        rel_table = self.encoder.embed_positions.table(self._n_rel).to(dev).contiguous()
         arr = (c_void_p * len(ws))(*[p.data_ptr() for p in ws])
         h = c_void_p()
-        with torch.cuda.device(dev):
-            _lib.check(lib.bsg_fs2midi_create(byref(h), byref(cfg), cast(arr, POINTER(c_void_p)), len(ws),
-                                              _lib.ptr(dec_table), _lib.ptr(rel_table), _lib.stream_ptr()),
-                       'bsg_fs2midi_create')
+        if self.FRONT == _lib.FS2_FRONT_MIDI and not self.use_pitch_embed:
+            # the configuration of every BiSinger experiment: the entry it has always been created through
+            assert lib.bsg_fs2midi_n_weights(byref(base)) == len(ws)
+            with torch.cuda.device(dev):
+                _lib.check(lib.bsg_fs2midi_create(byref(h), byref(base), cast(arr, POINTER(c_void_p)), len(ws),
+                                                  _lib.ptr(dec_table), _lib.ptr(tok_table), _lib.stream_ptr()),
+                           'bsg_fs2midi_create')
+        else:
+            pit_table = None
+            cfg = _lib.Fs2XCfg(base, self.FRONT, 0, 0, 0, 0, 0)
+            if self.use_pitch_embed:
+                pit_table = self.pitch_predictor.embed_positions.table(self._n_pos).to(dev).contiguous()
+                cfg = _lib.Fs2XCfg(base, self.FRONT, 1, self.pitch_predictor.n_layers, self.pitch_predictor.kernel_size, int(self.use_uv),
+                                   self._n_pos)
+            n = lib.bsg_fs2_n_weights(byref(cfg))
+            if n < 0:
+                _lib.check(n, 'bsg_fs2_n_weights')
+            assert n == len(ws), (n, len(ws))
+            with torch.cuda.device(dev):
+                _lib.check(lib.bsg_fs2_create(byref(h), byref(cfg), cast(arr, POINTER(c_void_p)), len(ws), _lib.ptr(dec_table),
+                                              _lib.ptr(tok_table), _lib.ptr(pit_table), _lib.stream_ptr()), 'bsg_fs2_create')
         self._h, self._h_key = h, key
         self._apply_guard_state()
         return h
@@ -258,6 +339,148 @@ class FastSpeech2MIDI(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
             self.release()
         except Exception:
             pass
+
+    def last_rows(self):
+        """-> (token rows the last encode ran its encoder on, rows of the last FFT stack): test introspection."""
+        from ctypes import c_int32
+        a, b = c_int32(), c_int32()
+        _lib.check(_lib.load().bsg_fs2midi_last_rows(self._h if self._h is not None else self.handle(), byref(a), byref(b)), 'bsg_fs2midi_last_rows')
+        return a.value, b.value
+
+    def last_path(self):
+        """The launch forms of the last encode and of the decode after it, as blank-separated tokens in launch order
+        (include/bisinger_hip.h, bsg_fs2midi_last_path): 'esm:wave enc.qkv:fused enc.attn:planes/ks2 enc.gemm:h2w/32/deep ... dec. ...';
+        'none' before the first call.  Test introspection."""
+        return _lib.load().bsg_fs2midi_last_path(self._h).decode() if self._h is not None else 'none'
+
+    def poison_workspace(self):
+        """Test hook (bsg_fs2midi_debug_poison_workspace): NaN bytes over every activation workspace of the handle."""
+        with torch.cuda.device(next(self.parameters()).device):
+            _lib.check(_lib.load().bsg_fs2midi_debug_poison_workspace(self.handle(), _lib.stream_ptr()), 'bsg_fs2midi_debug_poison_workspace')
+
+    @torch.no_grad()
+    def regulate(self, enc):
+        """LengthRegulator on the predicted durations (tts_modules.py:161-191); one host sync, as in the
+        reference (the output length is data dependent, :182)."""
+        dur, txt = enc['dur'], enc['txt']
+        B, Tt = txt.shape
+        T = int((dur * (txt != 0)).sum(-1).max().item())
+        if T <= 0:
+            raise _lib.BsgError('duration predictor produced an empty utterance')
+        mel2ph = torch.empty(B, T, dtype=torch.long, device=txt.device)
+        with torch.cuda.device(txt.device):
+            _lib.check(_lib.load().bsg_length_regulator(_lib.ptr(dur), _lib.ptr(txt), _lib.ptr(mel2ph), B, Tt, T,
+                                                        _lib.stream_ptr()), 'bsg_length_regulator')
+        return mel2ph
+
+    @torch.no_grad()
+    def decode(self, enc_out, mel2ph, spk, speechsing, skip_decoder=False):
+        """Frame-level part -> (decoder_inp, mel_out): decode_all() without the adaptor's inputs and outputs."""
+        r = self.decode_all(enc_out, mel2ph, spk, speechsing, skip_decoder)
+        return r['decoder_inp'], r.get('mel_out')
+
+    @torch.no_grad()
+    def decode_all(self, enc_out, mel2ph, spk, speechsing, skip_decoder=False, f0=None, uv=None):
+        """Frame-level part: gather by mel2ph (+ the pitch adaptor, fs2.py:139-142, 201-234), +spk +style, mask; FFT decoder + mel_out
+        (fs2.py:166-195).  ``f0`` / ``uv`` [B,T]: supplied values (neither is written: the reference zeroes the caller's f0 in place,
+        fs2.py:230; this does not).  -> dict: decoder_inp, mel_out (unless skip_decoder) and, with the adaptor, pitch_pred [B,T,2],
+        f0_denorm [B,T] and pitch_bin [B,T]."""
+        dev = enc_out.device
+        h = self.handle()
+        B, Tt, _ = enc_out.shape
+        mel2ph = mel2ph.to(device=dev, dtype=torch.long).contiguous()
+        T = mel2ph.shape[1]
+        if T >= self._n_pos:
+            raise _lib.BsgError(f'T={T} exceeds the decoder position table ({self._n_pos})')
+        if speechsing is not None:
+            speechsing = speechsing.to(device=dev, dtype=torch.long).contiguous()
+        spk = None if spk is None else spk.contiguous()
+        decoder_inp = torch.empty(B, T, self.hidden_size, device=dev)
+        mel_out = None if skip_decoder else torch.empty(B, T, self.out_dims, device=dev)
+        lib = _lib.load()
+        if not self.use_pitch_embed and self.FRONT == _lib.FS2_FRONT_MIDI:
+            with torch.cuda.device(dev):
+                _lib.check(lib.bsg_fs2midi_decode(h, _lib.ptr(enc_out.contiguous()), _lib.ptr(mel2ph), _lib.ptr(spk),
+                                                  _lib.ptr(speechsing), B, Tt, T, _lib.ptr(decoder_inp), _lib.ptr(mel_out),
+                                                  _lib.stream_ptr()), 'bsg_fs2midi_decode')
+            return dict(decoder_inp=decoder_inp) if skip_decoder else dict(decoder_inp=decoder_inp, mel_out=mel_out)
+        pred = f0d = bins = None
+        if self.use_pitch_embed:
+            f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()
+            f0, uv = f32(f0), f32(uv)
+            for n, t in (('f0', f0), ('uv', uv)):
+                if t is not None and tuple(t.shape) != (B, T):
+                    raise _lib.BsgError(f'{n} must be [B,T] = {(B, T)}, got {tuple(t.shape)}')
+            pred = torch.empty(B, T, 2, device=dev)
+            f0d = torch.empty(B, T, device=dev)
+            bins = torch.empty(B, T, dtype=torch.long, device=dev)
+        else:
+            f0 = uv = None
+        with torch.cuda.device(dev):
+            _lib.check(lib.bsg_fs2_decode(h, _lib.ptr(enc_out.contiguous()), _lib.ptr(mel2ph), _lib.ptr(spk), _lib.ptr(speechsing),
+                                          _lib.ptr(f0), _lib.ptr(uv), B, Tt, T, _lib.ptr(pred), _lib.ptr(f0d), _lib.ptr(bins),
+                                          _lib.ptr(decoder_inp), _lib.ptr(mel_out), _lib.stream_ptr()), 'bsg_fs2_decode')
+        ret = dict(decoder_inp=decoder_inp) if skip_decoder else dict(decoder_inp=decoder_inp, mel_out=mel_out)
+        if self.use_pitch_embed:
+            ret.update(pitch_pred=pred, f0_denorm=f0d, pitch_bin=bins)
+        return ret
+
+    def forward(self, txt_tokens, mel2ph=None, spk_embed=None, ref_mels=None, f0=None, uv=None, energy=None,
+                skip_decoder=False, spk_embed_dur_id=None, spk_embed_f0_id=None, infer=False, rows=None, **kwargs):
+        """``rows`` (slice, extension): generate only these batch rows — what a rank of a sharded run asks for (SURVEY.md §8e).  The inputs
+        stay the WHOLE batch's: the ESM attends over the batch axis, so every row's ``lang`` enters this rank's K / V; with ``mel2ph``
+        given nothing else of the other rows is computed (``encode(rows=...)``).  With predicted durations the frame count T is the
+        maximum over the whole batch (tts_modules.py:182), so the token-level front then runs on every row and is sliced afterwards.
+        ``f0`` / ``uv`` [B,T] (use_pitch_embed): supplied pitch (log2 Hz) and unvoiced flags; never written."""
+        return _lib.range_guarded(lambda: self._forward(txt_tokens, mel2ph, spk_embed, skip_decoder, rows, f0, uv, **kwargs),
+                                  f'{type(self).__name__}.forward', device=self, owners=(self,))
+
+    def _forward(self, txt_tokens, mel2ph, spk_embed, skip_decoder, rows, f0=None, uv=None, **kwargs):
+        ret = {}
+        local = rows is not None and mel2ph is not None      # the token front on this rank's rows only
+        enc = self.encode(txt_tokens, spk_embed, predict_dur=mel2ph is None, rows=rows if local else None, **kwargs)
+        if mel2ph is None:
+            mel2ph = self.regulate(enc)
+            ret['dur'] = enc['dur_xs'][:, :, None]
+            ret['dur_choice'] = enc['dur']
+        # (with mel2ph given the reference also runs the predictor for its training loss; inference does not use it)
+        enc_out, spk = enc['enc_out'], enc['spk']
+        speechsing = kwargs['speechsing'] if self.FRONT == _lib.FS2_FRONT_MIDI else None     # (the plain front has no style row)
+        if rows is not None:
+            if not local:
+                enc_out = enc_out[rows]
+            spk = None if spk is None else spk[rows]
+            speechsing = None if speechsing is None else speechsing[rows]
+            mel2ph = mel2ph[rows]
+            f0 = None if f0 is None else f0[rows]
+            uv = None if uv is None else uv[rows]
+        ret['mel2ph'] = mel2ph
+        ret.update(self.decode_all(enc_out, mel2ph, spk, speechsing, skip_decoder, f0=f0, uv=uv))
+        return ret
+
+
+class FastSpeech2MIDI(_FastSpeech2Base):
+    FRONT = _lib.FS2_FRONT_MIDI
+
+    def __init__(self, dictionary, out_dims=None):
+        super().__init__()
+        hp = hparams
+        check_fs2_hparams(hp, plain=False)
+        assert hp['use_spk_id'], 'BiSinger path: use_spk_id speaker table (SURVEY.md §8)'
+        assert hp['ffn_act'] == 'gelu' and hp['ffn_padding'] == 'SAME' and hp['use_pos_embed'] and hp.get('rel_pos')
+        self._init_base(dictionary, out_dims)
+        H = self.hidden_size
+        self._init_tail(out_dims)
+        self.esm = ESM(d_model=H, nhead=8)
+        self.encoder = FastspeechMIDIEncoder(self.esm, self.encoder_embed_tokens)
+        self.midi_embed = Embedding(300, H, self.padding_idx)
+        self.midi_dur_layer = Linear(1, H)
+        self.is_slur_embed = Embedding(2, H)
+        self.lang_embed = Embedding(2, H)
+        self.style_embed = Embedding(3, H)
+
+    def _token_table(self):
+        return self.encoder.embed_positions.table(self.encoder.embed_positions.max_len)
 
     # ------------------------------------------------------------------ reference forward (fs2.py:94-197)
     @torch.no_grad()
@@ -300,83 +523,50 @@ class FastSpeech2MIDI(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
                                                        _lib.ptr(dur_xs), _lib.ptr(dur), _lib.stream_ptr()), 'bsg_fs2midi_encode_rows')
         return dict(enc_out=enc_out, txt=txt, spk=spk, dur_xs=dur_xs, dur=dur)
 
-    def last_rows(self):
-        """-> (token rows the last encode ran its encoder on, rows of the last FFT stack): test introspection."""
-        from ctypes import c_int32
-        a, b = c_int32(), c_int32()
-        _lib.check(_lib.load().bsg_fs2midi_last_rows(self._h if self._h is not None else self.handle(), byref(a), byref(b)), 'bsg_fs2midi_last_rows')
-        return a.value, b.value
 
-    def last_path(self):
-        """The launch forms of the last encode and of the decode after it, as blank-separated tokens in launch order
-        (include/bisinger_hip.h, bsg_fs2midi_last_path): 'esm:wave enc.qkv:fused enc.attn:planes/ks2 enc.gemm:h2w/32/deep ... dec. ...';
-        'none' before the first call.  Test introspection."""
-        return _lib.load().bsg_fs2midi_last_path(self._h).decode() if self._h is not None else 'none'
+class FastSpeech2(_FastSpeech2Base):
+    """modules/fastspeech/fs2.py:24-240 with the 'fft' encoder and decoder, no rel_pos: what GaussianDiffusion builds when ``use_midi`` is
+    absent or false (the DiffSinger / PopCS family).  Speaker forms: none, or ``use_spk_id``."""
+    FRONT = _lib.FS2_FRONT_PLAIN
 
-    def poison_workspace(self):
-        """Test hook (bsg_fs2midi_debug_poison_workspace): NaN bytes over every activation workspace of the handle."""
-        with torch.cuda.device(next(self.parameters()).device):
-            _lib.check(_lib.load().bsg_fs2midi_debug_poison_workspace(self.handle(), _lib.stream_ptr()), 'bsg_fs2midi_debug_poison_workspace')
+    def __init__(self, dictionary, out_dims=None):
+        super().__init__()
+        hp = hparams
+        check_fs2_hparams(hp, plain=True)
+        assert hp['ffn_act'] == 'gelu' and hp['ffn_padding'] == 'SAME' and hp['use_pos_embed']
+        self._init_base(dictionary, out_dims)
+        self.encoder = FastspeechEncoder(self.encoder_embed_tokens)
+        self._init_tail(out_dims)
 
-    @torch.no_grad()
-    def regulate(self, enc):
-        """LengthRegulator on the predicted durations (tts_modules.py:161-191); one host sync, as in the
-        reference (the output length is data dependent, :182)."""
-        dur, txt = enc['dur'], enc['txt']
-        B, Tt = txt.shape
-        T = int((dur * (txt != 0)).sum(-1).max().item())
-        if T <= 0:
-            raise _lib.BsgError('duration predictor produced an empty utterance')
-        mel2ph = torch.empty(B, T, dtype=torch.long, device=txt.device)
-        with torch.cuda.device(txt.device):
-            _lib.check(_lib.load().bsg_length_regulator(_lib.ptr(dur), _lib.ptr(txt), _lib.ptr(mel2ph), B, Tt, T,
-                                                        _lib.stream_ptr()), 'bsg_length_regulator')
-        return mel2ph
+    def _token_table(self):
+        return self.encoder.embed_positions.table(DEFAULT_MAX_TARGET_POSITIONS + 2)
 
     @torch.no_grad()
-    def decode(self, enc_out, mel2ph, spk, speechsing, skip_decoder=False):
-        """Frame-level part: gather by mel2ph, +spk +style, mask; FFT decoder + mel_out   (fs2.py:166-195)."""
-        dev = enc_out.device
+    def encode(self, txt_tokens, spk_embed, predict_dur=False, rows=None, **kwargs):
+        """Token-level front (fs2.py:100-129): one embedding launch, the FFT encoder (+ duration predictor).  Nothing couples the rows of a
+        batch: ``rows`` (a contiguous slice) simply selects the rows that run."""
+        lib = _lib.load()
         h = self.handle()
-        B, Tt, _ = enc_out.shape
-        mel2ph = mel2ph.to(device=dev, dtype=torch.long).contiguous()
-        T = mel2ph.shape[1]
-        if T >= self._n_pos:
-            raise _lib.BsgError(f'T={T} exceeds the decoder position table ({self._n_pos})')
-        speechsing = speechsing.to(device=dev, dtype=torch.long).contiguous()
-        decoder_inp = torch.empty(B, T, self.hidden_size, device=dev)
-        mel_out = None if skip_decoder else torch.empty(B, T, self.out_dims, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().bsg_fs2midi_decode(h, _lib.ptr(enc_out.contiguous()), _lib.ptr(mel2ph), _lib.ptr(spk.contiguous()),
-                                                      _lib.ptr(speechsing), B, Tt, T, _lib.ptr(decoder_inp), _lib.ptr(mel_out),
-                                                      _lib.stream_ptr()), 'bsg_fs2midi_decode')
-        return decoder_inp, mel_out
-
-    def forward(self, txt_tokens, mel2ph=None, spk_embed=None, ref_mels=None, f0=None, uv=None, energy=None,
-                skip_decoder=False, spk_embed_dur_id=None, spk_embed_f0_id=None, infer=False, rows=None, **kwargs):
-        """``rows`` (slice, extension): generate only these batch rows — what a rank of a sharded run asks for (SURVEY.md §8e).  The inputs
-        stay the WHOLE batch's: the ESM attends over the batch axis, so every row's ``lang`` enters this rank's K / V; with ``mel2ph``
-        given nothing else of the other rows is computed (``encode(rows=...)``).  With predicted durations the frame count T is the
-        maximum over the whole batch (tts_modules.py:182), so the token-level front then runs on every row and is sliced afterwards."""
-        return _lib.range_guarded(lambda: self._forward(txt_tokens, mel2ph, spk_embed, skip_decoder, rows, **kwargs),
-                                  'FastSpeech2MIDI.forward', device=self, owners=(self,))
-
-    def _forward(self, txt_tokens, mel2ph, spk_embed, skip_decoder, rows, **kwargs):
-        ret = {}
-        local = rows is not None and mel2ph is not None      # the token front on this rank's rows only
-        enc = self.encode(txt_tokens, spk_embed, predict_dur=mel2ph is None, rows=rows if local else None, **kwargs)
-        if mel2ph is None:
-            mel2ph = self.regulate(enc)
-            ret['dur'] = enc['dur_xs'][:, :, None]
-            ret['dur_choice'] = enc['dur']
-        # (with mel2ph given the reference also runs the predictor for its training loss; inference does not use it)
-        enc_out, spk, speechsing = enc['enc_out'], enc['spk'], kwargs['speechsing']
+        dev = txt_tokens.device
+        txt = txt_tokens.to(device=dev, dtype=torch.long).contiguous()
+        B, Tt = txt.shape
+        if Tt >= self._n_rel:
+            raise _lib.BsgError(f'T_txt={Tt} exceeds the positional table ({self._n_rel})')
+        spk = None
+        if hasattr(self, 'spk_embed_proj'):
+            if spk_embed is None:
+                raise _lib.BsgError('use_spk_id: spk_embed (speaker ids [B]) is required')
+            spk = spk_embed.to(device=dev, dtype=torch.long).contiguous()
+        row0, nb = 0, B
         if rows is not None:
-            if not local:
-                enc_out = enc_out[rows]
-            spk, speechsing, mel2ph = spk[rows], speechsing[rows], mel2ph[rows]
-        ret['mel2ph'] = mel2ph
-        ret['decoder_inp'], mel_out = self.decode(enc_out, mel2ph, spk, speechsing, skip_decoder)
-        if not skip_decoder:
-            ret['mel_out'] = mel_out
-        return ret
+            row0, stop, stride = rows.indices(B)
+            if stride != 1 or stop <= row0:
+                raise _lib.BsgError('rows must be a contiguous non-empty slice')
+            nb = stop - row0
+        enc_out = torch.empty(nb, Tt, self.hidden_size, device=dev)
+        dur_xs = torch.empty(nb, Tt, device=dev) if predict_dur else None
+        dur = torch.empty(nb, Tt, dtype=torch.long, device=dev) if predict_dur else None
+        with torch.cuda.device(dev):
+            _lib.check(lib.bsg_fs2_encode_plain(h, _lib.ptr(txt), _lib.ptr(spk), B, Tt, row0, nb, _lib.ptr(enc_out), _lib.ptr(dur_xs),
+                                                _lib.ptr(dur), _lib.stream_ptr()), 'bsg_fs2_encode_plain')
+        return dict(enc_out=enc_out, txt=txt, spk=spk, dur_xs=dur_xs, dur=dur)

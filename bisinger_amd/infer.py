@@ -218,7 +218,8 @@ class DiffSingerE2EInfer(BaseSVSInfer):
         sample = self.input_to_batch(inp)
         output = self._generate(sample, seed)
         mel_out = output['mel_out']
-        f0_pred = self.pe(mel_out)['f0_denorm_pred'] if hparams.get('pe_enable') else None      # a-*.py:629-632
+        # a-*.py:629-632: the pitch extractor's f0, else the model's own (use_pitch_embed: FastSpeech2.add_pitch returns f0_denorm)
+        f0_pred = self.pe(mel_out)['f0_denorm_pred'] if hparams.get('pe_enable') else output.get('f0_denorm')
         wav_out = self.run_vocoder(mel_out, f0=f0_pred)
         return wav_out.cpu().numpy()[0]
 

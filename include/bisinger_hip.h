@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define BSG_ABI_VERSION 15
+#define BSG_ABI_VERSION 16
 
 #define BSG_OK 0
 #define BSG_EINVAL (-22)  /* bad argument / shape the kernels do not support            */
@@ -323,6 +323,8 @@ int bsg_fs2midi_last_rows(const bsg_fs2midi* h, int32_t* token_rows, int32_t* st
  *   <s>.gemm:h2w/<32|64|128>/<ring4|ring8|ring16|deep> gemm_h2w_kernel: rows per tile, steps of the weight ring (deep: 256-deep slices)
  *   <s>.gemm:gemm_split/<64|128> | gemm_fast/<64|128> | gemm_f32
  *                                                      launch_gemm: split-fp16 | fp32 matrix pipe | the unaligned form
+ *   tok:front                                          token_front_kernel (the plain front's embedding, ABI v16)
+ *   pit.pos pit.entry pit.gemm:<form as above> pit.ln pit.tail pit.launches:<n>   the pitch adaptor of a decode (ABI v16, bsg_fs2_decode)
  * with <s> = esm (the ESM's Linear layers), enc, dec (the FFT stacks); bsg_fftden_last_path: den, cleared by every bsg_fftden_forward.
  * The string belongs to the handle: valid until its next call or its destruction. */
 const char* bsg_fs2midi_last_path(bsg_fs2midi* h);
@@ -340,6 +342,61 @@ int bsg_length_regulator(const int64_t* dur, const int64_t* txt, int64_t* mel2ph
 int bsg_fs2midi_decode(bsg_fs2midi* h, const float* enc_out, const int64_t* mel2ph, const int64_t* spk_id,
                        const int64_t* speechsing, int32_t B, int32_t T_txt, int32_t T, float* decoder_inp,
                        float* mel_out, void* stream);
+
+/* ABI v16: the frame-level pitch adaptor (hparams['use_pitch_embed'], FastSpeech2.add_pitch, modules/fastspeech/fs2.py:201-234, with
+ * pitch_type: frame, pitch_ar: false, pitch_norm: log) and the plain FastSpeech2 front (use_midi absent or false, fs2.py:24-152:
+ * FastspeechEncoder, tts_modules.py:312-349, without rel_pos).  bsg_fs2_create returns the SAME handle type as bsg_fs2midi_create:
+ * bsg_fs2midi_decode, _last_path, _last_rows, _debug_poison_workspace, the per-handle range-guard calls and bsg_fs2midi_destroy work on
+ * it unchanged; with front = BSG_FS2_FRONT_MIDI and use_pitch_embed = 0 it is bsg_fs2midi_create. */
+#define BSG_FS2_FRONT_MIDI 0   /* FastSpeech2MIDI: ESM + MIDI / slur / language embeddings, style row in the decoder input */
+#define BSG_FS2_FRONT_PLAIN 1  /* FastSpeech2: sqrt(H) * embed_tokens[txt] + sinusoidal positions counted over the non-pad tokens */
+
+typedef struct {
+  bsg_fs2midi_cfg base;      /* plain front: esm_heads is ignored, spk_rows may be 0 (use_spk_id: false), n_rel = rows of tok_pos_table */
+  int32_t front;             /* BSG_FS2_FRONT_*                                                                                     */
+  int32_t use_pitch_embed;   /* 0 | 1; the four fields below are read only when it is 1                                             */
+  int32_t pitch_layers;      /* hparams['predictor_layers']                                                       fs2.py:75-81      */
+  int32_t pitch_kernel;      /* hparams['predictor_kernel'] (odd: ffn_padding SAME)                                                 */
+  int32_t use_uv;            /* hparams['use_uv']: uv = pitch_pred[..., 1] > 0 zeroes f0_denorm                   fs2.py:226-227    */
+  int32_t n_pitch_pos;       /* rows of pitch_pos_table (frames T must be < n_pitch_pos)                                            */
+} bsg_fs2_cfg;
+
+/* Entries of the model's state_dict() for this configuration (114 for the PopCS chain: plain front, no speaker table, 2-layer duration
+ * and pitch predictors), or BSG_EINVAL for a configuration bsg_fs2_create refuses. */
+int bsg_fs2_n_weights(const bsg_fs2_cfg* cfg);
+
+/* dev_weights in state_dict() order.  MIDI front: as bsg_fs2midi_create, with pitch_embed.weight [300,H] and pitch_predictor.{pos_embed_alpha,
+ * conv.l.1.{weight [H,H,k], bias}, conv.l.3.{weight, bias}, linear.{weight [2,H], bias}, embed_positions._float_tensor} between
+ * dur_predictor.* and esm.* when use_pitch_embed.  Plain front: encoder_embed_tokens, encoder.{layers.*, layer_norm.w,b, embed_tokens (alias),
+ * embed_positions._float_tensor}, decoder.{pos_embed_alpha, embed_positions._float_tensor, layers.*, layer_norm.w,b}, mel_out.w,b,
+ * spk_embed_proj (when spk_rows > 0), dur_predictor.*, then the pitch entries.
+ * tok_pos_table [n_rel,H]: MIDI front: rel_pos_table of bsg_fs2midi_create; plain front: the sinusoidal table the token positions index
+ * (T_txt must be < n_rel).  pitch_pos_table [n_pitch_pos,H] (NULL without use_pitch_embed): the sinusoidal table of PitchPredictor
+ * (tts_modules.py:221).  A bad configuration is BSG_EINVAL with a message before any device call. */
+int bsg_fs2_create(bsg_fs2midi** out, const bsg_fs2_cfg* cfg, const void* const* dev_weights, int32_t n_weights,
+                   const float* dec_pos_table, const float* tok_pos_table, const float* pitch_pos_table, void* stream);
+
+/* The plain front's encode (fs2.py:100-129): txt [B,T_txt] i64 (pad id 0), spk_id [B] i64 or NULL (no speaker table), for the batch rows
+ * [row0, row0 + n_rows) (nothing couples the rows of a batch: row0 = 0, n_rows = B is the whole batch).  enc_out [n_rows,T_txt,H];
+ * dur_xs / dur [n_rows,T_txt] as for bsg_fs2midi_encode.  One launch forms the embedding (tok:front in the launch record). */
+int bsg_fs2_encode_plain(bsg_fs2midi* h, const int64_t* txt, const int64_t* spk_id, int32_t B, int32_t T_txt, int32_t row0,
+                         int32_t n_rows, float* enc_out, float* dur_xs, int64_t* dur, void* stream);
+
+/* bsg_fs2midi_decode with the adaptor's inputs and outputs.  spk_id NULL without a speaker table, speechsing NULL on the plain front.
+ * f0 [B,T] f32 (log2 Hz) and uv [B,T] f32 (> 0 = unvoiced) are supplied values or NULL = the predictor's (uv is ignored without use_uv);
+ * neither is written.  pitch_pred [B,T,2] (the predictor runs with supplied f0 too, as the reference's does; with predicted f0 its
+ * [..., 0] is 0 where mel2ph == 0, as the reference returns it: its in-place f0[pitch_padding] = 0 goes through a view), f0_denorm [B,T] =
+ * 2^f0, 0 where unvoiced or mel2ph == 0, pitch_bin [B,T] i64 = f0_to_coarse(f0_denorm) (utils/pitch_utils.py:22-31): each may be NULL.
+ * Without use_pitch_embed all five must be NULL.  decoder_inp = (enc[mel2ph] + pitch_embed[bin] + spk (+ style)) * (mel2ph > 0).
+ * Launch record: pit.pos, pit.entry, pit.gemm:<form> (the predictor's k-tap convolutions with bias + ReLU), pit.ln (the LayerNorm launches
+ * between the layers; absent with one layer), pit.tail (the last layer's LayerNorm, Linear(256 -> 2), exp2, zeroing, bin, embedding gather,
+ * sum and mask in one launch, one wavefront per frame) and pit.launches:<n>, the adaptor's launches of this decode counted where they
+ * were made (a form launched in every layer is named once, so the count is what tells a missing layer).
+ * Token, speaker and style ids outside their tables are clamped by the kernels of this ABI version's additions (torch raises).
+ * On a plain-front handle bsg_fs2midi_decode takes the same NULLs (spk_id without a speaker table, speechsing always). */
+int bsg_fs2_decode(bsg_fs2midi* h, const float* enc_out, const int64_t* mel2ph, const int64_t* spk_id, const int64_t* speechsing,
+                   const float* f0, const float* uv, int32_t B, int32_t T_txt, int32_t T, float* pitch_pred, float* f0_denorm,
+                   int64_t* pitch_bin, float* decoder_inp, float* mel_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * FFT candidate denoiser: DIFF_DECODERS['fft'] = FFT(hidden, dec_layers, dec_ffn_kernel_size,
