@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'lib', 'libbisinger_hip.so')
 if os.environ.get('BSG_LIB'):      # development: an alternative build of the same ABI (kernel experiments)
     LIB_PATH = os.environ['BSG_LIB']
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 
 class BsgError(RuntimeError):
@@ -80,6 +80,9 @@ _SIGS = {
     'bsg_diffnet_create': (c_int32, [POINTER(c_void_p), POINTER(DiffnetCfg), POINTER(c_void_p), c_int32, c_void_p, c_void_p]),
     'bsg_diffnet_destroy': (None, [c_void_p]),
     'bsg_diffnet_prepare': (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
+    'bsg_diffnet_prepare_tokens': (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    'bsg_fs2midi_token_rows': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    'bsg_diffnet_debug_cond_quads': (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     'bsg_diffnet_prepare_ragged': (c_int32, [c_void_p, c_void_p, POINTER(c_int32), c_int32, c_int32, c_void_p]),
     'bsg_diffnet_ragged_native': (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_int32)]),
     'bsg_ragged_plan': (c_int32, [POINTER(c_int32), c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32)]),

@@ -1119,6 +1119,19 @@ struct bsg_diffnet {
   // rows are derived from the quads by ensure_cond_rows() the first time a launch that reads them runs (655 MB less per pass at B = 16)
   size_t cap_cond_rows = 0;      // frames condterm holds (allocated on demand)
   bool cond_rows_valid = false;  // condterm holds the term of the bound condition
+  // token binding (bsg_diffnet_prepare_tokens): the term per TOKEN, [L][B][2C/4][K][4], and every frame's token id.  The token form of the
+  // 16-row stack launch gathers from it; every other launch reads the per-frame layouts above, which ensure_cond_quads() / ensure_cond_rows()
+  // expand from the table the first time such a launch runs (cond_q_valid / cond_rows_valid are false behind a token prepare)
+  float* cond_tok = nullptr;     // [L][B][2C/4][tok_K][4]
+  size_t cap_cond_tok = 0;       // B x K it holds
+  int* tok_dev = nullptr;        // [B][T] token id of every frame, clamped to [0, tok_K)
+  size_t cap_tok = 0;            // frames it holds
+  unsigned* tok_bad = nullptr;   // device word: ids the last conversion found outside [0, K)
+  int tok_K = 0;
+  bool tok_bound = false;        // the bound condition came per token (a plain prepare clears this)
+  float* cond_exp = nullptr;     // [B][H][T]: the per-frame condition of a token prepare that cannot keep the table (bf16 compute, no pre-split GEMM)
+  size_t cap_cond_exp = 0;
+  int occ_stack_tok = -1;        // resident workgroups per CU of the token form (-1: not queried)
   float* xa = nullptr;        // [B][C][T]
   float* xb = nullptr;
   float* skip = nullptr;
@@ -1207,6 +1220,10 @@ extern "C" void bsg_diffnet_destroy(bsg_diffnet* h) {
   if (h->apack1h) (void)hipFree(h->apack1h);
   if (h->condterm_h) (void)hipFree(h->condterm_h);
   if (h->condterm_q) (void)hipFree(h->condterm_q);
+  if (h->cond_tok) (void)hipFree(h->cond_tok);
+  if (h->tok_dev) (void)hipFree(h->tok_dev);
+  if (h->tok_bad) (void)hipFree(h->tok_bad);
+  if (h->cond_exp) (void)hipFree(h->cond_exp);
   if (h->skip_h) (void)hipFree(h->skip_h);
   if (h->apack2h) (void)hipFree(h->apack2h);
   if (h->tail_h) (void)hipFree(h->tail_h);
@@ -1453,8 +1470,65 @@ __global__ __launch_bounds__(256) void quad_to_rows_kernel(const float* __restri
 
 // the rows of the bound condition's term, derived from its quads the first time a launch that reads rows runs behind a prepare that wrote
 // only the quads (a fallback after a range event or a give-up, BSG_H2_Q=0 shapes, the per-layer hooks): 2 x 655 MB at B = 16, once
+// [z][R/4][K][4] -> [z][R/4][T][4] through tok [B][T] (z = l B + b): a frame's quad is a COPY of its token's, so the expanded term equals what
+// a per-frame prepare writes wherever the projection of a column does not depend on the column's place in the GEMM
+__global__ __launch_bounds__(256) void tok_to_quads_kernel(const float* __restrict__ tab, const int* __restrict__ tok, float* __restrict__ q, int R4,
+                                                           int K, int T, int B) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= T) return;
+  const long long z = blockIdx.z, qr = blockIdx.y;
+  const int k = tok[(z % B) * T + t];
+  *reinterpret_cast<f32x4*>(q + ((z * R4 + qr) * T + t) * 4) = *reinterpret_cast<const f32x4*>(tab + ((z * R4 + qr) * K + k) * 4);
+}
+
+// int64 token ids -> int32, clamped to [0, K) (as the front's gathers treat an id beyond the table); *bad counts the ids that were clamped
+__global__ void tok_convert_kernel(const long long* __restrict__ src, int* __restrict__ dst, long long n, int K, unsigned* __restrict__ bad) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const long long v = src[i];
+  const bool out = v < 0 || v >= K;
+  dst[i] = out ? 0 : (int)v;
+  if (out) atomicAdd(bad, 1u);
+}
+
+// [B][K][H] token rows -> [B][H][T] frames through tok: the per-frame condition of a token prepare that takes the per-frame path
+__global__ __launch_bounds__(256) void tok_expand_cond_kernel(const float* __restrict__ ct, const int* __restrict__ tok, float* __restrict__ cond,
+                                                              int K, int T) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= T) return;
+  const long long b = blockIdx.z;
+  const int c = blockIdx.y;
+  cond[(b * C + c) * T + t] = ct[(b * K + tok[b * T + t]) * C + c];
+}
+
+// the quads of a token binding's term, expanded from the table the first time a launch that reads per-frame quads runs behind
+// bsg_diffnet_prepare_tokens (part forms, 32-frame tiles, BSG_COND_TOK=0) — and the source of ensure_cond_rows() below
+static int ensure_cond_quads(bsg_diffnet* h, hipStream_t st) {
+  if (h->cond_q_valid || !h->tok_bound) return BSG_OK;
+  const size_t bt = (size_t)h->B * h->T;
+  if (bt > h->cap_cond_q) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (st) (void)hipStreamIsCapturing(st, &cap);
+    BSG_REQUIRE(cap == hipStreamCaptureStatusNone, "diffnet: the per-frame conditioner term of a token binding is allocated by the first eager call that reads it; run it once before capturing");
+    BSG_HIP(hipStreamSynchronize(st));
+    if (h->condterm_q) (void)hipFree(h->condterm_q);
+    h->condterm_q = nullptr;
+    h->cap_cond_q = 0;
+    BSG_HIP(hipMalloc((void**)&h->condterm_q, (size_t)h->L * 2 * C * bt * sizeof(float)));
+    h->cap_cond_q = bt;
+  }
+  const long long zs = (long long)h->L * h->B;
+  BSG_REQUIRE(zs <= 65535, "diffnet: L * B = %lld launch slices", zs);
+  hipLaunchKernelGGL(tok_to_quads_kernel, dim3(cdiv(h->T, 256), 2 * C / 4, (unsigned)zs), dim3(256), 0, st, (const float*)h->cond_tok,
+                     (const int*)h->tok_dev, h->condterm_q, 2 * C / 4, h->tok_K, h->T, h->B);
+  BSG_LAUNCH_CHECK();
+  h->cond_q_valid = true;
+  return BSG_OK;
+}
+
 static int ensure_cond_rows(bsg_diffnet* h, hipStream_t st) {
   if (h->cond_rows_valid) return BSG_OK;
+  TRY(ensure_cond_quads(h, st));
   if (!h->cond_q_valid) {
     set_error("diffnet: the conditioner term of the bound condition exists in the bf16 layout only (bound under BSG_COMPUTE_BF16); call bsg_diffnet_prepare again");
     return BSG_ESTATE;
@@ -1469,13 +1543,13 @@ static int ensure_cond_rows(bsg_diffnet* h, hipStream_t st) {
   return BSG_OK;
 }
 
-extern "C" int bsg_diffnet_prepare(bsg_diffnet* h, const float* cond, int32_t B, int32_t T, void* stream) {
-  GuardScope guard_scope(h ? &h->guard : nullptr);
-  BSG_REQUIRE(h && cond, "diffnet_prepare: null argument");
-  BSG_REQUIRE(B > 0 && T > 0, "diffnet_prepare: B=%d T=%d", B, T);
-  BSG_REQUIRE((long long)B * T < (1LL << 31) / (2 * C), "diffnet_prepare: B*T=%lld too large", (long long)B * T);
-  hipStream_t st = (hipStream_t)stream;
+// bsg_diffnet_prepare (cond: [B][H][T]) and bsg_diffnet_prepare_tokens (cond null; cond_tok [B][K][H], tok [B][T]): workspaces, flags and the
+// hoisted conditioner projection — of the B K token columns where the token table can be kept (fp32 compute, the pre-split GEMM, the quad
+// layout wanted), of the B T frames otherwise (a token call then expands its condition first)
+static int prepare_impl(bsg_diffnet* h, const float* cond, const float* cond_tok, const int64_t* tok, int32_t B, int32_t K, int32_t T,
+                        hipStream_t st) {
   h->ragged = false;   // (bsg_diffnet_prepare_ragged sets it again behind this call)
+  h->tok_bound = false;
   const size_t bt = (size_t)B * T;
   if (bt > h->cap_bt) {
     BSG_HIP(hipStreamSynchronize(st));
@@ -1553,6 +1627,77 @@ extern "C" int bsg_diffnet_prepare(bsg_diffnet* h, const float* cond, int32_t B,
   const DnSwitches& sw = dn_switches();
   bool bf16_direct = false;
   const bool h2w = sw.gemm_h2w && h->cond_h2w_ok && gemm_split_enabled() && h2w_supports(T, 2 * C, C, 1, C) && (long long)h->L * B <= 65535;
+  if (cond_tok) {
+    // the frames' token ids, converted and clamped once (the launches index the table with them unchecked)
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (st) (void)hipStreamIsCapturing(st, &cap);
+    const bool capturing = cap != hipStreamCaptureStatusNone;
+    if (bt > h->cap_tok || !h->tok_bad) {
+      BSG_HIP(hipStreamSynchronize(st));
+      if (h->tok_dev) (void)hipFree(h->tok_dev);
+      h->tok_dev = nullptr;
+      h->cap_tok = 0;
+      BSG_HIP(hipMalloc((void**)&h->tok_dev, bt * sizeof(int)));
+      h->cap_tok = bt;
+      if (!h->tok_bad) BSG_HIP(hipMalloc((void**)&h->tok_bad, sizeof(unsigned)));
+    }
+    BSG_HIP(hipMemsetAsync(h->tok_bad, 0, sizeof(unsigned), st));
+    hipLaunchKernelGGL(tok_convert_kernel, dim3(cdiv((long long)bt, 256)), dim3(256), 0, st, (const long long*)tok, h->tok_dev, (long long)bt, K, h->tok_bad);
+    BSG_LAUNCH_CHECK();
+    if (!capturing) {   // (a captured binding cannot wait: its ids are clamped, not reported)
+      unsigned bad = 0;
+      BSG_HIP(hipMemcpyAsync(&bad, h->tok_bad, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+      BSG_HIP(hipStreamSynchronize(st));
+      if (bad) h->B = h->T = 0;   // (nothing is bound: the compute calls say so)
+      BSG_REQUIRE(bad == 0, "diffnet_prepare_tokens: %u token ids outside [0, K=%d)", bad, K);
+    }
+    const size_t bk = (size_t)B * K;
+    const bool keep_table = h2w && h2w_supports(K, 2 * C, C, 1, C) && sw.cond_quad && sw.h2_q && h->compute == BSG_COMPUTE_F32 && h->apack1q &&
+                            !h->h2_off && !h->split_off;
+    if (keep_table) {
+      if (bk > h->cap_cond_planes) {
+        BSG_HIP(hipStreamSynchronize(st));
+        if (h->cond_planes) (void)hipFree(h->cond_planes);
+        h->cond_planes = nullptr;
+        h->cap_cond_planes = 0;
+        BSG_HIP(hipMalloc((void**)&h->cond_planes, 2 * bk * C * sizeof(unsigned short)));
+        h->cap_cond_planes = bk;
+      }
+      if (bk > h->cap_cond_tok) {
+        BSG_HIP(hipStreamSynchronize(st));
+        if (h->cond_tok) (void)hipFree(h->cond_tok);
+        h->cond_tok = nullptr;
+        h->cap_cond_tok = 0;
+        BSG_HIP(hipMalloc((void**)&h->cond_tok, (size_t)h->L * 2 * C * bk * sizeof(float)));
+        h->cap_cond_tok = bk;
+      }
+      // the token rows are [B][K][H] already: split in place of the transposing split, then the SAME launch and epilogue as the per-frame
+      // hoist below with K columns per item instead of T, quads only
+      TRY(h2w_split_rows(cond_tok, h->cond_planes, h->cond_planes + bk * C, (long long)bk, C, C, st));
+      H2wArgs g{};
+      g.Cq = h->cond_tok;
+      g.act = h->cond_planes; g.act_plane = (long long)bk * C; g.lda = C; g.sAct = (long long)K * C; g.wpack = h->wcond_pack;
+      g.sW = (long long)2 * 2 * C * C; g.zdiv = B; g.rows = K; g.K = C; g.Wn = 2 * C; g.taps = 1; g.act_is_a = 0; g.C = nullptr; g.ldc = K;
+      g.sC = (long long)2 * C * K; g.bias = h->b_cond; g.sBias = 2 * C; g.alpha = 1.f; g.act_fn = ACT_NONE; g.batch = h->L * B;
+      TRY(launch_gemm_h2w(g, st));
+      h->tok_K = K;
+      h->tok_bound = true;
+      h->prepared_compute = h->compute;
+      return BSG_OK;
+    }
+    // no table in this state (bf16 compute, the GEMMs on the fp32 matrix pipe, a handle demoted off the 16-row launch): the per-frame path
+    if (bt > h->cap_cond_exp) {
+      BSG_HIP(hipStreamSynchronize(st));
+      dev_free(h->cond_exp);
+      h->cap_cond_exp = 0;
+      TRY(dev_alloc(&h->cond_exp, C * bt));
+      h->cap_cond_exp = bt;
+    }
+    BSG_REQUIRE(B <= 65535, "diffnet_prepare_tokens: B=%d", B);
+    hipLaunchKernelGGL(tok_expand_cond_kernel, dim3(cdiv(T, 256), C, B), dim3(256), 0, st, cond_tok, (const int*)h->tok_dev, h->cond_exp, K, T);
+    BSG_LAUNCH_CHECK();
+    cond = h->cond_exp;
+  }
   if (h2w) {
     // All L projections of all B rows as ONE launch on the 16-bit matrix pipe with pre-split operands (gemm_h2w.hip): cond is transposed and
     // split once into hi / lo fp16 planes [B][T][H]; the weights were split at create; batch index z = l B + b writes condterm[l][b] =
@@ -1620,6 +1765,23 @@ extern "C" int bsg_diffnet_prepare(bsg_diffnet* h, const float* cond, int32_t B,
   return BSG_OK;
 }
 
+extern "C" int bsg_diffnet_prepare(bsg_diffnet* h, const float* cond, int32_t B, int32_t T, void* stream) {
+  GuardScope guard_scope(h ? &h->guard : nullptr);
+  BSG_REQUIRE(h && cond, "diffnet_prepare: null argument");
+  BSG_REQUIRE(B > 0 && T > 0, "diffnet_prepare: B=%d T=%d", B, T);
+  BSG_REQUIRE((long long)B * T < (1LL << 31) / (2 * C), "diffnet_prepare: B*T=%lld too large", (long long)B * T);
+  return prepare_impl(h, cond, nullptr, nullptr, B, 0, T, (hipStream_t)stream);
+}
+
+extern "C" int bsg_diffnet_prepare_tokens(bsg_diffnet* h, const float* cond_tok, const int64_t* tok, int32_t B, int32_t K, int32_t T, void* stream) {
+  GuardScope guard_scope(h ? &h->guard : nullptr);
+  BSG_REQUIRE(h && cond_tok && tok, "diffnet_prepare_tokens: null argument");
+  BSG_REQUIRE(B > 0 && T > 0 && K > 0, "diffnet_prepare_tokens: B=%d K=%d T=%d", B, K, T);
+  BSG_REQUIRE((long long)B * T < (1LL << 31) / (2 * C), "diffnet_prepare_tokens: B*T=%lld too large", (long long)B * T);
+  BSG_REQUIRE((long long)B * K < (1LL << 31) / (2 * C), "diffnet_prepare_tokens: B*K=%lld too large", (long long)B * K);
+  return prepare_impl(h, nullptr, cond_tok, tok, B, K, T, (hipStream_t)stream);
+}
+
 // GEMM1 of the residual block: BSG_WINO unset = 2: Winograd F(2,3) kernels, and the F(4,3) stack launch (diffnet_f43.hip) for launches
 // that fill the chip with 64-frame tiles (plan_stack; BSG_STACK43=2: for any shape); 1: F(2,3) only; 0: the direct K=768 form
 static bool use_wino() { return dn_switches().wino != 0; }
@@ -1685,6 +1847,7 @@ struct StackPlan {
   int parts = 0;        // STACK_PART: workgroups per tile (4: quads, 2: pairs)
   int rows = 0;         // rows per launch group
   bool ragged = false;  // a ragged call: one launch per group of the plan bound by bsg_diffnet_prepare_ragged (rows = B)
+  bool tok = false;     // STACK_H2Q on 64-frame tiles behind a token binding: the launch gathers the conditioner term from the token table
   LayerForm layer = LAYER_PLAIN;   // STACK_NONE: the form of the per-layer launches
   bool small_lds = false;          // ... and the pair / 4-way form at the un-padded LDS size (PLAN_HALF_SMALL)
   int row0 = 0;         // the launches work on rows [row0, row0 + B) of the bound batch (the second half-batch chain of dual_fork)
@@ -1887,6 +2050,11 @@ static void stack_form(bsg_diffnet* h, StackPlan& plan, int B, int T, hipStream_
         plan.form = q ? STACK_H2Q : STACK_H2;
         plan.nct = nct;
         plan.rows = h->num_cus / tpr < B ? h->num_cus / tpr : B;
+        // the token form: a token binding, the 16-row launch at 64-frame tiles (BSG_COND_TOK=0: the expanded per-frame term instead)
+        if (q && nct == 2 && h->tok_bound && sw.cond_tok) {
+          if (h->occ_stack_tok < 0) h->occ_stack_tok = stack_h2q_tok_occupancy() >= 1 ? 1 : 0;
+          plan.tok = h->occ_stack_tok >= 1;
+        }
         return;
       }
     }
@@ -1923,7 +2091,7 @@ static const char* stack_path(const StackPlan& plan, bool tail) {
   switch (plan.form) {
     case STACK_F43: return "stack_f43";
     case STACK_H2: return tail ? "stack_h2_tail" : "stack_h2";
-    case STACK_H2Q: return plan.ragged ? (tail ? "stack_h2q_ragged_tail" : "stack_h2q_ragged") : tail ? "stack_h2q_tail" : "stack_h2q";
+    case STACK_H2Q: return plan.tok ? (tail ? "stack_h2q_tok_tail" : "stack_h2q_tok") : plan.ragged ? (tail ? "stack_h2q_ragged_tail" : "stack_h2q_ragged") : tail ? "stack_h2q_tail" : "stack_h2q";
     case STACK_PART: return plan.parts == 2 ? "stack_h2_pair64" : plan.nct == 2 ? "stack_h2_quad64" : "stack_h2_quad";
     case STACK_BF16: return plan.ragged ? "stack_bf16_ragged" : "stack_bf16";
     default: return "none";
@@ -2010,6 +2178,13 @@ static int stack_args(bsg_diffnet* h, const StackPlan& plan, int g, const long l
   p.apack1s = h->apack1s; p.apack2s = h->apack2s; p.h2_scale = h->h2_scale;
   p.apack1q = h->apack1q; p.apack2q = h->apack2q;
   p.condterm_q = plan.form != STACK_H2 && h->cond_q_valid ? h->condterm_q + row * 2 * C * T : nullptr;
+  if (plan.tok) {
+    BSG_REQUIRE(h->tok_bound && h->cond_tok && h->tok_dev && plan.form == STACK_H2Q, "stack launch: no token binding");
+    p.condterm_q = h->cond_tok + row * 2 * C * h->tok_K;
+    p.ct_stride = (long long)2 * C * h->B * h->tok_K;
+    p.tok = h->tok_dev + row * T;
+    p.tok_K = h->tok_K;
+  }
   if (part) {
     TRY(grow_part_bufs(h, (size_t)p.n_tiles * plan.nct, st));
     p.zx = h->part_zx; p.ix = h->part_ix; p.pflags = h->part_flags;
@@ -2108,7 +2283,10 @@ static bool cond_rows_needed(const bsg_diffnet* h, const StackPlan& plan) {
   if (h->compute == BSG_COMPUTE_BF16) return false;
   return !((plan.form == STACK_H2Q || plan.form == STACK_PART) && h->cond_q_valid);
 }
+// (behind a token binding: nothing for the token form, the expanded quads for the other launches that read quads, the rows for the rest)
 static int cond_layout_for(bsg_diffnet* h, const StackPlan& plan, hipStream_t st) {
+  if (plan.tok) return BSG_OK;
+  if (h->tok_bound && (plan.form == STACK_H2Q || plan.form == STACK_PART)) TRY(ensure_cond_quads(h, st));
   return cond_rows_needed(h, plan) ? ensure_cond_rows(h, st) : BSG_OK;
 }
 
@@ -2549,6 +2727,19 @@ extern "C" int bsg_diffnet_debug_stack_stamps(bsg_diffnet* h, int32_t t_uniform,
 }
 
 extern "C" const char* bsg_diffnet_last_path(bsg_diffnet* h) { return h ? h->last_path : "none"; }
+
+// test hook: the per-frame conditioner term of the bound condition in channel-quad order — behind a token binding its expansion
+extern "C" int bsg_diffnet_debug_cond_quads(bsg_diffnet* h, float* out, int32_t B, int32_t T, void* stream) {
+  TRY(check_bound(h, B, T, "diffnet_debug_cond_quads"));
+  BSG_REQUIRE(out, "diffnet_debug_cond_quads: null argument");
+  TRY(ensure_cond_quads(h, (hipStream_t)stream));
+  if (!h->cond_q_valid) {
+    set_error("diffnet_debug_cond_quads: the bound condition's term was not written in channel-quad order");
+    return BSG_ESTATE;
+  }
+  BSG_HIP(hipMemcpyAsync(out, h->condterm_q, (size_t)h->L * 2 * C * B * T * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return BSG_OK;
+}
 extern "C" int bsg_diffnet_last_launch(bsg_diffnet* h, int32_t* chains, int32_t* groups) {
   BSG_REQUIRE(h && chains && groups, "diffnet_last_launch: null argument");
   *chains = h->last_chains;

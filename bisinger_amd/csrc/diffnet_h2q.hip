@@ -170,15 +170,25 @@ __device__ __forceinline__ void mfma_pipe_q(f32x4q (&c)[4][NQ], f16x8 (&A)[NS][8
 // frame count p.vl_len[b] is the boundary wherever T was one (right neighbour, stored columns, halo, the right-end mask of the step term,
 // the tail).  T stays the row stride.
 constexpr int Q_VARLEN = 7;
+// DIAG = Q_TOK: the TOKEN form (bsg_diffnet_prepare_tokens), arithmetic as DIAG = 0, 64-frame tiles.  The conditioner term is bound per token,
+// p.condterm_q = [L][B][2C/4][K][4], and a frame's quad is gathered through the row's token ids p.tok [B][T]: only cond_request differs.  The
+// tile's 64 token offsets (16 tok bytes) are staged in LDS once at entry (behind the bias table) and a lane reads its four right before the
+// 16 loads of a layer — four more registers live across a layer are more than the 64-frame form has.
+constexpr int Q_TOK = 8;
+#ifndef BSG_CQ_TOK_AUX
+#define BSG_CQ_TOK_AUX 0   // cache-policy bits of the token form's loads: the table (65 MB at B = 16) is re-read every step and by neighbouring lanes
+#endif
 
 template <bool FAIRB, bool TAIL, int NCT, int DIAG = 0, int NS = 2>
 __global__ __launch_bounds__(512, 2) void residual_stack_q_kernel(StackArgs p, TailArgs a) {
-  constexpr bool VARLEN = DIAG == Q_VARLEN;
+  constexpr bool VARLEN = DIAG == Q_VARLEN, TOK = DIAG == Q_TOK;
+  static_assert(!TOK || NCT == 2, "the token form is built for 64-frame tiles");
   constexpr int NT = 32 * NCT, NQ = 2 * NCT, XP = h2_xp(NCT), ZP = h2_zp(NCT);   // frames / column tiles of 16 per workgroup; bytes per plane
   extern __shared__ __attribute__((aligned(16))) char lds_raw[];
   char* xs = lds_raw;                  // [2 planes][NT + 16 frames][528 B]: hi / lo of x + d_l, frames t0-8 .. t0+NT+7
   char* zs = lds_raw + 2 * XP;         // [2 planes][NT frames][528 B]: hi / lo of 2^10 x gated activation
   float* btab = reinterpret_cast<float*>(lds_raw + 2 * XP + 2 * ZP);   // [512]: output-projection bias of the current layer
+  int* toff = reinterpret_cast<int*>(btab + 2 * C);                    // [NT] (token form): 16 x token id of the tile's frames
 
   const int n_tiles = p.n_tiles, per_xcd = (n_tiles + 7) >> 3;
   const int tile_id = ((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3);
@@ -250,6 +260,25 @@ __global__ __launch_bounds__(512, 2) void residual_stack_q_kernel(StackArgs p, T
         for (int ct = 0; ct < NQ; ++ct)
 #pragma unroll
           for (int i = 0; i < 4; ++i) y[k][ct][i] = (float)((lane * 37 + l * 13 + 29 * k + 11 * ct + 5 * i) & 31) * 0.0625f - 1.0f;
+      return;
+    }
+    if constexpr (TOK) {
+      // per token [2C/4][K][4]: the quad of frame f is the quad of token tok[f] — consecutive tokens are adjacent 16-byte pieces, so the 16 lanes
+      // of a column tile touch one or two 128-byte lines per channel quad
+      const int K16 = p.tok_K * 16;
+      const rsrc_t rs_cq = mk_rsrc(p.condterm_q + (long long)l * p.ct_stride + (long long)b * 2 * C * p.tok_K, (unsigned)(2 * C * p.tok_K * 4));
+      int vt[NQ];
+#pragma unroll
+      for (int ct = 0; ct < NQ; ++ct) vt[ct] = toff[n16 + 16 * ct] + q4 * K16;
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt) {
+        const int so = (8 * wave + 4 * rt) * K16;
+#pragma unroll
+        for (int ct = 0; ct < NQ; ++ct) {
+          y[rt][ct] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_cq, vt[ct], so, BSG_CQ_TOK_AUX));
+          y[2 + rt][ct] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_cq, vt[ct], so + (C / 4) * K16, BSG_CQ_TOK_AUX));
+        }
+      }
       return;
     }
     if (p.condterm_q) {
@@ -380,6 +409,10 @@ __global__ __launch_bounds__(512, 2) void residual_stack_q_kernel(StackArgs p, T
     *reinterpret_cast<u32x4*>(xs + XP + hrow * ROWB + hc * 16) = wl;
   }
   btab[tid] = p.bias_out[tid];
+  if constexpr (TOK) {
+    if (tid < NT) toff[tid] = t0 + tid < Tl ? 16 * p.tok[(long long)b * T + t0 + tid] : 0;   // (frames beyond the row: token 0)
+    __syncthreads();
+  }
   cond_request(0);
   dconv_request(0);
   __syncthreads();
@@ -736,6 +769,34 @@ static int h2q_launch_varlen(const StackArgs& p, const TailArgs* tail, hipStream
   return BSG_OK;
 }
 
+// the token form (p.tok set): 64-frame tiles, time-sliced issue priority, as the ragged form
+static int h2q_launch_tok(const StackArgs& p, const TailArgs* tail, hipStream_t st) {
+  const dim3 grid(8 * cdiv(p.n_tiles, 8)), block(512);
+  const TailArgs a = tail ? *tail : TailArgs{};
+  const size_t lds = h2_lds(2);
+  static bool attr = false;
+  if (!attr) {
+    BSG_HIP(hipFuncSetAttribute((const void*)residual_stack_q_kernel<true, false, 2, Q_TOK, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    BSG_HIP(hipFuncSetAttribute((const void*)residual_stack_q_kernel<true, true, 2, Q_TOK, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    attr = true;
+  }
+  if (tail) hipLaunchKernelGGL((residual_stack_q_kernel<true, true, 2, Q_TOK, 2>), grid, block, lds, st, p, a);
+  else hipLaunchKernelGGL((residual_stack_q_kernel<true, false, 2, Q_TOK, 2>), grid, block, lds, st, p, a);
+  BSG_LAUNCH_CHECK();
+  return BSG_OK;
+}
+
+// resident workgroups per CU (0 on error) of the token form
+int stack_h2q_tok_occupancy() {
+  int o = 0;
+  const int lds = (int)h2_lds(2);
+  if (hipFuncSetAttribute((const void*)residual_stack_q_kernel<true, false, 2, Q_TOK, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
+      hipFuncSetAttribute((const void*)residual_stack_q_kernel<true, true, 2, Q_TOK, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, (const void*)residual_stack_q_kernel<true, true, 2, Q_TOK, 2>, 512, lds) != hipSuccess)
+    return 0;
+  return o;
+}
+
 // resident workgroups per CU (0 on error) of the ragged form
 int stack_h2q_varlen_occupancy() {
   int o = 0;
@@ -753,6 +814,10 @@ int launch_residual_stack_h2q(const StackArgs& p, const TailArgs* tail, hipStrea
   if (p.vl_tiles) {
     BSG_REQUIRE(nct == 2 && p.vl_len, "16-row stack launch: the ragged form takes 64-frame tiles and the row lengths");
     return h2q_launch_varlen(p, tail, st);
+  }
+  if (p.tok) {
+    BSG_REQUIRE(nct == 2 && p.tok_K > 0 && p.condterm_q, "16-row stack launch: the token form takes 64-frame tiles and the token table");
+    return h2q_launch_tok(p, tail, st);
   }
   const int ns = ring_depth(nct);
   if (nct == 1) return ns == 2 ? h2q_launch<1, 2>(p, tail, st) : h2q_launch<1, NS_DEEP_32>(p, tail, st);

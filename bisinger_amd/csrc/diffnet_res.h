@@ -84,6 +84,9 @@ struct StackArgs {
   // ragged launch (residual_stack_q_kernel<.., VARLEN = true>, residual_stack_bf16_varlen_kernel; bsg_diffnet_prepare_ragged); null otherwise
   const int2* vl_tiles;   // [n_tiles] {row of the bound batch, column tile in the row}: each row's tiles contiguous, in order
   const int* vl_len;      // [B] frames of every row of the bound batch (<= T, the row stride)
+  // token form of the 16-row launch (residual_stack_q_kernel<.., Q_TOK>; bsg_diffnet_prepare_tokens); null / 0 otherwise
+  const int* tok;         // [rows][T] token id of every frame of this launch's rows, in [0, tok_K); condterm_q is then [L][B][2C/4][tok_K][4]
+  int tok_K;              // token rows per utterance (row 0: the padding token)
 };
 
 // Launch epoch in device memory (StackArgs::epoch): taken at entry by every workgroup ...
@@ -117,6 +120,7 @@ int stack_bf16_varlen_occupancy();   // its ragged form (p.vl_tiles set: launch_
 int stack_h2_occupancy(int nct);   // nct = column tiles of 32 frames per workgroup (1 or 2)
 int stack_h2q_occupancy(int nct);  // the 16-row-tile form of the same launch (diffnet_h2q.hip)
 int stack_h2q_varlen_occupancy();   // its ragged form (64-frame tiles; resident workgroups per CU, 0 on error)
+int stack_h2q_tok_occupancy();      // its token form (64-frame tiles)
 // part forms on 16-row matrix tiles: `parts` workgroups (on as many CUs of one XCD) per tile of 32 nct frames, each C / parts channels:
 // (4, 1) quad of a 32-frame tile, (4, 2) quad of a 64-frame tile, (2, 2) pair of a 64-frame tile (8 waves); p.n_tiles tiles -> grid of 8 parts ceil(n_tiles / 8) workgroups, all resident
 int launch_residual_part_h2(const StackArgs& p, hipStream_t st, int parts, int nct);
@@ -215,6 +219,7 @@ struct DnSwitches {
   int debug_wrap_r04 = env_int("BSG_DEBUG_WRAP_R04", 0);      // 1: round 4's behaviour (only a PART launch zeroes the part flags at a wrap): the negative control of tests/test_gpu_handoff.py
   int h2q_diag = env_int("BSG_H2Q_DIAG", 0);                  // 1 .. 6: timing experiments on the 16-row launches of 64-frame tiles (diffnet_h2q.hip h2q_launch; all but 3: wrong results)
   int h2q_fair = env_int("BSG_H2Q_FAIR", 1);                  // 0: no time-sliced issue priority between the two waves of a SIMD
+  int cond_tok = env_int("BSG_COND_TOK", 1);                  // 0: behind bsg_diffnet_prepare_tokens the stack launch reads the per-frame term (expanded), not the token table
 };
 inline const DnSwitches& dn_switches() { static const DnSwitches s; return s; }
 

@@ -947,6 +947,25 @@ __global__ void gather_frames_kernel(const float* __restrict__ enc, const long l
   reinterpret_cast<f32x4*>(out + row * H)[lane] = e;
 }
 
+// The same per TOKEN: out[b,k] = what gather_frames_kernel writes for a frame with mel2ph = k, k = 0 .. Tt (row 0: the padding token) — the
+// same expression in the same order, so that out[b, mel2ph[b,t]] equals decoder_inp[b,t] bit for bit
+__global__ void token_rows_kernel(const float* __restrict__ enc, const long long* __restrict__ spk_id, const long long* __restrict__ style_id,
+                                  const float* __restrict__ Espk, const float* __restrict__ Estyle, float* __restrict__ out, long long rows,
+                                  int Tt) {
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int lane = threadIdx.x & 63;
+  const int b = (int)(row / (Tt + 1));
+  const long long ph = row - (long long)b * (Tt + 1);
+  f32x4 e = {0.f, 0.f, 0.f, 0.f};
+  if (ph > 0 && ph <= Tt) e = reinterpret_cast<const f32x4*>(enc + ((long long)b * Tt + (ph - 1)) * H)[lane];
+  if (Espk) e = e + reinterpret_cast<const f32x4*>(Espk + spk_id[b] * H)[lane];
+  if (Estyle) e = e + reinterpret_cast<const f32x4*>(Estyle + style_id[b] * H)[lane];
+  const float kp = ph > 0 ? 1.f : 0.f;
+  e = e * kp;
+  reinterpret_cast<f32x4*>(out + row * H)[lane] = e;
+}
+
 // FFTBlocks entry for the decoder (tts_modules.py:289-297): padding = (sum |x| == 0), positions =
 // cumsum(x[...,0] != 0) * (x[...,0] != 0) (utils/__init__.py:146-158), x = (x + alpha * table[pos]) * keep.
 // One wave per utterance scans T in 64-frame chunks; then every lane copies rows.
@@ -2073,6 +2092,21 @@ extern "C" int bsg_fs2midi_decode(bsg_fs2midi* h, const float* enc_out, const in
   // (spk_id / speechsing: required on a MIDI handle, NULL where a plain-front handle has no such table — decode_impl says which)
   return decode_impl(h, "fs2midi_decode", enc_out, mel2ph, spk_id, speechsing, nullptr, nullptr, B, Tt, T, nullptr, nullptr, nullptr, decoder_inp,
                      mel_out, (hipStream_t)stream);
+}
+
+extern "C" int bsg_fs2midi_token_rows(bsg_fs2midi* h, const float* enc_out, const int64_t* spk_id, const int64_t* speechsing, int32_t B,
+                                      int32_t Tt, float* cond_tok, void* stream) {
+  GuardScope guard_scope(h ? &h->guard : nullptr);
+  BSG_REQUIRE(h && enc_out && cond_tok, "fs2midi_token_rows: null argument");
+  BSG_REQUIRE(!h->use_pitch, "fs2midi_token_rows: with a frame-level pitch embedding the condition is per frame");
+  BSG_REQUIRE((spk_id != nullptr) == (h->Espk != nullptr), "fs2midi_token_rows: spk_id goes with a speaker table (spk_rows=%d)", h->cfg.spk_rows);
+  BSG_REQUIRE((speechsing != nullptr) == (h->front == BSG_FS2_FRONT_MIDI), "fs2midi_token_rows: speechsing goes with the MIDI front");
+  BSG_REQUIRE(B > 0 && Tt > 0, "fs2midi_token_rows: B=%d T_txt=%d", B, Tt);
+  const long long rows = (long long)B * (Tt + 1);
+  hipLaunchKernelGGL(token_rows_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, enc_out, (const long long*)spk_id,
+                     (const long long*)speechsing, h->Espk, h->Estyle, cond_tok, rows, Tt);
+  BSG_LAUNCH_CHECK();
+  return BSG_OK;
 }
 
 extern "C" int bsg_fs2_decode(bsg_fs2midi* h, const float* enc_out, const int64_t* mel2ph, const int64_t* spk_id, const int64_t* speechsing,

@@ -154,17 +154,7 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         ``lengths`` (B ints, 1..T): a ragged batch — the calls that follow decode row b on its first lengths[b] frames only, as if it were
         alone at T = lengths[b] (include/bisinger_hip.h bsg_diffnet_prepare_ragged; INTEGRATION.md "Ragged batches")."""
         h = self.handle()
-        # a range event of a split-fp16 launch was a property of the condition bound then: with another condition the handle tries the faster
-        # launch again — unless this is the repeated pass of an outer guarded call (GaussianDiffusion.forward recomputes cond: a NEW tensor with
-        # the same values), or the handle's inputs keep leaving the range (H2_STRIKES_MAX)
-        for attr, strikes, setter in (('_h2_range_off', '_h2_strikes', 'bsg_diffnet_set_h2'), ('_h2q_range_off', '_h2q_strikes', 'bsg_diffnet_set_h2q')):
-            off = getattr(self, attr, False)
-            if off is not False and off is not cond:
-                if _lib.in_retry() or getattr(self, strikes, 0) >= self.H2_STRIKES_MAX:
-                    setattr(self, attr, cond)
-                else:
-                    _lib.check(getattr(_lib.load(), setter)(h, 1), setter)
-                    setattr(self, attr, False)
+        self._rearm(cond)
         cond = cond.contiguous().float()
         B, H, T = cond.shape
         assert H == self.encoder_hidden
@@ -176,8 +166,42 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
                 _lib.check(_lib.load().bsg_diffnet_prepare_ragged(h, _lib.ptr(cond), (c_int32 * B)(*lens), B, T, _lib.stream_ptr()),
                            'bsg_diffnet_prepare_ragged')
         self._bound = (cond, cond._version, B, T)      # strong reference: the allocator cannot hand this address to another tensor
+        self._bound_tok = None
         self._lengths = lens
         return B, T
+
+    def prepare_tokens(self, cond_tok, tok):
+        """Bind a condition that is constant over the frames of a token: ``cond_tok`` [B,K,H] (row 0: the padding token) and ``tok`` [B,T]
+        int64 in [0,K) — equivalent to prepare(cond_tok[b, tok[b]].transpose(1, 2)) (include/bisinger_hip.h bsg_diffnet_prepare_tokens):
+        the hoisted projection runs on the B K token rows, and the fp32 16-row stack launch gathers a frame's term through ``tok``."""
+        h = self.handle()
+        self._rearm(cond_tok)
+        cond_tok = cond_tok.contiguous().float()
+        B, K, H = cond_tok.shape
+        assert H == self.encoder_hidden and tok.shape[0] == B
+        tok = tok.to(device=cond_tok.device, dtype=torch.long).contiguous()
+        T = tok.shape[1]
+        with torch.cuda.device(cond_tok.device):
+            _lib.check(_lib.load().bsg_diffnet_prepare_tokens(h, _lib.ptr(cond_tok), _lib.ptr(tok), B, K, T, _lib.stream_ptr()),
+                       'bsg_diffnet_prepare_tokens')
+        self._bound = (cond_tok, cond_tok._version, B, T)
+        self._bound_tok = tok
+        self._lengths = None
+        return B, T
+
+    def _rearm(self, cond):
+        """A range event of a split-fp16 launch was a property of the condition bound then: with another condition the handle tries the
+        faster launch again — unless this is the repeated pass of an outer guarded call (GaussianDiffusion.forward recomputes cond: a NEW
+        tensor with the same values), or the handle's inputs keep leaving the range (H2_STRIKES_MAX)."""
+        h = self.handle()
+        for attr, strikes, setter in (('_h2_range_off', '_h2_strikes', 'bsg_diffnet_set_h2'), ('_h2q_range_off', '_h2q_strikes', 'bsg_diffnet_set_h2q')):
+            off = getattr(self, attr, False)
+            if off is not False and off is not cond:
+                if _lib.in_retry() or getattr(self, strikes, 0) >= self.H2_STRIKES_MAX:
+                    setattr(self, attr, cond)
+                else:
+                    _lib.check(getattr(_lib.load(), setter)(h, 1), setter)
+                    setattr(self, attr, False)
 
     def _ensure_bound(self, cond, lengths=None):
         """Skip the hoisted conditioner work only when ``cond`` IS the tensor bound last (same object, not modified since) with the same
@@ -185,6 +209,7 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         b = self._bound
         lens = None if lengths is None else ragged_lens(lengths, cond.shape[0], cond.shape[2])
         if (self._h is None or self._key() != self._h_key or b is None or b[0] is not cond or b[1] != cond._version
+                or getattr(self, '_bound_tok', None) is not None
                 or not cond.is_contiguous() or cond.dtype != torch.float32 or getattr(self, '_lengths', None) != lens):
             self.prepare(cond, lengths)
             if cond.is_contiguous() and cond.dtype == torch.float32:
@@ -297,7 +322,9 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
             return
 
         def again():
-            if self._bound is not None:
+            if self._bound is not None and getattr(self, '_bound_tok', None) is not None:
+                self.prepare_tokens(self._bound[0], self._bound_tok)
+            elif self._bound is not None:
                 self.prepare(self._bound[0], getattr(self, '_lengths', None))
             if restore is not None:
                 restore()

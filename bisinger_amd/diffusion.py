@@ -119,13 +119,16 @@ class GaussianDiffusion(nn.Module):
 
     # ------------------------------------------------------------------ samplers
     @torch.no_grad()
-    def sample(self, cond, x, noise=None, seed=0, row0=0, B_total=None, n_steps=None, lengths=None):
+    def sample(self, cond, x, noise=None, seed=0, row0=0, B_total=None, n_steps=None, lengths=None, cond_tok=None, tok=None):
         """Run the inference loop (:258-267) from ``x`` ([B,1,M,T], modified in place) under ``cond`` [B,H,T].
         ``lengths`` (B ints): a ragged batch — row b is decoded on its first lengths[b] frames as if it were alone at T = lengths[b], and x
         beyond is left as given (INTEGRATION.md "Ragged batches").  Philox draws keep their index (global row, padded stride T), so a
         row's frames see the draws of the padded batch; the row-by-row fallback (a handle without the ragged launch:
         DiffNet.ragged_native) runs each row at T = lengths[b] and so draws other values — supplied ``noise`` gives the same result on
-        both paths."""
+        both paths.
+        ``cond_tok`` [B,K,H] with ``tok`` [B,T] (the front's token rows and mel2ph): the same condition per token,
+        cond[b, :, f] == cond_tok[b, tok[b, f]]; the WaveNet denoiser then binds the token rows (DiffNet.prepare_tokens) and ``cond`` is
+        not read.  Not with ``lengths``."""
         lib = _lib.load()
         B, _, M, T = x.shape
         assert x.is_contiguous() and x.dtype == torch.float32
@@ -133,7 +136,9 @@ class GaussianDiffusion(nn.Module):
             raise ValueError('sample(): the PLMS loop (pndm_speedup) is deterministic after x_T and always runs the whole '
                              'schedule; n_steps / noise only apply to the DDPM loop')
         from .diffnet import DiffNet
-        if lengths is None:
+        if lengths is None and cond_tok is not None and tok is not None and isinstance(self.denoise_fn, DiffNet):
+            self.denoise_fn.prepare_tokens(cond_tok, tok)
+        elif lengths is None:
             self.denoise_fn.prepare(cond)
         elif not isinstance(self.denoise_fn, DiffNet):
             raise NotImplementedError('sample(lengths=...): ragged batches need the WaveNet denoiser (DiffNet)')
@@ -319,8 +324,12 @@ class GaussianDiffusion(nn.Module):
         if ragged:
             mel2ph = ret['mel2ph'] if mel2ph is None else mel2ph      # (the predicted one also masks mel_out below)
             lengths = ragged_lengths(mel2ph)
+        # the MIDI front without a frame-level pitch embedding gives the condition per token as well: the denoiser binds that
+        # (the rows are the front's hand-over to the denoiser, not a result: the returned dict keeps the reference's keys)
+        cond_tok = ret.pop('cond_tok', None)
+        tok = ret['mel2ph'] if cond_tok is not None and not ragged else None
         x = self.sample(cond, x, noise=None if hparams.get('pndm_speedup') else steps, seed=seed, row0=row0, B_total=B_total,
-                        lengths=lengths)
+                        lengths=lengths, cond_tok=cond_tok if tok is not None else None, tok=tok)
         out = torch.empty(B, T, M, device=cond.device)
         m2p = None if mel2ph is None else mel2ph.to(device=cond.device, dtype=torch.long).contiguous()
         with torch.cuda.device(cond.device):

@@ -403,7 +403,15 @@ class _FastSpeech2Base(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
                 _lib.check(lib.bsg_fs2midi_decode(h, _lib.ptr(enc_out.contiguous()), _lib.ptr(mel2ph), _lib.ptr(spk),
                                                   _lib.ptr(speechsing), B, Tt, T, _lib.ptr(decoder_inp), _lib.ptr(mel_out),
                                                   _lib.stream_ptr()), 'bsg_fs2midi_decode')
-            return dict(decoder_inp=decoder_inp) if skip_decoder else dict(decoder_inp=decoder_inp, mel_out=mel_out)
+                # the same condition per token (row 0: padding): every frame of a token carries one vector, and the denoiser binds the
+                # Tt + 1 rows instead of the T frames (DiffNet.prepare_tokens); cond_tok[b, mel2ph[b, f]] == decoder_inp[b, f] bit for bit
+                cond_tok = torch.empty(B, Tt + 1, self.hidden_size, device=dev)
+                _lib.check(lib.bsg_fs2midi_token_rows(h, _lib.ptr(enc_out.contiguous()), _lib.ptr(spk), _lib.ptr(speechsing), B, Tt,
+                                                      _lib.ptr(cond_tok), _lib.stream_ptr()), 'bsg_fs2midi_token_rows')
+            ret = dict(decoder_inp=decoder_inp, cond_tok=cond_tok)
+            if not skip_decoder:
+                ret['mel_out'] = mel_out
+            return ret
         pred = f0d = bins = None
         if self.use_pitch_embed:
             f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define BSG_ABI_VERSION 16
+#define BSG_ABI_VERSION 17
 
 #define BSG_OK 0
 #define BSG_EINVAL (-22)  /* bad argument / shape the kernels do not support            */
@@ -97,6 +97,23 @@ int bsg_diffnet_forward(bsg_diffnet* h, const float* x, const int64_t* t, float*
 int bsg_diffnet_prepare_ragged(bsg_diffnet* h, const float* cond, const int32_t* lens, int32_t B, int32_t T, void* stream);
 int bsg_diffnet_ragged_native(bsg_diffnet* h, int32_t B, int32_t T, int32_t* native);
 int bsg_ragged_plan(const int32_t* lens, int32_t B, int32_t tile_frames, int32_t cus, int32_t* group_of_row, int32_t* n_groups);
+
+/* ABI v17, a condition that is constant over the frames of a token (the FastSpeech2-MIDI front without a frame-level pitch embedding:
+ * decoder_inp[f] = (enc[mel2ph[f]] + spk + style) (mel2ph[f] > 0), fs2.py:225-228): bind it per TOKEN.
+ * bsg_diffnet_prepare_tokens: cond_tok [B,K,H] fp32 (K token rows, row 0 = the padding token), tok [B,T] i64 with values in [0,K).
+ *   Equivalent to bsg_diffnet_prepare on cond[b][:,f] = cond_tok[b][tok[b][f]]: same workspaces, flags and guard scope.  The hoisted
+ *   projection runs on the B K token columns only and is kept as a table [L,B,2C/4,K,4]; no per-frame term is written.  The fp32 16-row
+ *   stack launch on 64-frame tiles gathers from the table (bsg_diffnet_last_path "stack_h2q_tok" / "stack_h2q_tok_tail"; BSG_COND_TOK=0:
+ *   not); every other launch form reads the per-frame term, expanded from the table by a copy the first time such a launch runs (under
+ *   stream capture only when an eager call has allocated it).  Under BSG_COMPUTE_BF16, or where the handle's state has no pre-split
+ *   projection, the call expands the condition and takes the per-frame path of bsg_diffnet_prepare itself.
+ *   BSG_EINVAL for an id outside [0,K) (checked on the device; the call waits for `stream`.  Under stream capture it cannot wait: ids are
+ *   clamped to token 0 there).  A plain bsg_diffnet_prepare (and so bsg_diffnet_prepare_ragged) clears the token binding. */
+int bsg_diffnet_prepare_tokens(bsg_diffnet* h, const float* cond_tok, const int64_t* tok, int32_t B, int32_t K, int32_t T, void* stream);
+
+/* Test hook: out [L,B,2C/4,T,4] = the per-frame conditioner term of the bound condition in channel-quad order (what the 16-row stack
+ * launch loads); behind bsg_diffnet_prepare_tokens the expansion of the token table.  BSG_ESTATE where the bound state has no quads. */
+int bsg_diffnet_debug_cond_quads(bsg_diffnet* h, float* out, int32_t B, int32_t T, void* stream);
 
 /* Per-layer fused residual block alone (net.py:66-78), exported for unit tests and micro-benchmarks:
  * x_in [B,C,T], t [B] -> x_out [B,C,T]; skip [B,C,T] is read-modify-written unless layer == 0
@@ -342,6 +359,12 @@ int bsg_length_regulator(const int64_t* dur, const int64_t* txt, int64_t* mel2ph
 int bsg_fs2midi_decode(bsg_fs2midi* h, const float* enc_out, const int64_t* mel2ph, const int64_t* spk_id,
                        const int64_t* speechsing, int32_t B, int32_t T_txt, int32_t T, float* decoder_inp,
                        float* mel_out, void* stream);
+
+/* ABI v17: the condition per TOKEN, for bsg_diffnet_prepare_tokens: cond_tok [B,T_txt+1,H], row 0 = the padding token (what a frame with
+ * mel2ph = 0 gets), row k = enc_out[k-1] + spk + style — the expression and order of the decode's gather, so that cond_tok[b][mel2ph[b][f]]
+ * equals decoder_inp[b][f] bit for bit.  Handles without use_pitch_embed only (with it the condition is per frame: BSG_EINVAL). */
+int bsg_fs2midi_token_rows(bsg_fs2midi* h, const float* enc_out, const int64_t* spk_id, const int64_t* speechsing, int32_t B,
+                           int32_t T_txt, float* cond_tok, void* stream);
 
 /* ABI v16: the frame-level pitch adaptor (hparams['use_pitch_embed'], FastSpeech2.add_pitch, modules/fastspeech/fs2.py:201-234, with
  * pitch_type: frame, pitch_ar: false, pitch_norm: log) and the plain FastSpeech2 front (use_midi absent or false, fs2.py:24-152:

@@ -16,6 +16,7 @@ import csv
 import glob
 import json
 import os
+import re
 import sys
 
 src, dst = sys.argv[1], sys.argv[2]
@@ -83,7 +84,9 @@ for cfg in ('f32', 'bf16', 'voc', 'voc1', 'rank', 'b1'):
                      ('residual_layer_kernel<false, true>', 'layer')],
              'bf16': [('residual_stack_bf16_kernel<true>', 'stack_bf16'), ('residual_stack_bf16_kernel<false>', 'stack_bf16'),
                       ('residual_layer_bf16_kernel<false>', 'bf16')]}.get(cfg, [])
-    cands = ([(k, 'stack_h2q') for k in per_kernel if k.startswith('residual_stack_q_kernel')] +          # 16-row matrix tiles (round 5's default)
+    # 16-row matrix tiles (round 5's default); DIAG = 8 (the 4th template argument): the token form, whose last_path is stack_h2q_tok
+    q_path = lambda k: 'stack_h2q_tok' if re.match(r'residual_stack_q_kernel<\w+, *\w+, *2, *8,', k) else 'stack_h2q'
+    cands = ([(k, q_path(k)) for k in per_kernel if k.startswith('residual_stack_q_kernel')] +
              [(k, 'stack_h2') for k in per_kernel if k.startswith('residual_stack_h2_kernel')] + cands)   # any instantiation (<FAIR, TAIL>)
     for dom, path in cands:
         if dom not in per_kernel or 'hbm_bytes_per_launch' not in per_kernel[dom]:
@@ -97,6 +100,8 @@ for cfg in ('f32', 'bf16', 'voc', 'voc1', 'rank', 'b1'):
             # (fp32 2 KB; bf16 form: in registers) + x in / skip out once per 20 layers + edges through L2
             if path in ('stack_h2', 'stack_h2q'):      # conditioner term fp32 2 KB + x in / skip out once per 20 layers + two fp16 planes of the edges through L2
                 alg_form = (2048 + 2048 / 20 + 2 * 16384 / 64) * frames
+            elif path == 'stack_h2q_tok':              # the term per token (bench: 101 token rows per 1000 frames), the rest as above
+                alg_form = (2048 * 101 / 1000 + 2048 / 20 + 2 * 16384 / 64) * frames
             else:
                 alg_form = (2048 + 2048 + 1024 / 20) * frames if cfg == 'f32' else (1024 + 2048 / 20 + 2 * 8192 / 64) * frames
         else:
