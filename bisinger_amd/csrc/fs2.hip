@@ -16,6 +16,7 @@
 // and simplicity; the unfused attention materialises the [B*H,T,T] score matrix in HBM.
 #include <math.h>
 
+#include <array>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -1271,19 +1272,25 @@ static int fs2_conv(bsg_fs2midi* h, float** dst, const void* src, int M, int Cin
   return BSG_OK;
 }
 
+// The handle's row-sized workspaces, in allocation order: destroy, ensure_ws and poison_ws all walk this one table.  `poison`: whether the
+// test hook fills it (not the position words).  w_scores, w_fsk and w_fcnt have capacities of their own (ensure_fft_ws).
+struct WsBuf { void** p; size_t per_row, elem; bool poison; };
+static std::array<WsBuf, 10> ws_table(bsg_fs2midi* h) {
+  return {{{(void**)&h->w_x, H, sizeof(float), true},      {(void**)&h->w_a, H, sizeof(float), true},
+           {(void**)&h->w_b, H, sizeof(float), true},      {(void**)&h->w_c, H, sizeof(float), true},
+           {(void**)&h->w_qkv, 3 * H, sizeof(float), true}, {(void**)&h->w_ffn, 4 * H, sizeof(float), true},
+           {(void**)&h->w_keep, 1, sizeof(float), true},   {(void**)&h->w_pos, 1, sizeof(int), false},
+           {(void**)&h->w_ap, 2 * H, sizeof(unsigned short), true}, {(void**)&h->w_fp, 2 * 4 * H, sizeof(unsigned short), true}}};
+}
+
 extern "C" void bsg_fs2midi_destroy(bsg_fs2midi* h) {
   if (!h) return;
   guard_free(&h->guard);
   for (float* p : h->owned) (void)hipFree(p);
-  float* ws[] = {h->w_x, h->w_a, h->w_b, h->w_qkv, h->w_ffn, h->w_keep, h->w_scores, h->w_c};
-  for (float* p : ws)
+  for (const WsBuf& w : ws_table(h))
+    if (*w.p) (void)hipFree(*w.p);
+  for (void* p : {(void*)h->w_scores, (void*)h->w_fsk, (void*)h->w_fcnt, (void*)h->pack_bad})
     if (p) (void)hipFree(p);
-  if (h->w_pos) (void)hipFree(h->w_pos);
-  if (h->w_ap) (void)hipFree(h->w_ap);
-  if (h->w_fp) (void)hipFree(h->w_fp);
-  if (h->w_fsk) (void)hipFree(h->w_fsk);
-  if (h->w_fcnt) (void)hipFree(h->w_fcnt);
-  if (h->pack_bad) (void)hipFree(h->pack_bad);
   for (std::vector<FftLayerW>* v : {&h->enc, &h->dec})
     for (FftLayerW& L : *v) { h2w_free(&L.p_in); h2w_free(&L.p_out); h2w_free(&L.p_ffn1); h2w_free(&L.p_ffn2); }
   for (H2wWeights* p : {&h->p_esm_q, &h->p_esm_kv, &h->p_esm_out, &h->p_esm_f0, &h->p_esm_f2}) h2w_free(p);
@@ -1351,6 +1358,36 @@ static int load_dur(bsg_fs2midi* h, const void* const* w, int& i, hipStream_t st
   return BSG_OK;
 }
 
+// decoder.*, mel_out, [spk_embed_proj], dur_predictor, [pitch_embed, pitch_predictor]: one run of tensors in the state_dict() of both fronts
+static int load_decoder(bsg_fs2midi* h, const void* const* w, int& i, hipStream_t st) {
+  const bsg_fs2midi_cfg& c = h->cfg;
+  TRY(fs2_copy(h, &h->dec_alpha, w[i++], 1, st));
+  i++;  // decoder.embed_positions._float_tensor: placeholder buffer of the reference, no meaning
+  TRY(load_fft_layers(h, h->dec, w + i, c.dec_layers, c.dec_ffn_kernel_size, st));
+  i += 10 * c.dec_layers;
+  TRY(fs2_copy(h, &h->dec_lnw, w[i++], H, st));
+  TRY(fs2_copy(h, &h->dec_lnb, w[i++], H, st));
+  TRY(fs2_copy(h, &h->mel_w, w[i++], (size_t)c.out_dims * H, st));
+  TRY(fs2_copy(h, &h->mel_b, w[i++], c.out_dims, st));
+  if (c.spk_rows > 0) TRY(fs2_copy(h, &h->Espk, w[i++], (size_t)c.spk_rows * H, st));
+  TRY(load_dur(h, w, i, st));
+  if (h->use_pitch) TRY(load_pitch(h, w, i, st));
+  return BSG_OK;
+}
+
+// The end of every create: the position tables (tok_table: none for the FFT denoiser), then the read-back of the packing (h2w_ok)
+static int create_tail(bsg_fs2midi* h, const float* dec_table, const float* tok_table, const float* pitch_table, hipStream_t st) {
+  const bsg_fs2midi_cfg& c = h->cfg;
+  TRY(fs2_copy(h, &h->dec_table, dec_table, (size_t)c.n_pos * H, st));
+  if (tok_table) TRY(fs2_copy(h, &h->rel_table, tok_table, (size_t)c.n_rel * H, st));
+  if (h->use_pitch) TRY(fs2_copy(h, &h->pit_table, pitch_table, (size_t)h->n_pitch_pos * H, st));
+  unsigned bad = 0;
+  BSG_HIP(hipMemcpyAsync(&bad, h->pack_bad, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  BSG_HIP(hipStreamSynchronize(st));
+  h->h2w_ok = bad == 0 && c.enc_ffn_kernel_size <= 17 && c.dec_ffn_kernel_size <= 17;
+  return BSG_OK;
+}
+
 // The plain FastSpeech2 (fastspeech/fs2.py:24-89) in state_dict() order: encoder_embed_tokens, encoder.{layers, layer_norm, embed_tokens
 // (alias), embed_positions._float_tensor}, decoder.{pos_embed_alpha, embed_positions._float_tensor, layers, layer_norm}, mel_out,
 // [spk_embed_proj], dur_predictor, [pitch_embed, pitch_predictor]
@@ -1364,51 +1401,16 @@ static int fs2_create_plain(bsg_fs2midi* h, const void* const* w, const float* d
   TRY(fs2_copy(h, &h->enc_lnw, w[i++], H, st));
   TRY(fs2_copy(h, &h->enc_lnb, w[i++], H, st));
   i += 2;  // encoder.embed_tokens (alias of encoder_embed_tokens), encoder.embed_positions._float_tensor
-  TRY(fs2_copy(h, &h->dec_alpha, w[i++], 1, st));
-  i++;     // decoder.embed_positions._float_tensor
-  TRY(load_fft_layers(h, h->dec, w + i, c.dec_layers, c.dec_ffn_kernel_size, st));
-  i += 10 * c.dec_layers;
-  TRY(fs2_copy(h, &h->dec_lnw, w[i++], H, st));
-  TRY(fs2_copy(h, &h->dec_lnb, w[i++], H, st));
-  TRY(fs2_copy(h, &h->mel_w, w[i++], (size_t)c.out_dims * H, st));
-  TRY(fs2_copy(h, &h->mel_b, w[i++], c.out_dims, st));
-  if (c.spk_rows > 0) TRY(fs2_copy(h, &h->Espk, w[i++], (size_t)c.spk_rows * H, st));
-  TRY(load_dur(h, w, i, st));
-  if (h->use_pitch) TRY(load_pitch(h, w, i, st));
-  TRY(fs2_copy(h, &h->dec_table, dec_table, (size_t)c.n_pos * H, st));
-  TRY(fs2_copy(h, &h->rel_table, tok_table, (size_t)c.n_rel * H, st));
-  if (h->use_pitch) TRY(fs2_copy(h, &h->pit_table, pitch_table, (size_t)h->n_pitch_pos * H, st));
-  unsigned bad = 0;
-  BSG_HIP(hipMemcpyAsync(&bad, h->pack_bad, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  BSG_HIP(hipStreamSynchronize(st));
-  h->h2w_ok = bad == 0 && c.enc_ffn_kernel_size <= 17 && c.dec_ffn_kernel_size <= 17;
-  return BSG_OK;
+  TRY(load_decoder(h, w, i, st));
+  return create_tail(h, dec_table, tok_table, pitch_table, st);
 }
 
-static int fs2_create_impl(bsg_fs2midi* h, const void* const* w, const float* dec_table, const float* rel_table, hipStream_t st,
-                           const float* pitch_table = nullptr) {
+static int fs2_create_impl(bsg_fs2midi* h, const void* const* w, const float* dec_table, const float* rel_table, const float* pitch_table,
+                           hipStream_t st) {
   const bsg_fs2midi_cfg& c = h->cfg;
   int i = 0;
   TRY(fs2_copy(h, &h->Etok, w[i++], (size_t)c.vocab * H, st));
-  TRY(fs2_copy(h, &h->dec_alpha, w[i++], 1, st));
-  i++;  // decoder.embed_positions._float_tensor: placeholder buffer of the reference, no meaning
-  TRY(load_fft_layers(h, h->dec, w + i, c.dec_layers, c.dec_ffn_kernel_size, st));
-  i += 10 * c.dec_layers;
-  TRY(fs2_copy(h, &h->dec_lnw, w[i++], H, st));
-  TRY(fs2_copy(h, &h->dec_lnb, w[i++], H, st));
-  TRY(fs2_copy(h, &h->mel_w, w[i++], (size_t)c.out_dims * H, st));
-  TRY(fs2_copy(h, &h->mel_b, w[i++], c.out_dims, st));
-  TRY(fs2_copy(h, &h->Espk, w[i++], (size_t)c.spk_rows * H, st));
-  h->dur_conv.resize(c.dur_layers); h->dur_convb.resize(c.dur_layers); h->dur_lnw.resize(c.dur_layers); h->dur_lnb.resize(c.dur_layers);
-  for (int l = 0; l < c.dur_layers; ++l) {
-    TRY(fs2_conv(h, &h->dur_conv[l], w[i++], H, H, c.dur_kernel, st));
-    TRY(fs2_copy(h, &h->dur_convb[l], w[i++], H, st));
-    TRY(fs2_copy(h, &h->dur_lnw[l], w[i++], H, st));
-    TRY(fs2_copy(h, &h->dur_lnb[l], w[i++], H, st));
-  }
-  TRY(fs2_copy(h, &h->dur_lin_w, w[i++], H, st));
-  TRY(fs2_copy(h, &h->dur_lin_b, w[i++], 1, st));
-  if (h->use_pitch) TRY(load_pitch(h, w, i, st));
+  TRY(load_decoder(h, w, i, st));
   TRY(fs2_copy(h, &h->esm_in_w, w[i++], (size_t)3 * H * H, st));
   TRY(fs2_copy(h, &h->esm_in_b, w[i++], 3 * H, st));
   TRY(fs2_copy(h, &h->esm_out_w, w[i++], (size_t)H * H, st));
@@ -1437,47 +1439,14 @@ static int fs2_create_impl(bsg_fs2midi* h, const void* const* w, const float* de
   TRY(fs2_copy(h, &h->Eslur, w[i++], (size_t)2 * H, st));
   TRY(fs2_copy(h, &h->Elang, w[i++], (size_t)2 * H, st));
   TRY(fs2_copy(h, &h->Estyle, w[i++], (size_t)3 * H, st));
-  TRY(fs2_copy(h, &h->dec_table, dec_table, (size_t)c.n_pos * H, st));
-  TRY(fs2_copy(h, &h->rel_table, rel_table, (size_t)c.n_rel * H, st));
-  if (h->use_pitch) TRY(fs2_copy(h, &h->pit_table, pitch_table, (size_t)h->n_pitch_pos * H, st));
-  unsigned bad = 0;
-  BSG_HIP(hipMemcpyAsync(&bad, h->pack_bad, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  BSG_HIP(hipStreamSynchronize(st));
-  h->h2w_ok = bad == 0 && c.enc_ffn_kernel_size <= 17 && c.dec_ffn_kernel_size <= 17;
-  return BSG_OK;
+  return create_tail(h, dec_table, rel_table, pitch_table, st);
 }
 
 extern "C" int bsg_fs2midi_n_weights(const bsg_fs2midi_cfg* c) {
   return 3 + 10 * c->dec_layers + 2 + 2 + 1 + 4 * c->dur_layers + 2 + 12 + 10 * c->enc_layers + 2 + 1 + 12 + 6;
 }
 
-extern "C" int bsg_fs2midi_create(bsg_fs2midi** out, const bsg_fs2midi_cfg* cfg, const void* const* dev_weights,
-                                  int32_t n_weights, const float* dec_pos_table, const float* rel_pos_table, void* stream) {
-  BSG_REQUIRE(out && cfg && dev_weights && dec_pos_table && rel_pos_table, "fs2midi_create: null argument");
-  BSG_REQUIRE(cfg->hidden_size == H, "fs2midi_create: hidden_size=%d; kernels are built for 256", cfg->hidden_size);
-  BSG_REQUIRE(cfg->num_heads > 0 && H % cfg->num_heads == 0 && (H / cfg->num_heads) % 4 == 0, "fs2midi_create: num_heads=%d", cfg->num_heads);
-  BSG_REQUIRE(cfg->esm_heads == 8, "fs2midi_create: esm_heads=%d (the reference fixes 8, fs2.py:83)", cfg->esm_heads);
-  BSG_REQUIRE(cfg->enc_layers > 0 && cfg->dec_layers > 0 && cfg->dur_layers > 0 && cfg->vocab > 0 && cfg->out_dims > 0 &&
-                  cfg->out_dims % 4 == 0 && cfg->spk_rows > 0 && cfg->n_pos > 1 && cfg->n_rel > 0,
-              "fs2midi_create: bad config");
-  BSG_REQUIRE(cfg->enc_ffn_kernel_size % 2 == 1 && cfg->dec_ffn_kernel_size % 2 == 1 && cfg->dur_kernel % 2 == 1,
-              "fs2midi_create: SAME padding needs odd kernels");
-  BSG_REQUIRE(n_weights == bsg_fs2midi_n_weights(cfg), "fs2midi_create: expected %d weight tensors, got %d",
-              bsg_fs2midi_n_weights(cfg), n_weights);
-  for (int i = 0; i < n_weights; ++i) BSG_REQUIRE(dev_weights[i] != nullptr, "fs2midi_create: weight %d is null", i);
-  bsg_fs2midi* h = new bsg_fs2midi();
-  h->cfg = *cfg;
-  int rc = guard_init(&h->guard, (hipStream_t)stream);
-  if (rc == BSG_OK) rc = fs2_create_impl(h, dev_weights, dec_pos_table, rel_pos_table, (hipStream_t)stream);
-  if (rc != BSG_OK) {
-    bsg_fs2midi_destroy(h);
-    return rc;
-  }
-  *out = h;
-  return BSG_OK;
-}
-
-// every refusal of bsg_fs2_create / bsg_fs2_n_weights, before any device call
+// every refusal of bsg_fs2_create / bsg_fs2midi_create / bsg_fs2_n_weights, before any device call
 static int fs2_cfg_check(const bsg_fs2_cfg* cfg, const char* who) {
   BSG_REQUIRE(cfg, "%s: null config", who);
   const bsg_fs2midi_cfg& b = cfg->base;
@@ -1510,23 +1479,23 @@ extern "C" int bsg_fs2_n_weights(const bsg_fs2_cfg* cfg) {
   return 1 + 10 * b.enc_layers + 2 + 2 + 2 + 10 * b.dec_layers + 2 + 2 + (b.spk_rows > 0 ? 1 : 0) + 4 * b.dur_layers + 2 + pitch;
 }
 
-extern "C" int bsg_fs2_create(bsg_fs2midi** out, const bsg_fs2_cfg* cfg, const void* const* dev_weights, int32_t n_weights,
-                              const float* dec_pos_table, const float* tok_pos_table, const float* pitch_pos_table, void* stream) {
-  TRY(fs2_cfg_check(cfg, "fs2_create"));
-  BSG_REQUIRE(out && dev_weights && dec_pos_table && tok_pos_table, "fs2_create: null argument");
-  BSG_REQUIRE(!cfg->use_pitch_embed || pitch_pos_table, "fs2_create: use_pitch_embed without a pitch position table");
+// the body of both create entries; `who` keeps each entry's messages under its own name
+static int fs2_create(const char* who, bsg_fs2midi** out, const bsg_fs2_cfg* cfg, const void* const* dev_weights, int32_t n_weights,
+                      const float* dec_pos_table, const float* tok_pos_table, const float* pitch_pos_table, hipStream_t st) {
+  TRY(fs2_cfg_check(cfg, who));
+  BSG_REQUIRE(out && dev_weights && dec_pos_table && tok_pos_table, "%s: null argument", who);
+  BSG_REQUIRE(!cfg->use_pitch_embed || pitch_pos_table, "%s: use_pitch_embed without a pitch position table", who);
   const int want = bsg_fs2_n_weights(cfg);
-  BSG_REQUIRE(n_weights == want, "fs2_create: expected %d weight tensors, got %d", want, n_weights);
-  for (int i = 0; i < n_weights; ++i) BSG_REQUIRE(dev_weights[i] != nullptr, "fs2_create: weight %d is null", i);
+  BSG_REQUIRE(n_weights == want, "%s: expected %d weight tensors, got %d", who, want, n_weights);
+  for (int i = 0; i < n_weights; ++i) BSG_REQUIRE(dev_weights[i] != nullptr, "%s: weight %d is null", who, i);
   bsg_fs2midi* h = new bsg_fs2midi();
   h->cfg = cfg->base;
   h->front = cfg->front;
   h->use_pitch = cfg->use_pitch_embed;
   if (h->use_pitch) { h->pitch_layers = cfg->pitch_layers; h->pitch_kernel = cfg->pitch_kernel; h->use_uv = cfg->use_uv; h->n_pitch_pos = cfg->n_pitch_pos; }
-  int rc = guard_init(&h->guard, (hipStream_t)stream);
+  int rc = guard_init(&h->guard, st);
   if (rc == BSG_OK)
-    rc = h->front == BSG_FS2_FRONT_MIDI ? fs2_create_impl(h, dev_weights, dec_pos_table, tok_pos_table, (hipStream_t)stream, pitch_pos_table)
-                                        : fs2_create_plain(h, dev_weights, dec_pos_table, tok_pos_table, pitch_pos_table, (hipStream_t)stream);
+    rc = (h->front == BSG_FS2_FRONT_MIDI ? fs2_create_impl : fs2_create_plain)(h, dev_weights, dec_pos_table, tok_pos_table, pitch_pos_table, st);
   if (rc != BSG_OK) {
     bsg_fs2midi_destroy(h);
     return rc;
@@ -1535,59 +1504,46 @@ extern "C" int bsg_fs2_create(bsg_fs2midi** out, const bsg_fs2_cfg* cfg, const v
   return BSG_OK;
 }
 
-// workspace for `rows` token/frame rows and attention scores of batch B, length T
-static int ensure_ws(bsg_fs2midi* h, size_t rows, size_t scores, hipStream_t st) {
-  if (rows > h->cap_rows) {
-    BSG_HIP(hipStreamSynchronize(st));
-    float** bufs[] = {&h->w_x, &h->w_a, &h->w_b, &h->w_c, &h->w_qkv, &h->w_ffn, &h->w_keep};
-    for (float** p : bufs) { if (*p) (void)hipFree(*p); *p = nullptr; }
-    if (h->w_pos) { (void)hipFree(h->w_pos); h->w_pos = nullptr; }
-    if (h->w_ap) { (void)hipFree(h->w_ap); h->w_ap = nullptr; }
-    if (h->w_fp) { (void)hipFree(h->w_fp); h->w_fp = nullptr; }
-    h->cap_rows = 0;
-    BSG_HIP(hipMalloc((void**)&h->w_x, rows * H * sizeof(float)));
-    BSG_HIP(hipMalloc((void**)&h->w_a, rows * H * sizeof(float)));
-    BSG_HIP(hipMalloc((void**)&h->w_b, rows * H * sizeof(float)));
-    BSG_HIP(hipMalloc((void**)&h->w_c, rows * H * sizeof(float)));
-    BSG_HIP(hipMalloc((void**)&h->w_qkv, rows * 3 * H * sizeof(float)));
-    BSG_HIP(hipMalloc((void**)&h->w_ffn, rows * 4 * H * sizeof(float)));
-    BSG_HIP(hipMalloc((void**)&h->w_keep, rows * sizeof(float)));
-    BSG_HIP(hipMalloc((void**)&h->w_pos, rows * sizeof(int)));
-    BSG_HIP(hipMalloc((void**)&h->w_ap, 2 * rows * H * sizeof(unsigned short)));
-    BSG_HIP(hipMalloc((void**)&h->w_fp, 2 * rows * 4 * H * sizeof(unsigned short)));
-    h->cap_rows = rows;
-  }
-  (void)scores;   // the score tensor of the unfused attention is allocated on demand (ensure_scores)
+extern "C" int bsg_fs2_create(bsg_fs2midi** out, const bsg_fs2_cfg* cfg, const void* const* dev_weights, int32_t n_weights,
+                              const float* dec_pos_table, const float* tok_pos_table, const float* pitch_pos_table, void* stream) {
+  return fs2_create("fs2_create", out, cfg, dev_weights, n_weights, dec_pos_table, tok_pos_table, pitch_pos_table, (hipStream_t)stream);
+}
+
+// the extended configuration of the older entry: MIDI front, no pitch embedding
+extern "C" int bsg_fs2midi_create(bsg_fs2midi** out, const bsg_fs2midi_cfg* cfg, const void* const* dev_weights,
+                                  int32_t n_weights, const float* dec_pos_table, const float* rel_pos_table, void* stream) {
+  BSG_REQUIRE(cfg, "fs2midi_create: null argument");
+  const bsg_fs2_cfg x{*cfg, BSG_FS2_FRONT_MIDI};
+  return fs2_create("fs2midi_create", out, &x, dev_weights, n_weights, dec_pos_table, rel_pos_table, nullptr, (hipStream_t)stream);
+}
+
+// workspace for `rows` token / frame rows (ws_table); what depends on the attention form is grown by ensure_fft_ws
+static int ensure_ws(bsg_fs2midi* h, size_t rows, hipStream_t st) {
+  if (rows <= h->cap_rows) return BSG_OK;
+  BSG_HIP(hipStreamSynchronize(st));
+  h->cap_rows = 0;
+  for (const WsBuf& w : ws_table(h)) { if (*w.p) (void)hipFree(*w.p); *w.p = nullptr; }
+  for (const WsBuf& w : ws_table(h)) BSG_HIP(hipMalloc(w.p, rows * w.per_row * w.elem));
+  h->cap_rows = rows;
   return BSG_OK;
 }
 
-// [B*heads, T, T] scores: only the unfused attention path (BSG_NO_FLASH_ATTN=1, or a head dim other than 128) needs them
-static int ensure_scores(bsg_fs2midi* h, size_t scores, hipStream_t st) {
-  if (scores > h->cap_scores) {
-    BSG_HIP(hipStreamSynchronize(st));
-    if (h->w_scores) (void)hipFree(h->w_scores);
-    h->w_scores = nullptr;
-    h->cap_scores = 0;
-    BSG_HIP(hipMalloc((void**)&h->w_scores, scores * sizeof(float)));
-    h->cap_scores = scores;
-  }
-  return BSG_OK;
-}
-
-// launch_gemm / launch_gemm_h2w with the form they picked added to the handle's launch record under `tag`
-static int gemm_rec(bsg_fs2midi* h, const char* tag, GemmArgs& g, hipStream_t st) {
+// launch_gemm / launch_gemm_h2w; with `rec`, the form it picked is added to that handle's launch record under `tag`
+template <class Args>
+static int launch_rec(int (*launch)(const Args&, hipStream_t), bsg_fs2midi* rec, const char* tag, Args& g, hipStream_t st) {
   const char* form = nullptr;
-  g.form_out = &form;
-  const int rc = launch_gemm(g, st);
-  if (form) path_add(h, tag, form);
+  g.form_out = rec ? &form : nullptr;
+  const int rc = launch(g, st);
+  if (form) path_add(rec, tag, form);
   return rc;
 }
-static int h2w_rec(bsg_fs2midi* h, const char* tag, H2wArgs& g, hipStream_t st) {
-  const char* form = nullptr;
-  g.form_out = &form;
-  const int rc = launch_gemm_h2w(g, st);
-  if (form) path_add(h, tag, form);
-  return rc;
+static int gemm_rec(bsg_fs2midi* rec, const char* tag, GemmArgs& g, hipStream_t st) { return launch_rec(launch_gemm, rec, tag, g, st); }
+static int h2w_rec(bsg_fs2midi* rec, const char* tag, H2wArgs& g, hipStream_t st) { return launch_rec(launch_gemm_h2w, rec, tag, g, st); }
+// a token its stack names once, after the first launch it names (the QKV producer, the attention form): appended, never searched for
+static void path_name(bsg_fs2midi* h, bool first, const char* stack, const char* site, const char* form) {
+  if (!first) return;   // (the later layers of a stack launch the plan's same forms)
+  if (!h->path.empty()) h->path += ' ';
+  h->path.append(stack).append(site).append(form);
 }
 
 static int linear(const float* X, const float* W, const float* bias, float* Y, long long rows, int N, int K, int act,
@@ -1596,7 +1552,7 @@ static int linear(const float* X, const float* W, const float* bias, float* Y, l
   GemmArgs g{};
   g.A = X; g.B = W; g.C = Y; g.M = (int)rows; g.N = N; g.K = K; g.lda = K; g.ldb = K; g.ldc = N; g.trans_b = 1; g.taps = 1;
   g.bias_n = bias; g.alpha = alpha; g.alpha_ncols = alpha_ncols; g.act = act; g.R = R; g.ldr = N; g.rowscale = rowscale; g.batch = 1;
-  return rec ? gemm_rec(rec, tag, g, st) : launch_gemm(g, st);
+  return gemm_rec(rec, tag, g, st);
 }
 
 static int ln(const float* x, const float* w, const float* b, float* y, const float* rowscale, long long rows, float eps, hipStream_t st) {
@@ -1613,187 +1569,233 @@ static int ln_planes(const float* x, const float* w, const float* b, unsigned sh
   return BSG_OK;
 }
 // y[rows][N] = epi(planes[rows][K] W^T): Linear through gemm_h2w_kernel (W pre-split); `planes_out`: the result as planes [2][rows][N] instead
-static int linear_h2w(bsg_fs2midi* h, const char* tag, const unsigned short* planes, const H2wWeights& W, int N, const float* bias, float* Y, unsigned short* planes_out, long long rows,
+static int linear_h2w(bsg_fs2midi* rec, const char* tag, const unsigned short* planes, const H2wWeights& W, int N, const float* bias, float* Y, unsigned short* planes_out, long long rows,
                       int act, const float* R, const float* rowscale, hipStream_t st, float alpha = 1.f, int alpha_ncols = 0,
                       long long act_plane = 0) {
   H2wArgs g{};
   g.act = planes; g.act_plane = act_plane ? act_plane : rows * W.K; g.lda = W.K; g.wpack = W.pack; g.rows = (int)rows; g.K = W.K; g.Wn = W.Wn; g.taps = 1;
   g.act_is_a = 1; g.C = Y; g.ldc = N; g.out = planes_out; g.out_plane = rows * N; g.ldo = N; g.bias = bias; g.alpha = alpha;
   g.alpha_ncols = alpha_ncols; g.act_fn = act; g.R = R; g.ldr = N; g.rowscale = rowscale; g.batch = 1;
-  return h2w_rec(h, tag, g, st);
+  return h2w_rec(rec, tag, g, st);
 }
 
-// EncSALayer x FFTBlocks tail (common_layers.py:706-730, tts_modules.py:298-305); x [B*T, H] in place
-static int fft_stack(bsg_fs2midi* h, const std::vector<FftLayerW>& layers, const float* lnw, const float* lnb, int ksz,
-                     float* x, const float* keep, int B, int T, hipStream_t st, const char* tag) {
-  const long long rows = (long long)B * T;
+// The environment switches of the FFT stack and of the ESM front, with the one device probe among them: read by the first call that asks (an
+// encode or a stack: a device is current then) and never again in the process.  The probe runs then whichever GEMM path that call takes.
+struct FftSwitches {
+  bool gemm_h2w = env_int("BSG_GEMM_H2W", 1);         // =0: gemm_split_kernel (operands split while staged) instead of the pre-split GEMMs
+  bool esm_h2w = env_int("BSG_ESM_H2W", 1);           // =0: the ESM's Linear layers on gemm_split_kernel and the thread-per-query attention
+  bool flash = !getenv("BSG_NO_FLASH_ATTN");          // set at all: the score tensor + masked_softmax_kernel instead of a fused attention
+  bool flash_split = env_int("BSG_FLASH_SPLIT", 1);   // =0: the fp32-MFMA attention even while the GEMMs run split-fp16
+  bool flash_planes = env_int("BSG_FLASH_PLANES", 1); // =0: flash_attn_split_kernel (K / V split while staged) instead of the pre-split attention
+  bool qkv_fused = env_int("BSG_QKV_FUSED", 1);       // =0: fp32 QKV tensor + qkv_split_kernel instead of the QKV product's own plane output
+  int flash_ks = env_int("BSG_FLASH_KS", 0);          // 0 = auto, 1 = never split, 2 / 4 / 8 = that many key splits whenever the sequence allows
+  FftSwitches() {   // no planes attention either where the device does not grant flash_attn_planes_kernel its LDS
+    if (flash_planes && hipFuncSetAttribute(reinterpret_cast<const void*>(flash_attn_planes_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, FLP_LDS) != hipSuccess) {
+      (void)hipGetLastError();
+      flash_planes = false;
+    }
+  }
+};
+static const FftSwitches& fft_switches() { static const FftSwitches sw; return sw; }
+
+// What one FFT stack launches at (B, T): chosen once per call by plan_fft, the same for every layer.
+enum FftAttn { ATTN_PLANES, ATTN_SPLIT, ATTN_FLASH, ATTN_SOFTMAX };   // flash_attn_planes_kernel<2> · flash_attn_split_kernel<NW> · flash_attn_kernel<NW> · score tensor
+enum FftQkv { QKV_FUSED, QKV_SPLIT_KERNEL, QKV_H2W, QKV_GEMM };       // who writes what the attention reads (the index of QKV_TOKEN)
+static const char* const QKV_TOKEN[] = {"fused", "split_kernel", "h2w", "gemm"};
+struct FftPlan {
+  int B, T, Tp, ksz, heads, hd;
+  long long rows;
+  float qscale;
+  bool h2w;            // every product on launch_gemm_h2w (operands pre-split by their producers) · on launch_gemm (split while staged)
+  FftQkv qkv;
+  FftAttn attn;
+  int nw, ks;          // waves per workgroup of the attention; planes: the workgroups that share the keys of a query tile
+  const char* attn_tok;   // the form as last_path names it, set where the form is chosen
+  dim3 grid, block;    // of the attention launch (softmax: of masked_softmax_kernel)
+  size_t need_fsk, need_fcnt, need_scores;   // elements the call needs of w_fsk / w_fcnt / w_scores; 0 where the form needs none
+  // Operand views of the pre-split path: Q | K planes [2][rows][2H] in the (not yet written) FFN planes buffer w_fp; V^T planes [2][B][H][Tp] in
+  // the fp32 FFN buffer that path does not use; the key mask words [B][Tp / 32] behind them.  attn_*: where the attention writes, fp32 rows
+  // for the staged GEMM, planes (w_ap) for the pre-split one.
+  _Float16 *qk, *vt, *attn_planes;
+  long long qk_plane, vt_plane, attn_plane;
+  unsigned* km;
+  float* attn_out;
+};
+
+// Pure: reads the handle (h2w_ok, heads, its workspace pointers, gemm_split_enabled() under the call's guard scope), the switches and the
+// shape; writes nothing, allocates and launches nothing.  Every threshold is a workgroup count of the shape against a constant.
+static FftPlan plan_fft(const bsg_fs2midi* h, int B, int T, int ksz) {
+  const FftSwitches& sw = fft_switches();
+  FftPlan p{};
+  p.B = B; p.T = T; p.Tp = cdiv(T, 32) * 32; p.ksz = ksz; p.heads = h->cfg.num_heads; p.hd = H / p.heads;
+  p.rows = (long long)B * T; p.qscale = (float)sqrt(1.0 / (double)p.hd);
+  const bool split_ok = gemm_split_enabled(), flash = p.hd == 128 && sw.flash;
+  p.h2w = sw.gemm_h2w && h->h2w_ok && split_ok && sw.flash_split && flash && h2w_supports(T, 4 * H, H, ksz, H) &&
+          h2w_supports((int)p.rows, 3 * H, H, 1, H) && p.rows * 4 * H * 2 < (1LL << 31);
+  if (p.h2w && sw.flash_planes && p.Tp <= 3 * T && p.rows >= 32) {
+    // 2 waves (64 queries) per workgroup at every size: the pipelined loop keeps two score tiles live and does not fit 4 waves x 2 workgroups.
+    // Small batches: the keys of a query tile over ks workgroups (a single utterance is 32 workgroups, each a serial chain of 32 key blocks)
+    p.attn = ATTN_PLANES; p.nw = 2; p.qkv = sw.qkv_fused ? QKV_FUSED : QKV_SPLIT_KERNEL;
+    const int units = cdiv(T, 64) * B * p.heads, nb = p.Tp / 32;
+    p.ks = 1;
+    if (sw.flash_ks == 0) { while (p.ks < 4 && units * p.ks * 2 <= 512 && nb / (p.ks * 2) >= 4) p.ks *= 2; }
+    else { while (p.ks < sw.flash_ks && nb / (p.ks * 2) >= 1) p.ks *= 2; }
+    p.attn_tok = p.ks == 1 ? "planes/ks1" : p.ks == 2 ? "planes/ks2" : p.ks == 4 ? "planes/ks4" : p.ks == 8 ? "planes/ks8" : "planes/ks16+";
+    p.grid = dim3(cdiv(T, 64), B * p.heads, p.ks); p.block = dim3(128);
+    if (p.ks > 1) { p.need_fsk = (size_t)units * p.ks * (2 * 64 * 66); p.need_fcnt = (size_t)units; }
+  } else if (flash) {
+    // fused attention without planes: 2 waves per workgroup when 4 would leave CUs idle; fp32 MFMA unless the GEMMs run split-fp16
+    p.attn = p.h2w || (sw.flash_split && split_ok) ? ATTN_SPLIT : ATTN_FLASH;
+    p.nw = (long long)cdiv(T, 128) * B * p.heads >= 512 ? 4 : 2;
+    p.attn_tok = p.attn == ATTN_SPLIT ? (p.nw == 4 ? "split/nw4" : "split/nw2") : (p.nw == 4 ? "flash/nw4" : "flash/nw2");
+    p.qkv = p.h2w ? QKV_H2W : QKV_GEMM;
+    p.grid = dim3(cdiv(T, 32 * p.nw), B * p.heads); p.block = dim3(64 * p.nw);
+  } else {
+    // [B*heads, T, T] scores: only this form (BSG_NO_FLASH_ATTN, or a head dim other than 128) needs them
+    p.attn = ATTN_SOFTMAX; p.attn_tok = "softmax"; p.qkv = QKV_GEMM;
+    p.grid = dim3((unsigned)((long long)B * p.heads * T)); p.block = dim3(256);
+    p.need_scores = (size_t)B * p.heads * T * T;
+  }
+  p.qk = reinterpret_cast<_Float16*>(h->w_fp); p.qk_plane = p.rows * 2 * H;
+  p.vt = reinterpret_cast<_Float16*>(h->w_ffn); p.vt_plane = (long long)B * H * p.Tp;
+  p.km = reinterpret_cast<unsigned*>(p.vt + 2 * p.vt_plane);
+  if (p.h2w) { p.attn_planes = reinterpret_cast<_Float16*>(h->w_ap); p.attn_plane = p.rows * H; } else p.attn_out = h->w_a;
+  return p;
+}
+
+// Before the first layer, what the plan's attention form needs beyond ws_table: the key-split partials with their arrival counters (zeroed
+// when (re)allocated: the kernel leaves every counter at zero) and the score tensor.  They only grow; the stream is drained before a free.
+static int ensure_fft_ws(bsg_fs2midi* h, const FftPlan& p, hipStream_t st) {
+  if (p.need_fsk > h->cap_fsk || p.need_fcnt > h->cap_fcnt) {
+    BSG_HIP(hipStreamSynchronize(st));
+    (void)hipFree(h->w_fsk); (void)hipFree(h->w_fcnt);
+    h->w_fsk = nullptr; h->w_fcnt = nullptr; h->cap_fsk = h->cap_fcnt = 0;
+    BSG_HIP(hipMalloc((void**)&h->w_fsk, p.need_fsk * sizeof(float)));
+    BSG_HIP(hipMalloc((void**)&h->w_fcnt, p.need_fcnt * sizeof(unsigned)));
+    BSG_HIP(hipMemsetAsync(h->w_fcnt, 0, p.need_fcnt * sizeof(unsigned), st));
+    h->cap_fsk = p.need_fsk; h->cap_fcnt = p.need_fcnt;
+  }
+  if (p.need_scores > h->cap_scores) {
+    BSG_HIP(hipStreamSynchronize(st));
+    (void)hipFree(h->w_scores); h->w_scores = nullptr; h->cap_scores = 0;
+    BSG_HIP(hipMalloc((void**)&h->w_scores, p.need_scores * sizeof(float)));
+    h->cap_scores = p.need_scores;
+  }
+  return BSG_OK;
+}
+
+// Q | K | V of a layer on the pre-split path, from the LayerNorm planes in h->w_ap
+static int qkv_h2w(bsg_fs2midi* h, const char* gtag, const FftPlan& p, const FftLayerW& L, const float* keep, hipStream_t st) {
+  if (p.qkv == QKV_FUSED) {
+    H2wArgs g{};   // the QKV product writes the attention's planes itself (H2wArgs::qkv_T): no fp32 QKV tensor, no split launch
+    g.act = h->w_ap; g.act_plane = p.rows * H; g.lda = H; g.wpack = L.p_in.pack; g.rows = (int)p.rows; g.K = H; g.Wn = 3 * H; g.taps = 1; g.act_is_a = 1;
+    g.out = h->w_fp; g.out_plane = p.qk_plane; g.ldo = 2 * H; g.alpha = p.qscale; g.alpha_ncols = H; g.act_fn = ACT_NONE; g.batch = 1;
+    g.qkv_T = p.T; g.qkv_Tp = p.Tp; g.qkv_H = H; g.vt = reinterpret_cast<unsigned short*>(p.vt); g.vt_plane = p.vt_plane;
+    return h2w_rec(h, gtag, g, st);
+  }
+  TRY(linear_h2w(h, gtag, h->w_ap, L.p_in, 3 * H, nullptr, h->w_qkv, nullptr, p.rows, ACT_NONE, nullptr, nullptr, st, p.qscale, H));
+  if (p.qkv == QKV_SPLIT_KERNEL) {
+    hipLaunchKernelGGL(qkv_split_kernel, dim3(p.Tp / 32, p.B), dim3(256), 0, st, (const float*)h->w_qkv, p.qk, p.qk_plane, p.vt, p.vt_plane, p.T, p.Tp, keep, p.km, gemm_range_counter());
+    BSG_LAUNCH_CHECK();
+  }
+  return BSG_OK;
+}
+
+// The attention of a layer: the one launch site of every form, named once its kernel has been launched
+static int attention(bsg_fs2midi* h, bool first, const char* stack, const char* gtag, const FftPlan& p, const float* keep, hipStream_t st) {
+  const int T = p.T, heads = p.heads;
+  const float* qkv = h->w_qkv;
+  switch (p.attn) {
+    case ATTN_PLANES:
+      hipLaunchKernelGGL(flash_attn_planes_kernel<2>, p.grid, p.block, FLP_LDS, st, (const _Float16*)p.qk, p.qk_plane, (const _Float16*)p.vt, p.vt_plane, (const unsigned*)p.km, T, p.Tp, heads, p.attn_planes, p.attn_plane, H, gemm_range_counter(), h->w_fsk, h->w_fcnt);
+      break;
+    case ATTN_SPLIT:
+      if (p.nw == 4) hipLaunchKernelGGL(flash_attn_split_kernel<4>, p.grid, p.block, 0, st, qkv, keep, p.attn_out, T, heads, 3 * H, H, gemm_range_counter(), p.attn_planes, p.attn_plane);
+      else hipLaunchKernelGGL(flash_attn_split_kernel<2>, p.grid, p.block, 0, st, qkv, keep, p.attn_out, T, heads, 3 * H, H, gemm_range_counter(), p.attn_planes, p.attn_plane);
+      break;
+    case ATTN_FLASH:   // no [B*heads, T, T] score tensor (flash_attn_kernel)
+      if (p.nw == 4) hipLaunchKernelGGL(flash_attn_kernel<4>, p.grid, p.block, 0, st, qkv, keep, p.attn_out, T, heads, 3 * H, H);
+      else hipLaunchKernelGGL(flash_attn_kernel<2>, p.grid, p.block, 0, st, qkv, keep, p.attn_out, T, heads, 3 * H, H);
+      break;
+    case ATTN_SOFTMAX: {
+      const int hd = p.hd, nbh = p.B * heads;
+      GemmArgs s{};   // S[b,h] = Q K^T
+      s.A = qkv; s.B = qkv + H; s.C = h->w_scores; s.M = T; s.N = T; s.K = hd; s.lda = 3 * H; s.ldb = 3 * H; s.ldc = T;
+      s.trans_b = 1; s.taps = 1; s.alpha = 1.f; s.batch = nbh; s.batch2 = heads;
+      s.sA = (long long)T * 3 * H; s.sA2 = hd; s.sB = (long long)T * 3 * H; s.sB2 = hd;
+      s.sC = (long long)heads * T * T; s.sC2 = (long long)T * T;
+      TRY(gemm_rec(h, gtag, s, st));
+      hipLaunchKernelGGL(masked_softmax_kernel, p.grid, p.block, 0, st, h->w_scores, keep, T, T, heads);
+      BSG_LAUNCH_CHECK();
+      path_name(h, first, stack, "attn:", p.attn_tok);
+      GemmArgs o{};   // O[b,:,h] = P V
+      o.A = h->w_scores; o.B = qkv + 2 * H; o.C = p.attn_out; o.M = T; o.N = hd; o.K = T; o.lda = T; o.ldb = 3 * H; o.ldc = H;
+      o.trans_b = 0; o.taps = 1; o.alpha = 1.f; o.batch = nbh; o.batch2 = heads;
+      o.sA = (long long)heads * T * T; o.sA2 = (long long)T * T; o.sB = (long long)T * 3 * H; o.sB2 = hd;
+      o.sC = (long long)T * H; o.sC2 = hd;
+      return gemm_rec(h, gtag, o, st);
+    }
+  }
+  BSG_LAUNCH_CHECK();
+  path_name(h, first, stack, "attn:", p.attn_tok);
+  return BSG_OK;
+}
+
+// EncSALayer x FFTBlocks tail (common_layers.py:706-730, tts_modules.py:298-305); x [B*T, H] in place.  plan_fft decides, ensure_fft_ws
+// allocates, the loops only launch.  Every GEMM launch of every layer goes through path_add; the QKV and attention tokens are named in the
+// first layer only (`first`), the later layers launching the plan's same forms.
+static int launch_fft(bsg_fs2midi* h, const std::vector<FftLayerW>& layers, const float* lnw, const float* lnb, int ksz,
+                      float* x, const float* keep, int B, int T, hipStream_t st, const char* stack) {
+  const FftPlan p = plan_fft(h, B, T, ksz);
+  const long long rows = p.rows;
   h->last_stack_rows = (int)rows;
-  const std::string gemm_tag_s = std::string(tag) + "gemm:", attn_tag_s = std::string(tag) + "attn:", qkv_tag_s = std::string(tag) + "qkv:";
-  const char *gtag = gemm_tag_s.c_str(), *atag = attn_tag_s.c_str(), *qtag = qkv_tag_s.c_str();
-  const int heads = h->cfg.num_heads, hd = H / heads;
-  const float qscale = (float)sqrt(1.0 / (double)hd);
-  static int env_h2w = -1;   // BSG_GEMM_H2W=0: gemm_split_kernel (operands split while staged) instead of the pre-split GEMMs
-  if (env_h2w < 0) { const char* e = getenv("BSG_GEMM_H2W"); env_h2w = e ? atoi(e) : 1; }
-  static int fsplit_env = -1;
-  if (fsplit_env < 0) { const char* e = getenv("BSG_FLASH_SPLIT"); fsplit_env = e ? atoi(e) : 1; }
-  const bool h2w = env_h2w && h->h2w_ok && gemm_split_enabled() && fsplit_env && hd == 128 && !getenv("BSG_NO_FLASH_ATTN") &&
-                   h2w_supports(T, 4 * H, H, ksz, H) && h2w_supports((int)rows, 3 * H, H, 1, H) && rows * 4 * H * 2 < (1LL << 31);
-  if (h2w) {
+  TRY(ensure_fft_ws(h, p, st));
+  const std::string gemm_tag = std::string(stack) + "gemm:";
+  const char* gtag = gemm_tag.c_str();
+  const float ffn_alpha = (float)pow((double)ksz, -0.5);
+  bool first = true;
+  if (p.qkv == QKV_FUSED) {   // the key mask words once per stack: qkv_split_kernel writes them itself, the fused QKV product does not
+    hipLaunchKernelGGL(key_mask_kernel, dim3(cdiv(B * (p.Tp / 32), 4)), dim3(256), 0, st, keep, p.km, B, T, p.Tp);
+    BSG_LAUNCH_CHECK();
+  }
+  if (p.h2w) {
     // Every product on the 16-bit matrix pipe with PRE-SPLIT operands (gemm_h2w.hip): the weights were split into hi / lo fp16 fragments at
     // create, and each activation is written as hi / lo fp16 planes by the kernel that produces it (LayerNorm, the fused attention, the
-    // GELU epilogue of the FFN convolution) — no kernel splits an operand while it stages it.  Same arithmetic as the path below.
-    unsigned short* ap = h->w_ap;   // [2][rows][H]
-    unsigned short* fp = h->w_fp;   // [2][rows][4H]
-    static int fplanes = -1;        // BSG_FLASH_PLANES=0: flash_attn_split_kernel (K / V split while staged) instead of the pre-split attention
-    if (fplanes < 0) {
-      const char* e = getenv("BSG_FLASH_PLANES");
-      fplanes = e ? atoi(e) : 1;
-      if (fplanes && hipFuncSetAttribute(reinterpret_cast<const void*>(flash_attn_planes_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, FLP_LDS) != hipSuccess) {
-        (void)hipGetLastError();
-        fplanes = 0;
-      }
-    }
-    const int Tp = cdiv(T, 32) * 32;
-    static int qkv_fused = -1;   // BSG_QKV_FUSED=0: fp32 QKV tensor + qkv_split_kernel instead of the QKV product's own plane output
-    if (qkv_fused < 0) { const char* e = getenv("BSG_QKV_FUSED"); qkv_fused = e ? atoi(e) : 1; }
+    // GELU epilogue of the FFN convolution) — no kernel splits an operand while it stages it.  Same arithmetic as the loop below.
     for (const FftLayerW& L : layers) {
-      TRY(ln_planes(x, L.ln1w, L.ln1b, ap, rows, 1e-5f, st));
-      const long long wg4 = (long long)cdiv(T, 128) * B * heads;
-      const bool use_planes = fplanes && Tp <= 3 * T && rows >= 32;
-      // Q | K planes [2][rows][2H] in the (not yet written) FFN planes buffer, V^T planes [2][B][H][Tp] in the fp32 FFN buffer this path does not use
-      _Float16* qk = reinterpret_cast<_Float16*>(fp);
-      _Float16* vt = reinterpret_cast<_Float16*>(h->w_ffn);
-      const long long vplane = (long long)B * H * Tp;
-      unsigned* km = reinterpret_cast<unsigned*>(vt + 2 * vplane);   // key mask words [B][Tp / 32] behind the V^T planes
-      if (use_planes && qkv_fused) {
-        // the QKV product writes the attention's planes itself (H2wArgs::qkv_T): no fp32 QKV tensor, no split launch; the mask words once per stack
-        if (&L == &layers.front()) {
-          hipLaunchKernelGGL(key_mask_kernel, dim3(cdiv(B * (Tp / 32), 4)), dim3(256), 0, st, keep, km, B, T, Tp);
-          BSG_LAUNCH_CHECK();
-        }
-        H2wArgs g{};
-        g.act = ap; g.act_plane = rows * H; g.lda = H; g.wpack = L.p_in.pack; g.rows = (int)rows; g.K = H; g.Wn = 3 * H; g.taps = 1; g.act_is_a = 1;
-        g.out = fp; g.out_plane = rows * 2 * H; g.ldo = 2 * H; g.alpha = qscale; g.alpha_ncols = H; g.act_fn = ACT_NONE; g.batch = 1;
-        g.qkv_T = T; g.qkv_Tp = Tp; g.qkv_H = H; g.vt = h->w_ffn ? reinterpret_cast<unsigned short*>(h->w_ffn) : nullptr; g.vt_plane = vplane;
-        TRY(h2w_rec(h, gtag, g, st));
-        path_add(h, qtag, "fused");
-      } else {
-        TRY(linear_h2w(h, gtag, ap, L.p_in, 3 * H, nullptr, h->w_qkv, nullptr, rows, ACT_NONE, nullptr, nullptr, st, qscale, H));
-        path_add(h, qtag, use_planes ? "split_kernel" : "h2w");
-      }
-      if (use_planes) {
-        if (!qkv_fused) {
-          hipLaunchKernelGGL(qkv_split_kernel, dim3(Tp / 32, B), dim3(256), 0, st, (const float*)h->w_qkv, qk, rows * 2 * H, vt, vplane, T, Tp, keep, km, gemm_range_counter());
-          BSG_LAUNCH_CHECK();
-        }
-        // 2 waves (64 queries) per workgroup at every size: the pipelined loop keeps two score tiles live and does not fit 4 waves x 2 workgroups.
-        // Small batches: the keys of a query tile over KS workgroups (a single utterance is 32 workgroups, each a serial chain of 32 key blocks)
-        static int ks_env = -1;   // BSG_FLASH_KS: 0 = auto, 1 = never split, 2 / 4 / 8 = that many splits whenever the sequence allows
-        if (ks_env < 0) { const char* e = getenv("BSG_FLASH_KS"); ks_env = e ? atoi(e) : 0; }
-        const int units = cdiv(T, 64) * B * heads, nb = Tp / 32;
-        int ks = 1;
-        if (ks_env == 0) { while (ks < 4 && units * ks * 2 <= 512 && nb / (ks * 2) >= 4) ks *= 2; }
-        else { while (ks < ks_env && nb / (ks * 2) >= 1) ks *= 2; }
-        if (ks > 1) {
-          const size_t need = (size_t)units * ks * (2 * 64 * 66);
-          if (need > h->cap_fsk || (size_t)units > h->cap_fcnt) {
-            BSG_HIP(hipStreamSynchronize(st));
-            if (h->w_fsk) (void)hipFree(h->w_fsk);
-            if (h->w_fcnt) (void)hipFree(h->w_fcnt);
-            h->w_fsk = nullptr; h->w_fcnt = nullptr; h->cap_fsk = h->cap_fcnt = 0;
-            BSG_HIP(hipMalloc((void**)&h->w_fsk, need * sizeof(float)));
-            BSG_HIP(hipMalloc((void**)&h->w_fcnt, (size_t)units * sizeof(unsigned)));
-            BSG_HIP(hipMemsetAsync(h->w_fcnt, 0, (size_t)units * sizeof(unsigned), st));   // (the kernel leaves every counter at zero)
-            h->cap_fsk = need; h->cap_fcnt = (size_t)units;
-          }
-        }
-        hipLaunchKernelGGL(flash_attn_planes_kernel<2>, dim3(cdiv(T, 64), B * heads, ks), dim3(128), FLP_LDS, st, (const _Float16*)qk, rows * 2 * H, (const _Float16*)vt, vplane, (const unsigned*)km, T, Tp, heads, reinterpret_cast<_Float16*>(ap), rows * H, H, gemm_range_counter(), h->w_fsk, h->w_fcnt);
-        path_add(h, atag, ks == 1 ? "planes/ks1" : ks == 2 ? "planes/ks2" : ks == 4 ? "planes/ks4" : ks == 8 ? "planes/ks8" : "planes/ks16+");
-      } else if (wg4 >= 512) {
-        hipLaunchKernelGGL(flash_attn_split_kernel<4>, dim3(cdiv(T, 128), B * heads), dim3(256), 0, st, (const float*)h->w_qkv, keep, (float*)nullptr, T, heads, 3 * H, H, gemm_range_counter(), reinterpret_cast<_Float16*>(ap), rows * H);
-        path_add(h, atag, "split/nw4");
-      } else {
-        hipLaunchKernelGGL(flash_attn_split_kernel<2>, dim3(cdiv(T, 64), B * heads), dim3(128), 0, st, (const float*)h->w_qkv, keep, (float*)nullptr, T, heads, 3 * H, H, gemm_range_counter(), reinterpret_cast<_Float16*>(ap), rows * H);
-        path_add(h, atag, "split/nw2");
-      }
-      BSG_LAUNCH_CHECK();
-      TRY(linear_h2w(h, gtag, ap, L.p_out, H, nullptr, h->w_b, nullptr, rows, ACT_NONE, x, keep, st));   // x1 = (x + attn) * keep
-      TRY(ln_planes(h->w_b, L.ln2w, L.ln2b, ap, rows, 1e-5f, st));
-      {
-        H2wArgs g{};   // Conv1d(H -> 4H, k, SAME) * k^-1/2 -> GELU, written as the planes the second Linear reads
-        g.act = ap; g.act_plane = rows * H; g.lda = H; g.sAct = (long long)T * H; g.wpack = L.p_ffn1.pack; g.rows = T; g.K = H; g.Wn = 4 * H;
-        g.taps = ksz; g.tap_shift0 = -(ksz / 2); g.act_is_a = 1; g.out = fp; g.out_plane = rows * 4 * H; g.ldo = 4 * H; g.sO = (long long)T * 4 * H;
-        g.bias = L.ffn1b; g.alpha = (float)pow((double)ksz, -0.5); g.act_fn = ACT_GELU; g.batch = B;
-        TRY(h2w_rec(h, gtag, g, st));
-      }
-      TRY(linear_h2w(h, gtag, fp, L.p_ffn2, H, L.ffn2b, x, nullptr, rows, ACT_NONE, h->w_b, keep, st));   // x = (x1 + ffn) * keep
+      TRY(ln_planes(x, L.ln1w, L.ln1b, h->w_ap, rows, 1e-5f, st));
+      TRY(qkv_h2w(h, gtag, p, L, keep, st));
+      path_name(h, first, stack, "qkv:", QKV_TOKEN[p.qkv]);
+      TRY(attention(h, first, stack, gtag, p, keep, st));
+      TRY(linear_h2w(h, gtag, h->w_ap, L.p_out, H, nullptr, h->w_b, nullptr, rows, ACT_NONE, x, keep, st));   // x1 = (x + attn) * keep
+      TRY(ln_planes(h->w_b, L.ln2w, L.ln2b, h->w_ap, rows, 1e-5f, st));
+      H2wArgs g{};   // Conv1d(H -> 4H, k, SAME) * k^-1/2 -> GELU, written as the planes the second Linear reads
+      g.act = h->w_ap; g.act_plane = rows * H; g.lda = H; g.sAct = (long long)T * H; g.wpack = L.p_ffn1.pack; g.rows = T; g.K = H; g.Wn = 4 * H;
+      g.taps = ksz; g.tap_shift0 = -(ksz / 2); g.act_is_a = 1; g.out = h->w_fp; g.out_plane = rows * 4 * H; g.ldo = 4 * H; g.sO = (long long)T * 4 * H;
+      g.bias = L.ffn1b; g.alpha = ffn_alpha; g.act_fn = ACT_GELU; g.batch = B;
+      TRY(h2w_rec(h, gtag, g, st));
+      TRY(linear_h2w(h, gtag, h->w_fp, L.p_ffn2, H, L.ffn2b, x, nullptr, rows, ACT_NONE, h->w_b, keep, st));   // x = (x1 + ffn) * keep
+      first = false;
     }
-    TRY(ln(x, lnw, lnb, x, keep, rows, 1e-5f, st));
-    return BSG_OK;
-  }
-  for (const FftLayerW& L : layers) {
-    // --- self attention ---
-    TRY(ln(x, L.ln1w, L.ln1b, h->w_a, nullptr, rows, 1e-5f, st));
-    TRY(linear(h->w_a, L.in_proj, nullptr, h->w_qkv, rows, 3 * H, H, ACT_NONE, nullptr, nullptr, st, qscale, H, h, gtag));
-    path_add(h, qtag, "gemm");
-    if (hd == 128 && !getenv("BSG_NO_FLASH_ATTN")) {
-      // fused attention: no [B*heads, T, T] score tensor (flash_attn_kernel); 2 waves per workgroup when 4 would leave CUs idle
-      const long long wg4 = (long long)cdiv(T, 128) * B * heads;
-      static int fsplit = -1;   // BSG_FLASH_SPLIT=0: the fp32-MFMA form even while the GEMMs run split-fp16
-      if (fsplit < 0) { const char* e = getenv("BSG_FLASH_SPLIT"); fsplit = e ? atoi(e) : 1; }
-      if (fsplit && gemm_split_enabled()) {
-        if (wg4 >= 512) {
-          hipLaunchKernelGGL(flash_attn_split_kernel<4>, dim3(cdiv(T, 128), B * heads), dim3(256), 0, st, (const float*)h->w_qkv, keep, h->w_a, T, heads, 3 * H, H, gemm_range_counter(), (_Float16*)nullptr, 0LL);
-          path_add(h, atag, "split/nw4");
-        } else {
-          hipLaunchKernelGGL(flash_attn_split_kernel<2>, dim3(cdiv(T, 64), B * heads), dim3(128), 0, st, (const float*)h->w_qkv, keep, h->w_a, T, heads, 3 * H, H, gemm_range_counter(), (_Float16*)nullptr, 0LL);
-          path_add(h, atag, "split/nw2");
-        }
-      } else if (wg4 >= 512) {
-        hipLaunchKernelGGL(flash_attn_kernel<4>, dim3(cdiv(T, 128), B * heads), dim3(256), 0, st, (const float*)h->w_qkv, keep, h->w_a, T, heads, 3 * H, H);
-        path_add(h, atag, "flash/nw4");
-      } else {
-        hipLaunchKernelGGL(flash_attn_kernel<2>, dim3(cdiv(T, 64), B * heads), dim3(128), 0, st, (const float*)h->w_qkv, keep, h->w_a, T, heads, 3 * H, H);
-        path_add(h, atag, "flash/nw2");
-      }
-      BSG_LAUNCH_CHECK();
-    } else {
-      TRY(ensure_scores(h, (size_t)B * heads * T * T, st));
-      {
-      GemmArgs g{};   // S[b,h] = Q K^T
-      g.A = h->w_qkv; g.B = h->w_qkv + H; g.C = h->w_scores; g.M = T; g.N = T; g.K = hd; g.lda = 3 * H; g.ldb = 3 * H; g.ldc = T;
-      g.trans_b = 1; g.taps = 1; g.alpha = 1.f; g.batch = B * heads; g.batch2 = heads;
-      g.sA = (long long)T * 3 * H; g.sA2 = hd; g.sB = (long long)T * 3 * H; g.sB2 = hd;
-      g.sC = (long long)heads * T * T; g.sC2 = (long long)T * T;
-      TRY(gemm_rec(h, gtag, g, st));
-      }
-      hipLaunchKernelGGL(masked_softmax_kernel, dim3((unsigned)((long long)B * heads * T)), dim3(256), 0, st, h->w_scores, keep, T, T, heads);
-      BSG_LAUNCH_CHECK();
-      path_add(h, atag, "softmax");
-      {
-      GemmArgs g{};   // O[b,:,h] = P V
-      g.A = h->w_scores; g.B = h->w_qkv + 2 * H; g.C = h->w_a; g.M = T; g.N = hd; g.K = T; g.lda = T; g.ldb = 3 * H; g.ldc = H;
-      g.trans_b = 0; g.taps = 1; g.alpha = 1.f; g.batch = B * heads; g.batch2 = heads;
-      g.sA = (long long)heads * T * T; g.sA2 = (long long)T * T; g.sB = (long long)T * 3 * H; g.sB2 = hd;
-      g.sC = (long long)T * H; g.sC2 = hd;
-      TRY(gemm_rec(h, gtag, g, st));
-      }
-    }
-    TRY(linear(h->w_a, L.out_proj, nullptr, h->w_b, rows, H, H, ACT_NONE, x, keep, st, 1.f, 0, h, gtag));   // x1 = (x + attn) * keep
-    // --- conv FFN ---
-    TRY(ln(h->w_b, L.ln2w, L.ln2b, h->w_a, nullptr, rows, 1e-5f, st));
-    {
+  } else {
+    for (const FftLayerW& L : layers) {
+      TRY(ln(x, L.ln1w, L.ln1b, h->w_a, nullptr, rows, 1e-5f, st));
+      TRY(linear(h->w_a, L.in_proj, nullptr, h->w_qkv, rows, 3 * H, H, ACT_NONE, nullptr, nullptr, st, p.qscale, H, h, gtag));
+      path_name(h, first, stack, "qkv:", QKV_TOKEN[p.qkv]);
+      TRY(attention(h, first, stack, gtag, p, keep, st));
+      TRY(linear(h->w_a, L.out_proj, nullptr, h->w_b, rows, H, H, ACT_NONE, x, keep, st, 1.f, 0, h, gtag));   // x1 = (x + attn) * keep
+      TRY(ln(h->w_b, L.ln2w, L.ln2b, h->w_a, nullptr, rows, 1e-5f, st));
       GemmArgs g{};   // Conv1d(H -> 4H, k, SAME) * k^-1/2 -> GELU
       g.A = h->w_a; g.B = L.ffn1; g.C = h->w_ffn; g.M = T; g.N = 4 * H; g.K = H; g.lda = H; g.ldb = H; g.ldc = 4 * H;
       g.trans_b = 1; g.taps = ksz; g.tap_shift0 = -(ksz / 2); g.sTapB = (long long)4 * H * H;
-      g.bias_n = L.ffn1b; g.alpha = (float)pow((double)ksz, -0.5); g.act = ACT_GELU; g.batch = B;
+      g.bias_n = L.ffn1b; g.alpha = ffn_alpha; g.act = ACT_GELU; g.batch = B;
       g.sA = (long long)T * H; g.sC = (long long)T * 4 * H;
       TRY(gemm_rec(h, gtag, g, st));
+      TRY(linear(h->w_ffn, L.ffn2, L.ffn2b, x, rows, H, 4 * H, ACT_NONE, h->w_b, keep, st, 1.f, 0, h, gtag));   // x = (x1 + ffn) * keep
+      first = false;
     }
-    TRY(linear(h->w_ffn, L.ffn2, L.ffn2b, x, rows, H, 4 * H, ACT_NONE, h->w_b, keep, st, 1.f, 0, h, gtag));   // x = (x1 + ffn) * keep
   }
-  TRY(ln(x, lnw, lnb, x, keep, rows, 1e-5f, st));
-  return BSG_OK;
+  return ln(x, lnw, lnb, x, keep, rows, 1e-5f, st);
 }
 
 // duration predictor (tts_modules.py:108-133) on (x + spk) * keep for the nb utterances of x (their keep in w_keep); spk_id: these rows'
@@ -1832,17 +1834,14 @@ static int encode_impl(bsg_fs2midi* h, const int64_t* txt, const int64_t* pitch_
   const long long rows = (long long)B * Tt;        // every utterance: the lang embedding and K / V
   const long long lrows = (long long)nb * Tt;      // the rows asked for
   const long long off = (long long)row0 * Tt;
-  TRY(ensure_ws(h, (size_t)rows, (size_t)nb * h->cfg.num_heads * Tt * Tt, st));
+  TRY(ensure_ws(h, (size_t)rows, st));
   h->last_token_rows = (int)lrows;
   const dim3 rg(cdiv(rows, 4)), lg(cdiv(lrows, 4)), rb(256);
   const float sq = sqrtf((float)H);
   float* x0 = h->w_x;      // sqrt(H) * tok                [rows][H]
   float* lange = h->w_b;   // lang embedding LP            [rows][H]
-  static int esm_env = -1;   // BSG_ESM_H2W=0: the ESM's Linear layers on gemm_split_kernel and the thread-per-query attention
-  if (esm_env < 0) { const char* e = getenv("BSG_ESM_H2W"); esm_env = e ? atoi(e) : 1; }
-  static int esm_gemm_env = -1;
-  if (esm_gemm_env < 0) { const char* e = getenv("BSG_GEMM_H2W"); esm_gemm_env = e ? atoi(e) : 1; }
-  const bool esm_h2w = esm_env && esm_gemm_env && h->h2w_ok && gemm_split_enabled() && B <= 64 && h2w_supports((int)rows, H, H, 1, H) &&
+  const FftSwitches& sw = fft_switches();
+  const bool esm_h2w = sw.esm_h2w && sw.gemm_h2w && h->h2w_ok && gemm_split_enabled() && B <= 64 && h2w_supports((int)rows, H, H, 1, H) &&
                        h2w_supports((int)lrows, H, H, 1, H) && rows * 4 * H * 2 < (1LL << 31);
   if (esm_h2w) {
     // ---- ESM (common_layers.py:848-860) on the pre-split GEMM: every operand is written as hi / lo planes by its producer; the K and V
@@ -1902,7 +1901,7 @@ static int encode_impl(bsg_fs2midi* h, const int64_t* txt, const int64_t* pitch_
                      (const long long*)pitch_midi + off, midi_dur + off, (const long long*)is_slur + off, h->Emidi, h->Wdur, h->bdur, h->Eslur,
                      h->rel_table, x, h->w_keep, lrows, Tt, sq);
   BSG_LAUNCH_CHECK();
-  TRY(fft_stack(h, h->enc, h->enc_lnw, h->enc_lnb, h->cfg.enc_ffn_kernel_size, x, h->w_keep, nb, Tt, st, "enc."));
+  TRY(launch_fft(h, h->enc, h->enc_lnw, h->enc_lnb, h->cfg.enc_ffn_kernel_size, x, h->w_keep, nb, Tt, st, "enc."));
   BSG_HIP(hipMemcpyAsync(enc_out, x, lrows * H * sizeof(float), hipMemcpyDeviceToDevice, st));
   if (dur) TRY(dur_predict(h, x, spk_id ? spk_id + row0 : nullptr, nb, Tt, dur_xs, dur, st));
   return BSG_OK;
@@ -1951,14 +1950,14 @@ extern "C" int bsg_fs2_encode_plain(bsg_fs2midi* h, const int64_t* txt, const in
   hipStream_t st = (hipStream_t)stream;
   h->path.clear();
   const long long lrows = (long long)n_rows * Tt, off = (long long)row0 * Tt;
-  TRY(ensure_ws(h, (size_t)lrows, 0, st));
+  TRY(ensure_ws(h, (size_t)lrows, st));
   h->last_token_rows = (int)lrows;
   float* x = h->w_c;
   hipLaunchKernelGGL(token_front_kernel, dim3(cdiv(lrows, 4)), dim3(256), 0, st, (const long long*)txt + off, h->Etok, h->rel_table, x, h->w_keep,
                      lrows, Tt, sqrtf((float)H), h->cfg.n_rel, h->cfg.vocab);
   BSG_LAUNCH_CHECK();
   path_add(h, "tok:", "front");
-  TRY(fft_stack(h, h->enc, h->enc_lnw, h->enc_lnb, h->cfg.enc_ffn_kernel_size, x, h->w_keep, n_rows, Tt, st, "enc."));
+  TRY(launch_fft(h, h->enc, h->enc_lnw, h->enc_lnb, h->cfg.enc_ffn_kernel_size, x, h->w_keep, n_rows, Tt, st, "enc."));
   BSG_HIP(hipMemcpyAsync(enc_out, x, lrows * H * sizeof(float), hipMemcpyDeviceToDevice, st));
   if (dur) TRY(dur_predict(h, x, spk_id ? spk_id + row0 : nullptr, n_rows, Tt, dur_xs, dur, st));
   h->path_enc_len = h->path.size();
@@ -1978,15 +1977,10 @@ extern "C" const char* bsg_fs2midi_last_path(bsg_fs2midi* h) { return h && !h->p
 // that a correct kernel never lets into a result.  Not the arrival counters of the key split (they must stay zero between launches), not
 // the position words, not weights.
 static int poison_ws(bsg_fs2midi* h, hipStream_t st) {
-  const size_t r = h->cap_rows;
-  const struct { void* p; size_t bytes; } ws[] = {
-      {h->w_x, r * H * sizeof(float)},       {h->w_a, r * H * sizeof(float)},       {h->w_b, r * H * sizeof(float)},
-      {h->w_c, r * H * sizeof(float)},       {h->w_qkv, r * 3 * H * sizeof(float)}, {h->w_ffn, r * 4 * H * sizeof(float)},
-      {h->w_keep, r * sizeof(float)},        {h->w_ap, 2 * r * H * sizeof(unsigned short)},
-      {h->w_fp, 2 * r * 4 * H * sizeof(unsigned short)},
-      {h->w_scores, h->cap_scores * sizeof(float)},                                 {h->w_fsk, h->cap_fsk * sizeof(float)}};
-  for (const auto& w : ws)
-    if (w.p && w.bytes) BSG_HIP(hipMemsetAsync(w.p, 0xFF, w.bytes, st));
+  for (const WsBuf& w : ws_table(h))
+    if (w.poison && *w.p && h->cap_rows) BSG_HIP(hipMemsetAsync(*w.p, 0xFF, h->cap_rows * w.per_row * w.elem, st));
+  if (h->w_scores && h->cap_scores) BSG_HIP(hipMemsetAsync(h->w_scores, 0xFF, h->cap_scores * sizeof(float), st));
+  if (h->w_fsk && h->cap_fsk) BSG_HIP(hipMemsetAsync(h->w_fsk, 0xFF, h->cap_fsk * sizeof(float), st));
   return BSG_OK;
 }
 
@@ -2059,7 +2053,7 @@ static int decode_impl(bsg_fs2midi* h, const char* who, const float* enc_out, co
   BSG_REQUIRE(!h->use_pitch || T < h->n_pitch_pos, "%s: T=%d (pitch position table has %d rows)", who, T, h->n_pitch_pos);
   h->path.resize(h->path_enc_len);   // the record keeps the encode this decode follows
   const long long rows = (long long)B * T;
-  TRY(ensure_ws(h, (size_t)rows, mel_out ? (size_t)B * h->cfg.num_heads * T * T : 0, st));
+  TRY(ensure_ws(h, (size_t)rows, st));
   const dim3 rg(cdiv(rows, 4)), rb(256);
   if (h->use_pitch) {
     TRY(pitch_adaptor(h, enc_out, mel2ph, spk_id, speechsing, f0, uv, B, Tt, T, pitch_pred, f0_denorm, pitch_bin, decoder_inp, st));
@@ -2075,7 +2069,7 @@ static int decode_impl(bsg_fs2midi* h, const char* who, const float* enc_out, co
   BSG_LAUNCH_CHECK();
   hipLaunchKernelGGL(decoder_entry_kernel, rg, rb, 0, st, x, (const int*)h->w_pos, h->dec_table, h->dec_alpha, h->w_keep, rows, h->cfg.n_pos);
   BSG_LAUNCH_CHECK();
-  TRY(fft_stack(h, h->dec, h->dec_lnw, h->dec_lnb, h->cfg.dec_ffn_kernel_size, x, h->w_keep, B, T, st, "dec."));
+  TRY(launch_fft(h, h->dec, h->dec_lnw, h->dec_lnb, h->cfg.dec_ffn_kernel_size, x, h->w_keep, B, T, st, "dec."));
   // mel_out = Linear(H -> M)(x) * (mel2ph > 0)                                        (fastspeech/fs2.py:236-240)
   TRY(linear(x, h->mel_w, h->mel_b, mel_out, rows, h->cfg.out_dims, H, ACT_NONE, nullptr, nullptr, st));
   // ... * tgt_nonpadding, which comes from mel2ph (not from the decoder's own |x| test)
@@ -2122,7 +2116,7 @@ extern "C" int bsg_fs2_decode(bsg_fs2midi* h, const float* enc_out, const int64_
 // the `FFT` candidate denoiser (DIFF_DECODERS['fft'], usr/diff/candidate_decoder.py:39-100):
 // input projection -> concat[x, cond, step embedding] -> Linear(3C -> H) -> FastspeechDecoder stack -> Linear(H -> M).
 // The concat-Linear is split by columns: the cond part is step-invariant (hoisted to prepare), the step part is one
-// vector per utterance, so per call only x * W_x^T runs over all frames.  Reuses fft_stack() of the FS2 decoder.
+// vector per utterance, so per call only x * W_x^T runs over all frames.  Reuses launch_fft() of the FS2 decoder.
 // ================================================================================================
 namespace bsg {
 namespace {
@@ -2156,7 +2150,7 @@ struct bsg_fftden {
   bsg_fs2midi* core = nullptr;   // owns weights + the FFT-stack workspaces
   int M = 0, S = 0, n_pos = 0, ksz = 9;
   std::vector<FftLayerW> layers;
-  float *alpha, *lnw, *lnb, *in_w, *in_b, *mel_w, *mel_b, *gdi_w, *gdi_b, *dtab, *table;
+  float *alpha, *lnw, *lnb, *in_w, *in_b, *mel_w, *mel_b, *gdi_w, *gdi_b, *dtab;
   size_t cap = 0;
   int B = 0, T = 0;
   float *condpart = nullptr, *xT = nullptr, *xp = nullptr, *te = nullptr, *tvec = nullptr, *mel = nullptr;
@@ -2174,6 +2168,37 @@ extern "C" void bsg_fftden_destroy(bsg_fftden* h) {
 
 extern "C" int bsg_fftden_n_weights(int32_t n_layers) { return 2 + 10 * n_layers + 2 + 2 + 4 + 2 + 2; }
 
+// FFT.state_dict(): pos_embed_alpha, embed_positions._float_tensor, layers.*, layer_norm.{w,b}, input_projection.{w,b},
+// mlp.0.{w,b}, mlp.2.{w,b}, get_mel_out.{w,b}, get_decode_inp.{w,b}
+static int fftden_load(bsg_fftden* h, int n_layers, const void* const* w, const float* step_table, const float* pos_table, hipStream_t st) {
+  bsg_fs2midi* c = h->core;
+  const int M = h->M;
+  int i = 0;
+  TRY(guard_init(&c->guard, st));
+  GuardScope guard_scope(&c->guard);
+  TRY(fs2_copy(c, &h->alpha, w[i++], 1, st));
+  i++;
+  TRY(load_fft_layers(c, h->layers, w + i, n_layers, h->ksz, st));
+  i += 10 * n_layers;
+  TRY(fs2_copy(c, &h->lnw, w[i++], H, st));
+  TRY(fs2_copy(c, &h->lnb, w[i++], H, st));
+  TRY(fs2_copy(c, &h->in_w, w[i++], (size_t)H * M, st));
+  TRY(fs2_copy(c, &h->in_b, w[i++], H, st));
+  const float *m0w = (const float*)w[i], *m0b = (const float*)w[i + 1], *m2w = (const float*)w[i + 2], *m2b = (const float*)w[i + 3];
+  i += 4;
+  TRY(fs2_copy(c, &h->mel_w, w[i++], (size_t)M * H, st));
+  TRY(fs2_copy(c, &h->mel_b, w[i++], M, st));
+  TRY(fs2_copy(c, &h->gdi_w, w[i++], (size_t)H * 3 * H, st));
+  TRY(fs2_copy(c, &h->gdi_b, w[i++], H, st));
+  // step-embedding MLP tabulated for every timestep (candidate_decoder.py:60-62)
+  float* hid = nullptr;
+  TRY(fs2_alloc(c, &hid, (size_t)h->S * 4 * H));
+  TRY(fs2_alloc(c, &h->dtab, (size_t)h->S * H));
+  TRY(linear(step_table, m0w, m0b, hid, h->S, 4 * H, H, ACT_MISH, nullptr, nullptr, st));
+  TRY(linear(hid, m2w, m2b, h->dtab, h->S, H, 4 * H, ACT_NONE, nullptr, nullptr, st));
+  return create_tail(c, pos_table, nullptr, nullptr, st);   // the frame position table: c->dec_table
+}
+
 extern "C" int bsg_fftden_create(bsg_fftden** out, int32_t in_dims, int32_t n_layers, int32_t num_heads, int32_t ffn_kernel,
                                  int32_t max_steps, int32_t n_pos, const void* const* w, int32_t n_weights, const float* step_table,
                                  const float* pos_table, void* stream) {
@@ -2182,44 +2207,18 @@ extern "C" int bsg_fftden_create(bsg_fftden** out, int32_t in_dims, int32_t n_la
                   ffn_kernel % 2 == 1 && max_steps > 0 && n_pos > 1, "fftden_create: bad config");
   BSG_REQUIRE(n_weights == bsg_fftden_n_weights(n_layers), "fftden_create: expected %d weight tensors, got %d", bsg_fftden_n_weights(n_layers), n_weights);
   for (int i = 0; i < n_weights; ++i) BSG_REQUIRE(w[i] != nullptr, "fftden_create: weight %d is null", i);
-  hipStream_t st = (hipStream_t)stream;
   bsg_fftden* h = new bsg_fftden();
   h->core = new bsg_fs2midi();
   h->core->cfg = bsg_fs2midi_cfg{};
   h->core->cfg.num_heads = num_heads;
+  h->core->cfg.dec_ffn_kernel_size = ffn_kernel;   // (create_tail reads these two)
+  h->core->cfg.n_pos = n_pos;
   h->M = in_dims; h->S = max_steps; h->n_pos = n_pos; h->ksz = ffn_kernel;
-  bsg_fs2midi* c = h->core;
-  auto fail = [&](int rc) { bsg_fftden_destroy(h); return rc; };
-  int rc, i = 0;
-  if ((rc = guard_init(&c->guard, st)) != BSG_OK) return fail(rc);
-  GuardScope guard_scope(&c->guard);
-  // FFT.state_dict(): pos_embed_alpha, embed_positions._float_tensor, layers.*, layer_norm.{w,b}, input_projection.{w,b},
-  // mlp.0.{w,b}, mlp.2.{w,b}, get_mel_out.{w,b}, get_decode_inp.{w,b}
-  if ((rc = fs2_copy(c, &h->alpha, w[i++], 1, st)) != BSG_OK) return fail(rc);
-  i++;
-  if ((rc = load_fft_layers(c, h->layers, w + i, n_layers, ffn_kernel, st)) != BSG_OK) return fail(rc);
-  i += 10 * n_layers;
-  if ((rc = fs2_copy(c, &h->lnw, w[i++], H, st)) != BSG_OK) return fail(rc);
-  if ((rc = fs2_copy(c, &h->lnb, w[i++], H, st)) != BSG_OK) return fail(rc);
-  if ((rc = fs2_copy(c, &h->in_w, w[i++], (size_t)H * in_dims, st)) != BSG_OK) return fail(rc);
-  if ((rc = fs2_copy(c, &h->in_b, w[i++], H, st)) != BSG_OK) return fail(rc);
-  const float *m0w = (const float*)w[i], *m0b = (const float*)w[i + 1], *m2w = (const float*)w[i + 2], *m2b = (const float*)w[i + 3];
-  i += 4;
-  if ((rc = fs2_copy(c, &h->mel_w, w[i++], (size_t)in_dims * H, st)) != BSG_OK) return fail(rc);
-  if ((rc = fs2_copy(c, &h->mel_b, w[i++], in_dims, st)) != BSG_OK) return fail(rc);
-  if ((rc = fs2_copy(c, &h->gdi_w, w[i++], (size_t)H * 3 * H, st)) != BSG_OK) return fail(rc);
-  if ((rc = fs2_copy(c, &h->gdi_b, w[i++], H, st)) != BSG_OK) return fail(rc);
-  if ((rc = fs2_copy(c, &h->table, pos_table, (size_t)n_pos * H, st)) != BSG_OK) return fail(rc);
-  // step-embedding MLP tabulated for every timestep (candidate_decoder.py:60-62)
-  float* hid = nullptr;
-  if ((rc = fs2_alloc(c, &hid, (size_t)max_steps * 4 * H)) != BSG_OK) return fail(rc);
-  if ((rc = fs2_alloc(c, &h->dtab, (size_t)max_steps * H)) != BSG_OK) return fail(rc);
-  if ((rc = linear(step_table, m0w, m0b, hid, max_steps, 4 * H, H, ACT_MISH, nullptr, nullptr, st)) != BSG_OK) return fail(rc);
-  if ((rc = linear(hid, m2w, m2b, h->dtab, max_steps, H, 4 * H, ACT_NONE, nullptr, nullptr, st)) != BSG_OK) return fail(rc);
-  unsigned pack_bad = 1;
-  if (hipMemcpyAsync(&pack_bad, c->pack_bad, sizeof(unsigned), hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) { set_error("fftden_create: sync failed"); return fail(BSG_EHIP); }
-  c->h2w_ok = pack_bad == 0 && ffn_kernel <= 17;
+  const int rc = fftden_load(h, n_layers, w, step_table, pos_table, (hipStream_t)stream);
+  if (rc != BSG_OK) {
+    bsg_fftden_destroy(h);
+    return rc;
+  }
   *out = h;
   return BSG_OK;
 }
@@ -2242,7 +2241,7 @@ extern "C" int bsg_fftden_prepare(bsg_fftden* h, const float* cond, int32_t B, i
     BSG_HIP(hipMalloc((void**)&h->mel, rows * h->M * sizeof(float)));
     h->cap = rows;
   }
-  TRY(ensure_ws(h->core, rows, (size_t)B * h->core->cfg.num_heads * T * T, st));
+  TRY(ensure_ws(h->core, rows, st));
   h->B = B; h->T = T;
   // cond [B][H][T] -> [B*T][H]; condpart = cond_t * W[:, C:2C]^T                           (candidate_decoder.py:63-70)
   hipLaunchKernelGGL(transpose_brc_kernel, dim3(cdiv(T, 32), cdiv(H, 32), B), dim3(256), 0, st, cond, h->xT, H, T);
@@ -2285,9 +2284,9 @@ extern "C" int bsg_fftden_forward(bsg_fftden* h, const float* x, const int64_t* 
   const dim3 rg(cdiv(rows, 4)), rb(256);
   hipLaunchKernelGGL(decoder_positions_kernel, dim3(B), dim3(64), 0, st, (const float*)xs, c->w_pos, c->w_keep, T);
   BSG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(decoder_entry_kernel, rg, rb, 0, st, xs, (const int*)c->w_pos, h->table, h->alpha, c->w_keep, rows, h->n_pos);
+  hipLaunchKernelGGL(decoder_entry_kernel, rg, rb, 0, st, xs, (const int*)c->w_pos, c->dec_table, h->alpha, c->w_keep, rows, h->n_pos);
   BSG_LAUNCH_CHECK();
-  TRY(fft_stack(c, h->layers, h->lnw, h->lnb, h->ksz, xs, c->w_keep, B, T, st, "den."));
+  TRY(launch_fft(c, h->layers, h->lnw, h->lnb, h->ksz, xs, c->w_keep, B, T, st, "den."));
   TRY(linear(xs, h->mel_w, h->mel_b, h->mel, rows, h->M, H, ACT_NONE, nullptr, nullptr, st));       // get_mel_out (:98)
   hipLaunchKernelGGL(transpose_brc_kernel, dim3(cdiv(h->M, 32), cdiv(T, 32), B), dim3(256), 0, st, (const float*)h->mel, eps, T, h->M);
   BSG_LAUNCH_CHECK();

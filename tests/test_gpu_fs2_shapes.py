@@ -1,6 +1,6 @@
 """GPU parity of every FastSpeech2-MIDI launch form at its shape edges, against the float64 evaluation of the CPU oracle.
 
-fft_stack() (csrc/fs2.hip) picks per call among nine attention forms (flash_attn_planes_kernel<2> with its keys on 1, 2 or 4 workgroups,
+plan_fft() (csrc/fs2.hip) picks per call among nine attention forms (flash_attn_planes_kernel<2> with its keys on 1, 2 or 4 workgroups,
 flash_attn_split_kernel<2> / <4>, flash_attn_kernel<2> / <4>, the score tensor + masked_softmax_kernel), two producers of Q / K / V^T (the
 GEMM's own epilogue, qkv_split_kernel) and, inside launch_gemm_h2w, 32-, 64- or 128-row tiles with 4-, 8- or 16-step rings; the ESM has two
 attention kernels.  tests/test_gpu_fs2.py and tests/test_gpu_edges.py reach part of that map, against the fp32 oracle at 1e-4 .. 3e-4.  Here
@@ -96,7 +96,7 @@ import torch
 
 from bisinger_amd import _lib, synth
 from oracle import candidate_decoder as ocd, fs2 as ofs2
-from tests.util import ROOT, cpu_sd, load_formula_weights, use_config
+from tests.util import ROOT, cpu_sd, load_formula_weights, load_golden, use_config
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
@@ -470,6 +470,7 @@ def test_fallback_forms_vs_fp64(tmp_path, fs2):
         np.savez(f + '.inp.npz', **_ref(sd, case)['inp'], **extra)
         files[case] = f
     seen = set()
+    gold = load_golden('fs2_paths.json')['forms']
     for name, (env, check, with_nw4) in FORMS.items():
         cases = SHORT_LIST + ([NW4] if with_nw4 else [])
         res = subprocess.run([sys.executable, '-c', CHILD, name] + [files[c] for c in cases], env=dict(os.environ, **env), capture_output=True,
@@ -480,6 +481,7 @@ def test_fallback_forms_vs_fp64(tmp_path, fs2):
             r = info[files[case]]
             z = np.load(f'{files[case]}.{name}.npz')
             assert r['retries'] == 0 and r['events'] == 0, (name, _name(case), r)
+            assert r['path'] == gold[name][_name(case)], (name, _name(case), r['path'], gold[name][_name(case)])
             rec = _record(name, case, {k: z[k] for k in OUTS}, r['path'], _REF[case])
             check(case, rec['tokens'])
             seen |= set(rec['tokens'])
@@ -489,7 +491,7 @@ def test_fallback_forms_vs_fp64(tmp_path, fs2):
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# the FFT candidate denoiser (shares fft_stack)
+# the FFT candidate denoiser (shares launch_fft)
 # ------------------------------------------------------------------------------------------------------------------
 DEN_SHAPES = [(1, 1), (2, 33), (2, 301), (2, 1000)]
 _DEN = {}
@@ -530,6 +532,7 @@ def test_fft_denoiser_vs_fp64(B, T, den):
     want = ocd.fft_denoiser_forward(sd, x, t, cond, dtype=F64).numpy()
     w32 = ocd.fft_denoiser_forward(sd, x, t, cond, dtype=F32).double().numpy()
     got, path = _den_run(net, B, T)
+    assert path == load_golden('fs2_paths.json')['den'][f'{B}x{T}'], (B, T, path)
     _DEN[(B, T)] = got
     assert got.shape == want.shape == (B, 1, 80, T) and np.isfinite(got).all()
     d = np.abs(got.astype(np.float64) - want)

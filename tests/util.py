@@ -30,6 +30,12 @@ def load_formula_weights(module, seed=0, gain=None, prefix=''):
     return module
 
 
+def load_golden(name):
+    """tests/golden/<name> (a JSON record, e.g. the launch strings of a parent commit)."""
+    with open(os.path.join(ROOT, 'tests', 'golden', name)) as f:
+        return json.load(f)
+
+
 def cpu_sd(module, prefix=''):
     return {prefix + k: v.detach().cpu() for k, v in module.state_dict().items()}
 
