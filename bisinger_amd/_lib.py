@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'lib', 'libbisinger_hip.so')
 if os.environ.get('BSG_LIB'):      # development: an alternative build of the same ABI (kernel experiments)
     LIB_PATH = os.environ['BSG_LIB']
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 
 class BsgError(RuntimeError):
@@ -138,6 +138,9 @@ _SIGS = {
     'bsg_hifigan_forward': (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     'bsg_hifigan_forward_nsf': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     'bsg_hifigan_last_path': (c_char_p, [c_void_p]),
+    'bsg_hifigan_forward_ragged': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),      # lengths_host: B int32 on the host (ABI v18)
+    'bsg_hifigan_forward_nsf_ragged': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
+    'bsg_hifigan_debug_poison_workspace': (c_int32, [c_void_p, c_void_p]),
     'bsg_fs2midi_last_path': (c_char_p, [c_void_p]),
     'bsg_fs2_n_weights': (c_int32, [POINTER(Fs2XCfg)]),
     'bsg_fs2_create': (c_int32, [POINTER(c_void_p), POINTER(Fs2XCfg), POINTER(c_void_p), c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -167,9 +167,10 @@ int h2w_pack_into(unsigned short* dst, const float* src, int Wn, int K, int taps
 void h2w_free(H2wWeights* w);
 int h2w_split_rows(const float* src, unsigned short* hi, unsigned short* lo, long long rows, int K, long long ld, hipStream_t st);
 int h2w_split_transposed(const float* src, unsigned short* hi, unsigned short* lo, int B, int K, int T, hipStream_t st);   // [B][K][T] -> [B][T][K]
-// the same with LeakyReLU(slope) applied first, `rows_per_b` >= T rows per batch item and Kp >= K columns per row in the planes (the padding is zero)
+// the same with LeakyReLU(slope) applied first, `rows_per_b` >= T rows per batch item and Kp >= K columns per row in the planes (the padding is zero);
+// lens (device, may be null): item b is read up to lens[b] * lmul <= T positions only and zero from there on (ragged HiFi-GAN batches)
 int h2w_split_transposed_lrelu(const float* src, unsigned short* hi, unsigned short* lo, int B, int K, int Kp, int T, int rows_per_b, float slope,
-                               hipStream_t st);
+                               const int* lens, int lmul, hipStream_t st);
 int launch_gemm_h2w(const H2wArgs& g, hipStream_t st);
 unsigned* gemm_range_counter();   // device address of the range-event counter (null on error): kernels of other translation units add to it
 

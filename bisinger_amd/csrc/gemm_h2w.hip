@@ -78,15 +78,17 @@ __global__ void h2w_split_rows_kernel(const float* __restrict__ src, _Float16* _
 
 // fp32 [B][K][T] (the [B, C, T] layout of the reference's cond) -> planes [B][TR][KP] (TR >= T rows per item, KP >= K columns; rows T.. and
 // columns K.. zero) of 16 x lrelu_slope(value): a 32 x 32 tile through LDS per 256-thread workgroup
+template <bool RAG>   // ragged batches (hifigan): item b ends at lens[b] * lmul; a template flag, so that the padded form compiles to what it was
 __global__ __launch_bounds__(256) void h2w_split_transposed_kernel(const float* __restrict__ src, _Float16* __restrict__ hi,
                                                                    _Float16* __restrict__ lo, int K, int KP, int T, int TR, float slope,
-                                                                   unsigned* __restrict__ range_events) {
+                                                                   unsigned* __restrict__ range_events, const int* __restrict__ lens, int lmul) {
   __shared__ float tile[32][33];
   const int b = blockIdx.z, k0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int Tb = RAG ? lens[b] * lmul : T;   // item b is read up to ITS end, zeros from there on; T stays the row pitch of src
   for (int j = ty; j < 32; j += 8) {
     const int k = k0 + j, t = t0 + tx;
-    const float v = (k < K && t < T) ? src[((long long)b * K + k) * T + t] : 0.f;
+    const float v = (k < K && t < Tb) ? src[((long long)b * K + k) * T + t] : 0.f;
     tile[j][tx] = fmaxf(v, v * slope);   // slope in [0, 1]; 1: the identity
   }
   __syncthreads();
@@ -556,17 +558,20 @@ int h2w_split_rows(const float* src, unsigned short* hi, unsigned short* lo, lon
 }
 
 int h2w_split_transposed_lrelu(const float* src, unsigned short* hi, unsigned short* lo, int B, int K, int Kp, int T, int rows_per_b, float slope,
-                               hipStream_t st) {
+                               const int* lens, int lmul, hipStream_t st) {
   BSG_REQUIRE(src && hi && lo && B > 0 && K > 0 && Kp >= K && T > 0 && B <= 65535 && rows_per_b >= T && slope >= 0.f && slope <= 1.f,
               "h2w_split_transposed: B=%d K=%d Kp=%d T=%d rows=%d slope=%g", B, K, Kp, T, rows_per_b, (double)slope);
-  hipLaunchKernelGGL(h2w_split_transposed_kernel, dim3(cdiv(rows_per_b, 32), cdiv(Kp, 32), B), dim3(256), 0, st, src, reinterpret_cast<_Float16*>(hi),
-                     reinterpret_cast<_Float16*>(lo), K, Kp, T, rows_per_b, slope, gemm_range_counter());
+  const dim3 grid(cdiv(rows_per_b, 32), cdiv(Kp, 32), B);
+  if (lens) hipLaunchKernelGGL(h2w_split_transposed_kernel<true>, grid, dim3(256), 0, st, src, reinterpret_cast<_Float16*>(hi), reinterpret_cast<_Float16*>(lo), K,
+                               Kp, T, rows_per_b, slope, gemm_range_counter(), lens, lmul);
+  else hipLaunchKernelGGL(h2w_split_transposed_kernel<false>, grid, dim3(256), 0, st, src, reinterpret_cast<_Float16*>(hi), reinterpret_cast<_Float16*>(lo), K,
+                          Kp, T, rows_per_b, slope, gemm_range_counter(), lens, lmul);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
 }
 
 int h2w_split_transposed(const float* src, unsigned short* hi, unsigned short* lo, int B, int K, int T, hipStream_t st) {
-  return h2w_split_transposed_lrelu(src, hi, lo, B, K, K, T, T, 1.0f, st);
+  return h2w_split_transposed_lrelu(src, hi, lo, B, K, K, T, T, 1.0f, nullptr, 1, st);
 }
 
 int launch_gemm_h2w(const H2wArgs& g0, hipStream_t st) {

@@ -51,6 +51,13 @@ struct HgSwitches {
 };
 const HgSwitches& hg_switches() { static const HgSwitches s; return s; }
 
+// Ragged batches (bsg_hifigan_forward_ragged): `lens` (device, one frame count per batch row; null = the padded call) and `lmul`, the
+// product of the upsample rates up to the tensor a launch reads.  The row PITCH of every tensor stays L (the padded length); the BOUND that
+// a position is tested against at the end of a row is lens[b] * lmul.  Wave-uniform: one scalar load per workgroup.  Every kernel takes the
+// choice as a template flag RAG (as DIAG = Q_VARLEN is in the stack launch): the padded instantiation compiles to what it was without it.
+template <bool RAG>
+__device__ __forceinline__ int row_bound(const int* __restrict__ lens, int lmul, int b, int L) { return RAG ? lens[b] * lmul : L; }
+
 struct ConvArgs {
   const float* x;      // [B][Cin][L]
   const float* w;      // packed [ceil(Cout/CO_BLK)][Cin][K][CO_BLK] (zero padded): the CO_BLK weights of one (ci, k) are one wide scalar load
@@ -66,9 +73,14 @@ struct ConvArgs {
   // q*u + r + ph_off of a row of Lout samples; the phase's 2-tap weights start at w + r*w_phase_stride
   int n_phase, ph_off, Lq, Lout;
   long long w_phase_stride;
+  const int* lens;     // ragged: see row_bound
+  int lmul;
+  int zero_tail;       // ragged conv_post: positions [bound, L) of a row are stored as 0
 };
 
-template <int K, int CO_BLK, int TT>
+// RAG: the ragged instantiation (row_bound).  With the bound selected at run time this kernel's padded form lost a resident wave in 8 of its
+// 30 instantiations ("Ragged HiFi-GAN batches").
+template <int K, int CO_BLK, int TT, bool RAG = false>
 __global__ __launch_bounds__(256) void conv1d_kernel(ConvArgs a) {
   constexpr int TILE = 256 * TT;  // samples per workgroup
   extern __shared__ float xs[];   // [CI_CHUNK][TILE + (K-1)*dil]
@@ -78,6 +90,19 @@ __global__ __launch_bounds__(256) void conv1d_kernel(ConvArgs a) {
   const int ph = a.n_phase > 0 ? (int)blockIdx.z % a.n_phase : 0;
   const int b = a.n_phase > 0 ? (int)blockIdx.z / a.n_phase : (int)blockIdx.z;
   const int span = TILE + (K - 1) * a.dil;
+  const int Lb = row_bound<RAG>(a.lens, a.lmul, b, a.L);
+  if constexpr (RAG) {
+    if (t0 >= (a.n_phase > 0 ? Lb + 1 : Lb)) {   // the whole tile lies beyond the row's end: nothing to load
+      if (a.zero_tail) {
+#pragma unroll
+        for (int j = 0; j < TT; ++j) {
+          const int t = t0 + tid + 256 * j;
+          if (t < a.L && co0 < a.Cout) a.y[((long long)b * a.Cout + co0) * a.L + t] = 0.f;   // (conv_post: one output channel)
+        }
+      }
+      return;
+    }
+  }
   const float* __restrict__ xb = a.x + (long long)b * a.Cin * a.L;
   const float* __restrict__ wbase = a.w + (long long)ph * a.w_phase_stride;
 
@@ -98,7 +123,7 @@ __global__ __launch_bounds__(256) void conv1d_kernel(ConvArgs a) {
         const int idx = idx0 + 256 * u;
         const int ci = idx / span, j = idx - ci * span;
         const int t = t0 - a.pad + j;
-        v[u] = (idx < CI_CHUNK * span && ci0 + ci < a.Cin && t >= 0 && t < a.L) ? xb[(long long)(ci0 + ci) * a.L + t] : 0.f;
+        v[u] = (idx < CI_CHUNK * span && ci0 + ci < a.Cin && t >= 0 && t < Lb) ? xb[(long long)(ci0 + ci) * a.L + t] : 0.f;
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u)
@@ -134,7 +159,7 @@ __global__ __launch_bounds__(256) void conv1d_kernel(ConvArgs a) {
       for (int j = 0; j < TT; ++j) {
         const int q = t0 + tid + 256 * j;
         const int to = q * a.n_phase + ph + a.ph_off;
-        if (q < a.Lq && to >= 0 && to < a.Lout && co0 + c < a.Cout) a.y[rowo + to] = acc[c][j];
+        if (q <= Lb && to >= 0 && to < Lb * a.n_phase && co0 + c < a.Cout) a.y[rowo + to] = acc[c][j];   // (Lq = L + 1, Lout = L n_phase)
       }
     }
     return;
@@ -146,6 +171,12 @@ __global__ __launch_bounds__(256) void conv1d_kernel(ConvArgs a) {
     for (int j = 0; j < TT; ++j) {
       const int t = t0 + tid + 256 * j;
       if (t >= a.L || co0 + c >= a.Cout) continue;
+      if constexpr (RAG) {
+        if (t >= Lb) {
+          if (a.zero_tail) a.y[rowo + t] = 0.f;
+          continue;
+        }
+      }
       float v = acc[c][j];
       if (a.res) v += a.res[rowo + t];
       if (a.acc_in) v = a.acc_in[rowo + t] + v;
@@ -182,9 +213,11 @@ struct PairArgs {
   float slope;
   int L, dil;
   unsigned* range_events;   // split-fp16 form: counter of operands beyond the fp16 range (gemm_range_counter())
+  const int* lens;          // ragged: see row_bound
+  int lmul;
 };
 
-template <int K, int C, int TT>
+template <int K, int C, int TT, bool RAG = false>
 __global__ __launch_bounds__(256) void resblock_pair_kernel(PairArgs a) {
   constexpr int P = 256 * TT, H2 = (K - 1) / 2, POUT = P - (K - 1);
   constexpr int CI = C == 16 ? 8 : 4;   // input channels per staged chunk (span <= P + 50 floats each): stays inside the [C][P] image
@@ -192,6 +225,10 @@ __global__ __launch_bounds__(256) void resblock_pair_kernel(PairArgs a) {
   const int tid = threadIdx.x;
   const int t0 = blockIdx.x * POUT;     // first output position of this workgroup
   const int b = blockIdx.y;
+  const int Lb = row_bound<RAG>(a.lens, a.lmul, b, a.L);
+  if constexpr (RAG) {
+    if (t0 >= Lb) return;   // the tile lies beyond the row's end: before the first load and the first barrier
+  }
   const int h1 = H2 * a.dil, span = P + 2 * h1;
   const float* __restrict__ xb = a.x + (long long)b * C * a.L;
   const float slope = a.slope;
@@ -213,7 +250,7 @@ __global__ __launch_bounds__(256) void resblock_pair_kernel(PairArgs a) {
         const int idx = idx0 + 256 * u;
         const int ci = idx / span, jx = idx - ci * span;
         const int t = t0 - H2 - h1 + jx;
-        v[u] = (idx < CI * span && t >= 0 && t < a.L) ? xb[(long long)(ci0 + ci) * a.L + t] : 0.f;
+        v[u] = (idx < CI * span && t >= 0 && t < Lb) ? xb[(long long)(ci0 + ci) * a.L + t] : 0.f;
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u)
@@ -246,7 +283,7 @@ __global__ __launch_bounds__(256) void resblock_pair_kernel(PairArgs a) {
 #pragma unroll
   for (int j = 0; j < TT; ++j) {
     const int u = t0 - H2 + tid + 256 * j;
-    const bool in = u >= 0 && u < a.L;
+    const bool in = u >= 0 && u < Lb;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
       const float v = acc[c][j];
@@ -283,7 +320,7 @@ __global__ __launch_bounds__(256) void resblock_pair_kernel(PairArgs a) {
 #pragma unroll
   for (int j = 0; j < TT; ++j) {
     const int o = tid + 256 * j, t = t0 + o;
-    if (o >= POUT || t >= a.L) continue;
+    if (o >= POUT || t >= Lb) continue;
     const long long i0 = (long long)b * C * a.L + t;
     float xr[C];
 #pragma unroll
@@ -362,7 +399,7 @@ __device__ __forceinline__ void conv_mfma(f32x16 (&acc)[C / 32][NB], const float
   }
 }
 
-template <int K, int C, int NB>   // NB column tiles of 32 positions per wave: 2 (256 positions per workgroup), or 1 for short inputs (more workgroups)
+template <int K, int C, int NB, bool RAG = false>   // NB column tiles of 32 positions per wave: 2 (256 positions per workgroup), or 1 for short inputs (more workgroups)
 __global__ __launch_bounds__(256) void resblock_pair_mfma_kernel(PairArgs a) {
   constexpr int PT = 128 * NB, H2 = (K - 1) / 2, POUT = PT - (K - 1), RT = C / 32, TS = PT + 16;
   static_assert(C % 32 == 0 && (C / 8) % 2 == 0, "channel count");
@@ -370,6 +407,10 @@ __global__ __launch_bounds__(256) void resblock_pair_mfma_kernel(PairArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, lh = lane >> 5;
   const int t0 = blockIdx.x * POUT, b = blockIdx.y;
+  const int Lb = row_bound<RAG>(a.lens, a.lmul, b, a.L);
+  if constexpr (RAG) {
+    if (t0 >= Lb) return;   // the tile lies beyond the row's end: before the first load and the first barrier
+  }
   const int h1 = H2 * a.dil, span = PT + 2 * h1, XS = (span + 3) & ~3;
   const float* __restrict__ xb = a.x + (long long)b * C * a.L;
   const float slope = a.slope;
@@ -378,7 +419,7 @@ __global__ __launch_bounds__(256) void resblock_pair_mfma_kernel(PairArgs a) {
   for (int idx = tid; idx < C * span; idx += 256) {
     const int ci = idx / span, jx = idx - ci * span;
     const int t = t0 - H2 - h1 + jx;
-    float v = (t >= 0 && t < a.L) ? xb[(long long)ci * a.L + t] : 0.f;
+    float v = (t >= 0 && t < Lb) ? xb[(long long)ci * a.L + t] : 0.f;
     lds[ci * XS + jx] = fmaxf(v, v * slope);
   }
   const int n0 = 32 * NB * wave;
@@ -399,7 +440,7 @@ __global__ __launch_bounds__(256) void resblock_pair_mfma_kernel(PairArgs a) {
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
     const int pcol = n0 + 32 * nb + l31, u = t0 - H2 + pcol;
-    const bool in = u >= 0 && u < a.L;
+    const bool in = u >= 0 && u < Lb;
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -428,7 +469,7 @@ __global__ __launch_bounds__(256) void resblock_pair_mfma_kernel(PairArgs a) {
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
     const int pcol = n0 + 32 * nb + l31, t = t0 + pcol;
-    if (pcol >= POUT || t >= a.L) continue;
+    if (pcol >= POUT || t >= Lb) continue;
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
       const long long i0 = ((long long)b * C + 32 * rt + 4 * lh) * a.L + t;
@@ -470,8 +511,10 @@ struct UpArgs {
   float* y;           // [B][Cout][Lin*u]
   float slope;
   int Cin, Cout, Lin, p;
+  const int* lens;    // ragged: see row_bound (the bound of the INPUT row)
+  int lmul;
 };
-template <int U>
+template <int U, bool RAG = false>
 __global__ __launch_bounds__(256) void upsample_kernel(UpArgs a) {
   constexpr int CO = 8, CIC = 16;
   __shared__ float xs[CIC][260];
@@ -479,6 +522,10 @@ __global__ __launch_bounds__(256) void upsample_kernel(UpArgs a) {
   const int q0 = blockIdx.x * 256, q = q0 + tid;     // q in [0, Lin]: position q contributes outputs [q U - p, q U - p + U)
   const int cb = blockIdx.y, b = blockIdx.z;
   const int nblk = (a.Cout + CO - 1) / CO;
+  const int Lb = row_bound<RAG>(a.lens, a.lmul, b, a.Lin);
+  if constexpr (RAG) {
+    if (q0 > Lb) return;   // position Lb still contributes the row's last outputs; tiles beyond it: nothing
+  }
   const float* __restrict__ xb = a.x + (long long)b * a.Cin * a.Lin;
   float acc[CO][U];
 #pragma unroll
@@ -492,7 +539,7 @@ __global__ __launch_bounds__(256) void upsample_kernel(UpArgs a) {
     for (int idx = tid; idx < CIC * 257; idx += 256) {
       const int ci = idx / 257, j = idx - ci * 257;
       const int t = q0 - 1 + j;
-      float v = (ci0 + ci < a.Cin && t >= 0 && t < a.Lin) ? xb[(long long)(ci0 + ci) * a.Lin + t] : 0.f;
+      float v = (ci0 + ci < a.Cin && t >= 0 && t < Lb) ? xb[(long long)(ci0 + ci) * a.Lin + t] : 0.f;
       xs[ci][j] = fmaxf(v, v * a.slope);
     }
     __syncthreads();
@@ -508,13 +555,13 @@ __global__ __launch_bounds__(256) void upsample_kernel(UpArgs a) {
       }
     }
   }
-  if (q > a.Lin) return;
-  const int Lout = a.Lin * U;
+  if (q > Lb) return;
+  const int Lout = Lb * U;   // the bound of the output row; its pitch is Lin U
   const int o0 = q * U - a.p;
 #pragma unroll
   for (int c = 0; c < CO; ++c) {
     if (cb * CO + c >= a.Cout) continue;
-    float* __restrict__ yr = a.y + ((long long)b * a.Cout + cb * CO + c) * Lout;
+    float* __restrict__ yr = a.y + ((long long)b * a.Cout + cb * CO + c) * ((long long)a.Lin * U);
     if (o0 >= 0 && o0 + U <= Lout && (U % 4) == 0 && ((o0 & 3) == 0)) {
 #pragma unroll
       for (int r = 0; r < U; r += 4) *reinterpret_cast<f32x4*>(yr + o0 + r) = f32x4{acc[c][r], acc[c][r + 1], acc[c][r + 2], acc[c][r + 3]};
@@ -533,13 +580,17 @@ __global__ __launch_bounds__(256) void upsample_kernel(UpArgs a) {
 // The weights are read in their own layout [Cin][Cout][4] (wave-uniform: scalar loads).  upsample_kernel<2> wrote 2 samples per lane with
 // 4-byte stores at odd offsets and staged x once per block of 8 output channels: 117 us per stage at B = 16 against 52 us of HBM time; this
 // form: 100 / 90 us (16 / 8 output channels) — the staging of a 16-channel chunk and its FMAs still alternate.
-template <int CO>
+template <int CO, bool RAG = false>
 __global__ __launch_bounds__(256) void upsample2_kernel(UpArgs a) {
   constexpr int CIC = 16, XS = 516;      // xs[ci][j] = lrelu(x[2 m0 - 2 + j]): the lane's x[2m-1] sits at the EVEN index 2 tid + 1... see below
   __shared__ __attribute__((aligned(16))) float xs[CIC][XS];
   const int tid = threadIdx.x;
   const int m0 = blockIdx.x * 256, m = m0 + tid;   // outputs [4m, 4m + 4)
   const int cb = blockIdx.y, b = blockIdx.z;
+  const int Lb = row_bound<RAG>(a.lens, a.lmul, b, a.Lin);
+  if constexpr (RAG) {
+    if (4 * m0 >= 2 * Lb) return;   // the tile's first output lies beyond the row's end
+  }
   const float* __restrict__ xb = a.x + (long long)b * a.Cin * a.Lin;
   float acc[CO][4];
 #pragma unroll
@@ -558,7 +609,7 @@ __global__ __launch_bounds__(256) void upsample2_kernel(UpArgs a) {
         const int idx = idx0 + 256 * u;
         const int ci = idx / 514, j = idx - ci * 514;
         const int t = 2 * m0 - 1 + j;
-        v[u] = (idx < CIC * 514 && ci0 + ci < a.Cin && t >= 0 && t < a.Lin) ? xb[(long long)(ci0 + ci) * a.Lin + t] : 0.f;
+        v[u] = (idx < CIC * 514 && ci0 + ci < a.Cin && t >= 0 && t < Lb) ? xb[(long long)(ci0 + ci) * a.Lin + t] : 0.f;
       }
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
@@ -583,12 +634,12 @@ __global__ __launch_bounds__(256) void upsample2_kernel(UpArgs a) {
       }
     }
   }
-  const int Lout = a.Lin * 2, o0 = 4 * m;
+  const int Lout = Lb * 2, Lp = a.Lin * 2, o0 = 4 * m;   // bound and pitch of the output row
   if (o0 >= Lout) return;
 #pragma unroll
   for (int c = 0; c < CO; ++c) {
-    float* __restrict__ yr = a.y + ((long long)b * a.Cout + cb * CO + c) * Lout;
-    if (o0 + 3 < Lout && (Lout & 3) == 0) {
+    float* __restrict__ yr = a.y + ((long long)b * a.Cout + cb * CO + c) * Lp;
+    if (o0 + 3 < Lout && (Lp & 3) == 0) {
       *reinterpret_cast<f32x4*>(yr + o0) = f32x4{acc[c][0], acc[c][1], acc[c][2], acc[c][3]};
     } else {
 #pragma unroll
@@ -601,15 +652,29 @@ __global__ __launch_bounds__(256) void upsample2_kernel(UpArgs a) {
 // conv_post (hifigan.py:169-171): Conv1d(C -> 1, 7, padding 3) on LeakyReLU(x, 0.01), then tanh.  One output channel: the generic conv1d_kernel
 // spends 7 of its 8 output-channel lanes' FMAs on nothing.  A lane produces 4 consecutive samples from three 16-byte loads per input channel
 // (x[4m-4 .. 4m+7]; neighbours' loads overlap in L1), no LDS; weights wave-uniform.  98 -> 33 us at B = 16 (147 MB: 4.4 TB/s).
-template <int C>
+template <int C, bool RAG = false>
 __global__ __launch_bounds__(256) void conv_post_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                                                        float* __restrict__ y, int L, float slope) {
+                                                        float* __restrict__ y, int L, float slope, const int* __restrict__ lens,
+                                                        int lmul) {
   const int m = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
   const int t0 = 4 * m;
   if (t0 >= L) return;
+  const int Lb = row_bound<RAG>(lens, lmul, b, L);   // ragged: the bound of the row (its pitch stays L); samples [Lb, L) are stored as 0
+  if constexpr (RAG) {
+    if (t0 >= Lb) {
+      float* __restrict__ yz = y + (long long)b * L + t0;
+      if (t0 + 3 < L && (L & 3) == 0) {
+        *reinterpret_cast<f32x4*>(yz) = f32x4{0.f, 0.f, 0.f, 0.f};
+      } else {
+        for (int r = 0; r < 4; ++r)
+          if (t0 + r < L) yz[r] = 0.f;
+      }
+      return;
+    }
+  }
   const float* __restrict__ xb = x + (long long)b * C * L;
   float acc[4] = {bias[0], bias[0], bias[0], bias[0]};
-  const bool inner = t0 >= 4 && t0 + 8 <= L && (L & 3) == 0;
+  const bool inner = t0 >= 4 && t0 + 8 <= Lb && (L & 3) == 0;
 #pragma unroll
   for (int ci = 0; ci < C; ++ci) {
     float v[12];   // x[t0 - 4 + j]
@@ -624,7 +689,7 @@ __global__ __launch_bounds__(256) void conv_post_kernel(const float* __restrict_
 #pragma unroll
       for (int j = 0; j < 12; ++j) {
         const int t = t0 - 4 + j;
-        v[j] = (t >= 0 && t < L) ? xr[t] : 0.f;
+        v[j] = (t >= 0 && t < Lb) ? xr[t] : 0.f;
       }
     }
 #pragma unroll
@@ -637,12 +702,12 @@ __global__ __launch_bounds__(256) void conv_post_kernel(const float* __restrict_
     }
   }
   float* __restrict__ yr = y + (long long)b * L + t0;
-  if (t0 + 3 < L && (L & 3) == 0) {
+  if (t0 + 3 < Lb && (L & 3) == 0) {
     *reinterpret_cast<f32x4*>(yr) = f32x4{tanhf(acc[0]), tanhf(acc[1]), tanhf(acc[2]), tanhf(acc[3])};
   } else {
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-      if (t0 + r < L) yr[r] = tanhf(acc[r]);
+      if (t0 + r < L) yr[r] = (!RAG || t0 + r < Lb) ? tanhf(acc[r]) : 0.f;
   }
 }
 
@@ -655,14 +720,17 @@ struct ConvTArgs {
   float* y;           // [B][Cout][Lin*u]
   float in_slope;
   int Cin, Cout, Lin, K, u, p;
+  const int* lens;    // ragged: see row_bound (the bound of the INPUT row)
+  int lmul;
 };
-template <int CO_BLK>
+template <int CO_BLK, bool RAG = false>
 __global__ __launch_bounds__(256) void conv_transpose1d_kernel(ConvTArgs a) {
   const int Lout = a.Lin * a.u;
   const int t = blockIdx.x * 256 + threadIdx.x;
   const int co0 = blockIdx.y * CO_BLK;
   const int b = blockIdx.z;
-  if (t >= Lout) return;
+  const int Lb = row_bound<RAG>(a.lens, a.lmul, b, a.Lin);
+  if (t >= Lb * a.u) return;   // (ragged: tiles beyond the row's end leave here, before any load)
   float acc[CO_BLK];
 #pragma unroll
   for (int c = 0; c < CO_BLK; ++c) acc[c] = (co0 + c < a.Cout) ? a.bias[co0 + c] : 0.f;
@@ -671,7 +739,7 @@ __global__ __launch_bounds__(256) void conv_transpose1d_kernel(ConvTArgs a) {
   const float* __restrict__ xb = a.x + (long long)b * a.Cin * a.Lin;
   for (int k = r; k < a.K; k += a.u) {
     const int i = q - (k - r) / a.u;
-    if (i < 0 || i >= a.Lin) continue;
+    if (i < 0 || i >= Lb) continue;
     for (int ci = 0; ci < a.Cin; ++ci) {
       float xv = xb[(long long)ci * a.Lin + i];
       xv = xv > 0.f ? xv : xv * a.in_slope;
@@ -733,10 +801,12 @@ int launch_conv_kt(const ConvArgs& a, int B, hipStream_t st) {
   const size_t lds = (size_t)CI_CHUNK * (TILE + (K - 1) * a.dil) * sizeof(float);
   if (a.Cout >= 16) {
     dim3 grid(cdiv(a.L, TILE), cdiv(a.Cout, 16), B);
-    hipLaunchKernelGGL((conv1d_kernel<K, 16, TT>), grid, dim3(256), lds, st, a);
+    if (a.lens) hipLaunchKernelGGL((conv1d_kernel<K, 16, TT, true>), grid, dim3(256), lds, st, a);
+    else hipLaunchKernelGGL((conv1d_kernel<K, 16, TT>), grid, dim3(256), lds, st, a);
   } else {
     dim3 grid(cdiv(a.L, TILE), cdiv(a.Cout, 8), B);
-    hipLaunchKernelGGL((conv1d_kernel<K, 8, TT>), grid, dim3(256), lds, st, a);
+    if (a.lens) hipLaunchKernelGGL((conv1d_kernel<K, 8, TT, true>), grid, dim3(256), lds, st, a);
+    else hipLaunchKernelGGL((conv1d_kernel<K, 8, TT>), grid, dim3(256), lds, st, a);
   }
   BSG_LAUNCH_CHECK();
   return BSG_OK;
@@ -754,8 +824,14 @@ template <int TT>
 int launch_convT_t(const ConvArgs& a, int B, hipStream_t st) {
   constexpr int TILE = 256 * TT;
   const size_t lds = (size_t)CI_CHUNK * (TILE + 1) * sizeof(float);
-  if (a.Cout >= 16) hipLaunchKernelGGL((conv1d_kernel<2, 16, TT>), dim3(cdiv(a.Lq, TILE), cdiv(a.Cout, 16), B * a.n_phase), dim3(256), lds, st, a);
-  else hipLaunchKernelGGL((conv1d_kernel<2, 8, TT>), dim3(cdiv(a.Lq, TILE), cdiv(a.Cout, 8), B * a.n_phase), dim3(256), lds, st, a);
+  const dim3 grid(cdiv(a.Lq, TILE), cdiv(a.Cout, a.Cout >= 16 ? 16 : 8), B * a.n_phase);
+  if (a.Cout >= 16) {
+    if (a.lens) hipLaunchKernelGGL((conv1d_kernel<2, 16, TT, true>), grid, dim3(256), lds, st, a);
+    else hipLaunchKernelGGL((conv1d_kernel<2, 16, TT>), grid, dim3(256), lds, st, a);
+  } else {
+    if (a.lens) hipLaunchKernelGGL((conv1d_kernel<2, 8, TT, true>), grid, dim3(256), lds, st, a);
+    else hipLaunchKernelGGL((conv1d_kernel<2, 8, TT>), grid, dim3(256), lds, st, a);
+  }
   BSG_LAUNCH_CHECK();
   return BSG_OK;
 }
@@ -783,18 +859,22 @@ int dispatch_kc(int K, int C, F f) {
   }
 }
 
-template <int K, int C, int TT>
-int launch_pair_t(const PairArgs& a, int B, hipStream_t st) {
+template <int K, int C, int TT, bool RAG>
+int launch_pair_t_r(const PairArgs& a, int B, hipStream_t st) {
   constexpr int P = 256 * TT, POUT = P - (K - 1);
   const size_t lds = ((size_t)C * P + 16) * sizeof(float);
   static bool attr = false;
   if (!attr) {
-    BSG_HIP(hipFuncSetAttribute((const void*)resblock_pair_kernel<K, C, TT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    BSG_HIP(hipFuncSetAttribute((const void*)resblock_pair_kernel<K, C, TT, RAG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = true;
   }
-  hipLaunchKernelGGL((resblock_pair_kernel<K, C, TT>), dim3(cdiv(a.L, POUT), B), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((resblock_pair_kernel<K, C, TT, RAG>), dim3(cdiv(a.L, POUT), B), dim3(256), lds, st, a);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
+}
+template <int K, int C, int TT>
+int launch_pair_t(const PairArgs& a, int B, hipStream_t st) {
+  return a.lens ? launch_pair_t_r<K, C, TT, true>(a, B, st) : launch_pair_t_r<K, C, TT, false>(a, B, st);
 }
 // tt positions per thread (pair_valu_tt): only the widths within the 64-accumulator budget (C TT <= 64) are built
 template <int K, int C>
@@ -894,7 +974,7 @@ __device__ __forceinline__ void conv_h2(f32x16 (&acc)[C / 32][NB], const _Float1
   }
 }
 
-template <int K, int C, int NB>
+template <int K, int C, int NB, bool RAG = false>
 __global__ __launch_bounds__(256) void resblock_pair_h2_kernel(PairArgs a) {
   constexpr int PT = 128 * NB, H2 = (K - 1) / 2, POUT = PT - (K - 1), RT = C / 32, TS = PT + 16, ROWB = 2 * C + 16;
   constexpr float ACC_SC = HG_WSC * HG_ASC, ACC_INV = 1.0f / (HG_WSC * HG_ASC);
@@ -903,6 +983,10 @@ __global__ __launch_bounds__(256) void resblock_pair_h2_kernel(PairArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, lh = lane >> 5;
   const int t0 = blockIdx.x * POUT, b = blockIdx.y;
+  const int Lb = row_bound<RAG>(a.lens, a.lmul, b, a.L);
+  if constexpr (RAG) {
+    if (t0 >= Lb) return;   // the tile lies beyond the row's end: before the first load and the first barrier
+  }
   const int h1 = H2 * a.dil, span = PT + 2 * h1;
   const int plane = (span > TS ? span : TS) * ROWB;
   const float* __restrict__ xb = a.x + (long long)b * C * a.L;
@@ -928,7 +1012,7 @@ __global__ __launch_bounds__(256) void resblock_pair_h2_kernel(PairArgs a) {
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       const int pcol = 32 * NB * wave + 32 * nb + l31, t = t0 + pcol;
-      const bool ok = pcol < POUT && t < a.L;
+      const bool ok = pcol < POUT && t < Lb;
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -944,7 +1028,7 @@ __global__ __launch_bounds__(256) void resblock_pair_h2_kernel(PairArgs a) {
       const int idx = idx0 + 256 * u;
       const int cq = idx / span, jx = idx - cq * span;
       const int t = t0 - H2 - h1 + jx;
-      const bool ok = idx < (C / 4) * span && t >= 0 && t < a.L;
+      const bool ok = idx < (C / 4) * span && t >= 0 && t < Lb;
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[u][e] = ok ? xb[(long long)(4 * cq + e) * a.L + t] : 0.f;
     }
@@ -979,7 +1063,7 @@ __global__ __launch_bounds__(256) void resblock_pair_h2_kernel(PairArgs a) {
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
     const int pcol = n0 + 32 * nb + l31, u = t0 - H2 + pcol;
-    const bool in = u >= 0 && u < a.L;
+    const bool in = u >= 0 && u < Lb;
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -1020,7 +1104,7 @@ __global__ __launch_bounds__(256) void resblock_pair_h2_kernel(PairArgs a) {
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
     const int pcol = n0 + 32 * nb + l31, t = t0 + pcol;
-    if (pcol >= POUT || t >= a.L) continue;
+    if (pcol >= POUT || t >= Lb) continue;
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
       const long long i0 = ((long long)b * C + 32 * rt + 4 * lh) * a.L + t;
@@ -1050,19 +1134,23 @@ __global__ __launch_bounds__(256) void resblock_pair_h2_kernel(PairArgs a) {
   }
 }
 
-template <int K, int C, int NB>
-int launch_pair_h2_t(const PairArgs& a, int B, hipStream_t st) {
+template <int K, int C, int NB, bool RAG>
+int launch_pair_h2_t_r(const PairArgs& a, int B, hipStream_t st) {
   constexpr int PT = 128 * NB, POUT = PT - (K - 1), ROWB = 2 * C + 16;
   const int span = PT + 2 * ((K - 1) / 2 * a.dil);
   const size_t lds = (size_t)2 * (span > PT + 16 ? span : PT + 16) * ROWB;
   static size_t attr = 0;
   if (lds > attr) {
-    BSG_HIP(hipFuncSetAttribute((const void*)resblock_pair_h2_kernel<K, C, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    BSG_HIP(hipFuncSetAttribute((const void*)resblock_pair_h2_kernel<K, C, NB, RAG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = lds;
   }
-  hipLaunchKernelGGL((resblock_pair_h2_kernel<K, C, NB>), dim3(cdiv(a.L, POUT), B), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((resblock_pair_h2_kernel<K, C, NB, RAG>), dim3(cdiv(a.L, POUT), B), dim3(256), lds, st, a);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
+}
+template <int K, int C, int NB>
+int launch_pair_h2_t(const PairArgs& a, int B, hipStream_t st) {
+  return a.lens ? launch_pair_h2_t_r<K, C, NB, true>(a, B, st) : launch_pair_h2_t_r<K, C, NB, false>(a, B, st);
 }
 int launch_pair_h2(const PairArgs& a, int K, int C, int nb, int B, hipStream_t st) {
   const int rc = dispatch_kc<32, 64>(K, C, [&](auto k, auto c) {
@@ -1224,7 +1312,7 @@ __device__ __forceinline__ void conv_h16(f32x4h (&acc)[NC], const hf16x8 (&A)[(K
 #endif
 }
 
-template <int K, int C, int NB>
+template <int K, int C, int NB, bool RAG = false>
 __global__ __launch_bounds__(256) void resblock_pair_h16_kernel(PairArgs a) {
   constexpr int PT = 128 * NB, H2 = (K - 1) / 2, POUT = PT - (K - 1), TS = PT + 16, ROWB = 2 * C, NC = 2 * NB;
   constexpr float ACC_SC = HG_WSC * HG_ASC, ACC_INV = 1.0f / (HG_WSC * HG_ASC);
@@ -1233,6 +1321,10 @@ __global__ __launch_bounds__(256) void resblock_pair_h16_kernel(PairArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l15 = lane & 15, kb = lane >> 4;
   const int t0 = blockIdx.x * POUT, b = blockIdx.y;
+  const int Lb = row_bound<RAG>(a.lens, a.lmul, b, a.L);
+  if constexpr (RAG) {
+    if (t0 >= Lb) return;   // the tile lies beyond the row's end: before the first load and the first barrier
+  }
   const int h1 = H2 * a.dil, span = PT + 2 * h1;
   const int plane = (span > TS ? span : TS) * ROWB;
   const float* __restrict__ xb = a.x + (long long)b * C * a.L;
@@ -1258,7 +1350,7 @@ __global__ __launch_bounds__(256) void resblock_pair_h16_kernel(PairArgs a) {
 #pragma unroll
     for (int ct = 0; ct < 2 * NB; ++ct) {
       const int pcol = 32 * NB * wave + 16 * ct + (lane & 15), t = t0 + pcol;
-      const bool ok = rows_ok_ && pcol < POUT && t < a.L;
+      const bool ok = rows_ok_ && pcol < POUT && t < Lb;
 #pragma unroll
       for (int r = 0; r < 4; ++r) xres[ct][r] = ok ? xb[(long long)(4 * (lane >> 4) + r) * a.L + t] : 0.f;
     }
@@ -1271,7 +1363,7 @@ __global__ __launch_bounds__(256) void resblock_pair_h16_kernel(PairArgs a) {
       const int idx = idx0 + 256 * u;
       const int cq = idx / span, jx = idx - cq * span;
       const int t = t0 - H2 - h1 + jx;
-      const bool ok = idx < (C / 4) * span && t >= 0 && t < a.L;
+      const bool ok = idx < (C / 4) * span && t >= 0 && t < Lb;
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[u][e] = ok ? xb[(long long)(4 * cq + e) * a.L + t] : 0.f;
     }
@@ -1309,7 +1401,7 @@ __global__ __launch_bounds__(256) void resblock_pair_h16_kernel(PairArgs a) {
 #pragma unroll
     for (int ct = 0; ct < NC; ++ct) {
       const int pcol = n0 + 16 * ct + l15, u = t0 - H2 + pcol;
-      const bool in = u >= 0 && u < a.L;
+      const bool in = u >= 0 && u < Lb;
       float v[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -1340,7 +1432,7 @@ __global__ __launch_bounds__(256) void resblock_pair_h16_kernel(PairArgs a) {
 #pragma unroll
   for (int ct = 0; ct < NC; ++ct) {
     const int pcol = n0 + 16 * ct + l15, t = t0 + pcol;
-    if (pcol >= POUT || t >= a.L) continue;
+    if (pcol >= POUT || t >= Lb) continue;
     const long long i0 = ((long long)b * C + 4 * kb) * a.L + t;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -1352,19 +1444,23 @@ __global__ __launch_bounds__(256) void resblock_pair_h16_kernel(PairArgs a) {
   }
 }
 
-template <int K, int C, int NB>
-int launch_pair_h16_t(const PairArgs& a, int B, hipStream_t st) {
+template <int K, int C, int NB, bool RAG>
+int launch_pair_h16_t_r(const PairArgs& a, int B, hipStream_t st) {
   constexpr int PT = 128 * NB, POUT = PT - (K - 1), ROWB = 2 * C;
   const int span = PT + 2 * ((K - 1) / 2 * a.dil);
   const size_t lds = (size_t)2 * (span > PT + 16 ? span : PT + 16) * ROWB;
   static size_t attr = 0;
   if (lds > attr) {
-    BSG_HIP(hipFuncSetAttribute((const void*)resblock_pair_h16_kernel<K, C, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    BSG_HIP(hipFuncSetAttribute((const void*)resblock_pair_h16_kernel<K, C, NB, RAG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = lds;
   }
-  hipLaunchKernelGGL((resblock_pair_h16_kernel<K, C, NB>), dim3(cdiv(a.L, POUT), B), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((resblock_pair_h16_kernel<K, C, NB, RAG>), dim3(cdiv(a.L, POUT), B), dim3(256), lds, st, a);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
+}
+template <int K, int C, int NB>
+int launch_pair_h16_t(const PairArgs& a, int B, hipStream_t st) {
+  return a.lens ? launch_pair_h16_t_r<K, C, NB, true>(a, B, st) : launch_pair_h16_t_r<K, C, NB, false>(a, B, st);
 }
 int launch_pair_h16(const PairArgs& a, int K, int C, int nb, int B, hipStream_t st) {
   const int rc = dispatch_kc<16, 8>(K, C, [&](auto k, auto c) {
@@ -1407,9 +1503,11 @@ struct ChainArgs {
   int L, n_pairs;
   int dil[3];
   unsigned* range_events;
+  const int* lens;       // ragged: see row_bound
+  int lmul;
 };
 
-template <int K, int C, int NC>   // NC column tiles of 16 positions per wave: a tile of PT = 64 NC positions
+template <int K, int C, int NC, bool RAG = false>   // NC column tiles of 16 positions per wave: a tile of PT = 64 NC positions
 __global__ __launch_bounds__(256) void resblock_chain_h16_kernel(ChainArgs a) {
   constexpr int PT = 64 * NC, H2 = (K - 1) / 2, ROWB = 2 * C;
   constexpr float ACC_SC = HG_WSC * HG_ASC, ACC_INV = 1.0f / (HG_WSC * HG_ASC);
@@ -1421,6 +1519,10 @@ __global__ __launch_bounds__(256) void resblock_chain_h16_kernel(ChainArgs a) {
   for (int m = 0; m < a.n_pairs; ++m) {
     ht += H2 * (a.dil[m] + 1);
     dmax = a.dil[m] > dmax ? a.dil[m] : dmax;
+  }
+  const int Lb = row_bound<RAG>(a.lens, a.lmul, (int)blockIdx.y, a.L);
+  if constexpr (RAG) {
+    if ((int)blockIdx.x * (PT - 2 * ht) >= Lb) return;   // the tile's first output position lies beyond the row's end
   }
   const int pa = H2 * dmax;              // pad rows on each side of the image (always zero)
   const int plane = (PT + 2 * pa) * ROWB;
@@ -1442,7 +1544,7 @@ __global__ __launch_bounds__(256) void resblock_chain_h16_kernel(ChainArgs a) {
 #pragma unroll
   for (int ct = 0; ct < NC; ++ct) {
     const int t = t0 + n0 + 16 * ct + l15;
-    const bool in = t >= 0 && t < a.L;
+    const bool in = t >= 0 && t < Lb;
     in_mask |= in ? 1u << ct : 0u;
 #pragma unroll
     for (int r = 0; r < 4; ++r) xres[ct][r] = (in && rows_ok) ? xb[(long long)(4 * kb + r) * a.L + t] : 0.f;
@@ -1514,7 +1616,7 @@ __global__ __launch_bounds__(256) void resblock_chain_h16_kernel(ChainArgs a) {
 #pragma unroll
   for (int ct = 0; ct < NC; ++ct) {
     const int pcol = n0 + 16 * ct + l15, t = t0 + pcol;
-    if (pcol < ht || pcol >= PT - ht || t >= a.L) continue;
+    if (pcol < ht || pcol >= PT - ht || t >= Lb) continue;
     const long long i0 = ((long long)b * C + 4 * kb) * a.L + t;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -1526,8 +1628,8 @@ __global__ __launch_bounds__(256) void resblock_chain_h16_kernel(ChainArgs a) {
   }
 }
 
-template <int K, int C, int NC>
-int launch_chain_h16_t(const ChainArgs& a, int B, hipStream_t st) {
+template <int K, int C, int NC, bool RAG>
+int launch_chain_h16_t_r(const ChainArgs& a, int B, hipStream_t st) {
   constexpr int PT = 64 * NC, H2 = (K - 1) / 2, ROWB = 2 * C;
   int ht = 0, dmax = 1;
   for (int m = 0; m < a.n_pairs; ++m) { ht += H2 * (a.dil[m] + 1); dmax = a.dil[m] > dmax ? a.dil[m] : dmax; }
@@ -1535,12 +1637,16 @@ int launch_chain_h16_t(const ChainArgs& a, int B, hipStream_t st) {
   const size_t lds = (size_t)2 * (PT + 2 * H2 * dmax) * ROWB + 6 * 16 * sizeof(float);
   static size_t attr = 0;
   if (lds > attr) {
-    BSG_HIP(hipFuncSetAttribute((const void*)resblock_chain_h16_kernel<K, C, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    BSG_HIP(hipFuncSetAttribute((const void*)resblock_chain_h16_kernel<K, C, NC, RAG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = lds;
   }
-  hipLaunchKernelGGL((resblock_chain_h16_kernel<K, C, NC>), dim3(cdiv(a.L, pout), B), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((resblock_chain_h16_kernel<K, C, NC, RAG>), dim3(cdiv(a.L, pout), B), dim3(256), lds, st, a);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
+}
+template <int K, int C, int NC>
+int launch_chain_h16_t(const ChainArgs& a, int B, hipStream_t st) {
+  return a.lens ? launch_chain_h16_t_r<K, C, NC, true>(a, B, st) : launch_chain_h16_t_r<K, C, NC, false>(a, B, st);
 }
 bool chain_h16_supported(int K, int C, int n_pairs, const int* dil) {
   if (!((K == 3 || K == 7 || K == 11) && (C == 16 || C == 8)) || n_pairs < 1 || n_pairs > 3) return false;
@@ -1557,20 +1663,24 @@ int launch_chain_h16(const ChainArgs& a, int K, int C, int nc, int B, hipStream_
   return BSG_EINVAL;
 }
 
-template <int K, int C, int NB>
-int launch_pair_mfma_t(const PairArgs& a, int B, hipStream_t st) {
+template <int K, int C, int NB, bool RAG>
+int launch_pair_mfma_t_r(const PairArgs& a, int B, hipStream_t st) {
   constexpr int PT = 128 * NB, POUT = PT - (K - 1);
   const int h1 = (K - 1) / 2 * a.dil;
   const int XS = (PT + 2 * h1 + 3) & ~3;
   const size_t lds = (size_t)C * (XS > PT + 16 ? XS : PT + 16) * sizeof(float);
   static size_t attr = 0;
   if (lds > attr) {
-    BSG_HIP(hipFuncSetAttribute((const void*)resblock_pair_mfma_kernel<K, C, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    BSG_HIP(hipFuncSetAttribute((const void*)resblock_pair_mfma_kernel<K, C, NB, RAG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = lds;
   }
-  hipLaunchKernelGGL((resblock_pair_mfma_kernel<K, C, NB>), dim3(cdiv(a.L, POUT), B), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((resblock_pair_mfma_kernel<K, C, NB, RAG>), dim3(cdiv(a.L, POUT), B), dim3(256), lds, st, a);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
+}
+template <int K, int C, int NB>
+int launch_pair_mfma_t(const PairArgs& a, int B, hipStream_t st) {
+  return a.lens ? launch_pair_mfma_t_r<K, C, NB, true>(a, B, st) : launch_pair_mfma_t_r<K, C, NB, false>(a, B, st);
 }
 int launch_pair_mfma(const PairArgs& a, int K, int C, int nb, int B, hipStream_t st) {
   const int rc = dispatch_kc<32, 64>(K, C, [&](auto k, auto c) {
@@ -1600,9 +1710,9 @@ int launch_conv(const ConvArgs& a, int K, int tt, int B, hipStream_t st) {
 
 namespace bsg {
 int nsf_launch_source(const float* f0, const float* rand_ini, const float* noise, const float* lin_w, const float* lin_b,
-                      float* sw_tmp, float* har, int B, int T, int hop, int NH, float sr, hipStream_t st);
+                      float* sw_tmp, float* har, int B, int T, int hop, int NH, float sr, const int* lens, hipStream_t st);
 int nsf_launch_source_add(float* x, const float* har, const float* w, const float* bias, int B, int Cc, int Lx, long long Lh, int k,
-                          int stride, int pad, hipStream_t st);
+                          int stride, int pad, const int* lens, int lmul, int hop, hipStream_t st);
 }
 using namespace bsg;
 
@@ -1663,6 +1773,8 @@ struct bsg_hifigan {
   bool h2_ok = true;
   unsigned short* planes = nullptr;       // activation planes of the gemm_h2w products (hi, then lo)
   size_t planes_cap = 0;                  // halfs
+  int* lens = nullptr;                    // ragged forwards: the rows' frame counts on the device, written by set_lens_kernel launches of the call itself
+  size_t lens_cap = 0;
   std::string path;                       // the launches of the last forward (bsg_hifigan_last_path)
   std::vector<HgStep> steps;              // room for the plan of a forward (plan_hifigan), sized at create
 };
@@ -1693,6 +1805,7 @@ extern "C" void bsg_hifigan_destroy(bsg_hifigan* h) {
   if (h->sw_tmp) (void)hipFree(h->sw_tmp);
   if (h->har) (void)hipFree(h->har);
   if (h->planes) (void)hipFree(h->planes);
+  if (h->lens) (void)hipFree(h->lens);
   h2w_free(&h->pre.h2w);
   for (ConvW& c : h->ups) h2w_free(&c.h2w);
   for (float* t : h->create_tmp) (void)hipFree(t);
@@ -2032,9 +2145,16 @@ static int plan_hifigan(const bsg_hifigan* h, int B, int T, bool nsf, HgStep* ou
   return n;
 }
 
+// the ragged part of a launch's arguments: the device array of frame counts (null: the padded call) and the product of the upsample rates so far
+struct HgRows {
+  const int* lens;
+  int lmul;
+};
+
 static int run_conv(const ConvW& c, const float* x, float* y, int tt, int B, int L, int dil, float in_slope, const float* res,
-                    const float* acc_in, float out_div, int out_tanh, hipStream_t st) {
+                    const float* acc_in, float out_div, int out_tanh, HgRows rows, hipStream_t st) {
   ConvArgs a{};
+  a.lens = rows.lens; a.lmul = rows.lmul; a.zero_tail = rows.lens && out_tanh;   // (out_tanh: conv_post, whose output is the caller's)
   a.x = x; a.w = c.wpk; a.bias = c.b; a.y = y; a.res = res; a.acc_in = acc_in; a.out_div = out_div; a.in_slope = in_slope;
   a.out_tanh = out_tanh; a.Cin = c.cin; a.Cout = c.cout; a.L = L; a.dil = dil; a.pad = (c.k * dil - dil) / 2;
   return launch_conv(a, c.k, tt, B, st);
@@ -2043,11 +2163,12 @@ static int run_conv(const ConvW& c, const float* x, float* y, int tt, int B, int
 // conv_pre :150 / a u = 8 transposed convolution on the matrix pipe (gemm_h2w): lrelu(src) as planes [rows][Kp] (rows >= Lin: the rest zero),
 // ONE `taps`-tap product with the pre-split weight rows; up_u = 8: the rows are (co, phase), stored phase-interleaved (H2wArgs::up_u)
 static int run_h2w(bsg_hifigan* h, const ConvW& c, const float* src, float* dst, int B, int Lin, int rows, int taps, float slope, int up_u, int up_p,
-                   hipStream_t st) {
+                   HgRows rg, hipStream_t st) {
   const long long n = (long long)B * rows * c.h2w_kp;
   const int Lout = up_u ? Lin * up_u : Lin;
   TRY(ensure_planes(h, (size_t)2 * n, st));
-  TRY(h2w_split_transposed_lrelu(src, h->planes, h->planes + n, B, c.cin, c.h2w_kp, Lin, rows, slope, st));
+  // ragged: the feeding pass reads a row up to ITS end and writes zeros from there on, as it does from Lin on; the product runs the padded shape
+  TRY(h2w_split_transposed_lrelu(src, h->planes, h->planes + n, B, c.cin, c.h2w_kp, Lin, rows, slope, rg.lens, rg.lmul, st));
   H2wArgs g{};
   g.act = h->planes; g.act_plane = n; g.lda = c.h2w_kp; g.sAct = (long long)rows * c.h2w_kp; g.wpack = c.h2w.pack; g.rows = rows; g.K = c.h2w_kp;
   g.Wn = up_u ? c.cout * up_u : c.cout; g.taps = taps; g.tap_shift0 = up_u ? -1 : -(taps / 2); g.act_is_a = 0; g.C = dst; g.ldc = Lout;
@@ -2055,7 +2176,8 @@ static int run_h2w(bsg_hifigan* h, const ConvW& c, const float* src, float* dst,
   return launch_gemm_h2w(g, st);
 }
 
-static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, int32_t T, void* stream, const float* har, long long Lh) {
+static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, int32_t T, void* stream, const float* har, long long Lh,
+                       const int* lens) {
   BSG_REQUIRE(h && mel && wav && B > 0 && T > 0, "hifigan_forward: bad argument");
   BSG_REQUIRE(B <= 65535, "hifigan_forward: B=%d > 65535", B);
   hipStream_t st = (hipStream_t)stream;
@@ -2086,34 +2208,45 @@ static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, 
   const float slope = 0.1f;   // LRELU_SLOPE, hifigan.py:11
   const float* y = xs;
   int L = T;
+  int hop = 1;
+  for (int i = 0; i < c.n_ups; ++i) hop *= c.upsample_rates[i];
   for (int n = 0; n < n_steps; ++n) {
     const HgStep& s = h->steps[n];
     const int i = s.i, j = s.j, m = s.m;
+    const HgRows rg{lens, L / T};   // (L = T x the rates so far)
     if (s.site == HG_PRE) {
-      if (s.form == HG_H2W) TRY(run_h2w(h, h->pre, mel, x, B, T, T, h->pre.k, 1.0f, 0, 0, st));
-      else TRY(run_conv(h->pre, mel, x, s.var, B, T, 1, 1.0f, nullptr, nullptr, 1.0f, 0, st));            // conv_pre :150
+      if (s.form == HG_H2W) TRY(run_h2w(h, h->pre, mel, x, B, T, T, h->pre.k, 1.0f, 0, 0, rg, st));
+      else TRY(run_conv(h->pre, mel, x, s.var, B, T, 1, 1.0f, nullptr, nullptr, 1.0f, 0, rg, st));            // conv_pre :150
     } else if (s.site == HG_POST) {
-      if (s.form == HG_POST4) hipLaunchKernelGGL(conv_post_kernel<8>, dim3(cdiv(L, 1024), B), dim3(256), 0, st, (const float*)x, (const float*)h->post.w, (const float*)h->post.b, wav, L, 0.01f);
-      else TRY(run_conv(h->post, x, wav, s.var, B, L, 1, 0.01f, nullptr, nullptr, 1.0f, 1, st));          // :169-171 (default slope 0.01)
+      if (s.form == HG_POST4 && lens) hipLaunchKernelGGL((conv_post_kernel<8, true>), dim3(cdiv(L, 1024), B), dim3(256), 0, st, (const float*)x, (const float*)h->post.w, (const float*)h->post.b, wav, L, 0.01f, rg.lens, rg.lmul);
+      else if (s.form == HG_POST4) hipLaunchKernelGGL(conv_post_kernel<8>, dim3(cdiv(L, 1024), B), dim3(256), 0, st, (const float*)x, (const float*)h->post.w, (const float*)h->post.b, wav, L, 0.01f, rg.lens, rg.lmul);
+      else TRY(run_conv(h->post, x, wav, s.var, B, L, 1, 0.01f, nullptr, nullptr, 1.0f, 1, rg, st));          // :169-171 (default slope 0.01)
       BSG_LAUNCH_CHECK();
     } else if (s.site == HG_SRC) {   // x = x + LayerNorm_C(relu(noise_conv_i(har_source)))                       (hifigan.py:154-160)
       const ConvW& nc = h->noise_convs[i];
       const int stride = i + 1 < c.n_ups ? nc.k / 2 : 1;
-      TRY(nsf_launch_source_add(xs, har, nc.w, nc.b, B, nc.cout, L, Lh, nc.k, stride, i + 1 < c.n_ups ? stride / 2 : 0, st));
+      TRY(nsf_launch_source_add(xs, har, nc.w, nc.b, B, nc.cout, L, Lh, nc.k, stride, i + 1 < c.n_ups ? stride / 2 : 0, rg.lens, rg.lmul, hop, st));
     } else if (s.site == HG_UP) {
       const ConvW& up = h->ups[i];
       const int u = c.upsample_rates[i], p = (up.k - u) / 2, Lout = L * u;
       UpArgs ua{};
       ua.x = x; ua.w = s.form == HG_UPK ? up.wpu : up.w; ua.bias = up.b; ua.y = xs; ua.slope = slope; ua.Cin = up.cin; ua.Cout = up.cout; ua.Lin = L; ua.p = p;
+      ua.lens = rg.lens; ua.lmul = rg.lmul;
       switch (s.form) {
-        case HG_H2W: TRY(run_h2w(h, up, x, xs, B, L, L + 1, 2, slope, 8, p, st)); break;
+        case HG_H2W: TRY(run_h2w(h, up, x, xs, B, L, L + 1, 2, slope, 8, p, rg, st)); break;
         case HG_UP2:
-          if (up.cout == 16) hipLaunchKernelGGL(upsample2_kernel<16>, dim3(cdiv(Lout, 1024), 1, B), dim3(256), 0, st, ua);
+          if (up.cout == 16 && lens) hipLaunchKernelGGL((upsample2_kernel<16, true>), dim3(cdiv(Lout, 1024), 1, B), dim3(256), 0, st, ua);
+          else if (up.cout == 16) hipLaunchKernelGGL(upsample2_kernel<16>, dim3(cdiv(Lout, 1024), 1, B), dim3(256), 0, st, ua);
+          else if (lens) hipLaunchKernelGGL((upsample2_kernel<8, true>), dim3(cdiv(Lout, 1024), 1, B), dim3(256), 0, st, ua);
           else hipLaunchKernelGGL(upsample2_kernel<8>, dim3(cdiv(Lout, 1024), 1, B), dim3(256), 0, st, ua);
           break;
         case HG_UPK: {
           const dim3 grid(cdiv(L + 1, 256), cdiv(up.cout, 8), B);
-          if (u == 8) hipLaunchKernelGGL(upsample_kernel<8>, grid, dim3(256), 0, st, ua);
+          if (lens) {
+            if (u == 8) hipLaunchKernelGGL((upsample_kernel<8, true>), grid, dim3(256), 0, st, ua);
+            else if (u == 4) hipLaunchKernelGGL((upsample_kernel<4, true>), grid, dim3(256), 0, st, ua);
+            else hipLaunchKernelGGL((upsample_kernel<2, true>), grid, dim3(256), 0, st, ua);
+          } else if (u == 8) hipLaunchKernelGGL(upsample_kernel<8>, grid, dim3(256), 0, st, ua);
           else if (u == 4) hipLaunchKernelGGL(upsample_kernel<4>, grid, dim3(256), 0, st, ua);
           else hipLaunchKernelGGL(upsample_kernel<2>, grid, dim3(256), 0, st, ua);
           break;
@@ -2122,15 +2255,17 @@ static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, 
           ConvArgs a{};
           a.x = x; a.w = up.wpk; a.bias = up.b; a.y = xs; a.out_div = 1.0f; a.in_slope = slope;
           a.Cin = up.cin; a.Cout = up.cout; a.L = L; a.dil = 1; a.pad = 1;
-          a.n_phase = u; a.ph_off = -p; a.Lq = L + 1; a.Lout = Lout;
+          a.n_phase = u; a.ph_off = -p; a.Lq = L + 1; a.Lout = Lout; a.lens = rg.lens; a.lmul = rg.lmul;
           a.w_phase_stride = (long long)cdiv(up.cout, up.cout >= 16 ? 16 : 8) * up.cin * 2 * (up.cout >= 16 ? 16 : 8);
           TRY(launch_convT(a, s.var, B, st));
           break;
         }
         default: {
           ConvTArgs t{};
-          t.x = x; t.w = up.w; t.bias = up.b; t.y = xs; t.in_slope = slope; t.Cin = up.cin; t.Cout = up.cout; t.Lin = L; t.K = up.k; t.u = u; t.p = p;
-          if (up.cout >= 16) hipLaunchKernelGGL(conv_transpose1d_kernel<16>, dim3(cdiv(Lout, 256), cdiv(up.cout, 16), B), dim3(256), 0, st, t);
+          t.x = x; t.w = up.w; t.bias = up.b; t.y = xs; t.in_slope = slope; t.Cin = up.cin; t.Cout = up.cout; t.Lin = L; t.K = up.k; t.u = u; t.p = p; t.lens = rg.lens; t.lmul = rg.lmul;
+          if (up.cout >= 16 && lens) hipLaunchKernelGGL((conv_transpose1d_kernel<16, true>), dim3(cdiv(Lout, 256), cdiv(up.cout, 16), B), dim3(256), 0, st, t);
+          else if (up.cout >= 16) hipLaunchKernelGGL(conv_transpose1d_kernel<16>, dim3(cdiv(Lout, 256), cdiv(up.cout, 16), B), dim3(256), 0, st, t);
+          else if (lens) hipLaunchKernelGGL((conv_transpose1d_kernel<8, true>), dim3(cdiv(Lout, 256), cdiv(up.cout, 8), B), dim3(256), 0, st, t);
           else hipLaunchKernelGGL(conv_transpose1d_kernel<8>, dim3(cdiv(Lout, 256), cdiv(up.cout, 8), B), dim3(256), 0, st, t);
         }
       }
@@ -2147,12 +2282,13 @@ static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, 
       const float out_div = (last && j == c.n_kernels - 1) ? (float)c.n_kernels : 1.0f;
       const int dil = c.resblock_dilations[j][m < 0 ? 0 : m];
       PairArgs pa{};
-      pa.x = y; pa.b1 = c1.b; pa.y = dst; pa.acc_in = acc_in; pa.out_div = out_div; pa.slope = slope; pa.L = L; pa.dil = dil;
+      pa.x = y; pa.b1 = c1.b; pa.y = dst; pa.acc_in = acc_in; pa.out_div = out_div; pa.slope = slope; pa.L = L; pa.dil = dil; pa.lens = rg.lens; pa.lmul = rg.lmul;
       if (c2) pa.b2 = c2->b;
       switch (s.form) {
         case HG_CHAIN: {   // a whole ResBlock1 of 8 / 16 channels in one launch (resblock_chain_h16_kernel)
           ChainArgs ca{};
           ca.x = xs; ca.y = x; ca.acc_in = acc_in; ca.out_div = out_div; ca.slope = slope; ca.L = L; ca.n_pairs = c.n_dil; ca.range_events = gemm_range_counter();
+          ca.lens = rg.lens; ca.lmul = rg.lmul;
           for (int q = 0; q < c.n_dil; ++q) {
             ca.w1[q] = h->rb1[r + q].wp16c; ca.b1[q] = h->rb1[r + q].b; ca.w2[q] = h->rb2[r + q].wp16c; ca.b2[q] = h->rb2[r + q].b;
             ca.dil[q] = c.resblock_dilations[j][q];
@@ -2161,7 +2297,7 @@ static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, 
           break;
         }
         case HG_CONV:   // ResBlock2 (hifigan.py:70-91): x = conv_d(lrelu(x)) + x per dilation
-          TRY(run_conv(c1, y, dst, s.var, B, L, dil, slope, y, acc_in, out_div, 0, st));
+          TRY(run_conv(c1, y, dst, s.var, B, L, dil, slope, y, acc_in, out_div, 0, rg, st));
           break;
         case HG_PAIR_H16:
           pa.w1 = c1.wp16; pa.w2 = c2->wp16; pa.range_events = gemm_range_counter();
@@ -2179,8 +2315,8 @@ static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, 
           pa.w1 = c1.wpc; pa.w2 = c2->wpc;
           TRY(launch_pair(pa, c1.k, c1.cout, s.var, B, st));
           break;
-        case HG_CONV1: TRY(run_conv(c1, y, tmp, s.var, B, L, dil, slope, nullptr, nullptr, 1.0f, 0, st)); break;     // :56-57
-        default: TRY(run_conv(*c2, tmp, dst, s.var, B, L, 1, slope, y, acc_in, out_div, 0, st));                      // conv2 :58-60
+        case HG_CONV1: TRY(run_conv(c1, y, tmp, s.var, B, L, dil, slope, nullptr, nullptr, 1.0f, 0, rg, st)); break;     // :56-57
+        default: TRY(run_conv(*c2, tmp, dst, s.var, B, L, 1, slope, y, acc_in, out_div, 0, rg, st));                      // conv2 :58-60
       }
       if (s.form != HG_CONV1) y = dst;
     }
@@ -2189,20 +2325,60 @@ static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, 
   return BSG_OK;
 }
 
-extern "C" int bsg_hifigan_forward(bsg_hifigan* h, const float* mel, float* wav, int32_t B, int32_t T, void* stream) {
-  GuardScope guard_scope(h ? &h->guard : nullptr);
-  BSG_REQUIRE(h && !h->cfg.use_nsf, "hifigan_forward: this generator was created with the NSF source; call bsg_hifigan_forward_nsf");
-  h->path.clear();
-  return hifigan_run(h, mel, wav, B, T, stream, nullptr, 0);
+// The rows' frame counts reach the kernels through a handle-owned device array that the call itself fills: launches of set_lens_kernel carry
+// up to 256 counts each in their ARGUMENTS, so a captured forward replays the same counts and no host memory is read after the call returns.
+struct LensChunk { int n[256]; };
+__global__ void set_lens_kernel(LensChunk c, int* __restrict__ dst, int rows) {
+  if ((int)threadIdx.x < rows) dst[threadIdx.x] = c.n[threadIdx.x];
+}
+// checks lengths_host (1 .. T each) and enqueues the fill; nothing is enqueued when a length is refused
+static int hifigan_set_lens(bsg_hifigan* h, const int32_t* lengths_host, int B, int T, const char* who, hipStream_t st) {
+  BSG_REQUIRE(lengths_host, "%s: lengths_host is null", who);
+  BSG_REQUIRE(B > 0 && B <= 65535 && T > 0, "%s: bad argument (B=%d T=%d)", who, B, T);
+  for (int b = 0; b < B; ++b)
+    BSG_REQUIRE(lengths_host[b] >= 1 && lengths_host[b] <= T, "%s: lengths[%d]=%d outside 1..T=%d", who, b, lengths_host[b], T);
+  if ((size_t)B > h->lens_cap) {
+    BSG_HIP(hipStreamSynchronize(st));
+    if (h->lens) (void)hipFree(h->lens);
+    h->lens = nullptr; h->lens_cap = 0;
+    BSG_HIP(hipMalloc((void**)&h->lens, (size_t)B * sizeof(int)));
+    h->lens_cap = B;
+  }
+  for (int b0 = 0; b0 < B; b0 += 256) {
+    LensChunk c{};
+    const int rows = B - b0 < 256 ? B - b0 : 256;
+    for (int r = 0; r < rows; ++r) c.n[r] = lengths_host[b0 + r];
+    hipLaunchKernelGGL(set_lens_kernel, dim3(1), dim3(256), 0, st, c, h->lens + b0, rows);
+    BSG_LAUNCH_CHECK();
+  }
+  return BSG_OK;
 }
 
-extern "C" int bsg_hifigan_forward_nsf(bsg_hifigan* h, const float* mel, const float* f0, const float* rand_ini, const float* noise,
-                                       float* wav, int32_t B, int32_t T, void* stream) {
+static int hifigan_forward_plain(bsg_hifigan* h, const float* mel, const int32_t* lengths_host, float* wav, int32_t B, int32_t T, void* stream,
+                                 const char* who) {
   GuardScope guard_scope(h ? &h->guard : nullptr);
-  BSG_REQUIRE(h && h->cfg.use_nsf, "hifigan_forward_nsf: generator created without the NSF source");
-  BSG_REQUIRE(mel && f0 && rand_ini && noise && wav && B > 0 && T > 0, "hifigan_forward_nsf: bad argument");
+  BSG_REQUIRE(h && !h->cfg.use_nsf, "%s: this generator was created with the NSF source; call bsg_hifigan_forward_nsf[_ragged]", who);
+  h->path.clear();
+  if (lengths_host) {
+    BSG_REQUIRE(mel && wav, "%s: bad argument", who);
+    TRY(hifigan_set_lens(h, lengths_host, B, T, who, (hipStream_t)stream));
+    path_token(h, "ragged");
+  }
+  return hifigan_run(h, mel, wav, B, T, stream, nullptr, 0, lengths_host ? h->lens : nullptr);
+}
+
+static int hifigan_forward_nsf_any(bsg_hifigan* h, const float* mel, const float* f0, const float* rand_ini, const float* noise,
+                                   const int32_t* lengths_host, float* wav, int32_t B, int32_t T, void* stream, const char* who) {
+  GuardScope guard_scope(h ? &h->guard : nullptr);
+  BSG_REQUIRE(h && h->cfg.use_nsf, "%s: generator created without the NSF source", who);
+  BSG_REQUIRE(mel && f0 && rand_ini && noise && wav && B > 0 && T > 0, "%s: bad argument", who);
   h->path.clear();
   hipStream_t st = (hipStream_t)stream;
+  if (lengths_host) {
+    TRY(hifigan_set_lens(h, lengths_host, B, T, who, st));
+    path_token(h, "ragged");
+  }
+  const int* lens = lengths_host ? h->lens : nullptr;
   int hop = 1;
   for (int i = 0; i < h->cfg.n_ups; ++i) hop *= h->cfg.upsample_rates[i];
   const long long L = (long long)T * hop;
@@ -2218,9 +2394,44 @@ extern "C" int bsg_hifigan_forward_nsf(bsg_hifigan* h, const float* mel, const f
     BSG_HIP(hipMalloc((void**)&h->har, need * sizeof(float)));
     h->cap_src = need;
   }
-  TRY(nsf_launch_source(f0, rand_ini, noise, h->src_w, h->src_b, h->sw_tmp, h->har, B, T, hop, NH, (float)h->cfg.sample_rate, st));
+  TRY(nsf_launch_source(f0, rand_ini, noise, h->src_w, h->src_b, h->sw_tmp, h->har, B, T, hop, NH, (float)h->cfg.sample_rate, lens, st));
   path_token(h, "src:nsf");
-  return hifigan_run(h, mel, wav, B, T, stream, h->har, L);
+  return hifigan_run(h, mel, wav, B, T, stream, h->har, L, lens);
+}
+
+extern "C" int bsg_hifigan_forward(bsg_hifigan* h, const float* mel, float* wav, int32_t B, int32_t T, void* stream) {
+  return hifigan_forward_plain(h, mel, nullptr, wav, B, T, stream, "hifigan_forward");
+}
+
+extern "C" int bsg_hifigan_forward_nsf(bsg_hifigan* h, const float* mel, const float* f0, const float* rand_ini, const float* noise,
+                                       float* wav, int32_t B, int32_t T, void* stream) {
+  return hifigan_forward_nsf_any(h, mel, f0, rand_ini, noise, nullptr, wav, B, T, stream, "hifigan_forward_nsf");
+}
+
+// Ragged batches: row b runs at lengths_host[b] frames (1 .. T) inside the padded tensors — the same plan, grids and launches as the padded call
+// at (B, T); every launch bounds row b by lengths[b] x (the upsample rates so far) and workgroups beyond a row's end leave at once.
+extern "C" int bsg_hifigan_forward_ragged(bsg_hifigan* h, const float* mel, const int32_t* lengths_host, float* wav, int32_t B, int32_t T,
+                                          void* stream) {
+  BSG_REQUIRE(lengths_host, "hifigan_forward_ragged: lengths_host is null");
+  return hifigan_forward_plain(h, mel, lengths_host, wav, B, T, stream, "hifigan_forward_ragged");
+}
+
+extern "C" int bsg_hifigan_forward_nsf_ragged(bsg_hifigan* h, const float* mel, const float* f0, const float* rand_ini, const float* noise,
+                                              const int32_t* lengths_host, float* wav, int32_t B, int32_t T, void* stream) {
+  BSG_REQUIRE(lengths_host, "hifigan_forward_nsf_ragged: lengths_host is null");
+  return hifigan_forward_nsf_any(h, mel, f0, rand_ini, noise, lengths_host, wav, B, T, stream, "hifigan_forward_nsf_ragged");
+}
+
+// test hook: NaN bytes into every stage buffer, the NSF source buffers and the planes of the split-fp16 GEMM forms
+extern "C" int bsg_hifigan_debug_poison_workspace(bsg_hifigan* h, void* stream) {
+  BSG_REQUIRE(h, "hifigan_debug_poison_workspace: null handle");
+  hipStream_t st = (hipStream_t)stream;
+  for (float* p : h->buf)
+    if (p) BSG_HIP(hipMemsetAsync(p, 0xFF, h->cap * sizeof(float), st));
+  if (h->sw_tmp) BSG_HIP(hipMemsetAsync(h->sw_tmp, 0xFF, h->cap_src * (h->cfg.harmonic_num + 1) * sizeof(float), st));
+  if (h->har) BSG_HIP(hipMemsetAsync(h->har, 0xFF, h->cap_src * sizeof(float), st));
+  if (h->planes) BSG_HIP(hipMemsetAsync(h->planes, 0xFF, h->planes_cap * sizeof(unsigned short), st));
+  return BSG_OK;
 }
 
 // The launches of the last bsg_hifigan_forward[_nsf] of this handle, one token per launch in launch order ("none" before the first).  The

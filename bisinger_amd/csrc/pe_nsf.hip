@@ -153,6 +153,7 @@ struct SineArgs {
   float* sw;              // [B][NH][L] sine_waves * uv + noise
   int T, hop, NH;
   float sr, sine_amp, noise_std;
+  const int* lens;        // ragged (bsg_hifigan_forward_nsf_ragged): frames per row; T stays the pitch of f0 / noise / sw.  null: every row has T
 };
 
 // one workgroup per (harmonic, utterance); thread k owns samples [k*S, (k+1)*S)
@@ -165,7 +166,8 @@ struct SineArgs {
 __global__ __launch_bounds__(256) void sine_source_kernel(SineArgs a) {
   __shared__ double sh[256];
   const int hh = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const long long L = (long long)a.T * a.hop;
+  const long long Lp = (long long)a.T * a.hop;                            // row pitch of sw and noise
+  const long long L = (long long)(a.lens ? a.lens[b] : a.T) * a.hop;      // samples of this row: nothing at or beyond them is read or written
   const long long S = (L + 255) / 256;
   const long long i0 = tid * S, i1 = (i0 + S < L) ? i0 + S : L;
   const double mult = (double)(hh + 1);
@@ -190,8 +192,8 @@ __global__ __launch_bounds__(256) void sine_source_kernel(SineArgs a) {
   for (int k = 0; k < tid; ++k) p += sh[k];
   p -= floor(p);
   // level 2: phase_i = frac(C_i), one subtraction per wrap
-  float* out = a.sw + ((long long)b * a.NH + hh) * L;
-  const float* nz = a.noise + (long long)b * L * a.NH + hh;
+  float* out = a.sw + ((long long)b * a.NH + hh) * Lp;
+  const float* nz = a.noise + (long long)b * Lp * a.NH + hh;
   for (long long i = i0; i < i1;) {
     const long long t = i / a.hop;
     const long long e = (t + 1) * a.hop < i1 ? (t + 1) * a.hop : i1;
@@ -209,10 +211,10 @@ __global__ __launch_bounds__(256) void sine_source_kernel(SineArgs a) {
 
 // har[b][i] = tanh(sum_h w[h] * sw[b][h][i] + bias)                    (source.py:391)
 __global__ void sine_merge_kernel(const float* __restrict__ sw, const float* __restrict__ w, const float* __restrict__ bias,
-                                  float* __restrict__ har, long long L, int NH) {
+                                  float* __restrict__ har, long long L, int NH, const int* __restrict__ lens, int hop) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const int b = blockIdx.y;
-  if (i >= L) return;
+  if (i >= (lens ? (long long)lens[b] * hop : L)) return;   // (ragged: the row's own samples; L stays the pitch)
   float acc = 0.f;
   for (int h = 0; h < NH; ++h) acc = fmaf(sw[((long long)b * NH + h) * L + i], w[h], acc);
   har[(long long)b * L + i] = tanhf(acc + bias[0]);
@@ -221,17 +223,21 @@ __global__ void sine_merge_kernel(const float* __restrict__ sw, const float* __r
 // x[b][c][t] += LayerNorm_c(relu(Conv1d(1 -> CC, k, stride, pad)(har)))      (hifigan.py:154-160)
 template <int CC>
 __global__ void nsf_source_add_kernel(float* __restrict__ x, const float* __restrict__ har, const float* __restrict__ w,
-                                      const float* __restrict__ bias, int Lx, long long Lh, int k, int stride, int pad) {
+                                      const float* __restrict__ bias, int Lx, long long Lh, int k, int stride, int pad,
+                                      const int* __restrict__ lens, int lmul, int hop) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int b = blockIdx.y;
-  if (t >= Lx) return;
+  // ragged: positions and source samples are bounded by the row's own end (lens[b] x the rates so far / x hop); Lx and Lh stay the pitches
+  const int Lxb = lens ? lens[b] * lmul : Lx;
+  const long long Lhb = lens ? (long long)lens[b] * hop : Lh;
+  if (t >= Lxb) return;
   float v[CC];
 #pragma unroll
   for (int c = 0; c < CC; ++c) v[c] = bias[c];
   const float* hp = har + (long long)b * Lh;
   for (int j = 0; j < k; ++j) {
     const long long i = (long long)t * stride - pad + j;
-    if (i < 0 || i >= Lh) continue;
+    if (i < 0 || i >= Lhb) continue;
     const float hv = hp[i];
 #pragma unroll
     for (int c = 0; c < CC; ++c) v[c] = fmaf(w[c * k + j], hv, v[c]);
@@ -261,24 +267,24 @@ __global__ void repack_conv5_kernel(const float* __restrict__ w, float* __restri
 }  // namespace
 
 int nsf_launch_source(const float* f0, const float* rand_ini, const float* noise, const float* lin_w, const float* lin_b,
-                      float* sw_tmp, float* har, int B, int T, int hop, int NH, float sr, hipStream_t st) {
-  SineArgs a{f0, rand_ini, noise, sw_tmp, T, hop, NH, sr, 0.1f, 0.003f};
+                      float* sw_tmp, float* har, int B, int T, int hop, int NH, float sr, const int* lens, hipStream_t st) {
+  SineArgs a{f0, rand_ini, noise, sw_tmp, T, hop, NH, sr, 0.1f, 0.003f, lens};
   hipLaunchKernelGGL(sine_source_kernel, dim3(NH, B), dim3(256), 0, st, a);
   BSG_LAUNCH_CHECK();
   const long long L = (long long)T * hop;
-  hipLaunchKernelGGL(sine_merge_kernel, dim3(cdiv(L, 256), B), dim3(256), 0, st, (const float*)sw_tmp, lin_w, lin_b, har, L, NH);
+  hipLaunchKernelGGL(sine_merge_kernel, dim3(cdiv(L, 256), B), dim3(256), 0, st, (const float*)sw_tmp, lin_w, lin_b, har, L, NH, lens, hop);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
 }
 
 int nsf_launch_source_add(float* x, const float* har, const float* w, const float* bias, int B, int Cc, int Lx, long long Lh, int k,
-                          int stride, int pad, hipStream_t st) {
+                          int stride, int pad, const int* lens, int lmul, int hop, hipStream_t st) {
   const dim3 grid(cdiv(Lx, 128), B), block(128);
   switch (Cc) {
-    case 64: hipLaunchKernelGGL(nsf_source_add_kernel<64>, grid, block, 0, st, x, har, w, bias, Lx, Lh, k, stride, pad); break;
-    case 32: hipLaunchKernelGGL(nsf_source_add_kernel<32>, grid, block, 0, st, x, har, w, bias, Lx, Lh, k, stride, pad); break;
-    case 16: hipLaunchKernelGGL(nsf_source_add_kernel<16>, grid, block, 0, st, x, har, w, bias, Lx, Lh, k, stride, pad); break;
-    case 8: hipLaunchKernelGGL(nsf_source_add_kernel<8>, grid, block, 0, st, x, har, w, bias, Lx, Lh, k, stride, pad); break;
+    case 64: hipLaunchKernelGGL(nsf_source_add_kernel<64>, grid, block, 0, st, x, har, w, bias, Lx, Lh, k, stride, pad, lens, lmul, hop); break;
+    case 32: hipLaunchKernelGGL(nsf_source_add_kernel<32>, grid, block, 0, st, x, har, w, bias, Lx, Lh, k, stride, pad, lens, lmul, hop); break;
+    case 16: hipLaunchKernelGGL(nsf_source_add_kernel<16>, grid, block, 0, st, x, har, w, bias, Lx, Lh, k, stride, pad, lens, lmul, hop); break;
+    case 8: hipLaunchKernelGGL(nsf_source_add_kernel<8>, grid, block, 0, st, x, har, w, bias, Lx, Lh, k, stride, pad, lens, lmul, hop); break;
     default: set_error("nsf: %d channels not built (64/32/16/8)", Cc); return BSG_EINVAL;
   }
   BSG_LAUNCH_CHECK();
@@ -490,10 +496,10 @@ extern "C" int bsg_nsf_source(const float* f0, const float* rand_ini, const floa
   BSG_REQUIRE(f0 && rand_ini && noise && lin_w && lin_b && har && B > 0 && T > 0 && hop > 0 && NH > 0 && sample_rate > 0,
               "nsf_source: bad argument (B=%d T=%d hop=%d NH=%d sample_rate=%d)", B, T, hop, NH, sample_rate);
   hipStream_t st = (hipStream_t)stream;
-  if (sines) return nsf_launch_source(f0, rand_ini, noise, lin_w, lin_b, sines, har, B, T, hop, NH, (float)sample_rate, st);
+  if (sines) return nsf_launch_source(f0, rand_ini, noise, lin_w, lin_b, sines, har, B, T, hop, NH, (float)sample_rate, nullptr, st);
   float* tmp = nullptr;
   BSG_HIP(hipMalloc((void**)&tmp, (size_t)B * T * hop * NH * sizeof(float)));
-  int rc = nsf_launch_source(f0, rand_ini, noise, lin_w, lin_b, tmp, har, B, T, hop, NH, (float)sample_rate, st);
+  int rc = nsf_launch_source(f0, rand_ini, noise, lin_w, lin_b, tmp, har, B, T, hop, NH, (float)sample_rate, nullptr, st);
   if (rc == BSG_OK && hipStreamSynchronize(st) != hipSuccess) rc = BSG_EHIP;
   (void)hipFree(tmp);
   return rc;

@@ -6,7 +6,7 @@ registered in the checkpoint layout (``bias, weight_g, weight_v`` per conv) so t
 vocoders/hifigan.py:27-29; an already folded ``weight`` layout loads too.  Discriminators / GAN losses
 (hifigan.py:185-369) are training-only and out of scope.
 """
-from ctypes import POINTER, byref, c_void_p, cast
+from ctypes import POINTER, byref, c_int32, c_void_p, cast
 
 import numpy as np
 import torch
@@ -199,20 +199,41 @@ class HifiGanGenerator(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         a forward that the range guard repeated it names the repeat."""
         return _lib.load().bsg_hifigan_last_path(self._h).decode() if self._h is not None else 'none'
 
+    def poison_workspace(self):
+        """Test hook (bsg_hifigan_debug_poison_workspace): NaN bytes into every stage buffer, the NSF source buffers and the GEMM planes."""
+        if self._h is not None:
+            _lib.check(_lib.load().bsg_hifigan_debug_poison_workspace(self._h, _lib.stream_ptr()), 'bsg_hifigan_debug_poison_workspace')
+
     @torch.no_grad()
-    def forward(self, x, f0=None, rand_ini=None, noise=None, seed=0):
+    def forward(self, x, f0=None, rand_ini=None, noise=None, seed=0, lengths=None):
         """x [B,80,T] (, f0 [B,T]) -> [B,1,T*hop]   (hifigan.py:144-173).
         NSF draws (source.py:53, :130): supplied (``rand_ini`` [B,9], ``noise`` [B,T*hop,9]) or generated
-        (numpy RandomState(seed) for the 9 initial phases, the library's Philox stream 0x4E5346 for the noise)."""
-        # range guard of the split-fp16 ResBlock pairs (an activation beyond the fp16 range is counted by the kernels, never clipped):
-        # read once per outermost call; on an event the call is repeated on the fp32 matrix pipe (_lib.range_guarded)
-        return _lib.range_guarded(lambda: self._forward(x, f0, rand_ini, noise, seed), 'HifiGanGenerator.forward', device=self, owners=(self,))
+        (numpy RandomState(seed) for the 9 initial phases, the library's Philox stream 0x4E5346 for the noise).
 
-    def _forward(self, x, f0, rand_ini, noise, seed):
-        hd = self.handle()
+        ``lengths`` (list or tensor of B ints, 1 <= lengths[b] <= T): a ragged batch — row b is vocoded at its own length, as the reference
+        vocodes each utterance alone (vocoders/hifigan.py:55-69): ``out[b, 0, :lengths[b]*hop]`` is the generator applied to
+        ``x[b, :, :lengths[b]]`` (and ``f0[b, :lengths[b]]``) alone, the rest of the row is 0, and nothing at or beyond a row's end is read.
+        Drawn NSF noise keeps its Philox index (row, padded stride): a row sees the draws it sees in the padded call.  ``None``: the padded
+        call, every row at T frames."""
+        if lengths is not None:      # checked before anything touches the GPU: a refused call builds no handle and writes nothing
+            B, T = int(x.shape[0]), int(x.shape[-1])
+            lengths = [int(v) for v in (lengths.tolist() if hasattr(lengths, 'tolist') else lengths)]
+            if len(lengths) != B:
+                raise _lib.BsgError(f'HifiGanGenerator.forward: lengths has {len(lengths)} entries for a batch of {B} rows')
+            for b, v in enumerate(lengths):
+                if not 1 <= v <= T:
+                    raise _lib.BsgError(f'HifiGanGenerator.forward: lengths[{b}]={v} outside 1..T={T}')
+        # range guard of the split-fp16 ResBlock pairs (an activation beyond the fp16 range is counted by the kernels, never clipped):
+        # read once per outermost call; on an event the call (ragged or not) is repeated on the fp32 matrix pipe (_lib.range_guarded)
+        return _lib.range_guarded(lambda: self._forward(x, f0, rand_ini, noise, seed, lengths), 'HifiGanGenerator.forward', device=self,
+                                  owners=(self,))
+
+    def _forward(self, x, f0, rand_ini, noise, seed, lengths=None):
         x = x.contiguous().float()
         B, M, T = x.shape
         assert M == 80
+        lens = (c_int32 * B)(*lengths) if lengths is not None else None      # (checked by forward)
+        hd = self.handle()
         hop = int(np.prod(self.h['upsample_rates']))
         y = torch.empty(B, 1, T * hop, device=x.device)
         lib = _lib.load()
@@ -230,10 +251,17 @@ class HifiGanGenerator(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
                 rand_ini = rand_ini.to(x.device, torch.float32).contiguous()
                 noise = noise.to(x.device, torch.float32).contiguous()
                 assert tuple(rand_ini.shape) == (B, NH) and tuple(noise.shape) == (B, T * hop, NH) and tuple(f0.shape) == (B, T)
-                _lib.check(lib.bsg_hifigan_forward_nsf(hd, _lib.ptr(x), _lib.ptr(f0), _lib.ptr(rand_ini), _lib.ptr(noise), _lib.ptr(y),
-                                                       B, T, _lib.stream_ptr()), 'bsg_hifigan_forward_nsf')
+                if lens is not None:
+                    _lib.check(lib.bsg_hifigan_forward_nsf_ragged(hd, _lib.ptr(x), _lib.ptr(f0), _lib.ptr(rand_ini), _lib.ptr(noise), lens,
+                                                                  _lib.ptr(y), B, T, _lib.stream_ptr()), 'bsg_hifigan_forward_nsf_ragged')
+                else:
+                    _lib.check(lib.bsg_hifigan_forward_nsf(hd, _lib.ptr(x), _lib.ptr(f0), _lib.ptr(rand_ini), _lib.ptr(noise), _lib.ptr(y),
+                                                           B, T, _lib.stream_ptr()), 'bsg_hifigan_forward_nsf')
             else:
                 if f0 is not None:
                     raise _lib.BsgError('f0 given but this generator was built without use_pitch_embed')
-                _lib.check(lib.bsg_hifigan_forward(hd, _lib.ptr(x), _lib.ptr(y), B, T, _lib.stream_ptr()), 'bsg_hifigan_forward')
+                if lens is not None:
+                    _lib.check(lib.bsg_hifigan_forward_ragged(hd, _lib.ptr(x), lens, _lib.ptr(y), B, T, _lib.stream_ptr()), 'bsg_hifigan_forward_ragged')
+                else:
+                    _lib.check(lib.bsg_hifigan_forward(hd, _lib.ptr(x), _lib.ptr(y), B, T, _lib.stream_ptr()), 'bsg_hifigan_forward')
         return y

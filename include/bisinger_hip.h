@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define BSG_ABI_VERSION 17
+#define BSG_ABI_VERSION 18
 
 #define BSG_OK 0
 #define BSG_EINVAL (-22)  /* bad argument / shape the kernels do not support            */
@@ -488,8 +488,25 @@ int bsg_hifigan_forward_nsf(bsg_hifigan* h, const float* mel, const float* f0, c
  * conv2 (conv1d_kernel, /TT1 /TT2 /TT4 = samples per lane), up2 (upsample2_kernel), upk (upsample_kernel), poly (polyphase conv1d_kernel,
  * /TT*), convT (conv_transpose1d_kernel), chain (resblock_chain_h16_kernel, /NC4 /NC8), pair_h16, pair_h2, pair_mfma (/NB1 /NB2),
  * pair_valu (resblock_pair_kernel, /TT*), post4 (conv_post_kernel), nsf, add.  The string belongs to the handle: it is valid until the
- * handle's next forward or its destruction.  A forward that fails leaves the launches made up to the failure. */
+ * handle's next forward or its destruction.  A forward that fails leaves the launches made up to the failure.
+ * ABI v18: after a ragged forward the string is the token "ragged" followed by the tokens of the padded call at the same (B, T). */
 const char* bsg_hifigan_last_path(bsg_hifigan* h);
+
+/* ABI v18: ragged batches — every row at its own length inside the padded tensors.  mel [B,n_mel,T] (NSF: f0 [B,T], rand_ini, noise
+ * [B,T*hop,NH] as above), lengths_host: B frame counts on the HOST, 1 <= lengths_host[b] <= T (read before the call returns; a captured
+ * forward replays them).  With n_b = lengths_host[b]:
+ *   wav[b, 0, :n_b*hop] is the generator applied to mel[b, :, :n_b] alone (NSF: with f0[b, :n_b], rand_ini[b] and noise[b, :n_b*hop]) — what
+ *                       vocoders/hifigan.py:55-69 computes for that utterance; it depends on row b alone;
+ *   wav[b, 0, n_b*hop:] is written as 0;
+ *   nothing at or beyond a row's end is read: not the inputs, not the stage tensors of an earlier call, not the planes of the GEMM forms.
+ * The plan, the grids and the launches are those of the padded call at (B, T) (all lengths = T gives its result bit for bit); each launch
+ * bounds row b by n_b x (the upsample rates so far), and a workgroup whose first output lies beyond its row's end leaves at once.
+ * A length outside 1..T: BSG_EINVAL with a message naming the row, before anything is enqueued. */
+int bsg_hifigan_forward_ragged(bsg_hifigan* h, const float* mel, const int32_t* lengths_host, float* wav, int32_t B, int32_t T, void* stream);
+int bsg_hifigan_forward_nsf_ragged(bsg_hifigan* h, const float* mel, const float* f0, const float* rand_ini, const float* noise,
+                                   const int32_t* lengths_host, float* wav, int32_t B, int32_t T, void* stream);
+/* test hook, as bsg_pwg_ / bsg_fftden_ have: NaN bytes into every stage buffer, the NSF source buffers and the planes of the GEMM forms */
+int bsg_hifigan_debug_poison_workspace(bsg_hifigan* h, void* stream);
 
 /* ABI v9, building block exported for unit tests: the NSF harmonic source alone (source.py:352-399 as bsg_hifigan_forward_nsf runs it).
  * f0 [B,T], rand_ini [B,NH], noise [B,T*hop,NH] as there; lin_w [NH], lin_b [1] = m_source.l_linear.{weight,bias}.
