@@ -1086,7 +1086,6 @@ struct bsg_diffnet {
   unsigned short* condterm_h = nullptr;  // [L][B][2C/4][T][4] bf16 (bf16 mode only)
   unsigned short* skip_h = nullptr;      // [B][C/4][T][4] bf16
   size_t cap_bt_h = 0;
-  int prepared_compute = BSG_COMPUTE_F32;   // mode the bound condition was prepared for
   unsigned short* wcond_pack = nullptr;  // [L][2 x 2C x H] the conditioner projections as pre-split fp16 fragments (gemm_h2w.hip)
   unsigned* pack_bad = nullptr;          // device word: packed conditioner weights beyond the fp16 range (then wcond_pack is not used)
   bool cond_h2w_ok = false;
@@ -1107,28 +1106,36 @@ struct bsg_diffnet {
   float* wi_pack = nullptr;  // [C*MP]
   float* b_fin96 = nullptr;  // [96]
   int MP = 0;
-  // workspaces for the bound (B,T)
-  int B = 0, T = 0;
+  // What is bound: written by a prepare as ONE record — cleared at its start, committed at its successful end, so a prepare that fails
+  // leaves nothing bound and check_bound() refuses the next compute call.  bsg_diffnet_prepare_ragged adds `ragged` behind its prepare;
+  // ensure_cond_quads() / ensure_cond_rows() add the layout they derive.
+  struct Bound {
+    int B = 0, T = 0;                  // B = 0: nothing is bound
+    int compute = BSG_COMPUTE_F32;     // bsg_diffnet_set_compute mode the condition was bound under
+    bool tok = false;                  // the condition came per token: cond_tok / tok_dev hold the term's table and every frame's token id
+    int K = 0;                         // ... with K token columns per item
+    bool ragged = false;               // the condition came with row lengths (rg_dev)
+    bool rows = false, quads = false, quads_h = false;   // condterm / condterm_q / condterm_h hold the bound condition's term
+  } bound;
+  // workspaces for the bound (B,T); every shape-sized buffer and its capacity word is listed in ws_table()
   size_t cap_bt = 0;
   float* condterm = nullptr;  // [L][B][2C][T]
-  float* condterm_q = nullptr;   // the same in channel-quad order [L][B][2C/4][T][4]: what the 16-row stack launch loads (16 bytes per lane)
+  float* condterm_q = nullptr;   // the same in channel-quad order [L][B][2C/4][T][4]: what the 16-row stack launch and the part forms load (16 bytes per lane)
   size_t cap_cond_q = 0;         // frames it holds
-  bool cond_q_valid = false;     // written by the last prepare
   // the ROW layout (condterm) is what the fallback launches read (32-row stack launch, F(4,3), per-layer and channel-split kernels); the
-  // default launches read the quads.  Round 6: prepare writes ONE layout — the quads when the shape's default launch reads them — and the
-  // rows are derived from the quads by ensure_cond_rows() the first time a launch that reads them runs (655 MB less per pass at B = 16)
+  // default launches read the quads.  Round 6: prepare writes ONE layout (plan_bind) — the quads whenever the HANDLE can take the 16-row
+  // launch (fp32 compute, BSG_COND_QUAD / BSG_H2_Q on, not demoted), whatever launch the bound shape takes; the bf16 quads under bf16
+  // compute; the rows otherwise — and the rows are derived from the quads by ensure_cond_rows() the first time a launch that reads them
+  // runs (655 MB less per pass at B = 16)
   size_t cap_cond_rows = 0;      // frames condterm holds (allocated on demand)
-  bool cond_rows_valid = false;  // condterm holds the term of the bound condition
   // token binding (bsg_diffnet_prepare_tokens): the term per TOKEN, [L][B][2C/4][K][4], and every frame's token id.  The token form of the
   // 16-row stack launch gathers from it; every other launch reads the per-frame layouts above, which ensure_cond_quads() / ensure_cond_rows()
-  // expand from the table the first time such a launch runs (cond_q_valid / cond_rows_valid are false behind a token prepare)
-  float* cond_tok = nullptr;     // [L][B][2C/4][tok_K][4]
+  // expand from the table the first time such a launch runs (bound.quads / bound.rows are false behind a token prepare that kept the table)
+  float* cond_tok = nullptr;     // [L][B][2C/4][bound.K][4]
   size_t cap_cond_tok = 0;       // B x K it holds
-  int* tok_dev = nullptr;        // [B][T] token id of every frame, clamped to [0, tok_K)
+  int* tok_dev = nullptr;        // [B][T] token id of every frame, clamped to [0, bound.K)
   size_t cap_tok = 0;            // frames it holds
   unsigned* tok_bad = nullptr;   // device word: ids the last conversion found outside [0, K)
-  int tok_K = 0;
-  bool tok_bound = false;        // the bound condition came per token (a plain prepare clears this)
   float* cond_exp = nullptr;     // [B][H][T]: the per-frame condition of a token prepare that cannot keep the table (bf16 compute, no pre-split GEMM)
   size_t cap_cond_exp = 0;
   int occ_stack_tok = -1;        // resident workgroups per CU of the token form (-1: not queried)
@@ -1183,65 +1190,127 @@ struct bsg_diffnet {
   // two half-batches on two streams (dual_fork): the second stream and the events that fork and join it
   hipStream_t st2 = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  // ragged binding (bsg_diffnet_prepare_ragged): every row of the bound (B, T) decoded at its own frame count
-  bool ragged = false;                 // the bound condition came with row lengths (a plain prepare clears this)
+  // ragged binding (bsg_diffnet_prepare_ragged, bound.ragged): every row of the bound (B, T) decoded at its own frame count
   int occ_stack_varlen = -1;           // resident workgroups per CU of the ragged 16-row stack launch (-1: not queried)
   int occ_stack_bf16_varlen = -1;      // the same for the ragged bf16 stack launch
   int* rg_dev = nullptr;               // [B rounded up to even] row lengths, then the tile tables {row, tile} of every launch group
   size_t rg_cap = 0;                   // ints rg_dev holds
   std::vector<int> rg_group_off;       // per launch group: offset of its table (in tiles) behind the lengths ...
   std::vector<int> rg_group_tiles;     // ... and its tile count
+  std::vector<void*> owned;            // every allocation that lives as long as the handle (own_alloc): destroy frees them
 };
 
-static int dev_alloc(float** p, size_t n) {
-  BSG_HIP(hipMalloc((void**)p, n * sizeof(float)));
+// an allocation that lives as long as the handle: the packed weights and tables of create, the once-only device words
+template <class P>
+static int own_alloc(bsg_diffnet* h, P** p, size_t n) {
+  BSG_HIP(hipMalloc((void**)p, n * sizeof(P)));
+  h->owned.push_back(*p);
   return BSG_OK;
 }
-static void dev_free(float*& p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
+
+static bool is_capturing(hipStream_t st) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (st) (void)hipStreamIsCapturing(st, &cap);
+  return cap != hipStreamCaptureStatusNone;
+}
+
+// h->num_cus, asked of the device once
+static int num_cus(bsg_diffnet* h) {
+  if (h->num_cus) return BSG_OK;
+  int dev = 0;
+  BSG_HIP(hipGetDevice(&dev));
+  BSG_HIP(hipDeviceGetAttribute(&h->num_cus, hipDeviceAttributeMultiprocessorCount, dev));
+  return BSG_OK;
+}
+
+// Every shape-sized buffer of the handle: destroy and grow() walk this one table.  Buffers with the same capacity word form a group and are
+// replaced together; a buffer holds `unit` bytes per capacity unit plus `extra`.  `zero`: flag words, zeroed when allocated (flag values are
+// launch epoch x 64 + layers published, so a zeroed word is older than every launch).  `lazy`: the group is (also) grown from a compute
+// call, which a captured stream cannot do — the refusal it gets then.
+static const char* const kLazyRows = "diffnet: the row layout of the conditioner term is allocated by the first eager call of a fallback launch; run it once before capturing";
+static const char* const kLazyQuads = "diffnet: the per-frame conditioner term of a token binding is allocated by the first eager call that reads it; run it once before capturing";
+static const char* const kLazyPart = "part launch: the exchange buffers of this shape are allocated by its first eager call; run it once before capturing";
+struct WsBuf { size_t* cap; void** p; size_t unit, extra; bool zero; const char* lazy; };
+static std::vector<WsBuf> ws_table(bsg_diffnet* h) {   // (a vector: its size is the initialiser's)
+  const size_t f = sizeof(float), u = sizeof(unsigned), s = sizeof(unsigned short), M = h->M, term = (size_t)h->L * 2 * C;
+  const size_t part_tile = (size_t)2 * 32 * C * s;   // all parts of a 32-frame tile: 2 planes x 32 frames x C fp16 = 32 KB
+  return {
+      // cap_bt, frames B x T: activations, eps, and the PLMS history ring + x_pred scratch (5 x [B][M][T]: 2 % of the conditioner term) —
+      // here, so that no sampler call allocates
+      {&h->cap_bt, (void**)&h->xa, C * f, 0, false, nullptr},          {&h->cap_bt, (void**)&h->xb, C * f, 0, false, nullptr},
+      {&h->cap_bt, (void**)&h->skip, C * f, 0, false, nullptr},        {&h->cap_bt, (void**)&h->hid, C * f, 0, false, nullptr},
+      {&h->cap_bt, (void**)&h->eps, M * f, 0, false, nullptr},         {&h->cap_bt, (void**)&h->eps_hist[0], M * f, 0, false, nullptr},
+      {&h->cap_bt, (void**)&h->eps_hist[1], M * f, 0, false, nullptr}, {&h->cap_bt, (void**)&h->eps_hist[2], M * f, 0, false, nullptr},
+      {&h->cap_bt, (void**)&h->eps_hist[3], M * f, 0, false, nullptr}, {&h->cap_bt, (void**)&h->xpred, M * f, 0, false, nullptr},
+      // flags_cap, tiles of one stack launch: flags + 4 status words, edge exchange
+      {&h->flags_cap, (void**)&h->flags, u, 4 * u, true, nullptr},     {&h->flags_cap, (void**)&h->hx, (size_t)2 * 2 * C * 8 * f, 0, false, nullptr},
+      // split_cap, 32-frame tiles of the batch: channel-split scratch, 16 flags per tile + 4 status words
+      {&h->split_cap, (void**)&h->zbuf, (size_t)C * 32 * f, 0, false, nullptr}, {&h->split_cap, (void**)&h->split_flags, 16 * u, 4 * u, true, nullptr},
+      // cap_bt_h, frames (bf16 compute only)
+      {&h->cap_bt_h, (void**)&h->condterm_h, term * s, 0, false, nullptr}, {&h->cap_bt_h, (void**)&h->skip_h, C * s, 0, false, nullptr},
+      // the binding's own: token ids (frames), GEMM operand planes (B x K or B x T columns), token table (B x K), expanded condition (frames)
+      {&h->cap_tok, (void**)&h->tok_dev, sizeof(int), 0, false, nullptr},
+      {&h->cap_cond_planes, (void**)&h->cond_planes, (size_t)2 * C * s, 0, false, nullptr},
+      {&h->cap_cond_tok, (void**)&h->cond_tok, term * f, 0, false, nullptr},
+      {&h->cap_cond_exp, (void**)&h->cond_exp, C * f, 0, false, nullptr},
+      // the conditioner term per frame, as quads and as rows
+      {&h->cap_cond_q, (void**)&h->condterm_q, term * f, 0, false, kLazyQuads},
+      {&h->cap_cond_rows, (void**)&h->condterm, term * f, 0, false, kLazyRows},
+      // part_cap, 32-frame tile equivalents (slots scale with the tile width): z parts, image parts of 2 parities, [2][tiles][4] flags
+      {&h->part_cap, (void**)&h->part_zx, part_tile, 0, false, kLazyPart}, {&h->part_cap, (void**)&h->part_ix, 2 * part_tile, 0, false, kLazyPart},
+      {&h->part_cap, (void**)&h->part_flags, 2 * 4 * u, 0, true, kLazyPart},
+      // rg_cap, ints: row lengths and tile tables of a ragged binding
+      {&h->rg_cap, (void**)&h->rg_dev, sizeof(int), 0, false, nullptr},
+  };
+}
+
+// How a call site grows a group.  GROW_BOUND: in a prepare; a failure is the call's.  GROW_LAZY: where a compute call may be the one that
+// grows (the rows, the quads behind a token binding, the part buffers): refused under capture with the group's message.  GROW_SOFT: in a
+// prepare, for a layout it can do without (a group of one buffer): out of device memory leaves the group empty (capacity 0), clears the HIP
+// error and returns BSG_OK.
+enum GrowHow { GROW_BOUND, GROW_LAZY, GROW_SOFT };
+
+// The buffers of the group with capacity word `cap`, grown to `need` units.  In this order: the stream is waited for before anything is
+// freed (launches in flight may read the old buffers); the capacity is 0 while the pointers are replaced, so a failed hipMalloc leaves the
+// group empty, not dangling; the zeroing memsets go to `st`, ahead of the launches that read the flags.
+static int grow(bsg_diffnet* h, size_t* cap, size_t need, hipStream_t st, GrowHow how = GROW_BOUND) {
+  if (need <= *cap) return BSG_OK;
+  std::vector<WsBuf> group;
+  for (const WsBuf& w : ws_table(h))
+    if (w.cap == cap) group.push_back(w);
+  BSG_REQUIRE(!group.empty(), "diffnet: grow() of a capacity word that ws_table does not list");
+  if (how == GROW_LAZY && is_capturing(st)) {
+    set_error("%s", group[0].lazy);
+    return BSG_EINVAL;
+  }
+  BSG_HIP(hipStreamSynchronize(st));
+  *cap = 0;
+  for (const WsBuf& w : group) { if (*w.p) (void)hipFree(*w.p); *w.p = nullptr; }
+  for (const WsBuf& w : group) {
+    const size_t bytes = need * w.unit + w.extra;
+    const hipError_t e = hipMalloc(w.p, bytes);
+    if (e != hipSuccess && how == GROW_SOFT) {
+      (void)hipGetLastError();
+      *w.p = nullptr;
+      return BSG_OK;
+    }
+    BSG_HIP(e);
+    if (w.zero) BSG_HIP(hipMemsetAsync(*w.p, 0, bytes, st));
+  }
+  *cap = need;
+  return BSG_OK;
 }
 
 extern "C" void bsg_diffnet_destroy(bsg_diffnet* h) {
   if (!h) return;
   guard_free(&h->guard);
-  float** all[] = {&h->w_in, &h->b_in, &h->apack1, &h->apack2, &h->apackw, &h->apackw43, &h->w_cond, &h->b_cond, &h->b_out, &h->w_skip,
-                   &h->b_skip, &h->w_fin, &h->b_fin, &h->dproj, &h->dconv, &h->ws_pack, &h->wo_pack, &h->wi_pack, &h->b_fin96, &h->apack2w, &h->zbuf, &h->condterm, &h->xa, &h->xb, &h->skip, &h->hid,
-                   &h->eps, &h->eps_hist[0], &h->eps_hist[1], &h->eps_hist[2], &h->eps_hist[3], &h->xpred};
-  for (float** p : all) dev_free(*p);
+  for (void* p : h->owned) (void)hipFree(p);
+  for (const WsBuf& w : ws_table(h))
+    if (*w.p) (void)hipFree(*w.p);
   for (hipEvent_t e : h->prof_ev) (void)hipEventDestroy(e);
-  if (h->flags) (void)hipFree(h->flags);
-  if (h->epoch_dev) (void)hipFree(h->epoch_dev);
-  if (h->hx) (void)hipFree(h->hx);
-  if (h->split_flags) (void)hipFree(h->split_flags);
   if (h->st2) (void)hipStreamDestroy(h->st2);
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
   if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-  if (h->apack1h) (void)hipFree(h->apack1h);
-  if (h->condterm_h) (void)hipFree(h->condterm_h);
-  if (h->condterm_q) (void)hipFree(h->condterm_q);
-  if (h->cond_tok) (void)hipFree(h->cond_tok);
-  if (h->tok_dev) (void)hipFree(h->tok_dev);
-  if (h->tok_bad) (void)hipFree(h->tok_bad);
-  if (h->cond_exp) (void)hipFree(h->cond_exp);
-  if (h->skip_h) (void)hipFree(h->skip_h);
-  if (h->apack2h) (void)hipFree(h->apack2h);
-  if (h->tail_h) (void)hipFree(h->tail_h);
-  if (h->apack1s) (void)hipFree(h->apack1s);
-  if (h->apack2s) (void)hipFree(h->apack2s);
-  if (h->h2_scale) (void)hipFree(h->h2_scale);
-  if (h->tail_s) (void)hipFree(h->tail_s);
-  if (h->tail_scale) (void)hipFree(h->tail_scale);
-  if (h->clk) (void)hipFree(h->clk);
-  if (h->part_zx) (void)hipFree(h->part_zx);
-  if (h->part_ix) (void)hipFree(h->part_ix);
-  if (h->part_flags) (void)hipFree(h->part_flags);
-  if (h->rg_dev) (void)hipFree(h->rg_dev);
-  if (h->apack1q) (void)hipFree(h->apack1q);
-  if (h->apack2q) (void)hipFree(h->apack2q);
-  if (h->wcond_pack) (void)hipFree(h->wcond_pack);
-  if (h->pack_bad) (void)hipFree(h->pack_bad);
-  if (h->cond_planes) (void)hipFree(h->cond_planes);
   delete h;
 }
 
@@ -1274,48 +1343,55 @@ static int conv1x1(const float* W, const float* bias, const float* X, float* Y, 
   return launch_gemm(g, st);
 }
 
-static int create_impl(bsg_diffnet* h, const void* const* w, const float* step_table, hipStream_t st) {
+static int tmp_alloc(std::vector<float*>& tmp, float** p, size_t n) {
+  BSG_HIP(hipMalloc((void**)p, n * sizeof(float)));
+  tmp.push_back(*p);
+  return BSG_OK;
+}
+
+// the weights of create, packed into every form the launches read.  `tmp` receives the temporaries: create_impl frees them on every path
+static int create_pack(bsg_diffnet* h, const void* const* w, const float* step_table, hipStream_t st, std::vector<float*>& tmp) {
   const int M = h->M, L = h->L, S = h->cfg.max_steps;
-  TRY(dev_alloc(&h->w_in, (size_t)C * M));
-  TRY(dev_alloc(&h->b_in, C));
-  TRY(dev_alloc(&h->apack1, (size_t)L * 2 * C * 3 * C));
-  TRY(dev_alloc(&h->apack2, (size_t)L * 2 * C * C));
-  TRY(dev_alloc(&h->apackw, (size_t)L * 4 * 2 * C * C));
-  TRY(dev_alloc(&h->apackw43, (size_t)L * 6 * 2 * C * C));
-  TRY(dev_alloc(&h->apack2w, (size_t)L * 2 * C * C));
-  BSG_HIP(hipMalloc((void**)&h->apack1h, (size_t)L * 2 * C * 3 * C * sizeof(unsigned short)));
-  BSG_HIP(hipMalloc((void**)&h->apack2h, (size_t)L * 2 * C * C * sizeof(unsigned short)));
-  BSG_HIP(hipMalloc((void**)&h->apack1s, (size_t)L * 2 * 2 * C * 3 * C * sizeof(unsigned short)));
-  BSG_HIP(hipMalloc((void**)&h->apack2s, (size_t)L * 2 * 2 * C * C * sizeof(unsigned short)));
-  BSG_HIP(hipMalloc((void**)&h->apack1q, (size_t)L * 2 * 2 * C * 3 * C * sizeof(unsigned short)));
-  BSG_HIP(hipMalloc((void**)&h->apack2q, (size_t)L * 2 * 2 * C * C * sizeof(unsigned short)));
-  BSG_HIP(hipMalloc((void**)&h->h2_scale, (size_t)(4 * L + 2 * L) * sizeof(float)));   // table + [2L] scratch of the max reduction
-  TRY(dev_alloc(&h->w_cond, (size_t)L * 2 * C * C));
-  BSG_HIP(hipMalloc((void**)&h->wcond_pack, (size_t)L * 2 * 2 * C * C * sizeof(unsigned short)));
-  BSG_HIP(hipMalloc((void**)&h->pack_bad, sizeof(unsigned)));
+  TRY(own_alloc(h, &h->w_in, (size_t)C * M));
+  TRY(own_alloc(h, &h->b_in, C));
+  TRY(own_alloc(h, &h->apack1, (size_t)L * 2 * C * 3 * C));
+  TRY(own_alloc(h, &h->apack2, (size_t)L * 2 * C * C));
+  TRY(own_alloc(h, &h->apackw, (size_t)L * 4 * 2 * C * C));
+  TRY(own_alloc(h, &h->apackw43, (size_t)L * 6 * 2 * C * C));
+  TRY(own_alloc(h, &h->apack2w, (size_t)L * 2 * C * C));
+  TRY(own_alloc(h, &h->apack1h, (size_t)L * 2 * C * 3 * C));
+  TRY(own_alloc(h, &h->apack2h, (size_t)L * 2 * C * C));
+  TRY(own_alloc(h, &h->apack1s, (size_t)L * 2 * 2 * C * 3 * C));
+  TRY(own_alloc(h, &h->apack2s, (size_t)L * 2 * 2 * C * C));
+  TRY(own_alloc(h, &h->apack1q, (size_t)L * 2 * 2 * C * 3 * C));
+  TRY(own_alloc(h, &h->apack2q, (size_t)L * 2 * 2 * C * C));
+  TRY(own_alloc(h, &h->h2_scale, (size_t)(4 * L + 2 * L)));   // table + [2L] scratch of the max reduction
+  TRY(own_alloc(h, &h->w_cond, (size_t)L * 2 * C * C));
+  TRY(own_alloc(h, &h->wcond_pack, (size_t)L * 2 * 2 * C * C));
+  TRY(own_alloc(h, &h->pack_bad, 1));
   BSG_HIP(hipMemsetAsync(h->pack_bad, 0, sizeof(unsigned), st));
-  TRY(dev_alloc(&h->b_cond, (size_t)L * 2 * C));
-  TRY(dev_alloc(&h->b_out, (size_t)L * 2 * C));
-  TRY(dev_alloc(&h->w_skip, (size_t)C * C));
-  TRY(dev_alloc(&h->b_skip, C));
-  TRY(dev_alloc(&h->w_fin, (size_t)M * C));
-  TRY(dev_alloc(&h->b_fin, M));
-  TRY(dev_alloc(&h->dproj, (size_t)S * L * C));
-  TRY(dev_alloc(&h->dconv, (size_t)S * L * 4 * 2 * C));
+  TRY(own_alloc(h, &h->b_cond, (size_t)L * 2 * C));
+  TRY(own_alloc(h, &h->b_out, (size_t)L * 2 * C));
+  TRY(own_alloc(h, &h->w_skip, (size_t)C * C));
+  TRY(own_alloc(h, &h->b_skip, C));
+  TRY(own_alloc(h, &h->w_fin, (size_t)M * C));
+  TRY(own_alloc(h, &h->b_fin, M));
+  TRY(own_alloc(h, &h->dproj, (size_t)S * L * C));
+  TRY(own_alloc(h, &h->dconv, (size_t)S * L * 4 * 2 * C));
   TRY(copy_dev(h->w_in, w[0], (size_t)C * M, st));
   TRY(copy_dev(h->b_in, w[1], C, st));
   // step-embedding MLP over the whole table: D = W2 * mish(W1 * e + b1) + b2        (net.py:92-96,120)
   float *hid = nullptr, *dtab = nullptr;
-  TRY(dev_alloc(&hid, (size_t)S * 4 * C));
-  TRY(dev_alloc(&dtab, (size_t)S * C));
-  int rc = gemm_nt(step_table, (const float*)w[2], hid, (const float*)w[3], S, 4 * C, C, C, 4 * C, ACT_MISH, st);
-  if (rc == BSG_OK) rc = gemm_nt(hid, (const float*)w[4], dtab, (const float*)w[5], S, C, 4 * C, 4 * C, C, ACT_NONE, st);
-  if (rc == BSG_OK) {   // split-fp16 form: per-layer power-of-two scales from max |w|, then the hi / lo fragments below
+  TRY(tmp_alloc(tmp, &hid, (size_t)S * 4 * C));
+  TRY(tmp_alloc(tmp, &dtab, (size_t)S * C));
+  TRY(gemm_nt(step_table, (const float*)w[2], hid, (const float*)w[3], S, 4 * C, C, C, 4 * C, ACT_MISH, st));
+  TRY(gemm_nt(hid, (const float*)w[4], dtab, (const float*)w[5], S, C, 4 * C, 4 * C, C, ACT_NONE, st));
+  {   // split-fp16 form: per-layer power-of-two scales from max |w|, then the hi / lo fragments below
     std::vector<const float*> w1(L), w2(L);
     for (int l = 0; l < L; ++l) { w1[l] = (const float*)w[6 + 8 * l]; w2[l] = (const float*)w[6 + 8 * l + 6]; }
-    rc = h2_scales(w1.data(), w2.data(), L, reinterpret_cast<unsigned*>(h->h2_scale + 4 * L), h->h2_scale, st);
+    TRY(h2_scales(w1.data(), w2.data(), L, reinterpret_cast<unsigned*>(h->h2_scale + 4 * L), h->h2_scale, st));
   }
-  for (int l = 0; l < L && rc == BSG_OK; ++l) {
+  for (int l = 0; l < L; ++l) {
     const void* const* lw = w + 6 + 8 * l;
     // dilated conv [2C][C][3] -> fragment order with k = tap*C + ci
     {
@@ -1330,87 +1406,77 @@ static int create_impl(bsg_diffnet* h, const void* const* w, const float* step_t
       hipLaunchKernelGGL(pack_a_frag_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, (const float*)lw[6],
                          h->apack2 + (size_t)l * total, 2 * C, C, C, (long long)C, 1LL, 0LL);
     }
-    rc = pack_wino43((const float*)lw[0], h->apackw43 + (size_t)l * 6 * 2 * C * C, st);
-    if (rc == BSG_OK) rc = pack_a_frag_bf16((const float*)lw[0], h->apack1h + (size_t)l * 2 * C * 3 * C, 2 * C, 3 * C, C, (long long)3 * C, 3LL, 1LL, st);
-    if (rc == BSG_OK) rc = pack_a_frag_bf16((const float*)lw[6], h->apack2h + (size_t)l * 2 * C * C, 2 * C, C, C, (long long)C, 1LL, 0LL, st);
-    if (rc == BSG_OK) rc = pack_a_frag_h2((const float*)lw[0], h->apack1s + (size_t)l * 2 * 2 * C * 3 * C, 2 * C, 3 * C, C, (long long)3 * C, 3LL, 1LL, h->h2_scale + 4 * l, 0, st);
-    if (rc == BSG_OK) rc = pack_a_frag_h2((const float*)lw[6], h->apack2s + (size_t)l * 2 * 2 * C * C, 2 * C, C, C, (long long)C, 1LL, 0LL, h->h2_scale + 4 * l, 1, st);
-    if (rc == BSG_OK) rc = pack_a_frag_q((const float*)lw[0], h->apack1q + (size_t)l * 2 * 2 * C * 3 * C, 2 * C, 3 * C, C, (long long)3 * C, 3LL, 1LL, h->h2_scale + 4 * l, 0, st);
-    if (rc == BSG_OK) rc = pack_a_frag_q((const float*)lw[6], h->apack2q + (size_t)l * 2 * 2 * C * C, 2 * C, C, C, (long long)C, 1LL, 0LL, h->h2_scale + 4 * l, 1, st);
-    if (rc != BSG_OK) break;
+    TRY(pack_wino43((const float*)lw[0], h->apackw43 + (size_t)l * 6 * 2 * C * C, st));
+    TRY(pack_a_frag_bf16((const float*)lw[0], h->apack1h + (size_t)l * 2 * C * 3 * C, 2 * C, 3 * C, C, (long long)3 * C, 3LL, 1LL, st));
+    TRY(pack_a_frag_bf16((const float*)lw[6], h->apack2h + (size_t)l * 2 * C * C, 2 * C, C, C, (long long)C, 1LL, 0LL, st));
+    TRY(pack_a_frag_h2((const float*)lw[0], h->apack1s + (size_t)l * 2 * 2 * C * 3 * C, 2 * C, 3 * C, C, (long long)3 * C, 3LL, 1LL, h->h2_scale + 4 * l, 0, st));
+    TRY(pack_a_frag_h2((const float*)lw[6], h->apack2s + (size_t)l * 2 * 2 * C * C, 2 * C, C, C, (long long)C, 1LL, 0LL, h->h2_scale + 4 * l, 1, st));
+    TRY(pack_a_frag_q((const float*)lw[0], h->apack1q + (size_t)l * 2 * 2 * C * 3 * C, 2 * C, 3 * C, C, (long long)3 * C, 3LL, 1LL, h->h2_scale + 4 * l, 0, st));
+    TRY(pack_a_frag_q((const float*)lw[6], h->apack2q + (size_t)l * 2 * 2 * C * C, 2 * C, C, C, (long long)C, 1LL, 0LL, h->h2_scale + 4 * l, 1, st));
     hipLaunchKernelGGL(pack_a16_kernel, dim3(cdiv(2 * C * C, 256)), dim3(256), 0, st, (const float*)lw[6], h->apack2w + (size_t)l * 2 * C * C,
                        2 * C, C);
     hipLaunchKernelGGL(vec_add_kernel, dim3(cdiv(2 * C, 256)), dim3(256), 0, st, (const float*)lw[5], (const float*)lw[1],
                        h->b_cond + (size_t)l * 2 * C, 2 * C);
-    if (hipGetLastError() != hipSuccess) { set_error("diffnet_create: pack kernels failed"); rc = BSG_EHIP; break; }
-    rc = copy_dev(h->w_cond + (size_t)l * 2 * C * C, lw[4], (size_t)2 * C * C, st);
-    if (rc == BSG_OK) rc = h2w_pack_into(h->wcond_pack + (size_t)l * 2 * 2 * C * C, (const float*)lw[4], 2 * C, C, 1, 0, C, 1, h->pack_bad, st);
-    if (rc == BSG_OK) rc = copy_dev(h->b_out + (size_t)l * 2 * C, lw[7], 2 * C, st);
+    if (hipGetLastError() != hipSuccess) { set_error("diffnet_create: pack kernels failed"); return BSG_EHIP; }
+    TRY(copy_dev(h->w_cond + (size_t)l * 2 * C * C, lw[4], (size_t)2 * C * C, st));
+    TRY(h2w_pack_into(h->wcond_pack + (size_t)l * 2 * 2 * C * C, (const float*)lw[4], 2 * C, C, 1, 0, C, 1, h->pack_bad, st));
+    TRY(copy_dev(h->b_out + (size_t)l * 2 * C, lw[7], 2 * C, st));
     // diffusion_projection of the tabulated step embedding -> dproj[s][l][:]            (net.py:67)
-    if (rc == BSG_OK) rc = gemm_nt(dtab, (const float*)lw[2], h->dproj + (size_t)l * C, (const float*)lw[3], S, C, C, C, L * C, ACT_NONE, st);
-    if (rc == BSG_OK) {
-      const size_t dl = ((size_t)DCONV_SMAX * (C + 1) + DCONV_ROWS * 3 * C) * sizeof(float);
-      (void)hipFuncSetAttribute((const void*)dconv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dl);
-      hipLaunchKernelGGL(dconv_kernel, dim3(2 * C / DCONV_ROWS, cdiv(S, DCONV_SMAX)), dim3(DCONV_ROWS * DCONV_SMAX), dl, st, (const float*)lw[0], (const float*)h->dproj,
-                         h->dconv, S, L, l);
-      if (hipGetLastError() != hipSuccess) { set_error("diffnet_create: dconv kernel failed"); rc = BSG_EHIP; }
-    }
+    TRY(gemm_nt(dtab, (const float*)lw[2], h->dproj + (size_t)l * C, (const float*)lw[3], S, C, C, C, L * C, ACT_NONE, st));
+    const size_t dl = ((size_t)DCONV_SMAX * (C + 1) + DCONV_ROWS * 3 * C) * sizeof(float);
+    (void)hipFuncSetAttribute((const void*)dconv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dl);
+    hipLaunchKernelGGL(dconv_kernel, dim3(2 * C / DCONV_ROWS, cdiv(S, DCONV_SMAX)), dim3(DCONV_ROWS * DCONV_SMAX), dl, st, (const float*)lw[0], (const float*)h->dproj,
+                       h->dconv, S, L, l);
+    if (hipGetLastError() != hipSuccess) { set_error("diffnet_create: dconv kernel failed"); return BSG_EHIP; }
   }
   const void* const* tw = w + 6 + 8 * L;
-  if (rc == BSG_OK) rc = copy_dev(h->w_skip, tw[0], (size_t)C * C, st);
-  if (rc == BSG_OK) rc = copy_dev(h->b_skip, tw[1], C, st);
-  if (rc == BSG_OK) rc = copy_dev(h->w_fin, tw[2], (size_t)M * C, st);
-  if (rc == BSG_OK) rc = copy_dev(h->b_fin, tw[3], M, st);
+  TRY(copy_dev(h->w_skip, tw[0], (size_t)C * C, st));
+  TRY(copy_dev(h->b_skip, tw[1], C, st));
+  TRY(copy_dev(h->w_fin, tw[2], (size_t)M * C, st));
+  TRY(copy_dev(h->b_fin, tw[3], M, st));
+  if (M > 96) return BSG_OK;
+  const int MP = (M + 7) / 8 * 8;
+  h->MP = MP;
   float *wo_pad = nullptr, *wi_pad = nullptr, *wi_pad96 = nullptr;
-  if (rc == BSG_OK && M <= 96) {
-    const int MP = (M + 7) / 8 * 8;
-    h->MP = MP;
-    rc = dev_alloc(&h->ws_pack, (size_t)C * C);
-    if (rc == BSG_OK) rc = dev_alloc(&h->wo_pack, (size_t)96 * C);
-    if (rc == BSG_OK) rc = dev_alloc(&h->wi_pack, (size_t)C * MP);
-    if (rc == BSG_OK) rc = dev_alloc(&h->b_fin96, 96);
-    if (rc == BSG_OK) rc = dev_alloc(&wo_pad, (size_t)96 * C);
-    if (rc == BSG_OK) rc = dev_alloc(&wi_pad, (size_t)C * MP);
-    if (rc == BSG_OK) {
-      hipLaunchKernelGGL(pack_a_frag_kernel, dim3(cdiv((long long)C * C, 256)), dim3(256), 0, st, (const float*)tw[0], h->ws_pack, C, C, C, (long long)C, 1LL, 0LL);
-      hipLaunchKernelGGL(pad_rows_kernel, dim3(cdiv(96 * C, 256)), dim3(256), 0, st, (const float*)tw[2], wo_pad, M, 96, C, C);
-      hipLaunchKernelGGL(pack_a_frag_kernel, dim3(cdiv((long long)96 * C, 256)), dim3(256), 0, st, (const float*)wo_pad, h->wo_pack, 96, C, C, (long long)C, 1LL, 0LL);
-      hipLaunchKernelGGL(pad_rows_kernel, dim3(cdiv(C * MP, 256)), dim3(256), 0, st, (const float*)w[0], wi_pad, C, C, M, MP);
-      hipLaunchKernelGGL(pack_a_frag_kernel, dim3(cdiv((long long)C * MP, 256)), dim3(256), 0, st, (const float*)wi_pad, h->wi_pack, C, MP, MP, (long long)MP, 1LL, 0LL);
-      hipLaunchKernelGGL(pad_rows_kernel, dim3(1), dim3(256), 0, st, (const float*)tw[3], h->b_fin96, M, 96, 1, 1);
-      if (hipGetLastError() != hipSuccess) { set_error("diffnet_create: tail pack kernels failed"); rc = BSG_EHIP; }
-    }
-    // the same three projections as bf16 fragments (bf16-operand configuration); the input projection's K is padded to 96
-    if (rc == BSG_OK) rc = dev_alloc(&wi_pad96, (size_t)C * 96);
-    if (rc == BSG_OK && hipMalloc((void**)&h->tail_h, (size_t)(C * C + 96 * C + C * 96) * sizeof(unsigned short)) != hipSuccess) {
-      set_error("diffnet_create: out of device memory");
-      rc = BSG_EHIP;
-    }
-    if (rc == BSG_OK) {
-      hipLaunchKernelGGL(pad_rows_kernel, dim3(cdiv(C * 96, 256)), dim3(256), 0, st, (const float*)w[0], wi_pad96, C, C, M, 96);
-      rc = pack_a_frag_bf16((const float*)tw[0], h->tail_h, C, C, C, (long long)C, 1LL, 0LL, st);
-      if (rc == BSG_OK) rc = pack_a_frag_bf16(wo_pad, h->tail_h + C * C, 96, C, C, (long long)C, 1LL, 0LL, st);
-      if (rc == BSG_OK) rc = pack_a_frag_bf16(wi_pad96, h->tail_h + C * C + 96 * C, C, 96, 96, 96LL, 1LL, 0LL, st);
-    }
-    // and as split-fp16 fragments (hi / lo planes) for the tail fused into the split-fp16 stack launch
-    if (rc == BSG_OK && (hipMalloc((void**)&h->tail_s, (size_t)2 * (C * C + 96 * C + C * 96) * sizeof(unsigned short)) != hipSuccess ||
-                         hipMalloc((void**)&h->tail_scale, 9 * sizeof(float)) != hipSuccess)) {
-      set_error("diffnet_create: out of device memory");
-      rc = BSG_EHIP;
-    }
-    if (rc == BSG_OK)
-      rc = h2_tail_pack((const float*)tw[0], wo_pad, wi_pad96, h->tail_s, h->tail_s + 2 * C * C, h->tail_s + 2 * C * C + 2 * 96 * C,
-                        reinterpret_cast<unsigned*>(h->tail_scale + 6), h->tail_scale, st);
+  TRY(own_alloc(h, &h->ws_pack, (size_t)C * C));
+  TRY(own_alloc(h, &h->wo_pack, (size_t)96 * C));
+  TRY(own_alloc(h, &h->wi_pack, (size_t)C * MP));
+  TRY(own_alloc(h, &h->b_fin96, 96));
+  TRY(tmp_alloc(tmp, &wo_pad, (size_t)96 * C));
+  TRY(tmp_alloc(tmp, &wi_pad, (size_t)C * MP));
+  hipLaunchKernelGGL(pack_a_frag_kernel, dim3(cdiv((long long)C * C, 256)), dim3(256), 0, st, (const float*)tw[0], h->ws_pack, C, C, C, (long long)C, 1LL, 0LL);
+  hipLaunchKernelGGL(pad_rows_kernel, dim3(cdiv(96 * C, 256)), dim3(256), 0, st, (const float*)tw[2], wo_pad, M, 96, C, C);
+  hipLaunchKernelGGL(pack_a_frag_kernel, dim3(cdiv((long long)96 * C, 256)), dim3(256), 0, st, (const float*)wo_pad, h->wo_pack, 96, C, C, (long long)C, 1LL, 0LL);
+  hipLaunchKernelGGL(pad_rows_kernel, dim3(cdiv(C * MP, 256)), dim3(256), 0, st, (const float*)w[0], wi_pad, C, C, M, MP);
+  hipLaunchKernelGGL(pack_a_frag_kernel, dim3(cdiv((long long)C * MP, 256)), dim3(256), 0, st, (const float*)wi_pad, h->wi_pack, C, MP, MP, (long long)MP, 1LL, 0LL);
+  hipLaunchKernelGGL(pad_rows_kernel, dim3(1), dim3(256), 0, st, (const float*)tw[3], h->b_fin96, M, 96, 1, 1);
+  if (hipGetLastError() != hipSuccess) { set_error("diffnet_create: tail pack kernels failed"); return BSG_EHIP; }
+  // the same three projections as bf16 fragments (bf16-operand configuration); the input projection's K is padded to 96
+  TRY(tmp_alloc(tmp, &wi_pad96, (size_t)C * 96));
+  const size_t tail_n = (size_t)C * C + 96 * C + C * 96;
+  if (own_alloc(h, &h->tail_h, tail_n) != BSG_OK) { set_error("diffnet_create: out of device memory"); return BSG_EHIP; }
+  hipLaunchKernelGGL(pad_rows_kernel, dim3(cdiv(C * 96, 256)), dim3(256), 0, st, (const float*)w[0], wi_pad96, C, C, M, 96);
+  TRY(pack_a_frag_bf16((const float*)tw[0], h->tail_h, C, C, C, (long long)C, 1LL, 0LL, st));
+  TRY(pack_a_frag_bf16(wo_pad, h->tail_h + C * C, 96, C, C, (long long)C, 1LL, 0LL, st));
+  TRY(pack_a_frag_bf16(wi_pad96, h->tail_h + C * C + 96 * C, C, 96, 96, 96LL, 1LL, 0LL, st));
+  // and as split-fp16 fragments (hi / lo planes) for the tail fused into the split-fp16 stack launch
+  if (own_alloc(h, &h->tail_s, 2 * tail_n) != BSG_OK || own_alloc(h, &h->tail_scale, 9) != BSG_OK) {
+    set_error("diffnet_create: out of device memory");
+    return BSG_EHIP;
   }
+  return h2_tail_pack((const float*)tw[0], wo_pad, wi_pad96, h->tail_s, h->tail_s + 2 * C * C, h->tail_s + 2 * C * C + 2 * 96 * C,
+                      reinterpret_cast<unsigned*>(h->tail_scale + 6), h->tail_scale, st);
+}
+
+// create: pack, read the pre-split GEMM's range word back, and free the temporaries once the stream is idle — on every path
+static int create_impl(bsg_diffnet* h, const void* const* w, const float* step_table, hipStream_t st) {
+  std::vector<float*> tmp;
+  const int rc = create_pack(h, w, step_table, st, tmp);
   unsigned pack_bad = 1;
   if (rc == BSG_OK && hipMemcpyAsync(&pack_bad, h->pack_bad, sizeof(unsigned), hipMemcpyDeviceToHost, st) != hipSuccess) pack_bad = 1;
   hipError_t e = hipStreamSynchronize(st);
   h->cond_h2w_ok = rc == BSG_OK && e == hipSuccess && pack_bad == 0;
-  dev_free(hid);
-  dev_free(dtab);
-  dev_free(wo_pad);
-  dev_free(wi_pad);
-  dev_free(wi_pad96);
+  for (float* p : tmp) (void)hipFree(p);
   if (rc != BSG_OK) return rc;
   BSG_HIP(e);
   return BSG_OK;
@@ -1441,20 +1507,6 @@ extern "C" int bsg_diffnet_create(bsg_diffnet** out, const bsg_diffnet_cfg* cfg,
     return rc;
   }
   *out = h;
-  return BSG_OK;
-}
-
-// condterm (row layout [L][B][2C][T]) on demand: only the fallback launches read it (bsg_diffnet.cond_rows_valid)
-static int alloc_cond_rows(bsg_diffnet* h, size_t bt, hipStream_t st) {
-  if (bt <= h->cap_cond_rows) return BSG_OK;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (st) (void)hipStreamIsCapturing(st, &cap);
-  BSG_REQUIRE(cap == hipStreamCaptureStatusNone, "diffnet: the row layout of the conditioner term is allocated by the first eager call of a fallback launch; run it once before capturing");
-  BSG_HIP(hipStreamSynchronize(st));
-  dev_free(h->condterm);
-  h->cap_cond_rows = 0;
-  TRY(dev_alloc(&h->condterm, (size_t)h->L * 2 * C * bt));
-  h->cap_cond_rows = bt;
   return BSG_OK;
 }
 
@@ -1504,264 +1556,197 @@ __global__ __launch_bounds__(256) void tok_expand_cond_kernel(const float* __res
 // the quads of a token binding's term, expanded from the table the first time a launch that reads per-frame quads runs behind
 // bsg_diffnet_prepare_tokens (part forms, 32-frame tiles, BSG_COND_TOK=0) — and the source of ensure_cond_rows() below
 static int ensure_cond_quads(bsg_diffnet* h, hipStream_t st) {
-  if (h->cond_q_valid || !h->tok_bound) return BSG_OK;
-  const size_t bt = (size_t)h->B * h->T;
-  if (bt > h->cap_cond_q) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (st) (void)hipStreamIsCapturing(st, &cap);
-    BSG_REQUIRE(cap == hipStreamCaptureStatusNone, "diffnet: the per-frame conditioner term of a token binding is allocated by the first eager call that reads it; run it once before capturing");
-    BSG_HIP(hipStreamSynchronize(st));
-    if (h->condterm_q) (void)hipFree(h->condterm_q);
-    h->condterm_q = nullptr;
-    h->cap_cond_q = 0;
-    BSG_HIP(hipMalloc((void**)&h->condterm_q, (size_t)h->L * 2 * C * bt * sizeof(float)));
-    h->cap_cond_q = bt;
-  }
-  const long long zs = (long long)h->L * h->B;
+  const bsg_diffnet::Bound& b = h->bound;
+  if (b.quads || !b.tok) return BSG_OK;
+  TRY(grow(h, &h->cap_cond_q, (size_t)b.B * b.T, st, GROW_LAZY));
+  const long long zs = (long long)h->L * b.B;
   BSG_REQUIRE(zs <= 65535, "diffnet: L * B = %lld launch slices", zs);
-  hipLaunchKernelGGL(tok_to_quads_kernel, dim3(cdiv(h->T, 256), 2 * C / 4, (unsigned)zs), dim3(256), 0, st, (const float*)h->cond_tok,
-                     (const int*)h->tok_dev, h->condterm_q, 2 * C / 4, h->tok_K, h->T, h->B);
+  hipLaunchKernelGGL(tok_to_quads_kernel, dim3(cdiv(b.T, 256), 2 * C / 4, (unsigned)zs), dim3(256), 0, st, (const float*)h->cond_tok,
+                     (const int*)h->tok_dev, h->condterm_q, 2 * C / 4, b.K, b.T, b.B);
   BSG_LAUNCH_CHECK();
-  h->cond_q_valid = true;
+  h->bound.quads = true;
   return BSG_OK;
 }
 
+// the rows (condterm, [L][B][2C][T]) on demand: only the fallback launches read them
 static int ensure_cond_rows(bsg_diffnet* h, hipStream_t st) {
-  if (h->cond_rows_valid) return BSG_OK;
+  const bsg_diffnet::Bound& b = h->bound;
+  if (b.rows) return BSG_OK;
   TRY(ensure_cond_quads(h, st));
-  if (!h->cond_q_valid) {
+  if (!b.quads) {
     set_error("diffnet: the conditioner term of the bound condition exists in the bf16 layout only (bound under BSG_COMPUTE_BF16); call bsg_diffnet_prepare again");
     return BSG_ESTATE;
   }
-  const size_t bt = (size_t)h->B * h->T;
-  TRY(alloc_cond_rows(h, bt, st));
-  const long long zs = (long long)h->L * h->B;
+  TRY(grow(h, &h->cap_cond_rows, (size_t)b.B * b.T, st, GROW_LAZY));
+  const long long zs = (long long)h->L * b.B;
   BSG_REQUIRE(zs <= 65535, "diffnet: L * B = %lld launch slices", zs);
-  hipLaunchKernelGGL(quad_to_rows_kernel, dim3(cdiv(h->T, 256), 2 * C / 4, (unsigned)zs), dim3(256), 0, st, (const float*)h->condterm_q, h->condterm, 2 * C, h->T);
+  hipLaunchKernelGGL(quad_to_rows_kernel, dim3(cdiv(b.T, 256), 2 * C / 4, (unsigned)zs), dim3(256), 0, st, (const float*)h->condterm_q, h->condterm, 2 * C, b.T);
   BSG_LAUNCH_CHECK();
-  h->cond_rows_valid = true;
+  h->bound.rows = true;
   return BSG_OK;
 }
 
-// bsg_diffnet_prepare (cond: [B][H][T]) and bsg_diffnet_prepare_tokens (cond null; cond_tok [B][K][H], tok [B][T]): workspaces, flags and the
-// hoisted conditioner projection — of the B K token columns where the token table can be kept (fp32 compute, the pre-split GEMM, the quad
-// layout wanted), of the B T frames otherwise (a token call then expands its condition first)
-static int prepare_impl(bsg_diffnet* h, const float* cond, const float* cond_tok, const int64_t* tok, int32_t B, int32_t K, int32_t T,
-                        hipStream_t st) {
-  h->ragged = false;   // (bsg_diffnet_prepare_ragged sets it again behind this call)
-  h->tok_bound = false;
-  const size_t bt = (size_t)B * T;
-  if (bt > h->cap_bt) {
-    BSG_HIP(hipStreamSynchronize(st));
-    float** bufs[] = {&h->xa, &h->xb, &h->skip, &h->hid, &h->eps, &h->eps_hist[0], &h->eps_hist[1],
-                      &h->eps_hist[2], &h->eps_hist[3], &h->xpred};
-    for (float** p : bufs) dev_free(*p);
-    h->cap_bt = 0;
-    TRY(dev_alloc(&h->xa, C * bt));
-    TRY(dev_alloc(&h->xb, C * bt));
-    TRY(dev_alloc(&h->skip, C * bt));
-    TRY(dev_alloc(&h->hid, C * bt));
-    TRY(dev_alloc(&h->eps, (size_t)h->M * bt));
-    // PLMS history ring + x_pred scratch (5 x [B][M][T]: 2 % of the conditioner term) — here, so that no sampler call allocates
-    for (int i = 0; i < 4; ++i) TRY(dev_alloc(&h->eps_hist[i], (size_t)h->M * bt));
-    TRY(dev_alloc(&h->xpred, (size_t)h->M * bt));
-    h->cap_bt = bt;
-  }
-  h->B = B;
-  h->T = T;
-  {
-    if (!h->num_cus) {
-      int dev = 0;
-      BSG_HIP(hipGetDevice(&dev));
-      BSG_HIP(hipDeviceGetAttribute(&h->num_cus, hipDeviceAttributeMultiprocessorCount, dev));
-    }
-    // the stack launch handles at most 2 workgroups per CU at a time (larger batches run as groups of rows, one after the other)
-    const size_t all_tiles = (size_t)B * cdiv(T, 32);
-    const size_t need = all_tiles < 2 * (size_t)h->num_cus ? all_tiles : 2 * (size_t)h->num_cus;
-    if (need > h->flags_cap) {
-      BSG_HIP(hipStreamSynchronize(st));
-      if (h->flags) (void)hipFree(h->flags);
-      if (h->hx) (void)hipFree(h->hx);
-      h->flags = nullptr;
-      h->hx = nullptr;
-      h->flags_cap = 0;
-      BSG_HIP(hipMalloc((void**)&h->flags, (need + 4) * sizeof(unsigned)));
-      BSG_HIP(hipMemsetAsync(h->flags, 0, (need + 4) * sizeof(unsigned), st));
-      if (!h->epoch_dev) {   // epochs start at 1: a zeroed flag word is older than every launch (flag values = epoch * 64 + layers published)
-        BSG_HIP(hipMalloc((void**)&h->epoch_dev, 2 * sizeof(unsigned)));
-        const unsigned init[2] = {1u, 0u};
-        BSG_HIP(hipMemcpy(h->epoch_dev, init, sizeof(init), hipMemcpyHostToDevice));
-      }
-      BSG_HIP(hipMalloc((void**)&h->hx, 2 * need * 2 * C * 8 * sizeof(float)));
-      h->flags_cap = need;
-      if (!h->clk) {
-        BSG_HIP(hipMalloc((void**)&h->clk, 4 * sizeof(unsigned long long)));
-        BSG_HIP(hipMemsetAsync(h->clk, 0, 4 * sizeof(unsigned long long), st));
-      }
-    }
-    const size_t tiles = (size_t)B * cdiv(T, 32);
-    if (tiles > h->split_cap) {
-      BSG_HIP(hipStreamSynchronize(st));
-      dev_free(h->zbuf);
-      if (h->split_flags) (void)hipFree(h->split_flags);
-      h->split_flags = nullptr;
-      h->split_cap = 0;
-      TRY(dev_alloc(&h->zbuf, tiles * C * 32));
-      BSG_HIP(hipMalloc((void**)&h->split_flags, (16 * tiles + 4) * sizeof(unsigned)));
-      BSG_HIP(hipMemsetAsync(h->split_flags, 0, (16 * tiles + 4) * sizeof(unsigned), st));
-      h->split_cap = tiles;
-    }
-  }
-  if (h->compute == BSG_COMPUTE_BF16 && bt > h->cap_bt_h) {
-    BSG_HIP(hipStreamSynchronize(st));
-    if (h->condterm_h) (void)hipFree(h->condterm_h);
-    if (h->skip_h) (void)hipFree(h->skip_h);
-    h->condterm_h = h->skip_h = nullptr;
-    h->cap_bt_h = 0;
-    BSG_HIP(hipMalloc((void**)&h->condterm_h, (size_t)h->L * 2 * C * bt * sizeof(unsigned short)));
-    BSG_HIP(hipMalloc((void**)&h->skip_h, (size_t)C * bt * sizeof(unsigned short)));
-    h->cap_bt_h = bt;
-  }
-  h->cond_q_valid = false;
-  h->cond_rows_valid = false;
+// How a prepare binds a condition: the form of the hoisted conditioner projection, its columns, the layouts of the term it writes, and the
+// workspaces all of that needs.  plan_bind() decides, ensure_bind_ws() grows, launch_bind() launches.
+enum BindProj {
+  PROJ_H2W,      // all L projections of all B items as ONE launch of the pre-split GEMM (gemm_h2w.hip)
+  PROJ_ONE_GEMM, // B = 1: ONE conv1x1 of L x 2C rows
+  PROJ_LAYERS,   // L conv1x1 launches
+};
+struct BindPlan {
+  BindProj proj;
+  bool tokens;    // a bsg_diffnet_prepare_tokens call: the frames' token ids are converted and checked
+  bool table;     // ... that keeps the term per TOKEN (cond_tok, quads only): the projection runs over K columns per item
+  bool expand;    // ... that cannot: its condition is expanded to frames first (cond_exp) and takes the per-frame path
+  int cols;       // columns per item of the projection: K with `table`, else T
+  // the layouts written.  ONE per pass: the rows only when neither the quads nor the bf16 quads are written (BSG_COND_ROWS=1: the rows as
+  // well, round 5's way)
+  bool rows, quads;
+  bool quads_h_direct;    // bf16 compute: the GEMM's epilogue rounds the term to bf16 quads itself and writes NO fp32 copy (until round 5 the
+                          // 2.6 GB of fp32 at B = 64 went to HBM and 20 conversion launches read them back; BSG_COND_BF16_DIRECT=0: that form)
+  bool quads_h_convert;   // bf16 compute otherwise: L conversion launches from the rows
+  // capacity each workspace group needs, in its own unit (ws_table); 0: not used by this binding
+  size_t bt, flag_tiles, split_tiles, bt_h, tok, planes, cond_tok, cond_exp, quad_frames, row_frames;
+};
+
+// needs h->num_cus; otherwise pure: no HIP call, no write to the handle
+static BindPlan plan_bind(const bsg_diffnet* h, int B, int K, int T, bool tokens) {
   const DnSwitches& sw = dn_switches();
-  bool bf16_direct = false;
+  const bool bf16 = h->compute == BSG_COMPUTE_BF16;
   const bool h2w = sw.gemm_h2w && h->cond_h2w_ok && gemm_split_enabled() && h2w_supports(T, 2 * C, C, 1, C) && (long long)h->L * B <= 65535;
-  if (cond_tok) {
+  // the 16-row stack launch (diffnet_h2q.hip) loads the term as channel quads: can this HANDLE take it (BSG_H2_Q=0 / BSG_COND_QUAD=0: not)?
+  // The bound shape is not asked: its launch may read the rows, which ensure_cond_rows() then derives
+  const bool q_launch = sw.cond_quad && sw.h2_q && !bf16 && h->apack1q && !h->h2_off && !h->split_off;
+  BindPlan p{};
+  p.tokens = tokens;
+  // no table in these states (bf16 compute, the GEMMs on the fp32 matrix pipe, a handle demoted off the 16-row launch): the per-frame path
+  p.table = tokens && h2w && h2w_supports(K, 2 * C, C, 1, C) && q_launch;
+  p.expand = tokens && !p.table;
+  p.cols = p.table ? K : T;
+  p.proj = h2w ? PROJ_H2W : B == 1 ? PROJ_ONE_GEMM : PROJ_LAYERS;
+  if (!p.table) {
+    p.quads = h2w && q_launch;
+    p.quads_h_direct = h2w && bf16 && sw.cond_bf16_direct;
+    p.quads_h_convert = bf16 && !p.quads_h_direct;
+    p.rows = sw.cond_rows || !(p.quads || p.quads_h_direct);
+  }
+  const size_t bt = (size_t)B * T, tiles = (size_t)B * cdiv(T, 32);
+  p.bt = bt;
+  // the stack launch handles at most 2 workgroups per CU at a time (larger batches run as groups of rows, one after the other)
+  p.flag_tiles = std::min(tiles, 2 * (size_t)h->num_cus);
+  p.split_tiles = tiles;
+  p.bt_h = bf16 ? bt : 0;
+  p.tok = tokens ? bt : 0;
+  p.planes = h2w ? (size_t)B * p.cols : 0;
+  p.cond_tok = p.table ? (size_t)B * K : 0;
+  p.cond_exp = p.expand ? bt : 0;
+  p.quad_frames = p.quads ? bt : 0;
+  p.row_frames = p.rows ? bt : 0;
+  return p;
+}
+
+static int ensure_bind_ws(bsg_diffnet* h, BindPlan& p, hipStream_t st) {
+  TRY(grow(h, &h->cap_bt, p.bt, st));
+  TRY(grow(h, &h->flags_cap, p.flag_tiles, st));
+  // once per handle, with their initial values: the launch epoch {1, 0} — epochs start at 1: a zeroed flag word is older than every launch
+  // (flag values = epoch * 64 + layers published) — the profiling clocks, the bad-id word of the token conversion
+  if (!h->epoch_dev) {
+    TRY(own_alloc(h, &h->epoch_dev, 2));
+    const unsigned init[2] = {1u, 0u};
+    BSG_HIP(hipMemcpy(h->epoch_dev, init, sizeof(init), hipMemcpyHostToDevice));
+  }
+  if (!h->clk) {
+    TRY(own_alloc(h, &h->clk, 4));
+    BSG_HIP(hipMemsetAsync(h->clk, 0, 4 * sizeof(unsigned long long), st));
+  }
+  if (p.tokens && !h->tok_bad) TRY(own_alloc(h, &h->tok_bad, 1));
+  const struct { size_t* cap; size_t need; } groups[] = {{&h->split_cap, p.split_tiles},     {&h->cap_bt_h, p.bt_h},         {&h->cap_tok, p.tok},
+                                                          {&h->cap_cond_planes, p.planes}, {&h->cap_cond_tok, p.cond_tok}, {&h->cap_cond_exp, p.cond_exp}};
+  for (const auto& g : groups) TRY(grow(h, g.cap, g.need, st));
+  TRY(grow(h, &h->cap_cond_q, p.quad_frames, st, GROW_SOFT));
+  if (h->cap_cond_q < p.quad_frames) {
+    // THE amendment of the plan: out of memory for the quads, so this binding writes the rows and the launches read those (dword loads: a
+    // few per cent slower), nothing fails
+    p.quads = false;
+    p.quad_frames = 0;
+    p.rows = true;
+    p.row_frames = p.bt;
+  }
+  return grow(h, &h->cap_cond_rows, p.row_frames, st, GROW_LAZY);
+}
+
+// the arguments of the pre-split GEMM over `p.cols` columns per item (K token columns or T frames): batch index z = l B + b writes
+// term[l][b] = W_l cond_b + (b_cond + b_dil) in the plan's layouts — [2C][cols] rows, lanes along the columns; the same epilogue stores the
+// quads; the weights were split at create
+static H2wArgs cond_gemm_args(const bsg_diffnet* h, const BindPlan& p, int B) {
+  const int cols = p.cols;
+  H2wArgs g{};
+  g.act = h->cond_planes; g.act_plane = (long long)B * cols * C; g.lda = C; g.sAct = (long long)cols * C; g.wpack = h->wcond_pack;
+  g.sW = (long long)2 * 2 * C * C; g.zdiv = B; g.rows = cols; g.K = C; g.Wn = 2 * C; g.taps = 1; g.act_is_a = 0;
+  g.C = p.rows ? h->condterm : nullptr; g.ldc = cols; g.sC = (long long)2 * C * cols;
+  g.Cq = p.table ? h->cond_tok : p.quads ? h->condterm_q : nullptr;
+  g.Ch = p.quads_h_direct ? h->condterm_h : nullptr;
+  g.bias = h->b_cond; g.sBias = 2 * C; g.alpha = 1.f; g.act_fn = ACT_NONE; g.batch = h->L * B;
+  return g;
+}
+
+static int launch_bind(bsg_diffnet* h, const BindPlan& p, const float* cond, const float* cond_tok, const int64_t* tok, int B, int K, int T,
+                       hipStream_t st) {
+  const size_t bt = (size_t)B * T;
+  if (p.tokens) {
     // the frames' token ids, converted and clamped once (the launches index the table with them unchecked)
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (st) (void)hipStreamIsCapturing(st, &cap);
-    const bool capturing = cap != hipStreamCaptureStatusNone;
-    if (bt > h->cap_tok || !h->tok_bad) {
-      BSG_HIP(hipStreamSynchronize(st));
-      if (h->tok_dev) (void)hipFree(h->tok_dev);
-      h->tok_dev = nullptr;
-      h->cap_tok = 0;
-      BSG_HIP(hipMalloc((void**)&h->tok_dev, bt * sizeof(int)));
-      h->cap_tok = bt;
-      if (!h->tok_bad) BSG_HIP(hipMalloc((void**)&h->tok_bad, sizeof(unsigned)));
-    }
     BSG_HIP(hipMemsetAsync(h->tok_bad, 0, sizeof(unsigned), st));
     hipLaunchKernelGGL(tok_convert_kernel, dim3(cdiv((long long)bt, 256)), dim3(256), 0, st, (const long long*)tok, h->tok_dev, (long long)bt, K, h->tok_bad);
     BSG_LAUNCH_CHECK();
-    if (!capturing) {   // (a captured binding cannot wait: its ids are clamped, not reported)
+    if (!is_capturing(st)) {   // (a captured binding cannot wait: its ids are clamped, not reported)
       unsigned bad = 0;
       BSG_HIP(hipMemcpyAsync(&bad, h->tok_bad, sizeof(unsigned), hipMemcpyDeviceToHost, st));
       BSG_HIP(hipStreamSynchronize(st));
-      if (bad) h->B = h->T = 0;   // (nothing is bound: the compute calls say so)
       BSG_REQUIRE(bad == 0, "diffnet_prepare_tokens: %u token ids outside [0, K=%d)", bad, K);
     }
-    const size_t bk = (size_t)B * K;
-    const bool keep_table = h2w && h2w_supports(K, 2 * C, C, 1, C) && sw.cond_quad && sw.h2_q && h->compute == BSG_COMPUTE_F32 && h->apack1q &&
-                            !h->h2_off && !h->split_off;
-    if (keep_table) {
-      if (bk > h->cap_cond_planes) {
-        BSG_HIP(hipStreamSynchronize(st));
-        if (h->cond_planes) (void)hipFree(h->cond_planes);
-        h->cond_planes = nullptr;
-        h->cap_cond_planes = 0;
-        BSG_HIP(hipMalloc((void**)&h->cond_planes, 2 * bk * C * sizeof(unsigned short)));
-        h->cap_cond_planes = bk;
-      }
-      if (bk > h->cap_cond_tok) {
-        BSG_HIP(hipStreamSynchronize(st));
-        if (h->cond_tok) (void)hipFree(h->cond_tok);
-        h->cond_tok = nullptr;
-        h->cap_cond_tok = 0;
-        BSG_HIP(hipMalloc((void**)&h->cond_tok, (size_t)h->L * 2 * C * bk * sizeof(float)));
-        h->cap_cond_tok = bk;
-      }
-      // the token rows are [B][K][H] already: split in place of the transposing split, then the SAME launch and epilogue as the per-frame
-      // hoist below with K columns per item instead of T, quads only
-      TRY(h2w_split_rows(cond_tok, h->cond_planes, h->cond_planes + bk * C, (long long)bk, C, C, st));
-      H2wArgs g{};
-      g.Cq = h->cond_tok;
-      g.act = h->cond_planes; g.act_plane = (long long)bk * C; g.lda = C; g.sAct = (long long)K * C; g.wpack = h->wcond_pack;
-      g.sW = (long long)2 * 2 * C * C; g.zdiv = B; g.rows = K; g.K = C; g.Wn = 2 * C; g.taps = 1; g.act_is_a = 0; g.C = nullptr; g.ldc = K;
-      g.sC = (long long)2 * C * K; g.bias = h->b_cond; g.sBias = 2 * C; g.alpha = 1.f; g.act_fn = ACT_NONE; g.batch = h->L * B;
-      TRY(launch_gemm_h2w(g, st));
-      h->tok_K = K;
-      h->tok_bound = true;
-      h->prepared_compute = h->compute;
-      return BSG_OK;
-    }
-    // no table in this state (bf16 compute, the GEMMs on the fp32 matrix pipe, a handle demoted off the 16-row launch): the per-frame path
-    if (bt > h->cap_cond_exp) {
-      BSG_HIP(hipStreamSynchronize(st));
-      dev_free(h->cond_exp);
-      h->cap_cond_exp = 0;
-      TRY(dev_alloc(&h->cond_exp, C * bt));
-      h->cap_cond_exp = bt;
-    }
+  }
+  if (p.expand) {
     BSG_REQUIRE(B <= 65535, "diffnet_prepare_tokens: B=%d", B);
     hipLaunchKernelGGL(tok_expand_cond_kernel, dim3(cdiv(T, 256), C, B), dim3(256), 0, st, cond_tok, (const int*)h->tok_dev, h->cond_exp, K, T);
     BSG_LAUNCH_CHECK();
     cond = h->cond_exp;
   }
-  if (h2w) {
-    // All L projections of all B rows as ONE launch on the 16-bit matrix pipe with pre-split operands (gemm_h2w.hip): cond is transposed and
-    // split once into hi / lo fp16 planes [B][T][H]; the weights were split at create; batch index z = l B + b writes condterm[l][b] =
-    // W_l cond_b + (b_cond + b_dil) as [2C][T] rows — lanes run along T
-    if (bt > h->cap_cond_planes) {
-      BSG_HIP(hipStreamSynchronize(st));
-      if (h->cond_planes) (void)hipFree(h->cond_planes);
-      h->cond_planes = nullptr;
-      h->cap_cond_planes = 0;
-      BSG_HIP(hipMalloc((void**)&h->cond_planes, 2 * bt * C * sizeof(unsigned short)));
-      h->cap_cond_planes = bt;
-    }
-    TRY(h2w_split_transposed(cond, h->cond_planes, h->cond_planes + bt * C, B, C, T, st));
-    // the 16-row stack launch (diffnet_h2q.hip) loads the term as channel quads: the same epilogue stores it once more in that order
-    // (BSG_H2_Q=0 / BSG_COND_QUAD=0: not)
-    bool want_q = sw.cond_quad && sw.h2_q && h->compute == BSG_COMPUTE_F32 && h->apack1q && !h->h2_off && !h->split_off;
-    if (want_q && bt > h->cap_cond_q) {
-      BSG_HIP(hipStreamSynchronize(st));
-      if (h->condterm_q) (void)hipFree(h->condterm_q);
-      h->condterm_q = nullptr;
-      h->cap_cond_q = 0;
-      if (hipMalloc((void**)&h->condterm_q, (size_t)h->L * 2 * C * bt * sizeof(float)) != hipSuccess) {
-        // out of memory for the quads: the launches read the rows instead (dword loads: a few per cent slower), nothing fails
-        (void)hipGetLastError();
-        h->condterm_q = nullptr;
-        want_q = false;
-      } else {
-        h->cap_cond_q = bt;
-      }
-    }
-    h->cond_q_valid = want_q;
-    H2wArgs g{};
-    g.Cq = want_q ? h->condterm_q : nullptr;
-    // bf16-operand configuration: the epilogue rounds the term to bf16 quads itself and writes NO fp32 copy (until round 5 the 2.6 GB of fp32 at
-    // B = 64 went to HBM and 20 conversion launches read them back; BSG_COND_BF16_DIRECT=0: that form)
-    bf16_direct = sw.cond_bf16_direct && h->compute == BSG_COMPUTE_BF16 && h->condterm_h;
-    g.Ch = bf16_direct ? h->condterm_h : nullptr;
-    // ONE layout per pass: the rows only when neither the quads nor the bf16 quads are written (BSG_COND_ROWS=1: the rows as well, round 5's way)
-    const bool rows_now = sw.cond_rows || !(want_q || bf16_direct);
-    if (rows_now) TRY(alloc_cond_rows(h, bt, st));
-    h->cond_rows_valid = rows_now;
-    g.act = h->cond_planes; g.act_plane = (long long)bt * C; g.lda = C; g.sAct = (long long)T * C; g.wpack = h->wcond_pack;
-    g.sW = (long long)2 * 2 * C * C; g.zdiv = B; g.rows = T; g.K = C; g.Wn = 2 * C; g.taps = 1; g.act_is_a = 0; g.C = rows_now ? h->condterm : nullptr; g.ldc = T;
-    g.sC = (long long)2 * C * T; g.bias = h->b_cond; g.sBias = 2 * C; g.alpha = 1.f; g.act_fn = ACT_NONE; g.batch = h->L * B;
-    TRY(launch_gemm_h2w(g, st));
-  } else if (B == 1) {
-    TRY(alloc_cond_rows(h, bt, st));
-    h->cond_rows_valid = true;
+  if (p.proj == PROJ_H2W) {
+    // the activation as hi / lo fp16 planes [B][cols][H]: the condition is transposed and split once; the token rows are [B][K][H] already,
+    // so a split in place of the transposing split, then the SAME launch and epilogue with K columns per item instead of T
+    const size_t n = (size_t)B * p.cols;
+    if (p.table) TRY(h2w_split_rows(cond_tok, h->cond_planes, h->cond_planes + n * C, (long long)n, C, C, st));
+    else TRY(h2w_split_transposed(cond, h->cond_planes, h->cond_planes + n * C, B, C, T, st));
+    TRY(launch_gemm_h2w(cond_gemm_args(h, p, B), st));
+  } else if (p.proj == PROJ_ONE_GEMM) {
     // a single utterance: the L projections are ONE GEMM of L x 2C rows ([L][2C][C] weights and [L][1][2C][T] outputs are contiguous) — twenty
     // launches of 64 workgroups each left most of the chip idle (1.0 -> 0.15 ms of a 25-ms pass)
     TRY(conv1x1(h->w_cond, h->b_cond, cond, h->condterm, h->L * 2 * C, C, 1, T, ACT_NONE, st));
   }
-  if (B != 1 && !h2w) {
-    TRY(alloc_cond_rows(h, bt, st));
-    h->cond_rows_valid = true;
-  }
   for (int l = 0; l < h->L; ++l) {
-    if (B != 1 && !h2w)
+    if (p.proj == PROJ_LAYERS)
       TRY(conv1x1(h->w_cond + (size_t)l * 2 * C * C, h->b_cond + (size_t)l * 2 * C, cond,
                   h->condterm + (size_t)l * 2 * C * bt, 2 * C, C, B, T, ACT_NONE, st));
-    if (h->compute == BSG_COMPUTE_BF16 && !bf16_direct)
+    if (p.quads_h_convert)
       TRY(f32_to_quad_bf16(h->condterm + (size_t)l * 2 * C * bt, h->condterm_h + (size_t)l * 2 * C * bt, B, 2 * C, T, st));
   }
-  h->prepared_compute = h->compute;
+  return BSG_OK;
+}
+
+// bsg_diffnet_prepare (cond: [B][H][T]) and bsg_diffnet_prepare_tokens (cond null; cond_tok [B][K][H], tok [B][T]): workspaces, flags and the
+// hoisted conditioner projection.  Nothing is bound while it runs: a failure at any point (bad token ids among them) leaves it so
+static int prepare_impl(bsg_diffnet* h, const float* cond, const float* cond_tok, const int64_t* tok, int32_t B, int32_t K, int32_t T,
+                        hipStream_t st) {
+  h->bound = bsg_diffnet::Bound{};
+  TRY(num_cus(h));
+  BindPlan p = plan_bind(h, B, K, T, cond_tok != nullptr);
+  TRY(ensure_bind_ws(h, p, st));
+  TRY(launch_bind(h, p, cond, cond_tok, tok, B, K, T, st));
+  bsg_diffnet::Bound b;
+  b.B = B; b.T = T; b.compute = h->compute;
+  b.tok = p.table; b.K = p.table ? K : 0;
+  b.rows = p.rows; b.quads = p.quads; b.quads_h = p.quads_h_direct || p.quads_h_convert;
+  h->bound = b;
   return BSG_OK;
 }
 
@@ -1883,7 +1868,7 @@ static int launch_layer(bsg_diffnet* h, const StackPlan& plan, int layer, const 
                         float* skip, int B, int T, hipStream_t st, unsigned long long* stamps = nullptr) {
   ResArgs a{};
   a.x_in = x_in; a.x_out = x_out; a.skip = skip;
-  a.condterm = h->condterm + ((size_t)layer * h->B + plan.row0) * 2 * C * (size_t)T;   // [L][B bound][2C][T], this launch's rows
+  a.condterm = h->condterm + ((size_t)layer * h->bound.B + plan.row0) * 2 * C * (size_t)T;   // [L][B bound][2C][T], this launch's rows
   a.dproj = h->dproj; a.t_dev = t_dev; a.t_uniform = t_uniform;
   a.apack1 = h->apack1 + (size_t)layer * 2 * C * 3 * C;
   a.apack2 = h->apack2 + (size_t)layer * 2 * C * C;
@@ -1924,7 +1909,7 @@ static int launch_layer(bsg_diffnet* h, const StackPlan& plan, int layer, const 
   if (form == LAYER_BF16) {
     // the running skip sum lives in h->skip_h (bf16); a caller-supplied fp32 buffer (the unit-test hook) is converted
     // in and out around the launch
-    a.condterm_h = h->condterm_h + ((size_t)layer * h->B + plan.row0) * 2 * C * (size_t)T;
+    a.condterm_h = h->condterm_h + ((size_t)layer * h->bound.B + plan.row0) * 2 * C * (size_t)T;
     a.skip_h = h->skip_h + (size_t)plan.row0 * C * T;
     const bool ext = skip != h->skip + (size_t)plan.row0 * C * T;
     if (ext && !a.first) TRY(f32_to_quad_bf16(skip, h->skip_h, B, C, T, st));
@@ -1991,7 +1976,7 @@ static void stack_form(bsg_diffnet* h, StackPlan& plan, int B, int T, hipStream_
     // launch (bsg_diffnet_set_h2q / set_h2 / set_split 0, or the process switches BSG_H2 / BSG_H2_Q = 0), and it reads the conditioner
     // term's channel quads only
     if (sw.h2 && sw.h2_q && !h->h2_off && !h->q_off && !h->split_off && h->num_cus && h->hx && h->epoch_dev && h->apack1q && h->apack2q &&
-        h->dconv && h->cond_q_valid) {
+        h->dconv && h->bound.quads) {
       if (h->occ_stack_varlen < 0) h->occ_stack_varlen = stack_h2q_varlen_occupancy() >= 1 ? 1 : 0;
       if (h->occ_stack_varlen >= 1) { plan.form = STACK_H2Q; plan.rows = B; plan.ragged = true; }
     }
@@ -2002,9 +1987,7 @@ static void stack_form(bsg_diffnet* h, StackPlan& plan, int B, int T, hipStream_
     // CU, whole rows per launch group, every batch size.  BSG_H2=0 / bsg_diffnet_set_h2(h, 0): off (the kernels of the fp32 matrix pipe)
     // (round 4: the launch epoch of the flags lives in device memory, so these launches can be captured and replayed; only the part forms'
     // exchange buffers must exist already — their first eager call allocates them)
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (st) (void)hipStreamIsCapturing(st, &cap);
-    const bool capturing = cap != hipStreamCaptureStatusNone;
+    const bool capturing = is_capturing(st);
     if (sw.h2 && !h->h2_off && h->compute == BSG_COMPUTE_F32 && !h->split_off && h->num_cus && h->hx && h->apack1s && h->epoch_dev) {
       // tile width: 32 frames (one column tile per workgroup) while those tiles fit ONE launch group, else 64 frames (two column tiles:
       // half the weight stream per frame).  ms per 100-step pass at T = 1000 on one box (tools/bench_small.py), 32-frame / 64-frame /
@@ -2051,7 +2034,7 @@ static void stack_form(bsg_diffnet* h, StackPlan& plan, int B, int T, hipStream_
         plan.nct = nct;
         plan.rows = h->num_cus / tpr < B ? h->num_cus / tpr : B;
         // the token form: a token binding, the 16-row launch at 64-frame tiles (BSG_COND_TOK=0: the expanded per-frame term instead)
-        if (q && nct == 2 && h->tok_bound && sw.cond_tok) {
+        if (q && nct == 2 && h->bound.tok && sw.cond_tok) {
           if (h->occ_stack_tok < 0) h->occ_stack_tok = stack_h2q_tok_occupancy() >= 1 ? 1 : 0;
           plan.tok = h->occ_stack_tok >= 1;
         }
@@ -2098,28 +2081,6 @@ static const char* stack_path(const StackPlan& plan, bool tail) {
   }
 }
 
-// the part forms' exchange buffers, grown to `need32` 32-frame tile equivalents (slots scale with the tile width); a shape's first eager
-// call allocates them, a captured one cannot
-static int grow_part_bufs(bsg_diffnet* h, size_t need32, hipStream_t st) {
-  if (need32 <= h->part_cap) return BSG_OK;
-  hipStreamCaptureStatus capst = hipStreamCaptureStatusNone;
-  if (st) (void)hipStreamIsCapturing(st, &capst);
-  BSG_REQUIRE(capst == hipStreamCaptureStatusNone, "part launch: the exchange buffers of this shape are allocated by its first eager call; run it once before capturing");
-  BSG_HIP(hipStreamSynchronize(st));
-  if (h->part_zx) (void)hipFree(h->part_zx);
-  if (h->part_ix) (void)hipFree(h->part_ix);
-  if (h->part_flags) (void)hipFree(h->part_flags);
-  h->part_zx = nullptr; h->part_ix = nullptr; h->part_flags = nullptr; h->part_cap = 0;
-  const size_t cap = (size_t)h->num_cus > need32 ? (size_t)h->num_cus : need32;
-  const size_t tile_bytes = (size_t)2 * 32 * C * sizeof(unsigned short);   // all parts of a 32-frame tile: 2 planes x 32 frames x C fp16 = 32 KB
-  BSG_HIP(hipMalloc((void**)&h->part_zx, cap * tile_bytes));
-  BSG_HIP(hipMalloc((void**)&h->part_ix, 2 * cap * tile_bytes));
-  BSG_HIP(hipMalloc((void**)&h->part_flags, 2 * cap * 4 * sizeof(unsigned)));
-  BSG_HIP(hipMemsetAsync(h->part_flags, 0, 2 * cap * 4 * sizeof(unsigned), st));   // flag values are launch epoch x 64 + layer: monotonic
-  h->part_cap = cap;
-  return BSG_OK;
-}
-
 // The arguments of launch group g: rows [r0, r0 + nb) of this call's batch (r0 = g x plan.rows), or group g of the bound ragged plan —
 // a workgroup then finds its row and tile in the group's table, and every pointer is the bound batch's row 0 (rows are not contiguous
 // inside a group).
@@ -2139,7 +2100,7 @@ static int stack_args(bsg_diffnet* h, const StackPlan& plan, int g, const long l
   p.dproj = h->dproj; p.t_dev = t_dev ? t_dev + r0 : nullptr; p.t_uniform = t_uniform;
   p.bias_out = h->b_out;
   p.T = T; p.L = h->L; p.tiles_per_row = tpr;
-  p.ct_stride = (long long)2 * C * h->B * T;   // bound batch: per-layer stride of the conditioner term
+  p.ct_stride = (long long)2 * C * h->bound.B * T;   // bound batch: per-layer stride of the conditioner term
   p.n_tiles = plan.ragged ? h->rg_group_tiles[g] : nb * tpr; p.cycle = h->cfg.dilation_cycle_length;
   BSG_REQUIRE((size_t)p.n_tiles <= h->flags_cap && h->L < 64, "stack launch: %d tiles exceed the exchange array (%zu)", p.n_tiles, h->flags_cap);
   p.hx = h->hx; p.flags = h->flags; p.status = h->flags + h->flags_cap;
@@ -2160,7 +2121,7 @@ static int stack_args(bsg_diffnet* h, const StackPlan& plan, int g, const long l
   p.clk = h->prof_on && g == 0 ? h->clk : nullptr;
   if (plan.ragged) {
     p.vl_len = h->rg_dev;
-    p.vl_tiles = reinterpret_cast<const int2*>(h->rg_dev + ((h->B + 1) & ~1)) + h->rg_group_off[g];   // the tables follow the lengths
+    p.vl_tiles = reinterpret_cast<const int2*>(h->rg_dev + ((h->bound.B + 1) & ~1)) + h->rg_group_off[g];   // the tables follow the lengths
   }
   if (plan.form == STACK_BF16) {
     p.skip_h = h->skip_h + row * C * T;
@@ -2177,16 +2138,17 @@ static int stack_args(bsg_diffnet* h, const StackPlan& plan, int g, const long l
   }
   p.apack1s = h->apack1s; p.apack2s = h->apack2s; p.h2_scale = h->h2_scale;
   p.apack1q = h->apack1q; p.apack2q = h->apack2q;
-  p.condterm_q = plan.form != STACK_H2 && h->cond_q_valid ? h->condterm_q + row * 2 * C * T : nullptr;
+  p.condterm_q = plan.form != STACK_H2 && h->bound.quads ? h->condterm_q + row * 2 * C * T : nullptr;
   if (plan.tok) {
-    BSG_REQUIRE(h->tok_bound && h->cond_tok && h->tok_dev && plan.form == STACK_H2Q, "stack launch: no token binding");
-    p.condterm_q = h->cond_tok + row * 2 * C * h->tok_K;
-    p.ct_stride = (long long)2 * C * h->B * h->tok_K;
+    BSG_REQUIRE(h->bound.tok && h->cond_tok && h->tok_dev && plan.form == STACK_H2Q, "stack launch: no token binding");
+    p.condterm_q = h->cond_tok + row * 2 * C * h->bound.K;
+    p.ct_stride = (long long)2 * C * h->bound.B * h->bound.K;
     p.tok = h->tok_dev + row * T;
-    p.tok_K = h->tok_K;
+    p.tok_K = h->bound.K;
   }
   if (part) {
-    TRY(grow_part_bufs(h, (size_t)p.n_tiles * plan.nct, st));
+    // the exchange buffers for this launch's 32-frame tile equivalents, at least one per CU; a shape's first eager call allocates them
+    TRY(grow(h, &h->part_cap, std::max((size_t)h->num_cus, (size_t)p.n_tiles * plan.nct), st, GROW_LAZY));
     p.zx = h->part_zx; p.ix = h->part_ix; p.pflags = h->part_flags;
     p.pflag_words = (int)(2 * h->part_cap * 4);
     p.wrap_pflags = h->part_flags; p.wrap_pflag_words = p.pflag_words;   // (also under BSG_DEBUG_WRAP_R04: a part launch always zeroed its own)
@@ -2201,7 +2163,7 @@ static int launch_stack(bsg_diffnet* h, const StackPlan& plan, const long long* 
   BSG_REQUIRE(plan.form != STACK_NONE && plan.rows > 0, "stack launch: no launch form selected");
   BSG_REQUIRE(!tail || plan.form == STACK_H2 || plan.form == STACK_H2Q, "stack launch: a fused tail needs the split-fp16 form");
   BSG_REQUIRE(plan.form != STACK_PART || (!tail && plan.rows >= B), "part launch: whole batch, no fused tail");
-  BSG_REQUIRE(!plan.ragged || (h->ragged && h->rg_dev && plan.row0 == 0 && (plan.form == STACK_BF16 || h->cond_q_valid)),
+  BSG_REQUIRE(!plan.ragged || (h->bound.ragged && h->rg_dev && plan.row0 == 0 && (plan.form == STACK_BF16 || h->bound.quads)),
               "ragged stack launch: no ragged plan / conditioner quads bound");
   const int groups = plan.ragged ? (int)h->rg_group_tiles.size() : cdiv(B, plan.rows);
   for (int g = 0; g < groups; ++g) {
@@ -2234,14 +2196,14 @@ static int launch_stack(bsg_diffnet* h, const StackPlan& plan, const long long* 
 
 static int check_bound(bsg_diffnet* h, int B, int T, const char* who) {
   if (!h) { set_error("%s: null handle", who); return BSG_EINVAL; }
-  if (h->cap_bt == 0 || h->B != B || h->T != T) {
-    set_error("%s: (B=%d,T=%d) does not match the condition bound by bsg_diffnet_prepare (B=%d,T=%d)", who, B, T, h->B, h->T);
+  if (h->bound.B == 0 || h->bound.B != B || h->bound.T != T) {
+    set_error("%s: (B=%d,T=%d) does not match the condition bound by bsg_diffnet_prepare (B=%d,T=%d)", who, B, T, h->bound.B, h->bound.T);
     return BSG_ESTATE;
   }
-  if (h->compute != h->prepared_compute) {
+  if (h->compute != h->bound.compute) {
     // (either way: a BF16 prepare writes the bf16 quads only — since round 5 no fp32 copy — and an F32 prepare no bf16 quads)
     set_error("%s: the condition was bound under another bsg_diffnet_set_compute mode (%d) than the current one (%d); call bsg_diffnet_prepare again", who,
-              h->prepared_compute, h->compute);
+              h->bound.compute, h->compute);
     return BSG_ESTATE;
   }
   return BSG_OK;
@@ -2256,17 +2218,15 @@ static bool bf16_tail_on(const bsg_diffnet* h);
 // (BSG_NO_FUSED_TAIL unset), in the fp32 configuration the split-fp16 tail inside the launch, in the bf16 configuration the bf16 step tail
 // (BSG_TAIL_BF16=0: none).  (The callers otherwise decode the rows one by one.)
 static bool ragged_launch_ok(bsg_diffnet* h) {
-  if (!h->ragged || h->prepared_compute != h->compute || h->M > 96 || !fused_tail_ok(h)) return false;
+  if (!h->bound.ragged || h->bound.compute != h->compute || h->M > 96 || !fused_tail_ok(h)) return false;
   if (h->compute == BSG_COMPUTE_BF16 ? !bf16_tail_on(h) : !h->tail_s) return false;
-  return plan_stack(h, h->B, h->T, nullptr, PLAN_RAGGED).form != STACK_NONE;
+  return plan_stack(h, h->bound.B, h->bound.T, nullptr, PLAN_RAGGED).form != STACK_NONE;
 }
 
 // entry of a compute call on a ragged binding: refused under stream capture and where the handle has no ragged launch
 static int ragged_enter(bsg_diffnet* h, hipStream_t st, const char* who) {
-  if (!h->ragged) return BSG_OK;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (st) (void)hipStreamIsCapturing(st, &cap);
-  if (cap != hipStreamCaptureStatusNone) {
+  if (!h->bound.ragged) return BSG_OK;
+  if (is_capturing(st)) {
     set_error("%s: a ragged batch (bsg_diffnet_prepare_ragged) cannot be captured; run it eagerly", who);
     return BSG_ESTATE;
   }
@@ -2280,13 +2240,13 @@ static int ragged_enter(bsg_diffnet* h, hipStream_t st, const char* who) {
 // Does the launch this shape takes read the ROW layout of the conditioner term?  (The 16-row stack launch and the part forms read the quads,
 // the bf16 launches the bf16 quads; everything else — 32-row launch, F(4,3), per-layer and channel-split kernels — the rows.)
 static bool cond_rows_needed(const bsg_diffnet* h, const StackPlan& plan) {
-  if (h->compute == BSG_COMPUTE_BF16) return false;
-  return !((plan.form == STACK_H2Q || plan.form == STACK_PART) && h->cond_q_valid);
+  if (h->bound.quads_h) return false;
+  return !((plan.form == STACK_H2Q || plan.form == STACK_PART) && h->bound.quads);
 }
 // (behind a token binding: nothing for the token form, the expanded quads for the other launches that read quads, the rows for the rest)
 static int cond_layout_for(bsg_diffnet* h, const StackPlan& plan, hipStream_t st) {
   if (plan.tok) return BSG_OK;
-  if (h->tok_bound && (plan.form == STACK_H2Q || plan.form == STACK_PART)) TRY(ensure_cond_quads(h, st));
+  if (h->bound.tok && (plan.form == STACK_H2Q || plan.form == STACK_PART)) TRY(ensure_cond_quads(h, st));
   return cond_rows_needed(h, plan) ? ensure_cond_rows(h, st) : BSG_OK;
 }
 
@@ -2340,7 +2300,7 @@ extern "C" int bsg_diffnet_forward(bsg_diffnet* h, const float* x, const int64_t
   TRY(check_bound(h, B, T, "diffnet_forward"));
   BSG_REQUIRE(x && t && eps, "diffnet_forward: null argument");
   TRY(ragged_enter(h, (hipStream_t)stream, "diffnet_forward"));
-  const StackPlan plan = plan_stack(h, B, T, (hipStream_t)stream, h->ragged ? PLAN_RAGGED : PLAN_WHOLE);
+  const StackPlan plan = plan_stack(h, B, T, (hipStream_t)stream, h->bound.ragged ? PLAN_RAGGED : PLAN_WHOLE);
   TRY(cond_layout_for(h, plan, (hipStream_t)stream));
   return forward_impl(h, plan, x, (const long long*)t, 0, eps, B, T, (hipStream_t)stream);
 }
@@ -2408,7 +2368,7 @@ static int launch_tail(bsg_diffnet* h, const StackPlan& plan, TailArgs& a, float
       BSG_REQUIRE(plan.row0 == 0 && h->rg_dev, "ragged bf16 step tail: no ragged plan bound");
       int n_tiles = 0;
       for (int t : h->rg_group_tiles) n_tiles += t;
-      return launch_step_tail_bf16_ragged(a, reinterpret_cast<const int2*>(h->rg_dev + ((h->B + 1) & ~1)), h->rg_dev, n_tiles, st);
+      return launch_step_tail_bf16_ragged(a, reinterpret_cast<const int2*>(h->rg_dev + ((h->bound.B + 1) & ~1)), h->rg_dev, n_tiles, st);
     }
     return launch_step_tail_bf16(a, st);
   }
@@ -2526,7 +2486,7 @@ extern "C" int bsg_ddpm_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
   const long long n = (long long)B * h->M * T;
   BSG_REQUIRE(n % 4 == 0, "ddpm_sample: B*M*T must be a multiple of 4");
   TRY(ragged_enter(h, st, "ddpm_sample"));
-  const StackPlan plan = plan_stack(h, B, T, st, h->ragged ? PLAN_RAGGED : PLAN_WHOLE);
+  const StackPlan plan = plan_stack(h, B, T, st, h->bound.ragged ? PLAN_RAGGED : PLAN_WHOLE);
   TRY(cond_layout_for(h, plan, st));
   const long long n4 = n / 4;
   const unsigned long long quad0 = (unsigned long long)row0 * h->M * T / 4;
@@ -2629,12 +2589,8 @@ extern "C" int bsg_diffnet_handoff_take(bsg_diffnet* h, int32_t* handoff_timeout
 
 extern "C" int bsg_diffnet_uses_handoffs(bsg_diffnet* h, int32_t B, int32_t T, int32_t* uses) {
   BSG_REQUIRE(h && uses && B > 0 && T > 0, "diffnet_uses_handoffs: bad argument");
-  if (!h->num_cus) {   // normally set by prepare(); asked before any condition was bound
-    int dev = 0;
-    BSG_HIP(hipGetDevice(&dev));
-    BSG_HIP(hipDeviceGetAttribute(&h->num_cus, hipDeviceAttributeMultiprocessorCount, dev));
-  }
-  if (h->ragged && h->B == B && h->T == T && ragged_launch_ok(h)) {   // the bound ragged batch: its stack launch hands edges between tiles
+  TRY(num_cus(h));   // normally set by prepare(); asked before any condition was bound
+  if (h->bound.ragged && h->bound.B == B && h->bound.T == T && ragged_launch_ok(h)) {   // the bound ragged batch: its stack launch hands edges between tiles
     *uses = 1;
     return BSG_OK;
   }
@@ -2733,7 +2689,7 @@ extern "C" int bsg_diffnet_debug_cond_quads(bsg_diffnet* h, float* out, int32_t 
   TRY(check_bound(h, B, T, "diffnet_debug_cond_quads"));
   BSG_REQUIRE(out, "diffnet_debug_cond_quads: null argument");
   TRY(ensure_cond_quads(h, (hipStream_t)stream));
-  if (!h->cond_q_valid) {
+  if (!h->bound.quads) {
     set_error("diffnet_debug_cond_quads: the bound condition's term was not written in channel-quad order");
     return BSG_ESTATE;
   }
@@ -2846,7 +2802,7 @@ extern "C" int bsg_plms_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
   const size_t n = (size_t)B * h->M * T;
   BSG_REQUIRE(h->xpred, "plms_sample: history buffers missing (bsg_diffnet_prepare allocates them)");
   TRY(ragged_enter(h, st, "plms_sample"));
-  const StackPlan plan = plan_stack(h, B, T, st, h->ragged ? PLAN_RAGGED : PLAN_WHOLE);
+  const StackPlan plan = plan_stack(h, B, T, st, h->bound.ragged ? PLAN_RAGGED : PLAN_WHOLE);
   TRY(cond_layout_for(h, plan, st));
   const dim3 grid(cdiv((long long)n, 256)), block(256);
   // the unfused update (first iteration); ragged: on each row's own frames only
@@ -2964,18 +2920,12 @@ extern "C" int bsg_diffnet_prepare_ragged(bsg_diffnet* h, const float* cond, con
   BSG_REQUIRE(h && cond && lens, "diffnet_prepare_ragged: null argument");
   BSG_REQUIRE(B > 0 && T > 0, "diffnet_prepare_ragged: B=%d T=%d", B, T);
   hipStream_t st = (hipStream_t)stream;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (st) (void)hipStreamIsCapturing(st, &cap);
-  if (cap != hipStreamCaptureStatusNone) {
+  if (is_capturing(st)) {
     set_error("diffnet_prepare_ragged: a ragged batch cannot be bound or decoded under stream capture");
     return BSG_ESTATE;
   }
   for (int b = 0; b < B; ++b) BSG_REQUIRE(lens[b] >= 1 && lens[b] <= T, "diffnet_prepare_ragged: row %d has %d frames (1..T=%d)", b, lens[b], T);
-  if (!h->num_cus) {
-    int dev = 0;
-    BSG_HIP(hipGetDevice(&dev));
-    BSG_HIP(hipDeviceGetAttribute(&h->num_cus, hipDeviceAttributeMultiprocessorCount, dev));
-  }
+  TRY(num_cus(h));
   std::vector<int32_t> grp(B);
   int32_t ng = 0;
   TRY(bsg_ragged_plan(lens, B, 64, h->num_cus, grp.data(), &ng));
@@ -2996,21 +2946,15 @@ extern "C" int bsg_diffnet_prepare_ragged(bsg_diffnet* h, const float* cond, con
     h->rg_group_tiles[g] = off - h->rg_group_off[g];
   }
   BSG_HIP(hipStreamSynchronize(st));   // (the previous binding's tables may still be read by launches in flight)
-  if (host.size() > h->rg_cap) {
-    if (h->rg_dev) (void)hipFree(h->rg_dev);
-    h->rg_dev = nullptr;
-    h->rg_cap = 0;
-    BSG_HIP(hipMalloc((void**)&h->rg_dev, host.size() * sizeof(int)));
-    h->rg_cap = host.size();
-  }
+  TRY(grow(h, &h->rg_cap, host.size(), st));
   BSG_HIP(hipMemcpy(h->rg_dev, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice));
-  h->ragged = true;
+  h->bound.ragged = true;
   return BSG_OK;
 }
 
 extern "C" int bsg_diffnet_ragged_native(bsg_diffnet* h, int32_t B, int32_t T, int32_t* native) {
   BSG_REQUIRE(h && native, "diffnet_ragged_native: null argument");
-  *native = h->ragged && h->B == B && h->T == T && ragged_launch_ok(h) ? 1 : 0;
+  *native = h->bound.ragged && h->bound.B == B && h->bound.T == T && ragged_launch_ok(h) ? 1 : 0;
   return BSG_OK;
 }
 
