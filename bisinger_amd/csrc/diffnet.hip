@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "bsg_common.h"
+#include "bsg_ws.h"
 #include "diffnet_res.h"
 #include "diffnet_tail.h"
 
@@ -1197,22 +1198,8 @@ struct bsg_diffnet {
   size_t rg_cap = 0;                   // ints rg_dev holds
   std::vector<int> rg_group_off;       // per launch group: offset of its table (in tiles) behind the lengths ...
   std::vector<int> rg_group_tiles;     // ... and its tile count
-  std::vector<void*> owned;            // every allocation that lives as long as the handle (own_alloc): destroy frees them
+  DevOwned owned;                      // every allocation that lives as long as the handle (own_alloc): destroy frees them
 };
-
-// an allocation that lives as long as the handle: the packed weights and tables of create, the once-only device words
-template <class P>
-static int own_alloc(bsg_diffnet* h, P** p, size_t n) {
-  BSG_HIP(hipMalloc((void**)p, n * sizeof(P)));
-  h->owned.push_back(*p);
-  return BSG_OK;
-}
-
-static bool is_capturing(hipStream_t st) {
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (st) (void)hipStreamIsCapturing(st, &cap);
-  return cap != hipStreamCaptureStatusNone;
-}
 
 // h->num_cus, asked of the device once
 static int num_cus(bsg_diffnet* h) {
@@ -1223,90 +1210,55 @@ static int num_cus(bsg_diffnet* h) {
   return BSG_OK;
 }
 
-// Every shape-sized buffer of the handle: destroy and grow() walk this one table.  Buffers with the same capacity word form a group and are
-// replaced together; a buffer holds `unit` bytes per capacity unit plus `extra`.  `zero`: flag words, zeroed when allocated (flag values are
-// launch epoch x 64 + layers published, so a zeroed word is older than every launch).  `lazy`: the group is (also) grown from a compute
-// call, which a captured stream cannot do — the refusal it gets then.
+// Every shape-sized buffer of the handle (bsg_ws.h): destroy and grow() walk this one table.  WS_ZERO: flag words (flag values are launch
+// epoch x 64 + layers published, so a zeroed word is older than every launch).  `lazy`: the refusal a compute call that would have to grow
+// the group gets on a captured stream.
 static const char* const kLazyRows = "diffnet: the row layout of the conditioner term is allocated by the first eager call of a fallback launch; run it once before capturing";
 static const char* const kLazyQuads = "diffnet: the per-frame conditioner term of a token binding is allocated by the first eager call that reads it; run it once before capturing";
 static const char* const kLazyPart = "part launch: the exchange buffers of this shape are allocated by its first eager call; run it once before capturing";
-struct WsBuf { size_t* cap; void** p; size_t unit, extra; bool zero; const char* lazy; };
 static std::vector<WsBuf> ws_table(bsg_diffnet* h) {   // (a vector: its size is the initialiser's)
   const size_t f = sizeof(float), u = sizeof(unsigned), s = sizeof(unsigned short), M = h->M, term = (size_t)h->L * 2 * C;
   const size_t part_tile = (size_t)2 * 32 * C * s;   // all parts of a 32-frame tile: 2 planes x 32 frames x C fp16 = 32 KB
   return {
       // cap_bt, frames B x T: activations, eps, and the PLMS history ring + x_pred scratch (5 x [B][M][T]: 2 % of the conditioner term) —
       // here, so that no sampler call allocates
-      {&h->cap_bt, (void**)&h->xa, C * f, 0, false, nullptr},          {&h->cap_bt, (void**)&h->xb, C * f, 0, false, nullptr},
-      {&h->cap_bt, (void**)&h->skip, C * f, 0, false, nullptr},        {&h->cap_bt, (void**)&h->hid, C * f, 0, false, nullptr},
-      {&h->cap_bt, (void**)&h->eps, M * f, 0, false, nullptr},         {&h->cap_bt, (void**)&h->eps_hist[0], M * f, 0, false, nullptr},
-      {&h->cap_bt, (void**)&h->eps_hist[1], M * f, 0, false, nullptr}, {&h->cap_bt, (void**)&h->eps_hist[2], M * f, 0, false, nullptr},
-      {&h->cap_bt, (void**)&h->eps_hist[3], M * f, 0, false, nullptr}, {&h->cap_bt, (void**)&h->xpred, M * f, 0, false, nullptr},
+      {&h->cap_bt, (void**)&h->xa, C * f},          {&h->cap_bt, (void**)&h->xb, C * f},
+      {&h->cap_bt, (void**)&h->skip, C * f},        {&h->cap_bt, (void**)&h->hid, C * f},
+      {&h->cap_bt, (void**)&h->eps, M * f},         {&h->cap_bt, (void**)&h->eps_hist[0], M * f},
+      {&h->cap_bt, (void**)&h->eps_hist[1], M * f}, {&h->cap_bt, (void**)&h->eps_hist[2], M * f},
+      {&h->cap_bt, (void**)&h->eps_hist[3], M * f}, {&h->cap_bt, (void**)&h->xpred, M * f},
       // flags_cap, tiles of one stack launch: flags + 4 status words, edge exchange
-      {&h->flags_cap, (void**)&h->flags, u, 4 * u, true, nullptr},     {&h->flags_cap, (void**)&h->hx, (size_t)2 * 2 * C * 8 * f, 0, false, nullptr},
+      {&h->flags_cap, (void**)&h->flags, u, 4 * u, WS_ZERO},     {&h->flags_cap, (void**)&h->hx, (size_t)2 * 2 * C * 8 * f},
       // split_cap, 32-frame tiles of the batch: channel-split scratch, 16 flags per tile + 4 status words
-      {&h->split_cap, (void**)&h->zbuf, (size_t)C * 32 * f, 0, false, nullptr}, {&h->split_cap, (void**)&h->split_flags, 16 * u, 4 * u, true, nullptr},
+      {&h->split_cap, (void**)&h->zbuf, (size_t)C * 32 * f}, {&h->split_cap, (void**)&h->split_flags, 16 * u, 4 * u, WS_ZERO},
       // cap_bt_h, frames (bf16 compute only)
-      {&h->cap_bt_h, (void**)&h->condterm_h, term * s, 0, false, nullptr}, {&h->cap_bt_h, (void**)&h->skip_h, C * s, 0, false, nullptr},
+      {&h->cap_bt_h, (void**)&h->condterm_h, term * s}, {&h->cap_bt_h, (void**)&h->skip_h, C * s},
       // the binding's own: token ids (frames), GEMM operand planes (B x K or B x T columns), token table (B x K), expanded condition (frames)
-      {&h->cap_tok, (void**)&h->tok_dev, sizeof(int), 0, false, nullptr},
-      {&h->cap_cond_planes, (void**)&h->cond_planes, (size_t)2 * C * s, 0, false, nullptr},
-      {&h->cap_cond_tok, (void**)&h->cond_tok, term * f, 0, false, nullptr},
-      {&h->cap_cond_exp, (void**)&h->cond_exp, C * f, 0, false, nullptr},
+      {&h->cap_tok, (void**)&h->tok_dev, sizeof(int)},
+      {&h->cap_cond_planes, (void**)&h->cond_planes, (size_t)2 * C * s},
+      {&h->cap_cond_tok, (void**)&h->cond_tok, term * f},
+      {&h->cap_cond_exp, (void**)&h->cond_exp, C * f},
       // the conditioner term per frame, as quads and as rows
-      {&h->cap_cond_q, (void**)&h->condterm_q, term * f, 0, false, kLazyQuads},
-      {&h->cap_cond_rows, (void**)&h->condterm, term * f, 0, false, kLazyRows},
+      {&h->cap_cond_q, (void**)&h->condterm_q, term * f, 0, 0, kLazyQuads},
+      {&h->cap_cond_rows, (void**)&h->condterm, term * f, 0, 0, kLazyRows},
       // part_cap, 32-frame tile equivalents (slots scale with the tile width): z parts, image parts of 2 parities, [2][tiles][4] flags
-      {&h->part_cap, (void**)&h->part_zx, part_tile, 0, false, kLazyPart}, {&h->part_cap, (void**)&h->part_ix, 2 * part_tile, 0, false, kLazyPart},
-      {&h->part_cap, (void**)&h->part_flags, 2 * 4 * u, 0, true, kLazyPart},
+      {&h->part_cap, (void**)&h->part_zx, part_tile, 0, 0, kLazyPart}, {&h->part_cap, (void**)&h->part_ix, 2 * part_tile, 0, 0, kLazyPart},
+      {&h->part_cap, (void**)&h->part_flags, 2 * 4 * u, 0, WS_ZERO, kLazyPart},
       // rg_cap, ints: row lengths and tile tables of a ragged binding
-      {&h->rg_cap, (void**)&h->rg_dev, sizeof(int), 0, false, nullptr},
+      {&h->rg_cap, (void**)&h->rg_dev, sizeof(int)},
   };
 }
 
-// How a call site grows a group.  GROW_BOUND: in a prepare; a failure is the call's.  GROW_LAZY: where a compute call may be the one that
-// grows (the rows, the quads behind a token binding, the part buffers): refused under capture with the group's message.  GROW_SOFT: in a
-// prepare, for a layout it can do without (a group of one buffer): out of device memory leaves the group empty (capacity 0), clears the HIP
-// error and returns BSG_OK.
-enum GrowHow { GROW_BOUND, GROW_LAZY, GROW_SOFT };
-
-// The buffers of the group with capacity word `cap`, grown to `need` units.  In this order: the stream is waited for before anything is
-// freed (launches in flight may read the old buffers); the capacity is 0 while the pointers are replaced, so a failed hipMalloc leaves the
-// group empty, not dangling; the zeroing memsets go to `st`, ahead of the launches that read the flags.
+// (the capacity test comes first, so that a call that grows nothing builds no table)
 static int grow(bsg_diffnet* h, size_t* cap, size_t need, hipStream_t st, GrowHow how = GROW_BOUND) {
-  if (need <= *cap) return BSG_OK;
-  std::vector<WsBuf> group;
-  for (const WsBuf& w : ws_table(h))
-    if (w.cap == cap) group.push_back(w);
-  BSG_REQUIRE(!group.empty(), "diffnet: grow() of a capacity word that ws_table does not list");
-  if (how == GROW_LAZY && is_capturing(st)) {
-    set_error("%s", group[0].lazy);
-    return BSG_EINVAL;
-  }
-  BSG_HIP(hipStreamSynchronize(st));
-  *cap = 0;
-  for (const WsBuf& w : group) { if (*w.p) (void)hipFree(*w.p); *w.p = nullptr; }
-  for (const WsBuf& w : group) {
-    const size_t bytes = need * w.unit + w.extra;
-    const hipError_t e = hipMalloc(w.p, bytes);
-    if (e != hipSuccess && how == GROW_SOFT) {
-      (void)hipGetLastError();
-      *w.p = nullptr;
-      return BSG_OK;
-    }
-    BSG_HIP(e);
-    if (w.zero) BSG_HIP(hipMemsetAsync(*w.p, 0, bytes, st));
-  }
-  *cap = need;
-  return BSG_OK;
+  return need <= *cap ? BSG_OK : ws_grow(ws_table(h), "diffnet", cap, need, st, how);
 }
 
 extern "C" void bsg_diffnet_destroy(bsg_diffnet* h) {
   if (!h) return;
   guard_free(&h->guard);
-  for (void* p : h->owned) (void)hipFree(p);
-  for (const WsBuf& w : ws_table(h))
-    if (*w.p) (void)hipFree(*w.p);
+  h->owned.free_all();
+  ws_free(ws_table(h));
   for (hipEvent_t e : h->prof_ev) (void)hipEventDestroy(e);
   if (h->st2) (void)hipStreamDestroy(h->st2);
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -1352,32 +1304,32 @@ static int tmp_alloc(std::vector<float*>& tmp, float** p, size_t n) {
 // the weights of create, packed into every form the launches read.  `tmp` receives the temporaries: create_impl frees them on every path
 static int create_pack(bsg_diffnet* h, const void* const* w, const float* step_table, hipStream_t st, std::vector<float*>& tmp) {
   const int M = h->M, L = h->L, S = h->cfg.max_steps;
-  TRY(own_alloc(h, &h->w_in, (size_t)C * M));
-  TRY(own_alloc(h, &h->b_in, C));
-  TRY(own_alloc(h, &h->apack1, (size_t)L * 2 * C * 3 * C));
-  TRY(own_alloc(h, &h->apack2, (size_t)L * 2 * C * C));
-  TRY(own_alloc(h, &h->apackw, (size_t)L * 4 * 2 * C * C));
-  TRY(own_alloc(h, &h->apackw43, (size_t)L * 6 * 2 * C * C));
-  TRY(own_alloc(h, &h->apack2w, (size_t)L * 2 * C * C));
-  TRY(own_alloc(h, &h->apack1h, (size_t)L * 2 * C * 3 * C));
-  TRY(own_alloc(h, &h->apack2h, (size_t)L * 2 * C * C));
-  TRY(own_alloc(h, &h->apack1s, (size_t)L * 2 * 2 * C * 3 * C));
-  TRY(own_alloc(h, &h->apack2s, (size_t)L * 2 * 2 * C * C));
-  TRY(own_alloc(h, &h->apack1q, (size_t)L * 2 * 2 * C * 3 * C));
-  TRY(own_alloc(h, &h->apack2q, (size_t)L * 2 * 2 * C * C));
-  TRY(own_alloc(h, &h->h2_scale, (size_t)(4 * L + 2 * L)));   // table + [2L] scratch of the max reduction
-  TRY(own_alloc(h, &h->w_cond, (size_t)L * 2 * C * C));
-  TRY(own_alloc(h, &h->wcond_pack, (size_t)L * 2 * 2 * C * C));
-  TRY(own_alloc(h, &h->pack_bad, 1));
+  TRY(own_alloc(h->owned, &h->w_in, (size_t)C * M));
+  TRY(own_alloc(h->owned, &h->b_in, C));
+  TRY(own_alloc(h->owned, &h->apack1, (size_t)L * 2 * C * 3 * C));
+  TRY(own_alloc(h->owned, &h->apack2, (size_t)L * 2 * C * C));
+  TRY(own_alloc(h->owned, &h->apackw, (size_t)L * 4 * 2 * C * C));
+  TRY(own_alloc(h->owned, &h->apackw43, (size_t)L * 6 * 2 * C * C));
+  TRY(own_alloc(h->owned, &h->apack2w, (size_t)L * 2 * C * C));
+  TRY(own_alloc(h->owned, &h->apack1h, (size_t)L * 2 * C * 3 * C));
+  TRY(own_alloc(h->owned, &h->apack2h, (size_t)L * 2 * C * C));
+  TRY(own_alloc(h->owned, &h->apack1s, (size_t)L * 2 * 2 * C * 3 * C));
+  TRY(own_alloc(h->owned, &h->apack2s, (size_t)L * 2 * 2 * C * C));
+  TRY(own_alloc(h->owned, &h->apack1q, (size_t)L * 2 * 2 * C * 3 * C));
+  TRY(own_alloc(h->owned, &h->apack2q, (size_t)L * 2 * 2 * C * C));
+  TRY(own_alloc(h->owned, &h->h2_scale, (size_t)(4 * L + 2 * L)));   // table + [2L] scratch of the max reduction
+  TRY(own_alloc(h->owned, &h->w_cond, (size_t)L * 2 * C * C));
+  TRY(own_alloc(h->owned, &h->wcond_pack, (size_t)L * 2 * 2 * C * C));
+  TRY(own_alloc(h->owned, &h->pack_bad, 1));
   BSG_HIP(hipMemsetAsync(h->pack_bad, 0, sizeof(unsigned), st));
-  TRY(own_alloc(h, &h->b_cond, (size_t)L * 2 * C));
-  TRY(own_alloc(h, &h->b_out, (size_t)L * 2 * C));
-  TRY(own_alloc(h, &h->w_skip, (size_t)C * C));
-  TRY(own_alloc(h, &h->b_skip, C));
-  TRY(own_alloc(h, &h->w_fin, (size_t)M * C));
-  TRY(own_alloc(h, &h->b_fin, M));
-  TRY(own_alloc(h, &h->dproj, (size_t)S * L * C));
-  TRY(own_alloc(h, &h->dconv, (size_t)S * L * 4 * 2 * C));
+  TRY(own_alloc(h->owned, &h->b_cond, (size_t)L * 2 * C));
+  TRY(own_alloc(h->owned, &h->b_out, (size_t)L * 2 * C));
+  TRY(own_alloc(h->owned, &h->w_skip, (size_t)C * C));
+  TRY(own_alloc(h->owned, &h->b_skip, C));
+  TRY(own_alloc(h->owned, &h->w_fin, (size_t)M * C));
+  TRY(own_alloc(h->owned, &h->b_fin, M));
+  TRY(own_alloc(h->owned, &h->dproj, (size_t)S * L * C));
+  TRY(own_alloc(h->owned, &h->dconv, (size_t)S * L * 4 * 2 * C));
   TRY(copy_dev(h->w_in, w[0], (size_t)C * M, st));
   TRY(copy_dev(h->b_in, w[1], C, st));
   // step-embedding MLP over the whole table: D = W2 * mish(W1 * e + b1) + b2        (net.py:92-96,120)
@@ -1438,10 +1390,10 @@ static int create_pack(bsg_diffnet* h, const void* const* w, const float* step_t
   const int MP = (M + 7) / 8 * 8;
   h->MP = MP;
   float *wo_pad = nullptr, *wi_pad = nullptr, *wi_pad96 = nullptr;
-  TRY(own_alloc(h, &h->ws_pack, (size_t)C * C));
-  TRY(own_alloc(h, &h->wo_pack, (size_t)96 * C));
-  TRY(own_alloc(h, &h->wi_pack, (size_t)C * MP));
-  TRY(own_alloc(h, &h->b_fin96, 96));
+  TRY(own_alloc(h->owned, &h->ws_pack, (size_t)C * C));
+  TRY(own_alloc(h->owned, &h->wo_pack, (size_t)96 * C));
+  TRY(own_alloc(h->owned, &h->wi_pack, (size_t)C * MP));
+  TRY(own_alloc(h->owned, &h->b_fin96, 96));
   TRY(tmp_alloc(tmp, &wo_pad, (size_t)96 * C));
   TRY(tmp_alloc(tmp, &wi_pad, (size_t)C * MP));
   hipLaunchKernelGGL(pack_a_frag_kernel, dim3(cdiv((long long)C * C, 256)), dim3(256), 0, st, (const float*)tw[0], h->ws_pack, C, C, C, (long long)C, 1LL, 0LL);
@@ -1454,13 +1406,13 @@ static int create_pack(bsg_diffnet* h, const void* const* w, const float* step_t
   // the same three projections as bf16 fragments (bf16-operand configuration); the input projection's K is padded to 96
   TRY(tmp_alloc(tmp, &wi_pad96, (size_t)C * 96));
   const size_t tail_n = (size_t)C * C + 96 * C + C * 96;
-  if (own_alloc(h, &h->tail_h, tail_n) != BSG_OK) { set_error("diffnet_create: out of device memory"); return BSG_EHIP; }
+  if (own_alloc(h->owned, &h->tail_h, tail_n) != BSG_OK) { set_error("diffnet_create: out of device memory"); return BSG_EHIP; }
   hipLaunchKernelGGL(pad_rows_kernel, dim3(cdiv(C * 96, 256)), dim3(256), 0, st, (const float*)w[0], wi_pad96, C, C, M, 96);
   TRY(pack_a_frag_bf16((const float*)tw[0], h->tail_h, C, C, C, (long long)C, 1LL, 0LL, st));
   TRY(pack_a_frag_bf16(wo_pad, h->tail_h + C * C, 96, C, C, (long long)C, 1LL, 0LL, st));
   TRY(pack_a_frag_bf16(wi_pad96, h->tail_h + C * C + 96 * C, C, 96, 96, 96LL, 1LL, 0LL, st));
   // and as split-fp16 fragments (hi / lo planes) for the tail fused into the split-fp16 stack launch
-  if (own_alloc(h, &h->tail_s, 2 * tail_n) != BSG_OK || own_alloc(h, &h->tail_scale, 9) != BSG_OK) {
+  if (own_alloc(h->owned, &h->tail_s, 2 * tail_n) != BSG_OK || own_alloc(h->owned, &h->tail_scale, 9) != BSG_OK) {
     set_error("diffnet_create: out of device memory");
     return BSG_EHIP;
   }
@@ -1651,15 +1603,15 @@ static int ensure_bind_ws(bsg_diffnet* h, BindPlan& p, hipStream_t st) {
   // once per handle, with their initial values: the launch epoch {1, 0} — epochs start at 1: a zeroed flag word is older than every launch
   // (flag values = epoch * 64 + layers published) — the profiling clocks, the bad-id word of the token conversion
   if (!h->epoch_dev) {
-    TRY(own_alloc(h, &h->epoch_dev, 2));
+    TRY(own_alloc(h->owned, &h->epoch_dev, 2));
     const unsigned init[2] = {1u, 0u};
     BSG_HIP(hipMemcpy(h->epoch_dev, init, sizeof(init), hipMemcpyHostToDevice));
   }
   if (!h->clk) {
-    TRY(own_alloc(h, &h->clk, 4));
+    TRY(own_alloc(h->owned, &h->clk, 4));
     BSG_HIP(hipMemsetAsync(h->clk, 0, 4 * sizeof(unsigned long long), st));
   }
-  if (p.tokens && !h->tok_bad) TRY(own_alloc(h, &h->tok_bad, 1));
+  if (p.tokens && !h->tok_bad) TRY(own_alloc(h->owned, &h->tok_bad, 1));
   const struct { size_t* cap; size_t need; } groups[] = {{&h->split_cap, p.split_tiles},     {&h->cap_bt_h, p.bt_h},         {&h->cap_tok, p.tok},
                                                           {&h->cap_cond_planes, p.planes}, {&h->cap_cond_tok, p.cond_tok}, {&h->cap_cond_exp, p.cond_exp}};
   for (const auto& g : groups) TRY(grow(h, g.cap, g.need, st));

@@ -16,12 +16,12 @@
 // and simplicity; the unfused attention materialises the [B*H,T,T] score matrix in HBM.
 #include <math.h>
 
-#include <array>
 #include <string>
 #include <type_traits>
 #include <vector>
 
 #include "bsg_common.h"
+#include "bsg_ws.h"
 #include "diffnet_res.h"
 
 namespace bsg {
@@ -1214,7 +1214,7 @@ struct FftLayerW {
 struct bsg_fs2midi {
   bsg_fs2midi_cfg cfg;
   Guard guard;   // this handle's range-event word and split-fp16 GEMM switch
-  std::vector<float*> owned;
+  DevOwned owned;
   // weights
   float *Etok, *dec_alpha, *dec_lnw, *dec_lnb, *mel_w, *mel_b, *Espk, *dur_lin_w, *dur_lin_b;
   std::vector<FftLayerW> enc, dec;
@@ -1254,43 +1254,47 @@ static void path_add(bsg_fs2midi* h, const char* tag, const char* tok) {
   h->path += full;
 }
 
-static int fs2_alloc(bsg_fs2midi* h, float** p, size_t n) {
-  BSG_HIP(hipMalloc((void**)p, n * sizeof(float)));
-  h->owned.push_back(*p);
-  return BSG_OK;
-}
 static int fs2_copy(bsg_fs2midi* h, float** dst, const void* src, size_t n, hipStream_t st) {
-  TRY(fs2_alloc(h, dst, n));
+  TRY(own_alloc(h->owned, dst, n));
   BSG_HIP(hipMemcpyAsync(*dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, st));
   return BSG_OK;
 }
 static int fs2_conv(bsg_fs2midi* h, float** dst, const void* src, int M, int Cin, int k, hipStream_t st) {
-  TRY(fs2_alloc(h, dst, (size_t)M * Cin * k));
+  TRY(own_alloc(h->owned, dst, (size_t)M * Cin * k));
   const long long total = (long long)M * Cin * k;
   hipLaunchKernelGGL(repack_conv_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, (const float*)src, *dst, M, Cin, k);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
 }
 
-// The handle's row-sized workspaces, in allocation order: destroy, ensure_ws and poison_ws all walk this one table.  `poison`: whether the
-// test hook fills it (not the position words).  w_scores, w_fsk and w_fcnt have capacities of their own (ensure_fft_ws).
-struct WsBuf { void** p; size_t per_row, elem; bool poison; };
-static std::array<WsBuf, 10> ws_table(bsg_fs2midi* h) {
-  return {{{(void**)&h->w_x, H, sizeof(float), true},      {(void**)&h->w_a, H, sizeof(float), true},
-           {(void**)&h->w_b, H, sizeof(float), true},      {(void**)&h->w_c, H, sizeof(float), true},
-           {(void**)&h->w_qkv, 3 * H, sizeof(float), true}, {(void**)&h->w_ffn, 4 * H, sizeof(float), true},
-           {(void**)&h->w_keep, 1, sizeof(float), true},   {(void**)&h->w_pos, 1, sizeof(int), false},
-           {(void**)&h->w_ap, 2 * H, sizeof(unsigned short), true}, {(void**)&h->w_fp, 2 * 4 * H, sizeof(unsigned short), true}}};
+// The handle's shape-sized workspaces (bsg_ws.h): destroy, grow() and the poison hook all walk this one table.  cap_rows: token / frame rows.
+// What depends on the attention form has capacities of its own, sized from the plan (launch_fft): the key-split partials, their arrival
+// counters (zeroed when (re)allocated: the kernel leaves every counter at zero; never poisoned: they must stay zero between launches) and
+// the score tensor.  The position words are not poisoned either.
+static std::vector<WsBuf> ws_table(bsg_fs2midi* h) {
+  const size_t f = sizeof(float), s = sizeof(unsigned short);
+  return {
+      {&h->cap_rows, (void**)&h->w_x, H * f, 0, WS_POISON},       {&h->cap_rows, (void**)&h->w_a, H * f, 0, WS_POISON},
+      {&h->cap_rows, (void**)&h->w_b, H * f, 0, WS_POISON},       {&h->cap_rows, (void**)&h->w_c, H * f, 0, WS_POISON},
+      {&h->cap_rows, (void**)&h->w_qkv, 3 * H * f, 0, WS_POISON}, {&h->cap_rows, (void**)&h->w_ffn, 4 * H * f, 0, WS_POISON},
+      {&h->cap_rows, (void**)&h->w_keep, f, 0, WS_POISON},        {&h->cap_rows, (void**)&h->w_pos, sizeof(int)},
+      {&h->cap_rows, (void**)&h->w_ap, 2 * H * s, 0, WS_POISON},  {&h->cap_rows, (void**)&h->w_fp, 2 * 4 * H * s, 0, WS_POISON},
+      {&h->cap_scores, (void**)&h->w_scores, f, 0, WS_POISON},
+      {&h->cap_fsk, (void**)&h->w_fsk, f, 0, WS_POISON},
+      {&h->cap_fcnt, (void**)&h->w_fcnt, sizeof(unsigned), 0, WS_ZERO},
+  };
+}
+// (the capacity test comes first, so that a call that grows nothing builds no table)
+static int grow(bsg_fs2midi* h, size_t* cap, size_t need, hipStream_t st) {
+  return need <= *cap ? BSG_OK : ws_grow(ws_table(h), "fs2", cap, need, st);
 }
 
 extern "C" void bsg_fs2midi_destroy(bsg_fs2midi* h) {
   if (!h) return;
   guard_free(&h->guard);
-  for (float* p : h->owned) (void)hipFree(p);
-  for (const WsBuf& w : ws_table(h))
-    if (*w.p) (void)hipFree(*w.p);
-  for (void* p : {(void*)h->w_scores, (void*)h->w_fsk, (void*)h->w_fcnt, (void*)h->pack_bad})
-    if (p) (void)hipFree(p);
+  h->owned.free_all();
+  ws_free(ws_table(h));
+  if (h->pack_bad) (void)hipFree(h->pack_bad);
   for (std::vector<FftLayerW>* v : {&h->enc, &h->dec})
     for (FftLayerW& L : *v) { h2w_free(&L.p_in); h2w_free(&L.p_out); h2w_free(&L.p_ffn1); h2w_free(&L.p_ffn2); }
   for (H2wWeights* p : {&h->p_esm_q, &h->p_esm_kv, &h->p_esm_out, &h->p_esm_f0, &h->p_esm_f2}) h2w_free(p);
@@ -1517,17 +1521,6 @@ extern "C" int bsg_fs2midi_create(bsg_fs2midi** out, const bsg_fs2midi_cfg* cfg,
   return fs2_create("fs2midi_create", out, &x, dev_weights, n_weights, dec_pos_table, rel_pos_table, nullptr, (hipStream_t)stream);
 }
 
-// workspace for `rows` token / frame rows (ws_table); what depends on the attention form is grown by ensure_fft_ws
-static int ensure_ws(bsg_fs2midi* h, size_t rows, hipStream_t st) {
-  if (rows <= h->cap_rows) return BSG_OK;
-  BSG_HIP(hipStreamSynchronize(st));
-  h->cap_rows = 0;
-  for (const WsBuf& w : ws_table(h)) { if (*w.p) (void)hipFree(*w.p); *w.p = nullptr; }
-  for (const WsBuf& w : ws_table(h)) BSG_HIP(hipMalloc(w.p, rows * w.per_row * w.elem));
-  h->cap_rows = rows;
-  return BSG_OK;
-}
-
 // launch_gemm / launch_gemm_h2w; with `rec`, the form it picked is added to that handle's launch record under `tag`
 template <class Args>
 static int launch_rec(int (*launch)(const Args&, hipStream_t), bsg_fs2midi* rec, const char* tag, Args& g, hipStream_t st) {
@@ -1663,27 +1656,6 @@ static FftPlan plan_fft(const bsg_fs2midi* h, int B, int T, int ksz) {
   return p;
 }
 
-// Before the first layer, what the plan's attention form needs beyond ws_table: the key-split partials with their arrival counters (zeroed
-// when (re)allocated: the kernel leaves every counter at zero) and the score tensor.  They only grow; the stream is drained before a free.
-static int ensure_fft_ws(bsg_fs2midi* h, const FftPlan& p, hipStream_t st) {
-  if (p.need_fsk > h->cap_fsk || p.need_fcnt > h->cap_fcnt) {
-    BSG_HIP(hipStreamSynchronize(st));
-    (void)hipFree(h->w_fsk); (void)hipFree(h->w_fcnt);
-    h->w_fsk = nullptr; h->w_fcnt = nullptr; h->cap_fsk = h->cap_fcnt = 0;
-    BSG_HIP(hipMalloc((void**)&h->w_fsk, p.need_fsk * sizeof(float)));
-    BSG_HIP(hipMalloc((void**)&h->w_fcnt, p.need_fcnt * sizeof(unsigned)));
-    BSG_HIP(hipMemsetAsync(h->w_fcnt, 0, p.need_fcnt * sizeof(unsigned), st));
-    h->cap_fsk = p.need_fsk; h->cap_fcnt = p.need_fcnt;
-  }
-  if (p.need_scores > h->cap_scores) {
-    BSG_HIP(hipStreamSynchronize(st));
-    (void)hipFree(h->w_scores); h->w_scores = nullptr; h->cap_scores = 0;
-    BSG_HIP(hipMalloc((void**)&h->w_scores, p.need_scores * sizeof(float)));
-    h->cap_scores = p.need_scores;
-  }
-  return BSG_OK;
-}
-
 // Q | K | V of a layer on the pre-split path, from the LayerNorm planes in h->w_ap
 static int qkv_h2w(bsg_fs2midi* h, const char* gtag, const FftPlan& p, const FftLayerW& L, const float* keep, hipStream_t st) {
   if (p.qkv == QKV_FUSED) {
@@ -1741,7 +1713,7 @@ static int attention(bsg_fs2midi* h, bool first, const char* stack, const char* 
   return BSG_OK;
 }
 
-// EncSALayer x FFTBlocks tail (common_layers.py:706-730, tts_modules.py:298-305); x [B*T, H] in place.  plan_fft decides, ensure_fft_ws
+// EncSALayer x FFTBlocks tail (common_layers.py:706-730, tts_modules.py:298-305); x [B*T, H] in place.  plan_fft decides, grow()
 // allocates, the loops only launch.  Every GEMM launch of every layer goes through path_add; the QKV and attention tokens are named in the
 // first layer only (`first`), the later layers launching the plan's same forms.
 static int launch_fft(bsg_fs2midi* h, const std::vector<FftLayerW>& layers, const float* lnw, const float* lnb, int ksz,
@@ -1749,7 +1721,9 @@ static int launch_fft(bsg_fs2midi* h, const std::vector<FftLayerW>& layers, cons
   const FftPlan p = plan_fft(h, B, T, ksz);
   const long long rows = p.rows;
   h->last_stack_rows = (int)rows;
-  TRY(ensure_fft_ws(h, p, st));
+  TRY(grow(h, &h->cap_fsk, p.need_fsk, st));
+  TRY(grow(h, &h->cap_fcnt, p.need_fcnt, st));
+  TRY(grow(h, &h->cap_scores, p.need_scores, st));
   const std::string gemm_tag = std::string(stack) + "gemm:";
   const char* gtag = gemm_tag.c_str();
   const float ffn_alpha = (float)pow((double)ksz, -0.5);
@@ -1834,7 +1808,7 @@ static int encode_impl(bsg_fs2midi* h, const int64_t* txt, const int64_t* pitch_
   const long long rows = (long long)B * Tt;        // every utterance: the lang embedding and K / V
   const long long lrows = (long long)nb * Tt;      // the rows asked for
   const long long off = (long long)row0 * Tt;
-  TRY(ensure_ws(h, (size_t)rows, st));
+  TRY(grow(h, &h->cap_rows, (size_t)rows, st));
   h->last_token_rows = (int)lrows;
   const dim3 rg(cdiv(rows, 4)), lg(cdiv(lrows, 4)), rb(256);
   const float sq = sqrtf((float)H);
@@ -1950,7 +1924,7 @@ extern "C" int bsg_fs2_encode_plain(bsg_fs2midi* h, const int64_t* txt, const in
   hipStream_t st = (hipStream_t)stream;
   h->path.clear();
   const long long lrows = (long long)n_rows * Tt, off = (long long)row0 * Tt;
-  TRY(ensure_ws(h, (size_t)lrows, st));
+  TRY(grow(h, &h->cap_rows, (size_t)lrows, st));
   h->last_token_rows = (int)lrows;
   float* x = h->w_c;
   hipLaunchKernelGGL(token_front_kernel, dim3(cdiv(lrows, 4)), dim3(256), 0, st, (const long long*)txt + off, h->Etok, h->rel_table, x, h->w_keep,
@@ -1976,17 +1950,9 @@ extern "C" const char* bsg_fs2midi_last_path(bsg_fs2midi* h) { return h && !h->p
 // Test hook: every activation workspace of the handle, at its current capacity, filled with 0xFF bytes (a NaN as fp16 and as fp32) — data
 // that a correct kernel never lets into a result.  Not the arrival counters of the key split (they must stay zero between launches), not
 // the position words, not weights.
-static int poison_ws(bsg_fs2midi* h, hipStream_t st) {
-  for (const WsBuf& w : ws_table(h))
-    if (w.poison && *w.p && h->cap_rows) BSG_HIP(hipMemsetAsync(*w.p, 0xFF, h->cap_rows * w.per_row * w.elem, st));
-  if (h->w_scores && h->cap_scores) BSG_HIP(hipMemsetAsync(h->w_scores, 0xFF, h->cap_scores * sizeof(float), st));
-  if (h->w_fsk && h->cap_fsk) BSG_HIP(hipMemsetAsync(h->w_fsk, 0xFF, h->cap_fsk * sizeof(float), st));
-  return BSG_OK;
-}
-
 extern "C" int bsg_fs2midi_debug_poison_workspace(bsg_fs2midi* h, void* stream) {
   BSG_REQUIRE(h, "fs2midi_debug_poison_workspace: null handle");
-  return poison_ws(h, (hipStream_t)stream);
+  return ws_poison(ws_table(h), (hipStream_t)stream);
 }
 
 extern "C" int bsg_length_regulator(const int64_t* dur, const int64_t* txt, int64_t* mel2ph, int32_t B, int32_t Tt, int32_t T,
@@ -2053,7 +2019,7 @@ static int decode_impl(bsg_fs2midi* h, const char* who, const float* enc_out, co
   BSG_REQUIRE(!h->use_pitch || T < h->n_pitch_pos, "%s: T=%d (pitch position table has %d rows)", who, T, h->n_pitch_pos);
   h->path.resize(h->path_enc_len);   // the record keeps the encode this decode follows
   const long long rows = (long long)B * T;
-  TRY(ensure_ws(h, (size_t)rows, st));
+  TRY(grow(h, &h->cap_rows, (size_t)rows, st));
   const dim3 rg(cdiv(rows, 4)), rb(256);
   if (h->use_pitch) {
     TRY(pitch_adaptor(h, enc_out, mel2ph, spk_id, speechsing, f0, uv, B, Tt, T, pitch_pred, f0_denorm, pitch_bin, decoder_inp, st));
@@ -2151,16 +2117,24 @@ struct bsg_fftden {
   int M = 0, S = 0, n_pos = 0, ksz = 9;
   std::vector<FftLayerW> layers;
   float *alpha, *lnw, *lnb, *in_w, *in_b, *mel_w, *mel_b, *gdi_w, *gdi_b, *dtab;
-  size_t cap = 0;
+  size_t cap = 0;   // rows (B x T) of the per-call buffers below
   int B = 0, T = 0;
   float *condpart = nullptr, *xT = nullptr, *xp = nullptr, *te = nullptr, *tvec = nullptr, *mel = nullptr;
 };
 
+// the handle's own per-call buffers (the FFT stack's are the core's).  `condpart` is not poisoned: bsg_fftden_prepare's result is an input
+// of every forward.  te: [B][H] used; rows >= B for any later (B,T) that fits
+static std::vector<WsBuf> ws_table(bsg_fftden* h) {
+  const size_t f = sizeof(float);
+  return {
+      {&h->cap, (void**)&h->condpart, H * f},          {&h->cap, (void**)&h->xT, H * f, 0, WS_POISON},   {&h->cap, (void**)&h->xp, H * f, 0, WS_POISON},
+      {&h->cap, (void**)&h->te, H * f, 0, WS_POISON},  {&h->cap, (void**)&h->tvec, H * f, 0, WS_POISON}, {&h->cap, (void**)&h->mel, h->M * f, 0, WS_POISON},
+  };
+}
+
 extern "C" void bsg_fftden_destroy(bsg_fftden* h) {
   if (!h) return;
-  float* ws[] = {h->condpart, h->xT, h->xp, h->te, h->tvec, h->mel};
-  for (float* p : ws)
-    if (p) (void)hipFree(p);
+  ws_free(ws_table(h));
   for (FftLayerW& L : h->layers) { h2w_free(&L.p_in); h2w_free(&L.p_out); h2w_free(&L.p_ffn1); h2w_free(&L.p_ffn2); }
   bsg_fs2midi_destroy(h->core);
   delete h;
@@ -2192,8 +2166,8 @@ static int fftden_load(bsg_fftden* h, int n_layers, const void* const* w, const 
   TRY(fs2_copy(c, &h->gdi_b, w[i++], H, st));
   // step-embedding MLP tabulated for every timestep (candidate_decoder.py:60-62)
   float* hid = nullptr;
-  TRY(fs2_alloc(c, &hid, (size_t)h->S * 4 * H));
-  TRY(fs2_alloc(c, &h->dtab, (size_t)h->S * H));
+  TRY(own_alloc(c->owned, &hid, (size_t)h->S * 4 * H));
+  TRY(own_alloc(c->owned, &h->dtab, (size_t)h->S * H));
   TRY(linear(step_table, m0w, m0b, hid, h->S, 4 * H, H, ACT_MISH, nullptr, nullptr, st));
   TRY(linear(hid, m2w, m2b, h->dtab, h->S, H, 4 * H, ACT_NONE, nullptr, nullptr, st));
   return create_tail(c, pos_table, nullptr, nullptr, st);   // the frame position table: c->dec_table
@@ -2228,20 +2202,8 @@ extern "C" int bsg_fftden_prepare(bsg_fftden* h, const float* cond, int32_t B, i
   BSG_REQUIRE(h && cond && B > 0 && T > 0 && T < h->n_pos, "fftden_prepare: bad argument (T=%d)", T);
   hipStream_t st = (hipStream_t)stream;
   const size_t rows = (size_t)B * T;
-  if (rows > h->cap) {
-    BSG_HIP(hipStreamSynchronize(st));
-    float** bufs[] = {&h->condpart, &h->xT, &h->xp, &h->te, &h->tvec, &h->mel};
-    for (float** p : bufs) { if (*p) (void)hipFree(*p); *p = nullptr; }
-    h->cap = 0;
-    BSG_HIP(hipMalloc((void**)&h->condpart, rows * H * sizeof(float)));
-    BSG_HIP(hipMalloc((void**)&h->xT, rows * H * sizeof(float)));
-    BSG_HIP(hipMalloc((void**)&h->xp, rows * H * sizeof(float)));
-    BSG_HIP(hipMalloc((void**)&h->te, rows * H * sizeof(float)));      // [B][H] used; rows >= B for any later (B,T) that fits
-    BSG_HIP(hipMalloc((void**)&h->tvec, rows * H * sizeof(float)));
-    BSG_HIP(hipMalloc((void**)&h->mel, rows * h->M * sizeof(float)));
-    h->cap = rows;
-  }
-  TRY(ensure_ws(h->core, rows, st));
+  if (rows > h->cap) TRY(ws_grow(ws_table(h), "fftden", &h->cap, rows, st));
+  TRY(grow(h->core, &h->core->cap_rows, rows, st));
   h->B = B; h->T = T;
   // cond [B][H][T] -> [B*T][H]; condpart = cond_t * W[:, C:2C]^T                           (candidate_decoder.py:63-70)
   hipLaunchKernelGGL(transpose_brc_kernel, dim3(cdiv(T, 32), cdiv(H, 32), B), dim3(256), 0, st, cond, h->xT, H, T);
@@ -2300,12 +2262,8 @@ extern "C" const char* bsg_fftden_last_path(bsg_fftden* h) { return h && h->core
 extern "C" int bsg_fftden_debug_poison_workspace(bsg_fftden* h, void* stream) {
   BSG_REQUIRE(h && h->core, "fftden_debug_poison_workspace: null handle");
   hipStream_t st = (hipStream_t)stream;
-  TRY(poison_ws(h->core, st));
-  float* own[] = {h->xT, h->xp, h->te, h->tvec};
-  for (float* p : own)
-    if (p && h->cap) BSG_HIP(hipMemsetAsync(p, 0xFF, h->cap * H * sizeof(float), st));
-  if (h->mel && h->cap) BSG_HIP(hipMemsetAsync(h->mel, 0xFF, h->cap * h->M * sizeof(float), st));
-  return BSG_OK;
+  TRY(ws_poison(ws_table(h->core), st));
+  return ws_poison(ws_table(h), st);
 }
 
 namespace bsg {

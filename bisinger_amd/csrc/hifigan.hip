@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "bsg_common.h"
+#include "bsg_ws.h"
 
 namespace bsg {
 namespace {
@@ -1755,7 +1756,7 @@ struct HgStep {
 struct bsg_hifigan {
   bsg_hifigan_cfg cfg;
   Guard guard;   // this handle's range-event word and split-fp16 switch
-  std::vector<float*> owned;
+  DevOwned owned;
   std::vector<float*> create_tmp;   // reorder temporaries of the weight packing: freed behind create's stream synchronize
   ConvW pre, post;
   std::vector<ConvW> ups;                 // weight [Cin][Cout][K]
@@ -1796,32 +1797,38 @@ static void path_add(bsg_hifigan* h, const HgStep& s) {
   path_token(h, tok);
 }
 
+// The handle's shape-sized workspaces (bsg_ws.h): destroy, grow() and the poison hook walk this one table.  cap: elements of one stage
+// buffer; cap_src: samples B x L of the NSF source; planes_cap: halfs; lens_cap: rows (not poisoned: the call itself fills them).
+static std::vector<WsBuf> ws_table(bsg_hifigan* h) {
+  const size_t f = sizeof(float);
+  return {
+      {&h->cap, (void**)&h->buf[0], f, 0, WS_POISON}, {&h->cap, (void**)&h->buf[1], f, 0, WS_POISON}, {&h->cap, (void**)&h->buf[2], f, 0, WS_POISON},
+      {&h->cap, (void**)&h->buf[3], f, 0, WS_POISON}, {&h->cap, (void**)&h->buf[4], f, 0, WS_POISON},
+      {&h->cap_src, (void**)&h->sw_tmp, (h->cfg.harmonic_num + 1) * f, 0, WS_POISON}, {&h->cap_src, (void**)&h->har, f, 0, WS_POISON},
+      {&h->planes_cap, (void**)&h->planes, sizeof(unsigned short), 0, WS_POISON},
+      {&h->lens_cap, (void**)&h->lens, sizeof(int)},
+  };
+}
+// (the capacity test comes first, so that a call that grows nothing builds no table)
+static int grow(bsg_hifigan* h, size_t* cap, size_t need, hipStream_t st) {
+  return need <= *cap ? BSG_OK : ws_grow(ws_table(h), "hifigan", cap, need, st);
+}
+
 extern "C" void bsg_hifigan_destroy(bsg_hifigan* h) {
   if (!h) return;
   guard_free(&h->guard);
-  for (float* p : h->owned) (void)hipFree(p);
-  for (float* p : h->buf)
-    if (p) (void)hipFree(p);
-  if (h->sw_tmp) (void)hipFree(h->sw_tmp);
-  if (h->har) (void)hipFree(h->har);
-  if (h->planes) (void)hipFree(h->planes);
-  if (h->lens) (void)hipFree(h->lens);
+  h->owned.free_all();
+  ws_free(ws_table(h));
   h2w_free(&h->pre.h2w);
   for (ConvW& c : h->ups) h2w_free(&c.h2w);
   for (float* t : h->create_tmp) (void)hipFree(t);
   delete h;
 }
 
-static int hg_alloc(bsg_hifigan* h, float** p, size_t n) {
-  BSG_HIP(hipMalloc((void**)p, n * sizeof(float)));
-  h->owned.push_back(*p);
-  return BSG_OK;
-}
-
 // consumes (bias, weight) or (bias, weight_g, weight_v) from the state_dict-ordered pointer list
 static int take_conv(bsg_hifigan* h, ConvW& c, const void* const*& w, int dim0, int inner, hipStream_t st) {
   const size_t n = (size_t)dim0 * inner;
-  TRY(hg_alloc(h, &c.w, n));
+  TRY(own_alloc(h->owned, &c.w, n));
   const void* bias = *w++;
   if (h->cfg.weight_norm) {
     const float* g = (const float*)*w++;
@@ -1831,7 +1838,7 @@ static int take_conv(bsg_hifigan* h, ConvW& c, const void* const*& w, int dim0, 
   } else {
     BSG_HIP(hipMemcpyAsync(c.w, *w++, n * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
-  TRY(hg_alloc(h, &c.b, c.cout));
+  TRY(own_alloc(h->owned, &c.b, c.cout));
   BSG_HIP(hipMemcpyAsync(c.b, bias, c.cout * sizeof(float), hipMemcpyDeviceToDevice, st));
   return BSG_OK;
 }
@@ -1839,33 +1846,33 @@ static int take_conv(bsg_hifigan* h, ConvW& c, const void* const*& w, int dim0, 
 static int pack_conv(bsg_hifigan* h, ConvW& c, hipStream_t st, bool pair = false) {
   const int CO = c.cout >= 16 ? 16 : 8;
   const int n = cdiv(c.cout, CO) * c.cin * c.k * CO;
-  TRY(hg_alloc(h, &c.wpk, n));
+  TRY(own_alloc(h->owned, &c.wpk, n));
   hipLaunchKernelGGL(pack_conv_w_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, (const float*)c.w, c.wpk, c.cout, c.cin, c.k, CO);
   BSG_LAUNCH_CHECK();
   if (pair && c.cin == c.cout && pair_supported(c.k, c.cout)) {   // one block of all output channels: [cin][k][cout]
     const int m = c.cin * c.k * c.cout;
-    TRY(hg_alloc(h, &c.wpc, m));
+    TRY(own_alloc(h->owned, &c.wpc, m));
     hipLaunchKernelGGL(pack_conv_w_kernel, dim3(cdiv(m, 256)), dim3(256), 0, st, (const float*)c.w, c.wpc, c.cout, c.cin, c.k, c.cout);
     BSG_LAUNCH_CHECK();
     if (pair_h16_supported(c.k, c.cout)) {
       const int tpk = 32 / c.cout, ks = (c.k + tpk - 1) / tpk;
-      TRY(hg_alloc(h, &c.wp16, (size_t)ks * 512));   // ks x 2 planes x 64 lanes x 8 halves = ks x 512 floats
+      TRY(own_alloc(h->owned, &c.wp16, (size_t)ks * 512));   // ks x 2 planes x 64 lanes x 8 halves = ks x 512 floats
       hipLaunchKernelGGL(pack_conv_h16_kernel, dim3(cdiv(ks * 512, 256)), dim3(256), 0, st, (const float*)c.w, reinterpret_cast<_Float16*>(c.wp16), c.cout,
                          c.k, h->w_range_bad);
       BSG_LAUNCH_CHECK();
       c.wp16c = c.wp16;
     } else if ((c.cout == 8 || c.cout == 16) && (c.k == 3 || c.k == 7 || c.k == 11)) {   // (8 channels, K = 3 / 7: pairs on the vector pipe, chain on the matrix pipe)
       const int tpk = 32 / c.cout, ks = (c.k + tpk - 1) / tpk;
-      TRY(hg_alloc(h, &c.wp16c, (size_t)ks * 512));
+      TRY(own_alloc(h->owned, &c.wp16c, (size_t)ks * 512));
       hipLaunchKernelGGL(pack_conv_h16_kernel, dim3(cdiv(ks * 512, 256)), dim3(256), 0, st, (const float*)c.w, reinterpret_cast<_Float16*>(c.wp16c), c.cout,
                          c.k, h->w_range_bad);
       BSG_LAUNCH_CHECK();
     }
     if (pair_mfma_supported(c.k, c.cout)) {
-      TRY(hg_alloc(h, &c.wpm, m));
+      TRY(own_alloc(h->owned, &c.wpm, m));
       hipLaunchKernelGGL(pack_conv_mfma_kernel, dim3(cdiv(m, 256)), dim3(256), 0, st, (const float*)c.w, c.wpm, c.cout, c.k);
       BSG_LAUNCH_CHECK();
-      TRY(hg_alloc(h, &c.wps, m));
+      TRY(own_alloc(h->owned, &c.wps, m));
       hipLaunchKernelGGL(pack_conv_h2_kernel, dim3(cdiv(m, 256)), dim3(256), 0, st, (const float*)c.w, reinterpret_cast<_Float16*>(c.wps), c.cout, c.k,
                          h->w_range_bad);
       BSG_LAUNCH_CHECK();
@@ -1918,27 +1925,16 @@ static int pack_pre_h2w(bsg_hifigan* h, ConvW& c, hipStream_t st) {
   c.h2w_kp = kp;
   return BSG_OK;
 }
-static int ensure_planes(bsg_hifigan* h, size_t halfs, hipStream_t st) {
-  if (halfs > h->planes_cap) {
-    BSG_HIP(hipStreamSynchronize(st));
-    if (h->planes) (void)hipFree(h->planes);
-    h->planes = nullptr; h->planes_cap = 0;
-    BSG_HIP(hipMalloc((void**)&h->planes, halfs * sizeof(unsigned short)));
-    h->planes_cap = halfs;
-  }
-  return BSG_OK;
-}
-
 static int pack_convT(bsg_hifigan* h, ConvW& c, int u, hipStream_t st) {
   if (c.k != 2 * u) return BSG_OK;   // other shapes keep the gather kernel
   const int CO = c.cout >= 16 ? 16 : 8;
   const int n = u * cdiv(c.cout, CO) * c.cin * 2 * CO;
-  TRY(hg_alloc(h, &c.wpk, n));
+  TRY(own_alloc(h->owned, &c.wpk, n));
   hipLaunchKernelGGL(pack_convT_w_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, (const float*)c.w, c.wpk, c.cin, c.cout, u, CO);
   BSG_LAUNCH_CHECK();
   if (u == 8 || u == 2 || u == 4) {
     const int n8 = u * cdiv(c.cout, 8) * c.cin * 2 * 8;
-    TRY(hg_alloc(h, &c.wpu, n8));
+    TRY(own_alloc(h->owned, &c.wpu, n8));
     hipLaunchKernelGGL(pack_convT_w_kernel, dim3(cdiv(n8, 256)), dim3(256), 0, st, (const float*)c.w, c.wpu, c.cin, c.cout, u, 8);
     BSG_LAUNCH_CHECK();
   }
@@ -1987,16 +1983,14 @@ extern "C" int bsg_hifigan_create(bsg_hifigan** out, const bsg_hifigan_cfg* cfg,
   if ((rc = guard_init(&h->guard, st)) != BSG_OK) return fail(rc);
   const int C0 = cfg->upsample_initial_channel;
   {
-    float* cnt = nullptr;
-    if ((rc = hg_alloc(h, &cnt, 1)) != BSG_OK) return fail(rc);
-    h->w_range_bad = reinterpret_cast<unsigned*>(cnt);
+    if ((rc = own_alloc(h->owned, &h->w_range_bad, 1)) != BSG_OK) return fail(rc);
     if (hipMemsetAsync(h->w_range_bad, 0, sizeof(unsigned), st) != hipSuccess) { set_error("hifigan_create: memset failed"); return fail(BSG_EHIP); }
   }
   if (cfg->use_nsf) {
     // m_source.l_linear.{weight [1,NH], bias [1]}, noise_convs.i.{weight [c,1,k], bias [c]} precede conv_pre (hifigan.py:111-132)
     const int NH = cfg->harmonic_num + 1;
     auto cp = [&](float** dst, const void* src, size_t n) -> int {
-      int r = hg_alloc(h, dst, n);
+      int r = own_alloc(h->owned, dst, n);
       if (r != BSG_OK) return r;
       if (hipMemcpyAsync(*dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) { set_error("hifigan_create: copy failed"); return BSG_EHIP; }
       return BSG_OK;
@@ -2166,7 +2160,7 @@ static int run_h2w(bsg_hifigan* h, const ConvW& c, const float* src, float* dst,
                    HgRows rg, hipStream_t st) {
   const long long n = (long long)B * rows * c.h2w_kp;
   const int Lout = up_u ? Lin * up_u : Lin;
-  TRY(ensure_planes(h, (size_t)2 * n, st));
+  TRY(grow(h, &h->planes_cap, (size_t)2 * n, st));
   // ragged: the feeding pass reads a row up to ITS end and writes zeros from there on, as it does from Lin on; the product runs the padded shape
   TRY(h2w_split_transposed_lrelu(src, h->planes, h->planes + n, B, c.cin, c.h2w_kp, Lin, rows, slope, rg.lens, rg.lmul, st));
   H2wArgs g{};
@@ -2193,13 +2187,7 @@ static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, 
     }
     BSG_REQUIRE(L < (1LL << 31) / 4, "hifigan_forward: output length %lld too large", L);
   }
-  if (need > h->cap) {
-    BSG_HIP(hipStreamSynchronize(st));
-    for (float*& p : h->buf) { if (p) (void)hipFree(p); p = nullptr; }
-    h->cap = 0;
-    for (float*& p : h->buf) BSG_HIP(hipMalloc((void**)&p, need * sizeof(float)));
-    h->cap = need;
-  }
+  TRY(grow(h, &h->cap, need, st));
   const int n_steps = plan_hifigan(h, B, T, har != nullptr, h->steps.data());
   // The stage buffers: x holds conv_pre's output and then every stage's output (the MRF running sum), xs the stage's input (the upsampled
   // tensor, plus the source term); inside a ResBlock the running tensor y moves xs -> ya -> yb -> ... and lands in x with the last pair;
@@ -2337,13 +2325,7 @@ static int hifigan_set_lens(bsg_hifigan* h, const int32_t* lengths_host, int B, 
   BSG_REQUIRE(B > 0 && B <= 65535 && T > 0, "%s: bad argument (B=%d T=%d)", who, B, T);
   for (int b = 0; b < B; ++b)
     BSG_REQUIRE(lengths_host[b] >= 1 && lengths_host[b] <= T, "%s: lengths[%d]=%d outside 1..T=%d", who, b, lengths_host[b], T);
-  if ((size_t)B > h->lens_cap) {
-    BSG_HIP(hipStreamSynchronize(st));
-    if (h->lens) (void)hipFree(h->lens);
-    h->lens = nullptr; h->lens_cap = 0;
-    BSG_HIP(hipMalloc((void**)&h->lens, (size_t)B * sizeof(int)));
-    h->lens_cap = B;
-  }
+  TRY(grow(h, &h->lens_cap, (size_t)B, st));
   for (int b0 = 0; b0 < B; b0 += 256) {
     LensChunk c{};
     const int rows = B - b0 < 256 ? B - b0 : 256;
@@ -2383,17 +2365,7 @@ static int hifigan_forward_nsf_any(bsg_hifigan* h, const float* mel, const float
   for (int i = 0; i < h->cfg.n_ups; ++i) hop *= h->cfg.upsample_rates[i];
   const long long L = (long long)T * hop;
   const int NH = h->cfg.harmonic_num + 1;
-  const size_t need = (size_t)B * L;
-  if (need > h->cap_src) {
-    BSG_HIP(hipStreamSynchronize(st));
-    if (h->sw_tmp) (void)hipFree(h->sw_tmp);
-    if (h->har) (void)hipFree(h->har);
-    h->sw_tmp = h->har = nullptr;
-    h->cap_src = 0;
-    BSG_HIP(hipMalloc((void**)&h->sw_tmp, need * NH * sizeof(float)));
-    BSG_HIP(hipMalloc((void**)&h->har, need * sizeof(float)));
-    h->cap_src = need;
-  }
+  TRY(grow(h, &h->cap_src, (size_t)B * L, st));
   TRY(nsf_launch_source(f0, rand_ini, noise, h->src_w, h->src_b, h->sw_tmp, h->har, B, T, hop, NH, (float)h->cfg.sample_rate, lens, st));
   path_token(h, "src:nsf");
   return hifigan_run(h, mel, wav, B, T, stream, h->har, L, lens);
@@ -2425,13 +2397,7 @@ extern "C" int bsg_hifigan_forward_nsf_ragged(bsg_hifigan* h, const float* mel, 
 // test hook: NaN bytes into every stage buffer, the NSF source buffers and the planes of the split-fp16 GEMM forms
 extern "C" int bsg_hifigan_debug_poison_workspace(bsg_hifigan* h, void* stream) {
   BSG_REQUIRE(h, "hifigan_debug_poison_workspace: null handle");
-  hipStream_t st = (hipStream_t)stream;
-  for (float* p : h->buf)
-    if (p) BSG_HIP(hipMemsetAsync(p, 0xFF, h->cap * sizeof(float), st));
-  if (h->sw_tmp) BSG_HIP(hipMemsetAsync(h->sw_tmp, 0xFF, h->cap_src * (h->cfg.harmonic_num + 1) * sizeof(float), st));
-  if (h->har) BSG_HIP(hipMemsetAsync(h->har, 0xFF, h->cap_src * sizeof(float), st));
-  if (h->planes) BSG_HIP(hipMemsetAsync(h->planes, 0xFF, h->planes_cap * sizeof(unsigned short), st));
-  return BSG_OK;
+  return ws_poison(ws_table(h), (hipStream_t)stream);
 }
 
 // The launches of the last bsg_hifigan_forward[_nsf] of this handle, one token per launch in launch order ("none" before the first).  The

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "bsg_common.h"
+#include "bsg_ws.h"
 
 namespace bsg {
 namespace {
@@ -305,7 +306,7 @@ using namespace bsg;
 struct bsg_pitchext {
   bsg_pitchext_cfg cfg;
   Guard guard;   // this handle's range-event word and split-fp16 GEMM switch
-  std::vector<float*> owned;
+  DevOwned owned;
   float *pre_w[3], *pre_b[3], *pre_scale[3], *pre_shift[3], *pre_out_w, *pre_out_b;
   std::vector<float*> enc_w, enc_b, enc_gw, enc_gb;
   float *enc_in_w, *enc_in_b, *enc_out_w, *enc_out_b;
@@ -317,18 +318,21 @@ struct bsg_pitchext {
   int* pos = nullptr;
 };
 
-static int pe_alloc(bsg_pitchext* h, float** p, size_t n) {
-  BSG_HIP(hipMalloc((void**)p, n * sizeof(float)));
-  h->owned.push_back(*p);
-  return BSG_OK;
+// the handle's shape-sized workspaces (bsg_ws.h), all of cap = B x T rows: the forward grows them, destroy frees them
+static std::vector<WsBuf> ws_table(bsg_pitchext* h) {
+  const size_t f = sizeof(float);
+  return {
+      {&h->cap, (void**)&h->a, H * f}, {&h->cap, (void**)&h->b, H * f},        {&h->cap, (void**)&h->c, H * f},
+      {&h->cap, (void**)&h->keep, f},  {&h->cap, (void**)&h->pred, 2 * f},     {&h->cap, (void**)&h->pos, sizeof(int)},
+  };
 }
 static int pe_copy(bsg_pitchext* h, float** dst, const void* src, size_t n, hipStream_t st) {
-  TRY(pe_alloc(h, dst, n));
+  TRY(own_alloc(h->owned, dst, n));
   BSG_HIP(hipMemcpyAsync(*dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, st));
   return BSG_OK;
 }
 static int pe_conv(bsg_pitchext* h, float** dst, const void* src, int M, int Cin, int k, hipStream_t st) {
-  TRY(pe_alloc(h, dst, (size_t)M * Cin * k));
+  TRY(own_alloc(h->owned, dst, (size_t)M * Cin * k));
   const long long total = (long long)M * Cin * k;
   hipLaunchKernelGGL(repack_conv5_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, (const float*)src, *dst, M, Cin, k);
   BSG_LAUNCH_CHECK();
@@ -338,11 +342,8 @@ static int pe_conv(bsg_pitchext* h, float** dst, const void* src, int M, int Cin
 extern "C" void bsg_pitchext_destroy(bsg_pitchext* h) {
   if (!h) return;
   guard_free(&h->guard);
-  for (float* p : h->owned) (void)hipFree(p);
-  float* ws[] = {h->a, h->b, h->c, h->keep, h->pred};
-  for (float* p : ws)
-    if (p) (void)hipFree(p);
-  if (h->pos) (void)hipFree(h->pos);
+  h->owned.free_all();
+  ws_free(ws_table(h));
   delete h;
 }
 
@@ -357,8 +358,8 @@ static int pe_create_impl(bsg_pitchext* h, const void* const* w, const float* ta
     TRY(pe_copy(h, &h->pre_b[l], w[i++], H, st));
     const float *bw = (const float*)w[i++], *bb = (const float*)w[i++], *bm = (const float*)w[i++], *bv = (const float*)w[i++];
     i++;  // num_batches_tracked
-    TRY(pe_alloc(h, &h->pre_scale[l], H));
-    TRY(pe_alloc(h, &h->pre_shift[l], H));
+    TRY(own_alloc(h->owned, &h->pre_scale[l], H));
+    TRY(own_alloc(h->owned, &h->pre_shift[l], H));
     hipLaunchKernelGGL(bn_affine_kernel, dim3(1), dim3(256), 0, st, bw, bb, bm, bv, 1e-5f, h->pre_scale[l], h->pre_shift[l], H);
     BSG_LAUNCH_CHECK();
   }
@@ -430,20 +431,7 @@ extern "C" int bsg_pitchext_forward(bsg_pitchext* h, const float* mel, float* pi
   BSG_REQUIRE(h && mel && f0 && B > 0 && T > 0 && T < h->cfg.n_pos, "pitchext_forward: bad argument (T=%d, table %d rows)", T, h ? h->cfg.n_pos : 0);
   hipStream_t st = (hipStream_t)stream;
   const long long rows = (long long)B * T;
-  if ((size_t)rows > h->cap) {
-    BSG_HIP(hipStreamSynchronize(st));
-    float** bufs[] = {&h->a, &h->b, &h->c, &h->keep, &h->pred};
-    for (float** p : bufs) { if (*p) (void)hipFree(*p); *p = nullptr; }
-    if (h->pos) { (void)hipFree(h->pos); h->pos = nullptr; }
-    h->cap = 0;
-    BSG_HIP(hipMalloc((void**)&h->a, rows * H * sizeof(float)));
-    BSG_HIP(hipMalloc((void**)&h->b, rows * H * sizeof(float)));
-    BSG_HIP(hipMalloc((void**)&h->c, rows * H * sizeof(float)));
-    BSG_HIP(hipMalloc((void**)&h->keep, rows * sizeof(float)));
-    BSG_HIP(hipMalloc((void**)&h->pred, rows * 2 * sizeof(float)));
-    BSG_HIP(hipMalloc((void**)&h->pos, rows * sizeof(int)));
-    h->cap = (size_t)rows;
-  }
+  if ((size_t)rows > h->cap) TRY(ws_grow(ws_table(h), "pitchext", &h->cap, (size_t)rows, st));
   const dim3 rg(cdiv(rows, 4)), rb(256);
   hipLaunchKernelGGL(row_keep_kernel, rg, rb, 0, st, mel, h->keep, rows, h->cfg.n_mel);
   BSG_LAUNCH_CHECK();

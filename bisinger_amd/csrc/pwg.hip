@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "bsg_common.h"
+#include "bsg_ws.h"
 
 namespace bsg {
 namespace {
@@ -300,6 +301,9 @@ struct bsg_pwg {
   std::string path;
 };
 
+// the table of that one allocation (bsg_ws.h): the forward grows it, destroy frees it, the test hook poisons it
+static std::vector<WsBuf> ws_table(bsg_pwg* h) { return {{&h->ws_bytes, (void**)&h->ws, 1, 0, WS_POISON}}; }
+
 static int pwg_expected_weights(const bsg_pwg_cfg* c) { return 2 + 1 + c->n_scales + 7 * c->layers + 4 + (c->use_pitch_embed ? 3 : 0); }
 
 extern "C" int bsg_pwg_n_weights(const bsg_pwg_cfg* cfg) { return cfg ? pwg_expected_weights(cfg) : 0; }
@@ -307,7 +311,7 @@ extern "C" int bsg_pwg_n_weights(const bsg_pwg_cfg* cfg) { return cfg ? pwg_expe
 extern "C" void bsg_pwg_destroy(bsg_pwg* h) {
   if (!h) return;
   if (h->wdev) (void)hipFree(h->wdev);
-  if (h->ws) (void)hipFree(h->ws);
+  ws_free(ws_table(h));
   delete h;
 }
 
@@ -445,8 +449,7 @@ extern "C" int bsg_pwg_create(bsg_pwg** out, const bsg_pwg_cfg* cfg, const void*
 
 extern "C" int bsg_pwg_debug_poison_workspace(bsg_pwg* h, void* stream) {
   BSG_REQUIRE(h, "pwg_debug_poison_workspace: null handle");
-  if (h->ws) BSG_HIP(hipMemsetAsync(h->ws, 0xFF, h->ws_bytes, (hipStream_t)stream));
-  return BSG_OK;
+  return ws_poison(ws_table(h), (hipStream_t)stream);
 }
 
 extern "C" int bsg_pwg_forward(bsg_pwg* h, const float* z, const float* c, const int64_t* pitch, float* y, int32_t B, int32_t T, uint64_t seed,
@@ -468,12 +471,9 @@ extern "C" int bsg_pwg_forward(bsg_pwg* h, const float* z, const float* c, const
   const size_t n_cp = al((size_t)B * PW_A * Tp), n_c2 = al((size_t)B * PW_A * T), n_cf = al((size_t)B * PW_A * L),
                n_ct = al((size_t)B * PW_A * (L / s_last)), n_x = al((size_t)B * PW_R * L), n_z = al((size_t)B * L);
   const size_t need = (n_cp + n_c2 + n_cf + n_ct + 3 * n_x + n_z) * sizeof(float);
-  if (need > h->ws_bytes) {      // grows outside a capture only: hipMalloc inside one fails, and says so
-    BSG_HIP(hipStreamSynchronize(st));
-    if (h->ws) (void)hipFree(h->ws);
-    h->ws = nullptr; h->ws_bytes = 0;
-    BSG_HIP(hipMalloc((void**)&h->ws, need));
-    h->ws_bytes = need;
+  if (need > h->ws_bytes) {
+    const int rc = ws_grow(ws_table(h), "pwg", &h->ws_bytes, need, st);
+    if (rc != BSG_OK) return rc;
   }
   float* cp = h->ws;
   float* c2 = cp + n_cp;
