@@ -39,6 +39,12 @@ __device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// Ragged batches outside the vocoder (gemm.hip, pe_nsf.hip): `lens` (device, one row count per batch item) bounds item b by lens[b] while
+// the PITCH of its tensors stays T.  A template flag, as hifigan.hip's row_bound: the padded instantiation compiles to what it was without
+// it.  Wave-uniform wherever b is: one scalar load.
+template <bool RAG>
+__device__ __forceinline__ int rag_len(const int* __restrict__ lens, int b, int T) { return RAG ? lens[b] : T; }
+
 // an integer switch of the environment, or `dflt` while it is unset (host side; callers read it once and keep the value)
 static inline int env_int(const char* name, int dflt) {
   const char* e = getenv(name);
@@ -80,6 +86,10 @@ struct GemmArgs {
   const char** form_out;    // optional, host side only: launch_gemm stores the name of the form it launched (a string literal) for the caller's launch record
   int force_form;           // TEST HOOK (bsg_gemm_ex only; every other caller leaves it 0 = dispatch): 1 gemm_split/64, 2 gemm_split/128,
                             // 3 gemm_fast/64, 4 gemm_fast/128, 5 gemm_f32; 1-4 on a problem that fails the alignment rule is BSG_EINVAL
+  const int* lens;          // ragged (null everywhere but bsg_pitchext_forward_ragged): device, `batch` row counts, 1 <= lens[z] <= M.  Item z reads and
+                            // writes rows < lens[z] only, tap rows at or beyond the bound read as 0, and a workgroup whose first row lies beyond it
+                            // returns before its first load.  Same form choice and grid as without; gemm_split / gemm_fast with trans_b and no
+                            // batch2 only — anything else is BSG_EINVAL.  (Last member: the fields the padded kernels read keep their offsets.)
 };
 int launch_gemm(const GemmArgs& g, hipStream_t st);
 // the split-fp16 forms (gemm.hip, fs2.hip flash attention): true while products are formed on the 16-bit matrix pipe (BSG_GEMM_SPLIT,

@@ -38,6 +38,13 @@ void ws_free(const std::vector<WsBuf>& table);
 // test hooks: 0xFF bytes (a NaN as fp16 and as fp32) over capacity x unit of every WS_POISON buffer
 int ws_poison(const std::vector<WsBuf>& table, hipStream_t st);
 
+// Ragged forwards (bsg_hifigan_forward_ragged, bsg_pitchext_forward_ragged): the rows' counts reach the kernels through a handle-owned
+// device array — one more row of the handle's table, not poisoned — that the call itself fills.
+//   lens_check: lengths_host non-null and every count in 1 .. T, else BSG_EINVAL naming the row; touches nothing on the device.
+//   lens_fill:  launches of set_lens_kernel on `st` that carry the counts in their arguments and store them at dst[0 .. B).
+int lens_check(const int32_t* lengths_host, int B, int T, const char* who);
+int lens_fill(int* dst, const int32_t* lengths_host, int B, hipStream_t st);
+
 // The allocations that live as long as a handle (packed weights, tables, once-only device words): allocated and remembered, freed
 // together by destroy.
 struct DevOwned {

@@ -223,7 +223,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
 constexpr int FBN = 128;
 constexpr int FLDN = FBN + 8;                       // !TRANS_B image [k][n]: the two lane halves (k and k + 4) land 32 banks apart
 
-template <int BM, int FBK, bool TRANS_B>   // FBK = 16 or 32: k extent of an LDS stage
+template <int BM, int FBK, bool TRANS_B, bool RAG = false>   // FBK = 16 or 32: k extent of an LDS stage; RAG: rows bounded per batch item (GemmArgs::lens)
 __global__ __launch_bounds__(256) void gemm_fast_kernel(GemmArgs g) {
   constexpr int FLD = FBK + 4;   // row stride 20 / 36 floats: the 16 rows of a b128 lane group fall on 16 different bank quads
   constexpr int A_FLOATS = BM * FLD;
@@ -241,6 +241,10 @@ __global__ __launch_bounds__(256) void gemm_fast_kernel(GemmArgs g) {
   const int wm = BM == 128 ? wave >> 1 : 0, wn = BM == 128 ? wave & 1 : wave;
   const int l31 = lane & 31, lh = lane >> 5;
   const int bm = blockIdx.y * BM, bn = blockIdx.x * FBN, bz = blockIdx.z;
+  const int Mb = rag_len<RAG>(g.lens, bz, g.M);   // rows of this batch item; g.M stays the pitch of the grid
+  if constexpr (RAG) {
+    if (bm >= Mb) return;                         // the whole tile lies beyond the item's end: nothing to load, nothing to store
+  }
   const int b2 = g.batch2 > 1 ? g.batch2 : 1;
   const int zo = bz / b2, zi = bz - zo * b2;
   const float* __restrict__ A = g.A + (long long)zo * g.sA + (long long)zi * g.sA2;
@@ -267,7 +271,7 @@ __global__ __launch_bounds__(256) void gemm_fast_kernel(GemmArgs g) {
       const int row = idx >> KQS, gk = k0 + ((idx & (KQ - 1)) << 2);
       const int gr = bm + row + shift;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (gr >= 0 && gr < g.M && (bm + row) < g.M && gk < g.K) v = *reinterpret_cast<const f32x4*>(A + (long long)gr * g.lda + gk);
+      if (gr >= 0 && gr < Mb && (bm + row) < Mb && gk < g.K) v = *reinterpret_cast<const f32x4*>(A + (long long)gr * g.lda + gk);
       ra[j] = v;
     }
     const float* Bt = Bp + (long long)tap * g.sTapB;
@@ -361,7 +365,7 @@ __global__ __launch_bounds__(256) void gemm_fast_kernel(GemmArgs g) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = bm + wm * 64 + mi * 32 + acc_row(r, lh);
-        if (row < g.M && col < g.N) {
+        if (row < Mb && col < g.N) {
           float v = acc[mi][ni][r] + bn_v;
           if (g.bias_m) v += g.bias_m[row];
           if (g.alpha_ncols == 0 || col < g.alpha_ncols) v *= g.alpha;
@@ -402,7 +406,7 @@ __device__ __forceinline__ void split4(const f32x4 v, f16x4& hi, f16x4& lo, bool
   }
 }
 
-template <int BM, bool TRANS_B>
+template <int BM, bool TRANS_B, bool RAG = false>   // RAG: rows bounded per batch item (GemmArgs::lens)
 __global__ __launch_bounds__(256) void gemm_split_kernel(GemmArgs g) {
   constexpr int A_BYTES = BM * SROW, B_BYTES = FBN * SROW;       // one plane of one stage
   constexpr int STAGE = 2 * A_BYTES + 2 * B_BYTES;               // hi A, lo A, hi B, lo B
@@ -415,6 +419,10 @@ __global__ __launch_bounds__(256) void gemm_split_kernel(GemmArgs g) {
   const int wm = BM == 128 ? wave >> 1 : 0, wn = BM == 128 ? wave & 1 : wave;
   const int l31 = lane & 31, lh = lane >> 5;
   const int bm = blockIdx.y * BM, bn = blockIdx.x * FBN, bz = blockIdx.z;
+  const int Mb = rag_len<RAG>(g.lens, bz, g.M);   // rows of this batch item; g.M stays the pitch of the grid
+  if constexpr (RAG) {
+    if (bm >= Mb) return;                         // the whole tile lies beyond the item's end: nothing to load, nothing to store
+  }
   const int b2 = g.batch2 > 1 ? g.batch2 : 1;
   const int zo = bz / b2, zi = bz - zo * b2;
   const float* __restrict__ A = g.A + (long long)zo * g.sA + (long long)zi * g.sA2;
@@ -442,7 +450,7 @@ __global__ __launch_bounds__(256) void gemm_split_kernel(GemmArgs g) {
       const int row = idx >> 2, gk = k0 + ((idx & 3) << 2);
       const int gr = bm + row + shift;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (gr >= 0 && gr < g.M && (bm + row) < g.M && gk < g.K) v = *reinterpret_cast<const f32x4*>(A + (long long)gr * g.lda + gk);
+      if (gr >= 0 && gr < Mb && (bm + row) < Mb && gk < g.K) v = *reinterpret_cast<const f32x4*>(A + (long long)gr * g.lda + gk);
       ra[j] = v;
     }
     const float* Bt = Bp + (long long)tap * g.sTapB;
@@ -550,7 +558,7 @@ __global__ __launch_bounds__(256) void gemm_split_kernel(GemmArgs g) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = bm + wm * 64 + mi * 32 + acc_row(r, lh);
-        if (row < g.M && col < g.N) {
+        if (row < Mb && col < g.N) {
           float v = acc[mi][ni][r] * SPLIT_OUT + bn_v;
           if (g.bias_m) v += g.bias_m[row];
           if (g.alpha_ncols == 0 || col < g.alpha_ncols) v *= g.alpha;
@@ -565,23 +573,23 @@ __global__ __launch_bounds__(256) void gemm_split_kernel(GemmArgs g) {
     }
 }
 
-template <int BM, bool TRANS_B>
+template <int BM, bool TRANS_B, bool RAG = false>
 int launch_split(const GemmArgs& g, hipStream_t st) {
   constexpr size_t lds = (size_t)2 * (2 * BM * SROW + 2 * FBN * SROW);
-  hipLaunchKernelGGL((gemm_split_kernel<BM, TRANS_B>), dim3(cdiv(g.N, FBN), cdiv(g.M, BM), g.batch), dim3(256), lds, st, g);
+  hipLaunchKernelGGL((gemm_split_kernel<BM, TRANS_B, RAG>), dim3(cdiv(g.N, FBN), cdiv(g.M, BM), g.batch), dim3(256), lds, st, g);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
 }
 
-template <int BM, int FBK, bool TRANS_B>
+template <int BM, int FBK, bool TRANS_B, bool RAG = false>
 int launch_fast(const GemmArgs& g, hipStream_t st) {
   constexpr size_t lds = (size_t)(2 * BM * (FBK + 4) + 2 * (TRANS_B ? FBN * (FBK + 4) : FBK * FLDN)) * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
-    BSG_HIP(hipFuncSetAttribute((const void*)gemm_fast_kernel<BM, FBK, TRANS_B>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    BSG_HIP(hipFuncSetAttribute((const void*)gemm_fast_kernel<BM, FBK, TRANS_B, RAG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr_set = true;
   }
-  hipLaunchKernelGGL((gemm_fast_kernel<BM, FBK, TRANS_B>), dim3(cdiv(g.N, FBN), cdiv(g.M, BM), g.batch), dim3(256), lds, st, g);
+  hipLaunchKernelGGL((gemm_fast_kernel<BM, FBK, TRANS_B, RAG>), dim3(cdiv(g.N, FBN), cdiv(g.M, BM), g.batch), dim3(256), lds, st, g);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
 }
@@ -651,6 +659,10 @@ int launch_gemm(const GemmArgs& g_in, hipStream_t st) {
   const int force = g.force_form;   // test hook (bsg_gemm_ex): 0 everywhere else
   BSG_REQUIRE(force >= 0 && force <= 5, "gemm: force_form %d outside 0..5", force);
   BSG_REQUIRE(!(force >= 1 && force <= 4) || aligned, "gemm: force_form %d needs a 16-byte aligned problem", force);
+  // ragged: the bounded instantiations exist for what the pitch extractor reaches — the aligned forms, B as [N, K], one batch index
+  BSG_REQUIRE(!g.lens || ((force ? force <= 4 : aligned) && g.trans_b && g.batch2 <= 1),
+              "gemm: lengths are built for gemm_split / gemm_fast with trans_b and no batch2 only (form %s, trans_b=%d, batch2=%d)",
+              (force ? force <= 4 : aligned) ? "aligned" : "gemm_f32", g.trans_b, g.batch2);
   if (force ? force <= 4 : aligned) {
     // 64-row tiles when 128-row tiles would not give every CU two workgroups (e.g. [16000 x 256] outputs: 250 -> 500 workgroups)
     const long long wg128 = (long long)cdiv(g.N, FBN) * cdiv(g.M, 128) * g.batch;
@@ -660,10 +672,12 @@ int launch_gemm(const GemmArgs& g_in, hipStream_t st) {
       const long long wgs = (long long)cdiv(g.N, FBN) * cdiv(g.M, 128) * g.batch;
       const bool sm = force ? force == 1 : wgs < 3 * 256;
       if (g.form_out) *g.form_out = sm ? "gemm_split/64" : "gemm_split/128";
+      if (g.lens) return sm ? launch_split<64, true, true>(g, st) : launch_split<128, true, true>(g, st);
       if (g.trans_b) return sm ? launch_split<64, true>(g, st) : launch_split<128, true>(g, st);
       return sm ? launch_split<64, false>(g, st) : launch_split<128, false>(g, st);
     }
     if (g.form_out) *g.form_out = small ? "gemm_fast/64" : "gemm_fast/128";
+    if (g.lens) return small ? launch_fast<64, 16, true, true>(g, st) : launch_fast<128, 16, true, true>(g, st);
     if (g.trans_b) return small ? launch_fast<64, 16, true>(g, st) : launch_fast<128, 16, true>(g, st);
     return small ? launch_fast<64, 16, false>(g, st) : launch_fast<128, 16, false>(g, st);
   }

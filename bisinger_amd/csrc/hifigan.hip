@@ -1774,7 +1774,7 @@ struct bsg_hifigan {
   bool h2_ok = true;
   unsigned short* planes = nullptr;       // activation planes of the gemm_h2w products (hi, then lo)
   size_t planes_cap = 0;                  // halfs
-  int* lens = nullptr;                    // ragged forwards: the rows' frame counts on the device, written by set_lens_kernel launches of the call itself
+  int* lens = nullptr;                    // ragged forwards: the rows' frame counts on the device, written by launches of the call itself (lens_fill)
   size_t lens_cap = 0;
   std::string path;                       // the launches of the last forward (bsg_hifigan_last_path)
   std::vector<HgStep> steps;              // room for the plan of a forward (plan_hifigan), sized at create
@@ -2313,27 +2313,12 @@ static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, 
   return BSG_OK;
 }
 
-// The rows' frame counts reach the kernels through a handle-owned device array that the call itself fills: launches of set_lens_kernel carry
-// up to 256 counts each in their ARGUMENTS, so a captured forward replays the same counts and no host memory is read after the call returns.
-struct LensChunk { int n[256]; };
-__global__ void set_lens_kernel(LensChunk c, int* __restrict__ dst, int rows) {
-  if ((int)threadIdx.x < rows) dst[threadIdx.x] = c.n[threadIdx.x];
-}
-// checks lengths_host (1 .. T each) and enqueues the fill; nothing is enqueued when a length is refused
+// The rows' frame counts reach the kernels through a handle-owned device array that the call itself fills (bsg_ws.h, lens_fill): checks
+// lengths_host (1 .. T each) and enqueues the fill; nothing is enqueued when a length is refused
 static int hifigan_set_lens(bsg_hifigan* h, const int32_t* lengths_host, int B, int T, const char* who, hipStream_t st) {
-  BSG_REQUIRE(lengths_host, "%s: lengths_host is null", who);
-  BSG_REQUIRE(B > 0 && B <= 65535 && T > 0, "%s: bad argument (B=%d T=%d)", who, B, T);
-  for (int b = 0; b < B; ++b)
-    BSG_REQUIRE(lengths_host[b] >= 1 && lengths_host[b] <= T, "%s: lengths[%d]=%d outside 1..T=%d", who, b, lengths_host[b], T);
+  TRY(lens_check(lengths_host, B, T, who));
   TRY(grow(h, &h->lens_cap, (size_t)B, st));
-  for (int b0 = 0; b0 < B; b0 += 256) {
-    LensChunk c{};
-    const int rows = B - b0 < 256 ? B - b0 : 256;
-    for (int r = 0; r < rows; ++r) c.n[r] = lengths_host[b0 + r];
-    hipLaunchKernelGGL(set_lens_kernel, dim3(1), dim3(256), 0, st, c, h->lens + b0, rows);
-    BSG_LAUNCH_CHECK();
-  }
-  return BSG_OK;
+  return lens_fill(h->lens, lengths_host, B, st);
 }
 
 static int hifigan_forward_plain(bsg_hifigan* h, const float* mel, const int32_t* lengths_host, float* wav, int32_t B, int32_t T, void* stream,

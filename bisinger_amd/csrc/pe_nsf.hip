@@ -28,10 +28,23 @@ __device__ __forceinline__ float wsum(float v) {
   return v;
 }
 
+// Ragged batches (bsg_pitchext_forward_ragged): `lens` (device, one frame count per batch row; see rag_len) bounds row b by lens[b] while the
+// pitch of every tensor stays T.  Every kernel of the extractor takes the choice as a template flag RAG; its launch and grid are those of
+// the padded call, and the RAG form loops over a row as the B = 1, T = lens[b] launch does, so an element's sum order is the row-alone
+// call's.  frame_in_row: for the kernels with one wave (or thread) per frame of [B x T], whether that frame lies inside its row.
+template <bool RAG>
+__device__ __forceinline__ bool frame_in_row(const int* __restrict__ lens, long long row, int T) {
+  if constexpr (!RAG) return true;
+  const int b = (int)(row / T);
+  return (int)(row - (long long)b * T) < lens[b];
+}
+
 // keep[row] = (sum_j |x[row][j]| != 0)                     (pe.py:29, :142)
-__global__ void row_keep_kernel(const float* __restrict__ x, float* __restrict__ keep, long long rows, int width) {
+template <bool RAG>
+__global__ void row_keep_kernel(const float* __restrict__ x, float* __restrict__ keep, long long rows, int width, const int* __restrict__ lens,
+                                int T) {
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
+  if (row >= rows || !frame_in_row<RAG>(lens, row, T)) return;
   const int lane = threadIdx.x & 63;
   float s = 0.f;
   for (int j = lane; j < width; j += 64) s += fabsf(x[row * width + j]);
@@ -50,11 +63,14 @@ __global__ void bn_affine_kernel(const float* w, const float* b, const float* me
 }
 
 // y = res + relu(GroupNorm_{16 ch/group}(h))   h, res, y: [B][T][H]; statistics over (T x 16 channels)   (pe.py:57,71-77,111)
+// RAG: over (lens[b] x 16 channels), frames [lens[b], T) neither read nor written
+template <bool RAG>
 __global__ __launch_bounds__(256) void groupnorm_res_kernel(const float* __restrict__ h, const float* __restrict__ w,
                                                             const float* __restrict__ b, const float* __restrict__ res,
-                                                            float* __restrict__ y, int T, float eps) {
+                                                            float* __restrict__ y, int T, float eps, const int* __restrict__ lens) {
   __shared__ float red[4];
   const int g = blockIdx.x, bb = blockIdx.y, tid = threadIdx.x;
+  const int Tb = rag_len<RAG>(lens, bb, T);
   const float* hp = h + (long long)bb * T * H + g * 16;
   auto block_sum = [&](float v) {
     v = wsum(v);
@@ -64,20 +80,20 @@ __global__ __launch_bounds__(256) void groupnorm_res_kernel(const float* __restr
     return (red[0] + red[1]) + (red[2] + red[3]);
   };
   // element e of the group = (t = e / 4, float4 e % 4)
-  const long long n4 = (long long)T * 4;
+  const long long n4 = (long long)Tb * 4;
   float s = 0.f;
   for (long long e = tid; e < n4; e += 256) {
     const f32x4 v = *reinterpret_cast<const f32x4*>(hp + (e >> 2) * H + (e & 3) * 4);
     s += (v[0] + v[1]) + (v[2] + v[3]);
   }
-  const float mean = block_sum(s) / (float)(T * 16);
+  const float mean = block_sum(s) / (float)(Tb * 16);
   float q = 0.f;
   for (long long e = tid; e < n4; e += 256) {
     const f32x4 v = *reinterpret_cast<const f32x4*>(hp + (e >> 2) * H + (e & 3) * 4);
     const float d0 = v[0] - mean, d1 = v[1] - mean, d2 = v[2] - mean, d3 = v[3] - mean;
     q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
   }
-  const float rstd = 1.0f / sqrtf(block_sum(q) / (float)(T * 16) + eps);
+  const float rstd = 1.0f / sqrtf(block_sum(q) / (float)(Tb * 16) + eps);
   for (long long e = tid; e < n4; e += 256) {
     const long long off = (long long)bb * T * H + (e >> 2) * H + g * 16 + (e & 3) * 4;
     const f32x4 v = *reinterpret_cast<const f32x4*>(h + off);
@@ -92,23 +108,27 @@ __global__ __launch_bounds__(256) void groupnorm_res_kernel(const float* __restr
 }
 
 // positions = cumsum(x[...,0] != 0) * (x[...,0] != 0)  (one wave per utterance), then x += alpha * table[pos]  (tts_modules.py:239-240)
-__global__ void positions_kernel(const float* __restrict__ x, int* __restrict__ pos, int T) {
+// RAG: the count stops at the row's end, frames [lens[b], T) neither read nor written
+template <bool RAG>
+__global__ void positions_kernel(const float* __restrict__ x, int* __restrict__ pos, int T, const int* __restrict__ lens) {
   const int b = blockIdx.x, lane = threadIdx.x;
+  const int Tb = rag_len<RAG>(lens, b, T);
   int carry = 0;
-  for (int t0 = 0; t0 < T; t0 += 64) {
+  for (int t0 = 0; t0 < Tb; t0 += 64) {
     const int t = t0 + lane;
     bool nz = false;
-    if (t < T) nz = x[((long long)b * T + t) * H] != 0.f;
+    if (t < Tb) nz = x[((long long)b * T + t) * H] != 0.f;
     const unsigned long long bal = __ballot(nz);
     const int pre = __popcll(bal & ((1ull << lane) - 1ull)) + (nz ? 1 : 0);
-    if (t < T) pos[(long long)b * T + t] = nz ? carry + pre : 0;
+    if (t < Tb) pos[(long long)b * T + t] = nz ? carry + pre : 0;
     carry += __popcll(bal);
   }
 }
+template <bool RAG>
 __global__ void add_positions_kernel(float* __restrict__ x, const int* __restrict__ pos, const float* __restrict__ table,
-                                     const float* __restrict__ alpha, long long rows, int n_pos) {
+                                     const float* __restrict__ alpha, long long rows, int n_pos, const int* __restrict__ lens, int T) {
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
+  if (row >= rows || !frame_in_row<RAG>(lens, row, T)) return;
   const int lane = threadIdx.x & 63;
   int p = pos[row];
   p = p < n_pos ? p : n_pos - 1;
@@ -120,10 +140,11 @@ __global__ void add_positions_kernel(float* __restrict__ x, const int* __restric
   reinterpret_cast<f32x4*>(x + row * H)[lane] = v;
 }
 
+template <bool RAG>
 __global__ void layernorm256_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
-                                    float* __restrict__ y, long long rows, float eps) {
+                                    float* __restrict__ y, long long rows, float eps, const int* __restrict__ lens, int T) {
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
+  if (row >= rows || !frame_in_row<RAG>(lens, row, T)) return;
   const int lane = threadIdx.x & 63;
   const f32x4 v = reinterpret_cast<const f32x4*>(x + row * H)[lane];
   const float mean = wsum(v[0] + v[1] + v[2] + v[3]) * (1.0f / H);
@@ -136,10 +157,16 @@ __global__ void layernorm256_kernel(const float* __restrict__ x, const float* __
 }
 
 // f0 = 2^pred0, zeroed where unvoiced (pred1 > 0) or padded          (pitch_utils.py:63-76, pe.py:142-148)
-__global__ void f0_denorm_kernel(const float* __restrict__ pred, const float* __restrict__ keep, float* __restrict__ f0,
-                                 long long rows, int use_uv) {
+// RAG: frames [lens[b], T) of a row, which no launch before this one wrote, are stored as 0 in pred and in f0 and read nowhere
+template <bool RAG>
+__global__ void f0_denorm_kernel(float* __restrict__ pred, const float* __restrict__ keep, float* __restrict__ f0, long long rows,
+                                 int use_uv, const int* __restrict__ lens, int T) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= rows) return;
+  if (!frame_in_row<RAG>(lens, i, T)) {
+    pred[2 * i] = pred[2 * i + 1] = f0[i] = 0.f;
+    return;
+  }
   float v = exp2f(pred[2 * i]);
   if (use_uv && pred[2 * i + 1] > 0.f) v = 0.f;
   if (keep[i] == 0.f) v = 0.f;
@@ -316,14 +343,18 @@ struct bsg_pitchext {
   size_t cap = 0;
   float *a = nullptr, *b = nullptr, *c = nullptr, *keep = nullptr, *pred = nullptr;
   int* pos = nullptr;
+  int* lens = nullptr;   // ragged forwards: the rows' frame counts on the device, written by launches of the call itself (lens_fill)
+  size_t lens_cap = 0;
 };
 
-// the handle's shape-sized workspaces (bsg_ws.h), all of cap = B x T rows: the forward grows them, destroy frees them
+// the handle's shape-sized workspaces (bsg_ws.h): cap = B x T rows, lens_cap = B rows (not poisoned: the call itself fills them).  The
+// forward grows them, destroy frees them, the poison hook fills the first six
 static std::vector<WsBuf> ws_table(bsg_pitchext* h) {
   const size_t f = sizeof(float);
   return {
-      {&h->cap, (void**)&h->a, H * f}, {&h->cap, (void**)&h->b, H * f},        {&h->cap, (void**)&h->c, H * f},
-      {&h->cap, (void**)&h->keep, f},  {&h->cap, (void**)&h->pred, 2 * f},     {&h->cap, (void**)&h->pos, sizeof(int)},
+      {&h->cap, (void**)&h->a, H * f, 0, WS_POISON},  {&h->cap, (void**)&h->b, H * f, 0, WS_POISON},     {&h->cap, (void**)&h->c, H * f, 0, WS_POISON},
+      {&h->cap, (void**)&h->keep, f, 0, WS_POISON},   {&h->cap, (void**)&h->pred, 2 * f, 0, WS_POISON},  {&h->cap, (void**)&h->pos, sizeof(int), 0, WS_POISON},
+      {&h->lens_cap, (void**)&h->lens, sizeof(int)},
   };
 }
 static int pe_copy(bsg_pitchext* h, float** dst, const void* src, size_t n, hipStream_t st) {
@@ -409,74 +440,107 @@ extern "C" int bsg_pitchext_create(bsg_pitchext** out, const bsg_pitchext_cfg* c
   return BSG_OK;
 }
 
-static int pe_linear(const float* X, const float* W, const float* bias, float* Y, long long rows, int N, int K, const float* rowscale,
-                     hipStream_t st) {
+// a 1x1 projection over [B][T][K] rows.  Padded (lens null): one problem of B x T rows.  Ragged: the batched form (M = T, batch = B), so that
+// the one row bound of launch_gemm covers it — an element's sum order does not depend on its tile's place, so all lengths = T gives the same bits
+static int pe_linear(const float* X, const float* W, const float* bias, float* Y, int B, int T, int N, int K, const float* rowscale,
+                     const int* lens, hipStream_t st) {
   GemmArgs g{};
-  g.A = X; g.B = W; g.C = Y; g.M = (int)rows; g.N = N; g.K = K; g.lda = K; g.ldb = K; g.ldc = N; g.trans_b = 1; g.taps = 1;
+  g.A = X; g.B = W; g.C = Y; g.M = lens ? T : B * T; g.N = N; g.K = K; g.lda = K; g.ldb = K; g.ldc = N; g.trans_b = 1; g.taps = 1;
   g.bias_n = bias; g.alpha = 1.f; g.rowscale = rowscale; g.batch = 1;
+  if (lens) { g.batch = B; g.sA = (long long)T * K; g.sC = (long long)T * N; g.sRS = T; g.lens = lens; }
   return launch_gemm(g, st);
 }
 static int pe_conv_gemm(const float* X, const float* Wt, const float* bias, float* Y, int B, int T, int Cin, int ks, int act,
-                        const float* ps, const float* pb, const float* rowscale, hipStream_t st) {
+                        const float* ps, const float* pb, const float* rowscale, const int* lens, hipStream_t st) {
   GemmArgs g{};
   g.A = X; g.B = Wt; g.C = Y; g.M = T; g.N = H; g.K = Cin; g.lda = Cin; g.ldb = Cin; g.ldc = H; g.trans_b = 1;
   g.taps = ks; g.tap_shift0 = -(ks / 2); g.sTapB = (long long)H * Cin; g.bias_n = bias; g.alpha = 1.f; g.act = act;
   g.post_scale_n = ps; g.post_shift_n = pb; g.rowscale = rowscale; g.sRS = T; g.batch = B;
-  g.sA = (long long)T * Cin; g.sC = (long long)T * H;
+  g.sA = (long long)T * Cin; g.sC = (long long)T * H; g.lens = lens;
   return launch_gemm(g, st);
 }
 
-extern "C" int bsg_pitchext_forward(bsg_pitchext* h, const float* mel, float* pitch_pred, float* f0, int32_t B, int32_t T, void* stream) {
-  GuardScope guard_scope(h ? &h->guard : nullptr);
-  BSG_REQUIRE(h && mel && f0 && B > 0 && T > 0 && T < h->cfg.n_pos, "pitchext_forward: bad argument (T=%d, table %d rows)", T, h ? h->cfg.n_pos : 0);
-  hipStream_t st = (hipStream_t)stream;
+// the forward, padded (RAG = false, lens null) or ragged (lens = h->lens, filled by the caller on `st`): the same launches and grids
+template <bool RAG>
+static int pe_run(bsg_pitchext* h, const float* mel, float* pitch_pred, float* f0, int B, int T, const int* lens, hipStream_t st) {
   const long long rows = (long long)B * T;
-  if ((size_t)rows > h->cap) TRY(ws_grow(ws_table(h), "pitchext", &h->cap, (size_t)rows, st));
   const dim3 rg(cdiv(rows, 4)), rb(256);
-  hipLaunchKernelGGL(row_keep_kernel, rg, rb, 0, st, mel, h->keep, rows, h->cfg.n_mel);
+  hipLaunchKernelGGL(row_keep_kernel<RAG>, rg, rb, 0, st, mel, h->keep, rows, h->cfg.n_mel, lens, T);
   BSG_LAUNCH_CHECK();
   // Prenet: 3 x [conv k5 -> ReLU -> BatchNorm(eval) -> * keep], out_proj * keep        (pe.py:24-42)
   const float* x = mel;
   float* bufs[2] = {h->a, h->b};
   for (int l = 0; l < 3; ++l) {
     TRY(pe_conv_gemm(x, h->pre_w[l], h->pre_b[l], bufs[l & 1], B, T, l == 0 ? h->cfg.n_mel : H, 5, ACT_RELU, h->pre_scale[l],
-                     h->pre_shift[l], h->keep, st));
+                     h->pre_shift[l], h->keep, lens, st));
     x = bufs[l & 1];
   }
-  TRY(pe_linear(x, h->pre_out_w, h->pre_out_b, h->b, rows, H, H, h->keep, st));      // x = a (l=2 -> bufs[0]); out -> b
+  TRY(pe_linear(x, h->pre_out_w, h->pre_out_b, h->b, B, T, H, H, h->keep, lens, st));      // x = a (l=2 -> bufs[0]); out -> b
   float* cur = h->b;
   if (h->cfg.conv_layers > 0) {
     // ConvStacks: in_proj, n x (x + relu(GroupNorm(conv(x)))), out_proj                   (pe.py:99-117)
-    TRY(pe_linear(cur, h->enc_in_w, h->enc_in_b, h->a, rows, H, H, nullptr, st));
+    TRY(pe_linear(cur, h->enc_in_w, h->enc_in_b, h->a, B, T, H, H, nullptr, lens, st));
     float* xx = h->a;
     float* other = h->b;
     for (int l = 0; l < h->cfg.conv_layers; ++l) {
-      TRY(pe_conv_gemm(xx, h->enc_w[l], h->enc_b[l], h->c, B, T, H, 5, ACT_NONE, nullptr, nullptr, nullptr, st));
-      hipLaunchKernelGGL(groupnorm_res_kernel, dim3(H / 16, B), dim3(256), 0, st, (const float*)h->c, h->enc_gw[l], h->enc_gb[l],
-                         (const float*)xx, other, T, 1e-5f);
+      TRY(pe_conv_gemm(xx, h->enc_w[l], h->enc_b[l], h->c, B, T, H, 5, ACT_NONE, nullptr, nullptr, nullptr, lens, st));
+      hipLaunchKernelGGL(groupnorm_res_kernel<RAG>, dim3(H / 16, B), dim3(256), 0, st, (const float*)h->c, h->enc_gw[l], h->enc_gb[l],
+                         (const float*)xx, other, T, 1e-5f, lens);
       BSG_LAUNCH_CHECK();
       float* t = xx; xx = other; other = t;
     }
-    TRY(pe_linear(xx, h->enc_out_w, h->enc_out_b, other, rows, H, H, nullptr, st));
+    TRY(pe_linear(xx, h->enc_out_w, h->enc_out_b, other, B, T, H, H, nullptr, lens, st));
     cur = other;
   }
   // PitchPredictor                                                                        (tts_modules.py:233-247)
-  hipLaunchKernelGGL(positions_kernel, dim3(B), dim3(64), 0, st, (const float*)cur, h->pos, T);
+  hipLaunchKernelGGL(positions_kernel<RAG>, dim3(B), dim3(64), 0, st, (const float*)cur, h->pos, T, lens);
   BSG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(add_positions_kernel, rg, rb, 0, st, cur, (const int*)h->pos, h->table, h->alpha, rows, h->cfg.n_pos);
+  hipLaunchKernelGGL(add_positions_kernel<RAG>, rg, rb, 0, st, cur, (const int*)h->pos, h->table, h->alpha, rows, h->cfg.n_pos, lens, T);
   BSG_LAUNCH_CHECK();
   float* nxt = cur == h->a ? h->b : h->a;
   for (int l = 0; l < h->cfg.predictor_layers; ++l) {
-    TRY(pe_conv_gemm(cur, h->pp_w[l], h->pp_b[l], h->c, B, T, H, h->cfg.predictor_kernel, ACT_RELU, nullptr, nullptr, nullptr, st));
-    hipLaunchKernelGGL(layernorm256_kernel, rg, rb, 0, st, (const float*)h->c, h->pp_lw[l], h->pp_lb[l], nxt, rows, 1e-12f);
+    TRY(pe_conv_gemm(cur, h->pp_w[l], h->pp_b[l], h->c, B, T, H, h->cfg.predictor_kernel, ACT_RELU, nullptr, nullptr, nullptr, lens, st));
+    hipLaunchKernelGGL(layernorm256_kernel<RAG>, rg, rb, 0, st, (const float*)h->c, h->pp_lw[l], h->pp_lb[l], nxt, rows, 1e-12f, lens, T);
     BSG_LAUNCH_CHECK();
     float* t = cur; cur = nxt; nxt = t;
   }
   float* pred = pitch_pred ? pitch_pred : h->pred;
-  TRY(pe_linear(cur, h->pp_lin_w, h->pp_lin_b, pred, rows, 2, H, nullptr, st));
-  hipLaunchKernelGGL(f0_denorm_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, st, (const float*)pred, h->keep, f0, rows, h->cfg.use_uv);
+  TRY(pe_linear(cur, h->pp_lin_w, h->pp_lin_b, pred, B, T, 2, H, nullptr, lens, st));
+  hipLaunchKernelGGL(f0_denorm_kernel<RAG>, dim3(cdiv(rows, 256)), dim3(256), 0, st, pred, (const float*)h->keep, f0, rows, h->cfg.use_uv, lens, T);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
+}
+
+static int pe_forward_any(bsg_pitchext* h, const float* mel, const int32_t* lengths_host, float* pitch_pred, float* f0, int32_t B, int32_t T,
+                          void* stream, const char* who) {
+  GuardScope guard_scope(h ? &h->guard : nullptr);
+  BSG_REQUIRE(h && mel && f0 && B > 0 && T > 0 && T < h->cfg.n_pos, "%s: bad argument (T=%d, table %d rows)", who, T, h ? h->cfg.n_pos : 0);
+  hipStream_t st = (hipStream_t)stream;
+  if (lengths_host) TRY(lens_check(lengths_host, B, T, who));      // refused before anything is grown, enqueued or written
+  const size_t rows = (size_t)B * T;
+  if (rows > h->cap) TRY(ws_grow(ws_table(h), "pitchext", &h->cap, rows, st));
+  if (!lengths_host) return pe_run<false>(h, mel, pitch_pred, f0, B, T, nullptr, st);
+  if ((size_t)B > h->lens_cap) TRY(ws_grow(ws_table(h), "pitchext", &h->lens_cap, (size_t)B, st));
+  TRY(lens_fill(h->lens, lengths_host, B, st));
+  return pe_run<true>(h, mel, pitch_pred, f0, B, T, h->lens, st);
+}
+
+extern "C" int bsg_pitchext_forward(bsg_pitchext* h, const float* mel, float* pitch_pred, float* f0, int32_t B, int32_t T, void* stream) {
+  return pe_forward_any(h, mel, nullptr, pitch_pred, f0, B, T, stream, "pitchext_forward");
+}
+
+// Ragged batches: row b runs at lengths_host[b] frames (1 .. T) inside the padded tensors — the launches of the padded call at (B, T), each
+// bounding row b by lengths[b]; workgroups and waves beyond a row's end leave before their first load (include/bisinger_hip.h, ABI v19).
+extern "C" int bsg_pitchext_forward_ragged(bsg_pitchext* h, const float* mel, const int32_t* lengths_host, float* pitch_pred, float* f0,
+                                           int32_t B, int32_t T, void* stream) {
+  BSG_REQUIRE(lengths_host, "pitchext_forward_ragged: lengths_host is null");
+  return pe_forward_any(h, mel, lengths_host, pitch_pred, f0, B, T, stream, "pitchext_forward_ragged");
+}
+
+// test hook: NaN bytes into a / b / c / keep / pred / pos (the lengths array is the call's own and stays)
+extern "C" int bsg_pitchext_debug_poison_workspace(bsg_pitchext* h, void* stream) {
+  BSG_REQUIRE(h, "pitchext_debug_poison_workspace: null handle");
+  return ws_poison(ws_table(h), (hipStream_t)stream);
 }
 
 extern "C" int bsg_nsf_source(const float* f0, const float* rand_ini, const float* noise, const float* lin_w, const float* lin_b, float* har,

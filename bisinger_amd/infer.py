@@ -235,13 +235,16 @@ class DiffSingerE2EInfer(BaseSVSInfer):
         new[1:] = (d[1:] != d[:-1]) | (p[1:] != p[:-1])
         return int(np.ceil(d[new].sum() * hparams['audio_sample_rate'] / hparams['hop_size']))
 
-    def _generate_wavs(self, items, seed, ragged=False, denoise_c=None, ragged_vocoder=False):
+    def _generate_wavs(self, items, seed, ragged=False, denoise_c=None, ragged_vocoder=False, ragged_pitch=False):
         """One padded batch -> (list of trimmed waveforms, frames per item, padded frame count T).  ``ragged``: the mel decoder runs every
         row at its own length (GaussianDiffusion.forward(ragged=True)).  ``ragged_vocoder``: the HiFi-GAN generator (plain or NSF) runs every
         row at its own length too (HifiGanGenerator.forward(lengths=)), as the reference vocodes each utterance alone; False: it runs the
-        padded batch, whose zero frames beyond a row's end reach back into the row's last ~9 frames.  The pitch extractor still runs the
-        padded mel in both cases: the vocoder's contract is "given this mel and this f0".  ``denoise_c`` > 0: the padded batch of waveforms
-        goes through ONE launch of the spectral post-filter (vocoders.denoise), every row at its own length."""
+        padded batch, whose zero frames beyond a row's end reach back into the row's last ~9 frames.  ``ragged_pitch``: the pitch extractor
+        runs every row at its own length (PitchExtractor.forward(lengths=)), as the reference extracts each utterance's f0 alone; False: it
+        runs the padded mel, whose padding enters GroupNorm's statistics of every shorter row.  ``denoise_c`` > 0: the padded batch of
+        waveforms goes through ONE launch of the spectral post-filter (vocoders.denoise), every row at its own length."""
+        if ragged_pitch and not hparams.get('pe_enable'):      # refused before any model runs
+            raise ValueError('forward_batch(ragged_pitch=True): there is no pitch extractor to run (pe_enable is off)')
         if ragged_vocoder:      # refused before any model runs
             from .hifigan import HifiGanGenerator
             name = str(hparams.get('vocoder', ''))
@@ -254,7 +257,10 @@ class DiffSingerE2EInfer(BaseSVSInfer):
         hop = int(np.prod(self.vocoder.h['upsample_rates']))
         n_frames = (mel2ph > 0).sum(-1).tolist()
         if hparams.get('use_nsf'):                                   # the shipped M4Singer set-up: PitchExtractor f0 -> NSF source
-            f0 = self.pe(mel)['f0_denorm_pred'] if hparams.get('pe_enable') else output.get('f0_denorm')
+            if hparams.get('pe_enable'):
+                f0 = self.pe(mel, **({'lengths': n_frames} if ragged_pitch else {}))['f0_denorm_pred']
+            else:
+                f0 = output.get('f0_denorm')
             assert f0 is not None, 'use_nsf needs an f0: enable pe_enable (a-*.py:629-632)'
             vkw = {'lengths': n_frames} if ragged_vocoder else {}
             wav = self.vocoder(mel.transpose(2, 1), f0, seed=int(hparams.get('seed', 1234) if seed is None else seed), **vkw)[:, 0]
@@ -265,7 +271,8 @@ class DiffSingerE2EInfer(BaseSVSInfer):
             wav = denoise(wav.contiguous(), v=denoise_c, lengths=[n * hop for n in n_frames])
         return [wav[i, :n * hop].cpu().numpy() for i, n in enumerate(n_frames)], n_frames, int(mel.shape[1])
 
-    def forward_batch(self, items, seed=None, max_frames=None, max_sentences=None, ragged=False, denoise_c=None, ragged_vocoder=False):
+    def forward_batch(self, items, seed=None, max_frames=None, max_sentences=None, ragged=False, denoise_c=None, ragged_vocoder=False,
+                      ragged_pitch=False):
         """Batched generation: list of items -> list of 1-D waveforms (in the order given), each trimmed to its utterance.
 
         With ``max_frames`` (budget on padded frames per batch: rows x longest row) and/or ``max_sentences`` the items are
@@ -288,8 +295,13 @@ class DiffSingerE2EInfer(BaseSVSInfer):
         ``ragged_vocoder=True`` (with ``ragged`` on or off): the HiFi-GAN vocoder, plain or NSF, runs every row of a bucket at its own length
         (``HifiGanGenerator.forward(lengths=)``): each waveform is what the vocoder gives for that row's mel alone, as the reference vocodes
         (vocoders/hifigan.py:55-69), instead of carrying the padded batch's zero frames in its last ~9 frames; workgroups beyond a row's
-        end do no work.  The pitch extractor still runs the padded mel.  With a ``pwg`` vocoder: NotImplementedError.  False (default):
-        the padded vocoder batch, every result as before."""
+        end do no work.  With a ``pwg`` vocoder: NotImplementedError.  False (default): the padded vocoder batch, every result as before.
+
+        ``ragged_pitch=True`` (with ``ragged`` and ``ragged_vocoder`` on or off; needs ``pe_enable``, else ValueError before any model runs):
+        the pitch extractor runs every row of a bucket at its own length (``PitchExtractor.forward(lengths=)``): the f0 that drives the NSF
+        source is what the extractor gives for that row's mel alone, instead of depending on how much padding the bucket gave the row
+        (GroupNorm's statistics run over a row's frames; in the padded batch, over its padding too).  False (default): the padded mel,
+        every result as before."""
         est = [self.estimate_frames(it) for it in items]
         if ragged and max_frames is not None:
             raise ValueError('forward_batch(ragged=True): buckets by max_sentences only; max_frames budgets padded frames')
@@ -300,7 +312,7 @@ class DiffSingerE2EInfer(BaseSVSInfer):
         wavs, frames = [None] * len(items), [0] * len(items)
         padded = groups = tiles = 0
         for b in buckets:
-            w, nf, T = self._generate_wavs([items[i] for i in b], seed, ragged, denoise_c, ragged_vocoder)
+            w, nf, T = self._generate_wavs([items[i] for i in b], seed, ragged, denoise_c, ragged_vocoder, ragged_pitch)
             padded += T * len(b)
             if ragged:
                 from .diffnet import ragged_plan

@@ -3,7 +3,7 @@
 Used by the inference harness when ``pe_enable`` is set to feed the NSF vocoder (a-*.py:600-603, :629-630).
 Same module tree / ``state_dict`` (59 entries) as the reference; parameters only, the arithmetic is ``bsg_pitchext_*``.
 """
-from ctypes import POINTER, byref, c_void_p, cast
+from ctypes import POINTER, byref, c_int32, c_void_p, cast
 
 import torch
 import torch.nn as nn
@@ -123,12 +123,29 @@ class PitchExtractor(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         except Exception:
             pass
 
-    @torch.no_grad()
-    def forward(self, mel_input=None):
-        """mel [B,T,80] -> {'pitch_pred': [B,T,2], 'f0_denorm_pred': [B,T]}   (pe.py:136-149)."""
-        return _lib.range_guarded(lambda: self._forward(mel_input), 'PitchExtractor.forward', device=self, owners=(self,))
+    def poison_workspace(self):
+        """Test hook (bsg_pitchext_debug_poison_workspace): NaN bytes into every shape-sized buffer of the handle."""
+        if self._h is not None:
+            _lib.check(_lib.load().bsg_pitchext_debug_poison_workspace(self._h, _lib.stream_ptr()), 'bsg_pitchext_debug_poison_workspace')
 
-    def _forward(self, mel_input):
+    @torch.no_grad()
+    def forward(self, mel_input=None, lengths=None):
+        """mel [B,T,80] -> {'pitch_pred': [B,T,2], 'f0_denorm_pred': [B,T]}   (pe.py:136-149).
+
+        ``lengths`` (list or tensor of B ints, 1 <= lengths[b] <= T): a ragged batch — row b runs at its own length, as the reference
+        extracts the pitch of each utterance alone: ``pitch_pred[b, :lengths[b]]`` and ``f0_denorm_pred[b, :lengths[b]]`` are the extractor
+        applied to ``mel_input[b:b+1, :lengths[b]]``, the rest of the row is 0, and nothing at or beyond a row's end is read (GroupNorm's
+        statistics, the convolutions' padding and the predictor's positions all end with the row).  ``None``: the padded call, every row
+        at T frames, padding included."""
+        if lengths is not None:      # the count is checked before anything touches the GPU; the values by the library, before it enqueues anything
+            B = int(mel_input.shape[0])
+            lengths = [int(v) for v in (lengths.tolist() if hasattr(lengths, 'tolist') else lengths)]
+            if len(lengths) != B:
+                raise _lib.BsgError(f'PitchExtractor.forward: lengths has {len(lengths)} entries for a batch of {B} rows')
+        # the guard's repeat (an operand beyond the fp16 range of the split-fp16 GEMMs) runs the same call, ragged or not, on the fp32 matrix pipe
+        return _lib.range_guarded(lambda: self._forward(mel_input, lengths), 'PitchExtractor.forward', device=self, owners=(self,))
+
+    def _forward(self, mel_input, lengths=None):
         h = self.handle()
         mel = mel_input.contiguous().float()
         B, T, M = mel.shape
@@ -136,7 +153,12 @@ class PitchExtractor(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
             raise _lib.BsgError(f'T={T} exceeds the position table ({self._n_pos})')
         pred = torch.empty(B, T, 2, device=mel.device)
         f0 = torch.empty(B, T, device=mel.device)
+        lib = _lib.load()
         with torch.cuda.device(mel.device):
-            _lib.check(_lib.load().bsg_pitchext_forward(h, _lib.ptr(mel), _lib.ptr(pred), _lib.ptr(f0), B, T, _lib.stream_ptr()),
-                       'bsg_pitchext_forward')
+            if lengths is not None:
+                _lib.check(lib.bsg_pitchext_forward_ragged(h, _lib.ptr(mel), (c_int32 * B)(*lengths), _lib.ptr(pred), _lib.ptr(f0), B, T,
+                                                           _lib.stream_ptr()), 'bsg_pitchext_forward_ragged')
+            else:
+                _lib.check(lib.bsg_pitchext_forward(h, _lib.ptr(mel), _lib.ptr(pred), _lib.ptr(f0), B, T, _lib.stream_ptr()),
+                           'bsg_pitchext_forward')
         return {'pitch_pred': pred, 'f0_denorm_pred': f0}

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define BSG_ABI_VERSION 18
+#define BSG_ABI_VERSION 19
 
 #define BSG_OK 0
 #define BSG_EINVAL (-22)  /* bad argument / shape the kernels do not support            */
@@ -533,6 +533,30 @@ int bsg_pitchext_create(bsg_pitchext** out, const bsg_pitchext_cfg* cfg, const v
                         const float* pos_table, void* stream);
 void bsg_pitchext_destroy(bsg_pitchext* h);
 int bsg_pitchext_forward(bsg_pitchext* h, const float* mel, float* pitch_pred, float* f0, int32_t B, int32_t T, void* stream);
+
+/* ABI v19: ragged batches through the pitch extractor — every row at its own length inside the padded tensors, worded after
+ * bsg_hifigan_forward_ragged.  mel [B,T,n_mel], lengths_host: B frame counts on the HOST, 1 <= lengths_host[b] <= T (read before the call
+ * returns; they travel in kernel arguments into a handle-owned device array, so a captured forward replays them).  With n_b = lengths_host[b]:
+ *   pitch_pred[b, :n_b] and f0[b, :n_b] are the extractor applied to mel[b, :n_b] alone (B = 1, T = n_b) — what the reference, which vocodes
+ *                       every utterance alone, computes: GroupNorm's statistics run over n_b x 16, the convolutions see zeros beyond n_b,
+ *                       the predictor's positions stop counting at n_b.  They depend on row b alone.  Frames inside a row whose mel is
+ *                       exactly 0 keep the reference's `keep` mask (pe.py:29, :142), as in the padded call;
+ *   pitch_pred[b, n_b:] and f0[b, n_b:] are written as 0;
+ *   nothing at or beyond a row's end is read: not the mel (which may hold NaN there), not the workspaces of an earlier call.  The 1x1
+ *                       projections are bounded like the convolutions, so a NaN tail raises no range event of the split-fp16 GEMMs.
+ * The launches are those of the padded call at (B, T), and so are the grids and GEMM forms of the convolutions and row kernels; the 1x1
+ * projections are issued as B problems of T rows (B x ceil(T / tile) row tiles instead of ceil(B T / tile); the form by the same rule on that
+ * count) so that one row bound serves every product.  An element's sum order depends on neither the tile height nor the tile's place, and
+ * each ragged kernel walks a row as the B = 1, T = n_b launch does: all lengths = T gives the padded call's result bit for bit, and row b
+ * equals the row-alone call bit for bit.  A workgroup (of the row kernels: a wave) whose first frame lies beyond its row's end returns
+ * before its first load.
+ * lengths_host NULL ("lengths_host is null") or a length outside 1..T ("lengths[b]=.. outside 1..T=..", naming the row): BSG_EINVAL before
+ * anything is enqueued or written. */
+int bsg_pitchext_forward_ragged(bsg_pitchext* h, const float* mel, const int32_t* lengths_host, float* pitch_pred, float* f0, int32_t B,
+                                int32_t T, void* stream);
+/* test hook, as bsg_hifigan_ has: NaN bytes into every shape-sized buffer of the handle (a / b / c / keep / pred / pos); the lengths array,
+ * which every ragged call fills itself, is left alone */
+int bsg_pitchext_debug_poison_workspace(bsg_pitchext* h, void* stream);
 
 /* ABI v12: the spectral post-filter of the vocoder output, hparams['vocoder_denoise_c'] (vocoders/hifigan.py:66-69 -> vocoders/vocoder_utils.py:7-15:
  * librosa.stft(center, zero padding, periodic Hann of win_size points) -> |S| - v clipped at 0 with the phase kept -> librosa.istft), as one
