@@ -2340,6 +2340,25 @@ static int launch_tail(bsg_diffnet* h, const StackPlan& plan, TailArgs& a, float
 // One sampler step from the in-projected x in h->xa: the residual stack, then the tail (`a` carries the sampler-specific fields).  When
 // the stack runs as the split-fp16 launch, the tail runs inside it (one launch per step; BSG_H2_TAIL=0: two launches).  A ragged call
 // always fuses it (ragged_launch_ok checked the tail's weights).
+// does the step tail of this plan run on the 16-bit matrix pipe (inside the split-fp16 stack launch, or step_tail_h2_kernel behind a part launch)?
+static bool tail_on_h2(const bsg_diffnet* h, const StackPlan& plan) {
+  const bool h2_tail = plan.ragged || (dn_switches().h2_tail && h->tail_s && h->M <= 96);
+  return h2_tail && (plan.form == STACK_H2 || plan.form == STACK_H2Q || plan.form == STACK_PART);
+}
+
+// The input projection of a DDPM call's first evaluation, rows [plan.row0, plan.row0 + B) of x into h->xa.  In front of the split-fp16
+// tails it is computed as their head computes every later one (in_proj_h2_kernel), so that a call which continues where another stopped
+// gives the bits of one call over all the steps; in front of the other tails the generic GEMM.
+static int first_in_projection(bsg_diffnet* h, const StackPlan& plan, float* x, int B, int T, hipStream_t st) {
+  if (tail_on_h2(h, plan) && h->tail_s) {
+    TailArgs a{};
+    tail_fields(h, a, plan.row0, 32, true, x, B, T);
+    a.status = h->flags ? h->flags + h->flags_cap : nullptr;
+    return launch_in_proj_h2(a, st);
+  }
+  return conv1x1(h->w_in, h->b_in, x, h->xa + (size_t)plan.row0 * C * T, C, h->M, B, T, ACT_RELU, st);
+}
+
 static int step_from_xa(bsg_diffnet* h, const StackPlan& plan, int t_uniform, TailArgs& a, float* x, int B, int T, hipStream_t st) {
   const bool h2_tail = plan.ragged || (dn_switches().h2_tail && h->tail_s && h->M <= 96);
   if (h2_tail && (plan.form == STACK_H2 || plan.form == STACK_H2Q)) {
@@ -2462,8 +2481,7 @@ extern "C" int bsg_ddpm_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
   if (n_sub == 1) subs[0] = SubBatch{B, st, plan};
   int rc = BSG_OK;
   for (int u = 0; u < n_sub && rc == BSG_OK; ++u)
-    rc = conv1x1(h->w_in, h->b_in, x + (size_t)subs[u].plan.row0 * h->M * T, h->xa + (size_t)subs[u].plan.row0 * C * T, C, h->M, subs[u].B,
-                 T, ACT_RELU, subs[u].st);
+    rc = first_in_projection(h, subs[u].plan, x + (size_t)subs[u].plan.row0 * h->M * T, subs[u].B, T, subs[u].st);
   for (int k = 0; k < n_steps && rc == BSG_OK; ++k) {
     const int i = t_start - k;
     for (int u = 0; u < n_sub && rc == BSG_OK; ++u) {

@@ -920,6 +920,75 @@ __global__ __launch_bounds__(512, 1) void step_tail_h2_kernel(TailArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// The input projection of a sampler call's FIRST evaluation with the arithmetic of the split-fp16 step tails' head: the hi / lo planes of
+// x (channels 0..95, rows >= M zero) as the B operand, the fragments and scale of the tails' input projection, six k-steps in the same
+// order.  Every later evaluation's projection is the head of the previous step's tail (above, h2_fused_tail and the TAIL branch of
+// residual_stack_h2_kernel: the same GEMM over column tiles of 32 frames), so a call that continues where another one stopped computes what
+// one call over all the steps computes, bit for bit; the generic GEMM in its place summed in another order (1.2e-7 .. 1.8e-7 on x three
+// steps later).  One workgroup of 8 waves per 32-frame tile of a.x; a.xa_next, a.b_in, a.wi_s, a.tail_scale, a.status as for the tails.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(512, 1) void in_proj_h2_kernel(TailArgs a) {
+  constexpr int XP = h2_xp(1);
+  extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+  char* xs = lds_raw;                  // [2 planes][48 rows][528 B]: hi / lo of x (channels 0..95); rows HALO..HALO+31 used
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l31 = lane & 31, lh = lane >> 5;
+  const int T = a.T, M = a.M;
+  const int b = blockIdx.x / a.tiles_per_row;
+  const int t0 = (blockIdx.x - b * a.tiles_per_row) * 32;
+  const int col = t0 + l31;
+  const bool col_ok = col < T;
+  const int rowT = T * 4, vfrag = lane * 16;
+  const int vcol = (lh * 4 * T + (col_ok ? col : T - 1)) * 4, vst = (lh * 4 * T + col) * 4;
+  const unsigned plane = (unsigned)C * T * 4;
+  const float* tsc = a.tail_scale;
+  const rsrc_t rs_wi = mk_rsrc(a.wi_s, 2 * C * 96 * 2);
+  TailRing<6> ring_i;
+  tail_ring_fill<6>(ring_i, rs_wi, vfrag, wave * 1024, 2 * 8 * 1024, 8 * 1024);
+  // ---- x -> hi / lo image rows, by the three waves whose row tiles cover the M mel bins: the layout the tails' update leaves ----
+  if (wave < 3) {
+    const int rt = wave;
+    const rsrc_t rs_xx = mk_rsrc(a.x + (long long)b * M * T, (unsigned)M * T * 4);
+    float o[16];
+    unsigned worst = 0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int m = 32 * rt + acc_row(r, lh);
+      o[r] = ldf(rs_xx, vcol, (32 * rt + acc_row0(r)) * rowT);   // (rows >= M fall outside the descriptor's range)
+      if (m >= M) o[r] = 0.f;
+      worst = max(worst, __builtin_bit_cast(unsigned, o[r]) & 0x7fffffffu);
+    }
+    if (__builtin_amdgcn_ballot_w64(worst >= 0x476A6000u) != 0ull && lane == 0 && a.status) atomicAdd(a.status + 1, 1u);   // 60000.0f: a range event
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const HiLo s0 = split2(o[4 * g], o[4 * g + 1]), s1_ = split2(o[4 * g + 2], o[4 * g + 3]);
+      char* dst = xs + (HALO + l31) * ROWB + (32 * rt + 8 * g + 4 * lh) * 2;
+      *reinterpret_cast<u32x2*>(dst) = u32x2{s0.hi, s1_.hi};
+      *reinterpret_cast<u32x2*>(dst + XP) = u32x2{s0.lo, s1_.lo};
+    }
+  }
+  const char* xcore = xs + (HALO + l31) * ROWB + lh * 16;
+  auto ldb_x = [&](int ks, f16x8 (&Bf)[2]) {
+    Bf[0] = *reinterpret_cast<const f16x8*>(xcore + ks * 32);
+    Bf[1] = *reinterpret_cast<const f16x8*>(xcore + ks * 32 + XP);
+  };
+  // ---- xa = relu(W_in x + b), K = 96 (in_dims zero-padded)                                                      (net.py:116-118) ----------
+  const rsrc_t rs_bi = mk_rsrc(a.b_in, C * 4);
+  const float sc = tsc[4], inv = tsc[5];
+  f32x16 hc[1];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) hc[0][r] = ldf(rs_bi, lh * 16, (32 * wave + acc_row0(r)) * 4) * sc;
+  __syncthreads();   // the x tile is complete
+  tail_gemm_h2_run<1, 6>(hc, ring_i, rs_wi, vfrag, wave * 1024, 2 * 8 * 1024, 8 * 1024, ldb_x);
+  const rsrc_t rs_xa = mk_rsrc(a.xa_next + (long long)b * C * T, plane);
+  if (col_ok) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) stf(fmaxf(hc[0][r] * inv, 0.f), rs_xa, vst, (32 * wave + acc_row0(r)) * rowT);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // PART forms for small batches (residual_part_h2_kernel<P, W, NC>).  With one workgroup per tile a single utterance keeps 32 of the 256
 // CUs busy, each of them bound by streaming the layer's 2.1 MB of weight fragments out of L2 (tools/l2_fill.hip: a CU pulls at most
 // ~64 B/clk).  Here a tile is computed by P workgroups of W waves on P CUs of one XCD, each owning C / P channels — its gate / filter rows
@@ -1641,6 +1710,14 @@ int launch_step_tail_h2(const TailArgs& a, hipStream_t st) {
   }
   BSG_REQUIRE(a.ws_s && a.wo_s && a.wi_s && a.tail_scale && a.M <= 96, "split-fp16 step tail: fragments missing or in_dims > 96");
   hipLaunchKernelGGL(step_tail_h2_kernel, dim3(a.B * a.tiles_per_row), dim3(512), lds, st, a);
+  BSG_LAUNCH_CHECK();
+  return BSG_OK;
+}
+
+// a sampler call's first input projection as the tails' head computes the later ones: one workgroup per 32-frame tile of a.x
+int launch_in_proj_h2(const TailArgs& a, hipStream_t st) {
+  BSG_REQUIRE(a.x && a.xa_next && a.b_in && a.wi_s && a.tail_scale && a.M <= 96, "split-fp16 input projection: fragments missing or in_dims > 96");
+  hipLaunchKernelGGL(in_proj_h2_kernel, dim3(a.B * a.tiles_per_row), dim3(512), (size_t)2 * h2_xp(1), st, a);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
 }

@@ -112,6 +112,8 @@ int launch_residual_stack_h2(const StackArgs& p, const TailArgs* tail, hipStream
 int launch_residual_stack_h2q(const StackArgs& p, const TailArgs* tail, hipStream_t st, int nct);
 // the step tail behind a pair / quad launch, on the 16-bit matrix pipe (diffnet_h2.hip step_tail_h2_kernel)
 int launch_step_tail_h2(const TailArgs& a, hipStream_t st);
+// a sampler call's first input projection with the arithmetic of the split-fp16 tails' head (diffnet_h2.hip in_proj_h2_kernel)
+int launch_in_proj_h2(const TailArgs& a, hipStream_t st);
 int h2_tail_pack(const float* ws, const float* wo96, const float* wi96, unsigned short* out_ws, unsigned short* out_wo, unsigned short* out_wi,
                  unsigned* maxbits, float* tab, hipStream_t st);
 

@@ -144,7 +144,9 @@ typedef struct {
  * row 0 and global batch size, so a sharded run reproduces the unsharded noise.
  * For batches with more 32-frame tiles than the device has CUs the loop runs as two concurrent launch chains over half the
  * rows each: a handle-owned second stream is forked off `stream` and joined back before the call returns (BSG_DUAL=0
- * disables); results are bit-identical either way. */
+ * disables); results are bit-identical either way.
+ * On the split-fp16 launches (the default) a call that continues at t_start - n_steps where another call stopped gives the bits of
+ * one call over all the steps; on the fp32-pipe and bf16 tails the two agree to rounding. */
 int bsg_ddpm_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, const float* noise, uint64_t seed,
                     int32_t t_start, int32_t n_steps, int32_t B, int32_t T, int32_t row0,
                     int32_t B_total, void* stream);

@@ -271,7 +271,11 @@ def test_stack_launch_matches_per_layer_launches(B, T, base, stack, path, tol, t
     sizes): Winograd F(4,3) transforms instead of F(2,3) and x recovered as image - d: measured 7e-7, bar 1e-5.  One child process per
     environment (the switches are read once per process; every shape of that environment in the same child).  BSG_STACK43=2 / BSG_H2=2 force
     the form for small / ragged shapes.
-    Split-fp16 stack (diffnet_h2.hip): products exact to 3 x 2^-24, fp32 accumulation in another order: bar 1e-5."""
+    Split-fp16 stack (diffnet_h2.hip): products exact to 3 x 2^-24, fp32 accumulation in another order: bar 1e-5.
+    What the 10 steps can see: they run from t = 99 on x_T ~ N(0, 1), where about 80 % of x_recon is clamped to [-1, 1] (84 % at t = 99,
+    81 % at t = 90) and a clamped element's new x does not depend on eps, so a difference in eps between the two forms reaches x on one
+    element of five; the evaluation behind them goes through no step tail.  Each step-tail form against float64, in windows of steps
+    where at most 10 % / 20 % is clamped: tests/test_gpu_ddpm_shapes.py."""
     rb, ab = _stack_child(base, B, T, tmp_path_factory)
     rs_, as_ = _stack_child(stack, B, T, tmp_path_factory)
     assert rs_['path'] == path and not rb['path'].startswith('stack')
