@@ -1798,7 +1798,7 @@ static LayerForm use_split(bsg_diffnet* h, int B, int T, bool small_lds) {
   if ((size_t)tiles > h->split_cap) return LAYER_PLAIN;
   if (h->occ2 < 0) query_split_occupancy(h);
   // residency is what makes a hand-off terminate: every workgroup of the launch (and, for two chains sharing CUs, of both
-  // launches: dual_fork checks that sum) must fit the device at the LDS size actually launched
+  // launches: dual_scope checks that sum) must fit the device at the LDS size actually launched
   const int o4 = small_lds ? h->occ4s : h->occ4, o2 = small_lds ? h->occ2s : h->occ2;
   if (4 * tiles <= h->num_cus && env != 2 && o4 >= 1) return LAYER_SPLIT4;   // BSG_SPLIT=2: no 4-way split (A/B measurements)
   if (2 * tiles <= h->num_cus) return o2 >= 1 ? LAYER_SPLIT2 : LAYER_PLAIN;
@@ -2108,6 +2108,15 @@ static int stack_args(bsg_diffnet* h, const StackPlan& plan, int g, const long l
   return BSG_OK;
 }
 
+// `a` moved to the rows starting r rows further on: the tensors a launch group or a half-batch chain works on, and its Philox index
+static TailArgs tail_rows(TailArgs a, size_t r) {
+  const size_t mo = r * a.M * a.T;
+  a.x += mo; a.xa_next += r * C * a.T; a.quad_row0 += mo;
+  if (a.e_new) a.e_new += mo;
+  for (const float** p : {&a.noise, &a.h1, &a.h2, &a.h3}) if (*p) *p += mo;
+  return a;
+}
+
 // the planned stack launch of rows [plan.row0, plan.row0 + B): its launch groups one after the other on `st`; `tail`: the sampler
 // step's tail in the same launch (split-fp16 forms)
 static int launch_stack(bsg_diffnet* h, const StackPlan& plan, const long long* t_dev, int t_uniform, int B, int T, hipStream_t st,
@@ -2121,18 +2130,8 @@ static int launch_stack(bsg_diffnet* h, const StackPlan& plan, const long long* 
   for (int g = 0; g < groups; ++g) {
     StackArgs p;
     TRY(stack_args(h, plan, g, t_dev, t_uniform, B, T, st, stamps, p));
-    TailArgs a{};
-    if (tail) {   // the step tail in the same launch: its tensors start at this launch group's first row
-      a = *tail;
-      const size_t r0 = plan.ragged ? 0 : (size_t)g * plan.rows;
-      const size_t mo = r0 * h->M * T;
-      a.x += mo; a.xa_next += r0 * C * T; a.quad_row0 += mo;
-      if (a.noise) a.noise += mo;
-      if (a.e_new) a.e_new += mo;
-      if (a.h1) a.h1 += mo;
-      if (a.h2) a.h2 += mo;
-      if (a.h3) a.h3 += mo;
-    }
+    // the step tail in the same launch: its tensors start at this launch group's first row
+    const TailArgs a = tail ? tail_rows(*tail, plan.ragged ? 0 : (size_t)g * plan.rows) : TailArgs{};
     switch (plan.form) {
       case STACK_F43: TRY(launch_residual_stack_f43(p, st)); break;
       case STACK_H2: TRY(launch_residual_stack_h2(p, tail ? &a : nullptr, st, plan.nct)); break;
@@ -2161,18 +2160,46 @@ static int check_bound(bsg_diffnet* h, int B, int T, const char* who) {
   return BSG_OK;
 }
 
-static bool fused_tail_ok(const bsg_diffnet* h);
+// The step tail, what runs after the stack in a sampler step: skip and output projection, the DDPM or PLMS update of x, the next evaluation's input
+// projection.  plan_tail() alone decides its form, from the handle's state and the stack plan of its rows ("Which tail runs").
+enum TailForm {
+  TAIL_UNFUSED,       // no fused tail (BSG_NO_FUSED_TAIL, or no packed tail weights): forward_impl + ddpm_step_kernel / plms_step_kernel
+  TAIL_IN_STACK,      // inside the split-fp16 stack launch (residual_stack_h2_kernel / residual_stack_q_kernel with a TailArgs)
+  TAIL_H2,            // step_tail_h2_kernel behind a part launch
+  TAIL_F32,           // step_tail_kernel<MP, plms> on the fp32 matrix pipe
+  TAIL_BF16,          // step_tail_bf16_kernel (bf16 configuration; BSG_TAIL_BF16=0: TAIL_F32)
+  TAIL_BF16_RAGGED,   // step_tail_bf16_varlen_kernel: one launch over the tiles of every launch group of the bound ragged batch
+};
 
-static bool bf16_tail_on(const bsg_diffnet* h);
+struct TailPlan {
+  TailForm form = TAIL_UNFUSED;
+  int tile = 32;           // frames per tile that TailArgs::tiles_per_row counts: 64 in the stack launch, 32 for the launches of their own
+  int mp = 0;              // TAIL_F32: in_dims padded to a multiple of 8, the instantiation of step_tail_kernel (80 or 96)
+  bool first_h2 = false;   // a DDPM call's first input projection: in_proj_h2_kernel (the split-fp16 tails), else the generic GEMM
+};
+
+// A ragged plan takes the tail on the 16-bit matrix pipe whatever BSG_H2_TAIL says: its launch has no other fp32 tail.
+static TailPlan plan_tail(const bsg_diffnet* h, const StackPlan& plan) {
+  TailPlan tp;
+  tp.mp = h->MP;
+  if (!h->ws_pack || (tp.mp != 80 && tp.mp != 96) || live_no_fused_tail()) return tp;
+  const bool h2 = h->tail_s && h->M <= 96 && (plan.ragged || dn_switches().h2_tail);
+  if (h2 && (plan.form == STACK_H2 || plan.form == STACK_H2Q)) { tp.form = TAIL_IN_STACK; tp.tile = 64; }
+  else if (h2 && plan.form == STACK_PART) tp.form = TAIL_H2;
+  else if (h->compute == BSG_COMPUTE_BF16 && live_tail_bf16() && h->tail_h) tp.form = plan.ragged ? TAIL_BF16_RAGGED : TAIL_BF16;
+  else tp.form = TAIL_F32;
+  tp.first_h2 = tp.form == TAIL_IN_STACK || tp.form == TAIL_H2;
+  return tp;
+}
 
 // Can the handle's CURRENT state decode the bound ragged batch with the ragged launch?  When its ragged plan has a stack launch
-// (stack_form: the conditions of the launch itself) and the step tail that launch needs exists: the fused tail's packed weights
-// (BSG_NO_FUSED_TAIL unset), in the fp32 configuration the split-fp16 tail inside the launch, in the bf16 configuration the bf16 step tail
-// (BSG_TAIL_BF16=0: none).  (The callers otherwise decode the rows one by one.)
+// (stack_form: the conditions of the launch itself) and the tail that launch needs (plan_tail): in the fp32 configuration the one inside
+// the launch, in the bf16 configuration the ragged bf16 step tail.  (The callers otherwise decode the rows one by one.)
 static bool ragged_launch_ok(bsg_diffnet* h) {
-  if (!h->bound.ragged || h->bound.compute != h->compute || h->M > 96 || !fused_tail_ok(h)) return false;
-  if (h->compute == BSG_COMPUTE_BF16 ? !bf16_tail_on(h) : !h->tail_s) return false;
-  return plan_stack(h, h->bound.B, h->bound.T, nullptr, PLAN_RAGGED).form != STACK_NONE;
+  if (!h->bound.ragged || h->bound.compute != h->compute) return false;
+  const StackPlan plan = plan_stack(h, h->bound.B, h->bound.T, nullptr, PLAN_RAGGED);
+  const TailForm tail = plan_tail(h, plan).form;
+  return plan.form != STACK_NONE && (tail == TAIL_IN_STACK || tail == TAIL_BF16_RAGGED);
 }
 
 // entry of a compute call on a ragged binding: refused under stream capture and where the handle has no ragged launch
@@ -2280,115 +2307,79 @@ static int check_schedule(const bsg_schedule* s, const char* who, bool plms) {
   return BSG_OK;
 }
 
-static bool fused_tail_ok(const bsg_diffnet* h) {
-  return h->ws_pack != nullptr && (h->MP == 80 || h->MP == 96) && !live_no_fused_tail();
-}
+// rows [plan.row0, plan.row0 + B) of a sampler call's batch on stream st: their stack plan, the tail behind it and the tail's arguments
+struct SubBatch { int B; hipStream_t st; StackPlan plan; TailPlan tail; TailArgs args; };
 
-// the bf16-operand configuration runs its step tail's projections on bf16 MFMAs (step_tail_bf16_kernel; BSG_TAIL_BF16=0: the fp32 tail)
-static bool bf16_tail_on(const bsg_diffnet* h) {
-  return h->compute == BSG_COMPUTE_BF16 && live_tail_bf16() && h->tail_h;
-}
-
-// What every step tail takes for rows [row0, row0 + B) on tiles of `tile` frames: x, the next evaluation's in-projection, the biases and
-// the shape; h2: the tails on the 16-bit matrix pipe, their split-fp16 weights and scales too
-static void tail_fields(const bsg_diffnet* h, TailArgs& a, int row0, int tile, bool h2, float* x, int B, int T) {
-  a.x = x; a.xa_next = h->xa + (size_t)row0 * C * T;
-  a.b_skip = h->b_skip; a.b_fin = h->b_fin96; a.b_in = h->b_in;
-  a.B = B; a.T = T; a.M = h->M; a.tiles_per_row = cdiv(T, tile);
-  if (h2) { a.ws_s = h->tail_s; a.wo_s = h->tail_s + 2 * C * C; a.wi_s = h->tail_s + 2 * C * C + 2 * 96 * C; a.tail_scale = h->tail_scale; }
+// The chain of B rows from plan.row0 of x [.][M][T].  args: what the handle and the plans decide of its tail's arguments, filled once per call
+// (a step adds the sampler's own fields); x and xa_next at the call's row 0 (tail_rows moves them with the sampler's tensors), the chain's skip sum
+static SubBatch sub_batch(const bsg_diffnet* h, const StackPlan& plan, float* x, int B, int T, hipStream_t st) {
+  SubBatch sub{B, st, plan, plan_tail(h, plan), TailArgs{}};
+  const size_t off = (size_t)plan.row0 * C * T;
+  TailArgs& a = sub.args;
+  a.x = x; a.xa_next = h->xa;
+  a.skip = h->skip + off; a.skip_h = h->compute == BSG_COMPUTE_BF16 ? h->skip_h + off : nullptr;
+  a.b_skip = h->b_skip; a.b_fin = h->b_fin96; a.b_in = h->b_in; a.B = B; a.T = T; a.M = h->M; a.tiles_per_row = cdiv(T, sub.tail.tile);
+  a.status = h->flags ? h->flags + h->flags_cap : nullptr;   // (step_tail_h2_kernel, in_proj_h2_kernel: word 1 += range events)
+  if (sub.tail.first_h2) {   // the 16-bit matrix pipe: split-fp16 weights and their scales
+    a.ws_s = h->tail_s; a.wo_s = h->tail_s + 2 * C * C; a.wi_s = h->tail_s + 2 * C * C + 2 * 96 * C; a.tail_scale = h->tail_scale;
+  } else if (sub.tail.form == TAIL_F32) {
+    a.ws_pack = h->ws_pack; a.wo_pack = h->wo_pack; a.wi_pack = h->wi_pack;
+  } else if (sub.tail.form != TAIL_UNFUSED) {   // the projections on bf16 MFMAs
+    a.ws_h = h->tail_h; a.wo_h = h->tail_h + C * C; a.wi_h = h->tail_h + C * C + 96 * C;
+  }
+  return sub;
 }
 
 // step_tail_kernel: skip projection, output projection, sampler update of x (DDPM, or PLMS when a.plms_hist > 0) and the next
-// evaluation's in-projection into h->xa; the caller fills the sampler-specific fields of `a`
-static int launch_tail(bsg_diffnet* h, const StackPlan& plan, TailArgs& a, float* x, int B, int T, hipStream_t st) {
-  static bool tail_attr = false;
+// evaluation's in-projection into h->xa
+static int launch_tail(const TailPlan& tp, const TailArgs& a, hipStream_t st) {
+  void (*const kern[4])(TailArgs) = {step_tail_kernel<80, false>, step_tail_kernel<96, false>, step_tail_kernel<80, true>, step_tail_kernel<96, true>};
   const size_t tail_lds = (size_t)(C * 32 + 96 * 32) * sizeof(float);
-  if (!tail_attr) {
-    BSG_HIP(hipFuncSetAttribute((const void*)step_tail_kernel<80, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tail_lds));
-    BSG_HIP(hipFuncSetAttribute((const void*)step_tail_kernel<96, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tail_lds));
-    BSG_HIP(hipFuncSetAttribute((const void*)step_tail_kernel<80, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tail_lds));
-    BSG_HIP(hipFuncSetAttribute((const void*)step_tail_kernel<96, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tail_lds));
-    tail_attr = true;
-  }
-  const size_t off = (size_t)plan.row0 * C * T;
-  a.skip = h->skip + off; a.skip_h = h->compute == BSG_COMPUTE_BF16 ? h->skip_h + off : nullptr;
-  tail_fields(h, a, plan.row0, 32, false, x, B, T);
-  a.ws_pack = h->ws_pack; a.wo_pack = h->wo_pack; a.wi_pack = h->wi_pack;
-  if (bf16_tail_on(h)) {   // bf16-operand configuration: the projections on bf16 MFMAs too
-    a.ws_h = h->tail_h; a.wo_h = h->tail_h + C * C; a.wi_h = h->tail_h + C * C + 96 * C;
-    if (plan.ragged) {   // ragged: one launch over the tiles of every launch group's table (they follow the row lengths in rg_dev)
-      BSG_REQUIRE(plan.row0 == 0 && h->rg_dev, "ragged bf16 step tail: no ragged plan bound");
-      int n_tiles = 0;
-      for (int t : h->rg_group_tiles) n_tiles += t;
-      return launch_step_tail_bf16_ragged(a, reinterpret_cast<const int2*>(h->rg_dev + ((h->bound.B + 1) & ~1)), h->rg_dev, n_tiles, st);
-    }
-    return launch_step_tail_bf16(a, st);
-  }
-  BSG_REQUIRE(!plan.ragged, "step tail: a ragged call needs the bf16 tail in the bf16 configuration");
-  const dim3 grid(B * a.tiles_per_row), block(512);
-  if (a.plms_hist) {
-    if (h->MP == 80) hipLaunchKernelGGL((step_tail_kernel<80, true>), grid, block, tail_lds, st, a);
-    else hipLaunchKernelGGL((step_tail_kernel<96, true>), grid, block, tail_lds, st, a);
-  } else {
-    if (h->MP == 80) hipLaunchKernelGGL((step_tail_kernel<80, false>), grid, block, tail_lds, st, a);
-    else hipLaunchKernelGGL((step_tail_kernel<96, false>), grid, block, tail_lds, st, a);
-  }
+  static bool tail_attr = false;
+  for (int i = 0; i < 4 && !tail_attr; ++i) BSG_HIP(hipFuncSetAttribute((const void*)kern[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)tail_lds));
+  tail_attr = true;
+  hipLaunchKernelGGL(kern[2 * (a.plms_hist != 0) + (tp.mp != 80)], dim3(a.B * a.tiles_per_row), dim3(512), tail_lds, st, a);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
 }
 
-// One sampler step from the in-projected x in h->xa: the residual stack, then the tail (`a` carries the sampler-specific fields).  When
-// the stack runs as the split-fp16 launch, the tail runs inside it (one launch per step; BSG_H2_TAIL=0: two launches).  A ragged call
-// always fuses it (ragged_launch_ok checked the tail's weights).
-// does the step tail of this plan run on the 16-bit matrix pipe (inside the split-fp16 stack launch, or step_tail_h2_kernel behind a part launch)?
-static bool tail_on_h2(const bsg_diffnet* h, const StackPlan& plan) {
-  const bool h2_tail = plan.ragged || (dn_switches().h2_tail && h->tail_s && h->M <= 96);
-  return h2_tail && (plan.form == STACK_H2 || plan.form == STACK_H2Q || plan.form == STACK_PART);
+// The input projection of a DDPM call's first evaluation, the chain's rows of x into h->xa (TailPlan::first_h2).
+static int first_in_projection(bsg_diffnet* h, const SubBatch& sub) {
+  TailArgs a = tail_rows(sub.args, sub.plan.row0);
+  if (!sub.tail.first_h2) return conv1x1(h->w_in, h->b_in, a.x, a.xa_next, C, h->M, a.B, a.T, ACT_RELU, sub.st);
+  a.tiles_per_row = cdiv(a.T, 32);   // one workgroup per 32-frame tile, also in front of the stack launch's 64-frame tails
+  return launch_in_proj_h2(a, sub.st);
 }
 
-// The input projection of a DDPM call's first evaluation, rows [plan.row0, plan.row0 + B) of x into h->xa.  In front of the split-fp16
-// tails it is computed as their head computes every later one (in_proj_h2_kernel), so that a call which continues where another stopped
-// gives the bits of one call over all the steps; in front of the other tails the generic GEMM.
-static int first_in_projection(bsg_diffnet* h, const StackPlan& plan, float* x, int B, int T, hipStream_t st) {
-  if (tail_on_h2(h, plan) && h->tail_s) {
-    TailArgs a{};
-    tail_fields(h, a, plan.row0, 32, true, x, B, T);
-    a.status = h->flags ? h->flags + h->flags_cap : nullptr;
-    return launch_in_proj_h2(a, st);
+// One sampler step of a chain from the in-projected x in h->xa: the residual stack, then the tail in the chain's form.  `step`: sub.args
+// with the sampler's own fields set, at the call's row 0.
+static int run_step(bsg_diffnet* h, const SubBatch& sub, int t_uniform, const TailArgs& step) {
+  const TailArgs a = tail_rows(step, sub.plan.row0);
+  if (sub.tail.form == TAIL_IN_STACK) return run_layers(h, sub.plan, nullptr, t_uniform, a.B, a.T, sub.st, &a);   // one launch per step
+  TRY(run_layers(h, sub.plan, nullptr, t_uniform, a.B, a.T, sub.st));
+  switch (sub.tail.form) {
+    case TAIL_H2: return launch_step_tail_h2(a, sub.st);
+    case TAIL_BF16: return launch_step_tail_bf16(a, sub.st);
+    case TAIL_BF16_RAGGED: {   // one launch over the tiles of every launch group's table (they follow the row lengths in rg_dev)
+      BSG_REQUIRE(sub.plan.row0 == 0 && h->rg_dev, "ragged bf16 step tail: no ragged plan bound");
+      int n_tiles = 0;
+      for (int t : h->rg_group_tiles) n_tiles += t;
+      return launch_step_tail_bf16_ragged(a, reinterpret_cast<const int2*>(h->rg_dev + ((h->bound.B + 1) & ~1)), h->rg_dev, n_tiles, sub.st);
+    }
+    default:   // TAIL_F32 (TAIL_UNFUSED is each sampler's forward_impl path and never comes here)
+      BSG_REQUIRE(!sub.plan.ragged, "step tail: a ragged call needs the bf16 tail in the bf16 configuration");
+      return launch_tail(sub.tail, a, sub.st);
   }
-  return conv1x1(h->w_in, h->b_in, x, h->xa + (size_t)plan.row0 * C * T, C, h->M, B, T, ACT_RELU, st);
 }
-
-static int step_from_xa(bsg_diffnet* h, const StackPlan& plan, int t_uniform, TailArgs& a, float* x, int B, int T, hipStream_t st) {
-  const bool h2_tail = plan.ragged || (dn_switches().h2_tail && h->tail_s && h->M <= 96);
-  if (h2_tail && (plan.form == STACK_H2 || plan.form == STACK_H2Q)) {
-    tail_fields(h, a, plan.row0, 64, true, x, B, T);
-    return run_layers(h, plan, nullptr, t_uniform, B, T, st, &a);
-  }
-  TRY(run_layers(h, plan, nullptr, t_uniform, B, T, st));
-  if (h2_tail && plan.form == STACK_PART) {
-    // behind a part launch: the tail on the 16-bit matrix pipe too (step_tail_h2_kernel; BSG_H2_TAIL=0: the fp32-pipe tail)
-    a.skip = h->skip + (size_t)plan.row0 * C * T; a.skip_h = nullptr;
-    tail_fields(h, a, plan.row0, 32, true, x, B, T);
-    a.status = h->flags + h->flags_cap;
-    return launch_step_tail_h2(a, st);
-  }
-  return launch_tail(h, plan, a, x, B, T, st);
-}
-
-struct SubBatch { int B; hipStream_t st; StackPlan plan; };   // rows [plan.row0, plan.row0 + B) of the batch on stream st
 
 // Two half-batches on two streams.  One launch per layer puts all workgroups of the chip in the same phase (they stage, hit
 // the gate and drain together, and the younger of the two workgroups of a CU finishes alone); two independent launch chains
 // drift apart and fill each other's gaps: measured 239.6 -> 226.5 ms per 100 steps at B=16, T=1000 (+5.8 %), +4.0 % at B=32,
 // +9.9 % at B=12, +1.2 % at B=64, +4 % for the bf16 form at B=64; four chains are worse (a CU only holds two of these
 // workgroups).  On one of the boxes measured the two chains brought no gain (and no loss).  BSG_DUAL=0 disables.
-// Returns the number of sub-batches (1 or 2) and, for 2, forks the second stream off `st` and plans each half for what it is (PlanScope).
-// `plan`: the whole batch's.
-static int dual_fork(bsg_diffnet* h, const StackPlan& plan, int B, int T, hipStream_t st, SubBatch (&subs)[2]) {
+// Returns what each half is planned as (PlanScope), or PLAN_WHOLE: one chain.  `plan`: the whole batch's.
+static PlanScope dual_scope(bsg_diffnet* h, const StackPlan& plan, int B, int T) {
   const int dual_env = dn_switches().dual, split_env = dn_switches().split;
-  subs[0] = SubBatch{B, st, plan};
-  subs[1] = SubBatch{0, nullptr, StackPlan{}};
   const long long tiles = (long long)B * cdiv(T, 32);
   const bool big = tiles > h->num_cus;
   // 129..256 tiles (B = 5..8): two chains of channel-split launches (each workgroup half the matrix work, two per CU, one of each
@@ -2401,41 +2392,70 @@ static int dual_fork(bsg_diffnet* h, const StackPlan& plan, int B, int T, hipStr
     // polling workgroup could wait for a partner that cannot start.  Per half: parts x tiles workgroups of 1024/parts threads.
     if (h->occ2 < 0) query_split_occupancy(h);
     double cus = 0.0;   // CUs the workgroups of both launches occupy at the residency the runtime reports for each form
-    bool ok = true;
     for (int half = 0; half < 2; ++half) {
       const long long th = (long long)(half ? B - B / 2 : B / 2) * cdiv(T, 32);
       const int parts = 4 * th <= h->num_cus && split_env != 2 ? 4 : 2 * th <= h->num_cus ? 2 : 0;
       int occ = parts == 4 ? h->occ4s : h->occ2s;
       const int cap = parts == 4 ? 3 : 2;   // 48 KB of LDS each -> 3 per CU; 8 waves of 128 VGPRs -> 2 per CU
       if (occ > cap) occ = cap;
-      if (!parts || occ < 1) { ok = false; break; }
+      if (!parts || occ < 1) return PLAN_WHOLE;
       cus += (double)(parts * th) / occ;
     }
-    small = ok && cus <= (double)h->num_cus;
+    small = cus <= (double)h->num_cus;
   }
   const bool dual = dual_env && B >= 2 && use_wino() && plan.form == STACK_NONE && (big || small);
-  if (!dual) return 1;
-  if (!h->st2) {
-    if (hipStreamCreateWithFlags(&h->st2, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess)
-      return 1;
-  }
-  if (hipEventRecord(h->ev_fork, st) != hipSuccess || hipStreamWaitEvent(h->st2, h->ev_fork, 0) != hipSuccess) return 1;
-  const PlanScope half = big ? PLAN_HALF_BIG : PLAN_HALF_SMALL;
-  subs[0] = SubBatch{B / 2, st, plan_stack(h, B / 2, T, st, half)};
-  subs[1] = SubBatch{B - B / 2, h->st2, plan_stack(h, B - B / 2, T, h->st2, half)};
-  subs[1].plan.row0 = B / 2;
-  return 2;
+  return !dual ? PLAN_WHOLE : big ? PLAN_HALF_BIG : PLAN_HALF_SMALL;
 }
 
-// joins the second stream back into `st` (also after an error, so that the caller's stream stays ordered after everything
+// What both sampler entries keep of a call
+struct SamplerFrame {
+  StackPlan plan;     // the whole batch's stack plan
+  TailPlan tail;      // ... and the tail behind it; TAIL_UNFUSED: the entry's forward_impl loop
+  SubBatch subs[2];   // the chains of the fused steps; until dual_fork, [0] is the whole batch on the caller's stream
+  int n_sub = 0;      // chains; 0: not forked yet
+};
+
+// the entries' shared checks in front of their own: the binding and the schedule
+static int sampler_enter(bsg_diffnet* h, const bsg_schedule* s, int B, int T, const char* who, bool plms) {
+  TRY(check_bound(h, B, T, who));
+  h->last_chains = 1;   // this call's count from here on: the unfused loop and an early return never reach sampler_end
+  return check_schedule(s, who, plms);
+}
+
+// ... and behind them: the whole batch's plans, the conditioner term in the layout its launch reads
+static int sampler_begin(bsg_diffnet* h, SamplerFrame& f, float* x, int B, int T, hipStream_t st, const char* who) {
+  TRY(ragged_enter(h, st, who));
+  f.plan = plan_stack(h, B, T, st, h->bound.ragged ? PLAN_RAGGED : PLAN_WHOLE);
+  TRY(cond_layout_for(h, f.plan, st));
+  f.subs[0] = sub_batch(h, f.plan, x, B, T, st); f.tail = f.subs[0].tail;
+  return BSG_OK;
+}
+
+// The chains of the fused steps: two half-batches on two streams where `may_split` and dual_scope say so and the fork succeeds, each
+// half planned for what it is; else (always for a ragged batch: one chain of its launch groups) the whole batch stays the one chain.
+static void dual_fork(bsg_diffnet* h, SamplerFrame& f, bool may_split) {
+  const SubBatch w = f.subs[0];
+  const int B0 = w.B / 2, T = w.args.T;
+  const PlanScope half = may_split && !w.plan.ragged ? dual_scope(h, w.plan, w.B, T) : PLAN_WHOLE;
+  bool two = half != PLAN_WHOLE;   // the fork: the second stream and its events are created at the first one; a failed call leaves one chain
+  if (two && !h->st2)
+    two = hipStreamCreateWithFlags(&h->st2, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) == hipSuccess &&
+          hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) == hipSuccess;
+  f.n_sub = two && hipEventRecord(h->ev_fork, w.st) == hipSuccess && hipStreamWaitEvent(h->st2, h->ev_fork, 0) == hipSuccess ? 2 : 1;
+  if (f.n_sub == 1) return;
+  f.subs[0] = sub_batch(h, plan_stack(h, B0, T, w.st, half), w.args.x, B0, T, w.st);
+  StackPlan second = plan_stack(h, w.B - B0, T, h->st2, half);
+  second.row0 = B0;
+  f.subs[1] = sub_batch(h, second, w.args.x, w.B - B0, T, h->st2);
+}
+
+// joins the second stream back into the caller's (also after an error, so that the caller's stream stays ordered after everything
 // that was enqueued on the second one) and records the call's chain count
-static int dual_join(bsg_diffnet* h, int n_sub, hipStream_t st, int rc) {
-  h->last_chains = n_sub == 2 ? 2 : 1;
-  if (n_sub == 2) {
+static int sampler_end(bsg_diffnet* h, const SamplerFrame& f, int rc) {
+  h->last_chains = f.n_sub == 2 ? 2 : 1;
+  if (f.n_sub == 2) {
     hipError_t e1 = hipEventRecord(h->ev_join, h->st2);
-    hipError_t e2 = hipStreamWaitEvent(st, h->ev_join, 0);
+    hipError_t e2 = hipStreamWaitEvent(f.subs[0].st, h->ev_join, 0);
     if (rc == BSG_OK && (e1 != hipSuccess || e2 != hipSuccess)) { set_error("sampler: stream join failed"); rc = BSG_EHIP; }
   }
   return rc;
@@ -2445,9 +2465,7 @@ extern "C" int bsg_ddpm_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
                                int32_t t_start, int32_t n_steps, int32_t B, int32_t T, int32_t row0, int32_t B_total,
                                void* stream) {
   GuardScope guard_scope(h ? &h->guard : nullptr);
-  TRY(check_bound(h, B, T, "ddpm_sample"));
-  h->last_chains = 1;   // this call's count from here on: the unfused loop and an early return never reach dual_join
-  TRY(check_schedule(s, "ddpm_sample", false));
+  TRY(sampler_enter(h, s, B, T, "ddpm_sample", false));
   BSG_REQUIRE(x, "ddpm_sample: null x");
   BSG_REQUIRE(t_start < s->num_timesteps && t_start < h->cfg.max_steps && n_steps >= 0 && t_start - n_steps + 1 >= 0,
               "ddpm_sample: steps [%d..%d] outside the schedule (%d) / step table (%d)", t_start - n_steps + 1, t_start,
@@ -2456,47 +2474,36 @@ extern "C" int bsg_ddpm_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
   hipStream_t st = (hipStream_t)stream;
   const long long n = (long long)B * h->M * T;
   BSG_REQUIRE(n % 4 == 0, "ddpm_sample: B*M*T must be a multiple of 4");
-  TRY(ragged_enter(h, st, "ddpm_sample"));
-  const StackPlan plan = plan_stack(h, B, T, st, h->bound.ragged ? PLAN_RAGGED : PLAN_WHOLE);
-  TRY(cond_layout_for(h, plan, st));
-  const long long n4 = n / 4;
-  const unsigned long long quad0 = (unsigned long long)row0 * h->M * T / 4;
-  const bool fused = fused_tail_ok(h);
-  if (!fused) {
+  SamplerFrame f;
+  TRY(sampler_begin(h, f, x, B, T, st, "ddpm_sample"));
+  const unsigned long long elem0 = (unsigned long long)row0 * h->M * T;   // Philox: the flat element index of this shard's row 0
+  auto coef = [&](int i) {
+    return StepCoef{s->sqrt_recip_alphas_cumprod[i], s->sqrt_recipm1_alphas_cumprod[i], s->posterior_mean_coef1[i], s->posterior_mean_coef2[i], s->sigma[i]};
+  };
+  if (f.tail.form == TAIL_UNFUSED) {
     for (int k = 0; k < n_steps; ++k) {
       const int i = t_start - k;
-      TRY(forward_impl(h, plan, x, nullptr, i, h->eps, B, T, st));
-      StepCoef c{s->sqrt_recip_alphas_cumprod[i], s->sqrt_recipm1_alphas_cumprod[i], s->posterior_mean_coef1[i],
-                 s->posterior_mean_coef2[i], s->sigma[i]};
-      hipLaunchKernelGGL(ddpm_step_kernel, dim3(cdiv(n4, 256)), dim3(256), 0, st, x, (const float*)h->eps,
-                         noise ? noise + (long long)k * n : nullptr, c, n4, (unsigned long long)seed, (unsigned)(i + 1), quad0);
+      TRY(forward_impl(h, f.plan, x, nullptr, i, h->eps, B, T, st));
+      hipLaunchKernelGGL(ddpm_step_kernel, dim3(cdiv(n / 4, 256)), dim3(256), 0, st, x, (const float*)h->eps,
+                         noise ? noise + (long long)k * n : nullptr, coef(i), n / 4, (unsigned long long)seed, (unsigned)(i + 1), elem0 / 4);
       BSG_LAUNCH_CHECK();
     }
     return BSG_OK;
   }
-  // fused loop: [in-projection once] -> per step: 20 residual layers -> step_tail_kernel (skip projection, output
-  // projection, sampler update, next step's in-projection)
-  SubBatch subs[2];
-  const int n_sub = n_steps > 0 && !plan.ragged ? dual_fork(h, plan, B, T, st, subs) : 1;
-  if (n_sub == 1) subs[0] = SubBatch{B, st, plan};
+  // fused loop: [in-projection once] -> per step: 20 residual layers -> the step tail, which leaves the next step's in-projection
+  dual_fork(h, f, n_steps > 0);
   int rc = BSG_OK;
-  for (int u = 0; u < n_sub && rc == BSG_OK; ++u)
-    rc = first_in_projection(h, subs[u].plan, x + (size_t)subs[u].plan.row0 * h->M * T, subs[u].B, T, subs[u].st);
+  for (int u = 0; u < f.n_sub && rc == BSG_OK; ++u) rc = first_in_projection(h, f.subs[u]);
   for (int k = 0; k < n_steps && rc == BSG_OK; ++k) {
     const int i = t_start - k;
-    for (int u = 0; u < n_sub && rc == BSG_OK; ++u) {
-      const size_t mo = (size_t)subs[u].plan.row0 * h->M * T;   // this half's first element of x
-      TailArgs a{};
-      a.noise = noise ? noise + (long long)k * n + (long long)mo : nullptr;
-      a.k = StepCoef{s->sqrt_recip_alphas_cumprod[i], s->sqrt_recipm1_alphas_cumprod[i], s->posterior_mean_coef1[i],
-                     s->posterior_mean_coef2[i], s->sigma[i]};
-      a.seed = seed; a.quad_row0 = (unsigned long long)(row0 + subs[u].plan.row0) * h->M * T; a.stream = (unsigned)(i + 1);
-      a.do_head = k + 1 < n_steps;
-      rc = step_from_xa(h, subs[u].plan, i, a, x + mo, subs[u].B, T, subs[u].st);
+    for (int u = 0; u < f.n_sub && rc == BSG_OK; ++u) {
+      TailArgs a = f.subs[u].args;
+      a.noise = noise ? noise + (long long)k * n : nullptr; a.k = coef(i); a.do_head = k + 1 < n_steps;
+      a.seed = seed; a.quad_row0 = elem0; a.stream = (unsigned)(i + 1);
+      rc = run_step(h, f.subs[u], i, a);
     }
   }
-  rc = dual_join(h, n_sub, st, rc);
-  return rc;
+  return sampler_end(h, f, rc);
 }
 
 extern "C" int bsg_diffnet_set_compute(bsg_diffnet* h, int32_t mode) {
@@ -2763,32 +2770,27 @@ static void plms_blend(int n_hist, PlmsCoef& c) {
 extern "C" int bsg_plms_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, int32_t K_step, int32_t interval, int32_t B,
                                int32_t T, void* stream) {
   GuardScope guard_scope(h ? &h->guard : nullptr);
-  TRY(check_bound(h, B, T, "plms_sample"));
-  h->last_chains = 1;   // this call's count from here on: the unfused loop and an early return never reach dual_join
-  TRY(check_schedule(s, "plms_sample", true));
+  TRY(sampler_enter(h, s, B, T, "plms_sample", true));
   BSG_REQUIRE(x && interval > 0 && K_step > 0 && K_step <= s->num_timesteps && K_step <= h->cfg.max_steps,
               "plms_sample: K_step=%d interval=%d schedule=%d", K_step, interval, s->num_timesteps);
   hipStream_t st = (hipStream_t)stream;
   const size_t n = (size_t)B * h->M * T;
   BSG_REQUIRE(h->xpred, "plms_sample: history buffers missing (bsg_diffnet_prepare allocates them)");
-  TRY(ragged_enter(h, st, "plms_sample"));
-  const StackPlan plan = plan_stack(h, B, T, st, h->bound.ragged ? PLAN_RAGGED : PLAN_WHOLE);
-  TRY(cond_layout_for(h, plan, st));
+  SamplerFrame f;
+  TRY(sampler_begin(h, f, x, B, T, st, "plms_sample"));
   const dim3 grid(cdiv((long long)n, 256)), block(256);
   // the unfused update (first iteration); ragged: on each row's own frames only
   auto plms_step = [&](const float* xi, float* xo, const float* e0, const float* e1, const float* e2, const float* e3, const PlmsCoef& k) {
-    if (plan.ragged)
+    if (f.plan.ragged)
       hipLaunchKernelGGL(plms_step_ragged_kernel, dim3(cdiv(T, 256), h->M, B), dim3(256), 0, st, xi, xo, e0, e1, e2, e3, k, (const int*)h->rg_dev, h->M, T);
     else
       hipLaunchKernelGGL(plms_step_kernel, grid, block, 0, st, xi, xo, e0, e1, e2, e3, k, (long long)n);
   };
-  const bool fused = fused_tail_ok(h);
+  const bool fused = f.tail.form != TAIL_UNFUSED;
   // history ring: hist[0] = newest
   float* hist[4] = {h->eps_hist[0], h->eps_hist[1], h->eps_hist[2], h->eps_hist[3]};
-  int n_hist = 0;
+  int n_hist = 0, rc = BSG_OK;
   const int last = ((K_step - 1) / interval) * interval;
-  SubBatch subs[2];
-  int n_sub = 0, rc = BSG_OK;   // n_sub == 0: the half-batch chains have not been forked yet
   for (int i = last; i >= 0; i -= interval) {
     const int ip = i - interval > 0 ? i - interval : 0;
     PlmsCoef c{};
@@ -2798,32 +2800,28 @@ extern "C" int bsg_plms_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
     if (n_hist > 0 && fused) {
       // fused iteration: h->xa already holds the in-projection of x (left by the previous iteration); the tail projects the skip
       // sum to eps, stores it to the history slot, applies the multistep update to x and projects the new x for the next one
-      if (n_sub == 0) {   // the first fused iteration forks the two half-batch chains (not for a ragged batch: one chain of its launch groups)
-        if (plan.ragged) { subs[0] = SubBatch{B, st, plan}; n_sub = 1; }
-        else n_sub = dual_fork(h, plan, B, T, st, subs);
-      }
-      for (int u = 0; u < n_sub && rc == BSG_OK; ++u) {
-        const size_t mo = (size_t)subs[u].plan.row0 * h->M * T;
-        TailArgs a{};
-        a.plms_hist = n_hist; a.pk = c; a.e_new = e_new + mo; a.h1 = hist[0] + mo; a.h2 = hist[1] + mo; a.h3 = hist[2] + mo;
+      if (f.n_sub == 0) dual_fork(h, f, true);   // the first fused iteration forks the two half-batch chains, not an earlier one
+      for (int u = 0; u < f.n_sub && rc == BSG_OK; ++u) {
+        TailArgs a = f.subs[u].args;
+        a.plms_hist = n_hist; a.pk = c; a.e_new = e_new; a.h1 = hist[0]; a.h2 = hist[1]; a.h3 = hist[2];
         plms_blend(n_hist, a.pk);
         a.do_head = i - interval >= 0;
-        rc = step_from_xa(h, subs[u].plan, i, a, x + mo, subs[u].B, T, subs[u].st);
+        rc = run_step(h, f.subs[u], i, a);
       }
       if (rc != BSG_OK) break;
       hist[3] = hist[2]; hist[2] = hist[1]; hist[1] = hist[0]; hist[0] = e_new;
       if (n_hist < 3) ++n_hist;
       continue;
     }
-    TRY(forward_impl(h, plan, x, nullptr, i, e_new, B, T, st));
+    TRY(forward_impl(h, f.plan, x, nullptr, i, e_new, B, T, st));
     plms_blend(n_hist, c);
     if (n_hist == 0) {
       // ragged: the predictor below writes x_pred on each row's frames only; its padding takes x's (finite, the caller's), which the
       // input projection of the second evaluation reads
-      if (plan.ragged) BSG_HIP(hipMemcpyAsync(h->xpred, x, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+      if (f.plan.ragged) BSG_HIP(hipMemcpyAsync(h->xpred, x, n * sizeof(float), hipMemcpyDeviceToDevice, st));
       plms_step((const float*)x, h->xpred, (const float*)e_new,
                          (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, c);
-      TRY(forward_impl(h, plan, h->xpred, nullptr, ip, h->eps, B, T, st));
+      TRY(forward_impl(h, f.plan, h->xpred, nullptr, ip, h->eps, B, T, st));
       c.w0 = 1.f; c.inv = 2.f;
       plms_step((const float*)x, x, (const float*)e_new, (const float*)h->eps,
                          (const float*)nullptr, (const float*)nullptr, c);
@@ -2836,7 +2834,7 @@ extern "C" int bsg_plms_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
     hist[3] = hist[2]; hist[2] = hist[1]; hist[1] = hist[0]; hist[0] = e_new;
     if (n_hist < 3) ++n_hist;
   }
-  return dual_join(h, n_sub, st, rc);
+  return sampler_end(h, f, rc);
 }
 
 // One PLMS update given the noise predictions (p_sample_plms :168-201 without the denoiser calls), for denoisers that are not a

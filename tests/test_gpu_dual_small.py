@@ -1,4 +1,4 @@
-"""GPU: the half-batch chains of channel-split launches (the `small` branch of dual_fork, csrc/diffnet.hip) against float64.
+"""GPU: the half-batch chains of channel-split launches (the `small` branch of dual_scope, csrc/diffnet.hip) against float64.
 
 A whole batch whose per-layer form would be a pair-split or 16-wave launch is decoded by the fused PLMS loop as two half batches on two
 streams, each half a chain of 4-way or pair-split launches with the un-padded LDS size, so that workgroups of both chains share CUs and
