@@ -104,7 +104,7 @@ __global__ void masked_softmax_kernel(float* __restrict__ S, const float* __rest
   if ((tid & 63) == 0) red[tid >> 6] = sum;
   __syncthreads();
   sum = (red[0] + red[1]) + (red[2] + red[3]);
-  for (int k = tid; k < Tk; k += 256) s[k] = s[k] / sum;
+  for (int k = tid; k < Tk; k += 256) s[k] = sum > 0.f ? s[k] / sum : 0.f;   // (a row without keys: 0, not 0 / 0)
 }
 
 // ---- fused self-attention (EncSALayer's MultiheadAttention, common_layers.py:282-370, head dim 128) -------------------
@@ -202,7 +202,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_kernel(const float* __r
     }
   }
   if (q_ok) {
-    const float inv = 1.0f / l;
+    const float inv = l > 0.f ? 1.0f / l : 0.f;   // a row without keys (an empty utterance of the batch): O = 0 and l = 0 give 0, not 0 x inf
     float* __restrict__ op = out + ((long long)b * T + q_row) * ldo + hh * D;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
@@ -361,7 +361,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_split_kernel(const floa
   if (q_ok && out_h) {
     // the attention output is read by the output projection only: written as the hi / lo fp16 planes of 16 x value that gemm_h2w_kernel
     // stages (registers 4 g .. 4 g + 3 of a lane are 4 consecutive d: one 8-byte store per plane)
-    const float inv = 1.0f / (l * SIN * PSC);
+    const float inv = l > 0.f ? 1.0f / (l * SIN * PSC) : 0.f;   // (a row without keys: 0, not 0 x inf)
     _Float16* __restrict__ oph = out_h + ((long long)b * T + q_row) * ldo + hh * D;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
@@ -381,7 +381,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_split_kernel(const floa
   }
   if (range_events && __builtin_amdgcn_ballot_w64(bad) != 0ull && lane == 0) atomicAdd(range_events, 1u);
   if (q_ok && !out_h) {
-    const float inv = 1.0f / (l * SIN * PSC);
+    const float inv = l > 0.f ? 1.0f / (l * SIN * PSC) : 0.f;   // (a row without keys: 0, not 0 x inf)
     float* __restrict__ op = out + ((long long)b * T + q_row) * ldo + hh * D;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
@@ -707,7 +707,7 @@ __global__ __launch_bounds__(64 * NW, 1) void flash_attn_planes_kernel(const _Fl
   if (q_ok) {
     // the attention output is read by the output projection only: hi / lo fp16 planes of 16 x value (registers 4 g .. 4 g + 3 of a lane are 4
     // consecutive d: one 8-byte store per plane)
-    const float inv = 1.0f / (l * SIN);   // l carries the 2^10 of P
+    const float inv = l > 0.f ? 1.0f / (l * SIN) : 0.f;   // l carries the 2^10 of P; a row without keys: 0, not 0 x inf
     _Float16* __restrict__ oph = out_h + ((long long)b * T + q_row) * ldo + hh * D;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
@@ -1957,7 +1957,9 @@ extern "C" int bsg_fs2midi_debug_poison_workspace(bsg_fs2midi* h, void* stream) 
 
 extern "C" int bsg_length_regulator(const int64_t* dur, const int64_t* txt, int64_t* mel2ph, int32_t B, int32_t Tt, int32_t T,
                                     void* stream) {
-  BSG_REQUIRE(dur && mel2ph && B > 0 && Tt > 0 && T > 0 && Tt <= 8192, "length_regulator: bad argument (T_txt <= 8192)");
+  BSG_REQUIRE(dur && mel2ph, "length_regulator: null %s", dur ? "mel2ph" : "dur");
+  BSG_REQUIRE(B > 0 && Tt > 0 && T > 0, "length_regulator: B=%d T_txt=%d T=%d (each must be positive)", B, Tt, T);
+  BSG_REQUIRE(Tt <= 8192, "length_regulator: T_txt=%d (at most 8192: the running sums of an utterance live in 64 KiB of LDS)", Tt);
   hipLaunchKernelGGL(length_regulator_kernel, dim3(B), dim3(256), Tt * sizeof(long long), (hipStream_t)stream,
                      (const long long*)dur, (const long long*)txt, (long long*)mel2ph, Tt, T);
   BSG_LAUNCH_CHECK();
