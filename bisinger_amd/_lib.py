@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'lib', 'libbisinger_hip.so')
 if os.environ.get('BSG_LIB'):      # development: an alternative build of the same ABI (kernel experiments)
     LIB_PATH = os.environ['BSG_LIB']
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 
 class BsgError(RuntimeError):
@@ -158,6 +158,12 @@ _SIGS = {
     'bsg_pitchext_forward': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     'bsg_pitchext_forward_ragged': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),      # lengths_host: B int32 on the host (ABI v19)
     'bsg_pitchext_debug_poison_workspace': (c_int32, [c_void_p, c_void_p]),
+    # ABI v20: the ragged front; n_tok_host / n_frames_host: B int32 on the host
+    'bsg_fs2midi_encode_ragged': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                            c_void_p, c_void_p, c_void_p, c_void_p]),
+    'bsg_fs2_encode_plain_ragged': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'bsg_fs2_decode_ragged': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                        c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'bsg_wavden_create': (c_int32, [POINTER(c_void_p), c_int32, c_int32, c_int32, c_void_p]),
     'bsg_wavden_destroy': (None, [c_void_p]),
     'bsg_wavden_forward': (c_int32, [c_void_p, c_void_p, c_void_p, POINTER(c_int32), c_int32, c_int32, c_float, c_void_p]),

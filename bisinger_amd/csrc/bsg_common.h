@@ -168,6 +168,10 @@ struct H2wArgs {
   const char** form_out;       // optional, host side only: launch_gemm_h2w stores the tile height and ring it launched ("h2w/64/ring8", a string literal) for the
                                // caller's launch record
   int no_direct;               // set by launch_gemm_h2w (BSG_H2W_DIRECT=0): the [feature][frame] output through the LDS image even where the accumulators could be stored directly
+  const int* lens;             // ragged (null everywhere but the ragged FS2 front): device, `batch` row counts, 0 <= lens[z] <= rows.  Item z reads rows < lens[z]
+                               // only (rows and tap rows at or beyond the bound read as 0), a workgroup whose first row lies beyond it returns before its
+                               // first load, and the rows at or beyond it inside a straddling tile are stored as 0.  act_is_a forms with K % 256 == 0 only.
+                               // (Last member: the fields the padded kernels read keep their offsets.)
 };
 bool h2w_supports(int rows, int Wn, int K, int taps, int lda);
 // W(tap, n, k) at src[tap * ts + n * rs + k * ks]; allocates w->pack on first use; |16 w| >= 65000 counted into *bad_dev (device word)

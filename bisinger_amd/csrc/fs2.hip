@@ -16,6 +16,7 @@
 // and simplicity; the unfused attention materialises the [B*H,T,T] score matrix in HBM.
 #include <math.h>
 
+#include <algorithm>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -28,6 +29,9 @@ namespace bsg {
 namespace {
 
 constexpr int H = 256;   // hidden size (checked at create)
+// rows of the MIDI front's fixed-size tables (diffsinger_midi/fs2.py:88-92: midi_embed, is_slur_embed, lang_embed, style_embed): what
+// fs2_create_impl copies and what the kernels that clamp an id clamp it to
+constexpr int MIDI_ROWS = 300, SLUR_ROWS = 2, LANG_ROWS = 2, STYLE_ROWS = 3;
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -40,16 +44,29 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// Ragged front (bsg_fs2midi_encode_ragged / bsg_fs2_decode_ragged): `lens` (device, one count per utterance; null = the padded call) bounds
+// utterance b by lens[b] rows while the pitch of its tensors stays T.  true: the row lies at or beyond its utterance's end.
+__device__ __forceinline__ bool row_dead(const int* __restrict__ lens, long long row, int T) {
+  if (!lens) return false;
+  const long long b = row / T;
+  return (int)(row - b * T) >= lens[b];
+}
+
 // ---- LayerNorm over C = 256: one wave per row, 4 contiguous floats per lane ---------------------
 // y = (x - mean) * rsqrt(var + eps) * w + b, then * rowscale[row] (the reference's "* nonpadding").
 using ln_f16x4 = __attribute__((ext_vector_type(4))) _Float16;
 // yh / yl (optional, instead of y): the result as hi / lo fp16 planes of 16 x value — the activation operand of gemm_h2w_kernel
 __global__ void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
                                  float* __restrict__ y, const float* __restrict__ rowscale, long long rows, float eps,
-                                 _Float16* __restrict__ yh, _Float16* __restrict__ yl, unsigned* __restrict__ range_events) {
+                                 _Float16* __restrict__ yh, _Float16* __restrict__ yl, unsigned* __restrict__ range_events,
+                                 const int* __restrict__ lens, int T) {
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int lane = threadIdx.x & 63;
+  if (row_dead(lens, row, T)) {   // ragged: nothing is read; the fp32 result is 0 (the planes are read up to the row's end only)
+    if (y) reinterpret_cast<f32x4*>(y + row * H)[lane] = f32x4{0.f, 0.f, 0.f, 0.f};
+    return;
+  }
   const f32x4 v = reinterpret_cast<const f32x4*>(x + row * H)[lane];
   const float mean = wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.0f / H);
   const float d0 = v[0] - mean, d1 = v[1] - mean, d2 = v[2] - mean, d3 = v[3] - mean;
@@ -120,7 +137,8 @@ __global__ void masked_softmax_kernel(float* __restrict__ S, const float* __rest
 // reference's masked_fill; rows are [b*T + t][3H] with Q | K | V column blocks.
 template <int NW>
 __global__ __launch_bounds__(64 * NW, 2) void flash_attn_kernel(const float* __restrict__ qkv, const float* __restrict__ keep,
-                                                                float* __restrict__ out, int T, int heads, int ld, int ldo) {
+                                                                float* __restrict__ out, int T, int heads, int ld, int ldo,
+                                                                const int* __restrict__ lens) {
   constexpr int D = 128, BK = 32, LDK = D + 1;
   __shared__ float Ks[BK * LDK];
   __shared__ __attribute__((aligned(16))) float Vs[BK * D];
@@ -129,11 +147,13 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_kernel(const float* __r
   const int l31 = lane & 31, lh = lane >> 5;
   const int b = blockIdx.y / heads, hh = blockIdx.y - b * heads;
   const int q_row = (blockIdx.x * NW + wave) * 32 + l31;
-  const bool q_ok = q_row < T;
+  const int Tb = lens ? lens[b] : T;              // ragged: queries and keys of this utterance end at lens[b]; T stays the pitch
+  if ((int)blockIdx.x * NW * 32 >= Tb) return;    // (ragged only: the whole query tile lies beyond the utterance: nothing is loaded)
+  const bool q_ok = q_row < Tb;
   const float* __restrict__ base = qkv + (long long)b * T * ld + hh * D;
   float qreg[64];
   {
-    const float* __restrict__ qp = base + (long long)(q_ok ? q_row : T - 1) * ld;
+    const float* __restrict__ qp = base + (long long)(q_ok ? q_row : Tb - 1) * ld;
 #pragma unroll
     for (int s = 0; s < 64; ++s) qreg[s] = qp[2 * s + lh];
   }
@@ -144,7 +164,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_kernel(const float* __r
     for (int r = 0; r < 16; ++r) O[dt][r] = 0.f;
   float m = -INFINITY, l = 0.f;
   const int H3 = ld / 3;
-  for (int k0 = 0; k0 < T; k0 += BK) {
+  for (int k0 = 0; k0 < Tb; k0 += BK) {
     __syncthreads();   // the previous block's tiles are consumed
 #pragma unroll
     for (int j = 0; j < 1024 / (64 * NW); ++j) {
@@ -152,7 +172,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_kernel(const float* __r
       const int key = idx >> 5, c4 = (idx & 31) << 2;
       const int kt = k0 + key;
       f32x4 kv = {0.f, 0.f, 0.f, 0.f}, vv = kv;
-      if (kt < T) {
+      if (kt < Tb) {
         const float* __restrict__ rp = base + (long long)kt * ld + c4;
         kv = *reinterpret_cast<const f32x4*>(rp + H3);
         vv = *reinterpret_cast<const f32x4*>(rp + 2 * H3);
@@ -160,7 +180,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_kernel(const float* __r
       Ks[key * LDK + c4] = kv[0]; Ks[key * LDK + c4 + 1] = kv[1]; Ks[key * LDK + c4 + 2] = kv[2]; Ks[key * LDK + c4 + 3] = kv[3];
       *reinterpret_cast<f32x4*>(&Vs[key * D + c4]) = vv;
     }
-    if (tid < BK) kp[tid] = (k0 + tid < T) ? keep[(long long)b * T + k0 + tid] : 0.f;
+    if (tid < BK) kp[tid] = (k0 + tid < Tb) ? keep[(long long)b * T + k0 + tid] : 0.f;
     __syncthreads();
     f32x16 S;
 #pragma unroll
@@ -230,7 +250,7 @@ template <int NW>
 __global__ __launch_bounds__(64 * NW, 2) void flash_attn_split_kernel(const float* __restrict__ qkv, const float* __restrict__ keep,
                                                                       float* __restrict__ out, int T, int heads, int ld, int ldo,
                                                                       unsigned* __restrict__ range_events, _Float16* __restrict__ out_h,
-                                                                      long long out_plane) {
+                                                                      long long out_plane, const int* __restrict__ lens) {
   constexpr int D = 128, BK = 32, KROW = 2 * D + 16, VROW = 2 * BK + 16;   // bytes per LDS row: 272 (68 dwords = 4 mod 64), 80
   constexpr float SIN = 16.0f, PSC = 1024.0f;
   __shared__ __attribute__((aligned(16))) char Kp[2 * BK * KROW];    // hi plane, lo plane
@@ -240,7 +260,9 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_split_kernel(const floa
   const int l31 = lane & 31, lh = lane >> 5;
   const int b = blockIdx.y / heads, hh = blockIdx.y - b * heads;
   const int q_row = (blockIdx.x * NW + wave) * 32 + l31;
-  const bool q_ok = q_row < T;
+  const int Tb = lens ? lens[b] : T;              // ragged: queries and keys of this utterance end at lens[b]; T stays the pitch
+  if ((int)blockIdx.x * NW * 32 >= Tb) return;    // (ragged only: the whole query tile lies beyond the utterance: nothing is loaded)
+  const bool q_ok = q_row < Tb;
   const float* __restrict__ base = qkv + (long long)b * T * ld + hh * D;
   bool bad = false;
   auto split8 = [&](const f32x4 a, const f32x4 c, f16x8& hi, f16x8& lo) {
@@ -254,7 +276,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_split_kernel(const floa
   };
   f16x8 qh[8], ql[8];   // d = 16 s + 8 lh + 0..7
   {
-    const float* __restrict__ qp = base + (long long)(q_ok ? q_row : T - 1) * ld + 8 * lh;
+    const float* __restrict__ qp = base + (long long)(q_ok ? q_row : Tb - 1) * ld + 8 * lh;
 #pragma unroll
     for (int s = 0; s < 8; ++s)
       split8(*reinterpret_cast<const f32x4*>(qp + 16 * s), *reinterpret_cast<const f32x4*>(qp + 16 * s + 4), qh[s], ql[s]);
@@ -266,7 +288,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_split_kernel(const floa
     for (int r = 0; r < 16; ++r) O[dt][r] = 0.f;
   float m = -INFINITY, l = 0.f;
   const int H3 = ld / 3;
-  for (int k0 = 0; k0 < T; k0 += BK) {
+  for (int k0 = 0; k0 < Tb; k0 += BK) {
     __syncthreads();   // the previous block's tiles are consumed
 #pragma unroll 2
     for (int j = 0; j < 1024 / (64 * NW); ++j) {
@@ -274,7 +296,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_split_kernel(const floa
       const int key = idx >> 5, c4 = (idx & 31) << 2;
       const int kt = k0 + key;
       f32x4 kv = {0.f, 0.f, 0.f, 0.f}, vv = kv;
-      if (kt < T) {
+      if (kt < Tb) {
         const float* __restrict__ rp = base + (long long)kt * ld + c4;
         kv = *reinterpret_cast<const f32x4*>(rp + H3);
         vv = *reinterpret_cast<const f32x4*>(rp + 2 * H3);
@@ -293,7 +315,7 @@ __global__ __launch_bounds__(64 * NW, 2) void flash_attn_split_kernel(const floa
       *reinterpret_cast<f16x4*>(Kp + key * KROW + c4 * 2) = kh4;
       *reinterpret_cast<f16x4*>(Kp + BK * KROW + key * KROW + c4 * 2) = kl4;
     }
-    if (tid < BK) kp[tid] = (k0 + tid < T) ? keep[(long long)b * T + k0 + tid] : 0.f;
+    if (tid < BK) kp[tid] = (k0 + tid < Tb) ? keep[(long long)b * T + k0 + tid] : 0.f;
     __syncthreads();
     f32x16 S;
 #pragma unroll
@@ -483,7 +505,7 @@ __global__ __launch_bounds__(64 * NW, 1) void flash_attn_planes_kernel(const _Fl
                                                                        const unsigned* __restrict__ kmask, int T, int Tp, int heads,
                                                                        _Float16* __restrict__ out_h, long long out_plane, int ldo,
                                                                        unsigned* __restrict__ range_events, float* __restrict__ part,
-                                                                       unsigned* __restrict__ cnt) {
+                                                                       unsigned* __restrict__ cnt, const int* __restrict__ lens) {
   constexpr int D = 128, BK = 32, KROW = 2 * D + 16, VROW = 2 * BK + 16;   // bytes per LDS row: 272 (68 dwords = 4 mod 64), 80
   constexpr int KB = 2 * BK * KROW, VB = 2 * D * VROW;                     // K hi | K lo, V^T hi | V^T lo of one key block
   constexpr int NTH = 64 * NW, NPC = 1024 / NTH;                           // 16-byte pieces of a block's K (or V^T) per thread
@@ -494,13 +516,19 @@ __global__ __launch_bounds__(64 * NW, 1) void flash_attn_planes_kernel(const _Fl
   const int l31 = lane & 31, lh = lane >> 5;
   const int b = blockIdx.y / heads, hh = blockIdx.y - b * heads;
   const int q_row = (blockIdx.x * NW + wave) * 32 + l31;
-  const bool q_ok = q_row < T;
+  // ragged: queries and keys of this utterance end at lens[b]; T and Tp stay the pitches.  A query tile beyond the end returns before it loads
+  // anything (all gridDim.z workgroups of the tile alike: the arrival counter stays 0).  Key blocks at or beyond the end are staged (the
+  // pipeline below is unconditional) but never scored into a result; inside the last block the keys beyond the end are masked (kmask) and
+  // their K / V rows are the zeros the QKV product stores there.
+  const int Tb = lens ? lens[b] : T;
+  if ((int)blockIdx.x * NW * 32 >= Tb) return;
+  const bool q_ok = q_row < Tb;
   const _Float16* __restrict__ qkb = qk + (long long)b * T * (2 * H) + hh * D;          // Q of this head; K at + H
   const _Float16* __restrict__ vtb = vt + ((long long)b * H + hh * D) * Tp;
   const unsigned* __restrict__ kmb = kmask + b * (Tp / 32);
   f16x8 qh[8], ql[8];   // d = 16 s + 8 lh + 0..7
   {
-    const _Float16* qp = qkb + (long long)(q_ok ? q_row : T - 1) * (2 * H) + 8 * lh;
+    const _Float16* qp = qkb + (long long)(q_ok ? q_row : Tb - 1) * (2 * H) + 8 * lh;
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
       qh[s] = *reinterpret_cast<const f16x8*>(qp + 16 * s);
@@ -634,7 +662,7 @@ __global__ __launch_bounds__(64 * NW, 1) void flash_attn_planes_kernel(const _Fl
   // partial (O, m, l); the last of the KS workgroups to arrive combines them in the order of z (below)
   const int KS = (int)gridDim.z;
   const int nbz = (Tp / BK + KS - 1) / KS;
-  const int kbeg = (int)blockIdx.z * nbz * BK, kend = min(T, kbeg + nbz * BK);
+  const int kbeg = (int)blockIdx.z * nbz * BK, kend = min(Tb, kbeg + nbz * BK);
   load_k(kbeg);
   store_k(0);
   load_k(kbeg + BK);
@@ -789,6 +817,49 @@ __global__ void embed_finish_kernel(const float* __restrict__ x0, const float* _
   if (lane == 0) keep[row] = kp;
 }
 
+// The ragged MIDI front (bsg_fs2midi_encode_ragged), embed_tokens_kernel + embed_finish_kernel in one launch: token j of utterance b with
+// j < lens[b] gets the same sum in the same order, its ESM term gathered from the two-row table esm_tab[lang] (the ESM of the utterance
+// alone: esm_alone_table below).  Beyond an utterance's end only the key mask is written and no input is read.  Ids outside their tables are
+// clamped (torch raises): no read out of bounds.
+__global__ void embed_ragged_kernel(const long long* __restrict__ txt, const long long* __restrict__ lang,
+                                    const long long* __restrict__ pitch_midi, const float* __restrict__ midi_dur,
+                                    const long long* __restrict__ is_slur, const float* __restrict__ Etok, const float* __restrict__ esm_tab,
+                                    const float* __restrict__ Emidi, const float* __restrict__ Wdur, const float* __restrict__ bdur,
+                                    const float* __restrict__ Eslur, const float* __restrict__ pe, float* __restrict__ x,
+                                    float* __restrict__ keep, long long rows, int Tt, float scale, int vocab, const int* __restrict__ lens) {
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int lane = threadIdx.x & 63;
+  const long long b = row / Tt;
+  const int j = (int)(row - b * Tt);
+  if (j >= lens[b]) {
+    if (lane == 0) keep[row] = 0.f;
+    return;
+  }
+  auto clampi = [](long long i, int n) { return i < 0 ? 0ll : i < n ? i : (long long)n - 1; };
+  const long long tok = clampi(txt[row], vocab);
+  const float kp = tok != 0 ? 1.f : 0.f;
+  f32x4 a = reinterpret_cast<const f32x4*>(Etok + tok * H)[lane];
+  a *= scale;
+  const f32x4 mi = reinterpret_cast<const f32x4*>(Emidi + clampi(pitch_midi[row], MIDI_ROWS) * H)[lane];
+  const f32x4 wd = reinterpret_cast<const f32x4*>(Wdur)[lane], bd = reinterpret_cast<const f32x4*>(bdur)[lane];
+  const f32x4 sl = reinterpret_cast<const f32x4*>(Eslur + clampi(is_slur[row], SLUR_ROWS) * H)[lane];
+  const f32x4 dy = reinterpret_cast<const f32x4*>(esm_tab + clampi(lang[row], LANG_ROWS) * H)[lane];
+  const f32x4 pv = reinterpret_cast<const f32x4*>(pe + (long long)j * H)[lane];
+  const float md = midi_dur[row];
+  f32x4 o;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float v = __fadd_rn(a[e], mi[e]);
+    v = __fadd_rn(v, __fadd_rn(__fmul_rn(md, wd[e]), bd[e]));
+    v = __fadd_rn(v, sl[e]);
+    v = __fadd_rn(v, dy[e]);
+    o[e] = __fadd_rn(__fmul_rn(v, scale), pv[e]) * kp;
+  }
+  reinterpret_cast<f32x4*>(x + row * H)[lane] = o;
+  if (lane == 0) keep[row] = kp;
+}
+
 // ---- ESM attention over the BATCH axis (reference quirk, common_layers.py:853) --------------------
 // q,k,v: [L=B][N=Tt][H]; for every (n, head) softmax over the L keys.  One thread per (l, n, head).
 // q / o hold the Lq QUERY utterances only (all L of them, or a rank's rows: bsg_fs2midi_encode_rows); k / v all L.
@@ -918,9 +989,9 @@ __global__ __launch_bounds__(256) void esm_attention_wave_kernel(const float* __
 // dur_inp = (enc + spk) * src_keep                                                    (fs2.py:164)
 __global__ void add_spk_kernel(const float* __restrict__ enc, const long long* __restrict__ spk_id,
                                const float* __restrict__ Espk, const float* __restrict__ keep, float* __restrict__ out,
-                               long long rows, int Tt) {
+                               long long rows, int Tt, const int* __restrict__ lens) {
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
+  if (row >= rows || row_dead(lens, row, Tt)) return;   // (ragged: the predictor's convolutions read a row up to its end only)
   const int lane = threadIdx.x & 63;
   const int b = (int)(row / Tt);
   f32x4 e = reinterpret_cast<const f32x4*>(enc + row * H)[lane];
@@ -933,14 +1004,19 @@ __global__ void add_spk_kernel(const float* __restrict__ enc, const long long* _
 __global__ void gather_frames_kernel(const float* __restrict__ enc, const long long* __restrict__ mel2ph,
                                      const long long* __restrict__ spk_id, const long long* __restrict__ style_id,
                                      const float* __restrict__ Espk, const float* __restrict__ Estyle,
-                                     float* __restrict__ out, long long rows, int T, int Tt) {
+                                     float* __restrict__ out, long long rows, int T, int Tt, const int* __restrict__ lens_f,
+                                     const int* __restrict__ lens_t) {
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int lane = threadIdx.x & 63;
   const int b = (int)(row / T);
+  if (row_dead(lens_f, row, T)) {   // ragged: a frame beyond its utterance's end is 0 and reads nothing
+    reinterpret_cast<f32x4*>(out + row * H)[lane] = f32x4{0.f, 0.f, 0.f, 0.f};
+    return;
+  }
   const long long ph = mel2ph[row];
   f32x4 e = {0.f, 0.f, 0.f, 0.f};
-  if (ph > 0 && ph <= Tt) e = reinterpret_cast<const f32x4*>(enc + ((long long)b * Tt + (ph - 1)) * H)[lane];
+  if (ph > 0 && ph <= (lens_t ? lens_t[b] : Tt)) e = reinterpret_cast<const f32x4*>(enc + ((long long)b * Tt + (ph - 1)) * H)[lane];
   if (Espk) e = e + reinterpret_cast<const f32x4*>(Espk + spk_id[b] * H)[lane];       // (the plain front: no style row, possibly no speaker table)
   if (Estyle) e = e + reinterpret_cast<const f32x4*>(Estyle + style_id[b] * H)[lane];
   const float kp = ph > 0 ? 1.f : 0.f;
@@ -970,25 +1046,32 @@ __global__ void token_rows_kernel(const float* __restrict__ enc, const long long
 // FFTBlocks entry for the decoder (tts_modules.py:289-297): padding = (sum |x| == 0), positions =
 // cumsum(x[...,0] != 0) * (x[...,0] != 0) (utils/__init__.py:146-158), x = (x + alpha * table[pos]) * keep.
 // One wave per utterance scans T in 64-frame chunks; then every lane copies rows.
-__global__ void decoder_positions_kernel(const float* __restrict__ x, int* __restrict__ pos, float* __restrict__ keep, int T) {
+__global__ void decoder_positions_kernel(const float* __restrict__ x, int* __restrict__ pos, float* __restrict__ keep, int T,
+                                         const int* __restrict__ lens) {
   const int b = blockIdx.x, lane = threadIdx.x;   // 64 threads
+  const int Tb = lens ? lens[b] : T;              // (ragged: the scan stops at the utterance's end)
   int carry = 0;
-  for (int t0 = 0; t0 < T; t0 += 64) {
+  for (int t0 = 0; t0 < Tb; t0 += 64) {
     const int t = t0 + lane;
     bool nz = false;
-    if (t < T) nz = x[((long long)b * T + t) * H] != 0.f;
+    if (t < Tb) nz = x[((long long)b * T + t) * H] != 0.f;
     const unsigned long long bal = __ballot(nz);
     const int pre = __popcll(bal & ((1ull << lane) - 1ull)) + (nz ? 1 : 0);
-    if (t < T) pos[(long long)b * T + t] = nz ? carry + pre : 0;
+    if (t < Tb) pos[(long long)b * T + t] = nz ? carry + pre : 0;
     carry += __popcll(bal);
   }
   (void)keep;
 }
 __global__ void decoder_entry_kernel(float* __restrict__ x, const int* __restrict__ pos, const float* __restrict__ table,
-                                     const float* __restrict__ alpha, float* __restrict__ keep, long long rows, int n_pos) {
+                                     const float* __restrict__ alpha, float* __restrict__ keep, long long rows, int n_pos,
+                                     const int* __restrict__ lens, int T) {
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int lane = threadIdx.x & 63;
+  if (row_dead(lens, row, T)) {   // ragged: only the key mask is written beyond an utterance's end
+    if (lane == 0) keep[row] = 0.f;
+    return;
+  }
   f32x4 v = reinterpret_cast<const f32x4*>(x + row * H)[lane];
   const float asum = wave_sum(fabsf(v[0]) + fabsf(v[1]) + fabsf(v[2]) + fabsf(v[3]));
   const float kp = asum == 0.f ? 0.f : 1.f;
@@ -1004,9 +1087,14 @@ __global__ void decoder_entry_kernel(float* __restrict__ x, const int* __restric
 
 // ---- duration predictor tail + length regulator --------------------------------------------------
 // dur = clamp(round(exp(xs) - 1), min=0) with xs already masked                       (tts_modules.py:124-129)
-__global__ void dur_from_log_kernel(const float* __restrict__ xs, long long* __restrict__ dur, long long n) {
+__global__ void dur_from_log_kernel(float* __restrict__ xs, long long* __restrict__ dur, long long n, const int* __restrict__ lens, int Tt) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  if (row_dead(lens, i, Tt)) {   // ragged: no launch wrote xs beyond an utterance's end
+    xs[i] = 0.f;
+    dur[i] = 0;
+    return;
+  }
   const float d = rintf(expf(xs[i]) - 1.0f);
   dur[i] = d > 0.f ? (long long)d : 0;
 }
@@ -1047,10 +1135,11 @@ __global__ void repack_conv_kernel(const float* __restrict__ w, float* __restric
   out[i] = w[((long long)m * Cin + c) * k + tap];
 }
 
-__global__ void mask_rows_by_index_kernel(float* __restrict__ x, const long long* __restrict__ idx, long long rows, int width) {
+__global__ void mask_rows_by_index_kernel(float* __restrict__ x, const long long* __restrict__ idx, long long rows, int width,
+                                          const int* __restrict__ lens, int T) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= rows * width) return;
-  if (idx[i / width] <= 0) x[i] = 0.f;
+  if (row_dead(lens, i / width, T) || idx[i / width] <= 0) x[i] = 0.f;   // (ragged: idx is not read beyond an utterance's end)
 }
 
 // ---- plain FastSpeech2 front (FastspeechEncoder.forward_embedding, tts_modules.py:342-349) -------------------------------------------
@@ -1058,12 +1147,17 @@ __global__ void mask_rows_by_index_kernel(float* __restrict__ x, const long long
 // token ids, utils/__init__.py:146-158; pad id 0 -> row 0 of the table, which is zero) and keep = (txt != 0) (FFTBlocks :297).  One wave per
 // token: it counts the non-pad tokens before it with ballots over 64-token pieces of its utterance (8-byte reads, T_txt is a few hundred).
 __global__ void token_front_kernel(const long long* __restrict__ txt, const float* __restrict__ Etok, const float* __restrict__ table,
-                                   float* __restrict__ x, float* __restrict__ keep, long long rows, int Tt, float scale, int n_pos, int vocab) {
+                                   float* __restrict__ x, float* __restrict__ keep, long long rows, int Tt, float scale, int n_pos, int vocab,
+                                   const int* __restrict__ lens) {
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int lane = threadIdx.x & 63;
   const long long b = row / Tt;
   const int j = (int)(row - b * Tt);
+  if (lens && j >= lens[b]) {   // ragged: only the key mask is written beyond an utterance's end; its tokens are not read
+    if (lane == 0) keep[row] = 0.f;
+    return;
+  }
   const long long* __restrict__ tb = txt + b * Tt;
   int cnt = 0;
   for (int t0 = 0; t0 <= j; t0 += 64) {
@@ -1090,40 +1184,42 @@ __global__ void token_front_kernel(const long long* __restrict__ txt, const floa
 // a speaker / style id outside its table is clamped (torch raises): the new kernels never read out of bounds
 __device__ __forceinline__ long long clamp_id(long long i, int n) { return i < 0 ? 0 : i < n ? i : n - 1; }
 __device__ __forceinline__ float pitch_inp0(const float* __restrict__ enc, const long long* __restrict__ mel2ph, const float* __restrict__ spk,
-                                            long long b, long long row, int Tt) {
+                                            long long b, long long row, int Tt, int ntok) {
   const long long ph = mel2ph[row];
   float e = 0.f;
-  if (ph > 0 && ph <= Tt) e = enc[(b * Tt + (ph - 1)) * H];
+  if (ph > 0 && ph <= ntok) e = enc[(b * Tt + (ph - 1)) * H];
   if (spk) e = e + spk[0];
   return e * (ph > 0 ? 1.f : 0.f);
 }
 __global__ void pitch_positions_kernel(const float* __restrict__ enc, const long long* __restrict__ mel2ph,
                                        const long long* __restrict__ spk_id, const float* __restrict__ Espk, int* __restrict__ pos, int T,
-                                       int Tt, int spk_rows) {
+                                       int Tt, int spk_rows, const int* __restrict__ lens_f, const int* __restrict__ lens_t) {
   const int b = blockIdx.x, lane = threadIdx.x;   // 64 threads
   const float* spk = Espk ? Espk + clamp_id(spk_id[b], spk_rows) * H : nullptr;
+  const int Tb = lens_f ? lens_f[b] : T, ntok = lens_t ? lens_t[b] : Tt;   // (ragged: the scan stops at the utterance's end)
   int carry = 0;
-  for (int t0 = 0; t0 < T; t0 += 64) {
+  for (int t0 = 0; t0 < Tb; t0 += 64) {
     const int t = t0 + lane;
     bool nz = false;
-    if (t < T) nz = pitch_inp0(enc, mel2ph, spk, b, (long long)b * T + t, Tt) != 0.f;
+    if (t < Tb) nz = pitch_inp0(enc, mel2ph, spk, b, (long long)b * T + t, Tt, ntok) != 0.f;
     const unsigned long long bal = __ballot(nz);
     const int pre = __popcll(bal & ((1ull << lane) - 1ull)) + (nz ? 1 : 0);
-    if (t < T) pos[(long long)b * T + t] = nz ? carry + pre : 0;
+    if (t < Tb) pos[(long long)b * T + t] = nz ? carry + pre : 0;
     carry += __popcll(bal);
   }
 }
 // x = pitch_inp + alpha * table[pos]: the predictor's input, one wave per frame.  Padded frames (pitch_inp == 0) take row 0 of the table (zero).
 __global__ void pitch_entry_kernel(const float* __restrict__ enc, const long long* __restrict__ mel2ph, const long long* __restrict__ spk_id,
                                    const float* __restrict__ Espk, const int* __restrict__ pos, const float* __restrict__ table,
-                                   const float* __restrict__ alpha, float* __restrict__ x, long long rows, int T, int Tt, int n_pos, int spk_rows) {
+                                   const float* __restrict__ alpha, float* __restrict__ x, long long rows, int T, int Tt, int n_pos, int spk_rows,
+                                   const int* __restrict__ lens_f, const int* __restrict__ lens_t) {
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
+  if (row >= rows || row_dead(lens_f, row, T)) return;   // (ragged: the predictor reads a row up to its end only)
   const int lane = threadIdx.x & 63;
   const long long b = row / T;
   const long long ph = mel2ph[row];
   f32x4 e = {0.f, 0.f, 0.f, 0.f};
-  if (ph > 0 && ph <= Tt) e = reinterpret_cast<const f32x4*>(enc + (b * Tt + (ph - 1)) * H)[lane];
+  if (ph > 0 && ph <= (lens_t ? lens_t[b] : Tt)) e = reinterpret_cast<const f32x4*>(enc + (b * Tt + (ph - 1)) * H)[lane];
   if (Espk) e = e + reinterpret_cast<const f32x4*>(Espk + clamp_id(spk_id[b], spk_rows) * H)[lane];
   e = e * (ph > 0 ? 1.f : 0.f);
   int p = pos[row];
@@ -1157,11 +1253,21 @@ __global__ void pitch_tail_kernel(const float* __restrict__ c, const float* __re
                                   const long long* __restrict__ mel2ph, const long long* __restrict__ spk_id,
                                   const long long* __restrict__ style_id, const float* __restrict__ Espk, const float* __restrict__ Estyle,
                                   const float* __restrict__ Epitch, float* __restrict__ pitch_pred, float* __restrict__ f0_denorm,
-                                  long long* __restrict__ bins, float* __restrict__ out, long long rows, int T, int Tt, int spk_rows) {
+                                  long long* __restrict__ bins, float* __restrict__ out, long long rows, int T, int Tt, int spk_rows,
+                                  const int* __restrict__ lens_f, const int* __restrict__ lens_t) {
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int lane = threadIdx.x & 63;
   const long long b = row / T;
+  if (row_dead(lens_f, row, T)) {   // ragged: beyond an utterance's end nothing is read; floats are 0, the bin is f0_to_coarse(0) = 1
+    if (lane == 0) {
+      if (pitch_pred) { pitch_pred[2 * row] = 0.f; pitch_pred[2 * row + 1] = 0.f; }
+      if (f0_denorm) f0_denorm[row] = 0.f;
+      if (bins) bins[row] = 1;
+    }
+    reinterpret_cast<f32x4*>(out + row * H)[lane] = f32x4{0.f, 0.f, 0.f, 0.f};
+    return;
+  }
   const f32x4 v = reinterpret_cast<const f32x4*>(c + row * H)[lane];
   const float mean = wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.0f / H);
   const float d0 = v[0] - mean, d1 = v[1] - mean, d2 = v[2] - mean, d3 = v[3] - mean;
@@ -1186,10 +1292,10 @@ __global__ void pitch_tail_kernel(const float* __restrict__ c, const float* __re
     if (bins) bins[row] = bin;
   }
   f32x4 e = {0.f, 0.f, 0.f, 0.f};
-  if (ph > 0 && ph <= Tt) e = reinterpret_cast<const f32x4*>(enc + (b * Tt + (ph - 1)) * H)[lane];
+  if (ph > 0 && ph <= (lens_t ? lens_t[b] : Tt)) e = reinterpret_cast<const f32x4*>(enc + (b * Tt + (ph - 1)) * H)[lane];
   e = e + reinterpret_cast<const f32x4*>(Epitch + bin * H)[lane];
   if (Espk) e = e + reinterpret_cast<const f32x4*>(Espk + clamp_id(spk_id[b], spk_rows) * H)[lane];
-  if (Estyle) e = e + reinterpret_cast<const f32x4*>(Estyle + clamp_id(style_id[b], 3) * H)[lane];
+  if (Estyle) e = e + reinterpret_cast<const f32x4*>(Estyle + clamp_id(style_id[b], STYLE_ROWS) * H)[lane];
   e = e * (ph > 0 ? 1.f : 0.f);
   reinterpret_cast<f32x4*>(out + row * H)[lane] = e;
 }
@@ -1239,6 +1345,9 @@ struct bsg_fs2midi {
   size_t cap_fsk = 0, cap_fcnt = 0;
   unsigned* pack_bad = nullptr;                      // device word: packed weights beyond the fp16 range (then the pre-split GEMMs are not used)
   bool h2w_ok = false;
+  int *w_lens_t = nullptr, *w_lens_f = nullptr;      // ragged calls: the utterances' token and frame counts on the device, filled by the call itself (lens_fill)
+  size_t cap_lens = 0;
+  float* esm_scr = nullptr;                          // MIDI front: [6][2][H] scratch of the two-row ESM table of the ragged encode (esm_alone_table)
   int last_token_rows = 0;   // rows (utterances x tokens) the last encode ran its encoder on; rows of the last FFT stack (bsg_fs2midi_last_rows)
   int last_stack_rows = 0;
   std::string path;          // the launch forms of the last encode and of the decode after it (bsg_fs2midi_last_path, bsg_fftden_last_path)
@@ -1282,6 +1391,7 @@ static std::vector<WsBuf> ws_table(bsg_fs2midi* h) {
       {&h->cap_scores, (void**)&h->w_scores, f, 0, WS_POISON},
       {&h->cap_fsk, (void**)&h->w_fsk, f, 0, WS_POISON},
       {&h->cap_fcnt, (void**)&h->w_fcnt, sizeof(unsigned), 0, WS_ZERO},
+      {&h->cap_lens, (void**)&h->w_lens_t, sizeof(int)},          {&h->cap_lens, (void**)&h->w_lens_f, sizeof(int)},
   };
 }
 // (the capacity test comes first, so that a call that grows nothing builds no table)
@@ -1437,12 +1547,13 @@ static int fs2_create_impl(bsg_fs2midi* h, const void* const* w, const float* de
   TRY(fs2_copy(h, &h->enc_lnw, w[i++], H, st));
   TRY(fs2_copy(h, &h->enc_lnb, w[i++], H, st));
   i += 1 + 12;  // encoder.embed_tokens / encoder.esm.*: aliases of encoder_embed_tokens / esm.* (fs2.py:84-87)
-  TRY(fs2_copy(h, &h->Emidi, w[i++], (size_t)300 * H, st));
+  TRY(fs2_copy(h, &h->Emidi, w[i++], (size_t)MIDI_ROWS * H, st));
   TRY(fs2_copy(h, &h->Wdur, w[i++], H, st));
   TRY(fs2_copy(h, &h->bdur, w[i++], H, st));
-  TRY(fs2_copy(h, &h->Eslur, w[i++], (size_t)2 * H, st));
-  TRY(fs2_copy(h, &h->Elang, w[i++], (size_t)2 * H, st));
-  TRY(fs2_copy(h, &h->Estyle, w[i++], (size_t)3 * H, st));
+  TRY(fs2_copy(h, &h->Eslur, w[i++], (size_t)SLUR_ROWS * H, st));
+  TRY(fs2_copy(h, &h->Elang, w[i++], (size_t)LANG_ROWS * H, st));
+  TRY(fs2_copy(h, &h->Estyle, w[i++], (size_t)STYLE_ROWS * H, st));
+  TRY(own_alloc(h->owned, &h->esm_scr, (size_t)6 * 2 * H));
   return create_tail(h, dec_table, rel_table, pitch_table, st);
 }
 
@@ -1539,36 +1650,48 @@ static void path_name(bsg_fs2midi* h, bool first, const char* stack, const char*
   h->path.append(stack).append(site).append(form);
 }
 
+// lens / T (ragged calls): the batched form (M = T, batch = rows / T) bounded per utterance by GemmArgs::lens — rows at or beyond an
+// utterance's end are neither read nor written, and a tile beyond it returns before its first load
 static int linear(const float* X, const float* W, const float* bias, float* Y, long long rows, int N, int K, int act,
                   const float* R, const float* rowscale, hipStream_t st, float alpha = 1.f, int alpha_ncols = 0,
-                  bsg_fs2midi* rec = nullptr, const char* tag = "") {
+                  bsg_fs2midi* rec = nullptr, const char* tag = "", const int* lens = nullptr, int T = 0) {
   GemmArgs g{};
   g.A = X; g.B = W; g.C = Y; g.M = (int)rows; g.N = N; g.K = K; g.lda = K; g.ldb = K; g.ldc = N; g.trans_b = 1; g.taps = 1;
   g.bias_n = bias; g.alpha = alpha; g.alpha_ncols = alpha_ncols; g.act = act; g.R = R; g.ldr = N; g.rowscale = rowscale; g.batch = 1;
+  if (lens) {
+    g.M = T; g.batch = (int)(rows / T); g.sA = (long long)T * K; g.sC = (long long)T * N; g.sR = (long long)T * N; g.sRS = T; g.lens = lens;
+  }
   return gemm_rec(rec, tag, g, st);
 }
 
-static int ln(const float* x, const float* w, const float* b, float* y, const float* rowscale, long long rows, float eps, hipStream_t st) {
+// lens / T (ragged calls; null = padded): rows at or beyond their utterance's end are not read, y is 0 there
+static int ln(const float* x, const float* w, const float* b, float* y, const float* rowscale, long long rows, float eps, hipStream_t st,
+              const int* lens = nullptr, int T = 0) {
   hipLaunchKernelGGL(layernorm_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, x, w, b, y, rowscale, rows, eps, (_Float16*)nullptr,
-                     (_Float16*)nullptr, (unsigned*)nullptr);
+                     (_Float16*)nullptr, (unsigned*)nullptr, lens, T);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
 }
 // LayerNorm whose result is read by a pre-split GEMM only: hi / lo fp16 planes [2][rows][H]
-static int ln_planes(const float* x, const float* w, const float* b, unsigned short* planes, long long rows, float eps, hipStream_t st) {
+static int ln_planes(const float* x, const float* w, const float* b, unsigned short* planes, long long rows, float eps, hipStream_t st,
+                     const int* lens = nullptr, int T = 0) {
   hipLaunchKernelGGL(layernorm_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, x, w, b, (float*)nullptr, (const float*)nullptr, rows, eps,
-                     reinterpret_cast<_Float16*>(planes), reinterpret_cast<_Float16*>(planes) + rows * H, gemm_range_counter());
+                     reinterpret_cast<_Float16*>(planes), reinterpret_cast<_Float16*>(planes) + rows * H, gemm_range_counter(), lens, T);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
 }
 // y[rows][N] = epi(planes[rows][K] W^T): Linear through gemm_h2w_kernel (W pre-split); `planes_out`: the result as planes [2][rows][N] instead
 static int linear_h2w(bsg_fs2midi* rec, const char* tag, const unsigned short* planes, const H2wWeights& W, int N, const float* bias, float* Y, unsigned short* planes_out, long long rows,
                       int act, const float* R, const float* rowscale, hipStream_t st, float alpha = 1.f, int alpha_ncols = 0,
-                      long long act_plane = 0) {
+                      long long act_plane = 0, const int* lens = nullptr, int T = 0) {
   H2wArgs g{};
   g.act = planes; g.act_plane = act_plane ? act_plane : rows * W.K; g.lda = W.K; g.wpack = W.pack; g.rows = (int)rows; g.K = W.K; g.Wn = W.Wn; g.taps = 1;
   g.act_is_a = 1; g.C = Y; g.ldc = N; g.out = planes_out; g.out_plane = rows * N; g.ldo = N; g.bias = bias; g.alpha = alpha;
   g.alpha_ncols = alpha_ncols; g.act_fn = act; g.R = R; g.ldr = N; g.rowscale = rowscale; g.batch = 1;
+  if (lens) {   // ragged: one batch item per utterance, bounded by H2wArgs::lens
+    g.rows = T; g.batch = (int)(rows / T); g.sAct = (long long)T * W.K; g.sC = (long long)T * N; g.sO = (long long)T * N; g.sR = (long long)T * N;
+    g.sRS = T; g.lens = lens;
+  }
   return h2w_rec(rec, tag, g, st);
 }
 
@@ -1617,7 +1740,10 @@ struct FftPlan {
 
 // Pure: reads the handle (h2w_ok, heads, its workspace pointers, gemm_split_enabled() under the call's guard scope), the switches and the
 // shape; writes nothing, allocates and launches nothing.  Every threshold is a workgroup count of the shape against a constant.
-static FftPlan plan_fft(const bsg_fs2midi* h, int B, int T, int ksz) {
+// ragged: the call carries per-utterance lengths.  The attention's thresholds are those of the padded call at (B, T); the forms that are not
+// built with lengths (the score tensor, qkv_split_kernel) are not chosen: the ragged entries refuse, before any device call, where the
+// score tensor would be the only one left (rag_plan_check).
+static FftPlan plan_fft(const bsg_fs2midi* h, int B, int T, int ksz, bool ragged = false) {
   const FftSwitches& sw = fft_switches();
   FftPlan p{};
   p.B = B; p.T = T; p.Tp = cdiv(T, 32) * 32; p.ksz = ksz; p.heads = h->cfg.num_heads; p.hd = H / p.heads;
@@ -1625,7 +1751,7 @@ static FftPlan plan_fft(const bsg_fs2midi* h, int B, int T, int ksz) {
   const bool split_ok = gemm_split_enabled(), flash = p.hd == 128 && sw.flash;
   p.h2w = sw.gemm_h2w && h->h2w_ok && split_ok && sw.flash_split && flash && h2w_supports(T, 4 * H, H, ksz, H) &&
           h2w_supports((int)p.rows, 3 * H, H, 1, H) && p.rows * 4 * H * 2 < (1LL << 31);
-  if (p.h2w && sw.flash_planes && p.Tp <= 3 * T && p.rows >= 32) {
+  if (p.h2w && sw.flash_planes && p.Tp <= 3 * T && p.rows >= 32 && (!ragged || sw.qkv_fused)) {
     // 2 waves (64 queries) per workgroup at every size: the pipelined loop keeps two score tiles live and does not fit 4 waves x 2 workgroups.
     // Small batches: the keys of a query tile over ks workgroups (a single utterance is 32 workgroups, each a serial chain of 32 key blocks)
     p.attn = ATTN_PLANES; p.nw = 2; p.qkv = sw.qkv_fused ? QKV_FUSED : QKV_SPLIT_KERNEL;
@@ -1657,15 +1783,19 @@ static FftPlan plan_fft(const bsg_fs2midi* h, int B, int T, int ksz) {
 }
 
 // Q | K | V of a layer on the pre-split path, from the LayerNorm planes in h->w_ap
-static int qkv_h2w(bsg_fs2midi* h, const char* gtag, const FftPlan& p, const FftLayerW& L, const float* keep, hipStream_t st) {
+static int qkv_h2w(bsg_fs2midi* h, const char* gtag, const FftPlan& p, const FftLayerW& L, const float* keep, hipStream_t st, const int* lens) {
   if (p.qkv == QKV_FUSED) {
     H2wArgs g{};   // the QKV product writes the attention's planes itself (H2wArgs::qkv_T): no fp32 QKV tensor, no split launch
     g.act = h->w_ap; g.act_plane = p.rows * H; g.lda = H; g.wpack = L.p_in.pack; g.rows = (int)p.rows; g.K = H; g.Wn = 3 * H; g.taps = 1; g.act_is_a = 1;
     g.out = h->w_fp; g.out_plane = p.qk_plane; g.ldo = 2 * H; g.alpha = p.qscale; g.alpha_ncols = H; g.act_fn = ACT_NONE; g.batch = 1;
     g.qkv_T = p.T; g.qkv_Tp = p.Tp; g.qkv_H = H; g.vt = reinterpret_cast<unsigned short*>(p.vt); g.vt_plane = p.vt_plane;
+    if (lens) {   // ragged: one batch item per utterance (its tiles start at the utterance's first row: every K / V row the attention stages up to
+                  // the end of the utterance's last 32-key block lies in a tile that is computed, and is 0 beyond the end)
+      g.rows = p.T; g.batch = p.B; g.sAct = (long long)p.T * H; g.sO = (long long)p.T * 2 * H; g.lens = lens;
+    }
     return h2w_rec(h, gtag, g, st);
   }
-  TRY(linear_h2w(h, gtag, h->w_ap, L.p_in, 3 * H, nullptr, h->w_qkv, nullptr, p.rows, ACT_NONE, nullptr, nullptr, st, p.qscale, H));
+  TRY(linear_h2w(h, gtag, h->w_ap, L.p_in, 3 * H, nullptr, h->w_qkv, nullptr, p.rows, ACT_NONE, nullptr, nullptr, st, p.qscale, H, 0, lens, p.T));
   if (p.qkv == QKV_SPLIT_KERNEL) {
     hipLaunchKernelGGL(qkv_split_kernel, dim3(p.Tp / 32, p.B), dim3(256), 0, st, (const float*)h->w_qkv, p.qk, p.qk_plane, p.vt, p.vt_plane, p.T, p.Tp, keep, p.km, gemm_range_counter());
     BSG_LAUNCH_CHECK();
@@ -1674,22 +1804,23 @@ static int qkv_h2w(bsg_fs2midi* h, const char* gtag, const FftPlan& p, const Fft
 }
 
 // The attention of a layer: the one launch site of every form, named once its kernel has been launched
-static int attention(bsg_fs2midi* h, bool first, const char* stack, const char* gtag, const FftPlan& p, const float* keep, hipStream_t st) {
+static int attention(bsg_fs2midi* h, bool first, const char* stack, const char* gtag, const FftPlan& p, const float* keep, hipStream_t st,
+                     const int* lens) {
   const int T = p.T, heads = p.heads;
   const float* qkv = h->w_qkv;
   switch (p.attn) {
     case ATTN_PLANES:
-      hipLaunchKernelGGL(flash_attn_planes_kernel<2>, p.grid, p.block, FLP_LDS, st, (const _Float16*)p.qk, p.qk_plane, (const _Float16*)p.vt, p.vt_plane, (const unsigned*)p.km, T, p.Tp, heads, p.attn_planes, p.attn_plane, H, gemm_range_counter(), h->w_fsk, h->w_fcnt);
+      hipLaunchKernelGGL(flash_attn_planes_kernel<2>, p.grid, p.block, FLP_LDS, st, (const _Float16*)p.qk, p.qk_plane, (const _Float16*)p.vt, p.vt_plane, (const unsigned*)p.km, T, p.Tp, heads, p.attn_planes, p.attn_plane, H, gemm_range_counter(), h->w_fsk, h->w_fcnt, lens);
       break;
     case ATTN_SPLIT:
-      if (p.nw == 4) hipLaunchKernelGGL(flash_attn_split_kernel<4>, p.grid, p.block, 0, st, qkv, keep, p.attn_out, T, heads, 3 * H, H, gemm_range_counter(), p.attn_planes, p.attn_plane);
-      else hipLaunchKernelGGL(flash_attn_split_kernel<2>, p.grid, p.block, 0, st, qkv, keep, p.attn_out, T, heads, 3 * H, H, gemm_range_counter(), p.attn_planes, p.attn_plane);
+      if (p.nw == 4) hipLaunchKernelGGL(flash_attn_split_kernel<4>, p.grid, p.block, 0, st, qkv, keep, p.attn_out, T, heads, 3 * H, H, gemm_range_counter(), p.attn_planes, p.attn_plane, lens);
+      else hipLaunchKernelGGL(flash_attn_split_kernel<2>, p.grid, p.block, 0, st, qkv, keep, p.attn_out, T, heads, 3 * H, H, gemm_range_counter(), p.attn_planes, p.attn_plane, lens);
       break;
     case ATTN_FLASH:   // no [B*heads, T, T] score tensor (flash_attn_kernel)
-      if (p.nw == 4) hipLaunchKernelGGL(flash_attn_kernel<4>, p.grid, p.block, 0, st, qkv, keep, p.attn_out, T, heads, 3 * H, H);
-      else hipLaunchKernelGGL(flash_attn_kernel<2>, p.grid, p.block, 0, st, qkv, keep, p.attn_out, T, heads, 3 * H, H);
+      if (p.nw == 4) hipLaunchKernelGGL(flash_attn_kernel<4>, p.grid, p.block, 0, st, qkv, keep, p.attn_out, T, heads, 3 * H, H, lens);
+      else hipLaunchKernelGGL(flash_attn_kernel<2>, p.grid, p.block, 0, st, qkv, keep, p.attn_out, T, heads, 3 * H, H, lens);
       break;
-    case ATTN_SOFTMAX: {
+    case ATTN_SOFTMAX: {   // (never with lengths: rag_plan_check refused the call)
       const int hd = p.hd, nbh = p.B * heads;
       GemmArgs s{};   // S[b,h] = Q K^T
       s.A = qkv; s.B = qkv + H; s.C = h->w_scores; s.M = T; s.N = T; s.K = hd; s.lda = 3 * H; s.ldb = 3 * H; s.ldc = T;
@@ -1716,11 +1847,15 @@ static int attention(bsg_fs2midi* h, bool first, const char* stack, const char* 
 // EncSALayer x FFTBlocks tail (common_layers.py:706-730, tts_modules.py:298-305); x [B*T, H] in place.  plan_fft decides, grow()
 // allocates, the loops only launch.  Every GEMM launch of every layer goes through path_add; the QKV and attention tokens are named in the
 // first layer only (`first`), the later layers launching the plan's same forms.
+// lens (ragged calls; null = the padded call, which launches exactly what it did): utterance b is lens[b] rows long.  The layout stays padded
+// ([B][T] rows, the pitch of every tensor) and every launch takes the lengths: LayerNorm and the GEMMs neither read nor compute rows at or
+// beyond an utterance's end (the k-tap convolution reads zeros there), the attention's query tiles and key blocks stop at it, and whole
+// tiles beyond it return before their first load.  The caller sets last_stack_rows (it knows the lengths on the host).
 static int launch_fft(bsg_fs2midi* h, const std::vector<FftLayerW>& layers, const float* lnw, const float* lnb, int ksz,
-                      float* x, const float* keep, int B, int T, hipStream_t st, const char* stack) {
-  const FftPlan p = plan_fft(h, B, T, ksz);
+                      float* x, const float* keep, int B, int T, hipStream_t st, const char* stack, const int* lens = nullptr) {
+  const FftPlan p = plan_fft(h, B, T, ksz, lens != nullptr);
   const long long rows = p.rows;
-  h->last_stack_rows = (int)rows;
+  if (!lens) h->last_stack_rows = (int)rows;
   TRY(grow(h, &h->cap_fsk, p.need_fsk, st));
   TRY(grow(h, &h->cap_fcnt, p.need_fcnt, st));
   TRY(grow(h, &h->cap_scores, p.need_scores, st));
@@ -1737,61 +1872,64 @@ static int launch_fft(bsg_fs2midi* h, const std::vector<FftLayerW>& layers, cons
     // create, and each activation is written as hi / lo fp16 planes by the kernel that produces it (LayerNorm, the fused attention, the
     // GELU epilogue of the FFN convolution) — no kernel splits an operand while it stages it.  Same arithmetic as the loop below.
     for (const FftLayerW& L : layers) {
-      TRY(ln_planes(x, L.ln1w, L.ln1b, h->w_ap, rows, 1e-5f, st));
-      TRY(qkv_h2w(h, gtag, p, L, keep, st));
+      TRY(ln_planes(x, L.ln1w, L.ln1b, h->w_ap, rows, 1e-5f, st, lens, T));
+      TRY(qkv_h2w(h, gtag, p, L, keep, st, lens));
       path_name(h, first, stack, "qkv:", QKV_TOKEN[p.qkv]);
-      TRY(attention(h, first, stack, gtag, p, keep, st));
-      TRY(linear_h2w(h, gtag, h->w_ap, L.p_out, H, nullptr, h->w_b, nullptr, rows, ACT_NONE, x, keep, st));   // x1 = (x + attn) * keep
-      TRY(ln_planes(h->w_b, L.ln2w, L.ln2b, h->w_ap, rows, 1e-5f, st));
+      TRY(attention(h, first, stack, gtag, p, keep, st, lens));
+      TRY(linear_h2w(h, gtag, h->w_ap, L.p_out, H, nullptr, h->w_b, nullptr, rows, ACT_NONE, x, keep, st, 1.f, 0, 0, lens, T));   // x1 = (x + attn) * keep
+      TRY(ln_planes(h->w_b, L.ln2w, L.ln2b, h->w_ap, rows, 1e-5f, st, lens, T));
       H2wArgs g{};   // Conv1d(H -> 4H, k, SAME) * k^-1/2 -> GELU, written as the planes the second Linear reads
       g.act = h->w_ap; g.act_plane = rows * H; g.lda = H; g.sAct = (long long)T * H; g.wpack = L.p_ffn1.pack; g.rows = T; g.K = H; g.Wn = 4 * H;
       g.taps = ksz; g.tap_shift0 = -(ksz / 2); g.act_is_a = 1; g.out = h->w_fp; g.out_plane = rows * 4 * H; g.ldo = 4 * H; g.sO = (long long)T * 4 * H;
-      g.bias = L.ffn1b; g.alpha = ffn_alpha; g.act_fn = ACT_GELU; g.batch = B;
+      g.bias = L.ffn1b; g.alpha = ffn_alpha; g.act_fn = ACT_GELU; g.batch = B; g.lens = lens;   // (ragged: the taps read zeros beyond the utterance's end)
       TRY(h2w_rec(h, gtag, g, st));
-      TRY(linear_h2w(h, gtag, h->w_fp, L.p_ffn2, H, L.ffn2b, x, nullptr, rows, ACT_NONE, h->w_b, keep, st));   // x = (x1 + ffn) * keep
+      TRY(linear_h2w(h, gtag, h->w_fp, L.p_ffn2, H, L.ffn2b, x, nullptr, rows, ACT_NONE, h->w_b, keep, st, 1.f, 0, 0, lens, T));   // x = (x1 + ffn) * keep
       first = false;
     }
   } else {
     for (const FftLayerW& L : layers) {
-      TRY(ln(x, L.ln1w, L.ln1b, h->w_a, nullptr, rows, 1e-5f, st));
-      TRY(linear(h->w_a, L.in_proj, nullptr, h->w_qkv, rows, 3 * H, H, ACT_NONE, nullptr, nullptr, st, p.qscale, H, h, gtag));
+      TRY(ln(x, L.ln1w, L.ln1b, h->w_a, nullptr, rows, 1e-5f, st, lens, T));
+      TRY(linear(h->w_a, L.in_proj, nullptr, h->w_qkv, rows, 3 * H, H, ACT_NONE, nullptr, nullptr, st, p.qscale, H, h, gtag, lens, T));
       path_name(h, first, stack, "qkv:", QKV_TOKEN[p.qkv]);
-      TRY(attention(h, first, stack, gtag, p, keep, st));
-      TRY(linear(h->w_a, L.out_proj, nullptr, h->w_b, rows, H, H, ACT_NONE, x, keep, st, 1.f, 0, h, gtag));   // x1 = (x + attn) * keep
-      TRY(ln(h->w_b, L.ln2w, L.ln2b, h->w_a, nullptr, rows, 1e-5f, st));
+      TRY(attention(h, first, stack, gtag, p, keep, st, lens));
+      TRY(linear(h->w_a, L.out_proj, nullptr, h->w_b, rows, H, H, ACT_NONE, x, keep, st, 1.f, 0, h, gtag, lens, T));   // x1 = (x + attn) * keep
+      TRY(ln(h->w_b, L.ln2w, L.ln2b, h->w_a, nullptr, rows, 1e-5f, st, lens, T));
       GemmArgs g{};   // Conv1d(H -> 4H, k, SAME) * k^-1/2 -> GELU
       g.A = h->w_a; g.B = L.ffn1; g.C = h->w_ffn; g.M = T; g.N = 4 * H; g.K = H; g.lda = H; g.ldb = H; g.ldc = 4 * H;
       g.trans_b = 1; g.taps = ksz; g.tap_shift0 = -(ksz / 2); g.sTapB = (long long)4 * H * H;
       g.bias_n = L.ffn1b; g.alpha = ffn_alpha; g.act = ACT_GELU; g.batch = B;
-      g.sA = (long long)T * H; g.sC = (long long)T * 4 * H;
+      g.sA = (long long)T * H; g.sC = (long long)T * 4 * H; g.lens = lens;   // (ragged: the taps read zeros beyond the utterance's end)
       TRY(gemm_rec(h, gtag, g, st));
-      TRY(linear(h->w_ffn, L.ffn2, L.ffn2b, x, rows, H, 4 * H, ACT_NONE, h->w_b, keep, st, 1.f, 0, h, gtag));   // x = (x1 + ffn) * keep
+      TRY(linear(h->w_ffn, L.ffn2, L.ffn2b, x, rows, H, 4 * H, ACT_NONE, h->w_b, keep, st, 1.f, 0, h, gtag, lens, T));   // x = (x1 + ffn) * keep
       first = false;
     }
   }
-  return ln(x, lnw, lnb, x, keep, rows, 1e-5f, st);
+  return ln(x, lnw, lnb, x, keep, rows, 1e-5f, st, lens, T);   // (ragged: 0 beyond an utterance's end — what the call returns there)
 }
 
 // duration predictor (tts_modules.py:108-133) on (x + spk) * keep for the nb utterances of x (their keep in w_keep); spk_id: these rows'
-static int dur_predict(bsg_fs2midi* h, const float* x, const int64_t* spk_id, int32_t nb, int32_t Tt, float* dur_xs, int64_t* dur, hipStream_t st) {
+// lens (ragged calls): the predictor is masked per layer already, so the lengths only skip the padded rows; dur_xs and dur are 0 beyond an
+// utterance's end
+static int dur_predict(bsg_fs2midi* h, const float* x, const int64_t* spk_id, int32_t nb, int32_t Tt, float* dur_xs, int64_t* dur, hipStream_t st,
+                       const int* lens = nullptr) {
   const long long lrows = (long long)nb * Tt;
   const dim3 lg(cdiv(lrows, 4)), rb(256);
   // duration predictor (tts_modules.py:108-133) on (enc + spk) * keep
   float* a = h->w_a;
   float* b = h->w_b;
-  hipLaunchKernelGGL(add_spk_kernel, lg, rb, 0, st, (const float*)x, (const long long*)spk_id, h->Espk, h->w_keep, a, lrows, Tt);
+  hipLaunchKernelGGL(add_spk_kernel, lg, rb, 0, st, (const float*)x, (const long long*)spk_id, h->Espk, h->w_keep, a, lrows, Tt, lens);
   BSG_LAUNCH_CHECK();
   const int ks = h->cfg.dur_kernel;
   for (int l = 0; l < h->cfg.dur_layers; ++l) {
     GemmArgs g{};
     g.A = a; g.B = h->dur_conv[l]; g.C = b; g.M = Tt; g.N = H; g.K = H; g.lda = H; g.ldb = H; g.ldc = H; g.trans_b = 1;
     g.taps = ks; g.tap_shift0 = -(ks / 2); g.sTapB = (long long)H * H; g.bias_n = h->dur_convb[l]; g.alpha = 1.f;
-    g.act = ACT_RELU; g.batch = nb; g.sA = (long long)Tt * H; g.sC = (long long)Tt * H;
+    g.act = ACT_RELU; g.batch = nb; g.sA = (long long)Tt * H; g.sC = (long long)Tt * H; g.lens = lens;
     TRY(launch_gemm(g, st));
-    TRY(ln(b, h->dur_lnw[l], h->dur_lnb[l], a, h->w_keep, lrows, 1e-12f, st));
+    TRY(ln(b, h->dur_lnw[l], h->dur_lnb[l], a, h->w_keep, lrows, 1e-12f, st, lens, Tt));
   }
-  TRY(linear(a, h->dur_lin_w, h->dur_lin_b, dur_xs, lrows, 1, H, ACT_NONE, nullptr, h->w_keep, st));
-  hipLaunchKernelGGL(dur_from_log_kernel, dim3(cdiv(lrows, 256)), dim3(256), 0, st, (const float*)dur_xs, (long long*)dur, lrows);
+  TRY(linear(a, h->dur_lin_w, h->dur_lin_b, dur_xs, lrows, 1, H, ACT_NONE, nullptr, h->w_keep, st, 1.f, 0, nullptr, "", lens, Tt));
+  hipLaunchKernelGGL(dur_from_log_kernel, dim3(cdiv(lrows, 256)), dim3(256), 0, st, dur_xs, (long long*)dur, lrows, lens, Tt);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
 }
@@ -1928,7 +2066,7 @@ extern "C" int bsg_fs2_encode_plain(bsg_fs2midi* h, const int64_t* txt, const in
   h->last_token_rows = (int)lrows;
   float* x = h->w_c;
   hipLaunchKernelGGL(token_front_kernel, dim3(cdiv(lrows, 4)), dim3(256), 0, st, (const long long*)txt + off, h->Etok, h->rel_table, x, h->w_keep,
-                     lrows, Tt, sqrtf((float)H), h->cfg.n_rel, h->cfg.vocab);
+                     lrows, Tt, sqrtf((float)H), h->cfg.n_rel, h->cfg.vocab, (const int*)nullptr);
   BSG_LAUNCH_CHECK();
   path_add(h, "tok:", "front");
   TRY(launch_fft(h, h->enc, h->enc_lnw, h->enc_lnb, h->cfg.enc_ffn_kernel_size, x, h->w_keep, n_rows, Tt, st, "enc."));
@@ -1936,6 +2074,109 @@ extern "C" int bsg_fs2_encode_plain(bsg_fs2midi* h, const int64_t* txt, const in
   if (dur) TRY(dur_predict(h, x, spk_id ? spk_id + row0 : nullptr, n_rows, Tt, dur_xs, dur, st));
   h->path_enc_len = h->path.size();
   return BSG_OK;
+}
+
+// ---- ragged batches through the front (ABI v20): every utterance as the B = 1 call on its own tokens and frames --------------------------
+// The counts come from a HOST array, are checked before any device call, and reach the kernels through the handle's own device rows
+// (w_lens_t / w_lens_f), which launches of the call itself fill (lens_fill): a captured call replays its counts.
+static int rag_check(const char* who, const char* what, const int32_t* n, int B, int lo, int hi) {
+  BSG_REQUIRE(n, "%s: %s is null", who, what);
+  for (int b = 0; b < B; ++b) BSG_REQUIRE(n[b] >= lo && n[b] <= hi, "%s: %s[%d]=%d outside %d..%d", who, what, b, n[b], lo, hi);
+  return BSG_OK;
+}
+// rows that a ragged stack computes, as bsg_fs2midi_last_rows reports them: every utterance rounded up to the 32-row granule (the smallest
+// tile of any launch of the stack: a 32-query wave of the attention, a 32-row GEMM tile; the 64- and 128-row tiles round further)
+static int rag_rows(const int32_t* n, int B, int T) {
+  long long r = 0;
+  for (int b = 0; b < B; ++b) r += std::min(T, (n[b] + 31) / 32 * 32);
+  return (int)r;
+}
+
+// The plan is pure, so a ragged entry asks it before its first device call: a stack whose attention could only be the score tensor is
+// refused here, with nothing enqueued (under capture: nothing in the graph).
+static int rag_plan_check(const bsg_fs2midi* h, const char* who, int B, int T, int ksz) {
+  BSG_REQUIRE(plan_fft(h, B, T, ksz, true).attn != ATTN_SOFTMAX,
+              "%s: the ragged front is built on the fused attention (head dim 128, BSG_NO_FLASH_ATTN unset), not on the score tensor", who);
+  return BSG_OK;
+}
+
+// The ESM of an utterance ALONE (common_layers.py:848-860 at B = 1): the attention over the batch axis has one key, its softmax is exactly 1,
+// so the attention's output is V and Q / K drop out:  Mo = out_proj(v_proj(LN1(E_lang[l]))) + E_lang[l],  Fo = ffn(LN2(Mo)) + Mo — a function of
+// the token's lang id only.  Two rows (one per row of lang_embed) on the handle's LayerNorm / GEMM launches (split-fp16: fp32-grade).
+static int esm_alone_table(bsg_fs2midi* h, const float** tab, hipStream_t st) {
+  float* s = h->esm_scr;   // [6][2][H]
+  float *lpn = s, *v = s + 2 * H, *Mo = s + 4 * H, *t1 = s + 6 * H, *t2 = s + 8 * H, *Fo = s + 10 * H;
+  TRY(ln(h->Elang, h->esm_ln1w, h->esm_ln1b, lpn, nullptr, 2, 1e-5f, st));
+  TRY(linear(lpn, h->esm_in_w + (size_t)2 * H * H, h->esm_in_b + 2 * H, v, 2, H, H, ACT_NONE, nullptr, nullptr, st, 1.f, 0, h, "esm.gemm:"));
+  TRY(linear(v, h->esm_out_w, h->esm_out_b, Mo, 2, H, H, ACT_NONE, h->Elang, nullptr, st, 1.f, 0, h, "esm.gemm:"));
+  TRY(ln(Mo, h->esm_ln2w, h->esm_ln2b, t1, nullptr, 2, 1e-5f, st));
+  TRY(linear(t1, h->esm_f0w, h->esm_f0b, t2, 2, H, H, ACT_RELU, nullptr, nullptr, st, 1.f, 0, h, "esm.gemm:"));
+  TRY(linear(t2, h->esm_f2w, h->esm_f2b, Fo, 2, H, H, ACT_NONE, Mo, nullptr, st, 1.f, 0, h, "esm.gemm:"));
+  path_add(h, "esm:", "alone");
+  *tab = Fo;
+  return BSG_OK;
+}
+
+// what both ragged encodes share once the front's rows are in w_c / w_keep
+static int encode_ragged_tail(bsg_fs2midi* h, const int64_t* spk_id, const int32_t* n_tok_host, int32_t B, int32_t Tt, float* enc_out,
+                              float* dur_xs, int64_t* dur, hipStream_t st) {
+  const long long rows = (long long)B * Tt;
+  float* x = h->w_c;
+  TRY(launch_fft(h, h->enc, h->enc_lnw, h->enc_lnb, h->cfg.enc_ffn_kernel_size, x, h->w_keep, B, Tt, st, "enc.", h->w_lens_t));
+  h->last_token_rows = h->last_stack_rows = rag_rows(n_tok_host, B, Tt);
+  BSG_HIP(hipMemcpyAsync(enc_out, x, rows * H * sizeof(float), hipMemcpyDeviceToDevice, st));
+  if (dur) TRY(dur_predict(h, x, spk_id, B, Tt, dur_xs, dur, st, h->w_lens_t));
+  h->path_enc_len = h->path.size();
+  return BSG_OK;
+}
+
+extern "C" int bsg_fs2midi_encode_ragged(bsg_fs2midi* h, const int64_t* txt, const int64_t* pitch_midi, const float* midi_dur,
+                                         const int64_t* is_slur, const int64_t* lang, const int64_t* spk_id, const int32_t* n_tok_host,
+                                         int32_t B, int32_t Tt, float* enc_out, float* dur_xs, int64_t* dur, void* stream) {
+  GuardScope guard_scope(h ? &h->guard : nullptr);
+  BSG_REQUIRE(h && txt && pitch_midi && midi_dur && is_slur && lang && spk_id && enc_out, "fs2midi_encode_ragged: null argument");
+  BSG_REQUIRE(h->front == BSG_FS2_FRONT_MIDI, "fs2midi_encode_ragged: the handle has the plain front (bsg_fs2_encode_plain_ragged)");
+  BSG_REQUIRE(B > 0 && B <= 65535 && Tt > 0 && Tt <= h->cfg.n_rel, "fs2midi_encode_ragged: B=%d T_txt=%d (rel-pos table has %d rows)", B, Tt, h->cfg.n_rel);
+  BSG_REQUIRE((dur_xs == nullptr) == (dur == nullptr), "fs2midi_encode_ragged: dur_xs and dur go together");
+  TRY(rag_check("fs2midi_encode_ragged", "n_tok_host", n_tok_host, B, 1, Tt));
+  TRY(rag_plan_check(h, "fs2midi_encode_ragged", B, Tt, h->cfg.enc_ffn_kernel_size));
+  hipStream_t st = (hipStream_t)stream;
+  h->path.clear();
+  const long long rows = (long long)B * Tt;
+  TRY(grow(h, &h->cap_rows, (size_t)rows, st));
+  TRY(grow(h, &h->cap_lens, (size_t)B, st));
+  TRY(lens_fill(h->w_lens_t, n_tok_host, B, st));
+  const float* tab = nullptr;
+  TRY(esm_alone_table(h, &tab, st));
+  hipLaunchKernelGGL(embed_ragged_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, (const long long*)txt, (const long long*)lang,
+                     (const long long*)pitch_midi, midi_dur, (const long long*)is_slur, h->Etok, tab, h->Emidi, h->Wdur, h->bdur, h->Eslur,
+                     h->rel_table, h->w_c, h->w_keep, rows, Tt, sqrtf((float)H), h->cfg.vocab, (const int*)h->w_lens_t);
+  BSG_LAUNCH_CHECK();
+  path_add(h, "tok:", "ragged");
+  return encode_ragged_tail(h, spk_id, n_tok_host, B, Tt, enc_out, dur_xs, dur, st);
+}
+
+extern "C" int bsg_fs2_encode_plain_ragged(bsg_fs2midi* h, const int64_t* txt, const int64_t* spk_id, const int32_t* n_tok_host, int32_t B,
+                                           int32_t Tt, float* enc_out, float* dur_xs, int64_t* dur, void* stream) {
+  GuardScope guard_scope(h ? &h->guard : nullptr);
+  BSG_REQUIRE(h && txt && enc_out, "fs2_encode_plain_ragged: null argument");
+  BSG_REQUIRE(h->front == BSG_FS2_FRONT_PLAIN, "fs2_encode_plain_ragged: the handle has the MIDI front (bsg_fs2midi_encode_ragged)");
+  BSG_REQUIRE((spk_id != nullptr) == (h->cfg.spk_rows > 0), "fs2_encode_plain_ragged: spk_id goes with a speaker table (spk_rows=%d)", h->cfg.spk_rows);
+  BSG_REQUIRE(B > 0 && B <= 65535 && Tt > 0 && Tt < h->cfg.n_rel, "fs2_encode_plain_ragged: B=%d T_txt=%d (position table has %d rows)", B, Tt, h->cfg.n_rel);
+  BSG_REQUIRE((dur_xs == nullptr) == (dur == nullptr), "fs2_encode_plain_ragged: dur_xs and dur go together");
+  TRY(rag_check("fs2_encode_plain_ragged", "n_tok_host", n_tok_host, B, 1, Tt));
+  TRY(rag_plan_check(h, "fs2_encode_plain_ragged", B, Tt, h->cfg.enc_ffn_kernel_size));
+  hipStream_t st = (hipStream_t)stream;
+  h->path.clear();
+  const long long rows = (long long)B * Tt;
+  TRY(grow(h, &h->cap_rows, (size_t)rows, st));
+  TRY(grow(h, &h->cap_lens, (size_t)B, st));
+  TRY(lens_fill(h->w_lens_t, n_tok_host, B, st));
+  hipLaunchKernelGGL(token_front_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, (const long long*)txt, h->Etok, h->rel_table, h->w_c, h->w_keep,
+                     rows, Tt, sqrtf((float)H), h->cfg.n_rel, h->cfg.vocab, (const int*)h->w_lens_t);
+  BSG_LAUNCH_CHECK();
+  path_add(h, "tok:", "ragged");
+  return encode_ragged_tail(h, spk_id, n_tok_host, B, Tt, enc_out, dur_xs, dur, st);
 }
 
 extern "C" int bsg_fs2midi_last_rows(const bsg_fs2midi* h, int32_t* token_rows, int32_t* stack_rows) {
@@ -1971,18 +2212,20 @@ extern "C" int bsg_length_regulator(const int64_t* dur, const int64_t* txt, int6
 // frames carry bias-driven values into the last real frames through the taps) — and pitch_tail_kernel.
 static int pitch_adaptor(bsg_fs2midi* h, const float* enc_out, const int64_t* mel2ph, const int64_t* spk_id, const int64_t* speechsing,
                          const float* f0, const float* uv, int32_t B, int32_t Tt, int32_t T, float* pitch_pred, float* f0_denorm,
-                         int64_t* pitch_bin, float* decoder_inp, hipStream_t st) {
+                         int64_t* pitch_bin, float* decoder_inp, hipStream_t st, const int* lens_f, const int* lens_t) {
+  // lens_f / lens_t (ragged calls; null = padded): the utterances' frame and token counts.  With them the predictor's convolutions read zeros
+  // beyond an utterance's end in EVERY layer (the utterance alone), and nothing is computed there.
   const long long rows = (long long)B * T;
   const dim3 rg(cdiv(rows, 4)), rb(256);
   float *cur = h->w_a, *cv = h->w_b;
   int n_launch = 0;   // counted where each launch is made: the record's last token
   hipLaunchKernelGGL(pitch_positions_kernel, dim3(B), dim3(64), 0, st, enc_out, (const long long*)mel2ph, (const long long*)spk_id, h->Espk,
-                     h->w_pos, T, Tt, h->cfg.spk_rows);
+                     h->w_pos, T, Tt, h->cfg.spk_rows, lens_f, lens_t);
   BSG_LAUNCH_CHECK();
   path_add(h, "pit.", "pos");
   ++n_launch;
   hipLaunchKernelGGL(pitch_entry_kernel, rg, rb, 0, st, enc_out, (const long long*)mel2ph, (const long long*)spk_id, h->Espk,
-                     (const int*)h->w_pos, h->pit_table, h->pit_alpha, cur, rows, T, Tt, h->n_pitch_pos, h->cfg.spk_rows);
+                     (const int*)h->w_pos, h->pit_table, h->pit_alpha, cur, rows, T, Tt, h->n_pitch_pos, h->cfg.spk_rows, lens_f, lens_t);
   BSG_LAUNCH_CHECK();
   path_add(h, "pit.", "entry");
   ++n_launch;
@@ -1991,18 +2234,18 @@ static int pitch_adaptor(bsg_fs2midi* h, const float* enc_out, const int64_t* me
     GemmArgs g{};
     g.A = cur; g.B = h->pit_conv[l]; g.C = cv; g.M = T; g.N = H; g.K = H; g.lda = H; g.ldb = H; g.ldc = H; g.trans_b = 1;
     g.taps = ks; g.tap_shift0 = -(ks / 2); g.sTapB = (long long)H * H; g.bias_n = h->pit_convb[l]; g.alpha = 1.f;
-    g.act = ACT_RELU; g.batch = B; g.sA = (long long)T * H; g.sC = (long long)T * H;
+    g.act = ACT_RELU; g.batch = B; g.sA = (long long)T * H; g.sC = (long long)T * H; g.lens = lens_f;
     TRY(gemm_rec(h, "pit.gemm:", g, st));
     ++n_launch;
     if (l + 1 < L) {
-      TRY(ln(cv, h->pit_lnw[l], h->pit_lnb[l], cur, nullptr, rows, 1e-12f, st));
+      TRY(ln(cv, h->pit_lnw[l], h->pit_lnb[l], cur, nullptr, rows, 1e-12f, st, lens_f, T));
       path_add(h, "pit.", "ln");
       ++n_launch;
     }
   }
   hipLaunchKernelGGL(pitch_tail_kernel, rg, rb, 0, st, (const float*)cv, h->pit_lnw[L - 1], h->pit_lnb[L - 1], h->pit_lin_w, h->pit_lin_b, f0, uv,
                      h->use_uv, enc_out, (const long long*)mel2ph, (const long long*)spk_id, (const long long*)speechsing, h->Espk, h->Estyle,
-                     h->Epitch, pitch_pred, f0_denorm, (long long*)pitch_bin, decoder_inp, rows, T, Tt, h->cfg.spk_rows);
+                     h->Epitch, pitch_pred, f0_denorm, (long long*)pitch_bin, decoder_inp, rows, T, Tt, h->cfg.spk_rows, lens_f, lens_t);
   BSG_LAUNCH_CHECK();
   path_add(h, "pit.", "tail");
   ++n_launch;
@@ -2012,37 +2255,53 @@ static int pitch_adaptor(bsg_fs2midi* h, const float* enc_out, const int64_t* me
 
 static int decode_impl(bsg_fs2midi* h, const char* who, const float* enc_out, const int64_t* mel2ph, const int64_t* spk_id,
                        const int64_t* speechsing, const float* f0, const float* uv, int32_t B, int32_t Tt, int32_t T, float* pitch_pred,
-                       float* f0_denorm, int64_t* pitch_bin, float* decoder_inp, float* mel_out, hipStream_t st) {
+                       float* f0_denorm, int64_t* pitch_bin, float* decoder_inp, float* mel_out, hipStream_t st,
+                       const int32_t* n_tok_host = nullptr, const int32_t* n_frames_host = nullptr, bool ragged = false) {
   BSG_REQUIRE(h && enc_out && mel2ph && decoder_inp, "%s: null argument", who);
   BSG_REQUIRE((spk_id != nullptr) == (h->Espk != nullptr), "%s: spk_id goes with a speaker table (spk_rows=%d)", who, h->cfg.spk_rows);
   BSG_REQUIRE((speechsing != nullptr) == (h->front == BSG_FS2_FRONT_MIDI), "%s: speechsing goes with the MIDI front", who);
   BSG_REQUIRE(B > 0 && Tt > 0 && T > 0 && T < h->cfg.n_pos, "%s: B=%d T_txt=%d T=%d (position table has %d rows)", who, B, Tt, T, h->cfg.n_pos);
   BSG_REQUIRE(h->use_pitch || (!f0 && !uv && !pitch_pred && !f0_denorm && !pitch_bin), "%s: f0 / uv / pitch outputs on a handle without use_pitch_embed", who);
   BSG_REQUIRE(!h->use_pitch || T < h->n_pitch_pos, "%s: T=%d (pitch position table has %d rows)", who, T, h->n_pitch_pos);
+  if (ragged) {   // every refusal before any device call
+    BSG_REQUIRE(B <= 65535, "%s: B=%d", who, B);
+    TRY(rag_check(who, "n_tok_host", n_tok_host, B, 1, Tt));
+    TRY(rag_check(who, "n_frames_host", n_frames_host, B, 0, T));
+    if (mel_out) TRY(rag_plan_check(h, who, B, T, h->cfg.dec_ffn_kernel_size));
+  }
   h->path.resize(h->path_enc_len);   // the record keeps the encode this decode follows
   const long long rows = (long long)B * T;
   TRY(grow(h, &h->cap_rows, (size_t)rows, st));
+  const int *lens_f = nullptr, *lens_t = nullptr;
+  if (ragged) {
+    TRY(grow(h, &h->cap_lens, (size_t)B, st));
+    TRY(lens_fill(h->w_lens_t, n_tok_host, B, st));
+    TRY(lens_fill(h->w_lens_f, n_frames_host, B, st));
+    lens_f = h->w_lens_f; lens_t = h->w_lens_t;
+    path_add(h, "dec.", "ragged");
+  }
   const dim3 rg(cdiv(rows, 4)), rb(256);
   if (h->use_pitch) {
-    TRY(pitch_adaptor(h, enc_out, mel2ph, spk_id, speechsing, f0, uv, B, Tt, T, pitch_pred, f0_denorm, pitch_bin, decoder_inp, st));
+    TRY(pitch_adaptor(h, enc_out, mel2ph, spk_id, speechsing, f0, uv, B, Tt, T, pitch_pred, f0_denorm, pitch_bin, decoder_inp, st, lens_f, lens_t));
   } else {
     hipLaunchKernelGGL(gather_frames_kernel, rg, rb, 0, st, enc_out, (const long long*)mel2ph, (const long long*)spk_id,
-                       (const long long*)speechsing, h->Espk, h->Estyle, decoder_inp, rows, T, Tt);
+                       (const long long*)speechsing, h->Espk, h->Estyle, decoder_inp, rows, T, Tt, lens_f, lens_t);
     BSG_LAUNCH_CHECK();
   }
   if (!mel_out) return BSG_OK;   // skip_decoder
   float* x = h->w_x;
   BSG_HIP(hipMemcpyAsync(x, decoder_inp, rows * H * sizeof(float), hipMemcpyDeviceToDevice, st));
-  hipLaunchKernelGGL(decoder_positions_kernel, dim3(B), dim3(64), 0, st, (const float*)x, h->w_pos, h->w_keep, T);
+  hipLaunchKernelGGL(decoder_positions_kernel, dim3(B), dim3(64), 0, st, (const float*)x, h->w_pos, h->w_keep, T, lens_f);
   BSG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(decoder_entry_kernel, rg, rb, 0, st, x, (const int*)h->w_pos, h->dec_table, h->dec_alpha, h->w_keep, rows, h->cfg.n_pos);
+  hipLaunchKernelGGL(decoder_entry_kernel, rg, rb, 0, st, x, (const int*)h->w_pos, h->dec_table, h->dec_alpha, h->w_keep, rows, h->cfg.n_pos, lens_f, T);
   BSG_LAUNCH_CHECK();
-  TRY(launch_fft(h, h->dec, h->dec_lnw, h->dec_lnb, h->cfg.dec_ffn_kernel_size, x, h->w_keep, B, T, st, "dec."));
+  TRY(launch_fft(h, h->dec, h->dec_lnw, h->dec_lnb, h->cfg.dec_ffn_kernel_size, x, h->w_keep, B, T, st, "dec.", lens_f));
+  if (ragged) h->last_stack_rows = rag_rows(n_frames_host, B, T);
   // mel_out = Linear(H -> M)(x) * (mel2ph > 0)                                        (fastspeech/fs2.py:236-240)
-  TRY(linear(x, h->mel_w, h->mel_b, mel_out, rows, h->cfg.out_dims, H, ACT_NONE, nullptr, nullptr, st));
+  TRY(linear(x, h->mel_w, h->mel_b, mel_out, rows, h->cfg.out_dims, H, ACT_NONE, nullptr, nullptr, st, 1.f, 0, nullptr, "", lens_f, T));
   // ... * tgt_nonpadding, which comes from mel2ph (not from the decoder's own |x| test)
   hipLaunchKernelGGL(mask_rows_by_index_kernel, dim3(cdiv(rows * h->cfg.out_dims, 256)), dim3(256), 0, st, mel_out,
-                     (const long long*)mel2ph, rows, h->cfg.out_dims);
+                     (const long long*)mel2ph, rows, h->cfg.out_dims, lens_f, T);
   BSG_LAUNCH_CHECK();
   return BSG_OK;
 }
@@ -2079,6 +2338,16 @@ extern "C" int bsg_fs2_decode(bsg_fs2midi* h, const float* enc_out, const int64_
                      (hipStream_t)stream);
 }
 
+// ABI v20: bsg_fs2_decode on a ragged batch.  Utterance b has n_tok_host[b] tokens and n_frames_host[b] frames; serves handles without the
+// adaptor too (the five adaptor pointers NULL), and both fronts.
+extern "C" int bsg_fs2_decode_ragged(bsg_fs2midi* h, const float* enc_out, const int64_t* mel2ph, const int64_t* spk_id, const int64_t* speechsing,
+                                     const float* f0, const float* uv, const int32_t* n_tok_host, const int32_t* n_frames_host, int32_t B,
+                                     int32_t Tt, int32_t T, float* pitch_pred, float* f0_denorm, int64_t* pitch_bin, float* decoder_inp,
+                                     float* mel_out, void* stream) {
+  GuardScope guard_scope(h ? &h->guard : nullptr);
+  return decode_impl(h, "fs2_decode_ragged", enc_out, mel2ph, spk_id, speechsing, f0, uv, B, Tt, T, pitch_pred, f0_denorm, pitch_bin, decoder_inp,
+                     mel_out, (hipStream_t)stream, n_tok_host, n_frames_host, true);
+}
 
 // ================================================================================================
 // the `FFT` candidate denoiser (DIFF_DECODERS['fft'], usr/diff/candidate_decoder.py:39-100):
@@ -2246,9 +2515,10 @@ extern "C" int bsg_fftden_forward(bsg_fftden* h, const float* x, const int64_t* 
     TRY(launch_gemm(g, st));
   }
   const dim3 rg(cdiv(rows, 4)), rb(256);
-  hipLaunchKernelGGL(decoder_positions_kernel, dim3(B), dim3(64), 0, st, (const float*)xs, c->w_pos, c->w_keep, T);
+  hipLaunchKernelGGL(decoder_positions_kernel, dim3(B), dim3(64), 0, st, (const float*)xs, c->w_pos, c->w_keep, T, (const int*)nullptr);
   BSG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(decoder_entry_kernel, rg, rb, 0, st, xs, (const int*)c->w_pos, c->dec_table, h->alpha, c->w_keep, rows, h->n_pos);
+  hipLaunchKernelGGL(decoder_entry_kernel, rg, rb, 0, st, xs, (const int*)c->w_pos, c->dec_table, h->alpha, c->w_keep, rows, h->n_pos,
+                     (const int*)nullptr, T);
   BSG_LAUNCH_CHECK();
   TRY(launch_fft(c, h->layers, h->lnw, h->lnb, h->ksz, xs, c->w_keep, B, T, st, "den."));
   TRY(linear(xs, h->mel_w, h->mel_b, h->mel, rows, h->M, H, ACT_NONE, nullptr, nullptr, st));       // get_mel_out (:98)

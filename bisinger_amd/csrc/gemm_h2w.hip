@@ -123,7 +123,10 @@ __global__ __launch_bounds__(256) void h2w_split_transposed_kernel(const float* 
 // KK = MFMA steps of 16 per slice and tap: 2 (32-deep slices) for convolutions, whose slices are long (2 x taps steps); 4 (64-deep slices)
 // for plain products (taps = 1): with 32-deep slices the staging loads of a slice were requested 768 matrix cycles before they are
 // written to LDS — about the L2 latency, so every slice ended in a stall — and a barrier stood behind every 24 MFMAs.
-template <bool ACT_IS_A, int MI, int KK, int H2W_NS>
+// RAG (H2wArgs::lens, the ragged FS2 front): activation batch item za holds lens[za] <= rows real rows.  A workgroup whose first row lies at or
+// beyond that returns before its first load; rows at or beyond it read as zero (so do a convolution's taps that reach them) and are stored
+// as zero by the workgroups that straddle the bound.  A template flag as gemm.hip's: the padded instantiations compile to what they were.
+template <bool ACT_IS_A, int MI, int KK, int H2W_NS, bool RAG = false>
 __global__ __launch_bounds__(256, 2) void gemm_h2w_kernel(H2wArgs g) {
   constexpr int BMA = 32 * MI;
   constexpr int BK = 16 * KK, H2W_ROWB = 2 * BK + 16, PPR = 2 * KK;   // pieces of 16 bytes per row and plane
@@ -156,6 +159,10 @@ __global__ __launch_bounds__(256, 2) void gemm_h2w_kernel(H2wArgs g) {
   }
   const int zw = z / g.zdiv, za = z - zw * g.zdiv;
   const int arow0 = at * BMA;
+  const int Mb = rag_len<RAG>(g.lens, za, g.rows);   // rows of this batch item; g.rows stays the pitch of the grid
+  if constexpr (RAG) {
+    if (arow0 >= Mb) return;                         // the whole tile lies beyond the item's end: nothing to load, nothing to store
+  }
 
   const unsigned act_bytes = (unsigned)((long long)g.rows * g.lda * 2);
   const rsrc_t rs_hi = mk_rsrc(g.act + (long long)za * g.sAct, act_bytes);
@@ -176,7 +183,7 @@ __global__ __launch_bounds__(256, 2) void gemm_h2w_kernel(H2wArgs g) {
     const int p = tid + 256 * j, row = p / PPR, qd = p % PPR;
     const bool ok = row < WR;
     const int grow = arow0 + row + g.tap_shift0;          // rows outside [0, rows) read as zero: the descriptor's range check (negative offsets wrap)
-    goff[j] = ok && grow >= 0 ? (grow * g.lda + qd * 8) * 2 : 0x7ffffff0;
+    goff[j] = ok && grow >= 0 && (!RAG || grow < Mb) ? (grow * g.lda + qd * 8) * 2 : 0x7ffffff0;
     loff[j] = ok ? row * H2W_ROWB + qd * 16 : -1;
   }
   u32x4 sh[NPH], sl[NPH];
@@ -404,10 +411,11 @@ __global__ __launch_bounds__(256, 2) void gemm_h2w_kernel(H2wArgs g) {
       for (int e = 0; e < 4; ++e) {
         float x = et[(4 * rg + e) * EP + cc] * H2W_OUT + bv;
         if (g.alpha_ncols == 0 || wrow0 + cc < g.alpha_ncols) x *= g.alpha;
+        if (RAG && row0 + e >= Mb) x = 0.f;
         v[e] = x * H2W_IN;
         bad |= !(fabsf(v[e]) < 65000.0f) && row0 + e < g.rows;
       }
-      const int b0 = row0 / T, t0 = row0 - b0 * T;
+      const int b0 = RAG ? z : row0 / T, t0 = RAG ? row0 : row0 - b0 * T;   // (RAG: one utterance per batch item, rows == T)
       if ((T & 3) == 0 && row0 + 3 < g.rows) {   // the 4 keys belong to one utterance and stay consecutive in the stored order
         f16x4 hv, lv;
 #pragma unroll
@@ -427,7 +435,7 @@ __global__ __launch_bounds__(256, 2) void gemm_h2w_kernel(H2wArgs g) {
         for (int e = 0; e < 4; ++e) {
           const int row = row0 + e;
           if (row >= g.rows) break;
-          const int b = row / T, t = row - b * T;
+          const int b = RAG ? z : row / T, t = RAG ? row : row - b * T;
           _Float16* dst = vth + ((long long)b * g.qkv_H + d) * Tp;
           const _Float16 h = (_Float16)v[e];
           dst[stored(t)] = h;
@@ -459,6 +467,7 @@ __global__ __launch_bounds__(256, 2) void gemm_h2w_kernel(H2wArgs g) {
         if (Rp) v += Rp[ACT_IS_A ? (long long)arow * g.ldr + wrow : (long long)wrow * g.ldr + arow];
         if (RS) v *= RS[arow];
       }
+      if (RAG && arow >= Mb) v = 0.f;
       o4[e] = v;
     }
     if (Cp) {
@@ -490,7 +499,7 @@ __global__ __launch_bounds__(256, 2) void gemm_h2w_kernel(H2wArgs g) {
 }
 #undef BSG_MFMA_W
 
-template <bool ACT_IS_A, int MI, int KK, int NS>
+template <bool ACT_IS_A, int MI, int KK, int NS, bool RAG = false>
 int h2w_launch(const H2wArgs& g, hipStream_t st) {
   constexpr int BMA = 32 * MI;
   // the two stages; the epilogue's fp32 image of the workgroup tile aliases them (pitch = contiguous extent + 4 floats)
@@ -502,11 +511,11 @@ int h2w_launch(const H2wArgs& g, hipStream_t st) {
   static bool attr_set = false;
   if (!attr_set) {
     constexpr size_t smax = (size_t)2 * 2 * (BMA + H2W_MAXTAPS - 1) * (32 * KK + 16);
-    BSG_HIP(hipFuncSetAttribute((const void*)gemm_h2w_kernel<ACT_IS_A, MI, KK, NS>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    BSG_HIP(hipFuncSetAttribute((const void*)gemm_h2w_kernel<ACT_IS_A, MI, KK, NS, RAG>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)(smax > epi ? smax : epi)));
     attr_set = true;
   }
-  hipLaunchKernelGGL((gemm_h2w_kernel<ACT_IS_A, MI, KK, NS>), dim3(nwg), dim3(256), lds, st, g);
+  hipLaunchKernelGGL((gemm_h2w_kernel<ACT_IS_A, MI, KK, NS, RAG>), dim3(nwg), dim3(256), lds, st, g);
   BSG_LAUNCH_CHECK();
   // what was launched, for the caller's launch record: tile height, then the weight ring (KK = 16: the 256-deep slices of the 32-row tiles)
   if (g.form_out) *g.form_out = KK == 16 ? "h2w/32/deep" : MI == 1 ? (NS == 16 ? "h2w/32/ring16" : NS == 8 ? "h2w/32/ring8" : "h2w/32/ring4")
@@ -586,7 +595,7 @@ int launch_gemm_h2w(const H2wArgs& g0, hipStream_t st) {
   BSG_REQUIRE(g.up_u == 0 || (g.up_u == 8 && !g.act_is_a && g.C && g.up_p % 4 == 0 && g.up_lout > 0 && g.act_fn == ACT_NONE && !g.R && !g.rowscale &&
                               g.alpha == 1.f && g.sBias == 0),
               "gemm_h2w: polyphase output: up_u=%d act_is_a=%d", g.up_u, g.act_is_a);
-  BSG_REQUIRE(g.qkv_T == 0 || (g.act_is_a && g.out && g.vt && g.batch == 1 && g.qkv_H % 128 == 0 && g.Wn == 3 * g.qkv_H && g.ldo == 2 * g.qkv_H &&
+  BSG_REQUIRE(g.qkv_T == 0 || (g.act_is_a && g.out && g.vt && (g.batch == 1 || (g.lens && g.rows == g.qkv_T)) && g.qkv_H % 128 == 0 && g.Wn == 3 * g.qkv_H && g.ldo == 2 * g.qkv_H &&
                                g.qkv_Tp % 32 == 0 && g.qkv_Tp >= g.qkv_T && g.rows % g.qkv_T == 0 && !g.C && g.act_fn == ACT_NONE && !g.R && !g.rowscale),
               "gemm_h2w: QKV output: T=%d Tp=%d H=%d Wn=%d", g.qkv_T, g.qkv_Tp, g.qkv_H, g.Wn);
   if (g.zdiv <= 0) g.zdiv = g.batch;
@@ -606,6 +615,15 @@ int launch_gemm_h2w(const H2wArgs& g0, hipStream_t st) {
   const bool tiny = g.act_is_a && (long long)cdiv(g.rows, 64) * (g.Wn / 128) * g.batch < tiny_env;
   static int ring_env = -1;   // BSG_H2W_RING=4: the 4-step weight ring at every tile size (rounds 4's first form)
   if (ring_env < 0) { const char* e = getenv("BSG_H2W_RING"); ring_env = e ? atoi(e) : 16; }
+  if (g.lens) {
+    // ragged (the FS2 front): the [token][feature] forms at their default rings only, whatever BSG_H2W_RING / BSG_H2W_DEEP say — same tile
+    // heights and thresholds as below (K % 256 == 0 makes every ring length divide the step count)
+    BSG_REQUIRE(g.act_is_a && g.K % 256 == 0 && !g.up_u && g.zdiv == g.batch, "gemm_h2w: lengths are built for the [token][feature] forms with K %% 256 == 0 (act_is_a=%d K=%d)",
+                g.act_is_a, g.K);
+    if (tiny) return g.taps == 1 ? h2w_launch<true, 1, 16, 16, true>(g, st) : h2w_launch<true, 1, 2, 16, true>(g, st);
+    if (g.taps == 1) return !small ? h2w_launch<true, 4, 4, 4, true>(g, st) : h2w_launch<true, 2, 4, 8, true>(g, st);
+    return !small ? h2w_launch<true, 4, 2, 4, true>(g, st) : h2w_launch<true, 2, 2, 8, true>(g, st);
+  }
   const int steps = g.K / 16 * g.taps;
   const bool r16 = ring_env >= 16 && steps % 16 == 0, r8 = ring_env >= 8 && steps % 8 == 0;
   if (tiny) {

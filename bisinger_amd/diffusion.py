@@ -260,7 +260,7 @@ class GaussianDiffusion(nn.Module):
     # ------------------------------------------------------------------ reference forward (:230-273)
     @torch.no_grad()
     def forward(self, txt_tokens, mel2ph=None, spk_embed=None, ref_mels=None, f0=None, uv=None, energy=None,
-                infer=False, noise=None, seed=None, rows=None, ragged=False, **kwargs):
+                infer=False, noise=None, seed=None, rows=None, ragged=False, ragged_front=False, **kwargs):
         """Extensions over the reference signature: ``noise`` (supplied draws, parity mode), ``seed`` (Philox
         key, default hparams['seed']) and ``rows`` (slice of the batch this process generates; outputs then
         have len(rows) rows and reproduce the same rows of the unsharded call — SURVEY.md §8e).
@@ -270,26 +270,34 @@ class GaussianDiffusion(nn.Module):
         forms order GEMM1's k-steps differently and add the conditioner term last (1e-6 on the mel).  ``BSG_H2_PART=0`` makes the
         arithmetic of a row independent of the batch around it.
         ``ragged=True``: every row is decoded at its own length, lengths = (mel2ph > 0).sum(-1) of the given or predicted ``mel2ph``
-        (ragged_lengths: ValueError unless its non-zeros are a prefix of each row); ``mel_out`` is 0 beyond.  Not with ``rows``."""
+        (ragged_lengths: ValueError unless its non-zeros are a prefix of each row); ``mel_out`` is 0 beyond.  Not with ``rows``.
+        ``ragged_front=True`` (independent of ``ragged``): the FastSpeech2 front runs every row as that utterance alone
+        (``FastSpeech2MIDI.forward(ragged=True)`` / ``FastSpeech2.forward(ragged=True)``): ``decoder_inp``, ``fs2_mel``, the predicted
+        durations and pitch no longer depend on the batch around a row.  Not with ``rows``.  The sampler's Philox draws stay indexed by
+        global row and padded stride, so the final ``mel_out`` equals the lone call's only with supplied ``noise``."""
         if not infer:
             raise NotImplementedError('training (p_losses) is outside the accelerated hot path (SURVEY.md §8)')
         if ragged and rows is not None:
             raise NotImplementedError('forward(ragged=True, rows=...): sharded ragged batches are not supported')
+        if ragged_front and rows is not None:
+            raise NotImplementedError('forward(ragged_front=True, rows=...): sharded ragged batches are not supported')
         # one range guard around the whole call (FS2, the conditioner projections, the sampler): an operand beyond the fp16 range of the
         # split-fp16 GEMMs repeats all of it with THAT handle (FS2's or the denoiser's) on the fp32 matrix pipe (_lib.range_guarded; the nested
         # guards register their handles with this one and leave the check to it)
         return _lib.range_guarded(lambda: self._forward_infer(txt_tokens, mel2ph, spk_embed, ref_mels, f0, uv, energy, noise, seed, rows,
-                                                              ragged=ragged, **kwargs), 'GaussianDiffusion.forward', device=self,
+                                                              ragged=ragged, ragged_front=ragged_front, **kwargs),
+                                  'GaussianDiffusion.forward', device=self,
                                   owners=tuple(m for m in (self.fs2, self.denoise_fn) if isinstance(m, _lib.GemmGuarded)))
 
-    def _forward_infer(self, txt_tokens, mel2ph, spk_embed, ref_mels, f0, uv, energy, noise, seed, rows, ragged=False, **kwargs):
+    def _forward_infer(self, txt_tokens, mel2ph, spk_embed, ref_mels, f0, uv, energy, noise, seed, rows, ragged=False, ragged_front=False,
+                       **kwargs):
         B_total = txt_tokens.shape[0]
         row0 = 0
         if rows is not None:
             row0, stop, stride = rows.indices(B_total)
             assert stride == 1 and stop > row0, 'rows must be a contiguous non-empty slice'
         ret = self.fs2(txt_tokens, mel2ph, spk_embed, ref_mels, f0, uv, energy, skip_decoder=False, infer=True,
-                       rows=rows, **kwargs)
+                       rows=rows, **({'ragged': True} if ragged_front else {}), **kwargs)
         if mel2ph is not None and rows is not None:
             mel2ph = mel2ph[rows]
         cond = ret['decoder_inp'].transpose(1, 2).contiguous()

@@ -10,7 +10,7 @@ reference's 143 ``fs2.*`` entries (names, shapes, order — including the two al
 ``bsg_fs2midi_*`` in libbisinger_hip (csrc/fs2.hip).
 """
 import math
-from ctypes import POINTER, byref, c_void_p, cast
+from ctypes import POINTER, byref, c_int32, c_void_p, cast
 
 import torch
 import torch.nn as nn
@@ -213,6 +213,27 @@ class FastspeechEncoder(FFTBlocks):
         self.embed_positions = SinusoidalPositionalEmbedding(hparams['hidden_size'], 0, init_size=DEFAULT_MAX_TARGET_POSITIONS)
 
 
+def prefix_lengths(masks, whats, mins):
+    """Row lengths of a ragged batch in ONE host read: for every boolean mask [B, n] (``txt_tokens > 0``, ``mel2ph > 0``) the count of each
+    row as a list of ints.  ValueError (as diffusion.ragged_lengths) unless the set positions of each row are a prefix of it and the count
+    is at least ``mins[i]``: a row with a hole has no length at which it could run alone."""
+    cols = []
+    for m, lo in zip(masks, mins):
+        n = m.sum(-1)
+        prefix = torch.arange(m.shape[-1], device=m.device)[None, :] < n[:, None]
+        cols += [n, ((m != prefix).any(-1) | (n < lo)).long()]
+    host = torch.stack(cols, 0).tolist()
+    out = []
+    for i, what in enumerate(whats):
+        n, bad = host[2 * i], host[2 * i + 1]
+        if any(bad):
+            b = bad.index(1)
+            raise ValueError(f'ragged batch: row {b} of {what} is not one run from position 0 (non-zero prefix, then zeros) or is shorter '
+                             f'than {mins[i]}; it cannot run at its own length')
+        out.append([int(v) for v in n])
+    return out
+
+
 def _refuse(key, what):
     raise NotImplementedError(f"{key}: {what} (INTEGRATION.md, 'The pitch adaptor and the plain front')")
 
@@ -359,19 +380,21 @@ class _FastSpeech2Base(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
             _lib.check(_lib.load().bsg_fs2midi_debug_poison_workspace(self.handle(), _lib.stream_ptr()), 'bsg_fs2midi_debug_poison_workspace')
 
     @torch.no_grad()
-    def regulate(self, enc):
+    def regulate(self, enc, with_lengths=False):
         """LengthRegulator on the predicted durations (tts_modules.py:161-191); one host sync, as in the
-        reference (the output length is data dependent, :182)."""
+        reference (the output length is data dependent, :182).  ``with_lengths``: -> (mel2ph, frames of every row) from that same read
+        (a row's frames are a prefix by construction; a row may have none)."""
         dur, txt = enc['dur'], enc['txt']
         B, Tt = txt.shape
-        T = int((dur * (txt != 0)).sum(-1).max().item())
+        per_row = [int(v) for v in (dur * (txt != 0)).sum(-1).tolist()]
+        T = max(per_row)
         if T <= 0:
             raise _lib.BsgError('duration predictor produced an empty utterance')
         mel2ph = torch.empty(B, T, dtype=torch.long, device=txt.device)
         with torch.cuda.device(txt.device):
             _lib.check(_lib.load().bsg_length_regulator(_lib.ptr(dur), _lib.ptr(txt), _lib.ptr(mel2ph), B, Tt, T,
                                                         _lib.stream_ptr()), 'bsg_length_regulator')
-        return mel2ph
+        return (mel2ph, per_row) if with_lengths else mel2ph
 
     @torch.no_grad()
     def decode(self, enc_out, mel2ph, spk, speechsing, skip_decoder=False):
@@ -380,11 +403,13 @@ class _FastSpeech2Base(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         return r['decoder_inp'], r.get('mel_out')
 
     @torch.no_grad()
-    def decode_all(self, enc_out, mel2ph, spk, speechsing, skip_decoder=False, f0=None, uv=None):
+    def decode_all(self, enc_out, mel2ph, spk, speechsing, skip_decoder=False, f0=None, uv=None, n_tok=None, n_frames=None):
         """Frame-level part: gather by mel2ph (+ the pitch adaptor, fs2.py:139-142, 201-234), +spk +style, mask; FFT decoder + mel_out
         (fs2.py:166-195).  ``f0`` / ``uv`` [B,T]: supplied values (neither is written: the reference zeroes the caller's f0 in place,
         fs2.py:230; this does not).  -> dict: decoder_inp, mel_out (unless skip_decoder) and, with the adaptor, pitch_pred [B,T,2],
-        f0_denorm [B,T] and pitch_bin [B,T]."""
+        f0_denorm [B,T] and pitch_bin [B,T].  ``n_tok`` / ``n_frames`` (B ints each, together): a ragged batch (bsg_fs2_decode_ragged) — row b
+        is what the B = 1 call gives on its first n_tok[b] tokens and n_frames[b] frames; beyond them every float is 0, pitch_bin is 1 and
+        no input is read."""
         dev = enc_out.device
         h = self.handle()
         B, Tt, _ = enc_out.shape
@@ -398,11 +423,19 @@ class _FastSpeech2Base(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         decoder_inp = torch.empty(B, T, self.hidden_size, device=dev)
         mel_out = None if skip_decoder else torch.empty(B, T, self.out_dims, device=dev)
         lib = _lib.load()
+        if (n_tok is None) != (n_frames is None):
+            raise _lib.BsgError('decode_all: n_tok and n_frames go together')
+        rag = None if n_tok is None else ((c_int32 * B)(*n_tok), (c_int32 * B)(*n_frames))
         if not self.use_pitch_embed and self.FRONT == _lib.FS2_FRONT_MIDI:
             with torch.cuda.device(dev):
-                _lib.check(lib.bsg_fs2midi_decode(h, _lib.ptr(enc_out.contiguous()), _lib.ptr(mel2ph), _lib.ptr(spk),
-                                                  _lib.ptr(speechsing), B, Tt, T, _lib.ptr(decoder_inp), _lib.ptr(mel_out),
-                                                  _lib.stream_ptr()), 'bsg_fs2midi_decode')
+                if rag is None:
+                    _lib.check(lib.bsg_fs2midi_decode(h, _lib.ptr(enc_out.contiguous()), _lib.ptr(mel2ph), _lib.ptr(spk),
+                                                      _lib.ptr(speechsing), B, Tt, T, _lib.ptr(decoder_inp), _lib.ptr(mel_out),
+                                                      _lib.stream_ptr()), 'bsg_fs2midi_decode')
+                else:
+                    _lib.check(lib.bsg_fs2_decode_ragged(h, _lib.ptr(enc_out.contiguous()), _lib.ptr(mel2ph), _lib.ptr(spk), _lib.ptr(speechsing),
+                                                         None, None, rag[0], rag[1], B, Tt, T, None, None, None, _lib.ptr(decoder_inp),
+                                                         _lib.ptr(mel_out), _lib.stream_ptr()), 'bsg_fs2_decode_ragged')
                 # the same condition per token (row 0: padding): every frame of a token carries one vector, and the denoiser binds the
                 # Tt + 1 rows instead of the T frames (DiffNet.prepare_tokens); cond_tok[b, mel2ph[b, f]] == decoder_inp[b, f] bit for bit
                 cond_tok = torch.empty(B, Tt + 1, self.hidden_size, device=dev)
@@ -425,30 +458,54 @@ class _FastSpeech2Base(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         else:
             f0 = uv = None
         with torch.cuda.device(dev):
-            _lib.check(lib.bsg_fs2_decode(h, _lib.ptr(enc_out.contiguous()), _lib.ptr(mel2ph), _lib.ptr(spk), _lib.ptr(speechsing),
-                                          _lib.ptr(f0), _lib.ptr(uv), B, Tt, T, _lib.ptr(pred), _lib.ptr(f0d), _lib.ptr(bins),
-                                          _lib.ptr(decoder_inp), _lib.ptr(mel_out), _lib.stream_ptr()), 'bsg_fs2_decode')
+            if rag is None:
+                _lib.check(lib.bsg_fs2_decode(h, _lib.ptr(enc_out.contiguous()), _lib.ptr(mel2ph), _lib.ptr(spk), _lib.ptr(speechsing),
+                                              _lib.ptr(f0), _lib.ptr(uv), B, Tt, T, _lib.ptr(pred), _lib.ptr(f0d), _lib.ptr(bins),
+                                              _lib.ptr(decoder_inp), _lib.ptr(mel_out), _lib.stream_ptr()), 'bsg_fs2_decode')
+            else:
+                _lib.check(lib.bsg_fs2_decode_ragged(h, _lib.ptr(enc_out.contiguous()), _lib.ptr(mel2ph), _lib.ptr(spk), _lib.ptr(speechsing),
+                                                     _lib.ptr(f0), _lib.ptr(uv), rag[0], rag[1], B, Tt, T, _lib.ptr(pred), _lib.ptr(f0d),
+                                                     _lib.ptr(bins), _lib.ptr(decoder_inp), _lib.ptr(mel_out), _lib.stream_ptr()),
+                           'bsg_fs2_decode_ragged')
         ret = dict(decoder_inp=decoder_inp) if skip_decoder else dict(decoder_inp=decoder_inp, mel_out=mel_out)
         if self.use_pitch_embed:
             ret.update(pitch_pred=pred, f0_denorm=f0d, pitch_bin=bins)
         return ret
 
     def forward(self, txt_tokens, mel2ph=None, spk_embed=None, ref_mels=None, f0=None, uv=None, energy=None,
-                skip_decoder=False, spk_embed_dur_id=None, spk_embed_f0_id=None, infer=False, rows=None, **kwargs):
+                skip_decoder=False, spk_embed_dur_id=None, spk_embed_f0_id=None, infer=False, rows=None, ragged=False, **kwargs):
         """``rows`` (slice, extension): generate only these batch rows — what a rank of a sharded run asks for.  The inputs
         stay the WHOLE batch's: the ESM attends over the batch axis, so every row's ``lang`` enters this rank's K / V; with ``mel2ph``
         given nothing else of the other rows is computed (``encode(rows=...)``).  With predicted durations the frame count T is the
         maximum over the whole batch (tts_modules.py:182), so the token-level front then runs on every row and is sliced afterwards.
-        ``f0`` / ``uv`` [B,T] (use_pitch_embed): supplied pitch (log2 Hz) and unvoiced flags; never written."""
-        return _lib.range_guarded(lambda: self._forward(txt_tokens, mel2ph, spk_embed, skip_decoder, rows, f0, uv, **kwargs),
+        ``f0`` / ``uv`` [B,T] (use_pitch_embed): supplied pitch (log2 Hz) and unvoiced flags; never written.
+        ``ragged=True`` (extension, ABI v20): every row is what this forward returns for that utterance ALONE — the B = 1 call on
+        ``txt_tokens[b, :nt_b]``, ..., ``mel2ph[b, :n_b]`` with nt_b = (txt_tokens[b] > 0).sum() and n_b = (mel2ph[b] > 0).sum() of the given
+        or predicted ``mel2ph`` — instead of depending on the batch around it (the ESM's softmax over the batch axis, LayerNorm's bias read
+        by the k-tap convolutions in the padding).  Every float output is 0 beyond a row's end, ``mel2ph`` and ``dur_choice`` are 0,
+        ``pitch_bin`` is 1; inputs are not read there, and no padding is computed.  ValueError unless the non-pad tokens (and the frames of a
+        given ``mel2ph``) are a prefix of each row with at least one token; NotImplementedError with ``rows``.  The lengths cost one host
+        read (with predicted durations the frame counts come with the read ``regulate`` makes anyway)."""
+        if ragged and rows is not None:
+            raise NotImplementedError('forward(ragged=True, rows=...): sharded ragged batches are not supported')
+        return _lib.range_guarded(lambda: self._forward(txt_tokens, mel2ph, spk_embed, skip_decoder, rows, f0, uv, ragged=ragged, **kwargs),
                                   f'{type(self).__name__}.forward', device=self, owners=(self,))
 
-    def _forward(self, txt_tokens, mel2ph, spk_embed, skip_decoder, rows, f0=None, uv=None, **kwargs):
+    def _forward(self, txt_tokens, mel2ph, spk_embed, skip_decoder, rows, f0=None, uv=None, ragged=False, **kwargs):
         ret = {}
         local = rows is not None and mel2ph is not None      # the token front on this rank's rows only
-        enc = self.encode(txt_tokens, spk_embed, predict_dur=mel2ph is None, rows=rows if local else None, **kwargs)
+        n_tok = n_frames = None
+        if ragged:
+            if mel2ph is None:
+                n_tok, = prefix_lengths([txt_tokens > 0], ['txt_tokens'], [1])
+            else:
+                n_tok, n_frames = prefix_lengths([txt_tokens > 0, mel2ph.to(txt_tokens.device) > 0], ['txt_tokens', 'mel2ph'], [1, 0])
+        enc = self.encode(txt_tokens, spk_embed, predict_dur=mel2ph is None, rows=rows if local else None, n_tok=n_tok, **kwargs)
         if mel2ph is None:
-            mel2ph = self.regulate(enc)
+            if ragged:
+                mel2ph, n_frames = self.regulate(enc, with_lengths=True)
+            else:
+                mel2ph = self.regulate(enc)
             ret['dur'] = enc['dur_xs'][:, :, None]
             ret['dur_choice'] = enc['dur']
         # (with mel2ph given the reference also runs the predictor for its training loss; inference does not use it)
@@ -463,7 +520,7 @@ class _FastSpeech2Base(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
             f0 = None if f0 is None else f0[rows]
             uv = None if uv is None else uv[rows]
         ret['mel2ph'] = mel2ph
-        ret.update(self.decode_all(enc_out, mel2ph, spk, speechsing, skip_decoder, f0=f0, uv=uv))
+        ret.update(self.decode_all(enc_out, mel2ph, spk, speechsing, skip_decoder, f0=f0, uv=uv, n_tok=n_tok, n_frames=n_frames))
         return ret
 
 
@@ -492,8 +549,10 @@ class FastSpeech2MIDI(_FastSpeech2Base):
 
     # ------------------------------------------------------------------ reference forward (fs2.py:94-197)
     @torch.no_grad()
-    def encode(self, txt_tokens, spk_embed, predict_dur=False, rows=None, **kwargs):
+    def encode(self, txt_tokens, spk_embed, predict_dur=False, rows=None, n_tok=None, **kwargs):
         """Token-level front: embeddings + ESM + FFT encoder (+ duration predictor)   (fs2.py:111-165).
+        ``n_tok`` (B ints, not with ``rows``): a ragged batch (bsg_fs2midi_encode_ragged) — row b is the B = 1 call on its first n_tok[b]
+        tokens: its own ESM (one key: a function of the token's lang id), zeros read beyond its end, nothing computed there.
         ESM attends over the batch axis (common_layers.py:853): the inputs are always the WHOLE batch's.  ``rows`` (a contiguous slice,
         extension): the outputs for these batch rows only — K / V of the ESM (projections of LN(lang_embed[lang]), :850-853, the only thing
         other rows contribute) are still formed for every row; Q, the ESM's FFN, the encoder and the duration predictor run on the rows
@@ -520,8 +579,14 @@ class FastSpeech2MIDI(_FastSpeech2Base):
         enc_out = torch.empty(nb, Tt, self.hidden_size, device=dev)
         dur_xs = torch.empty(nb, Tt, device=dev) if predict_dur else None
         dur = torch.empty(nb, Tt, dtype=torch.long, device=dev) if predict_dur else None
+        if n_tok is not None and rows is not None:
+            raise NotImplementedError('encode(n_tok=..., rows=...): sharded ragged batches are not supported')
         with torch.cuda.device(dev):
-            if rows is None:
+            if n_tok is not None:
+                _lib.check(lib.bsg_fs2midi_encode_ragged(h, _lib.ptr(txt), _lib.ptr(pitch_midi), _lib.ptr(midi_dur), _lib.ptr(is_slur),
+                                                         _lib.ptr(lang), _lib.ptr(spk), (c_int32 * B)(*n_tok), B, Tt, _lib.ptr(enc_out),
+                                                         _lib.ptr(dur_xs), _lib.ptr(dur), _lib.stream_ptr()), 'bsg_fs2midi_encode_ragged')
+            elif rows is None:
                 _lib.check(lib.bsg_fs2midi_encode(h, _lib.ptr(txt), _lib.ptr(pitch_midi), _lib.ptr(midi_dur), _lib.ptr(is_slur),
                                                   _lib.ptr(lang), _lib.ptr(spk), B, Tt, _lib.ptr(enc_out), _lib.ptr(dur_xs),
                                                   _lib.ptr(dur), _lib.stream_ptr()), 'bsg_fs2midi_encode')
@@ -550,9 +615,10 @@ class FastSpeech2(_FastSpeech2Base):
         return self.encoder.embed_positions.table(DEFAULT_MAX_TARGET_POSITIONS + 2)
 
     @torch.no_grad()
-    def encode(self, txt_tokens, spk_embed, predict_dur=False, rows=None, **kwargs):
+    def encode(self, txt_tokens, spk_embed, predict_dur=False, rows=None, n_tok=None, **kwargs):
         """Token-level front (fs2.py:100-129): one embedding launch, the FFT encoder (+ duration predictor).  Nothing couples the rows of a
-        batch: ``rows`` (a contiguous slice) simply selects the rows that run."""
+        batch: ``rows`` (a contiguous slice) simply selects the rows that run.  ``n_tok`` (B ints, not with ``rows``): a ragged batch
+        (bsg_fs2_encode_plain_ragged) — row b is the B = 1 call on its first n_tok[b] tokens."""
         lib = _lib.load()
         h = self.handle()
         dev = txt_tokens.device
@@ -574,7 +640,13 @@ class FastSpeech2(_FastSpeech2Base):
         enc_out = torch.empty(nb, Tt, self.hidden_size, device=dev)
         dur_xs = torch.empty(nb, Tt, device=dev) if predict_dur else None
         dur = torch.empty(nb, Tt, dtype=torch.long, device=dev) if predict_dur else None
+        if n_tok is not None and rows is not None:
+            raise NotImplementedError('encode(n_tok=..., rows=...): sharded ragged batches are not supported')
         with torch.cuda.device(dev):
-            _lib.check(lib.bsg_fs2_encode_plain(h, _lib.ptr(txt), _lib.ptr(spk), B, Tt, row0, nb, _lib.ptr(enc_out), _lib.ptr(dur_xs),
-                                                _lib.ptr(dur), _lib.stream_ptr()), 'bsg_fs2_encode_plain')
+            if n_tok is not None:
+                _lib.check(lib.bsg_fs2_encode_plain_ragged(h, _lib.ptr(txt), _lib.ptr(spk), (c_int32 * B)(*n_tok), B, Tt, _lib.ptr(enc_out),
+                                                           _lib.ptr(dur_xs), _lib.ptr(dur), _lib.stream_ptr()), 'bsg_fs2_encode_plain_ragged')
+            else:
+                _lib.check(lib.bsg_fs2_encode_plain(h, _lib.ptr(txt), _lib.ptr(spk), B, Tt, row0, nb, _lib.ptr(enc_out), _lib.ptr(dur_xs),
+                                                    _lib.ptr(dur), _lib.stream_ptr()), 'bsg_fs2_encode_plain')
         return dict(enc_out=enc_out, txt=txt, spk=spk, dur_xs=dur_xs, dur=dur)

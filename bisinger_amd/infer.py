@@ -206,8 +206,10 @@ class DiffSingerE2EInfer(BaseSVSInfer):
             self.pe.eval()
         return model
 
-    def _generate(self, sample, seed=None, ragged=False):
+    def _generate(self, sample, seed=None, ragged=False, ragged_front=False):
         kw = {'ragged': True} if ragged else {}
+        if ragged_front:
+            kw['ragged_front'] = True
         with torch.no_grad():
             output = self.model(sample['txt_tokens'], spk_embed=sample.get('spk_ids'), ref_mels=None, infer=True,
                                 pitch_midi=sample['pitch_midi'], midi_dur=sample['midi_dur'], is_slur=sample['is_slur'],
@@ -235,7 +237,7 @@ class DiffSingerE2EInfer(BaseSVSInfer):
         new[1:] = (d[1:] != d[:-1]) | (p[1:] != p[:-1])
         return int(np.ceil(d[new].sum() * hparams['audio_sample_rate'] / hparams['hop_size']))
 
-    def _generate_wavs(self, items, seed, ragged=False, denoise_c=None, ragged_vocoder=False, ragged_pitch=False):
+    def _generate_wavs(self, items, seed, ragged=False, denoise_c=None, ragged_vocoder=False, ragged_pitch=False, ragged_front=False):
         """One padded batch -> (list of trimmed waveforms, frames per item, padded frame count T).  ``ragged``: the mel decoder runs every
         row at its own length (GaussianDiffusion.forward(ragged=True)).  ``ragged_vocoder``: the HiFi-GAN generator (plain or NSF) runs every
         row at its own length too (HifiGanGenerator.forward(lengths=)), as the reference vocodes each utterance alone; False: it runs the
@@ -252,7 +254,7 @@ class DiffSingerE2EInfer(BaseSVSInfer):
                 raise NotImplementedError(f"forward_batch(ragged_vocoder=True): vocoder '{name or type(self.vocoder).__name__}' "
                                           f'({type(self.vocoder).__name__}) has no ragged forward; only the HiFi-GAN generator, plain or NSF, has')
         sample = self.collate(items)
-        output = self._generate(sample, seed, ragged)
+        output = self._generate(sample, seed, ragged, **({'ragged_front': True} if ragged_front else {}))
         mel, mel2ph = output['mel_out'], output['mel2ph']
         hop = int(np.prod(self.vocoder.h['upsample_rates']))
         n_frames = (mel2ph > 0).sum(-1).tolist()
@@ -272,7 +274,7 @@ class DiffSingerE2EInfer(BaseSVSInfer):
         return [wav[i, :n * hop].cpu().numpy() for i, n in enumerate(n_frames)], n_frames, int(mel.shape[1])
 
     def forward_batch(self, items, seed=None, max_frames=None, max_sentences=None, ragged=False, denoise_c=None, ragged_vocoder=False,
-                      ragged_pitch=False):
+                      ragged_pitch=False, ragged_front=False):
         """Batched generation: list of items -> list of 1-D waveforms (in the order given), each trimmed to its utterance.
 
         With ``max_frames`` (budget on padded frames per batch: rows x longest row) and/or ``max_sentences`` the items are
@@ -280,8 +282,9 @@ class DiffSingerE2EInfer(BaseSVSInfer):
         size-ordered indices): sorted by estimated length, packed greedily while (n + 1) x longest <= max_frames and
         n < max_sentences; each bucket is one padded batch.  Without either, all items form one batch.
 
-        NB (reference quirk kept): ESM attends over the batch axis (common_layers.py:853), so a row's result depends on
-        the rows it is batched with — the unit of reproducibility (and of the oracle in the tests) is the BUCKET.
+        NB (reference quirk kept by default): ESM attends over the batch axis (common_layers.py:853), so a row's result depends on
+        the rows it is batched with — the unit of reproducibility (and of the oracle in the tests) is the BUCKET, unless
+        ``ragged_front=True`` (below) makes it the utterance.
         ``self.last_batch_stats`` reports the buckets and the padded-frame waste with and without bucketing.
 
         ``ragged=True``: buckets by ``max_sentences`` only (``max_frames`` is refused: a ragged bucket computes no padding), and the mel
@@ -301,7 +304,13 @@ class DiffSingerE2EInfer(BaseSVSInfer):
         the pitch extractor runs every row of a bucket at its own length (``PitchExtractor.forward(lengths=)``): the f0 that drives the NSF
         source is what the extractor gives for that row's mel alone, instead of depending on how much padding the bucket gave the row
         (GroupNorm's statistics run over a row's frames; in the padded batch, over its padding too).  False (default): the padded mel,
-        every result as before."""
+        every result as before.
+
+        ``ragged_front=True`` (with any of the other three on or off): the FastSpeech2 front runs every row of a bucket as that utterance
+        alone (``GaussianDiffusion.forward(ragged_front=True)``): the condition, the predicted durations and the adaptor's f0 are what
+        ``forward_model`` computes for the item — its own ESM instead of a softmax over the bucket, zeros instead of LayerNorm's bias in the
+        padding the convolutions reach — and no padded token or frame is computed.  The sampler's Philox draws stay indexed by the row's
+        place in the bucket, so the waveform still differs from ``forward_model``'s.  False (default): every result as before."""
         est = [self.estimate_frames(it) for it in items]
         if ragged and max_frames is not None:
             raise ValueError('forward_batch(ragged=True): buckets by max_sentences only; max_frames budgets padded frames')
@@ -312,7 +321,7 @@ class DiffSingerE2EInfer(BaseSVSInfer):
         wavs, frames = [None] * len(items), [0] * len(items)
         padded = groups = tiles = 0
         for b in buckets:
-            w, nf, T = self._generate_wavs([items[i] for i in b], seed, ragged, denoise_c, ragged_vocoder, ragged_pitch)
+            w, nf, T = self._generate_wavs([items[i] for i in b], seed, ragged, denoise_c, ragged_vocoder, ragged_pitch, ragged_front)
             padded += T * len(b)
             if ragged:
                 from .diffnet import ragged_plan

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define BSG_ABI_VERSION 19
+#define BSG_ABI_VERSION 20
 
 #define BSG_OK 0
 #define BSG_EINVAL (-22)  /* bad argument / shape the kernels do not support            */
@@ -343,6 +343,7 @@ int bsg_fs2midi_last_rows(const bsg_fs2midi* h, int32_t* token_rows, int32_t* st
  *   <s>.gemm:gemm_split/<64|128> | gemm_fast/<64|128> | gemm_f32
  *                                                      launch_gemm: split-fp16 | fp32 matrix pipe | the unaligned form
  *   tok:front                                          token_front_kernel (the plain front's embedding, ABI v16)
+ *   esm:alone tok:ragged dec.ragged                    the ragged entries (ABI v20, below): the ESM's two-row table, the ragged embedding launch, a ragged decode
  *   pit.pos pit.entry pit.gemm:<form as above> pit.ln pit.tail pit.launches:<n>   the pitch adaptor of a decode (ABI v16, bsg_fs2_decode)
  * with <s> = esm (the ESM's Linear layers), enc, dec (the FFT stacks); bsg_fftden_last_path: den, cleared by every bsg_fftden_forward.
  * The string belongs to the handle: valid until its next call or its destruction. */
@@ -422,6 +423,35 @@ int bsg_fs2_encode_plain(bsg_fs2midi* h, const int64_t* txt, const int64_t* spk_
 int bsg_fs2_decode(bsg_fs2midi* h, const float* enc_out, const int64_t* mel2ph, const int64_t* spk_id, const int64_t* speechsing,
                    const float* f0, const float* uv, int32_t B, int32_t T_txt, int32_t T, float* pitch_pred, float* f0_denorm,
                    int64_t* pitch_bin, float* decoder_inp, float* mel_out, void* stream);
+
+/* ABI v20: ragged batches through the front — every utterance as the B = 1 call on its own tokens and frames, worded after
+ * bsg_hifigan_forward_ragged / bsg_pitchext_forward_ragged.  The tensors keep their padded shapes ([B,T_txt] / [B,T]: the pitches); the
+ * counts are HOST arrays read before the call returns: n_tok_host[b] in 1 .. T_txt tokens (the non-pad tokens, a prefix of the row),
+ * n_frames_host[b] in 0 .. T frames (the frames with mel2ph > 0, a prefix).  A null array or a count outside its range is BSG_EINVAL with
+ * a message before any device call.  Every output of utterance b on [:n_tok] / [:n_frames] is what the padded entry returns for the
+ * B = 1 call on txt[b, :n_tok], ..., mel2ph[b, :n_frames] (to rounding: the sums are blocked differently); beyond an utterance's end
+ * every float output is 0, dur is 0 and pitch_bin is 1 (f0_to_coarse(0)), and NO input is read there.  What differs from the padded call:
+ *   the ESM (MIDI front) is the utterance's own: at B = 1 its attention over the batch axis has one key, so its result is a function of
+ *   the token's lang id — a two-row table per call, gathered in the embedding sum (esm:alone, tok:ragged in the launch record);
+ *   the k-tap convolutions of the FFT stacks and of the pitch predictor read zeros beyond an utterance's end in every layer (the padded
+ *   call reads LayerNorm's bias there);
+ *   nothing is computed beyond an utterance's end: LayerNorm rows, GEMM tiles, attention query tiles and key blocks that lie there return
+ *   before their first load.  bsg_fs2midi_last_rows then reports sum_b min(T, 32 * ceil(n_b / 32)) — rows in 32-row granules, the smallest
+ *   tile of any launch (64- and 128-row tiles round further) — for token_rows and stack_rows after an encode, stack_rows after a decode.
+ * The launch record adds tok:ragged / dec.ragged.  The QKV and attention forms are the padded call's at (B, T); the GEMM tile heights follow
+ * the same rules applied to (T rows, batch B) — the row-wise products go out as B problems of T rows — so near a threshold a tile token can
+ * differ from the padded call's.  A stack whose only attention form would be the score tensor (head dim other than 128,
+ * BSG_NO_FLASH_ATTN) is BSG_EINVAL before any device call.
+ * bsg_fs2_decode_ragged serves handles without the adaptor too (the five adaptor pointers NULL) and both fronts.  Workspaces grow as in
+ * every entry: a capturing stream that would have to grow one is refused before anything is touched. */
+int bsg_fs2midi_encode_ragged(bsg_fs2midi* h, const int64_t* txt, const int64_t* pitch_midi, const float* midi_dur, const int64_t* is_slur,
+                              const int64_t* lang, const int64_t* spk_id, const int32_t* n_tok_host, int32_t B, int32_t T_txt, float* enc_out,
+                              float* dur_xs, int64_t* dur, void* stream);
+int bsg_fs2_encode_plain_ragged(bsg_fs2midi* h, const int64_t* txt, const int64_t* spk_id, const int32_t* n_tok_host, int32_t B, int32_t T_txt,
+                                float* enc_out, float* dur_xs, int64_t* dur, void* stream);
+int bsg_fs2_decode_ragged(bsg_fs2midi* h, const float* enc_out, const int64_t* mel2ph, const int64_t* spk_id, const int64_t* speechsing,
+                          const float* f0, const float* uv, const int32_t* n_tok_host, const int32_t* n_frames_host, int32_t B, int32_t T_txt,
+                          int32_t T, float* pitch_pred, float* f0_denorm, int64_t* pitch_bin, float* decoder_inp, float* mel_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * FFT candidate denoiser: DIFF_DECODERS['fft'] = FFT(hidden, dec_layers, dec_ffn_kernel_size,
