@@ -173,6 +173,9 @@ _SIGS = {
     'bsg_pwg_forward': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_void_p]),
     'bsg_pwg_last_path': (c_char_p, [c_void_p]),
     'bsg_pwg_debug_poison_workspace': (c_int32, [c_void_p, c_void_p]),
+    # additions to v20: the ragged PWG forward; lengths_host: B int32 on the host
+    'bsg_pwg_forward_ragged': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_void_p]),
+    'bsg_pwg_last_tiles': (c_int32, [c_void_p]),
     'bsg_weight_norm_fold': (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     'bsg_gemm_f32': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                c_int32, c_int32, c_int32, c_int64, c_int64, c_int64, c_int32, c_void_p]),

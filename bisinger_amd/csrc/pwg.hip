@@ -50,6 +50,12 @@ struct LayerArgs {
   const float* auxw;   // PW_AUXW floats
   int L, dil, tiles_per_row, ntiles, first, last;
 };
+// ragged (RAG) only: frames per row | the rows' tile counts as a prefix table pre[0 .. B], pre[B] = ntiles; L stays the pitch of a row
+struct LayerRag {
+  const int* lens;
+  const int* pre;
+  int hop;
+};
 
 // acc[m][j] += A_step[m] (x) B_step[j] over `NS` k-steps; A and B are fetched U steps ahead of the products that use them
 template <int NS, typename AF, typename BF>
@@ -86,7 +92,12 @@ __device__ __forceinline__ void steps_product(f32x16 (&acc)[4][2], AF afetch, BF
   }
 }
 
-__global__ __launch_bounds__(256) void pwg_layer_kernel(const LayerArgs a) {
+// RAG (bsg_pwg_forward_ragged): row b ends at Lb = lens[b] hop inside the pitch L, and the workgroups walk the LIVE tiles only: tile ->
+// (row, tile of the row) through the prefix table.  A workgroup's tiles ascend, so its row only ever advances: two wave-uniform loads per
+// row passed (its tile count and its length), kept in scalar registers — a tile that stays in the row loads nothing before its first
+// sample.  The padded instantiation is the kernel without any of it.
+template <bool RAG>
+__global__ __launch_bounds__(256) void pwg_layer_kernel(const LayerArgs a, const LayerRag g) {
   extern __shared__ __attribute__((aligned(16))) float lds[];   // PW_IMG floats
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, lh = lane >> 5;
   {
@@ -101,12 +112,31 @@ __global__ __launch_bounds__(256) void pwg_layer_kernel(const LayerArgs a) {
   const float* b2 = b1 + PW_G;
   const float* __restrict__ auxw = a.auxw;
   const int L = a.L, dil = a.dil;
+  // RAG: the row of the last tile, its tiles [rlo, rhi) and its samples rL — the bound where the padded form has L (which it names itself
+  // below: it compiles to the kernel it was before RAG existed)
+  int rb = 0, rlo = 0, rhi = 0, rL = 0;
+  if (RAG) {
+    rhi = __builtin_amdgcn_readfirstlane(g.pre[1]);
+    rL = __builtin_amdgcn_readfirstlane(g.lens[0]) * g.hop;
+  }
 
   // no barrier below: every wave walks its own 64 samples of every tile of this workgroup
   for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
-    const int b = tile / a.tiles_per_row;
-    const int t0 = (tile - b * a.tiles_per_row) * PW_TILE + wave * PW_WCOLS;
-    if (t0 >= L) continue;
+    int b, t0;
+    if (RAG) {
+      while (tile >= rhi) {            // tile < ntiles = pre[B]: ends at a row b < B
+        ++rb;
+        rlo = rhi;
+        rhi = __builtin_amdgcn_readfirstlane(g.pre[rb + 1]);
+        rL = __builtin_amdgcn_readfirstlane(g.lens[rb]) * g.hop;
+      }
+      b = rb;
+      t0 = (tile - rlo) * PW_TILE + wave * PW_WCOLS;
+    } else {
+      b = tile / a.tiles_per_row;
+      t0 = (tile - b * a.tiles_per_row) * PW_TILE + wave * PW_WCOLS;
+    }
+    if (t0 >= (RAG ? rL : L)) continue;
     const float* __restrict__ xin = a.xin + (long long)b * PW_R * L;
     const float* __restrict__ cc = a.c + (long long)b * PW_A * L;
     float* __restrict__ xout = a.xout + (long long)b * PW_R * L;
@@ -127,14 +157,14 @@ __global__ __launch_bounds__(256) void pwg_layer_kernel(const LayerArgs a) {
         [&](int s, int j) {
           const int tap = s >> 5, ci = 2 * (s & 31) + lh;
           const int t = t0 + 32 * j + l31 + (tap - 1) * dil;
-          return (t >= 0 && t < L) ? xin[(long long)ci * L + t] : 0.f;
+          return (t >= 0 && t < (RAG ? rL : L)) ? xin[(long long)ci * L + t] : 0.f;
         });
     // the aux term: k = ch = 2 s + lh
     steps_product<PW_SA>(
         acc, [&](int s, int m) { return auxw[(s * 4 + m) * 64 + lane]; },
         [&](int s, int j) {
           const int t = t0 + 32 * j + l31;
-          return t < L ? cc[(long long)(2 * s + lh) * L + t] : 0.f;
+          return t < (RAG ? rL : L) ? cc[(long long)(2 * s + lh) * L + t] : 0.f;
         });
 
     // the gate: tanh first (residual_block.py:121)
@@ -172,7 +202,7 @@ __global__ __launch_bounds__(256) void pwg_layer_kernel(const LayerArgs a) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int t = t0 + 32 * j + l31;
-      if (t < L) {
+      if (t < (RAG ? rL : L)) {
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -188,12 +218,15 @@ __global__ __launch_bounds__(256) void pwg_layer_kernel(const LayerArgs a) {
 }
 
 // c'[b][o][f] = bc[o] + sum_i Wc[o][i] c[b][i][f] + sum_i Wc[o][80 + i] E[pitch[b][f]][i]   (parallel_wavegan.py:150-151)
+// RAG: Tp is the unpadded T (the front is per frame: edge-padding its output is its output on the edge-padded input), frames f < lens[b]
+template <bool RAG>
 __global__ void pwg_pitch_front_kernel(const float* __restrict__ c, const long long* __restrict__ pitch, const float* __restrict__ emb,
                                        const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ out, int B, int Tp,
-                                       int n_emb) {
+                                       int n_emb, const int* __restrict__ lens) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (long long)B * PW_A * Tp) return;
   const int f = (int)(idx % Tp), o = (int)((idx / Tp) % PW_A), b = (int)(idx / ((long long)Tp * PW_A));
+  if (RAG && f >= lens[b]) return;
   long long p = pitch[(long long)b * Tp + f];
   p = p < 0 ? 0 : (p >= n_emb ? n_emb - 1 : p);      // torch raises on an index outside the table; nothing outside it is read here
   const float* __restrict__ cb = c + (long long)b * PW_A * Tp + f;
@@ -206,51 +239,74 @@ __global__ void pwg_pitch_front_kernel(const float* __restrict__ c, const long l
 }
 
 // conv_in: out[b][o][f] = sum_i sum_k W[o][i][k] c[b][i][f + k], f < T (no padding: the caller padded by the window, upsample.py:157)
-__global__ void pwg_conv_in_kernel(const float* __restrict__ c, const float* __restrict__ w, float* __restrict__ out, int B, int T, int K) {
+// RAG: c is [B][80][T], unpadded; frame f + k of the row's own edge padding is frame clamp(f + k - w, 0, lens[b] - 1), f < lens[b]; the
+// same fmaf order
+template <bool RAG>
+__global__ void pwg_conv_in_kernel(const float* __restrict__ c, const float* __restrict__ w, float* __restrict__ out, int B, int T, int K,
+                                   const int* __restrict__ lens) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (long long)B * PW_A * T) return;
   const int f = (int)(idx % T), o = (int)((idx / T) % PW_A), b = (int)(idx / ((long long)T * PW_A));
-  const int Tp = T + K - 1;
-  const float* __restrict__ cb = c + (long long)b * PW_A * Tp + f;
   const float* __restrict__ wr = w + (long long)o * PW_A * K;
   float s = 0.f;
-  for (int i = 0; i < PW_A; ++i)
-    for (int k = 0; k < K; ++k) s = fmaf(wr[i * K + k], cb[(long long)i * Tp + k], s);
+  if (RAG) {
+    const int n = lens[b], hw = (K - 1) / 2;
+    if (f >= n) return;
+    const float* __restrict__ cb = c + (long long)b * PW_A * T;
+    for (int i = 0; i < PW_A; ++i)
+      for (int k = 0; k < K; ++k) {
+        const int g = f + k - hw;
+        s = fmaf(wr[i * K + k], cb[(long long)i * T + (g < 0 ? 0 : (g >= n ? n - 1 : g))], s);
+      }
+  } else {
+    const int Tp = T + K - 1;
+    const float* __restrict__ cb = c + (long long)b * PW_A * Tp + f;
+    for (int i = 0; i < PW_A; ++i)
+      for (int k = 0; k < K; ++k) s = fmaf(wr[i * K + k], cb[(long long)i * Tp + k], s);
+  }
   out[idx] = s;
 }
 
 // one scale of the up-sampler (upsample.py:85-99): nearest stretch by s, then a (2 s + 1)-tap convolution with zero padding s, per row
+// RAG: batch row b ends at lens[b] mul, mul = T-to-Lout rate (the scales so far, this one included): the zero padding sits there, and
+// nothing at or beyond it is read or written; Lin and Lout stay the pitches
+template <bool RAG>
 __global__ void pwg_upsample_kernel(const float* __restrict__ in, const float* __restrict__ w, float* __restrict__ out, long long rows, int Lin,
-                                    int s) {
+                                    int s, const int* __restrict__ lens, int mul) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const int Lout = Lin * s;
   if (idx >= rows * Lout) return;
   const int t = (int)(idx % Lout);
+  const int Lb = RAG ? lens[(idx / Lout) / PW_A] * mul : Lout;
+  if (RAG && t >= Lb) return;
   const float* __restrict__ r = in + (idx / Lout) * Lin;
   float v = 0.f;
   for (int j = 0; j <= 2 * s; ++j) {
     const int q = t + j - s;
-    if (q >= 0 && q < Lout) v = fmaf(w[j], r[q / s], v);
+    if (q >= 0 && q < Lb) v = fmaf(w[j], r[q / s], v);
   }
   out[idx] = v;
 }
 
-// first_conv: x[b][ch][t] = w[ch] z[b][t] + bias[ch]
+// first_conv: x[b][ch][t] = w[ch] z[b][t] + bias[ch]      (RAG: t < lens[b] hop)
+template <bool RAG>
 __global__ void pwg_first_kernel(const float* __restrict__ z, const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ x,
-                                 int B, int L) {
+                                 int B, int L, const int* __restrict__ lens, int hop) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (long long)B * L) return;
   const int b = (int)(idx / L), t = (int)(idx % L);
+  if (RAG && t >= lens[b] * hop) return;
   const float zv = z[idx];
   float* __restrict__ xb = x + (long long)b * PW_R * L + t;
 #pragma unroll 8
   for (int ch = 0; ch < PW_R; ++ch) xb[(long long)ch * L] = fmaf(w[ch], zv, bias[ch]);
 }
 
-// the tail (parallel_wavegan.py:161-166): y = b4 + w4 . relu(b3 + W3 relu(skips sqrt(1 / layers)))
+// the tail (parallel_wavegan.py:161-166): y = b4 + w4 . relu(b3 + W3 relu(skips sqrt(1 / layers)))      (RAG: y = 0 at t >= lens[b] hop)
+template <bool RAG>
 __global__ __launch_bounds__(256) void pwg_tail_kernel(const float* __restrict__ skip, const float* __restrict__ w3, const float* __restrict__ b3,
                                                        const float* __restrict__ w4, const float* __restrict__ b4, float* __restrict__ y, int B,
-                                                       int L, float scale) {
+                                                       int L, float scale, const int* __restrict__ lens, int hop) {
   __shared__ __attribute__((aligned(16))) float sw[PW_R * PW_R + 2 * PW_R];
   for (int i = threadIdx.x; i < PW_R * PW_R; i += 256) sw[i] = w3[i];
   if (threadIdx.x < PW_R) {
@@ -261,6 +317,10 @@ __global__ __launch_bounds__(256) void pwg_tail_kernel(const float* __restrict__
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (long long)B * L) return;
   const int b = (int)(idx / L), t = (int)(idx % L);
+  if (RAG && t >= lens[b] * hop) {
+    y[idx] = 0.f;
+    return;
+  }
   const float* __restrict__ sb = skip + (long long)b * PW_R * L + t;
   float v[PW_R];
 #pragma unroll
@@ -298,11 +358,17 @@ struct bsg_pwg {
          o_cb = 0;
   float* ws = nullptr;          // the workspaces, one allocation
   size_t ws_bytes = 0;
+  int* lens = nullptr;          // ragged forwards: lens[0 .. B) frames per row | pre[0 .. B] tiles before row b, written by launches of the call itself
+  size_t lens_cap = 0;          // rows
+  int tiles = 0;                // 256-sample tiles one layer launch of the last forward walked
   std::string path;
 };
 
-// the table of that one allocation (bsg_ws.h): the forward grows it, destroy frees it, the test hook poisons it
-static std::vector<WsBuf> ws_table(bsg_pwg* h) { return {{&h->ws_bytes, (void**)&h->ws, 1, 0, WS_POISON}}; }
+// the handle's shape-sized buffers (bsg_ws.h): the workspaces, one allocation that the forward grows, destroy frees and the test hook
+// poisons; and the lengths array of the ragged forward (2 lens_cap + 1 ints, not poisoned: the call itself fills it)
+static std::vector<WsBuf> ws_table(bsg_pwg* h) {
+  return {{&h->ws_bytes, (void**)&h->ws, 1, 0, WS_POISON}, {&h->lens_cap, (void**)&h->lens, 2 * sizeof(int), sizeof(int)}};
+}
 
 static int pwg_expected_weights(const bsg_pwg_cfg* c) { return 2 + 1 + c->n_scales + 7 * c->layers + 4 + (c->use_pitch_embed ? 3 : 0); }
 
@@ -436,8 +502,10 @@ extern "C" int bsg_pwg_create(bsg_pwg** out, const bsg_pwg_cfg* cfg, const void*
   if ((e = hipMalloc((void**)&h->wdev, P.size() * sizeof(float))) != hipSuccess) return fail(e, "hipMalloc");
   if ((e = hipMemcpyAsync(h->wdev, P.data(), P.size() * sizeof(float), hipMemcpyHostToDevice, st)) != hipSuccess) return fail(e, "hipMemcpyAsync");
   if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(e, "hipStreamSynchronize");
-  if ((e = hipFuncSetAttribute((const void*)pwg_layer_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PW_IMG * (int)sizeof(float))) !=
-      hipSuccess)
+  if ((e = hipFuncSetAttribute((const void*)pwg_layer_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               PW_IMG * (int)sizeof(float))) != hipSuccess ||
+      (e = hipFuncSetAttribute((const void*)pwg_layer_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               PW_IMG * (int)sizeof(float))) != hipSuccess)
     return fail(e, "hipFuncSetAttribute");
   int dev = 0;
   hipDeviceProp_t prop;
@@ -447,33 +515,61 @@ extern "C" int bsg_pwg_create(bsg_pwg** out, const bsg_pwg_cfg* cfg, const void*
   return BSG_OK;
 }
 
+// test hook: NaN bytes into the workspaces (the lengths array is the call's own and stays)
 extern "C" int bsg_pwg_debug_poison_workspace(bsg_pwg* h, void* stream) {
   BSG_REQUIRE(h, "pwg_debug_poison_workspace: null handle");
   return ws_poison(ws_table(h), (hipStream_t)stream);
 }
 
-extern "C" int bsg_pwg_forward(bsg_pwg* h, const float* z, const float* c, const int64_t* pitch, float* y, int32_t B, int32_t T, uint64_t seed,
-                               void* stream) {
-  BSG_REQUIRE(B >= 1 && T >= 1, "pwg_forward: B=%d, T=%d: both must be >= 1", B, T);
-  BSG_REQUIRE(h && c && y, "pwg_forward: null argument");
+extern "C" int bsg_pwg_last_tiles(bsg_pwg* h) { return h ? h->tiles : 0; }
+
+#define TRY(expr)                  \
+  do {                             \
+    int _rc = (expr);              \
+    if (_rc != BSG_OK) return _rc; \
+  } while (0)
+
+// The forward, padded (RAG = false: c [B][80][T + 2 w], lengths_host null) or ragged (c = mel [B][80][T]): the same launches in the same
+// order over the same workspaces, each bounding row b by its own length; only the layer launch has another grid (the live tiles).
+template <bool RAG>
+static int pwg_forward_any(bsg_pwg* h, const float* z, const float* c, const int64_t* pitch, const int32_t* lengths_host, float* y, int32_t B,
+                           int32_t T, uint64_t seed, void* stream, const char* who) {
+  if (RAG) TRY(lens_check(lengths_host, B, T, who));      // first: refused before anything is grown, enqueued or written
+  BSG_REQUIRE(B >= 1 && T >= 1, "%s: B=%d, T=%d: both must be >= 1", who, B, T);
+  BSG_REQUIRE(h && c && y, "%s: null argument", who);
   const bsg_pwg_cfg& cf = h->cfg;
-  BSG_REQUIRE(!cf.use_pitch_embed || pitch, "pwg_forward: this generator has the pitch front (use_pitch_embed): pitch is required");
-  BSG_REQUIRE(cf.use_pitch_embed || !pitch, "pwg_forward: pitch given but this generator was built without use_pitch_embed");
-  const long long L = (long long)T * h->hop;
-  BSG_REQUIRE((long long)B * L * PW_A < (1ll << 40) && L < (1ll << 30), "pwg_forward: B=%d rows of %lld samples are more than one call carries", B, L);
-  BSG_REQUIRE(z || (B * L) % 4 == 0, "pwg_forward: B * T * hop = %lld is no multiple of 4: supply z (the Philox stream is drawn four at a time)",
+  BSG_REQUIRE(!cf.use_pitch_embed || pitch, "%s: this generator has the pitch front (use_pitch_embed): pitch is required", who);
+  BSG_REQUIRE(cf.use_pitch_embed || !pitch, "%s: pitch given but this generator was built without use_pitch_embed", who);
+  const int hop = h->hop;
+  const long long L = (long long)T * hop;
+  BSG_REQUIRE((long long)B * L * PW_A < (1ll << 40) && L < (1ll << 30), "%s: B=%d rows of %lld samples are more than one call carries", who, B, L);
+  BSG_REQUIRE(z || (B * L) % 4 == 0, "%s: B * T * hop = %lld is no multiple of 4: supply z (the Philox stream is drawn four at a time)", who,
               B * L);
   hipStream_t st = (hipStream_t)stream;
   const int w = cf.aux_context_window, Tp = T + 2 * w;
   // the workspaces: c' [B][80][Tp] | c2 [B][80][T] | cfull [B][80][L] | ctmp [B][80][L / s_last] | x0, x1, skip [B][64][L] | z [B][L]
+  // (ragged: the same sizes; c' is [B][80][T] at the front of its part)
   const int s_last = cf.upsample_scales[cf.n_scales - 1];
   auto al = [](size_t n) { return (n + 63) & ~(size_t)63; };
   const size_t n_cp = al((size_t)B * PW_A * Tp), n_c2 = al((size_t)B * PW_A * T), n_cf = al((size_t)B * PW_A * L),
                n_ct = al((size_t)B * PW_A * (L / s_last)), n_x = al((size_t)B * PW_R * L), n_z = al((size_t)B * L);
   const size_t need = (n_cp + n_c2 + n_cf + n_ct + 3 * n_x + n_z) * sizeof(float);
-  if (need > h->ws_bytes) {
-    const int rc = ws_grow(ws_table(h), "pwg", &h->ws_bytes, need, st);
-    if (rc != BSG_OK) return rc;
+  if (need > h->ws_bytes) TRY(ws_grow(ws_table(h), "pwg", &h->ws_bytes, need, st));
+  const int tiles_per_row = cdiv(L, PW_TILE);
+  int ntiles = B * tiles_per_row;
+  const int* lens = nullptr;
+  const int* pre = nullptr;
+  if (RAG) {
+    // the counts and the prefix table of the rows' tile counts travel in kernel arguments (lens_fill): a captured forward replays them
+    if ((size_t)B > h->lens_cap) TRY(ws_grow(ws_table(h), "pwg", &h->lens_cap, (size_t)B, st));
+    std::vector<int32_t> pre_host((size_t)B + 1);
+    pre_host[0] = 0;
+    for (int b = 0; b < B; ++b) pre_host[b + 1] = pre_host[b] + cdiv((long long)lengths_host[b] * hop, PW_TILE);
+    ntiles = pre_host[B];
+    TRY(lens_fill(h->lens, lengths_host, B, st));
+    TRY(lens_fill(h->lens + B, pre_host.data(), B + 1, st));
+    lens = h->lens;
+    pre = h->lens + B;
   }
   float* cp = h->ws;
   float* c2 = cp + n_cp;
@@ -485,44 +581,50 @@ extern "C" int bsg_pwg_forward(bsg_pwg* h, const float* z, const float* c, const
   float* zbuf = skip + n_x;
   const float* Wd = h->wdev;
   h->path.clear();
+  h->tiles = 0;
   auto tok = [&](const std::string& s) { if (!h->path.empty()) h->path += ' '; h->path += s; };
+  if (RAG) tok("ragged");
 
   const float* cin = c;
   if (cf.use_pitch_embed) {
-    hipLaunchKernelGGL(pwg_pitch_front_kernel, dim3(cdiv((long long)B * PW_A * Tp, 256)), dim3(256), 0, st, c, (const long long*)pitch, Wd + h->o_emb,
-                       Wd + h->o_cw, Wd + h->o_cb, cp, B, Tp, cf.n_pitch);
+    const int Tf = RAG ? T : Tp;      // ragged: the front runs on the unpadded frames
+    hipLaunchKernelGGL(pwg_pitch_front_kernel<RAG>, dim3(cdiv((long long)B * PW_A * Tf, 256)), dim3(256), 0, st, c, (const long long*)pitch,
+                       Wd + h->o_emb, Wd + h->o_cw, Wd + h->o_cb, cp, B, Tf, cf.n_pitch, lens);
     BSG_LAUNCH_CHECK();
     tok("pitch");
     cin = cp;
   }
-  hipLaunchKernelGGL(pwg_conv_in_kernel, dim3(cdiv((long long)B * PW_A * T, 256)), dim3(256), 0, st, cin, Wd + h->o_cin, c2, B, T, 2 * w + 1);
+  hipLaunchKernelGGL(pwg_conv_in_kernel<RAG>, dim3(cdiv((long long)B * PW_A * T, 256)), dim3(256), 0, st, cin, Wd + h->o_cin, c2, B, T, 2 * w + 1,
+                     lens);
   BSG_LAUNCH_CHECK();
   tok("conv_in");
   const float* uin = c2;
-  int Lin = T;
+  int Lin = T, mul = 1;
   for (int i = 0; i < cf.n_scales; ++i) {
     float* uout = ((cf.n_scales - 1 - i) & 1) ? ctmp : cfull;
     const int s = cf.upsample_scales[i];
-    hipLaunchKernelGGL(pwg_upsample_kernel, dim3(cdiv((long long)B * PW_A * Lin * s, 256)), dim3(256), 0, st, uin, Wd + h->o_up[i], uout,
-                       (long long)B * PW_A, Lin, s);
+    mul *= s;
+    hipLaunchKernelGGL(pwg_upsample_kernel<RAG>, dim3(cdiv((long long)B * PW_A * Lin * s, 256)), dim3(256), 0, st, uin, Wd + h->o_up[i], uout,
+                       (long long)B * PW_A, Lin, s, lens, mul);
     BSG_LAUNCH_CHECK();
     tok("up" + std::to_string(i) + ":x" + std::to_string(s));
     uin = uout;
     Lin *= s;
   }
   if (!z) {
-    const int rc = bsg_philox_normal(zbuf, (long long)B * L, seed, PW_PHILOX_STREAM, 0, stream);
-    if (rc != BSG_OK) return rc;
+    TRY(bsg_philox_normal(zbuf, (long long)B * L, seed, PW_PHILOX_STREAM, 0, stream));
     tok("philox");
     z = zbuf;
   }
-  hipLaunchKernelGGL(pwg_first_kernel, dim3(cdiv((long long)B * L, 256)), dim3(256), 0, st, z, Wd + h->o_first_w, Wd + h->o_first_b, x0, B, (int)L);
+  hipLaunchKernelGGL(pwg_first_kernel<RAG>, dim3(cdiv((long long)B * L, 256)), dim3(256), 0, st, z, Wd + h->o_first_w, Wd + h->o_first_b, x0, B,
+                     (int)L, lens, hop);
   BSG_LAUNCH_CHECK();
   tok("first");
   LayerArgs a{};
   a.c = cfull; a.skip = skip; a.L = (int)L;
-  a.tiles_per_row = cdiv(L, PW_TILE);
-  a.ntiles = B * a.tiles_per_row;
+  a.tiles_per_row = tiles_per_row;
+  a.ntiles = ntiles;
+  const LayerRag rag{lens, pre, hop};
   const int grid = a.ntiles < h->cus ? a.ntiles : h->cus;
   float* xa = x0;
   float* xb = x1;
@@ -530,14 +632,28 @@ extern "C" int bsg_pwg_forward(bsg_pwg* h, const float* z, const float* c, const
     a.xin = xa; a.xout = xb; a.dil = h->dil[l]; a.first = l == 0; a.last = l == cf.layers - 1;
     a.img = Wd + h->o_img + (size_t)l * PW_IMG;
     a.auxw = Wd + h->o_aux + (size_t)l * PW_AUXW;
-    hipLaunchKernelGGL(pwg_layer_kernel, dim3(grid), dim3(256), PW_IMG * sizeof(float), st, a);
+    hipLaunchKernelGGL(pwg_layer_kernel<RAG>, dim3(grid), dim3(256), PW_IMG * sizeof(float), st, a, rag);
     BSG_LAUNCH_CHECK();
     tok("layer" + std::to_string(l) + ":f32/d" + std::to_string(a.dil));
     float* t = xa; xa = xb; xb = t;
   }
-  hipLaunchKernelGGL(pwg_tail_kernel, dim3(cdiv((long long)B * L, 256)), dim3(256), 0, st, skip, Wd + h->o_w3, Wd + h->o_b3, Wd + h->o_w4,
-                     Wd + h->o_b4, y, B, (int)L, (float)sqrt(1.0 / cf.layers));
+  hipLaunchKernelGGL(pwg_tail_kernel<RAG>, dim3(cdiv((long long)B * L, 256)), dim3(256), 0, st, skip, Wd + h->o_w3, Wd + h->o_b3, Wd + h->o_w4,
+                     Wd + h->o_b4, y, B, (int)L, (float)sqrt(1.0 / cf.layers), lens, hop);
   BSG_LAUNCH_CHECK();
   tok("tail");
+  h->tiles = ntiles;
   return BSG_OK;
 }
+
+extern "C" int bsg_pwg_forward(bsg_pwg* h, const float* z, const float* c, const int64_t* pitch, float* y, int32_t B, int32_t T, uint64_t seed,
+                               void* stream) {
+  return pwg_forward_any<false>(h, z, c, pitch, nullptr, y, B, T, seed, stream, "pwg_forward");
+}
+
+// Ragged batches: row b is the generator on its own n_b = lengths_host[b] frames (1 .. T) inside the (B, T) tensors, edge-padded at ITS
+// end by the library, bit for bit the B = 1, T = n_b call; the layer launches walk the live tiles only (include/bisinger_hip.h).
+extern "C" int bsg_pwg_forward_ragged(bsg_pwg* h, const float* z, const float* mel, const int64_t* pitch, const int32_t* lengths_host, float* y,
+                                      int32_t B, int32_t T, uint64_t seed, void* stream) {
+  return pwg_forward_any<true>(h, z, mel, pitch, lengths_host, y, B, T, seed, stream, "pwg_forward_ragged");
+}
+

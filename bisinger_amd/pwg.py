@@ -8,7 +8,7 @@ loads too.  What the kernels are built for (bsg_pwg_create refuses the rest with
 = 64, gate = 128, aux = 80 channels, ``ConvInUpsampleNetwork`` with the nearest stretch.  The discriminator and the losses are
 training-only and out of scope.
 """
-from ctypes import POINTER, byref, c_void_p, cast
+from ctypes import POINTER, byref, c_int32, c_void_p, cast
 
 import numpy as np
 import torch
@@ -210,6 +210,53 @@ class ParallelWaveGANGenerator(nn.Module, _lib.HandleOwner):
     def last_path(self):
         """The launches of the last forward in launch order (include/bisinger_hip.h, bsg_pwg_last_path); 'none' before the first."""
         return _lib.load().bsg_pwg_last_path(self._h).decode() if self._h is not None else 'none'
+
+    def last_tiles(self):
+        """The 256-sample tiles one residual-layer launch of the last forward walked (bsg_pwg_last_tiles): B ceil(T hop / 256) after
+        ``forward``, the sum of ceil(lengths[b] hop / 256) after ``forward_ragged``; 0 before the first."""
+        return int(_lib.load().bsg_pwg_last_tiles(self._h)) if self._h is not None else 0
+
+    @torch.no_grad()
+    def forward_ragged(self, x, mel, pitch=None, *, lengths, seed=None):
+        """A ragged batch: x [B,1,T*hop] noise (None: drawn on the device from the Philox stream of ``seed``), mel [B,80,T] UNPADDED,
+        pitch [B,T] int64 with use_pitch_embed, ``lengths`` a list or tensor of B ints in 1 .. T -> [B,1,T*hop].
+
+        Row b is the generator applied to that utterance alone, as vocoders/pwg.py:84-105 runs it: ``y[b, 0, :lengths[b]*hop]`` equals,
+        bit for bit, ``forward(x[b:b+1, :, :lengths[b]*hop], edge_pad(mel[b:b+1, :, :lengths[b]], w), edge_pad(pitch[b:b+1, :lengths[b]], w))``;
+        the rest of the row is 0, and nothing at or beyond a row's end is read.  A separate method, not a keyword of ``forward``: there
+        ``c`` is the mel the caller already edge-padded, here the library pads each row at its own end.  With ``x=None`` the draws keep
+        the index of the padded call at (B, T), element b*T*hop + t: a batched row with drawn noise is reproducible from the seed but
+        is not the waveform of the lone call with that seed."""
+        B, A, T = (int(v) for v in mel.shape)
+        # checked before the handle is built and before the output exists: without a GPU the refusal is the length's
+        lengths = [int(v) for v in (lengths.tolist() if hasattr(lengths, 'tolist') else lengths)]
+        if len(lengths) != B:
+            raise _lib.BsgError(f'ParallelWaveGANGenerator.forward_ragged: lengths has {len(lengths)} entries for a batch of {B} rows')
+        for b, n in enumerate(lengths):
+            if not 1 <= n <= T:
+                raise _lib.BsgError(f'ParallelWaveGANGenerator.forward_ragged: lengths[{b}]={n} outside 1..T={T}')
+        hd = self.handle()
+        dev = self.first_conv.weight.device
+        mel = mel.to(dev, torch.float32).contiguous()
+        assert A == self.aux_channels, (tuple(mel.shape), self.aux_channels)
+        L = T * self.hop_size
+        if x is not None:
+            x = x.to(dev, torch.float32).contiguous()
+            assert tuple(x.shape) == (B, 1, L), (tuple(x.shape), (B, 1, L))
+        elif seed is None:
+            raise _lib.BsgError('ParallelWaveGANGenerator.forward_ragged: x=None needs seed= (the noise is drawn on the device)')
+        if self.use_pitch_embed:
+            if pitch is None:
+                raise _lib.BsgError('this generator has the pitch front (use_pitch_embed): pitch is required')
+            pitch = pitch.to(dev, torch.int64).contiguous()
+            assert tuple(pitch.shape) == (B, T), (tuple(pitch.shape), (B, T))
+        elif pitch is not None:
+            raise _lib.BsgError('pitch given but this generator was built without use_pitch_embed')
+        y = torch.empty(B, 1, L, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().bsg_pwg_forward_ragged(hd, _lib.ptr(x), _lib.ptr(mel), _lib.ptr(pitch), (c_int32 * B)(*lengths), _lib.ptr(y),
+                                                          B, T, int(seed or 0), _lib.stream_ptr()), 'bsg_pwg_forward_ragged')
+        return y
 
     @torch.no_grad()
     def forward(self, x, c=None, pitch=None, seed=None, **kwargs):

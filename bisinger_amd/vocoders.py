@@ -275,6 +275,43 @@ class PWG(BaseVocoder):
             y = self.model(z, c, p, seed=int(hparams.get('seed', 1234) if seed is None else seed)).view(-1)
         return y.cpu().numpy()
 
+    def spec2wav_batch(self, mels, f0s=None, zs=None, seed=None):
+        """Many utterances in ONE ragged forward: mels a list of [T_i,80] (, f0s a list of [T_i], zs a list of [T_i*hop]) -> a list of
+        wav [T_i*hop] in the order given.  Per item: the scaler transform and ``f0_to_coarse``, as ``spec2wav`` does them; then the items
+        are padded to the longest, run through ``forward_ragged`` (which edge-pads every item at its own end) and trimmed.  With ``zs``
+        item i equals ``spec2wav(mels[i], f0=f0s[i], z=zs[i])`` bit for bit.  Without, the noise is drawn on the device from the Philox
+        stream of ``seed`` (default hparams['seed']) at the index of the padded batch: reproducible, but item i is then NOT the waveform
+        ``spec2wav(mels[i], seed=seed)`` draws."""
+        hop = self.config['hop_size']
+        cs = [np.asarray(m) for m in mels]
+        if self.scaler is not None:
+            cs = [self.scaler.transform(c) for c in cs]
+        B = len(cs)
+        assert B >= 1, 'spec2wav_batch: no items'
+        lengths = [int(c.shape[0]) for c in cs]
+        T = max(lengths)
+        for name, seq in (('f0s', f0s), ('zs', zs)):
+            assert seq is None or len(seq) == B, f'spec2wav_batch: {len(seq)} {name} for {B} mels'
+        mel = np.zeros((B, cs[0].shape[1], T), dtype=np.float32)
+        for b, c in enumerate(cs):
+            mel[b, :, :lengths[b]] = np.asarray(c, dtype=np.float32).T
+        pitch = z = None
+        if f0s is not None:
+            pitch = np.zeros((B, T), dtype=np.int64)
+            for b, f0 in enumerate(f0s):
+                pitch[b, :lengths[b]] = f0_to_coarse(np.asarray(f0))
+            pitch = torch.from_numpy(pitch).to(self.device)
+        if zs is not None:
+            z = np.zeros((B, 1, T * hop), dtype=np.float32)
+            for b, zi in enumerate(zs):
+                z[b, 0, :lengths[b] * hop] = np.asarray(zi, dtype=np.float32).reshape(lengths[b] * hop)
+            z = torch.from_numpy(z).to(self.device)
+        with torch.no_grad():
+            y = self.model.forward_ragged(z, torch.from_numpy(mel).to(self.device), pitch, lengths=lengths,
+                                          seed=int(hparams.get('seed', 1234) if seed is None else seed))
+        y = y.cpu().numpy()
+        return [y[b, 0, :lengths[b] * hop].copy() for b in range(B)]
+
     @staticmethod
     def wav2mfcc(wav_fn):
         raise NotImplementedError('analysis (wav -> mfcc) is data preparation, outside the hot path')

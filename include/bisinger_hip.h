@@ -659,6 +659,34 @@ int bsg_pwg_forward(bsg_pwg* h, const float* z, const float* c, const int64_t* p
 const char* bsg_pwg_last_path(bsg_pwg* h);
 int bsg_pwg_debug_poison_workspace(bsg_pwg* h, void* stream);
 
+/* Additions to v20 (no version bump, as bsg_pwg_n_weights was added beyond v13): ragged batches through the PWG generator — every row as
+ * the generator applied to that utterance alone, worded after bsg_hifigan_forward_ragged / bsg_pitchext_forward_ragged.
+ *   bsg_pwg_forward_ragged  mel [B][80][T] is UNPADDED: the library edge-pads each row at its own end.  pitch [B][T] int64 (required with
+ *                    use_pitch_embed, NULL without), z and y [B][1][T hop].  lengths_host: B frame counts on the HOST, each in 1 .. T, read
+ *                    before the call returns: they travel in kernel arguments into a handle-owned device array, so a captured forward
+ *                    replays them and the host array is dead on return.  With n_b = lengths_host[b], L_b = n_b hop:
+ *                      y[b,0,:L_b] is, BIT FOR BIT, what bsg_pwg_forward returns at B = 1, T = n_b for c = edge-pad(mel[b,:,:n_b], w),
+ *                      pitch = edge-pad(pitch[b,:n_b], w) and z[b,0,:L_b]; it depends on row b alone.  y[b,0,L_b:] is written as 0.
+ *                      Nothing at or beyond a row's end is read: mel and z may hold NaN there, pitch any integer, and what an earlier
+ *                      call left in the workspaces is not read.  All lengths = T: the padded call's result on the edge-padded input, bit
+ *                      for bit.
+ *                    z == NULL: the Philox draws keep the PADDED call's index — element b T hop + t, stream 0x505747, key `seed` — so a
+ *                    row sees the draws it sees in the padded call at (B, T) (as the NSF noise and the sampler do); a batched row with
+ *                    drawn noise is therefore NOT the lone call's waveform.
+ *                    BSG_EINVAL before anything is enqueued or written: lengths_host NULL ("lengths_host is null"), a length outside
+ *                    1 .. T ("lengths[b]=.. outside 1..T=..", naming the row) — the lengths are looked at first, before the handle — and
+ *                    what bsg_pwg_forward refuses.  Workspaces grow as for the padded call at (B, T) (the lengths array with B); otherwise
+ *                    the call only enqueues and is capturable.  The launches are the padded call's, each bounding row b by its own
+ *                    length (the pitch front runs over T frames, not T + 2 w); the residual-layer launches walk the LIVE 256-sample
+ *                    tiles only, sum_b ceil(L_b / 256) of them, through a prefix table of the rows' tile counts beside the lengths.
+ *                    bsg_pwg_last_path: the token `ragged`, then the padded call's tokens.  bsg_pwg_debug_poison_workspace leaves the
+ *                    lengths array alone.
+ *   bsg_pwg_last_tiles  the 256-sample tiles one residual-layer launch of the handle's last forward walked: B ceil(T hop / 256) after a
+ *                    padded forward, sum_b ceil(L_b / 256) after a ragged one; 0 before the first forward or for a null handle. */
+int bsg_pwg_forward_ragged(bsg_pwg* h, const float* z, const float* mel, const int64_t* pitch, const int32_t* lengths_host, float* y, int32_t B,
+                           int32_t T, uint64_t seed, void* stream);
+int bsg_pwg_last_tiles(bsg_pwg* h);
+
 /* w[d0,...] = g[d0] * v[d0,...] / ||v[d0,...]||   (remove_weight_norm, hifigan.py:175-182) */
 int bsg_weight_norm_fold(const float* g, const float* v, float* w, int32_t dim0, int32_t inner, void* stream);
 
