@@ -222,7 +222,8 @@ class DiffSingerE2EInfer(BaseSVSInfer):
         mel_out = output['mel_out']
         # a-*.py:629-632: the pitch extractor's f0, else the model's own (use_pitch_embed: FastSpeech2.add_pitch returns f0_denorm)
         f0_pred = self.pe(mel_out)['f0_denorm_pred'] if hparams.get('pe_enable') else output.get('f0_denorm')
-        wav_out = self.run_vocoder(mel_out, f0=f0_pred)
+        # a given seed keys the NSF source's draws too, as in forward_batch (None: hparams['seed'] for both)
+        wav_out = self.run_vocoder(mel_out, f0=f0_pred, **({} if seed is None else {'seed': seed}))
         return wav_out.cpu().numpy()[0]
 
     def estimate_frames(self, item):

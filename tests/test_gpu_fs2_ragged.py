@@ -402,6 +402,7 @@ def test_gaussian_diffusion_ragged_front_rows_equal_its_own_lone_calls(adaptor):
 
 
 def test_forward_batch_every_ragged_switch(nsf_workdir):  # noqa: F811
+    # (shapes and path tokens only; the values of this call, stage by stage against float64 on the utterance alone: tests/test_gpu_e2e_ragged.py)
     from bisinger_amd.hparams import hparams, set_hparams
     from bisinger_amd.infer import DiffSingerE2EInfer
     set_hparams('exp2.yaml', exp_name='exp_diff_e2e', print_hparams=False, hparams_str='seed=99')

@@ -172,7 +172,8 @@ def test_refusals(model):
 
 
 def test_end_to_end_forward_ragged(model):
-    """GaussianDiffusion.forward(ragged=True): lengths from mel2ph, mel_out 0 beyond each row's frames, everything finite."""
+    """GaussianDiffusion.forward(ragged=True): lengths from mel2ph, mel_out 0 beyond each row's frames, everything finite.
+    (The values of mel_out, row by row against float64 with the row's own Philox draws: tests/test_gpu_e2e_ragged.py.)"""
     B, T_txt, T = 4, 12, 300
     inp = synth.synth_inputs(B, T_txt, T, seed=2, ragged=True)
     d = {k: torch.from_numpy(v).cuda() for k, v in inp.items()}
@@ -195,6 +196,7 @@ from tests.test_gpu_infer import _item, workdir  # noqa: E402,F401  (the synthet
 
 
 def test_forward_batch_ragged(workdir):
+    # (shapes and launch groups only; the values, every row against float64 on the utterance alone: tests/test_gpu_e2e_ragged.py)
     from bisinger_amd.hparams import set_hparams, hparams
     from bisinger_amd.infer import DiffSingerE2EInfer
     set_hparams('exp.yaml', exp_name='exp_diff_e2e', print_hparams=False, hparams_str='seed=4321')

@@ -236,6 +236,7 @@ from tests.test_gpu_infer import _item, workdir  # noqa: E402,F401  (the synthet
 
 
 def test_forward_batch_ragged(workdir):
+    # (shapes and launch groups only; the values of the fp32 configuration's ragged forward_batch: tests/test_gpu_e2e_ragged.py)
     from bisinger_amd.hparams import set_hparams, hparams
     from bisinger_amd.infer import DiffSingerE2EInfer
     set_hparams('exp.yaml', exp_name='exp_diff_e2e', print_hparams=False, hparams_str='seed=4321')
