@@ -283,12 +283,84 @@ def gemm_range_peek(device=None):
 
 
 class HandleOwner:
-    """Mixin of every module that owns a library handle: the handle is re-created when a parameter or buffer was moved, replaced or
-    modified (load_ckpt, .to(), an in-place edit) — told from (data_ptr, _version) of every state_dict entry.  Walking the module tree for
-    that (state_dict()) costs 250-300 us per look, and a pass looks several times: ~1 ms of host time per pass, most of the gaps between
-    the front's kernels (tools/_front.sh).  The SLOTS — (dict of the owning module, name) of every parameter and persistent buffer — are
-    found once (the module tree of these drop-ins is fixed after construction); a look reads each slot's current tensor: a replaced
-    tensor (a buffer after .to(), an assigned Parameter) is seen like a modified one.  50 us."""
+    """Mixin of every module that owns a library handle, and the handle's whole life cycle: handle(), release(), __del__, last_path(),
+    poison_workspace().  A class names its entries (DESTROY, LAST_PATH, POISON: symbols, None where the library has none) and writes
+    _create(ws, arr): its config struct, its tables and its create call.  _before_weights() holds a refusal that comes before the weight
+    check, _created() what a new handle needs switched.
+
+    The handle is re-created when a parameter or buffer was moved, replaced or modified (load_ckpt, .to(), an in-place edit) — told from
+    (data_ptr, _version) of every state_dict entry.  Walking the module tree for that (state_dict()) costs 250-300 us per look, and a
+    pass looks several times: ~1 ms of host time per pass, most of the gaps between the front's kernels (tools/_front.sh).  The SLOTS —
+    (dict of the owning module, name) of every parameter and persistent buffer — are found once (the module tree of these drop-ins is
+    fixed after construction); a look reads each slot's current tensor: a replaced tensor (a buffer after .to(), an assigned Parameter)
+    is seen like a modified one.  50 us.  So the cached path of handle() is one _key() look and a tuple compare, and nothing else: no
+    state_dict(), no module walk, no load()."""
+    DESTROY = LAST_PATH = POISON = None
+    _h = None
+    _h_key = None
+
+    def handle(self):
+        """The library handle, (re)created when the parameters moved or changed (load_ckpt, .to())."""
+        key = self._key()
+        if self._h is not None and key == self._h_key:
+            return self._h
+        import torch
+        self.release()
+        self._before_weights()
+        ws = [p.detach() for p in self._weights()]
+        # before the library is loaded and before anything is allocated.  The library reads every floating tensor as float32 (.half() and
+        # .double() are the ways to get this wrong); an integer buffer — BatchNorm's num_batches_tracked in PitchExtractor — holds its
+        # place in the pointer array and is not read
+        for p in ws:
+            if not p.is_cuda or not p.is_contiguous() or (p.is_floating_point() and p.dtype != torch.float32):
+                raise BsgError(f'{type(self).__name__} parameters must be contiguous float32 on the GPU (model.cuda()); there is no CPU path')
+        arr = ctypes.cast((c_void_p * len(ws))(*[p.data_ptr() for p in ws]), POINTER(c_void_p))
+        with torch.cuda.device(ws[0].device):
+            h = self._create(ws, arr)
+        self._h, self._h_key = h, key
+        self._created()
+        if isinstance(self, GemmGuarded):
+            self._apply_guard_state()
+        return h
+
+    def _before_weights(self):
+        pass
+
+    def _create(self, ws, arr):
+        """-> the new handle (c_void_p) over the weights `ws` (`arr`: their device pointers in that order); the weights' device is current."""
+        raise NotImplementedError
+
+    def _created(self):
+        pass
+
+    def release(self):
+        if self._h is not None:
+            getattr(load(), self.DESTROY)(self._h)
+        self._h = self._h_key = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+    def last_path(self):
+        """The launch forms of the last call as the library recorded them (the owning class lists the tokens); 'none' without a handle."""
+        return getattr(load(), self.LAST_PATH)(self._h).decode() if self._h is not None else 'none'
+
+    def poison_workspace(self):
+        """Test hook (the class's *_debug_poison_workspace entry): NaN bytes over the handle's workspaces, on the handle's device.  Nothing
+        without a handle."""
+        if self._h is None:
+            return
+        if self.POISON is None:
+            raise BsgError(f'{type(self).__name__}: the library has no poison entry for this handle')
+        with on_device(self):
+            check(getattr(load(), self.POISON)(self._h, stream_ptr()), self.POISON)
+
+    def forget_slots(self):
+        """The parameters changed NAMES (weight norm folded: weight_g / weight_v -> weight): the next look finds the slots again."""
+        self.__dict__.pop('_handle_slots', None)
 
     def _slots(self):
         slots = self.__dict__.get('_handle_slots')
@@ -314,15 +386,29 @@ class HandleOwner:
                     k.append(t._version)
                 return tuple(k)
             except (KeyError, AttributeError):      # a parameter was removed or set to None (weight norm folded ...): find the slots again
-                self.__dict__.pop('_handle_slots', None)
+                self.forget_slots()
                 if attempt:
                     raise
 
 
+def row_lengths(lengths, B, who, T=None):
+    """The row lengths of a ragged batch (a list or a tensor of B ints) -> list of B Python ints; BsgError, in `who`'s name, when the count
+    is not B or (with `T`) a value lies outside 1..T.  Called before the handle is built: a refused call touches nothing."""
+    lengths = [int(v) for v in (lengths.tolist() if hasattr(lengths, 'tolist') else lengths)]
+    if len(lengths) != B:
+        raise BsgError(f'{who}: lengths has {len(lengths)} entries for a batch of {B} rows')
+    if T is not None:
+        for b, v in enumerate(lengths):
+            if not 1 <= v <= T:
+                raise BsgError(f'{who}: lengths[{b}]={v} outside 1..T={T}')
+    return lengths
+
+
 class GemmGuarded:
-    """Mixin of every module that owns a library handle (``self._h``; ``GUARD_KIND`` names its type): the range guard of the handle's
-    split-fp16 GEMMs / fused attention / ResBlock convolutions is the HANDLE's — its own device word, its own switch to the fp32 matrix
-    pipe, its own strike count (include/bisinger_hip.h bsg_handle_*).  An out-of-range input to one model demotes that model only."""
+    """Mixin of the handle owners (HandleOwner; ``GUARD_KIND`` names the handle's type) whose handle runs split-fp16 GEMMs / fused
+    attention / ResBlock convolutions: their range guard is the HANDLE's — its own device word, its own switch to the fp32 matrix
+    pipe, its own strike count (include/bisinger_hip.h bsg_handle_*).  An out-of-range input to one model demotes that model only.
+    HandleOwner.handle() calls _apply_guard_state() on every new handle of such a class."""
     GUARD_KIND = None
 
     def _guard_args(self):

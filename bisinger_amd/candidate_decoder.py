@@ -5,7 +5,7 @@ Same constructor ``FFT(hidden_size, num_layers, kernel_size, num_heads)``, state
 Not selected by any shipped BiSinger config (all use 'wavenet'), so its sampler loop is driven from Python:
 one ``bsg_fftden_forward`` + ``bsg_ddpm_step`` per step (see GaussianDiffusion.sample).
 """
-from ctypes import POINTER, byref, c_void_p, cast
+from ctypes import byref, c_void_p
 
 import torch
 import torch.nn as nn
@@ -18,6 +18,10 @@ from .hparams import hparams
 
 class FFT(FFTBlocks, _lib.HandleOwner, _lib.GemmGuarded):
     GUARD_KIND = 'fftden'
+    DESTROY = 'bsg_fftden_destroy'
+    LAST_PATH = 'bsg_fftden_last_path'      # the launch forms of the last forward's FFT stack ('den.' tokens; include/bisinger_hip.h, bsg_fs2midi_last_path)
+    POISON = 'bsg_fftden_debug_poison_workspace'      # NaN bytes over every activation workspace of the handle
+    _bound = None
 
     def __init__(self, hidden_size=None, num_layers=None, kernel_size=None, num_heads=None):
         num_heads = hparams['num_heads'] if num_heads is None else num_heads
@@ -35,52 +39,23 @@ class FFT(FFTBlocks, _lib.HandleOwner, _lib.GemmGuarded):
         self.mlp = nn.Sequential(nn.Linear(dim, dim * 4), Mish(), nn.Linear(dim * 4, dim))
         self.get_mel_out = nn.Linear(hidden_size, 80, bias=True)
         self.get_decode_inp = nn.Linear(hidden_size + dim + dim, hidden_size)
-        self._h = self._h_key = self._bound = None
 
-    def handle(self):
-        key = self._key()
-        if self._h is not None and key == self._h_key:
-            return self._h
-        self.release()
-        ws = [p.detach() for p in self._weights()]
-        for p in ws:
-            if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
-                raise _lib.BsgError('FFT parameters must be contiguous float32 on the GPU; there is no CPU path')
+    def _create(self, ws, arr):
         lib = _lib.load()
         assert lib.bsg_fftden_n_weights(self.num_layers) == len(ws), (lib.bsg_fftden_n_weights(self.num_layers), len(ws))
         dev = ws[0].device
         self._n_pos = max(2000, int(hparams.get('max_frames', 5000))) + 2
         step_table = self.diffusion_embedding.table(self.max_steps).to(dev).contiguous()
         pos_table = self.embed_positions.table(self._n_pos).to(dev).contiguous()
-        arr = (c_void_p * len(ws))(*[p.data_ptr() for p in ws])
         h = c_void_p()
-        with torch.cuda.device(dev):
-            _lib.check(lib.bsg_fftden_create(byref(h), self.in_dims, self.num_layers, self.num_heads, self.kernel_size,
-                                             self.max_steps, self._n_pos, cast(arr, POINTER(c_void_p)), len(ws),
-                                             _lib.ptr(step_table), _lib.ptr(pos_table), _lib.stream_ptr()), 'bsg_fftden_create')
-        self._h, self._h_key, self._bound = h, key, None
-        self._apply_guard_state()
+        _lib.check(lib.bsg_fftden_create(byref(h), self.in_dims, self.num_layers, self.num_heads, self.kernel_size, self.max_steps,
+                                         self._n_pos, arr, len(ws), _lib.ptr(step_table), _lib.ptr(pos_table), _lib.stream_ptr()),
+                   'bsg_fftden_create')
         return h
 
     def release(self):
-        if self._h is not None:
-            _lib.load().bsg_fftden_destroy(self._h)
-        self._h = self._h_key = self._bound = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
-
-    def last_path(self):
-        """The launch forms of the last forward's FFT stack ('den.' tokens; include/bisinger_hip.h, bsg_fs2midi_last_path); 'none' before it."""
-        return _lib.load().bsg_fftden_last_path(self._h).decode() if self._h is not None else 'none'
-
-    def poison_workspace(self):
-        """Test hook (bsg_fftden_debug_poison_workspace): NaN bytes over every activation workspace of the handle."""
-        with torch.cuda.device(next(self.parameters()).device):
-            _lib.check(_lib.load().bsg_fftden_debug_poison_workspace(self.handle(), _lib.stream_ptr()), 'bsg_fftden_debug_poison_workspace')
+        super().release()
+        self._bound = None      # (handle() releases first: a new handle starts unbound)
 
     def prepare(self, cond):
         h = self.handle()

@@ -7,7 +7,7 @@ The modules below only *hold* parameters; all arithmetic happens in libbisinger_
 (csrc/diffnet.hip) through the C ABI of include/bisinger_hip.h.  No CPU/eager fallback exists.
 """
 import math
-from ctypes import POINTER, byref, c_int32, c_void_p, cast
+from ctypes import byref, c_double, c_int32, c_int64, c_void_p
 
 import torch
 import torch.nn as nn
@@ -76,39 +76,30 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         # extension (not in the reference): arithmetic of the fused residual layers, 'fp32' (parity) or 'bf16'
         # (bf16 MFMA operands, fp32 accumulation; BASELINE config 3) — include/bisinger_hip.h bsg_diffnet_set_compute
         self.compute_dtype = str(hparams.get('diff_compute_dtype', 'fp32'))
-        self._h = None
-        self._h_key = None
-        self._bound = None
-        self._lengths = None     # row lengths of a ragged binding (prepare(cond, lengths))
 
     # ------------------------------------------------------------------ handle management
-    def handle(self):
-        """(Re)create the library handle when the parameters moved or changed (load_ckpt, .to())."""
-        key = self._key()
-        if self._h is not None and key == self._h_key:
-            return self._h
-        self.release()
-        ws = [p.detach() for p in self._weights()]
-        for p in ws:
-            if not p.is_cuda:
-                raise _lib.BsgError('DiffNet parameters must live on the GPU (model.cuda()); there is no CPU path')
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise _lib.BsgError('DiffNet parameters must be contiguous float32')
-        lib = _lib.load()
+    DESTROY = 'bsg_diffnet_destroy'
+    LAST_PATH = 'bsg_diffnet_last_path'
+    _bound = None          # (cond, its _version, B, T) of the condition bound last
+    _bound_tok = None      # the frame -> token map of a per-token binding (prepare_tokens)
+    _lengths = None        # row lengths of a ragged binding (prepare(cond, lengths))
+
+    def _create(self, ws, arr):
         cfg = _lib.DiffnetCfg(self.in_dims, self.residual_channels, self.encoder_hidden, self.n_layers,
                               self.dilation_cycle_length, self.max_steps)
-        arr = (c_void_p * len(ws))(*[p.data_ptr() for p in ws])
         table = self.diffusion_embedding.table(self.max_steps).to(ws[0].device).contiguous()
         h = c_void_p()
-        with torch.cuda.device(ws[0].device):
-            _lib.check(lib.bsg_diffnet_create(byref(h), byref(cfg), cast(arr, POINTER(c_void_p)), len(ws),
-                                              _lib.ptr(table), _lib.stream_ptr()), 'bsg_diffnet_create')
-        self._h, self._h_key, self._bound = h, key, None
-        self._apply_compute()
-        self._apply_guard_state()
-        if getattr(self, 'split_disabled', False):
-            _lib.check(lib.bsg_diffnet_set_split(h, 0), 'bsg_diffnet_set_split')
+        _lib.check(_lib.load().bsg_diffnet_create(byref(h), byref(cfg), arr, len(ws), _lib.ptr(table), _lib.stream_ptr()), 'bsg_diffnet_create')
         return h
+
+    def _created(self):
+        self._apply_compute()
+        if self.split_disabled:      # a handle that was demoted stays demoted
+            self._switch(self.SET_SPLIT, 0)
+
+    def release(self):
+        super().release()
+        self._bound = None      # (handle() releases first: a new handle starts unbound)
 
     _COMPUTE = {'fp32': 0, 'float32': 0, 'bf16': 1, 'bfloat16': 1}
 
@@ -137,17 +128,6 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         """False: not the 16-row stack launch (|x| < 3750) but the 32-row one (|x + d| < 60000) — what BSG_H2_Q=0 does for the whole process."""
         _lib.check(_lib.load().bsg_diffnet_set_h2q(self.handle(), int(bool(enable))), 'bsg_diffnet_set_h2q')
         self._h2q_range_off = False
-
-    def release(self):
-        if self._h is not None:
-            _lib.load().bsg_diffnet_destroy(self._h)
-        self._h = self._h_key = self._bound = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
 
     def prepare(self, cond, lengths=None):
         """Bind ``cond`` [B,H,T]: hoists every layer's conditioner projection out of the step loop.
@@ -193,14 +173,14 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         """A range event of a split-fp16 launch was a property of the condition bound then: with another condition the handle tries the
         faster launch again — unless this is the repeated pass of an outer guarded call (GaussianDiffusion.forward recomputes cond: a NEW
         tensor with the same values), or the handle's inputs keep leaving the range (H2_STRIKES_MAX)."""
-        h = self.handle()
-        for attr, strikes, setter in (('_h2_range_off', '_h2_strikes', 'bsg_diffnet_set_h2'), ('_h2q_range_off', '_h2q_strikes', 'bsg_diffnet_set_h2q')):
-            off = getattr(self, attr, False)
+        self.handle()
+        for attr, strikes, setter in self.RANGE_TIERS.values():
+            off = getattr(self, attr)
             if off is not False and off is not cond:
-                if _lib.in_retry() or getattr(self, strikes, 0) >= self.H2_STRIKES_MAX:
+                if _lib.in_retry() or getattr(self, strikes) >= self.H2_STRIKES_MAX:
                     setattr(self, attr, cond)
                 else:
-                    _lib.check(getattr(_lib.load(), setter)(h, 1), setter)
+                    self._switch(setter, 1)
                     setattr(self, attr, False)
 
     def _ensure_bound(self, cond, lengths=None):
@@ -209,8 +189,8 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         b = self._bound
         lens = None if lengths is None else ragged_lens(lengths, cond.shape[0], cond.shape[2])
         if (self._h is None or self._key() != self._h_key or b is None or b[0] is not cond or b[1] != cond._version
-                or getattr(self, '_bound_tok', None) is not None
-                or not cond.is_contiguous() or cond.dtype != torch.float32 or getattr(self, '_lengths', None) != lens):
+                or self._bound_tok is not None
+                or not cond.is_contiguous() or cond.dtype != torch.float32 or self._lengths != lens):
             self.prepare(cond, lengths)
             if cond.is_contiguous() and cond.dtype == torch.float32:
                 self._bound = (cond, cond._version, cond.shape[0], cond.shape[2])
@@ -271,7 +251,6 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
     def uses_handoffs(self, B, T):
         """True when launches of shape (B, T) may hand data between workgroups (channel-split launches of small batches,
         the on-chip stack launch whose tiles exchange edges every layer).  Otherwise nothing below synchronises."""
-        from ctypes import c_int32
         u = c_int32()
         with _lib.on_device(self):
             _lib.check(_lib.load().bsg_diffnet_uses_handoffs(self._h if self._h is not None else self.handle(), B, T, byref(u)), 'bsg_diffnet_uses_handoffs')
@@ -286,7 +265,6 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
     def take_health(self):
         """Wait for the current stream of the handle's device; (hand-off spins that gave up, values beyond the fp16 range seen by the
         split-fp16 stack launch) since the last take; resets both."""
-        from ctypes import c_int32
         c = (c_int32 * 2)()
         with _lib.on_device(self):
             _lib.check(_lib.load().bsg_diffnet_health_take(self._h, c, _lib.stream_ptr()), 'bsg_diffnet_health_take')
@@ -295,6 +273,71 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
     PART_PATHS = ('stack_h2_quad', 'stack_h2_quad64', 'stack_h2_pair64')
     CLEAN_CALLS_TO_REENABLE = 32     # guarded calls without a give-up after which a demoted handle tries hand-off launches again
     H2_STRIKES_MAX = 3               # range events of the split-fp16 stack launch after which the handle stays on the fp32 matrix pipe
+
+    # ------------------------------------------------------------------ the healing ladder: its state and its tiers, for both guard modes
+    # range event (status word 1), by the launch that raised it; both hold while the condition of the event is bound (the event is a
+    # property of the input: _rearm) and for good after H2_STRIKES_MAX events:
+    #   'h2q'  16-row stack launch (its conv image holds 16 x: |x| >= 3750)  -> the 32-row launch (|x + d| < 60000, ~8 % slower)
+    #   'h2'   any other split-fp16 launch (|x + d| >= 60000)               -> the fp32 matrix pipe (~2x slower)
+    # tier: (attribute: False, or the condition bound at the event / True when none was, the tier's strike count, its switch)
+    RANGE_TIERS = {'h2': ('_h2_range_off', '_h2_strikes', 'bsg_diffnet_set_h2'), 'h2q': ('_h2q_range_off', '_h2q_strikes', 'bsg_diffnet_set_h2q')}
+    _h2_range_off = _h2q_range_off = False
+    _h2_strikes = _h2q_strikes = 0
+    # hand-off give-up (status word 0): inside a part launch -> part forms off (one workgroup per tile); otherwise, or with the part forms
+    # off already -> every hand-off launch off (per-layer launches on the fp32 matrix pipe).  Each for CLEAN_CALLS_TO_REENABLE clean calls
+    SET_PARTS, SET_SPLIT = 'bsg_diffnet_set_parts', 'bsg_diffnet_set_split'
+    parts_disabled = split_disabled = False
+    _clean_calls_parts = _clean_calls = 0
+
+    def _switch(self, setter, on):
+        _lib.check(getattr(_lib.load(), setter)(self._h, int(on)), setter)
+
+    def _demote_range(self, rng, path):
+        """Range tier: `rng` waves of the launch `path` saw a value beyond its range.  -> what was done about it."""
+        q = path.startswith('stack_h2q') and self._h2q_range_off is False
+        attr, strikes, setter = self.RANGE_TIERS['h2q' if q else 'h2']
+        self._switch(setter, 0)
+        setattr(self, attr, self._bound[0] if self._bound is not None else True)
+        setattr(self, strikes, getattr(self, strikes) + 1)
+        if q:
+            return (f'{rng} waves saw an activation beyond the range of the 16-row split-fp16 stack launch (|x| >= 3750: its conv image holds '
+                    f'16 x in fp16 planes): this DiffNet handle takes the 32-row launch (|x + d| < 60000, about 8 % slower) while this '
+                    f'condition is bound')
+        return (f'{rng} waves saw an activation beyond the fp16 range of the split-fp16 launch {path} (|x + d| >= 60000): this DiffNet handle '
+                f'runs the kernels of the fp32 matrix pipe while this condition is bound')
+
+    def _demote_giveup(self, n, path, from_part):
+        """Give-up tier: `n` hand-offs of the launch `path` gave up; `from_part`: they came out of a part launch (several workgroups per
+        tile on CUs of one XCD: partners not on this XCD, or not resident — the one-workgroup-per-tile stack launch does not depend on
+        that placement).  -> what was done about it."""
+        if from_part and not self.parts_disabled:
+            self._switch(self.SET_PARTS, 0)
+            self.parts_disabled, self._clean_calls_parts = True, 0
+            return (f'{n} inter-workgroup hand-offs gave up inside a part launch ({path}): part forms are off for this DiffNet handle for '
+                    f'the next {self.CLEAN_CALLS_TO_REENABLE} calls (one workgroup per tile)')
+        self._switch(self.SET_SPLIT, 0)
+        self.split_disabled, self._clean_calls = True, 0
+        return (f'{n} inter-workgroup hand-offs gave up (a partner workgroup was not resident): channel-split and stack launches are off for '
+                f'this DiffNet handle for the next {self.CLEAN_CALLS_TO_REENABLE} calls (per-layer launches on the fp32 matrix pipe)')
+
+    def _count_clean(self, n, split):
+        """`n` clean calls against the demotion off every hand-off launch (`split`) or off the part forms: after CLEAN_CALLS_TO_REENABLE
+        it is tried again (a give-up is a property of the moment — another process on the GPU — not of the handle).  The split brings
+        the part forms back with it."""
+        if split:
+            self._clean_calls += n
+            if self._clean_calls < self.CLEAN_CALLS_TO_REENABLE:
+                return
+            self._switch(self.SET_SPLIT, 1)
+            self.split_disabled, self._clean_calls = False, 0
+            if not self.parts_disabled:
+                return
+        else:
+            self._clean_calls_parts += n
+            if self._clean_calls_parts < self.CLEAN_CALLS_TO_REENABLE:
+                return
+        self._switch(self.SET_PARTS, 1)
+        self.parts_disabled, self._clean_calls_parts = False, 0
 
     def guarded(self, run, B, T, restore=None):
         """Run ``run()`` (which enqueues evaluations on this handle) so that an invalid result never leaves the call.  Three events are
@@ -322,68 +365,36 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
             return
 
         def again():
-            if self._bound is not None and getattr(self, '_bound_tok', None) is not None:
+            if self._bound is not None and self._bound_tok is not None:
                 self.prepare_tokens(self._bound[0], self._bound_tok)
             elif self._bound is not None:
-                self.prepare(self._bound[0], getattr(self, '_lengths', None))
+                self.prepare(self._bound[0], self._lengths)
             if restore is not None:
                 restore()
         _lib.range_guarded(lambda: self._guarded_handoffs(run, B, T, restore), 'DiffNet', on_retry=again, device=self, owners=(self,))
 
     def _guarded_handoffs(self, run, B, T, restore):
         """run(), then look at the handle's health words and heal — tier by tier, one repeat per tier, whatever the order in which the
-        events show up (a repeat on another launch form can raise the OTHER kind of event: ADVICE r05):
-          range event (status word 1), by the launch that raised it:
-            16-row stack launch (its conv image holds 16 x: |x| >= 3750)  -> bsg_diffnet_set_h2q(h, 0): the 32-row launch (|x + d| < 60000, ~8 % slower)
-            any other split-fp16 launch (|x + d| >= 60000)               -> bsg_diffnet_set_h2(h, 0): the fp32 matrix pipe (~2x slower)
-            both while this condition is bound (the event is a property of the input); H2_STRIKES_MAX events keep the handle there
-          hand-off give-up (status word 0):
-            inside a part launch  -> part forms off (one workgroup per tile), CLEAN_CALLS_TO_REENABLE calls
-            otherwise             -> every hand-off launch off (per-layer launches on the fp32 matrix pipe)"""
+        events show up (a repeat on another launch form can raise the OTHER kind of event: ADVICE r05).  The tiers: RANGE_TIERS /
+        _demote_range for a range event, taken only when nothing gave up; _demote_giveup otherwise."""
         import warnings
         run()
-        if getattr(self, 'split_disabled', False):
+        if self.split_disabled:
             # a demoted handle launches nothing that hands data between workgroups (bsg_diffnet_uses_handoffs is 0 for every shape while
-            # the split is off), so the call just made is clean by construction: count it HERE, before the early return below, and give
-            # the hand-off launches another try after CLEAN_CALLS_TO_REENABLE of them (a give-up is a property of the moment — another
-            # process on the GPU — not of the handle)
-            self._clean_calls = getattr(self, '_clean_calls', 0) + 1
-            if self._clean_calls >= self.CLEAN_CALLS_TO_REENABLE:
-                _lib.check(_lib.load().bsg_diffnet_set_split(self._h, 1), 'bsg_diffnet_set_split')
-                self.split_disabled, self._clean_calls = False, 0
-                if getattr(self, 'parts_disabled', False):      # both tiers come back together
-                    _lib.check(_lib.load().bsg_diffnet_set_parts(self._h, 1), 'bsg_diffnet_set_parts')
-                    self.parts_disabled, self._clean_calls_parts = False, 0
+            # the split is off), so the call just made is clean by construction: count it HERE, before the early return below
+            self._count_clean(1, split=True)
             return
-        lib = _lib.load()
         for attempt in range(5):      # at most: h2q off, h2 off | parts off, split off — each tier once
             if not self.uses_handoffs(B, T):
                 return
             give, rng = self.take_health()
             if not give and not rng:
-                if attempt == 0 and getattr(self, 'parts_disabled', False):      # part forms come back after as many clean calls as hand-off launches do
-                    self._clean_calls_parts = getattr(self, '_clean_calls_parts', 0) + 1
-                    if self._clean_calls_parts >= self.CLEAN_CALLS_TO_REENABLE:
-                        _lib.check(lib.bsg_diffnet_set_parts(self._h, 1), 'bsg_diffnet_set_parts')
-                        self.parts_disabled, self._clean_calls_parts = False, 0
+                if attempt == 0 and self.parts_disabled:      # part forms come back after as many clean calls as hand-off launches do
+                    self._count_clean(1, split=False)
                 return
             path = self.last_path()
             if not give:
-                bound = self._bound[0] if self._bound is not None else True
-                if path.startswith('stack_h2q') and not getattr(self, '_h2q_range_off', False):
-                    warnings.warn(f'bisinger_amd: {rng} waves saw an activation beyond the range of the 16-row split-fp16 stack launch (|x| >= 3750: its '
-                                  f'conv image holds 16 x in fp16 planes); this DiffNet handle takes the 32-row launch (|x + d| < 60000, about 8 % slower) '
-                                  f'while this condition is bound and the evaluation is repeated')
-                    _lib.check(lib.bsg_diffnet_set_h2q(self._h, 0), 'bsg_diffnet_set_h2q')
-                    self._h2q_range_off = bound
-                    self._h2q_strikes = getattr(self, '_h2q_strikes', 0) + 1
-                else:
-                    warnings.warn(f'bisinger_amd: {rng} waves saw an activation beyond the fp16 range of the split-fp16 launch {path} (|x + d| >= 60000); '
-                                  f'this DiffNet handle runs the kernels of the fp32 matrix pipe while this condition is bound and the '
-                                  f'evaluation is repeated')
-                    _lib.check(lib.bsg_diffnet_set_h2(self._h, 0), 'bsg_diffnet_set_h2')
-                    self._h2_range_off = bound
-                    self._h2_strikes = getattr(self, '_h2_strikes', 0) + 1
+                what = self._demote_range(rng, path)
                 # A split-fp16 GEMM of this handle may have counted an operand too.  Behind a launch that tripped that is the rule, not a second
                 # fault: the launch's invalid output (inf / NaN) is the operand of the skip projection.  The word is cleared and only the launch
                 # goes one tier down; if a GEMM was the CAUSE (a condition or an x beyond |v| < 4062: its product is inf / NaN, never finite
@@ -391,23 +402,13 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
                 # makes the projections count once more — and the GEMM guard around this call then repeats everything, prepare() included,
                 # with the handle's GEMMs on the fp32 matrix pipe
                 self.gemm_range_take()
-            elif path in self.PART_PATHS and not getattr(self, 'parts_disabled', False):
-                # first tier: the give-up came out of a PART launch (several workgroups per tile on CUs of one XCD: partners not on this XCD,
-                # or not resident).  The one-workgroup-per-tile stack launch does not depend on that placement
-                warnings.warn(f'bisinger_amd: {give} inter-workgroup hand-offs gave up inside a part launch ({path}); part forms are off '
-                              f'for this DiffNet handle for the next {self.CLEAN_CALLS_TO_REENABLE} calls (one workgroup per tile) and the evaluation is repeated')
-                _lib.check(lib.bsg_diffnet_set_parts(self._h, 0), 'bsg_diffnet_set_parts')
-                self.parts_disabled, self._clean_calls_parts = True, 0
             else:
-                warnings.warn(f'bisinger_amd: {give} inter-workgroup hand-offs gave up (a partner workgroup was not resident); channel-split and '
-                              f'stack launches are off for this DiffNet handle for the next {self.CLEAN_CALLS_TO_REENABLE} calls (per-layer launches '
-                              f'on the fp32 matrix pipe) and the evaluation is repeated')
-                _lib.check(lib.bsg_diffnet_set_split(self._h, 0), 'bsg_diffnet_set_split')
-                self.split_disabled, self._clean_calls = True, 0
+                what = self._demote_giveup(give, path, path in self.PART_PATHS)
+            warnings.warn(f'bisinger_amd: {what} and the evaluation is repeated')
             if restore is not None:
                 restore()
             run()
-            if getattr(self, 'split_disabled', False):
+            if self.split_disabled:
                 give, rng = self.take_health()
                 if give or rng:
                     raise _lib.BsgError(f'{give + rng} inter-workgroup hand-offs gave up with split launches off: the result is invalid')
@@ -432,6 +433,8 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         _lib.check_deferred(self, block)
 
     def _check_deferred_own(self, block=False):
+        """The tiers of _guarded_handoffs, but nothing can be repeated here: the range demotion AND the give-up demotion are applied from
+        one read, and the error names both."""
         rec = getattr(self, '_deferred', None)
         if rec is None or not rec.armed() or self._h is None:
             return
@@ -441,48 +444,18 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         # the words are cumulative until a take resets them: the newest completed read says everything
         give, rng, give_split = words[-1]
         if not (give or rng or give_split):
-            if getattr(self, 'parts_disabled', False):
-                self._clean_calls_parts = getattr(self, '_clean_calls_parts', 0) + len(words)
-                if self._clean_calls_parts >= self.CLEAN_CALLS_TO_REENABLE:
-                    _lib.check(_lib.load().bsg_diffnet_set_parts(self._h, 1), 'bsg_diffnet_set_parts')
-                    self.parts_disabled, self._clean_calls_parts = False, 0
-            if getattr(self, 'split_disabled', False):
-                self._clean_calls = getattr(self, '_clean_calls', 0) + len(words)
-                if self._clean_calls >= self.CLEAN_CALLS_TO_REENABLE:
-                    _lib.check(_lib.load().bsg_diffnet_set_split(self._h, 1), 'bsg_diffnet_set_split')
-                    self.split_disabled, self._clean_calls = False, 0
-                    if getattr(self, 'parts_disabled', False):
-                        _lib.check(_lib.load().bsg_diffnet_set_parts(self._h, 1), 'bsg_diffnet_set_parts')
-                        self.parts_disabled, self._clean_calls_parts = False, 0
+            if self.parts_disabled:
+                self._count_clean(len(words), split=False)
+            if self.split_disabled:
+                self._count_clean(len(words), split=True)
             return
         self.take_health()      # waits for the stream and resets the words;
         rec.drop_pending()      # reads enqueued before this point repeat the same (cumulative) counts: dropped — repeat everything issued since the last clean check
-        what = []
+        path, what = self.last_path(), []
         if rng:
-            bound = self._bound[0] if self._bound is not None else True
-            if self.last_path().startswith('stack_h2q') and not getattr(self, '_h2q_range_off', False):
-                _lib.check(_lib.load().bsg_diffnet_set_h2q(self._h, 0), 'bsg_diffnet_set_h2q')
-                self._h2q_range_off = bound
-                self._h2q_strikes = getattr(self, '_h2q_strikes', 0) + 1
-                what.append(f'{rng} waves saw a value beyond the range of the 16-row split-fp16 stack launch (|x| >= 3750; this handle now takes the '
-                            f'32-row launch while this condition is bound)')
-            else:
-                _lib.check(_lib.load().bsg_diffnet_set_h2(self._h, 0), 'bsg_diffnet_set_h2')
-                self._h2_range_off = bound
-                self._h2_strikes = getattr(self, '_h2_strikes', 0) + 1
-                what.append(f'{rng} waves saw a value beyond the fp16 range of the split-fp16 launch (this handle now runs the fp32 matrix pipe '
-                            f'while this condition is bound)')
-        if give and not give_split and self.last_path() in self.PART_PATHS and not getattr(self, 'parts_disabled', False):
-            # first tier (as in the same-call mode): the give-up came out of a part launch; the one-workgroup-per-tile launch stays
-            _lib.check(_lib.load().bsg_diffnet_set_parts(self._h, 0), 'bsg_diffnet_set_parts')
-            self.parts_disabled, self._clean_calls_parts = True, 0
-            what.append(f'{give} inter-workgroup hand-offs gave up inside a part launch (part forms are off for the next '
-                        f'{self.CLEAN_CALLS_TO_REENABLE} calls)')
-        elif give or give_split:
-            _lib.check(_lib.load().bsg_diffnet_set_split(self._h, 0), 'bsg_diffnet_set_split')
-            self.split_disabled, self._clean_calls = True, 0
-            what.append(f'{give + give_split} inter-workgroup hand-offs gave up (hand-off launches are off for the next '
-                        f'{self.CLEAN_CALLS_TO_REENABLE} calls)')
+            what.append(self._demote_range(rng, path))
+        if give or give_split:      # the part tier only when no split launch gave up as well (the third word)
+            what.append(self._demote_giveup(give + give_split, path, bool(give) and not give_split and path in self.PART_PATHS))
         raise _lib.BsgError('a PREVIOUS call on this DiffNet handle produced an invalid result (guard_mode=deferred): ' + '; '.join(what) +
                             '.  Repeat the work')
 
@@ -507,7 +480,9 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         'stack_h2_pair64' (a tile as 4 / 4 / 2 workgroups), 'stack_h2q' / 'stack_h2' (16- / 32-row split-fp16 launch), 'stack_f43',
         'stack_bf16'; '_tail' behind a name: the sampler's step tail ran inside the launch; '_ragged': a ragged batch.  Per-layer
         launches: 'layer', 'split2', 'split4', 'wide', 'bf16'.  'none' before the first launch."""
-        return _lib.load().bsg_diffnet_last_path(self._h if self._h is not None else self.handle()).decode()      # (a query of the handle that exists: no look at the weights)
+        if self._h is None:      # bench.py and the tools ask before the first call (a handle that exists is queried without a look at the weights)
+            self.handle()
+        return super().last_path()
 
     def last_launch(self):
         """-> (launch chains of the last sampler call: 2 = the two half-batch chains, launch groups of the last stack launch or 0)."""
@@ -518,21 +493,18 @@ class DiffNet(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
 
     def handoff_timeouts(self):
         """Hand-off health: spins that gave up and were not yet taken (0 unless a workgroup was not resident). Synchronises."""
-        from ctypes import c_int32
         n = c_int32()
         _lib.check(_lib.load().bsg_diffnet_status(self._h, byref(n)), 'bsg_diffnet_status')
         return n.value
 
     def clock_read(self):
         """-> (shader MHz held over the last profiled stack launch, its in-kernel span in us); (0, 0) when none ran.  Synchronises."""
-        from ctypes import c_double
         mhz, span = c_double(), c_double()
         _lib.check(_lib.load().bsg_diffnet_clock_read(self._h, byref(mhz), byref(span)), 'bsg_diffnet_clock_read')
         return mhz.value, span.value
 
     def profile_read(self):
         """-> (summed device ms of the recorded residual-layer chains, number of layer launches covered)."""
-        from ctypes import c_double, c_int64
         ms, n = c_double(), c_int64()
         _lib.check(_lib.load().bsg_diffnet_profile_read(self._h, byref(ms), byref(n)), 'bsg_diffnet_profile_read')
         return ms.value, n.value

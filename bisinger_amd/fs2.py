@@ -10,7 +10,7 @@ reference's 143 ``fs2.*`` entries (names, shapes, order — including the two al
 ``bsg_fs2midi_*`` in libbisinger_hip (csrc/fs2.hip).
 """
 import math
-from ctypes import POINTER, byref, c_int32, c_void_p, cast
+from ctypes import byref, c_int32, c_void_p
 
 import torch
 import torch.nn as nn
@@ -266,6 +266,12 @@ class _FastSpeech2Base(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
     reference's forward."""
     GUARD_KIND = 'fs2midi'
     FRONT = _lib.FS2_FRONT_MIDI
+    DESTROY = 'bsg_fs2midi_destroy'
+    # last_path() (test introspection): the launch forms of the last encode and of the decode after it, as blank-separated tokens in
+    # launch order (include/bisinger_hip.h, bsg_fs2midi_last_path): 'esm:wave enc.qkv:fused enc.attn:planes/ks2 enc.gemm:h2w/32/deep ...
+    # dec. ...'; 'none' before the first call
+    LAST_PATH = 'bsg_fs2midi_last_path'
+    POISON = 'bsg_fs2midi_debug_poison_workspace'      # NaN bytes over every activation workspace of the handle
 
     def _init_base(self, dictionary, out_dims):
         """fastspeech/fs2.py:27-81 in the reference's registration order, without the encoder (the subclass adds its own)."""
@@ -293,25 +299,12 @@ class _FastSpeech2Base(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         if self.use_pitch_embed:
             self.pitch_embed = Embedding(300, H, self.padding_idx)
             self.pitch_predictor = PitchPredictor(H, hp['predictor_layers'], ph, hp['predictor_kernel'])
-        self._h = None
-        self._h_key = None
 
     # ------------------------------------------------------------------ handle management
     def _token_table(self):
         raise NotImplementedError
 
-    def handle(self):
-        key = self._key()
-        if self._h is not None and key == self._h_key:
-            return self._h
-        self.release()
-        name = type(self).__name__
-        ws = [p.detach() for p in self._weights()]
-        for p in ws:
-            if not p.is_cuda:
-                raise _lib.BsgError(f'{name} parameters must live on the GPU (model.cuda()); there is no CPU path')
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise _lib.BsgError(f'{name} parameters must be contiguous float32')
+    def _create(self, ws, arr):
         hp = hparams
         lib = _lib.load()
         self._n_pos = max(DEFAULT_MAX_TARGET_POSITIONS, int(hp.get('max_frames', 5000))) + 2
@@ -323,15 +316,12 @@ class _FastSpeech2Base(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
                            hp['num_heads'], hp['enc_ffn_kernel_size'], hp['dec_ffn_kernel_size'], self.out_dims,
                            len(self.dur_predictor.conv), self.dur_predictor.kernel_size, spk_rows, 8, self._n_pos, self._n_rel)
         dec_table = self.decoder.embed_positions.table(self._n_pos).to(dev).contiguous()
-        arr = (c_void_p * len(ws))(*[p.data_ptr() for p in ws])
         h = c_void_p()
         if self.FRONT == _lib.FS2_FRONT_MIDI and not self.use_pitch_embed:
             # the configuration of every BiSinger experiment: the entry it has always been created through
             assert lib.bsg_fs2midi_n_weights(byref(base)) == len(ws)
-            with torch.cuda.device(dev):
-                _lib.check(lib.bsg_fs2midi_create(byref(h), byref(base), cast(arr, POINTER(c_void_p)), len(ws),
-                                                  _lib.ptr(dec_table), _lib.ptr(tok_table), _lib.stream_ptr()),
-                           'bsg_fs2midi_create')
+            _lib.check(lib.bsg_fs2midi_create(byref(h), byref(base), arr, len(ws), _lib.ptr(dec_table), _lib.ptr(tok_table),
+                                              _lib.stream_ptr()), 'bsg_fs2midi_create')
         else:
             pit_table = None
             cfg = _lib.Fs2XCfg(base, self.FRONT, 0, 0, 0, 0, 0)
@@ -343,41 +333,15 @@ class _FastSpeech2Base(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
             if n < 0:
                 _lib.check(n, 'bsg_fs2_n_weights')
             assert n == len(ws), (n, len(ws))
-            with torch.cuda.device(dev):
-                _lib.check(lib.bsg_fs2_create(byref(h), byref(cfg), cast(arr, POINTER(c_void_p)), len(ws), _lib.ptr(dec_table),
-                                              _lib.ptr(tok_table), _lib.ptr(pit_table), _lib.stream_ptr()), 'bsg_fs2_create')
-        self._h, self._h_key = h, key
-        self._apply_guard_state()
+            _lib.check(lib.bsg_fs2_create(byref(h), byref(cfg), arr, len(ws), _lib.ptr(dec_table), _lib.ptr(tok_table), _lib.ptr(pit_table),
+                                          _lib.stream_ptr()), 'bsg_fs2_create')
         return h
-
-    def release(self):
-        if self._h is not None:
-            _lib.load().bsg_fs2midi_destroy(self._h)
-        self._h = self._h_key = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
 
     def last_rows(self):
         """-> (token rows the last encode ran its encoder on, rows of the last FFT stack): test introspection."""
-        from ctypes import c_int32
         a, b = c_int32(), c_int32()
         _lib.check(_lib.load().bsg_fs2midi_last_rows(self._h if self._h is not None else self.handle(), byref(a), byref(b)), 'bsg_fs2midi_last_rows')
         return a.value, b.value
-
-    def last_path(self):
-        """The launch forms of the last encode and of the decode after it, as blank-separated tokens in launch order
-        (include/bisinger_hip.h, bsg_fs2midi_last_path): 'esm:wave enc.qkv:fused enc.attn:planes/ks2 enc.gemm:h2w/32/deep ... dec. ...';
-        'none' before the first call.  Test introspection."""
-        return _lib.load().bsg_fs2midi_last_path(self._h).decode() if self._h is not None else 'none'
-
-    def poison_workspace(self):
-        """Test hook (bsg_fs2midi_debug_poison_workspace): NaN bytes over every activation workspace of the handle."""
-        with torch.cuda.device(next(self.parameters()).device):
-            _lib.check(_lib.load().bsg_fs2midi_debug_poison_workspace(self.handle(), _lib.stream_ptr()), 'bsg_fs2midi_debug_poison_workspace')
 
     @torch.no_grad()
     def regulate(self, enc, with_lengths=False):

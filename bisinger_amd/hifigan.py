@@ -6,7 +6,7 @@ registered in the checkpoint layout (``bias, weight_g, weight_v`` per conv) so t
 vocoders/hifigan.py:27-29; an already folded ``weight`` layout loads too.  Discriminators / GAN losses
 (hifigan.py:185-369) are training-only and out of scope.
 """
-from ctypes import POINTER, byref, c_int32, c_void_p, cast
+from ctypes import byref, c_int32, c_void_p
 
 import numpy as np
 import torch
@@ -94,6 +94,12 @@ class ResBlock2(nn.Module):
 
 class HifiGanGenerator(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
     GUARD_KIND = 'hifigan'
+    DESTROY = 'bsg_hifigan_destroy'
+    # last_path(): the launches of the last forward, one token per launch in launch order (include/bisinger_hip.h, bsg_hifigan_last_path):
+    # 'pre:h2w up0:h2w rb0.0.0:pair_h2/NB1 ... up2:upk rb2.2:chain/NC8 up3:up2 ... post:post4'; 'none' before the first forward.  After
+    # a forward that the range guard repeated it names the repeat
+    LAST_PATH = 'bsg_hifigan_last_path'
+    POISON = 'bsg_hifigan_debug_poison_workspace'      # NaN bytes into every stage buffer, the NSF source buffers and the GEMM planes
 
     def __init__(self, h, c_out=1):
         super().__init__()
@@ -128,8 +134,6 @@ class HifiGanGenerator(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
             for k, d in zip(h['resblock_kernel_sizes'], h['resblock_dilation_sizes']):
                 self.resblocks.append((ResBlock1 if self.resblock == 1 else ResBlock2)(h, ch, k, d))
         self.conv_post = _WNConv((c_out, ch, 7), c_out)
-        self._h = None
-        self._h_key = None
 
     def remove_weight_norm(self):
         print('Removing weight norm...')
@@ -139,18 +143,10 @@ class HifiGanGenerator(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
             l.remove_weight_norm()
         self.conv_pre.fold()
         self.conv_post.fold()
-        self.__dict__.pop('_handle_slots', None)      # the parameters changed NAMES (weight_g / weight_v -> weight): look the slots up again
+        self.forget_slots()
 
     # ------------------------------------------------------------------ handle
-    def handle(self):
-        key = self._key()
-        if self._h is not None and key == self._h_key:
-            return self._h
-        self.release()
-        ws = [p.detach() for p in self._weights()]
-        for p in ws:
-            if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
-                raise _lib.BsgError('HifiGanGenerator parameters must be contiguous float32 on the GPU; there is no CPU path')
+    def _create(self, ws, arr):
         states = {c.folded for c in self.modules() if isinstance(c, _WNConv)}
         if len(states) != 1:
             raise _lib.BsgError('mixed weight-norm / folded layers')
@@ -173,36 +169,9 @@ class HifiGanGenerator(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         cfg.resblock = self.resblock
         lib = _lib.load()
         assert lib.bsg_hifigan_n_weights(byref(cfg)) == len(ws), (lib.bsg_hifigan_n_weights(byref(cfg)), len(ws))
-        arr = (c_void_p * len(ws))(*[p.data_ptr() for p in ws])
         hd = c_void_p()
-        with torch.cuda.device(ws[0].device):
-            _lib.check(lib.bsg_hifigan_create(byref(hd), byref(cfg), cast(arr, POINTER(c_void_p)), len(ws), _lib.stream_ptr()),
-                       'bsg_hifigan_create')
-        self._h, self._h_key = hd, key
-        self._apply_guard_state()
+        _lib.check(lib.bsg_hifigan_create(byref(hd), byref(cfg), arr, len(ws), _lib.stream_ptr()), 'bsg_hifigan_create')
         return hd
-
-    def release(self):
-        if self._h is not None:
-            _lib.load().bsg_hifigan_destroy(self._h)
-        self._h = self._h_key = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
-
-    def last_path(self):
-        """The launches of the last forward, one token per launch in launch order (include/bisinger_hip.h, bsg_hifigan_last_path):
-        'pre:h2w up0:h2w rb0.0.0:pair_h2/NB1 ... up2:upk rb2.2:chain/NC8 up3:up2 ... post:post4'; 'none' before the first forward.  After
-        a forward that the range guard repeated it names the repeat."""
-        return _lib.load().bsg_hifigan_last_path(self._h).decode() if self._h is not None else 'none'
-
-    def poison_workspace(self):
-        """Test hook (bsg_hifigan_debug_poison_workspace): NaN bytes into every stage buffer, the NSF source buffers and the GEMM planes."""
-        if self._h is not None:
-            _lib.check(_lib.load().bsg_hifigan_debug_poison_workspace(self._h, _lib.stream_ptr()), 'bsg_hifigan_debug_poison_workspace')
 
     @torch.no_grad()
     def forward(self, x, f0=None, rand_ini=None, noise=None, seed=0, lengths=None):
@@ -216,13 +185,7 @@ class HifiGanGenerator(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         Drawn NSF noise keeps its Philox index (row, padded stride): a row sees the draws it sees in the padded call.  ``None``: the padded
         call, every row at T frames."""
         if lengths is not None:      # checked before anything touches the GPU: a refused call builds no handle and writes nothing
-            B, T = int(x.shape[0]), int(x.shape[-1])
-            lengths = [int(v) for v in (lengths.tolist() if hasattr(lengths, 'tolist') else lengths)]
-            if len(lengths) != B:
-                raise _lib.BsgError(f'HifiGanGenerator.forward: lengths has {len(lengths)} entries for a batch of {B} rows')
-            for b, v in enumerate(lengths):
-                if not 1 <= v <= T:
-                    raise _lib.BsgError(f'HifiGanGenerator.forward: lengths[{b}]={v} outside 1..T={T}')
+            lengths = _lib.row_lengths(lengths, int(x.shape[0]), 'HifiGanGenerator.forward', T=int(x.shape[-1]))
         # range guard of the split-fp16 ResBlock pairs (an activation beyond the fp16 range is counted by the kernels, never clipped):
         # read once per outermost call; on an event the call (ragged or not) is repeated on the fp32 matrix pipe (_lib.range_guarded)
         return _lib.range_guarded(lambda: self._forward(x, f0, rand_ini, noise, seed, lengths), 'HifiGanGenerator.forward', device=self,

@@ -3,7 +3,7 @@
 Used by the inference harness when ``pe_enable`` is set to feed the NSF vocoder (a-*.py:600-603, :629-630).
 Same module tree / ``state_dict`` (59 entries) as the reference; parameters only, the arithmetic is ``bsg_pitchext_*``.
 """
-from ctypes import POINTER, byref, c_int32, c_void_p, cast
+from ctypes import byref, c_int32, c_void_p
 
 import torch
 import torch.nn as nn
@@ -71,6 +71,8 @@ class PitchPredictor(_Holder):
 
 class PitchExtractor(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
     GUARD_KIND = 'pitchext'
+    DESTROY = 'bsg_pitchext_destroy'
+    POISON = 'bsg_pitchext_debug_poison_workspace'      # NaN bytes into every shape-sized buffer of the handle
 
     def __init__(self, n_mel_bins=80, conv_layers=2):
         super().__init__()
@@ -85,17 +87,8 @@ class PitchExtractor(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
             self.mel_encoder = ConvStacks(idim=self.hidden_size, n_chans=self.hidden_size, odim=self.hidden_size, n_layers=conv_layers)
         self.pitch_predictor = PitchPredictor(self.hidden_size, n_chans=ph, n_layers=5, dropout_rate=0.5, odim=2,
                                               kernel_size=self.predictor_kernel)
-        self._h = self._h_key = None
 
-    def handle(self):
-        key = self._key()
-        if self._h is not None and key == self._h_key:
-            return self._h
-        self.release()
-        ws = [p.detach() for p in self._weights()]
-        for p in ws:
-            if not p.is_cuda or not p.is_contiguous():
-                raise _lib.BsgError('PitchExtractor parameters must be contiguous tensors on the GPU; there is no CPU path')
+    def _create(self, ws, arr):
         assert hparams.get('pitch_norm', 'log') == 'log', "only pitch_norm: log is on the BiSinger path"
         use_uv = int(hparams.get('pitch_type', 'frame') == 'frame' and bool(hparams.get('use_uv', True)))
         self._n_pos = max(4096, int(hparams.get('max_frames', 5000)) + 2)
@@ -103,30 +96,9 @@ class PitchExtractor(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         lib = _lib.load()
         assert lib.bsg_pitchext_n_weights(byref(cfg)) == len(ws), (lib.bsg_pitchext_n_weights(byref(cfg)), len(ws))
         table = self.pitch_predictor.embed_positions.table(self._n_pos).to(ws[0].device).contiguous()
-        arr = (c_void_p * len(ws))(*[p.data_ptr() for p in ws])
         h = c_void_p()
-        with torch.cuda.device(ws[0].device):
-            _lib.check(lib.bsg_pitchext_create(byref(h), byref(cfg), cast(arr, POINTER(c_void_p)), len(ws), _lib.ptr(table),
-                                               _lib.stream_ptr()), 'bsg_pitchext_create')
-        self._h, self._h_key = h, key
-        self._apply_guard_state()
+        _lib.check(lib.bsg_pitchext_create(byref(h), byref(cfg), arr, len(ws), _lib.ptr(table), _lib.stream_ptr()), 'bsg_pitchext_create')
         return h
-
-    def release(self):
-        if self._h is not None:
-            _lib.load().bsg_pitchext_destroy(self._h)
-        self._h = self._h_key = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
-
-    def poison_workspace(self):
-        """Test hook (bsg_pitchext_debug_poison_workspace): NaN bytes into every shape-sized buffer of the handle."""
-        if self._h is not None:
-            _lib.check(_lib.load().bsg_pitchext_debug_poison_workspace(self._h, _lib.stream_ptr()), 'bsg_pitchext_debug_poison_workspace')
 
     @torch.no_grad()
     def forward(self, mel_input=None, lengths=None):
@@ -138,10 +110,7 @@ class PitchExtractor(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         statistics, the convolutions' padding and the predictor's positions all end with the row).  ``None``: the padded call, every row
         at T frames, padding included."""
         if lengths is not None:      # the count is checked before anything touches the GPU; the values by the library, before it enqueues anything
-            B = int(mel_input.shape[0])
-            lengths = [int(v) for v in (lengths.tolist() if hasattr(lengths, 'tolist') else lengths)]
-            if len(lengths) != B:
-                raise _lib.BsgError(f'PitchExtractor.forward: lengths has {len(lengths)} entries for a batch of {B} rows')
+            lengths = _lib.row_lengths(lengths, int(mel_input.shape[0]), 'PitchExtractor.forward')
         # the guard's repeat (an operand beyond the fp16 range of the split-fp16 GEMMs) runs the same call, ragged or not, on the fp32 matrix pipe
         return _lib.range_guarded(lambda: self._forward(mel_input, lengths), 'PitchExtractor.forward', device=self, owners=(self,))
 

@@ -8,7 +8,7 @@ loads too.  What the kernels are built for (bsg_pwg_create refuses the rest with
 = 64, gate = 128, aux = 80 channels, ``ConvInUpsampleNetwork`` with the nearest stretch.  The discriminator and the losses are
 training-only and out of scope.
 """
-from ctypes import POINTER, byref, c_int32, c_void_p, cast
+from ctypes import byref, c_int32, c_void_p
 
 import numpy as np
 import torch
@@ -110,6 +110,10 @@ class ResidualBlock(nn.Module):
 
 
 class ParallelWaveGANGenerator(nn.Module, _lib.HandleOwner):
+    DESTROY = 'bsg_pwg_destroy'
+    LAST_PATH = 'bsg_pwg_last_path'      # the launches of the last forward in launch order (include/bisinger_hip.h, bsg_pwg_last_path)
+    POISON = 'bsg_pwg_debug_poison_workspace'
+
     def __init__(self, in_channels=1, out_channels=1, kernel_size=3, layers=30, stacks=3, residual_channels=64, gate_channels=128,
                  skip_channels=64, aux_channels=80, aux_context_window=2, dropout=0.0, bias=True, use_weight_norm=True,
                  use_causal_conv=False, upsample_conditional_features=True, upsample_net='ConvInUpsampleNetwork',
@@ -142,8 +146,6 @@ class ParallelWaveGANGenerator(nn.Module, _lib.HandleOwner):
         if use_pitch_embed:
             self.pitch_embed = nn.Embedding(300, aux_channels, 0)
             self.c_proj = nn.Linear(2 * aux_channels, aux_channels)
-        self._h = None
-        self._h_key = None
 
     @property
     def hop_size(self):
@@ -158,21 +160,15 @@ class ParallelWaveGANGenerator(nn.Module, _lib.HandleOwner):
         for m in self.modules():
             if isinstance(m, _WNConv):
                 m.fold()
-        self.__dict__.pop('_handle_slots', None)      # the parameters changed names (weight_g / weight_v -> weight)
+        self.forget_slots()
 
     # ------------------------------------------------------------------ handle
-    def handle(self):
-        key = self._key()
-        if self._h is not None and key == self._h_key:
-            return self._h
-        self.release()
+    def _before_weights(self):
         if not all(m.folded for m in self.modules() if isinstance(m, _WNConv)):
             raise _lib.BsgError('ParallelWaveGANGenerator is in the weight-norm layout: call remove_weight_norm() before the first forward '
                                 '(vocoders/pwg.py:48)')
-        ws = [p.detach() for p in self._weights()]
-        for p in ws:
-            if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
-                raise _lib.BsgError('ParallelWaveGANGenerator parameters must be contiguous float32 on the GPU; there is no CPU path')
+
+    def _create(self, ws, arr):
         q = self.params
         cfg = _lib.PwgCfg()
         for n in ('in_channels', 'out_channels', 'kernel_size', 'layers', 'stacks', 'residual_channels', 'gate_channels', 'skip_channels',
@@ -188,28 +184,9 @@ class ParallelWaveGANGenerator(nn.Module, _lib.HandleOwner):
             cfg.upsample_scales[i] = s
         cfg.n_pitch = self.pitch_embed.weight.shape[0] if self.use_pitch_embed else 0
         cfg.hop_size = self.hop_size
-        arr = (c_void_p * len(ws))(*[p.data_ptr() for p in ws])
         hd = c_void_p()
-        with torch.cuda.device(ws[0].device):
-            _lib.check(_lib.load().bsg_pwg_create(byref(hd), byref(cfg), cast(arr, POINTER(c_void_p)), len(ws), _lib.stream_ptr()),
-                       'bsg_pwg_create')
-        self._h, self._h_key = hd, key
+        _lib.check(_lib.load().bsg_pwg_create(byref(hd), byref(cfg), arr, len(ws), _lib.stream_ptr()), 'bsg_pwg_create')
         return hd
-
-    def release(self):
-        if self._h is not None:
-            _lib.load().bsg_pwg_destroy(self._h)
-        self._h = self._h_key = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
-
-    def last_path(self):
-        """The launches of the last forward in launch order (include/bisinger_hip.h, bsg_pwg_last_path); 'none' before the first."""
-        return _lib.load().bsg_pwg_last_path(self._h).decode() if self._h is not None else 'none'
 
     def last_tiles(self):
         """The 256-sample tiles one residual-layer launch of the last forward walked (bsg_pwg_last_tiles): B ceil(T hop / 256) after
@@ -229,12 +206,7 @@ class ParallelWaveGANGenerator(nn.Module, _lib.HandleOwner):
         is not the waveform of the lone call with that seed."""
         B, A, T = (int(v) for v in mel.shape)
         # checked before the handle is built and before the output exists: without a GPU the refusal is the length's
-        lengths = [int(v) for v in (lengths.tolist() if hasattr(lengths, 'tolist') else lengths)]
-        if len(lengths) != B:
-            raise _lib.BsgError(f'ParallelWaveGANGenerator.forward_ragged: lengths has {len(lengths)} entries for a batch of {B} rows')
-        for b, n in enumerate(lengths):
-            if not 1 <= n <= T:
-                raise _lib.BsgError(f'ParallelWaveGANGenerator.forward_ragged: lengths[{b}]={n} outside 1..T={T}')
+        lengths = _lib.row_lengths(lengths, B, 'ParallelWaveGANGenerator.forward_ragged', T=T)
         hd = self.handle()
         dev = self.first_conv.weight.device
         mel = mel.to(dev, torch.float32).contiguous()
