@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'lib', 'libbisinger_hip.so')
 if os.environ.get('BSG_LIB'):      # development: an alternative build of the same ABI (kernel experiments)
     LIB_PATH = os.environ['BSG_LIB']
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 
 class BsgError(RuntimeError):
@@ -64,6 +64,20 @@ class GemmDesc(Structure):
                 ('sBiasN', c_int64), ('alpha', c_float), ('alpha_ncols', c_int32), ('act', c_int32),
                 ('post_scale_n', c_void_p), ('post_shift_n', c_void_p), ('R', c_void_p), ('ldr', c_int32), ('sR', c_int64),
                 ('rowscale', c_void_p), ('sRS', c_int64), ('batch', c_int32)]
+
+
+class H2wDesc(Structure):
+    """bsg_h2w_desc (include/bisinger_hip.h): every argument of the pre-split GEMM with fp32 operands, for the test entry bsg_gemm_h2w_ex."""
+    _fields_ = [('act', c_void_p), ('lda_src', c_int32), ('sAct_src', c_int64), ('lda', c_int32), ('sAct', c_int64),
+                ('w', c_void_p), ('ts', c_int64), ('rs', c_int64), ('ks', c_int64), ('sW', c_int64),
+                ('rows', c_int32), ('K', c_int32), ('Wn', c_int32), ('taps', c_int32), ('tap_shift0', c_int32), ('act_is_a', c_int32),
+                ('batch', c_int32), ('zdiv', c_int32),
+                ('C', c_void_p), ('ldc', c_int32), ('sC', c_int64), ('Cq', c_void_p), ('Ch', c_void_p),
+                ('out', c_void_p), ('out_plane', c_int64), ('ldo', c_int32), ('sO', c_int64),
+                ('bias', c_void_p), ('sBias', c_int64), ('alpha', c_float), ('alpha_ncols', c_int32), ('act_fn', c_int32),
+                ('R', c_void_p), ('ldr', c_int32), ('sR', c_int64), ('rowscale', c_void_p), ('sRS', c_int64),
+                ('up_u', c_int32), ('up_p', c_int32), ('up_lout', c_int32), ('qkv_T', c_int32), ('qkv_Tp', c_int32), ('qkv_H', c_int32),
+                ('vt', c_void_p), ('vt_plane', c_int64), ('lens', c_void_p)]
 
 
 class Schedule(Structure):
@@ -191,6 +205,7 @@ _SIGS = {
     'bsg_handle_get_gemm_split': (c_int32, [c_int32, c_void_p, POINTER(c_int32)]),
     'bsg_gemm_presplit_f32': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                         c_int32, c_void_p]),
+    'bsg_gemm_h2w_ex': (c_int32, [POINTER(H2wDesc), c_int32, POINTER(c_char_p), c_void_p]),      # ABI v21
 }
 
 _lib = None

@@ -186,6 +186,7 @@ int h2w_split_transposed(const float* src, unsigned short* hi, unsigned short* l
 int h2w_split_transposed_lrelu(const float* src, unsigned short* hi, unsigned short* lo, int B, int K, int Kp, int T, int rows_per_b, float slope,
                                const int* lens, int lmul, hipStream_t st);
 int launch_gemm_h2w(const H2wArgs& g, hipStream_t st);
+int launch_gemm_h2w(const H2wArgs& g, hipStream_t st, int force_form);   // force_form: bsg_gemm_h2w_ex's test hook (1 .. 7: bisinger_hip.h); 0 = dispatch, as the overload above
 unsigned* gemm_range_counter();   // device address of the range-event counter (null on error): kernels of other translation units add to it
 
 }  // namespace bsg

@@ -583,7 +583,27 @@ int h2w_split_transposed(const float* src, unsigned short* hi, unsigned short* l
   return h2w_split_transposed_lrelu(src, hi, lo, B, K, K, T, T, 1.0f, nullptr, 1, st);
 }
 
-int launch_gemm_h2w(const H2wArgs& g0, hipStream_t st) {
+// TEST HOOK (bsg_gemm_h2w_ex): what a forced form needs of the problem — the instantiation must exist and its ring must divide the k-steps
+static int h2w_force_check(const H2wArgs& g, int force) {
+  BSG_REQUIRE(force >= 0 && force <= 7, "gemm_h2w: force_form %d outside 0..7", force);
+  if (!force) return BSG_OK;
+  static const char* const names[8] = {"", "h2w/32/deep", "h2w/32/ring16", "h2w/32/ring8", "h2w/32/ring4", "h2w/64/ring8", "h2w/64/ring4", "h2w/128/ring4"};
+  static const int rings[8] = {0, 16, 16, 8, 4, 8, 4, 4};
+  BSG_REQUIRE(force > 4 || g.act_is_a, "gemm_h2w: force_form %d (%s): the 32-row tiles are built for the [token][feature] output only (act_is_a=0)", force,
+              names[force]);
+  BSG_REQUIRE(force != 1 || (g.taps == 1 && g.K % 256 == 0), "gemm_h2w: force_form 1 (%s) needs a plain product of 256-deep slices (taps=%d K=%d)",
+              names[force], g.taps, g.K);
+  BSG_REQUIRE(g.K / 16 * g.taps % rings[force] == 0, "gemm_h2w: force_form %d (%s): the ring of %d does not divide the %d k-steps (K=%d taps=%d)", force,
+              names[force], rings[force], g.K / 16 * g.taps, g.K, g.taps);
+  BSG_REQUIRE(!g.lens || (g.taps == 1 ? force == 1 : force == 2) || force == 5 || force == 7,
+              "gemm_h2w: force_form %d (%s): with lengths only the six ragged instantiations are built (32/deep plain, 32/ring16 conv, 64/ring8, "
+              "128/ring4; taps=%d)", force, names[force], g.taps);
+  return BSG_OK;
+}
+
+int launch_gemm_h2w(const H2wArgs& g, hipStream_t st) { return launch_gemm_h2w(g, st, 0); }
+
+int launch_gemm_h2w(const H2wArgs& g0, hipStream_t st, int force_form) {
   H2wArgs g = g0;
   BSG_REQUIRE(g.act && g.wpack && (g.C || g.out || g.Ch || g.Cq) && g.batch > 0, "gemm_h2w: null operand");
   BSG_REQUIRE(g.C || !(g.Ch || g.Cq) || (!g.act_is_a && !g.up_u && !g.R && !g.rowscale && g.act_fn == ACT_NONE), "gemm_h2w: a quad-order output without the fp32 row-order one needs the direct-store epilogue");
@@ -615,6 +635,36 @@ int launch_gemm_h2w(const H2wArgs& g0, hipStream_t st) {
   const bool tiny = g.act_is_a && (long long)cdiv(g.rows, 64) * (g.Wn / 128) * g.batch < tiny_env;
   static int ring_env = -1;   // BSG_H2W_RING=4: the 4-step weight ring at every tile size (rounds 4's first form)
   if (ring_env < 0) { const char* e = getenv("BSG_H2W_RING"); ring_env = e ? atoi(e) : 16; }
+  if (force_form) {
+    // TEST HOOK (bsg_gemm_h2w_ex only; every other caller passes 0 and reaches the dispatch below): the named instantiation, whatever the
+    // workgroup count and the environment say
+    if (g.lens) BSG_REQUIRE(g.act_is_a && g.K % 256 == 0 && !g.up_u && g.zdiv == g.batch, "gemm_h2w: lengths are built for the [token][feature] forms with K %% 256 == 0 (act_is_a=%d K=%d)", g.act_is_a, g.K);
+    if (const int rc = h2w_force_check(g, force_form)) return rc;
+    const bool plain = g.taps == 1, a = g.act_is_a != 0;
+    if (g.lens) {
+      switch (force_form) {
+        case 1: return h2w_launch<true, 1, 16, 16, true>(g, st);
+        case 2: return h2w_launch<true, 1, 2, 16, true>(g, st);
+        case 5: return plain ? h2w_launch<true, 2, 4, 8, true>(g, st) : h2w_launch<true, 2, 2, 8, true>(g, st);
+        default: return plain ? h2w_launch<true, 4, 4, 4, true>(g, st) : h2w_launch<true, 4, 2, 4, true>(g, st);
+      }
+    }
+    switch (force_form) {
+      case 1: return h2w_launch<true, 1, 16, 16>(g, st);
+      case 2: return plain ? h2w_launch<true, 1, 4, 16>(g, st) : h2w_launch<true, 1, 2, 16>(g, st);
+      case 3: return plain ? h2w_launch<true, 1, 4, 8>(g, st) : h2w_launch<true, 1, 2, 8>(g, st);
+      case 4: return plain ? h2w_launch<true, 1, 4, 4>(g, st) : h2w_launch<true, 1, 2, 4>(g, st);
+      case 5:
+        if (a) return plain ? h2w_launch<true, 2, 4, 8>(g, st) : h2w_launch<true, 2, 2, 8>(g, st);
+        return plain ? h2w_launch<false, 2, 4, 8>(g, st) : h2w_launch<false, 2, 2, 8>(g, st);
+      case 6:
+        if (a) return plain ? h2w_launch<true, 2, 4, 4>(g, st) : h2w_launch<true, 2, 2, 4>(g, st);
+        return plain ? h2w_launch<false, 2, 4, 4>(g, st) : h2w_launch<false, 2, 2, 4>(g, st);
+      default:
+        if (a) return plain ? h2w_launch<true, 4, 4, 4>(g, st) : h2w_launch<true, 4, 2, 4>(g, st);
+        return plain ? h2w_launch<false, 4, 4, 4>(g, st) : h2w_launch<false, 4, 2, 4>(g, st);
+    }
+  }
   if (g.lens) {
     // ragged (the FS2 front): the [token][feature] forms at their default rings only, whatever BSG_H2W_RING / BSG_H2W_DEEP say — same tile
     // heights and thresholds as below (K % 256 == 0 makes every ring length divide the step count)
@@ -680,5 +730,91 @@ extern "C" int bsg_gemm_presplit_f32(const float* act, const float* w, float* ou
   if (planes) (void)hipFree(planes);
   if (bad) (void)hipFree(bad);
   if (rc == BSG_OK && nbad) { set_error("gemm_presplit_f32: %u weights beyond the fp16 range of the split", nbad); rc = BSG_EINVAL; }
+  return rc;
+}
+
+// Test entry that reaches ALL of launch_gemm_h2w (include/bisinger_hip.h bsg_gemm_h2w_ex): fp32 operands in, every output mode, the form to
+// launch.  Builds the activation planes and the packed weights on every call, waits for the stream and frees what it allocated.  The plane
+// buffer is filled with an fp16 NaN pattern (bytes 0x7e) and only the logical rows x K windows are split into it (rows < lens[z] with
+// lengths): a tap, a padding column or a ragged row that the kernel fails to mask reads NaN.
+extern "C" int bsg_gemm_h2w_ex(const bsg_h2w_desc* d, int32_t force_form, const char** form, void* stream) {
+  using namespace bsg;
+  BSG_REQUIRE(d, "gemm_h2w_ex: null descriptor");
+  BSG_REQUIRE(d->act && d->w, "gemm_h2w_ex: null operand (act %p, w %p)", (const void*)d->act, (const void*)d->w);
+  BSG_REQUIRE(d->C || d->out || d->Ch || d->Cq, "gemm_h2w_ex: no output (C, Cq, Ch and out are null)");
+  BSG_REQUIRE(d->batch > 0 && d->zdiv >= 0 && (d->zdiv == 0 || d->batch % d->zdiv == 0), "gemm_h2w_ex: batch %d / zdiv %d", d->batch, d->zdiv);
+  BSG_REQUIRE(d->lda >= d->K && h2w_supports(d->rows, d->Wn, d->K, d->taps, d->lda),
+              "gemm_h2w_ex: unsupported shape rows=%d Wn=%d K=%d taps=%d lda=%d (Wn %% 128, K %% 64, taps <= 17, lda >= K, lda %% 8)", d->rows, d->Wn, d->K,
+              d->taps, d->lda);
+  const int n_act = d->zdiv > 0 ? d->zdiv : d->batch, n_w = d->batch / n_act;
+  BSG_REQUIRE(d->lda_src >= d->K && d->lda_src % 4 == 0 && d->sAct_src % 4 == 0 && ((uintptr_t)d->act & 15) == 0,
+              "gemm_h2w_ex: the fp32 activation needs 16-byte aligned rows (lda_src=%d sAct_src=%lld)", d->lda_src, (long long)d->sAct_src);
+  BSG_REQUIRE(n_act == 1 || (d->sAct >= (long long)d->rows * d->lda && d->sAct % 8 == 0), "gemm_h2w_ex: plane batch stride %lld (rows=%d lda=%d)",
+              (long long)d->sAct, d->rows, d->lda);
+  {
+    H2wArgs chk{};
+    chk.act_is_a = d->act_is_a; chk.taps = d->taps; chk.K = d->K; chk.lens = d->lens;
+    if (const int rc = h2w_force_check(chk, force_form)) return rc;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const long long plane = (((long long)(n_act - 1) * d->sAct + (long long)d->rows * d->lda) + 7) / 8 * 8;
+  const long long wset = (long long)2 * d->Wn * d->K * d->taps;   // halfs of one packed weight set
+  unsigned short *planes = nullptr, *pack = nullptr;
+  unsigned* bad = nullptr;
+  int* lens_h = nullptr;
+  int rc = BSG_OK;
+  if (hipMalloc((void**)&planes, (size_t)2 * plane * sizeof(unsigned short)) != hipSuccess ||
+      hipMalloc((void**)&pack, (size_t)n_w * wset * sizeof(unsigned short)) != hipSuccess || hipMalloc((void**)&bad, sizeof(unsigned)) != hipSuccess ||
+      hipMemsetAsync(bad, 0, sizeof(unsigned), st) != hipSuccess ||
+      hipMemsetAsync(planes, 0x7e, (size_t)2 * plane * sizeof(unsigned short), st) != hipSuccess) {
+    set_error("gemm_h2w_ex: out of device memory");
+    rc = BSG_ENOMEM;
+  }
+  if (rc == BSG_OK && d->lens) {
+    lens_h = (int*)malloc(sizeof(int) * (size_t)n_act);
+    if (!lens_h || hipMemcpyAsync(lens_h, d->lens, sizeof(int) * (size_t)n_act, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) {
+      set_error("gemm_h2w_ex: cannot read the lengths");
+      rc = BSG_EHIP;
+    }
+    for (int z = 0; rc == BSG_OK && z < n_act; ++z)
+      if (lens_h[z] < 0 || lens_h[z] > d->rows) { set_error("gemm_h2w_ex: lens[%d] = %d outside 0..%d", z, lens_h[z], d->rows); rc = BSG_EINVAL; }
+  }
+  for (int zw = 0; zw < n_w && rc == BSG_OK; ++zw)
+    rc = h2w_pack_into(pack + zw * wset, d->w + (long long)zw * d->sW, d->Wn, d->K, d->taps, d->ts, d->rs, d->ks, bad, st);
+  for (int za = 0; za < n_act && rc == BSG_OK; ++za) {
+    const int nr = lens_h ? lens_h[za] : d->rows;
+    const float* src = d->act + (long long)za * d->sAct_src;
+    unsigned short* hi = planes + (long long)za * d->sAct;
+    if (nr > 0 && d->lda == d->K) rc = h2w_split_rows(src, hi, hi + plane, nr, d->K, d->lda_src, st);
+    else   // h2w_split_rows writes rows K halfs apart: a wider plane row stride goes row by row
+      for (int r = 0; r < nr && rc == BSG_OK; ++r)
+        rc = h2w_split_rows(src + (long long)r * d->lda_src, hi + (long long)r * d->lda, hi + plane + (long long)r * d->lda, 1, d->K, d->lda_src, st);
+  }
+  if (rc == BSG_OK) {
+    H2wArgs g{};
+    g.act = planes; g.act_plane = plane; g.lda = d->lda; g.sAct = d->sAct; g.wpack = pack; g.sW = wset; g.zdiv = d->zdiv;
+    g.rows = d->rows; g.K = d->K; g.Wn = d->Wn; g.taps = d->taps; g.tap_shift0 = d->tap_shift0; g.act_is_a = d->act_is_a ? 1 : 0;
+    g.C = d->C; g.ldc = d->ldc; g.sC = d->sC; g.Cq = d->Cq; g.Ch = d->Ch;
+    g.out = d->out; g.out_plane = d->out_plane; g.ldo = d->ldo; g.sO = d->sO;
+    g.bias = d->bias; g.sBias = d->sBias; g.alpha = d->alpha; g.alpha_ncols = d->alpha_ncols; g.act_fn = d->act_fn;
+    g.R = d->R; g.ldr = d->ldr; g.sR = d->sR; g.rowscale = d->rowscale; g.sRS = d->sRS; g.batch = d->batch;
+    g.up_u = d->up_u; g.up_p = d->up_p; g.up_lout = d->up_lout;
+    g.qkv_T = d->qkv_T; g.qkv_Tp = d->qkv_Tp; g.qkv_H = d->qkv_H; g.vt = d->vt; g.vt_plane = d->vt_plane;
+    g.form_out = form; g.lens = d->lens;
+    rc = launch_gemm_h2w(g, st, force_form);
+  }
+  unsigned nbad = 0;
+  if (rc == BSG_OK && (hipMemcpyAsync(&nbad, bad, sizeof(unsigned), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) {
+    set_error("gemm_h2w_ex: device error");
+    rc = BSG_EHIP;
+  } else {
+    (void)hipStreamSynchronize(st);
+  }
+  if (planes) (void)hipFree(planes);
+  if (pack) (void)hipFree(pack);
+  if (bad) (void)hipFree(bad);
+  free(lens_h);
+  if (rc == BSG_OK && nbad) { set_error("gemm_h2w_ex: %u weights beyond the fp16 range of the split", nbad); rc = BSG_EINVAL; }
   return rc;
 }

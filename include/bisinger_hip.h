@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define BSG_ABI_VERSION 20
+#define BSG_ABI_VERSION 21
 
 #define BSG_OK 0
 #define BSG_EINVAL (-22)  /* bad argument / shape the kernels do not support            */
@@ -780,6 +780,58 @@ int bsg_handle_get_gemm_split(int32_t kind, void* handle, int32_t* enabled);
  *   the launch is repeated `reps` times (timing); waits for `stream`. */
 int bsg_gemm_presplit_f32(const float* act, const float* w, float* out, const float* bias, int32_t rows, int32_t Wn, int32_t K,
                           int32_t taps, int32_t act_is_a, int32_t batch, int32_t relu, int32_t reps, void* stream);
+
+/* ABI v21, test entry that reaches ALL of the pre-split GEMM (csrc/gemm_h2w.hip launch_gemm_h2w): bsg_h2w_desc mirrors every field a caller of
+ * it sets, with fp32 operands.  Per batch index z (activation item za = z % zdiv, weight set zw = z / zdiv; zdiv = 0: one weight set):
+ *   v(i, n) = sum_tap sum_k act[za][i + tap_shift0 + tap][k] * W[zw](tap, n, k)      rows outside [0, rows) (with lens: [0, lens[za])) are zero
+ *   v = (v + bias[zw][n]) * alpha' ;  v = act_fn(v) ;  v += R[z](i, n) ;  v *= rowscale[za][i]       alpha' = alpha on weight rows n < alpha_ncols (0: all)
+ * and v goes to C[z] ([rows][ldc] with act_is_a, [Wn][ldc] without), to the channel-quad copies Cq / Ch ([Wn / 4][rows][4], fp32 / bf16), to the
+ * hi / lo fp16 planes `out` of 16 v, to the V^T planes `vt` of the QKV mode or to the polyphase positions C[co][8 q + r - up_p], as H2wArgs
+ * (csrc/bsg_common.h) documents them.  On every call the entry packs the weights (W(tap, n, k) at w[zw * sW + tap * ts + n * rs + k * ks]) and
+ * builds the activation planes: a buffer of fp16 NaNs (bytes 0x7e) into which only the logical rows x K windows are split (rows < lens[za]
+ * with lengths), row stride lda and item stride sAct of their own — what the kernel fails to mask reads NaN.  Waits for `stream`, frees what it
+ * allocated.  A packed weight beyond the fp16 range is BSG_EINVAL after the call; activations count into bsg_gemm_range_events.
+ *   force_form  0: dispatch as every other caller; 1 h2w/32/deep, 2 h2w/32/ring16, 3 h2w/32/ring8, 4 h2w/32/ring4, 5 h2w/64/ring8,
+ *               6 h2w/64/ring4, 7 h2w/128/ring4 (tile height / weight ring).  Refused with BSG_EINVAL before anything is launched: a 32-row
+ *               form (1-4) with act_is_a = 0; 1 without taps == 1 && K % 256 == 0; a ring that does not divide the K / 16 * taps k-steps;
+ *               with lens, any form but the six ragged ones (1 plain, 2 conv, 5, 7)
+ *   form        NULL, or receives the name of the form that was launched (a string literal) */
+typedef struct {
+  const float* act;             /* fp32 activation: item za at act + za * sAct_src, row i at + i * lda_src (16-byte aligned rows) */
+  int32_t lda_src;
+  int64_t sAct_src;
+  int32_t lda;                  /* row stride of the planes the entry builds (halfs; >= K, % 8) */
+  int64_t sAct;                 /* their item stride (halfs; >= rows * lda, % 8) */
+  const float* w;               /* fp32 weights */
+  int64_t ts, rs, ks;           /* tap, row and k stride of one weight set */
+  int64_t sW;                   /* stride between weight sets (elements) */
+  int32_t rows, K, Wn, taps, tap_shift0, act_is_a, batch, zdiv;
+  float* C;
+  int32_t ldc;
+  int64_t sC;
+  float* Cq;
+  uint16_t* Ch;
+  uint16_t* out;
+  int64_t out_plane;
+  int32_t ldo;
+  int64_t sO;
+  const float* bias;
+  int64_t sBias;
+  float alpha;
+  int32_t alpha_ncols;
+  int32_t act_fn;               /* 0 none, 1 ReLU, 2 GELU (erf) */
+  const float* R;
+  int32_t ldr;
+  int64_t sR;
+  const float* rowscale;
+  int64_t sRS;
+  int32_t up_u, up_p, up_lout;
+  int32_t qkv_T, qkv_Tp, qkv_H;
+  uint16_t* vt;
+  int64_t vt_plane;
+  const int32_t* lens;          /* device, one row count per activation item, or NULL */
+} bsg_h2w_desc;
+int bsg_gemm_h2w_ex(const bsg_h2w_desc* d, int32_t force_form, const char** form, void* stream);
 
 #ifdef __cplusplus
 }

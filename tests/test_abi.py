@@ -115,3 +115,51 @@ def test_gemm_ex_refuses_bad_descriptors_with_a_message():
     for kw in unaligned:
         for force in (1, 2, 3, 4):
             refused(desc(**kw), force, 'force_form', 'aligned')
+
+
+def test_gemm_h2w_ex_refuses_bad_descriptors_and_forms_with_a_message():
+    """bsg_gemm_h2w_ex (the test entry that reaches all of launch_gemm_h2w): a bad descriptor and a forced form the kernel is not built for
+    are BSG_EINVAL with a message, before any device call — checked here without a GPU.  The struct is the header's, field for field."""
+    from ctypes import byref, c_char_p
+    lib = _lib.load()
+    src = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'bisinger_hip.h')).read(), flags=re.S)
+    body = re.search(r'typedef struct \{([^}]*)\} bsg_h2w_desc;', src).group(1)
+    names = [n.strip(' *') for decl in body.split(';') if decl.strip() for n in decl.strip().split(None, 2 if decl.strip().startswith('const') else 1)[-1].split(',')]
+    assert names == [f[0] for f in _lib.H2wDesc._fields_], names
+
+    def desc(**kw):
+        d = _lib.H2wDesc(act=0x1000, lda_src=256, lda=256, w=0x2000, ts=0, rs=256, ks=1, rows=8, K=256, Wn=128, taps=1, act_is_a=1, batch=1,
+                         C=0x3000, ldc=128, alpha=1.0)
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return d
+
+    def refused(d, force, *words):
+        form = c_char_p()
+        rc = lib.bsg_gemm_h2w_ex(byref(d) if d is not None else None, force, byref(form), None)
+        assert rc == -22 and form.value is None, (rc, form.value)
+        msg = lib.bsg_last_error().decode()
+        assert msg.startswith('gemm_h2w') and all(w in msg for w in words), msg
+
+    refused(None, 0, 'null descriptor')
+    refused(desc(act=None), 0, 'null operand')
+    refused(desc(w=None), 0, 'null operand')
+    refused(desc(C=None), 0, 'no output')
+    refused(desc(batch=0), 0, 'batch 0')
+    refused(desc(batch=4, zdiv=3), 0, 'zdiv 3')
+    for kw in (dict(rows=0), dict(Wn=100), dict(K=96), dict(taps=18), dict(lda=260), dict(lda=192)):
+        refused(desc(**kw), 0, 'unsupported shape')
+    for kw in (dict(lda_src=258), dict(sAct_src=2), dict(act=0x1004)):
+        refused(desc(**kw), 0, '16-byte aligned')
+    refused(desc(batch=2, sAct=8), 0, 'plane batch stride')
+    for force in (-1, 8):
+        refused(desc(), force, 'force_form', str(force))
+    for force in (1, 2, 3, 4):
+        refused(desc(act_is_a=0), force, 'force_form', '32-row')
+    refused(desc(taps=3, tap_shift0=-1), 1, 'force_form 1', 'plain product')
+    refused(desc(K=128, lda=128), 1, 'force_form 1', 'K=128')
+    refused(desc(K=64, lda=64), 3, 'ring of 8', 'does not divide')           # 4 k-steps
+    refused(desc(K=64, lda=64, taps=3), 2, 'ring of 16', 'does not divide')  # 12 k-steps
+    refused(desc(K=64, lda=64, taps=3, act_is_a=0), 5, 'ring of 8', 'does not divide')
+    for force, taps in ((3, 1), (4, 1), (6, 1), (2, 1), (1, 9), (3, 9), (4, 9), (6, 9)):
+        refused(desc(lens=0x4000, taps=taps), force, 'lengths', 'ragged') if not (force == 1 and taps == 9) else refused(desc(lens=0x4000, taps=taps), force, 'force_form 1')

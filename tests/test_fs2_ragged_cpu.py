@@ -125,7 +125,7 @@ def test_refusals_that_need_no_device():
 
 def test_abi_v20_entries_match_the_header():
     src = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'bisinger_hip.h')).read(), flags=re.S)
-    assert _lib.ABI_VERSION == 20 and re.search(r'#define BSG_ABI_VERSION 20\b', src)
+    assert _lib.ABI_VERSION >= 20 and re.search(rf'#define BSG_ABI_VERSION {_lib.ABI_VERSION}\b', src)      # (v21 added bsg_gemm_h2w_ex)
     for name in ('bsg_fs2midi_encode_ragged', 'bsg_fs2_encode_plain_ragged', 'bsg_fs2_decode_ragged'):
         args = re.search(rf'\bint {name}\s*\((.*?)\);', src, flags=re.S).group(1).split(',')
         restype, argtypes = _lib._SIGS[name]
