@@ -32,6 +32,7 @@
 #include "bsg_ws.h"
 #include "diffnet_res.h"
 #include "diffnet_tail.h"
+#include "diffnet_forms.h"
 
 namespace bsg {
 
@@ -1139,7 +1140,6 @@ struct bsg_diffnet {
   unsigned* tok_bad = nullptr;   // device word: ids the last conversion found outside [0, K)
   float* cond_exp = nullptr;     // [B][H][T]: the per-frame condition of a token prepare that cannot keep the table (bf16 compute, no pre-split GEMM)
   size_t cap_cond_exp = 0;
-  int occ_stack_tok = -1;        // resident workgroups per CU of the token form (-1: not queried)
   float* xa = nullptr;        // [B][C][T]
   float* xb = nullptr;
   float* skip = nullptr;
@@ -1158,13 +1158,8 @@ struct bsg_diffnet {
   size_t flags_cap = 0;                // tiles the exchange array and the flags are sized for
   unsigned* epoch_dev = nullptr;       // [2] launch epoch of the stack / part launches in device memory + workgroups done (diffnet_res.h StackArgs::epoch)
   unsigned long long* clk = nullptr;   // [4] s_memtime / s_memrealtime at the start and end of tile 0 of the last profiled stack launch
-  int occ_stack_h = -1;                // the same for residual_stack_bf16_kernel
-  int occ_stack43 = -1;                // the same for residual_stack_f43_kernel
   bool h2_off = false;                 // bsg_diffnet_set_h2(h, 0): this handle multiplies on the fp32 matrix pipe only
   bool q_off = false;                  // bsg_diffnet_set_h2q(h, 0): the 32-row stack launch (|x + d| < 60000) instead of the 16-row one (|x| < 3750)
-  int occ_stack_h2q[3] = {-1, -1, -1}; // the same for residual_stack_q_kernel (16-row matrix tiles, diffnet_h2q.hip)
-  int occ_stack_h2[3] = {-1, -1, -1};  // resident workgroups per CU of residual_stack_h2_kernel<.., NCT> by NCT (-1: not queried)
-  int occ_part[3] = {-1, -1, -1};      // resident workgroups per CU: [1] / [2] quad of 32- / 64-frame tiles, [0] pair of 64-frame tiles (-1: not queried)
   unsigned short *apack1q = nullptr, *apack2q = nullptr;   // the split-fp16 weights once more as 16-row fragments (part forms)
   unsigned short* part_zx = nullptr;   // part forms: exchange slots of the z parts [tiles][P][2 planes][tile frames][C/P] fp16
   unsigned short* part_ix = nullptr;   //             ... of the image parts [2 parities][tiles][P][2 planes][tile frames][C/P]
@@ -1185,15 +1180,11 @@ struct bsg_diffnet {
   int inject_nowait = 0;               // the same entry with a NEGATIVE count: part launches left that skip their waits silently (timing experiment)
   int inject_xcc = 0;                  // bsg_diffnet_debug_inject_xcc: part launches left in which odd parts report another XCD
   bool parts_off = false;              // bsg_diffnet_set_parts(h, 0): no part forms (several workgroups per tile on CUs of ONE XCD); the one-workgroup-per-tile launches stay
-  // residency of the split kernels on this handle's device (workgroups per CU; -1 = not queried yet): pair / 4-way form with the
-  // padded LDS size (one workgroup per CU by construction) and with the plain size (two chains share a CU), 16-wave form
-  int occ2 = -1, occ4 = -1, occw = -1, occ2s = -1, occ4s = -1;
+  FormMemo forms;                      // every launch form's LDS grant and residency on this handle's device (diffnet_forms.h)
   // two half-batches on two streams (dual_fork): the second stream and the events that fork and join it
   hipStream_t st2 = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   // ragged binding (bsg_diffnet_prepare_ragged, bound.ragged): every row of the bound (B, T) decoded at its own frame count
-  int occ_stack_varlen = -1;           // resident workgroups per CU of the ragged 16-row stack launch (-1: not queried)
-  int occ_stack_bf16_varlen = -1;      // the same for the ragged bf16 stack launch
   int* rg_dev = nullptr;               // [B rounded up to even] row lengths, then the tile tables {row, tile} of every launch group
   size_t rg_cap = 0;                   // ints rg_dev holds
   std::vector<int> rg_group_off;       // per launch group: offset of its table (in tiles) behind the lengths ...
@@ -1733,43 +1724,52 @@ static bool use_wino() { return dn_switches().wino != 0; }
 // that impossible.
 static constexpr size_t kSplitLds = 84 * 1024;
 
-static void query_split_occupancy(bsg_diffnet* h) {
-  const int lds = C * 48 * (int)sizeof(float);
-  auto occ_of = [](const void* fn, int threads, size_t bytes) {
-    int o = 0;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSplitLds) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, fn, threads, bytes) != hipSuccess)
-      return 0;
-    return o;
+// The fp32 per-layer launches.  LAYER_PLAIN: residual_layer_kernel<stamps, wino>, arguments (ResArgs a), 32-frame tiles: 48 KB of LDS -> 3
+// workgroups per CU.  (Wider tiles of 64 / 128 frames were built and measured in round 1: 0-50 % slower at every batch size, because fewer
+// workgroups per CU hide less of the L2 latency of the weight stream.)  The channel-split kernels, arguments (SplitArgs s): F(2,3) forms
+// without stamps; the pair / 4-way form at the padded LDS size (one workgroup per CU by construction) or, small_lds, at the plain size (two
+// chains share a CU); all of them are granted the padded size.
+const KernelForm* bsg::layer_form(LayerForm layer, bool small_lds, bool stamps, bool wino) {
+  constexpr size_t lds = (size_t)C * (32 + 2 * HALO) * sizeof(float);
+  static const KernelForm plain[] = {
+      {FORM_LAYER_DIRECT, (const void*)residual_layer_kernel<false, false>, nullptr, 512, lds, lds, "layer", nullptr},
+      {FORM_LAYER_DIRECT_STAMPS, (const void*)residual_layer_kernel<true, false>, nullptr, 512, lds, lds, "layer", nullptr},
+      {FORM_LAYER_WINO, (const void*)residual_layer_kernel<false, true>, nullptr, 512, lds, lds, "layer", nullptr},
+      {FORM_LAYER_WINO_STAMPS, (const void*)residual_layer_kernel<true, true>, nullptr, 512, lds, lds, "layer", nullptr},
   };
-  h->occ2 = occ_of((const void*)residual_split_kernel<false, 2>, 512, kSplitLds);
-  h->occ4 = occ_of((const void*)residual_split_kernel<false, 4>, 256, kSplitLds);
-  h->occ2s = occ_of((const void*)residual_split_kernel<false, 2>, 512, (size_t)lds);
-  h->occ4s = occ_of((const void*)residual_split_kernel<false, 4>, 256, (size_t)lds);
-  h->occw = occ_of((const void*)residual_split_kernel<true, 1>, 1024, (size_t)lds);
+  static const KernelForm split[] = {
+      {FORM_SPLIT2, (const void*)residual_split_kernel<false, 2>, nullptr, 512, kSplitLds, kSplitLds, "split2", nullptr},
+      {FORM_SPLIT2_SMALL, (const void*)residual_split_kernel<false, 2>, nullptr, 512, lds, kSplitLds, "split2", nullptr},
+      {FORM_SPLIT4, (const void*)residual_split_kernel<false, 4>, nullptr, 256, kSplitLds, kSplitLds, "split4", nullptr},
+      {FORM_SPLIT4_SMALL, (const void*)residual_split_kernel<false, 4>, nullptr, 256, lds, kSplitLds, "split4", nullptr},
+      {FORM_WIDE, (const void*)residual_split_kernel<true, 1>, nullptr, 1024, lds, kSplitLds, "wide", nullptr},
+  };
+  switch (layer) {
+    case LAYER_PLAIN: return &plain[2 * wino + stamps];
+    case LAYER_SPLIT2: return &split[small_lds];
+    case LAYER_SPLIT4: return &split[2 + small_lds];
+    case LAYER_WIDE: return &split[4];
+    default: return bf16_layer_form(stamps);
+  }
+}
+
+// step_tail_kernel<mp, plms>: skip projection, output projection, sampler update of x (DDPM, or PLMS) and the next evaluation's
+// in-projection.  Arguments (TailArgs a); one workgroup per 32-frame tile.
+const KernelForm* bsg::tail_f32_form(int mp, bool plms) {
+  constexpr size_t lds = (size_t)(C * 32 + 96 * 32) * sizeof(float);
+  static const KernelForm forms[] = {
+      {FORM_TAIL_F32_80, (const void*)step_tail_kernel<80, false>, nullptr, 512, lds, lds, "step_tail", nullptr},
+      {FORM_TAIL_F32_96, (const void*)step_tail_kernel<96, false>, nullptr, 512, lds, lds, "step_tail", nullptr},
+      {FORM_TAIL_F32_80_PLMS, (const void*)step_tail_kernel<80, true>, nullptr, 512, lds, lds, "step_tail", nullptr},
+      {FORM_TAIL_F32_96_PLMS, (const void*)step_tail_kernel<96, true>, nullptr, 512, lds, lds, "step_tail", nullptr},
+  };
+  return &forms[2 * plms + (mp != 80)];
 }
 
 // The launches of a call: which form runs the L residual layers, and how the batch splits into launch groups.  plan_stack() decides it
-// from the shape, the handle's state and what the plan is for (PlanScope), and writes nothing on the handle but its occupancy memos
-// (occ_*), so a query (bsg_diffnet_uses_handoffs, ragged_launch_ok) and the launch it predicts agree; every compute entry plans once and
-// hands the plan to the launches, which read nothing else about the call.
-enum StackForm {
-  STACK_NONE,   // no stack launch: one launch per layer (launch_layer), of the form in StackPlan::layer
-  STACK_F43,    // Winograd F(4,3) on the fp32 matrix pipe (diffnet_f43.hip)
-  STACK_H2,     // split-fp16, 32-row matrix tiles (residual_stack_h2_kernel, diffnet_h2.hip)
-  STACK_H2Q,    // split-fp16, 16-row matrix tiles (residual_stack_q_kernel, diffnet_h2q.hip)
-  STACK_PART,   // split-fp16 part form: several workgroups per tile (residual_part_h2_kernel, diffnet_h2.hip)
-  STACK_BF16,   // bf16-operand configuration (diffnet_bf16.hip)
-};
-
-enum LayerForm {   // (bsg_diffnet_last_path)
-  LAYER_PLAIN,    // "layer": residual_layer_kernel, one workgroup per 32-frame tile
-  LAYER_SPLIT2,   // "split2": residual_split_kernel<false, 2>, a pair of workgroups per tile, each half of the channels
-  LAYER_SPLIT4,   // "split4": residual_split_kernel<false, 4>
-  LAYER_WIDE,     // "wide": residual_split_kernel<true, 1>, one 16-wave workgroup per tile
-  LAYER_BF16,     // "bf16": bf16-operand configuration (launch_residual_layer_bf16)
-};
-
+// from the shape, the handle's state and what the plan is for (PlanScope), and writes nothing on the handle (what it asks of the device
+// is kept in h->forms, a memo), so a query (bsg_diffnet_uses_handoffs, ragged_launch_ok) and the launch it predicts agree; every compute
+// entry plans once and hands the plan to the launches, which read nothing else about the call.
 enum PlanScope {
   PLAN_WHOLE,        // the whole batch of a call
   PLAN_HALF_BIG,     // half of a batch of more tiles than CUs (dual_fork): per-layer launches of the one-workgroup-per-tile kernel
@@ -1779,37 +1779,36 @@ enum PlanScope {
 };
 
 struct StackPlan {
-  StackForm form = STACK_NONE;
-  int nct = 2;          // column tiles of 32 frames per workgroup: tiles of 32 * nct frames (F(4,3), bf16: 64)
-  int parts = 0;        // STACK_PART: workgroups per tile (4: quads, 2: pairs)
-  int rows = 0;         // rows per launch group
-  bool ragged = false;  // a ragged call: one launch per group of the plan bound by bsg_diffnet_prepare_ragged (rows = B)
-  bool tok = false;     // STACK_H2Q on 64-frame tiles behind a token binding: the launch gathers the conditioner term from the token table
-  LayerForm layer = LAYER_PLAIN;   // STACK_NONE: the form of the per-layer launches
+  const KernelForm* form = nullptr;   // the stack launch (diffnet_forms.h: its family, tile width, parts and variant); null: one launch per layer
+  int rows = 0;         // rows per launch group (a ragged call: one launch per group of the plan bound by bsg_diffnet_prepare_ragged, rows = B)
+  LayerForm layer = LAYER_PLAIN;   // no stack launch: the form of the per-layer launches
   bool small_lds = false;          // ... and the pair / 4-way form at the un-padded LDS size (PLAN_HALF_SMALL)
   int row0 = 0;         // the launches work on rows [row0, row0 + B) of the bound batch (the second half-batch chain of dual_fork)
+  StackForm family() const { return form ? form->family : STACK_NONE; }
+  int nct() const { return form ? form->nct : 2; }   // column tiles of 32 frames per workgroup: tiles of 32 * nct frames (F(4,3), bf16: 64)
+  bool ragged() const { return form && form->variant == FORM_RAGGED; }
+  bool tok() const { return form && form->variant == FORM_TOKEN; }   // the launch gathers the conditioner term from the token table
 };
 
 // the channel-split form of a per-layer launch of B x T (LAYER_PLAIN: none); small_lds: at the un-padded LDS size
-static LayerForm use_split(bsg_diffnet* h, int B, int T, bool small_lds) {
+static LayerForm use_split(const bsg_diffnet* h, int B, int T, bool small_lds) {
   const int env = dn_switches().split;
   if (!env || h->split_off || !h->num_cus || !h->zbuf) return LAYER_PLAIN;
   const long long tiles = (long long)B * cdiv(T, 32);
   if ((size_t)tiles > h->split_cap) return LAYER_PLAIN;
-  if (h->occ2 < 0) query_split_occupancy(h);
   // residency is what makes a hand-off terminate: every workgroup of the launch (and, for two chains sharing CUs, of both
   // launches: dual_scope checks that sum) must fit the device at the LDS size actually launched
-  const int o4 = small_lds ? h->occ4s : h->occ4, o2 = small_lds ? h->occ2s : h->occ2;
-  if (4 * tiles <= h->num_cus && env != 2 && o4 >= 1) return LAYER_SPLIT4;   // BSG_SPLIT=2: no 4-way split (A/B measurements)
-  if (2 * tiles <= h->num_cus) return o2 >= 1 ? LAYER_SPLIT2 : LAYER_PLAIN;
-  if (tiles <= h->num_cus && env != 3) return h->occw >= 1 ? LAYER_WIDE : LAYER_PLAIN;   // BSG_SPLIT=3: pair form only (A/B measurements)
+  auto fits = [&](LayerForm f) { return h->forms.resident(*layer_form(f, small_lds, false, true)) >= 1; };
+  if (4 * tiles <= h->num_cus && env != 2 && fits(LAYER_SPLIT4)) return LAYER_SPLIT4;   // BSG_SPLIT=2: no 4-way split (A/B measurements)
+  if (2 * tiles <= h->num_cus) return fits(LAYER_SPLIT2) ? LAYER_SPLIT2 : LAYER_PLAIN;
+  if (tiles <= h->num_cus && env != 3) return fits(LAYER_WIDE) ? LAYER_WIDE : LAYER_PLAIN;   // BSG_SPLIT=3: pair form only (A/B measurements)
   return LAYER_PLAIN;
 }
 
 // The per-layer launch of B x T rows: what a plan without a stack form runs, and all that the entries of ONE layer plan
 // (bsg_diffnet_residual_layer, bsg_diffnet_debug_stamps: they never take a stack launch).  The channel-split kernels are F(2,3) forms of
 // the fp32 configuration and carry no stamps; the half of a big batch keeps the one-workgroup-per-tile kernel.
-static void plan_layer(bsg_diffnet* h, StackPlan& plan, int B, int T, PlanScope scope, bool stamps = false) {
+static void plan_layer(const bsg_diffnet* h, StackPlan& plan, int B, int T, PlanScope scope, bool stamps = false) {
   plan.small_lds = scope == PLAN_HALF_SMALL;
   if (h->compute == BSG_COMPUTE_BF16) plan.layer = LAYER_BF16;
   else plan.layer = !stamps && use_wino() && scope != PLAN_HALF_BIG ? use_split(h, B, T, plan.small_lds) : LAYER_PLAIN;
@@ -1835,9 +1834,12 @@ static int launch_layer(bsg_diffnet* h, const StackPlan& plan, int layer, const 
   a.skip_div = layer == h->L - 1 ? sqrtf((float)h->L) : 1.0f;
   a.stamps = stamps;
   const LayerForm form = plan.layer;
+  const KernelForm& kf = *layer_form(form, plan.small_lds, stamps != nullptr, use_wino());
+  dim3 grid;
+  void* args[1] = {&a};
+  SplitArgs s{};
   if (form == LAYER_SPLIT2 || form == LAYER_SPLIT4 || form == LAYER_WIDE) {
     // small launch: a pair of workgroups per tile, each half of the channels (residual_split_kernel)
-    SplitArgs s{};
     a.tiles_per_row = cdiv(T, 32);
     s.base = a;
     s.apack2w = h->apack2w + (size_t)layer * 2 * C * C;
@@ -1849,76 +1851,47 @@ static int launch_layer(bsg_diffnet* h, const StackPlan& plan, int layer, const 
     if (++h->split_epoch == 0) h->split_epoch = 1;
     s.epoch = h->split_epoch;
     if (h->inject_giveup > 0 && form != LAYER_WIDE) { s.inject = 1; --h->inject_giveup; }
-    const size_t slds = plan.small_lds ? (size_t)C * 48 * sizeof(float) : kSplitLds;
-    if (form == LAYER_WIDE) hipLaunchKernelGGL((residual_split_kernel<true, 1>), dim3(B * a.tiles_per_row), dim3(1024), (size_t)C * 48 * sizeof(float), st, s);
-    else if (form == LAYER_SPLIT4) hipLaunchKernelGGL((residual_split_kernel<false, 4>), dim3(4 * B * a.tiles_per_row), dim3(256), slds, st, s);
-    else hipLaunchKernelGGL((residual_split_kernel<false, 2>), dim3(2 * B * a.tiles_per_row), dim3(512), slds, st, s);
-    BSG_LAUNCH_CHECK();
-    h->last_path = form == LAYER_WIDE ? "wide" : form == LAYER_SPLIT4 ? "split4" : "split2";
-    h->last_groups = 0;
-    return BSG_OK;
+    args[0] = &s;
+    grid = dim3((form == LAYER_WIDE ? 1 : form == LAYER_SPLIT4 ? 4 : 2) * B * a.tiles_per_row);
+  } else {
+    a.tiles_per_row = cdiv(T, form == LAYER_BF16 ? 64 : 32);
+    grid = dim3(8 * cdiv(B * a.tiles_per_row, 8));   // see the tile order in residual_layer_kernel / residual_layer_bf16_kernel
   }
+  const bool ext = form == LAYER_BF16 && skip != h->skip + (size_t)plan.row0 * C * T;
   if (form == LAYER_BF16) {
     // the running skip sum lives in h->skip_h (bf16); a caller-supplied fp32 buffer (the unit-test hook) is converted
     // in and out around the launch
     a.condterm_h = h->condterm_h + ((size_t)layer * h->bound.B + plan.row0) * 2 * C * (size_t)T;
     a.skip_h = h->skip_h + (size_t)plan.row0 * C * T;
-    const bool ext = skip != h->skip + (size_t)plan.row0 * C * T;
     if (ext && !a.first) TRY(f32_to_quad_bf16(skip, h->skip_h, B, C, T, st));
-    TRY(launch_residual_layer_bf16(a, st));
-    h->last_path = "bf16";
-    h->last_groups = 0;
-    if (ext) TRY(quad_bf16_to_f32(h->skip_h, skip, B, C, T, st));
-    return BSG_OK;
   }
-  // 32-frame tiles: 48 KB of LDS -> 3 workgroups per CU.  (Wider tiles of 64 / 128 frames were built and
-  // measured in round 1: 0-50 % slower at every batch size, because fewer workgroups per CU hide less of the
-  // L2 latency of the weight stream.)
-  a.tiles_per_row = cdiv(T, 32);
-  const dim3 grid(8 * cdiv(B * a.tiles_per_row, 8)), block(512);   // see the tile order in residual_layer_kernel
-  const size_t lds = (size_t)C * (32 + 2 * HALO) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    BSG_HIP(hipFuncSetAttribute((const void*)residual_layer_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    BSG_HIP(hipFuncSetAttribute((const void*)residual_layer_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    BSG_HIP(hipFuncSetAttribute((const void*)residual_layer_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    BSG_HIP(hipFuncSetAttribute((const void*)residual_layer_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
-  if (use_wino()) {
-    if (stamps) hipLaunchKernelGGL((residual_layer_kernel<true, true>), grid, block, lds, st, a);
-    else hipLaunchKernelGGL((residual_layer_kernel<false, true>), grid, block, lds, st, a);
-  } else {
-    if (stamps) hipLaunchKernelGGL((residual_layer_kernel<true, false>), grid, block, lds, st, a);
-    else hipLaunchKernelGGL((residual_layer_kernel<false, false>), grid, block, lds, st, a);
-  }
-  BSG_LAUNCH_CHECK();
-  h->last_path = "layer";
+  TRY(launch_form(h->forms, kf, false, grid, args, st));
+  h->last_path = kf.name;
   h->last_groups = 0;
-  return BSG_OK;
+  return ext ? quad_bf16_to_f32(h->skip_h, skip, B, C, T, st) : BSG_OK;
 }
 
 // A tile row is ceil(T / (32 nct)) workgroups that wait for each other, and every workgroup of a launch must be resident: at most
 // occ x CUs workgroups, whole rows only.  It pays when a launch has more workgroups than CUs (two per CU overlap each other's waits);
 // smaller launches keep the channel-split kernels.  `ragged`: the ragged stack launch of the bound batch (bsg_diffnet_prepare_ragged), if
-// the handle's state has one.  Leaves plan.form = STACK_NONE where no stack launch runs.
-static void stack_form(bsg_diffnet* h, StackPlan& plan, int B, int T, hipStream_t st, bool ragged) {
+// the handle's state has one.  Leaves plan.form null where no stack launch runs.
+static void stack_form(const bsg_diffnet* h, StackPlan& plan, int B, int T, hipStream_t st, bool ragged) {
   const DnSwitches& sw = dn_switches();
+  const bool exchange = !h->split_off && h->num_cus && h->hx && h->epoch_dev;   // hand-off launches are on, and prepare has allocated their edge exchange
+  auto fits = [&](const KernelForm* f) { return f && h->forms.resident(*f) >= 1; };
   if (h->compute == BSG_COMPUTE_BF16) {
     // bf16-operand configuration: the stack launch (the default; BSG_STACK_BF16=0 selects per-layer launches).  64-frame tiles, one
     // workgroup per CU (256 registers per wave), whole rows per launch group.  Measured on one box, ms per 100-step pass at T=1000,
     // stack / per-layer: B=1 43.2 / 56.4, B=16 58.2 / 87.8, B=32 109.7 / 133.3, B=64 213.8 / 237.3 (tools/bench_small.py with
     // BSG_DTYPE=bf16).  Per layer and tile ~21.5 us, of which the two GEMMs' MFMAs are ~7.  Whether it is taken
     // does not depend on B.
-    if (!sw.stack_bf16 || h->split_off || !h->num_cus || !h->hx || !h->epoch_dev) return;
-    if (h->occ_stack_h < 0) h->occ_stack_h = stack_bf16_occupancy() >= 1 ? 1 : 0;
+    if (!sw.stack_bf16 || !exchange || !fits(bf16_stack_form(false))) return;
     const int tpr = cdiv(T, 64);
-    const long long slots = (long long)h->occ_stack_h * h->num_cus;
+    const long long slots = h->num_cus;
     if (ragged) {   // residual_stack_bf16_varlen_kernel: groups from the bound plan
-      if (h->occ_stack_bf16_varlen < 0) h->occ_stack_bf16_varlen = stack_bf16_varlen_occupancy() >= 1 ? 1 : 0;
-      if (h->occ_stack_h >= 1 && h->occ_stack_bf16_varlen >= 1) { plan.form = STACK_BF16; plan.rows = B; plan.ragged = true; }
-    } else if (h->occ_stack_h >= 1 && tpr <= slots) {
-      plan.form = STACK_BF16;
+      if (fits(bf16_stack_form(true))) { plan.form = bf16_stack_form(true); plan.rows = B; }
+    } else if (tpr <= slots) {
+      plan.form = bf16_stack_form(false);
       plan.rows = slots / tpr < B ? (int)(slots / tpr) : B;
     }
     return;
@@ -1927,10 +1900,9 @@ static void stack_form(bsg_diffnet* h, StackPlan& plan, int B, int T, hipStream_
     // the ragged form of the 16-row launch on 64-frame tiles, groups from the bound plan.  Not on a handle that was demoted off the 16-row
     // launch (bsg_diffnet_set_h2q / set_h2 / set_split 0, or the process switches BSG_H2 / BSG_H2_Q = 0), and it reads the conditioner
     // term's channel quads only
-    if (sw.h2 && sw.h2_q && !h->h2_off && !h->q_off && !h->split_off && h->num_cus && h->hx && h->epoch_dev && h->apack1q && h->apack2q &&
-        h->dconv && h->bound.quads) {
-      if (h->occ_stack_varlen < 0) h->occ_stack_varlen = stack_h2q_varlen_occupancy() >= 1 ? 1 : 0;
-      if (h->occ_stack_varlen >= 1) { plan.form = STACK_H2Q; plan.rows = B; plan.ragged = true; }
+    if (sw.h2 && sw.h2_q && !h->h2_off && !h->q_off && exchange && h->apack1q && h->apack2q && h->dconv && h->bound.quads) {
+      const KernelForm* f = h2q_form(2, FORM_RAGGED, true, 0);
+      if (fits(f)) { plan.form = f; plan.rows = B; }
     }
     return;
   }
@@ -1940,7 +1912,7 @@ static void stack_form(bsg_diffnet* h, StackPlan& plan, int B, int T, hipStream_
     // (round 4: the launch epoch of the flags lives in device memory, so these launches can be captured and replayed; only the part forms'
     // exchange buffers must exist already — their first eager call allocates them)
     const bool capturing = is_capturing(st);
-    if (sw.h2 && !h->h2_off && h->compute == BSG_COMPUTE_F32 && !h->split_off && h->num_cus && h->hx && h->apack1s && h->epoch_dev) {
+    if (sw.h2 && !h->h2_off && h->compute == BSG_COMPUTE_F32 && exchange && h->apack1s) {
       // tile width: 32 frames (one column tile per workgroup) while those tiles fit ONE launch group, else 64 frames (two column tiles:
       // half the weight stream per frame).  ms per 100-step pass at T = 1000 on one box (tools/bench_small.py), 32-frame / 64-frame /
       // fp32-pipe kernels (BSG_H2=0):  B=1 55 / 70 / 60,  B=2 53 / 70 / 64,  B=4 52 / 70 / 84,  B=6 56 / 74 / 119,  B=8 69 / 76 / 132,
@@ -1956,12 +1928,9 @@ static void stack_form(bsg_diffnet* h, StackPlan& plan, int B, int T, hipStream_
         // B * ceil(T / 64) <= CUs / 2 (B <= 8).  ms per 100-step pass at T = 1000, one workgroup per tile / part form: B=1 54.5 / 24.1,
         // B=2 52.6 / 25.4, B=3 52.0 / 32.0, B=4 51.5 / 35.0, B=5 54.8 / 46.0, B=6 57.1 / 49.6, B=8 69.1 / 59.4.  BSG_H2_PART=0: none
         // (BSG_H2_QUAD=0 / BSG_H2_QUAD64=0 / BSG_H2_PAIR64=0: not that form)
-        // occ_part: [1] / [2] quads of 32- / 64-frame tiles, [0] pairs of 64-frame tiles
         auto part = [&](int parts, int pn) {
-          int& occ = h->occ_part[parts == 4 ? pn : 0];
-          if (occ < 0) occ = part_h2_occupancy(parts, pn) >= 1 ? 1 : 0;
-          if (occ < 1) return false;
-          plan.form = STACK_PART; plan.parts = parts; plan.nct = pn; plan.rows = B;
+          if (!fits(part_form(parts, pn))) return false;
+          plan.form = part_form(parts, pn); plan.rows = B;
           return true;
         };
         const long long t32 = (long long)B * cdiv(T, 32), t64 = (long long)B * cdiv(T, 64);
@@ -1974,22 +1943,14 @@ static void stack_form(bsg_diffnet* h, StackPlan& plan, int B, int T, hipStream_
       }
       // 16-row matrix tiles (residual_stack_q_kernel, diffnet_h2q.hip; round 5): the same launch with every product a v_mfma_f32_16x16x32_f16 —
       // the same matrix cycles, but the chip holds a higher clock under that shape.  BSG_H2_Q=0: the 32-row form (residual_stack_h2_kernel)
-      bool q = false;
-      if (sw.h2_q && !h->q_off && h->apack1q && h->apack2q) {
-        if (h->occ_stack_h2q[nct] < 0) h->occ_stack_h2q[nct] = stack_h2q_occupancy(nct) >= 1 ? 1 : 0;
-        q = h->occ_stack_h2q[nct] >= 1;
-      }
-      if (!q && h->occ_stack_h2[nct] < 0) h->occ_stack_h2[nct] = stack_h2_occupancy(nct) >= 1 ? 1 : 0;
+      // (the form launched is the one BSG_H2Q_FAIR / BSG_H2Q_DIAG select; whether the 16-row launch fits is asked of its default form)
+      const bool q = sw.h2_q && !h->q_off && h->apack1q && h->apack2q && fits(h2q_form(nct, FORM_PLAIN, true, 0));
       const int tpr = cdiv(T, 32 * nct);
-      if ((q || h->occ_stack_h2[nct] >= 1) && tpr <= h->num_cus) {
-        plan.form = q ? STACK_H2Q : STACK_H2;
-        plan.nct = nct;
+      if ((q || fits(h2_form(nct))) && tpr <= h->num_cus) {
+        plan.form = q ? h2q_form(nct, FORM_PLAIN, sw.h2q_fair != 0, sw.h2q_diag) : h2_form(nct);
         plan.rows = h->num_cus / tpr < B ? h->num_cus / tpr : B;
         // the token form: a token binding, the 16-row launch at 64-frame tiles (BSG_COND_TOK=0: the expanded per-frame term instead)
-        if (q && nct == 2 && h->bound.tok && sw.cond_tok) {
-          if (h->occ_stack_tok < 0) h->occ_stack_tok = stack_h2q_tok_occupancy() >= 1 ? 1 : 0;
-          plan.tok = h->occ_stack_tok >= 1;
-        }
+        if (q && nct == 2 && h->bound.tok && sw.cond_tok && fits(h2q_form(2, FORM_TOKEN, true, 0))) plan.form = h2q_form(2, FORM_TOKEN, true, 0);
         return;
       }
     }
@@ -1999,14 +1960,13 @@ static void stack_form(bsg_diffnet* h, StackPlan& plan, int B, int T, hipStream_
     // launches.  A launch group takes the same time whatever part of the chip it fills, so the form is taken when the groups are
     // >= 90 % full (B = 15, 16, 29..32, .. at T = 1000): it is ~6 % faster than two chains of per-layer F(2,3) launches, not more.
     const int env43 = sw.stack43;
-    if (env43 && h->compute == BSG_COMPUTE_F32 && !h->split_off && h->num_cus && h->hx && h->epoch_dev) {
-      if (h->occ_stack43 < 0) h->occ_stack43 = stack_f43_occupancy() >= 1 ? 1 : 0;
+    if (env43 && h->compute == BSG_COMPUTE_F32 && exchange) {
       const int tpr43 = cdiv(T, 64);
-      if (h->occ_stack43 >= 1 && tpr43 <= h->num_cus) {
+      if (fits(f43_form()) && tpr43 <= h->num_cus) {
         const int rows43 = h->num_cus / tpr43 < B ? h->num_cus / tpr43 : B;
         const int groups = cdiv(B, rows43);
         if (env43 == 2 || (long long)B * tpr43 * 10 >= (long long)groups * h->num_cus * 9) {   // BSG_STACK43=2: any shape (tests)
-          plan.form = STACK_F43;
+          plan.form = f43_form();
           plan.rows = rows43;
         }
       }
@@ -2014,23 +1974,11 @@ static void stack_form(bsg_diffnet* h, StackPlan& plan, int B, int T, hipStream_
   }
 }
 
-static StackPlan plan_stack(bsg_diffnet* h, int B, int T, hipStream_t st, PlanScope scope = PLAN_WHOLE) {
+static StackPlan plan_stack(const bsg_diffnet* h, int B, int T, hipStream_t st, PlanScope scope = PLAN_WHOLE) {
   StackPlan plan;
   if (scope != PLAN_HALF_BIG) stack_form(h, plan, B, T, st, scope == PLAN_RAGGED);
-  if (plan.form == STACK_NONE && scope != PLAN_RAGGED) plan_layer(h, plan, B, T, scope);
+  if (!plan.form && scope != PLAN_RAGGED) plan_layer(h, plan, B, T, scope);
   return plan;
-}
-
-// bsg_diffnet_last_path of a stack launch
-static const char* stack_path(const StackPlan& plan, bool tail) {
-  switch (plan.form) {
-    case STACK_F43: return "stack_f43";
-    case STACK_H2: return tail ? "stack_h2_tail" : "stack_h2";
-    case STACK_H2Q: return plan.tok ? (tail ? "stack_h2q_tok_tail" : "stack_h2q_tok") : plan.ragged ? (tail ? "stack_h2q_ragged_tail" : "stack_h2q_ragged") : tail ? "stack_h2q_tail" : "stack_h2q";
-    case STACK_PART: return plan.parts == 2 ? "stack_h2_pair64" : plan.nct == 2 ? "stack_h2_quad64" : "stack_h2_quad";
-    case STACK_BF16: return plan.ragged ? "stack_bf16_ragged" : "stack_bf16";
-    default: return "none";
-  }
 }
 
 // The arguments of launch group g: rows [r0, r0 + nb) of this call's batch (r0 = g x plan.rows), or group g of the bound ragged plan —
@@ -2042,8 +1990,8 @@ static const char* stack_path(const StackPlan& plan, bool tail) {
 // smaller batches), zeroes the flags and starts the epochs again (diffnet_res.h).
 static int stack_args(bsg_diffnet* h, const StackPlan& plan, int g, const long long* t_dev, int t_uniform, int B, int T, hipStream_t st,
                       unsigned long long* stamps, StackArgs& p) {
-  const int tpr = cdiv(T, 32 * plan.nct);
-  const int r0 = plan.ragged ? 0 : g * plan.rows;
+  const int tpr = cdiv(T, 32 * plan.nct());
+  const int r0 = plan.ragged() ? 0 : g * plan.rows;
   const int nb = B - r0 < plan.rows ? B - r0 : plan.rows;
   const size_t row = (size_t)plan.row0 + r0;
   p = StackArgs{};
@@ -2053,7 +2001,7 @@ static int stack_args(bsg_diffnet* h, const StackPlan& plan, int g, const long l
   p.bias_out = h->b_out;
   p.T = T; p.L = h->L; p.tiles_per_row = tpr;
   p.ct_stride = (long long)2 * C * h->bound.B * T;   // bound batch: per-layer stride of the conditioner term
-  p.n_tiles = plan.ragged ? h->rg_group_tiles[g] : nb * tpr; p.cycle = h->cfg.dilation_cycle_length;
+  p.n_tiles = plan.ragged() ? h->rg_group_tiles[g] : nb * tpr; p.cycle = h->cfg.dilation_cycle_length;
   BSG_REQUIRE((size_t)p.n_tiles <= h->flags_cap && h->L < 64, "stack launch: %d tiles exceed the exchange array (%zu)", p.n_tiles, h->flags_cap);
   p.hx = h->hx; p.flags = h->flags; p.status = h->flags + h->flags_cap;
   BSG_REQUIRE(h->epoch_dev, "stack launch: no launch epoch (bsg_diffnet_prepare allocates it)");
@@ -2065,17 +2013,17 @@ static int stack_args(bsg_diffnet* h, const StackPlan& plan, int g, const long l
   p.wrap_pflags = h->part_flags;
   p.wrap_pflag_words = h->part_flags ? (int)(2 * h->part_cap * 4) : 0;
   if (dn_switches().debug_wrap_r04) { p.wrap_pflags = nullptr; p.wrap_pflag_words = 0; }
-  const bool part = plan.form == STACK_PART;
+  const bool part = plan.family() == STACK_PART;
   if (h->inject_giveup > 0) { p.inject = 1; --h->inject_giveup; }
   else if (h->inject_xcc > 0 && part) { p.inject = 2; --h->inject_xcc; }
   else if (h->inject_nowait > 0 && part) { p.inject = 3; --h->inject_nowait; }
   p.stamps = stamps && g == 0 ? stamps : nullptr;
   p.clk = h->prof_on && g == 0 ? h->clk : nullptr;
-  if (plan.ragged) {
+  if (plan.ragged()) {
     p.vl_len = h->rg_dev;
     p.vl_tiles = reinterpret_cast<const int2*>(h->rg_dev + ((h->bound.B + 1) & ~1)) + h->rg_group_off[g];   // the tables follow the lengths
   }
-  if (plan.form == STACK_BF16) {
+  if (plan.family() == STACK_BF16) {
     p.skip_h = h->skip_h + row * C * T;
     p.condterm_h = h->condterm_h + row * 2 * C * T;
     p.apack1h = h->apack1h; p.apack2h = h->apack2h;
@@ -2084,15 +2032,16 @@ static int stack_args(bsg_diffnet* h, const StackPlan& plan, int g, const long l
   p.condterm = h->condterm + row * 2 * C * T;
   p.dconv = h->dconv; p.apackw = h->apackw; p.apack2 = h->apack2;
   if (stamps) p.stamp_mode = live_stamp_mode();
-  if (plan.form == STACK_F43) {
+  if (plan.family() == STACK_F43) {
     p.apackw43 = h->apackw43;
     return BSG_OK;
   }
   p.apack1s = h->apack1s; p.apack2s = h->apack2s; p.h2_scale = h->h2_scale;
   p.apack1q = h->apack1q; p.apack2q = h->apack2q;
-  p.condterm_q = plan.form != STACK_H2 && h->bound.quads ? h->condterm_q + row * 2 * C * T : nullptr;
-  if (plan.tok) {
-    BSG_REQUIRE(h->bound.tok && h->cond_tok && h->tok_dev && plan.form == STACK_H2Q, "stack launch: no token binding");
+  p.condterm_q = plan.family() != STACK_H2 && h->bound.quads ? h->condterm_q + row * 2 * C * T : nullptr;
+  if (plan.family() == STACK_H2Q) BSG_REQUIRE(p.apack1q && p.apack2q && p.dconv, "16-row stack launch: the 16-row weight fragments / the step-term table are missing");
+  if (plan.tok()) {
+    BSG_REQUIRE(h->bound.tok && h->cond_tok && h->tok_dev && h->bound.K > 0, "stack launch: no token binding");
     p.condterm_q = h->cond_tok + row * 2 * C * h->bound.K;
     p.ct_stride = (long long)2 * C * h->bound.B * h->bound.K;
     p.tok = h->tok_dev + row * T;
@@ -2100,8 +2049,9 @@ static int stack_args(bsg_diffnet* h, const StackPlan& plan, int g, const long l
   }
   if (part) {
     // the exchange buffers for this launch's 32-frame tile equivalents, at least one per CU; a shape's first eager call allocates them
-    TRY(grow(h, &h->part_cap, std::max((size_t)h->num_cus, (size_t)p.n_tiles * plan.nct), st, GROW_LAZY));
+    TRY(grow(h, &h->part_cap, std::max((size_t)h->num_cus, (size_t)p.n_tiles * plan.nct()), st, GROW_LAZY));
     p.zx = h->part_zx; p.ix = h->part_ix; p.pflags = h->part_flags;
+    BSG_REQUIRE(p.zx && p.ix && p.hx && p.pflags && p.apack1q && p.apack2q, "part launch: exchange buffers / 16-row weight fragments missing");
     p.pflag_words = (int)(2 * h->part_cap * 4);
     p.wrap_pflags = h->part_flags; p.wrap_pflag_words = p.pflag_words;   // (also under BSG_DEBUG_WRAP_R04: a part launch always zeroed its own)
   }
@@ -2121,26 +2071,22 @@ static TailArgs tail_rows(TailArgs a, size_t r) {
 // step's tail in the same launch (split-fp16 forms)
 static int launch_stack(bsg_diffnet* h, const StackPlan& plan, const long long* t_dev, int t_uniform, int B, int T, hipStream_t st,
                         unsigned long long* stamps = nullptr, const TailArgs* tail = nullptr) {
-  BSG_REQUIRE(plan.form != STACK_NONE && plan.rows > 0, "stack launch: no launch form selected");
-  BSG_REQUIRE(!tail || plan.form == STACK_H2 || plan.form == STACK_H2Q, "stack launch: a fused tail needs the split-fp16 form");
-  BSG_REQUIRE(plan.form != STACK_PART || (!tail && plan.rows >= B), "part launch: whole batch, no fused tail");
-  BSG_REQUIRE(!plan.ragged || (h->bound.ragged && h->rg_dev && plan.row0 == 0 && (plan.form == STACK_BF16 || h->bound.quads)),
+  BSG_REQUIRE(plan.form && plan.rows > 0, "stack launch: no launch form selected");
+  const KernelForm& f = *plan.form;
+  BSG_REQUIRE(!tail || f.fn_tail, "stack launch: a fused tail needs the split-fp16 form");
+  BSG_REQUIRE(f.family != STACK_PART || plan.rows >= B, "part launch: whole batch");
+  BSG_REQUIRE(!plan.ragged() || (h->bound.ragged && h->rg_dev && plan.row0 == 0 && (f.family == STACK_BF16 || h->bound.quads)),
               "ragged stack launch: no ragged plan / conditioner quads bound");
-  const int groups = plan.ragged ? (int)h->rg_group_tiles.size() : cdiv(B, plan.rows);
+  const int groups = plan.ragged() ? (int)h->rg_group_tiles.size() : cdiv(B, plan.rows);
   for (int g = 0; g < groups; ++g) {
     StackArgs p;
     TRY(stack_args(h, plan, g, t_dev, t_uniform, B, T, st, stamps, p));
     // the step tail in the same launch: its tensors start at this launch group's first row
-    const TailArgs a = tail ? tail_rows(*tail, plan.ragged ? 0 : (size_t)g * plan.rows) : TailArgs{};
-    switch (plan.form) {
-      case STACK_F43: TRY(launch_residual_stack_f43(p, st)); break;
-      case STACK_H2: TRY(launch_residual_stack_h2(p, tail ? &a : nullptr, st, plan.nct)); break;
-      case STACK_H2Q: TRY(launch_residual_stack_h2q(p, tail ? &a : nullptr, st, plan.nct)); break;
-      case STACK_PART: TRY(launch_residual_part_h2(p, st, plan.parts, plan.nct)); break;
-      default: TRY(launch_residual_stack_bf16(p, st)); break;
-    }
+    TailArgs a = tail ? tail_rows(*tail, plan.ragged() ? 0 : (size_t)g * plan.rows) : TailArgs{};
+    void* args[] = {&p, &a};   // (the forms without a tail instantiation take p alone)
+    TRY(launch_form(h->forms, f, tail != nullptr, dim3(8 * (f.parts ? f.parts : 1) * cdiv(p.n_tiles, 8)), args, st));
   }
-  h->last_path = stack_path(plan, tail != nullptr);
+  h->last_path = tail ? f.name_tail : f.name;
   h->last_groups = groups;
   return BSG_OK;
 }
@@ -2183,10 +2129,10 @@ static TailPlan plan_tail(const bsg_diffnet* h, const StackPlan& plan) {
   TailPlan tp;
   tp.mp = h->MP;
   if (!h->ws_pack || (tp.mp != 80 && tp.mp != 96) || live_no_fused_tail()) return tp;
-  const bool h2 = h->tail_s && h->M <= 96 && (plan.ragged || dn_switches().h2_tail);
-  if (h2 && (plan.form == STACK_H2 || plan.form == STACK_H2Q)) { tp.form = TAIL_IN_STACK; tp.tile = 64; }
-  else if (h2 && plan.form == STACK_PART) tp.form = TAIL_H2;
-  else if (h->compute == BSG_COMPUTE_BF16 && live_tail_bf16() && h->tail_h) tp.form = plan.ragged ? TAIL_BF16_RAGGED : TAIL_BF16;
+  const bool h2 = h->tail_s && h->M <= 96 && (plan.ragged() || dn_switches().h2_tail);
+  if (h2 && (plan.family() == STACK_H2 || plan.family() == STACK_H2Q)) { tp.form = TAIL_IN_STACK; tp.tile = 64; }
+  else if (h2 && plan.family() == STACK_PART) tp.form = TAIL_H2;
+  else if (h->compute == BSG_COMPUTE_BF16 && live_tail_bf16() && h->tail_h) tp.form = plan.ragged() ? TAIL_BF16_RAGGED : TAIL_BF16;
   else tp.form = TAIL_F32;
   tp.first_h2 = tp.form == TAIL_IN_STACK || tp.form == TAIL_H2;
   return tp;
@@ -2195,11 +2141,11 @@ static TailPlan plan_tail(const bsg_diffnet* h, const StackPlan& plan) {
 // Can the handle's CURRENT state decode the bound ragged batch with the ragged launch?  When its ragged plan has a stack launch
 // (stack_form: the conditions of the launch itself) and the tail that launch needs (plan_tail): in the fp32 configuration the one inside
 // the launch, in the bf16 configuration the ragged bf16 step tail.  (The callers otherwise decode the rows one by one.)
-static bool ragged_launch_ok(bsg_diffnet* h) {
+static bool ragged_launch_ok(const bsg_diffnet* h) {
   if (!h->bound.ragged || h->bound.compute != h->compute) return false;
   const StackPlan plan = plan_stack(h, h->bound.B, h->bound.T, nullptr, PLAN_RAGGED);
   const TailForm tail = plan_tail(h, plan).form;
-  return plan.form != STACK_NONE && (tail == TAIL_IN_STACK || tail == TAIL_BF16_RAGGED);
+  return plan.family() != STACK_NONE && (tail == TAIL_IN_STACK || tail == TAIL_BF16_RAGGED);
 }
 
 // entry of a compute call on a ragged binding: refused under stream capture and where the handle has no ragged launch
@@ -2220,12 +2166,12 @@ static int ragged_enter(bsg_diffnet* h, hipStream_t st, const char* who) {
 // the bf16 launches the bf16 quads; everything else — 32-row launch, F(4,3), per-layer and channel-split kernels — the rows.)
 static bool cond_rows_needed(const bsg_diffnet* h, const StackPlan& plan) {
   if (h->bound.quads_h) return false;
-  return !((plan.form == STACK_H2Q || plan.form == STACK_PART) && h->bound.quads);
+  return !((plan.family() == STACK_H2Q || plan.family() == STACK_PART) && h->bound.quads);
 }
 // (behind a token binding: nothing for the token form, the expanded quads for the other launches that read quads, the rows for the rest)
 static int cond_layout_for(bsg_diffnet* h, const StackPlan& plan, hipStream_t st) {
-  if (plan.tok) return BSG_OK;
-  if (h->bound.tok && (plan.form == STACK_H2Q || plan.form == STACK_PART)) TRY(ensure_cond_quads(h, st));
+  if (plan.tok()) return BSG_OK;
+  if (h->bound.tok && (plan.family() == STACK_H2Q || plan.family() == STACK_PART)) TRY(ensure_cond_quads(h, st));
   return cond_rows_needed(h, plan) ? ensure_cond_rows(h, st) : BSG_OK;
 }
 
@@ -2235,7 +2181,7 @@ static int run_layers(bsg_diffnet* h, const StackPlan& plan, const long long* t_
                       const TailArgs* tail = nullptr) {
   const bool prof = h->prof_on && h->prof_used + 2 <= h->prof_ev.size();
   if (prof) BSG_HIP(hipEventRecord(h->prof_ev[h->prof_used], st));
-  if (plan.form != STACK_NONE) {
+  if (plan.family() != STACK_NONE) {
     TRY(launch_stack(h, plan, t_dev, t_uniform, B, T, st, nullptr, tail));
   } else {
     const size_t off = (size_t)plan.row0 * C * T;
@@ -2260,13 +2206,13 @@ static int forward_impl(bsg_diffnet* h, const StackPlan& plan, const float* x, c
   TRY(conv1x1(h->w_in, h->b_in, x, h->xa, C, h->M, B, T, ACT_RELU, st));  // net.py:116-118
   TRY(run_layers(h, plan, t_dev, t_uniform, B, T, st));
   if (h->compute == BSG_COMPUTE_BF16) TRY(quad_bf16_to_f32(h->skip_h, h->skip, B, C, T, st));
-  if (plan.ragged) {   // ragged: the stack launch stored no skip sum at a row's padding; the projections below read every frame of B x T
+  if (plan.ragged()) {   // ragged: the stack launch stored no skip sum at a row's padding; the projections below read every frame of B x T
     hipLaunchKernelGGL(ragged_zero_pad_kernel, dim3(cdiv(T, 256), C, B), dim3(256), 0, st, h->skip, (const int*)h->rg_dev, C, T);
     BSG_LAUNCH_CHECK();
   }
   TRY(conv1x1(h->w_skip, h->b_skip, h->skip, h->hid, C, C, B, T, ACT_RELU, st));   // net.py:127-128
   TRY(conv1x1(h->w_fin, h->b_fin, h->hid, eps, h->M, C, B, T, ACT_NONE, st));      // net.py:129
-  if (plan.ragged) {   // ragged: the projections above ran on every frame of B x T; the padding's eps is 0
+  if (plan.ragged()) {   // ragged: the projections above ran on every frame of B x T; the padding's eps is 0
     hipLaunchKernelGGL(ragged_zero_pad_kernel, dim3(cdiv(T, 256), h->M, B), dim3(256), 0, st, eps, (const int*)h->rg_dev, h->M, T);
     BSG_LAUNCH_CHECK();
   }
@@ -2330,17 +2276,10 @@ static SubBatch sub_batch(const bsg_diffnet* h, const StackPlan& plan, float* x,
   return sub;
 }
 
-// step_tail_kernel: skip projection, output projection, sampler update of x (DDPM, or PLMS when a.plms_hist > 0) and the next
-// evaluation's in-projection into h->xa
-static int launch_tail(const TailPlan& tp, const TailArgs& a, hipStream_t st) {
-  void (*const kern[4])(TailArgs) = {step_tail_kernel<80, false>, step_tail_kernel<96, false>, step_tail_kernel<80, true>, step_tail_kernel<96, true>};
-  const size_t tail_lds = (size_t)(C * 32 + 96 * 32) * sizeof(float);
-  static bool tail_attr = false;
-  for (int i = 0; i < 4 && !tail_attr; ++i) BSG_HIP(hipFuncSetAttribute((const void*)kern[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)tail_lds));
-  tail_attr = true;
-  hipLaunchKernelGGL(kern[2 * (a.plms_hist != 0) + (tp.mp != 80)], dim3(a.B * a.tiles_per_row), dim3(512), tail_lds, st, a);
-  BSG_LAUNCH_CHECK();
-  return BSG_OK;
+// a launch of its own in front of or behind the stack: `a` (TailArgs) on `grid` workgroups, and whatever else the form takes behind it
+static int launch_step(const bsg_diffnet* h, const KernelForm* f, TailArgs a, int grid, hipStream_t st, const void* arg1 = nullptr, const void* arg2 = nullptr) {
+  void* args[] = {&a, &arg1, &arg2};
+  return launch_form(h->forms, *f, false, dim3(grid), args, st);
 }
 
 // The input projection of a DDPM call's first evaluation, the chain's rows of x into h->xa (TailPlan::first_h2).
@@ -2348,27 +2287,33 @@ static int first_in_projection(bsg_diffnet* h, const SubBatch& sub) {
   TailArgs a = tail_rows(sub.args, sub.plan.row0);
   if (!sub.tail.first_h2) return conv1x1(h->w_in, h->b_in, a.x, a.xa_next, C, h->M, a.B, a.T, ACT_RELU, sub.st);
   a.tiles_per_row = cdiv(a.T, 32);   // one workgroup per 32-frame tile, also in front of the stack launch's 64-frame tails
-  return launch_in_proj_h2(a, sub.st);
+  BSG_REQUIRE(a.x && a.xa_next && a.b_in && a.wi_s && a.tail_scale && a.M <= 96, "split-fp16 input projection: fragments missing or in_dims > 96");
+  return launch_step(h, h2_step_form(true), a, a.B * a.tiles_per_row, sub.st);
 }
 
 // One sampler step of a chain from the in-projected x in h->xa: the residual stack, then the tail in the chain's form.  `step`: sub.args
 // with the sampler's own fields set, at the call's row 0.
 static int run_step(bsg_diffnet* h, const SubBatch& sub, int t_uniform, const TailArgs& step) {
-  const TailArgs a = tail_rows(step, sub.plan.row0);
+  TailArgs a = tail_rows(step, sub.plan.row0);
   if (sub.tail.form == TAIL_IN_STACK) return run_layers(h, sub.plan, nullptr, t_uniform, a.B, a.T, sub.st, &a);   // one launch per step
   TRY(run_layers(h, sub.plan, nullptr, t_uniform, a.B, a.T, sub.st));
   switch (sub.tail.form) {
-    case TAIL_H2: return launch_step_tail_h2(a, sub.st);
-    case TAIL_BF16: return launch_step_tail_bf16(a, sub.st);
+    case TAIL_H2:
+      BSG_REQUIRE(a.ws_s && a.wo_s && a.wi_s && a.tail_scale && a.M <= 96, "split-fp16 step tail: fragments missing or in_dims > 96");
+      return launch_step(h, h2_step_form(false), a, a.B * a.tiles_per_row, sub.st);
+    case TAIL_BF16:
+      a.tiles_per_row = cdiv(a.T, 64);
+      return launch_step(h, bf16_tail_form(false, a.plms_hist != 0), a, a.B * a.tiles_per_row, sub.st);
     case TAIL_BF16_RAGGED: {   // one launch over the tiles of every launch group's table (they follow the row lengths in rg_dev)
       BSG_REQUIRE(sub.plan.row0 == 0 && h->rg_dev, "ragged bf16 step tail: no ragged plan bound");
       int n_tiles = 0;
       for (int t : h->rg_group_tiles) n_tiles += t;
-      return launch_step_tail_bf16_ragged(a, reinterpret_cast<const int2*>(h->rg_dev + ((h->bound.B + 1) & ~1)), h->rg_dev, n_tiles, sub.st);
+      BSG_REQUIRE(n_tiles > 0, "ragged bf16 step tail: no tile table");
+      return launch_step(h, bf16_tail_form(true, a.plms_hist != 0), a, n_tiles, sub.st, h->rg_dev + ((h->bound.B + 1) & ~1), h->rg_dev);
     }
     default:   // TAIL_F32 (TAIL_UNFUSED is each sampler's forward_impl path and never comes here)
-      BSG_REQUIRE(!sub.plan.ragged, "step tail: a ragged call needs the bf16 tail in the bf16 configuration");
-      return launch_tail(sub.tail, a, sub.st);
+      BSG_REQUIRE(!sub.plan.ragged(), "step tail: a ragged call needs the bf16 tail in the bf16 configuration");
+      return launch_step(h, tail_f32_form(sub.tail.mp, a.plms_hist != 0), a, a.B * a.tiles_per_row, sub.st);
   }
 }
 
@@ -2378,7 +2323,7 @@ static int run_step(bsg_diffnet* h, const SubBatch& sub, int t_uniform, const Ta
 // +9.9 % at B=12, +1.2 % at B=64, +4 % for the bf16 form at B=64; four chains are worse (a CU only holds two of these
 // workgroups).  On one of the boxes measured the two chains brought no gain (and no loss).  BSG_DUAL=0 disables.
 // Returns what each half is planned as (PlanScope), or PLAN_WHOLE: one chain.  `plan`: the whole batch's.
-static PlanScope dual_scope(bsg_diffnet* h, const StackPlan& plan, int B, int T) {
+static PlanScope dual_scope(const bsg_diffnet* h, const StackPlan& plan, int B, int T) {
   const int dual_env = dn_switches().dual, split_env = dn_switches().split;
   const long long tiles = (long long)B * cdiv(T, 32);
   const bool big = tiles > h->num_cus;
@@ -2390,12 +2335,11 @@ static PlanScope dual_scope(bsg_diffnet* h, const StackPlan& plan, int B, int T)
   if (small) {
     // two chains of split launches share CUs (un-padded LDS): all workgroups of BOTH launches must be resident at once, or a
     // polling workgroup could wait for a partner that cannot start.  Per half: parts x tiles workgroups of 1024/parts threads.
-    if (h->occ2 < 0) query_split_occupancy(h);
     double cus = 0.0;   // CUs the workgroups of both launches occupy at the residency the runtime reports for each form
     for (int half = 0; half < 2; ++half) {
       const long long th = (long long)(half ? B - B / 2 : B / 2) * cdiv(T, 32);
       const int parts = 4 * th <= h->num_cus && split_env != 2 ? 4 : 2 * th <= h->num_cus ? 2 : 0;
-      int occ = parts == 4 ? h->occ4s : h->occ2s;
+      int occ = h->forms.resident(*layer_form(parts == 4 ? LAYER_SPLIT4 : LAYER_SPLIT2, true, false, true));
       const int cap = parts == 4 ? 3 : 2;   // 48 KB of LDS each -> 3 per CU; 8 waves of 128 VGPRs -> 2 per CU
       if (occ > cap) occ = cap;
       if (!parts || occ < 1) return PLAN_WHOLE;
@@ -2403,7 +2347,7 @@ static PlanScope dual_scope(bsg_diffnet* h, const StackPlan& plan, int B, int T)
     }
     small = cus <= (double)h->num_cus;
   }
-  const bool dual = dual_env && B >= 2 && use_wino() && plan.form == STACK_NONE && (big || small);
+  const bool dual = dual_env && B >= 2 && use_wino() && plan.family() == STACK_NONE && (big || small);
   return !dual ? PLAN_WHOLE : big ? PLAN_HALF_BIG : PLAN_HALF_SMALL;
 }
 
@@ -2436,7 +2380,7 @@ static int sampler_begin(bsg_diffnet* h, SamplerFrame& f, float* x, int B, int T
 static void dual_fork(bsg_diffnet* h, SamplerFrame& f, bool may_split) {
   const SubBatch w = f.subs[0];
   const int B0 = w.B / 2, T = w.args.T;
-  const PlanScope half = may_split && !w.plan.ragged ? dual_scope(h, w.plan, w.B, T) : PLAN_WHOLE;
+  const PlanScope half = may_split && !w.plan.ragged() ? dual_scope(h, w.plan, w.B, T) : PLAN_WHOLE;
   bool two = half != PLAN_WHOLE;   // the fork: the second stream and its events are created at the first one; a failed call leaves one chain
   if (two && !h->st2)
     two = hipStreamCreateWithFlags(&h->st2, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) == hipSuccess &&
@@ -2577,7 +2521,7 @@ extern "C" int bsg_diffnet_uses_handoffs(bsg_diffnet* h, int32_t B, int32_t T, i
   // prepare allocated the exchange scratch has no split form yet.
   const long long tiles = (long long)B * cdiv(T, 32);
   const bool split = h->compute == BSG_COMPUTE_F32 && use_wino() && dn_switches().split && !h->split_off && h->num_cus && tiles <= h->num_cus;
-  *uses = (split || plan_stack(h, B, T, nullptr).form != STACK_NONE) ? 1 : 0;
+  *uses = (split || plan_stack(h, B, T, nullptr).form) ? 1 : 0;
   return BSG_OK;
 }
 
@@ -2654,7 +2598,7 @@ extern "C" int bsg_diffnet_debug_stack_stamps(bsg_diffnet* h, int32_t t_uniform,
   BSG_REQUIRE(stamps, "diffnet_debug_stack_stamps: null stamps");
   const StackPlan plan = plan_stack(h, B, T, (hipStream_t)stream);
   TRY(cond_layout_for(h, plan, (hipStream_t)stream));
-  BSG_REQUIRE(plan.form != STACK_NONE && plan.rows >= B, "diffnet_debug_stack_stamps: (B=%d,T=%d) does not run as one %sstack launch", B, T,
+  BSG_REQUIRE(plan.family() != STACK_NONE && plan.rows >= B, "diffnet_debug_stack_stamps: (B=%d,T=%d) does not run as one %sstack launch", B, T,
               h->compute == BSG_COMPUTE_BF16 ? "bf16 " : "");
   return launch_stack(h, plan, nullptr, t_uniform, B, T, (hipStream_t)stream, (unsigned long long*)stamps);
 }
@@ -2781,7 +2725,7 @@ extern "C" int bsg_plms_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
   const dim3 grid(cdiv((long long)n, 256)), block(256);
   // the unfused update (first iteration); ragged: on each row's own frames only
   auto plms_step = [&](const float* xi, float* xo, const float* e0, const float* e1, const float* e2, const float* e3, const PlmsCoef& k) {
-    if (f.plan.ragged)
+    if (f.plan.ragged())
       hipLaunchKernelGGL(plms_step_ragged_kernel, dim3(cdiv(T, 256), h->M, B), dim3(256), 0, st, xi, xo, e0, e1, e2, e3, k, (const int*)h->rg_dev, h->M, T);
     else
       hipLaunchKernelGGL(plms_step_kernel, grid, block, 0, st, xi, xo, e0, e1, e2, e3, k, (long long)n);
@@ -2818,7 +2762,7 @@ extern "C" int bsg_plms_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
     if (n_hist == 0) {
       // ragged: the predictor below writes x_pred on each row's frames only; its padding takes x's (finite, the caller's), which the
       // input projection of the second evaluation reads
-      if (f.plan.ragged) BSG_HIP(hipMemcpyAsync(h->xpred, x, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+      if (f.plan.ragged()) BSG_HIP(hipMemcpyAsync(h->xpred, x, n * sizeof(float), hipMemcpyDeviceToDevice, st));
       plms_step((const float*)x, h->xpred, (const float*)e_new,
                          (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, c);
       TRY(forward_impl(h, f.plan, h->xpred, nullptr, ip, h->eps, B, T, st));

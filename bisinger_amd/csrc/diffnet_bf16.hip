@@ -26,6 +26,7 @@
 //   out    x_out = (x + res)/sqrt(2), skip += o_skip   (fp32, 128-B coalesced rows as in the fp32 kernel)
 #include "diffnet_res.h"
 #include "diffnet_tail.h"
+#include "diffnet_forms.h"
 
 namespace bsg {
 
@@ -949,74 +950,39 @@ int pack_a_frag_bf16(const float* src, unsigned short* out, int M, int K, int Kc
   return BSG_OK;
 }
 
-int launch_step_tail_bf16(const TailArgs& a_in, hipStream_t st) {
-  TailArgs a = a_in;
-  a.tiles_per_row = cdiv(a.T, NT);
-  const dim3 grid(a.B * a.tiles_per_row), block(512);
-  if (a.plms_hist) hipLaunchKernelGGL(step_tail_bf16_kernel<true>, grid, block, TAIL_LDS, st, a);
-  else hipLaunchKernelGGL(step_tail_bf16_kernel<false>, grid, block, TAIL_LDS, st, a);
-  BSG_LAUNCH_CHECK();
-  return BSG_OK;
+// The bf16 stack launch: 64-frame tiles, one workgroup per CU.  Arguments (StackArgs p); grid = p.n_tiles rounded up to 8.  ragged:
+// p.vl_tiles and p.vl_len set.
+const KernelForm* bf16_stack_form(bool ragged) {
+  constexpr size_t lds = XS_BYTES + ZS_BYTES + 3 * C * 4;
+  static const KernelForm forms[] = {
+      {FORM_BF16_STACK, (const void*)residual_stack_bf16_kernel<true>, nullptr, 512, lds, lds, "stack_bf16", nullptr, STACK_BF16, 2},
+      {FORM_BF16_STACK_RAGGED, (const void*)residual_stack_bf16_varlen_kernel, nullptr, 512, lds, lds, "stack_bf16_ragged", nullptr, STACK_BF16, 2, 0, FORM_RAGGED},
+  };
+  return &forms[ragged];
 }
 
-// ragged form: one workgroup per entry of the tile table `tiles` (n_tiles entries, every launch group's), row lengths `len`
-int launch_step_tail_bf16_ragged(const TailArgs& a, const int2* tiles, const int* len, int n_tiles, hipStream_t st) {
-  BSG_REQUIRE(tiles && len && n_tiles > 0, "ragged bf16 step tail: no tile table");
-  if (a.plms_hist) hipLaunchKernelGGL(step_tail_bf16_varlen_kernel<true>, dim3(n_tiles), dim3(512), TAIL_LDS, st, a, tiles, len);
-  else hipLaunchKernelGGL(step_tail_bf16_varlen_kernel<false>, dim3(n_tiles), dim3(512), TAIL_LDS, st, a, tiles, len);
-  BSG_LAUNCH_CHECK();
-  return BSG_OK;
+// The bf16-operand residual layer.  Arguments (ResArgs a) with a.tiles_per_row = ceil(T / 64): this form tiles an utterance in 64-frame
+// pieces; grid = B a.tiles_per_row rounded up to 8 (see the tile order in the kernel).
+const KernelForm* bf16_layer_form(bool stamps) {
+  constexpr size_t lds = XS_BYTES + ZS_BYTES;
+  static const KernelForm forms[] = {
+      {FORM_BF16_LAYER, (const void*)residual_layer_bf16_kernel<false>, nullptr, 512, lds, lds, "bf16", nullptr},
+      {FORM_BF16_LAYER_STAMPS, (const void*)residual_layer_bf16_kernel<true>, nullptr, 512, lds, lds, "bf16", nullptr},
+  };
+  return &forms[stamps];
 }
 
-int stack_bf16_occupancy() {
-  const size_t lds = XS_BYTES + ZS_BYTES + 3 * C * 4;
-  int o = 0;
-  if (hipFuncSetAttribute((const void*)residual_stack_bf16_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, (const void*)residual_stack_bf16_kernel<true>, 512, lds) != hipSuccess)
-    return 0;
-  return o;
-}
-
-// resident workgroups per CU (0 on error) of the ragged form
-int stack_bf16_varlen_occupancy() {
-  const size_t lds = XS_BYTES + ZS_BYTES + 3 * C * 4;
-  int o = 0;
-  if (hipFuncSetAttribute((const void*)residual_stack_bf16_varlen_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, (const void*)residual_stack_bf16_varlen_kernel, 512, lds) != hipSuccess)
-    return 0;
-  return o;
-}
-
-// p.vl_tiles set: the ragged form (p.vl_len the row lengths; stack_bf16_varlen_occupancy() has set its LDS attribute)
-int launch_residual_stack_bf16(const StackArgs& p, hipStream_t st) {
-  const size_t lds = XS_BYTES + ZS_BYTES + 3 * C * 4;
-  if (p.vl_tiles) {
-    BSG_REQUIRE(p.vl_len, "bf16 stack launch: the ragged form needs the row lengths");
-    hipLaunchKernelGGL(residual_stack_bf16_varlen_kernel, dim3(8 * cdiv(p.n_tiles, 8)), dim3(512), lds, st, p);
-    BSG_LAUNCH_CHECK();
-    return BSG_OK;
-  }
-  hipLaunchKernelGGL(residual_stack_bf16_kernel<true>, dim3(8 * cdiv(p.n_tiles, 8)), dim3(512), lds, st, p);
-  BSG_LAUNCH_CHECK();
-  return BSG_OK;
-}
-
-// `a.tiles_per_row` is set here: this form tiles an utterance in 64-frame pieces
-int launch_residual_layer_bf16(const ResArgs& a_in, hipStream_t st) {
-  ResArgs a = a_in;
-  a.tiles_per_row = cdiv(a.T, NT);
-  const size_t lds = XS_BYTES + ZS_BYTES;
-  const int grid = 8 * cdiv(a.B * a.tiles_per_row, 8);   // see the tile order in the kernel
-  static bool attr_set = false;
-  if (!attr_set) {
-    BSG_HIP(hipFuncSetAttribute((const void*)residual_layer_bf16_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    BSG_HIP(hipFuncSetAttribute((const void*)residual_layer_bf16_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
-  if (a.stamps) hipLaunchKernelGGL(residual_layer_bf16_kernel<true>, dim3(grid), dim3(512), lds, st, a);
-  else hipLaunchKernelGGL(residual_layer_bf16_kernel<false>, dim3(grid), dim3(512), lds, st, a);
-  BSG_LAUNCH_CHECK();
-  return BSG_OK;
+// The bf16-operand step tail on 64-frame tiles, skip sum read as bf16 channel quads (a.skip_h).  Arguments (TailArgs a) with
+// a.tiles_per_row = ceil(T / 64), grid = B a.tiles_per_row; ragged: (TailArgs a, const int2* tiles, const int* len), one workgroup per
+// entry {row, 64-frame tile} of `tiles` (every launch group's), `len` [B] the rows' frame counts.
+const KernelForm* bf16_tail_form(bool ragged, bool plms) {
+  static const KernelForm forms[] = {
+      {FORM_BF16_TAIL, (const void*)step_tail_bf16_kernel<false>, nullptr, 512, TAIL_LDS, TAIL_LDS, "step_tail_bf16", nullptr},
+      {FORM_BF16_TAIL_PLMS, (const void*)step_tail_bf16_kernel<true>, nullptr, 512, TAIL_LDS, TAIL_LDS, "step_tail_bf16", nullptr},
+      {FORM_BF16_TAIL_RAGGED, (const void*)step_tail_bf16_varlen_kernel<false>, nullptr, 512, TAIL_LDS, TAIL_LDS, "step_tail_bf16_ragged", nullptr},
+      {FORM_BF16_TAIL_RAGGED_PLMS, (const void*)step_tail_bf16_varlen_kernel<true>, nullptr, 512, TAIL_LDS, TAIL_LDS, "step_tail_bf16_ragged", nullptr},
+  };
+  return &forms[2 * ragged + plms];
 }
 
 }  // namespace bsg

@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "diffnet_res.h"
+#include "diffnet_forms.h"
 
 namespace bsg {
 
@@ -568,18 +569,10 @@ __global__ __launch_bounds__(512, 2) void residual_stack_f43_kernel(StackArgs p)
 
 }  // namespace
 
-int stack_f43_occupancy() {
-  int o = 0;
-  if (hipFuncSetAttribute((const void*)residual_stack_f43_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)STACK43_LDS) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, (const void*)residual_stack_f43_kernel<1>, 512, STACK43_LDS) != hipSuccess)
-    return 0;
-  return o;
-}
-
-int launch_residual_stack_f43(const StackArgs& p, hipStream_t st) {
-  hipLaunchKernelGGL(residual_stack_f43_kernel<1>, dim3(8 * cdiv(p.n_tiles, 8)), dim3(512), STACK43_LDS, st, p);
-  BSG_LAUNCH_CHECK();
-  return BSG_OK;
+// The F(4,3) stack launch: all L layers of 64-frame tiles, one workgroup per CU.  Arguments (StackArgs p); grid = p.n_tiles rounded up to 8.
+const KernelForm* f43_form() {
+  static const KernelForm form = {FORM_F43, (const void*)residual_stack_f43_kernel<1>, nullptr, 512, STACK43_LDS, STACK43_LDS, "stack_f43", nullptr, STACK_F43, 2};
+  return &form;
 }
 
 int pack_wino43(const float* w, float* out, hipStream_t st) {

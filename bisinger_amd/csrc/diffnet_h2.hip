@@ -29,6 +29,7 @@
 // NOTE for whoever edits the kernel: the NCT = 2 form needs all 256 VGPRs and its register allocation has no slack — check the spill
 // count after every change (tests/test_build_resources.py; ~10-17 spilled registers outside the matrix loops are the good state).
 #include "diffnet_h2_shared.h"
+#include "diffnet_forms.h"
 #include <type_traits>
 
 namespace bsg {
@@ -1668,87 +1669,42 @@ __global__ __launch_bounds__(64 * W, 1) void residual_part_h2_kernel(StackArgs p
 
 }  // namespace
 
-template <int NCT>
-static int h2_occupancy() {
-  int o = 0;
-  const int lds = (int)h2_lds(NCT);
-  if (hipFuncSetAttribute((const void*)residual_stack_h2_kernel<true, false, NCT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-      hipFuncSetAttribute((const void*)residual_stack_h2_kernel<true, true, NCT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, (const void*)residual_stack_h2_kernel<true, true, NCT>, 512, h2_lds(NCT)) != hipSuccess)
-    return 0;
-  return o;
-}
-// resident workgroups per CU (0 on error) of the form with `nct` column tiles of 32 frames per workgroup (1 or 2)
-int stack_h2_occupancy(int nct) { return nct == 1 ? h2_occupancy<1>() : h2_occupancy<2>(); }
-
+// The 32-row stack launch on 32 * nct frame tiles.  Arguments (StackArgs p, TailArgs a); grid = p.n_tiles rounded up to 8; p.tiles_per_row /
+// p.n_tiles count tiles of 32 * nct frames.  With the tail inside the launch, `a` is the TailArgs of THIS launch's rows (x, noise, xa_next,
+// history pointers and quad_row0 already offset to its first row); otherwise the residual stack only (skip sum to p.skip).
 // (FAIRB = the time-sliced issue priority between the two waves of a SIMD is always on: +1.2 % in round 2's A/B; the switch is gone)
-template <int NCT>
-static int h2_launch(const StackArgs& p, const TailArgs* tail, hipStream_t st) {
-  const dim3 grid(8 * cdiv(p.n_tiles, 8)), block(512);
-  const TailArgs a = tail ? *tail : TailArgs{};
-  const size_t lds = h2_lds(NCT);
-  if (tail) hipLaunchKernelGGL((residual_stack_h2_kernel<true, true, NCT>), grid, block, lds, st, p, a);
-  else hipLaunchKernelGGL((residual_stack_h2_kernel<true, false, NCT>), grid, block, lds, st, p, a);
-  BSG_LAUNCH_CHECK();
-  return BSG_OK;
+const KernelForm* h2_form(int nct) {
+  static const KernelForm forms[] = {
+      {FORM_H2_32, (const void*)residual_stack_h2_kernel<true, false, 1>, (const void*)residual_stack_h2_kernel<true, true, 1>, 512, h2_lds(1), h2_lds(1),
+       "stack_h2", "stack_h2_tail", STACK_H2, 1},
+      {FORM_H2_64, (const void*)residual_stack_h2_kernel<true, false, 2>, (const void*)residual_stack_h2_kernel<true, true, 2>, 512, h2_lds(2), h2_lds(2),
+       "stack_h2", "stack_h2_tail", STACK_H2, 2},
+  };
+  return nct == 1 || nct == 2 ? &forms[nct - 1] : nullptr;
 }
 
-// tail == nullptr: the residual stack only (skip sum to p.skip); else the sampler step's tail runs in the same launch (TailArgs of THIS
-// launch's rows: x, noise, xa_next, history pointers and quad_row0 already offset to its first row).  nct = column tiles of 32 frames per
-// workgroup: p.tiles_per_row / p.n_tiles count tiles of 32 * nct frames
-int launch_residual_stack_h2(const StackArgs& p, const TailArgs* tail, hipStream_t st, int nct) {
-  return nct == 1 ? h2_launch<1>(p, tail, st) : h2_launch<2>(p, tail, st);
+// step_tail_h2_kernel, the step tail behind a part launch: one workgroup per 32-frame tile (a.tiles_per_row = ceil(T / 32)), a.status the
+// launch's status words; in_proj: in_proj_h2_kernel, a sampler call's first input projection as the tails' head computes the later ones,
+// one workgroup per 32-frame tile of a.x.  Arguments (TailArgs a).
+const KernelForm* h2_step_form(bool in_proj) {
+  constexpr size_t tail_lds = (size_t)2 * h2_xp(1) + 2 * h2_zp(1) + 96 * 32 * sizeof(float), proj_lds = (size_t)2 * h2_xp(1);
+  static const KernelForm forms[] = {
+      {FORM_TAIL_H2, (const void*)step_tail_h2_kernel, nullptr, 512, tail_lds, tail_lds, "step_tail_h2", nullptr},
+      {FORM_IN_PROJ_H2, (const void*)in_proj_h2_kernel, nullptr, 512, proj_lds, proj_lds, "in_proj_h2", nullptr},
+  };
+  return &forms[in_proj];
 }
 
-// the step tail behind a part launch: one workgroup per 32-frame tile (a.tiles_per_row = ceil(T / 32)); a.status: the launch's status words
-int launch_step_tail_h2(const TailArgs& a, hipStream_t st) {
-  static bool attr = false;
-  const size_t lds = (size_t)2 * h2_xp(1) + 2 * h2_zp(1) + 96 * 32 * sizeof(float);
-  if (!attr) {
-    BSG_HIP(hipFuncSetAttribute((const void*)step_tail_h2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr = true;
-  }
-  BSG_REQUIRE(a.ws_s && a.wo_s && a.wi_s && a.tail_scale && a.M <= 96, "split-fp16 step tail: fragments missing or in_dims > 96");
-  hipLaunchKernelGGL(step_tail_h2_kernel, dim3(a.B * a.tiles_per_row), dim3(512), lds, st, a);
-  BSG_LAUNCH_CHECK();
-  return BSG_OK;
-}
-
-// a sampler call's first input projection as the tails' head computes the later ones: one workgroup per 32-frame tile of a.x
-int launch_in_proj_h2(const TailArgs& a, hipStream_t st) {
-  BSG_REQUIRE(a.x && a.xa_next && a.b_in && a.wi_s && a.tail_scale && a.M <= 96, "split-fp16 input projection: fragments missing or in_dims > 96");
-  hipLaunchKernelGGL(in_proj_h2_kernel, dim3(a.B * a.tiles_per_row), dim3(512), (size_t)2 * h2_xp(1), st, a);
-  BSG_LAUNCH_CHECK();
-  return BSG_OK;
-}
-
-template <int P, int W, int NC>
-static int part_occ() {
-  int o = 0;
-  const size_t lds = part_lds(NC);
-  if (hipFuncSetAttribute((const void*)residual_part_h2_kernel<P, W, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, (const void*)residual_part_h2_kernel<P, W, NC>, 64 * W, lds) != hipSuccess)
-    return 0;
-  return o;
-}
-// resident workgroups per CU of the part form (parts per tile, tile width in units of 32 frames): (4, 1) quad of 32 frames, (4, 2) quad of 64,
-// (2, 2) pair of 64
-int part_h2_occupancy(int parts, int nct) {
-  if (parts == 4 && nct == 1) return part_occ<4, 4, 2>();
-  if (parts == 4 && nct == 2) return part_occ<4, 4, 4>();
-  if (parts == 2 && nct == 2) return part_occ<2, 8, 4>();
-  return 0;
-}
-// part forms: `parts` workgroups per tile of 32 nct frames; grid = 8 parts ceil(n_tiles / 8) workgroups, all resident (one per CU)
-int launch_residual_part_h2(const StackArgs& p, hipStream_t st, int parts, int nct) {
-  BSG_REQUIRE(p.zx && p.ix && p.hx && p.pflags && p.apack1q && p.apack2q, "part launch: exchange buffers / 16-row weight fragments missing");
-  const dim3 grid(8 * parts * cdiv(p.n_tiles, 8));
-  if (parts == 4 && nct == 1) hipLaunchKernelGGL((residual_part_h2_kernel<4, 4, 2>), grid, dim3(256), part_lds(2), st, p);
-  else if (parts == 4 && nct == 2) hipLaunchKernelGGL((residual_part_h2_kernel<4, 4, 4>), grid, dim3(256), part_lds(4), st, p);
-  else if (parts == 2 && nct == 2) hipLaunchKernelGGL((residual_part_h2_kernel<2, 8, 4>), grid, dim3(512), part_lds(4), st, p);
-  else BSG_REQUIRE(false, "part launch: no form for %d parts of %d-frame tiles", parts, 32 * nct);
-  BSG_LAUNCH_CHECK();
-  return BSG_OK;
+// The part forms: `parts` workgroups per tile of 32 nct frames — (4, 1) quad of 32 frames, (4, 2) quad of 64, (2, 2) pair of 64 (8 waves).
+// Arguments (StackArgs p); grid = 8 parts ceil(n_tiles / 8) workgroups, all resident (one per CU).
+const KernelForm* part_form(int parts, int nct) {
+  static const KernelForm forms[] = {
+      {FORM_PART_QUAD32, (const void*)residual_part_h2_kernel<4, 4, 2>, nullptr, 256, part_lds(2), part_lds(2), "stack_h2_quad", nullptr, STACK_PART, 1, 4},
+      {FORM_PART_QUAD64, (const void*)residual_part_h2_kernel<4, 4, 4>, nullptr, 256, part_lds(4), part_lds(4), "stack_h2_quad64", nullptr, STACK_PART, 2, 4},
+      {FORM_PART_PAIR64, (const void*)residual_part_h2_kernel<2, 8, 4>, nullptr, 512, part_lds(4), part_lds(4), "stack_h2_pair64", nullptr, STACK_PART, 2, 2},
+  };
+  if (parts == 4 && (nct == 1 || nct == 2)) return &forms[nct - 1];
+  return parts == 2 && nct == 2 ? &forms[2] : nullptr;
 }
 // fp32 [M][K] weights -> hi / lo fp16 A fragments of v_mfma_f32_16x16x32_f16 (16-row tiles), scaled by the layer's table entry
 int pack_a_frag_q(const float* src, unsigned short* out, int M, int K, int Kc, long long sm, long long sc, long long stp, const float* tab,

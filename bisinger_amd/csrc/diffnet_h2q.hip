@@ -22,6 +22,7 @@
 // and a lo slab of 32 row tiles x 1 KB.  A k-step is 48 MFMAs per wave on 8 weight fragments (ring of 2 k-steps = 64 registers, as the 4 x 16
 // deep of the 32-row form) and, per column tile, 2 operand fragments from LDS, read two column tiles ahead into four buffers (32 registers, as there).
 #include "diffnet_h2_shared.h"
+#include "diffnet_forms.h"
 #include <type_traits>
 
 // (float)hi + (float)lo of one half of two packed f16 pairs in ONE instruction (round 5)
@@ -688,140 +689,40 @@ __global__ __launch_bounds__(512, 2) void residual_stack_q_kernel(StackArgs p, T
 
 }  // namespace
 
-// depth of the weight ring in k-steps of 32.  Deeper rings were built (the pipe takes any NS) and measured slower, profiles/r05_q_not_kept.txt:
+// (The weight ring holds 2 k-steps of 32.  Deeper rings were built — the pipe takes any NS — and measured slower, profiles/r05_q_not_kept.txt:
 // 3 k-steps on 64-frame tiles 157.5 k against 175.7 k mel-frames/s (65 spilled registers), 4 k-steps on 32-frame tiles — which have the
-// registers — 63.9 against 60.4 ms per pass at B = 8: the weight stream is not waiting for its latency
-constexpr int NS_DEEP_64 = 2, NS_DEEP_32 = 2;
-static int ring_depth(int) { return 2; }
-
-template <int NCT, int NS>
-static int h2q_occupancy_ns() {
-  int o = 0;
-  const int lds = (int)h2_lds(NCT);
-  if (hipFuncSetAttribute((const void*)residual_stack_q_kernel<true, false, NCT, 0, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-      hipFuncSetAttribute((const void*)residual_stack_q_kernel<true, true, NCT, 0, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, (const void*)residual_stack_q_kernel<true, true, NCT, 0, NS>, 512, h2_lds(NCT)) != hipSuccess)
-    return 0;
-  return o;
-}
-// resident workgroups per CU (0 on error) of the form with `nct` units of 32 frames per workgroup (1 or 2)
-int stack_h2q_occupancy(int nct) {
-  const int ns = ring_depth(nct);
-  if (nct == 1) return ns == 2 ? h2q_occupancy_ns<1, 2>() : h2q_occupancy_ns<1, NS_DEEP_32>();
-  return ns == 2 ? h2q_occupancy_ns<2, 2>() : h2q_occupancy_ns<2, NS_DEEP_64>();
+// registers — 63.9 against 60.4 ms per pass at B = 8: the weight stream is not waiting for its latency.)
+template <bool FAIR, int NCT, int MODE>
+static KernelForm q_row(FormId id, FormVariant variant, const char* name, const char* name_tail) {
+  return {id, (const void*)residual_stack_q_kernel<FAIR, false, NCT, MODE, 2>, (const void*)residual_stack_q_kernel<FAIR, true, NCT, MODE, 2>, 512,
+          h2_lds(NCT), h2_lds(NCT), name, name_tail, STACK_H2Q, NCT, 0, variant};
 }
 
-template <int NCT, int NS>
-static int h2q_launch(const StackArgs& p, const TailArgs* tail, hipStream_t st) {
-  const dim3 grid(8 * cdiv(p.n_tiles, 8)), block(512);
-  const TailArgs a = tail ? *tail : TailArgs{};
-  const size_t lds = h2_lds(NCT);
-  // BSG_H2Q_DIAG=1 / 2 / 3 / 4 / 5 / 6: timing experiments on the launches of 64-frame tiles (1: no weight reloads, 2: no operand reads either; 3: a stamp per pass;
-  // round 6, the buckets outside the GEMM phases: 4: no conditioner-term loads, 5: a two-instruction gate, 6: no hand-off and no publish — all but 3: wrong results)
-  const int diag = dn_switches().h2q_diag;
-  if constexpr (NCT == 2) {
-    if (diag) {
-      auto go = [&](auto kt, auto kn) {
-        (void)hipFuncSetAttribute((const void*)kt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)kn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (tail) hipLaunchKernelGGL(kt, grid, block, lds, st, p, a);
-        else hipLaunchKernelGGL(kn, grid, block, lds, st, p, a);
-      };
-      if (diag == 1) go(residual_stack_q_kernel<true, true, 2, 1, NS>, residual_stack_q_kernel<true, false, 2, 1, NS>);
-      else if (diag == 2) go(residual_stack_q_kernel<true, true, 2, 2, NS>, residual_stack_q_kernel<true, false, 2, 2, NS>);
-      else if (diag == 4) go(residual_stack_q_kernel<true, true, 2, 4, NS>, residual_stack_q_kernel<true, false, 2, 4, NS>);
-      else if (diag == 5) go(residual_stack_q_kernel<true, true, 2, 5, NS>, residual_stack_q_kernel<true, false, 2, 5, NS>);
-      else if (diag == 6) go(residual_stack_q_kernel<true, true, 2, 6, NS>, residual_stack_q_kernel<true, false, 2, 6, NS>);
-      else go(residual_stack_q_kernel<true, true, 2, 3, NS>, residual_stack_q_kernel<true, false, 2, 3, NS>);
-      BSG_LAUNCH_CHECK();
-      return BSG_OK;
-    }
-  }
-  if (!dn_switches().h2q_fair) {   // BSG_H2Q_FAIR=0: no time-sliced issue priority between the two waves of a SIMD
-    static bool attr = false;
-    if (!attr) {
-      BSG_HIP(hipFuncSetAttribute((const void*)residual_stack_q_kernel<false, false, NCT, 0, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      BSG_HIP(hipFuncSetAttribute((const void*)residual_stack_q_kernel<false, true, NCT, 0, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      attr = true;
-    }
-    if (tail) hipLaunchKernelGGL((residual_stack_q_kernel<false, true, NCT, 0, NS>), grid, block, lds, st, p, a);
-    else hipLaunchKernelGGL((residual_stack_q_kernel<false, false, NCT, 0, NS>), grid, block, lds, st, p, a);
-  } else if (tail) hipLaunchKernelGGL((residual_stack_q_kernel<true, true, NCT, 0, NS>), grid, block, lds, st, p, a);
-  else hipLaunchKernelGGL((residual_stack_q_kernel<true, false, NCT, 0, NS>), grid, block, lds, st, p, a);
-  BSG_LAUNCH_CHECK();
-  return BSG_OK;
-}
-
-// the ragged form (p.vl_tiles set): 64-frame tiles, time-sliced issue priority (the default form's arithmetic, whatever BSG_H2Q_FAIR says)
-static int h2q_launch_varlen(const StackArgs& p, const TailArgs* tail, hipStream_t st) {
-  const dim3 grid(8 * cdiv(p.n_tiles, 8)), block(512);
-  const TailArgs a = tail ? *tail : TailArgs{};
-  const size_t lds = h2_lds(2);
-  static bool attr = false;
-  if (!attr) {
-    BSG_HIP(hipFuncSetAttribute((const void*)residual_stack_q_kernel<true, false, 2, Q_VARLEN, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    BSG_HIP(hipFuncSetAttribute((const void*)residual_stack_q_kernel<true, true, 2, Q_VARLEN, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr = true;
-  }
-  if (tail) hipLaunchKernelGGL((residual_stack_q_kernel<true, true, 2, Q_VARLEN, 2>), grid, block, lds, st, p, a);
-  else hipLaunchKernelGGL((residual_stack_q_kernel<true, false, 2, Q_VARLEN, 2>), grid, block, lds, st, p, a);
-  BSG_LAUNCH_CHECK();
-  return BSG_OK;
-}
-
-// the token form (p.tok set): 64-frame tiles, time-sliced issue priority, as the ragged form
-static int h2q_launch_tok(const StackArgs& p, const TailArgs* tail, hipStream_t st) {
-  const dim3 grid(8 * cdiv(p.n_tiles, 8)), block(512);
-  const TailArgs a = tail ? *tail : TailArgs{};
-  const size_t lds = h2_lds(2);
-  static bool attr = false;
-  if (!attr) {
-    BSG_HIP(hipFuncSetAttribute((const void*)residual_stack_q_kernel<true, false, 2, Q_TOK, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    BSG_HIP(hipFuncSetAttribute((const void*)residual_stack_q_kernel<true, true, 2, Q_TOK, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr = true;
-  }
-  if (tail) hipLaunchKernelGGL((residual_stack_q_kernel<true, true, 2, Q_TOK, 2>), grid, block, lds, st, p, a);
-  else hipLaunchKernelGGL((residual_stack_q_kernel<true, false, 2, Q_TOK, 2>), grid, block, lds, st, p, a);
-  BSG_LAUNCH_CHECK();
-  return BSG_OK;
-}
-
-// resident workgroups per CU (0 on error) of the token form
-int stack_h2q_tok_occupancy() {
-  int o = 0;
-  const int lds = (int)h2_lds(2);
-  if (hipFuncSetAttribute((const void*)residual_stack_q_kernel<true, false, 2, Q_TOK, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-      hipFuncSetAttribute((const void*)residual_stack_q_kernel<true, true, 2, Q_TOK, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, (const void*)residual_stack_q_kernel<true, true, 2, Q_TOK, 2>, 512, lds) != hipSuccess)
-    return 0;
-  return o;
-}
-
-// resident workgroups per CU (0 on error) of the ragged form
-int stack_h2q_varlen_occupancy() {
-  int o = 0;
-  const int lds = (int)h2_lds(2);
-  if (hipFuncSetAttribute((const void*)residual_stack_q_kernel<true, false, 2, Q_VARLEN, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-      hipFuncSetAttribute((const void*)residual_stack_q_kernel<true, true, 2, Q_VARLEN, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, (const void*)residual_stack_q_kernel<true, true, 2, Q_VARLEN, 2>, 512, lds) != hipSuccess)
-    return 0;
-  return o;
-}
-
-// the arguments of launch_residual_stack_h2 (diffnet_h2.hip); p.apack1q / p.apack2q must hold the 16-row weight fragments
-int launch_residual_stack_h2q(const StackArgs& p, const TailArgs* tail, hipStream_t st, int nct) {
-  BSG_REQUIRE(p.apack1q && p.apack2q && p.dconv, "16-row stack launch: the 16-row weight fragments / the step-term table are missing");
-  if (p.vl_tiles) {
-    BSG_REQUIRE(nct == 2 && p.vl_len, "16-row stack launch: the ragged form takes 64-frame tiles and the row lengths");
-    return h2q_launch_varlen(p, tail, st);
-  }
-  if (p.tok) {
-    BSG_REQUIRE(nct == 2 && p.tok_K > 0 && p.condterm_q, "16-row stack launch: the token form takes 64-frame tiles and the token table");
-    return h2q_launch_tok(p, tail, st);
-  }
-  const int ns = ring_depth(nct);
-  if (nct == 1) return ns == 2 ? h2q_launch<1, 2>(p, tail, st) : h2q_launch<1, NS_DEEP_32>(p, tail, st);
-  return ns == 2 ? h2q_launch<2, 2>(p, tail, st) : h2q_launch<2, NS_DEEP_64>(p, tail, st);
+// The forms of the 16-row stack launch.  Arguments (StackArgs p, TailArgs a); p.apack1q / p.apack2q hold its weight fragments; grid =
+// p.n_tiles rounded up to 8.  The ragged form (p.vl_tiles, p.vl_len) and the token form (p.tok, p.tok_K, p.condterm_q the token table)
+// take 64-frame tiles and the time-sliced issue priority (the default form's arithmetic, whatever BSG_H2Q_FAIR says).  fair = false
+// (BSG_H2Q_FAIR=0): no time-sliced issue priority between the two waves of a SIMD.  diag (BSG_H2Q_DIAG) = 1 .. 6: timing experiments on the
+// launches of 64-frame tiles (1: no weight reloads, 2: no operand reads either; 3: a stamp per pass; round 6, the buckets outside the GEMM
+// phases: 4: no conditioner-term loads, 5: a two-instruction gate, 6: no hand-off and no publish — all but 3: wrong results).
+const KernelForm* h2q_form(int nct, FormVariant variant, bool fair, int diag) {
+  static const KernelForm forms[] = {
+      q_row<true, 1, 0>(FORM_Q32, FORM_PLAIN, "stack_h2q", "stack_h2q_tail"),
+      q_row<true, 2, 0>(FORM_Q64, FORM_PLAIN, "stack_h2q", "stack_h2q_tail"),
+      q_row<false, 1, 0>(FORM_Q32_UNFAIR, FORM_PLAIN, "stack_h2q", "stack_h2q_tail"),
+      q_row<false, 2, 0>(FORM_Q64_UNFAIR, FORM_PLAIN, "stack_h2q", "stack_h2q_tail"),
+      q_row<true, 2, Q_VARLEN>(FORM_Q64_RAGGED, FORM_RAGGED, "stack_h2q_ragged", "stack_h2q_ragged_tail"),
+      q_row<true, 2, Q_TOK>(FORM_Q64_TOKEN, FORM_TOKEN, "stack_h2q_tok", "stack_h2q_tok_tail"),
+      q_row<true, 2, 1>(FORM_Q64_DIAG1, FORM_PLAIN, "stack_h2q", "stack_h2q_tail"),
+      q_row<true, 2, 2>(FORM_Q64_DIAG2, FORM_PLAIN, "stack_h2q", "stack_h2q_tail"),
+      q_row<true, 2, 3>(FORM_Q64_DIAG3, FORM_PLAIN, "stack_h2q", "stack_h2q_tail"),
+      q_row<true, 2, 4>(FORM_Q64_DIAG4, FORM_PLAIN, "stack_h2q", "stack_h2q_tail"),
+      q_row<true, 2, 5>(FORM_Q64_DIAG5, FORM_PLAIN, "stack_h2q", "stack_h2q_tail"),
+      q_row<true, 2, 6>(FORM_Q64_DIAG6, FORM_PLAIN, "stack_h2q", "stack_h2q_tail"),
+  };
+  if (nct != 1 && nct != 2) return nullptr;
+  if (variant != FORM_PLAIN) return nct == 2 ? &forms[variant == FORM_RAGGED ? 4 : 5] : nullptr;
+  if (nct == 2 && diag) return &forms[6 + (diag >= 1 && diag <= 6 ? diag : 3) - 1];
+  return &forms[(fair ? 0 : 2) + nct - 1];
 }
 
 }  // namespace bsg

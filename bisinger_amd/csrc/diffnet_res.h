@@ -110,21 +110,9 @@ __device__ __forceinline__ void stack_epoch_done(const StackArgs& p, unsigned fb
   __hip_atomic_store(p.epoch, next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// bf16 stack launch: 64-frame tiles, one workgroup per CU (see diffnet_bf16.hip); grid = p.n_tiles rounded up to 8
-int launch_residual_stack_bf16(const StackArgs& p, hipStream_t st);
-int stack_bf16_occupancy();   // resident workgroups per CU of residual_stack_bf16_kernel (0 on error)
-int stack_bf16_varlen_occupancy();   // its ragged form (p.vl_tiles set: launch_residual_stack_bf16 takes it)
+// (the launch forms that take these arguments: diffnet_forms.h)
 
-// fp32 stack launch on the 16-bit matrix pipe: operands split exactly into hi + lo fp16 terms (diffnet_h2.hip); 64-frame tiles, one
-// workgroup per CU; grid = p.n_tiles rounded up to 8
-int stack_h2_occupancy(int nct);   // nct = column tiles of 32 frames per workgroup (1 or 2)
-int stack_h2q_occupancy(int nct);  // the 16-row-tile form of the same launch (diffnet_h2q.hip)
-int stack_h2q_varlen_occupancy();   // its ragged form (64-frame tiles; resident workgroups per CU, 0 on error)
-int stack_h2q_tok_occupancy();      // its token form (64-frame tiles)
-// part forms on 16-row matrix tiles: `parts` workgroups (on as many CUs of one XCD) per tile of 32 nct frames, each C / parts channels:
-// (4, 1) quad of a 32-frame tile, (4, 2) quad of a 64-frame tile, (2, 2) pair of a 64-frame tile (8 waves); p.n_tiles tiles -> grid of 8 parts ceil(n_tiles / 8) workgroups, all resident
-int launch_residual_part_h2(const StackArgs& p, hipStream_t st, int parts, int nct);
-int part_h2_occupancy(int parts, int nct);
+// split-fp16 weight fragments and their scales (diffnet_h2.hip)
 int pack_a_frag_q(const float* src, unsigned short* out, int M, int K, int Kc, long long sm, long long sc, long long stp, const float* tab,
                   int is_gemm2, hipStream_t st);
 int h2_scales(const float* const* w1, const float* const* w2, int L, unsigned* maxbits, float* tab, hipStream_t st);
@@ -132,12 +120,7 @@ int pack_a_frag_h2(const float* src, unsigned short* out, int M, int K, int Kc, 
                    int is_gemm2, hipStream_t st);
 
 int pack_wino43(const float* w, float* out, hipStream_t st);   // [2C][C][3] -> [6][32][16][64][4]
-// F(4,3) stack launch: all L layers of 64-frame tiles, one workgroup per CU (diffnet_f43.hip); grid = p.n_tiles rounded up to 8
-int launch_residual_stack_f43(const StackArgs& p, hipStream_t st);
-int stack_f43_occupancy();
 
-// bf16-operand form of the residual layer (diffnet_bf16.hip); same tensors, 64-frame tiles
-int launch_residual_layer_bf16(const ResArgs& a, hipStream_t st);
 // fp32 [M][K] weights -> bf16 A fragments of v_mfma_f32_32x32x16_bf16 (see diffnet_bf16.hip)
 int pack_a_frag_bf16(const float* src, unsigned short* out, int M, int K, int Kc, long long sm, long long sc, long long stp,
                      hipStream_t st);
@@ -217,7 +200,7 @@ struct DnSwitches {
   int h2_tail = env_int("BSG_H2_TAIL", 1);                    // 0: the step tail as its own launch behind a split-fp16 stack / part launch
   int dual = env_int("BSG_DUAL", 1);                          // 0: no half-batch chains; 2: for big batches only
   int debug_wrap_r04 = env_int("BSG_DEBUG_WRAP_R04", 0);      // 1: round 4's behaviour (only a PART launch zeroes the part flags at a wrap): the negative control of tests/test_gpu_handoff.py
-  int h2q_diag = env_int("BSG_H2Q_DIAG", 0);                  // 1 .. 6: timing experiments on the 16-row launches of 64-frame tiles (diffnet_h2q.hip h2q_launch; all but 3: wrong results)
+  int h2q_diag = env_int("BSG_H2Q_DIAG", 0);                  // 1 .. 6: timing experiments on the 16-row launches of 64-frame tiles (diffnet_h2q.hip h2q_form; all but 3: wrong results)
   int h2q_fair = env_int("BSG_H2Q_FAIR", 1);                  // 0: no time-sliced issue priority between the two waves of a SIMD
   int cond_tok = env_int("BSG_COND_TOK", 1);                  // 0: behind bsg_diffnet_prepare_tokens the stack launch reads the per-frame term (expanded), not the token table
 };

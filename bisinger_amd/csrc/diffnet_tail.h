@@ -106,20 +106,8 @@ __device__ __forceinline__ float philox_normal1(unsigned long long seed, unsigne
 }
 
 
-// split-fp16 stack launch (diffnet_h2.hip), optionally with the step tail in the same launch
-int launch_residual_stack_h2(const StackArgs& p, const TailArgs* tail, hipStream_t st, int nct);
-// the same launch on 16-row matrix tiles (diffnet_h2q.hip): p.apack1q / p.apack2q hold its weight fragments
-int launch_residual_stack_h2q(const StackArgs& p, const TailArgs* tail, hipStream_t st, int nct);
-// the step tail behind a pair / quad launch, on the 16-bit matrix pipe (diffnet_h2.hip step_tail_h2_kernel)
-int launch_step_tail_h2(const TailArgs& a, hipStream_t st);
-// a sampler call's first input projection with the arithmetic of the split-fp16 tails' head (diffnet_h2.hip in_proj_h2_kernel)
-int launch_in_proj_h2(const TailArgs& a, hipStream_t st);
+// the split-fp16 tails' weight fragments and scales (diffnet_h2.hip)
 int h2_tail_pack(const float* ws, const float* wo96, const float* wi96, unsigned short* out_ws, unsigned short* out_wo, unsigned short* out_wi,
                  unsigned* maxbits, float* tab, hipStream_t st);
-
-// bf16-operand form of the fused step tail (diffnet_bf16.hip): 64-frame tiles, skip sum read as bf16 channel quads (a.skip_h)
-int launch_step_tail_bf16(const TailArgs& a, hipStream_t st);
-// the ragged form: one workgroup per entry {row, 64-frame tile} of `tiles` (n_tiles, every launch group's); `len` [B] the rows' frame counts
-int launch_step_tail_bf16_ragged(const TailArgs& a, const int2* tiles, const int* len, int n_tiles, hipStream_t st);
 
 }  // namespace bsg
