@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'lib', 'libbisinger_hip.so')
 if os.environ.get('BSG_LIB'):      # development: an alternative build of the same ABI (kernel experiments)
     LIB_PATH = os.environ['BSG_LIB']
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 
 class BsgError(RuntimeError):
@@ -206,6 +206,9 @@ _SIGS = {
     'bsg_gemm_presplit_f32': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                         c_int32, c_void_p]),
     'bsg_gemm_h2w_ex': (c_int32, [POINTER(H2wDesc), c_int32, POINTER(c_char_p), c_void_p]),      # ABI v21
+    # ABI v22: row-keyed draws; lengths_host / seeds_host: B int32 / B uint64 on the host
+    'bsg_philox_normal_rows': (c_int32, [c_void_p, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_uint64), c_uint32, c_void_p]),
+    'bsg_ddpm_sample_rows': (c_int32, [c_void_p, POINTER(Schedule), c_void_p, POINTER(c_uint64), c_int32, c_int32, c_int32, c_int32, c_void_p]),
 }
 
 _lib = None
@@ -417,6 +420,34 @@ def row_lengths(lengths, B, who, T=None):
             if not 1 <= v <= T:
                 raise BsgError(f'{who}: lengths[{b}]={v} outside 1..T={T}')
     return lengths
+
+
+def row_seeds_list(row_seeds, B, who, other=None):
+    """Row seeds (one int per row: each row's own Philox key) -> list of B ints in 0..2^64-1.  ValueError, in `who`'s name, when `other`
+    (a dict name -> value of the arguments row seeds exclude) holds anything but None, or the count is not B.  Called before anything runs."""
+    given = [k for k, v in (other or {}).items() if v is not None]
+    if given:
+        raise ValueError(f'{who}: row_seeds draws every row from its own seed; it cannot be combined with supplied {" / ".join(given)}')
+    seeds = [int(v) & 0xFFFFFFFFFFFFFFFF for v in (row_seeds.tolist() if hasattr(row_seeds, 'tolist') else row_seeds)]
+    if len(seeds) != B:
+        raise ValueError(f'{who}: row_seeds has {len(seeds)} entries for a batch of {B} rows')
+    return seeds
+
+
+def seeds_array(seeds):
+    """A list of ints as the host uint64 array the row-keyed entries take."""
+    return (c_uint64 * len(seeds))(*seeds)
+
+
+def philox_normal_rows(x, M, T, lengths, seeds, stream_id):
+    """bsg_philox_normal_rows into x (a contiguous fp32 device tensor of len(seeds) * M * T values): row b from the stream
+    (seeds[b], stream_id) at its own length lengths[b] (None: T), 0 beyond."""
+    B = len(seeds)
+    assert x.dtype.is_floating_point and x.element_size() == 4 and x.numel() == B * M * T, (tuple(x.shape), B, M, T)
+    lens = None if lengths is None else (c_int32 * B)(*[int(v) for v in lengths])
+    with on_device(x):
+        check(load().bsg_philox_normal_rows(ptr(x), B, M, T, lens, seeds_array(seeds), stream_id, stream_ptr()), 'bsg_philox_normal_rows')
+    return x
 
 
 class GemmGuarded:

@@ -977,6 +977,46 @@ __global__ void philox_fill_kernel(float* __restrict__ x, long long n4, unsigned
   reinterpret_cast<f32x4*>(x)[i] = philox_normal4(seed, stream, quad0 + (unsigned long long)i);
 }
 
+// Row-keyed draws (bsg_philox_normal_rows): row b of x [rows][M][T] from its OWN stream (seed[b], stream) — element m n_b + c at
+// x[b][m][c] for c < n_b = len[b], what philox_fill_kernel writes for the row alone at T = n_b — and 0 at n_b <= c < T.  The seeds and
+// lengths of up to 32 rows travel in the launch's arguments (nothing is copied, a captured call replays them).
+// blockIdx.y: the row.  Work item i of a row: i < M n_b / 4: quad i of the row's stream, every draw evaluated once; its four values go
+// to (m, c) = (idx / n_b, idx % n_b), one 16-byte store where they stay in one mel row and the address allows it (rows of odd T start
+// unaligned), single floats elsewhere.  The items behind: four elements each of the zero tail, M (T - n_b) in all.
+constexpr int kPhiloxRowsPerLaunch = 32;
+struct PhiloxRows {
+  unsigned long long seed[kPhiloxRowsPerLaunch];
+  int len[kPhiloxRowsPerLaunch];
+};
+__global__ __launch_bounds__(256) void philox_fill_rows_kernel(float* __restrict__ x, PhiloxRows rows, int M, int T, unsigned stream) {
+  const int b = blockIdx.y, nb = rows.len[b];
+  float* xb = x + (long long)b * M * T;
+  const long long nq = (long long)M * nb / 4;   // (M n_b is a multiple of 4: the host refuses anything else)
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nq) {
+    const f32x4 z = philox_normal4(rows.seed[b], stream, (unsigned long long)i);
+    const long long idx = 4 * i;
+    int m = (int)(idx / nb), c = (int)(idx - (long long)m * nb);
+    float* p = xb + (long long)m * T + c;
+    if (c + 3 < nb && (reinterpret_cast<unsigned long long>(p) & 15ull) == 0) {
+      *reinterpret_cast<f32x4*>(p) = z;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        xb[(long long)m * T + c] = z[e];
+        if (++c == nb) { c = 0; ++m; }
+      }
+    }
+    return;
+  }
+  const int pad = T - nb;
+  const long long nz = (long long)M * pad;
+  for (long long e = 4 * (i - nq), end = e + 4 < nz ? e + 4 : nz; e < end; ++e) {
+    const int m = (int)(e / pad);
+    xb[(long long)m * T + nb + (int)(e - (long long)m * pad)] = 0.f;
+  }
+}
+
 // mel_out[b,t,m] = denorm(x[b,m,t]) * (mel2ph[b,t] > 0)     (shallow_diffusion_tts.py:268-272, :278-279)
 // [M][64]-frame tile through LDS: reads coalesced along t, writes coalesced along m.
 __global__ __launch_bounds__(256) void mel_finish_kernel(const float* __restrict__ x, const float* __restrict__ smin,
@@ -1189,6 +1229,10 @@ struct bsg_diffnet {
   size_t rg_cap = 0;                   // ints rg_dev holds
   std::vector<int> rg_group_off;       // per launch group: offset of its table (in tiles) behind the lengths ...
   std::vector<int> rg_group_tiles;     // ... and its tile count
+  std::vector<int32_t> rg_lens;        // the bound row lengths once more on the host: what bsg_ddpm_sample_rows draws each row's noise at
+  // row-keyed draws (bsg_ddpm_sample_rows): the step's noise [B][M][T], filled in front of every step
+  float* row_noise = nullptr;
+  size_t row_noise_cap = 0;            // frames B x T it holds (grown by the first keyed call of a shape)
   DevOwned owned;                      // every allocation that lives as long as the handle (own_alloc): destroy frees them
 };
 
@@ -1206,6 +1250,7 @@ static int num_cus(bsg_diffnet* h) {
 // the group gets on a captured stream.
 static const char* const kLazyRows = "diffnet: the row layout of the conditioner term is allocated by the first eager call of a fallback launch; run it once before capturing";
 static const char* const kLazyQuads = "diffnet: the per-frame conditioner term of a token binding is allocated by the first eager call that reads it; run it once before capturing";
+static const char* const kLazyRowNoise = "ddpm_sample_rows: the buffer of a step's row-keyed draws is allocated by the first eager call of this shape; run it once before capturing";
 static const char* const kLazyPart = "part launch: the exchange buffers of this shape are allocated by its first eager call; run it once before capturing";
 static std::vector<WsBuf> ws_table(bsg_diffnet* h) {   // (a vector: its size is the initialiser's)
   const size_t f = sizeof(float), u = sizeof(unsigned), s = sizeof(unsigned short), M = h->M, term = (size_t)h->L * 2 * C;
@@ -1237,6 +1282,8 @@ static std::vector<WsBuf> ws_table(bsg_diffnet* h) {   // (a vector: its size is
       {&h->part_cap, (void**)&h->part_flags, 2 * 4 * u, 0, WS_ZERO, kLazyPart},
       // rg_cap, ints: row lengths and tile tables of a ragged binding
       {&h->rg_cap, (void**)&h->rg_dev, sizeof(int)},
+      // row_noise_cap, frames B x T: one step's row-keyed draws
+      {&h->row_noise_cap, (void**)&h->row_noise, M * f, 0, 0, kLazyRowNoise},
   };
 }
 
@@ -2405,21 +2452,34 @@ static int sampler_end(bsg_diffnet* h, const SamplerFrame& f, int rc) {
   return rc;
 }
 
-extern "C" int bsg_ddpm_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, const float* noise, uint64_t seed,
-                               int32_t t_start, int32_t n_steps, int32_t B, int32_t T, int32_t row0, int32_t B_total,
-                               void* stream) {
+// Both DDPM entries.  row_seeds (host [B], bsg_ddpm_sample_rows: noise null, row0 0): every step's draws are written to h->row_noise by
+// bsg_philox_normal_rows in front of the step's launches — a chain's rows on the chain's stream, so stream order covers the buffer's reuse by
+// the next step — and the step reads them as supplied noise.  Without, nothing here differs from the unkeyed call.
+static int ddpm_sample_impl(bsg_diffnet* h, const bsg_schedule* s, float* x, const float* noise, uint64_t seed, const uint64_t* row_seeds,
+                            int32_t t_start, int32_t n_steps, int32_t B, int32_t T, int32_t row0, int32_t B_total, void* stream,
+                            const char* who) {
   GuardScope guard_scope(h ? &h->guard : nullptr);
-  TRY(sampler_enter(h, s, B, T, "ddpm_sample", false));
-  BSG_REQUIRE(x, "ddpm_sample: null x");
+  TRY(sampler_enter(h, s, B, T, who, false));
+  BSG_REQUIRE(x, "%s: null x", who);
   BSG_REQUIRE(t_start < s->num_timesteps && t_start < h->cfg.max_steps && n_steps >= 0 && t_start - n_steps + 1 >= 0,
-              "ddpm_sample: steps [%d..%d] outside the schedule (%d) / step table (%d)", t_start - n_steps + 1, t_start,
+              "%s: steps [%d..%d] outside the schedule (%d) / step table (%d)", who, t_start - n_steps + 1, t_start,
               s->num_timesteps, h->cfg.max_steps);
-  BSG_REQUIRE(row0 >= 0 && row0 + B <= B_total, "ddpm_sample: rows [%d,%d) outside the global batch %d", row0, row0 + B, B_total);
+  BSG_REQUIRE(row0 >= 0 && row0 + B <= B_total, "%s: rows [%d,%d) outside the global batch %d", who, row0, row0 + B, B_total);
   hipStream_t st = (hipStream_t)stream;
   const long long n = (long long)B * h->M * T;
-  BSG_REQUIRE(n % 4 == 0, "ddpm_sample: B*M*T must be a multiple of 4");
+  BSG_REQUIRE(n % 4 == 0, "%s: B*M*T must be a multiple of 4", who);
   SamplerFrame f;
-  TRY(sampler_begin(h, f, x, B, T, st, "ddpm_sample"));
+  TRY(sampler_begin(h, f, x, B, T, st, who));
+  // keyed: the row lengths are the binding's (T for a padded one); what the fill would refuse is refused here, before a step is enqueued
+  const int32_t* lens = row_seeds && h->bound.ragged ? h->rg_lens.data() : nullptr;
+  if (row_seeds) {
+    for (int b = 0; b < B; ++b)
+      BSG_REQUIRE((long long)h->M * (lens ? lens[b] : T) % 4 == 0, "%s: row %d draws M * n = %d * %d values, no multiple of 4", who, b, h->M, lens ? lens[b] : T);
+    TRY(grow(h, &h->row_noise_cap, (size_t)B * T, st, GROW_LAZY));
+  }
+  auto fill = [&](int i, int r0, int rows, hipStream_t on) {   // the keyed draws of step i for rows [r0, r0 + rows), enqueued on `on`
+    return bsg_philox_normal_rows(h->row_noise + (size_t)r0 * h->M * T, rows, h->M, T, lens ? lens + r0 : nullptr, row_seeds + r0, (uint32_t)(i + 1), on);
+  };
   const unsigned long long elem0 = (unsigned long long)row0 * h->M * T;   // Philox: the flat element index of this shard's row 0
   auto coef = [&](int i) {
     return StepCoef{s->sqrt_recip_alphas_cumprod[i], s->sqrt_recipm1_alphas_cumprod[i], s->posterior_mean_coef1[i], s->posterior_mean_coef2[i], s->sigma[i]};
@@ -2428,8 +2488,9 @@ extern "C" int bsg_ddpm_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
     for (int k = 0; k < n_steps; ++k) {
       const int i = t_start - k;
       TRY(forward_impl(h, f.plan, x, nullptr, i, h->eps, B, T, st));
+      if (row_seeds) TRY(fill(i, 0, B, st));
       hipLaunchKernelGGL(ddpm_step_kernel, dim3(cdiv(n / 4, 256)), dim3(256), 0, st, x, (const float*)h->eps,
-                         noise ? noise + (long long)k * n : nullptr, coef(i), n / 4, (unsigned long long)seed, (unsigned)(i + 1), elem0 / 4);
+                         row_seeds ? (const float*)h->row_noise : noise ? noise + (long long)k * n : nullptr, coef(i), n / 4, (unsigned long long)seed, (unsigned)(i + 1), elem0 / 4);
       BSG_LAUNCH_CHECK();
     }
     return BSG_OK;
@@ -2444,10 +2505,27 @@ extern "C" int bsg_ddpm_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, 
       TailArgs a = f.subs[u].args;
       a.noise = noise ? noise + (long long)k * n : nullptr; a.k = coef(i); a.do_head = k + 1 < n_steps;
       a.seed = seed; a.quad_row0 = elem0; a.stream = (unsigned)(i + 1);
-      rc = run_step(h, f.subs[u], i, a);
+      if (row_seeds) {
+        a.noise = h->row_noise;   // (at the call's row 0, like x: run_step moves both to the chain's rows)
+        rc = fill(i, f.subs[u].plan.row0, f.subs[u].B, f.subs[u].st);
+      }
+      if (rc == BSG_OK) rc = run_step(h, f.subs[u], i, a);
     }
   }
   return sampler_end(h, f, rc);
+}
+
+extern "C" int bsg_ddpm_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, const float* noise, uint64_t seed,
+                               int32_t t_start, int32_t n_steps, int32_t B, int32_t T, int32_t row0, int32_t B_total,
+                               void* stream) {
+  return ddpm_sample_impl(h, s, x, noise, seed, nullptr, t_start, n_steps, B, T, row0, B_total, stream, "ddpm_sample");
+}
+
+// ABI v22: bsg_ddpm_sample with every row's draws from the row's own stream (seeds_host[b], i + 1) at the row's bound length
+extern "C" int bsg_ddpm_sample_rows(bsg_diffnet* h, const bsg_schedule* s, float* x, const uint64_t* seeds_host, int32_t t_start,
+                                    int32_t n_steps, int32_t B, int32_t T, void* stream) {
+  BSG_REQUIRE(seeds_host, "ddpm_sample_rows: null seeds_host");
+  return ddpm_sample_impl(h, s, x, nullptr, 0, seeds_host, t_start, n_steps, B, T, 0, B, stream, "ddpm_sample_rows");
 }
 
 extern "C" int bsg_diffnet_set_compute(bsg_diffnet* h, int32_t mode) {
@@ -2702,6 +2780,35 @@ extern "C" int bsg_philox_normal(float* x, int64_t n, uint64_t seed, uint32_t st
   return BSG_OK;
 }
 
+// ABI v22: x [B][M][T], row b from the stream (seeds_host[b], stream_id) at its own length — what bsg_philox_normal gives the row alone
+// (philox_fill_rows_kernel).  Every row is checked before the first launch; 32 rows per launch.
+extern "C" int bsg_philox_normal_rows(float* x, int32_t B, int32_t M, int32_t T, const int32_t* lengths_host, const uint64_t* seeds_host,
+                                      uint32_t stream_id, void* stream) {
+  BSG_REQUIRE(x && seeds_host, "philox_normal_rows: null %s", x ? "seeds_host" : "x");
+  BSG_REQUIRE(B > 0 && M > 0 && T > 0, "philox_normal_rows: bad argument (B=%d M=%d T=%d)", B, M, T);
+  for (int b = 0; b < B; ++b) {
+    const int nb = lengths_host ? lengths_host[b] : T;
+    BSG_REQUIRE(nb >= 1 && nb <= T, "philox_normal_rows: lengths[%d]=%d outside 1..T=%d", b, nb, T);
+    BSG_REQUIRE((long long)M * nb % 4 == 0, "philox_normal_rows: row %d draws M * n = %d * %d values, no multiple of 4 (the stream is drawn four at a time)",
+                b, M, nb);
+  }
+  for (int b0 = 0; b0 < B; b0 += kPhiloxRowsPerLaunch) {
+    PhiloxRows rows{};
+    const int n = B - b0 < kPhiloxRowsPerLaunch ? B - b0 : kPhiloxRowsPerLaunch;
+    long long items = 0;   // of the row with the most: its quads and the fours of its zero tail
+    for (int r = 0; r < n; ++r) {
+      rows.seed[r] = seeds_host[b0 + r];
+      rows.len[r] = lengths_host ? lengths_host[b0 + r] : T;
+      const long long it = (long long)M * rows.len[r] / 4 + cdiv((long long)M * (T - rows.len[r]), 4);
+      if (it > items) items = it;
+    }
+    hipLaunchKernelGGL(philox_fill_rows_kernel, dim3((unsigned)cdiv(items, 256), n), dim3(256), 0, (hipStream_t)stream,
+                       x + (long long)b0 * M * T, rows, (int)M, (int)T, (unsigned)stream_id);
+    BSG_LAUNCH_CHECK();
+  }
+  return BSG_OK;
+}
+
 // the multistep blend of the newest noise prediction with n_hist older ones (p_sample_plms :168-201): 0: the prediction itself,
 // 1: (3 e0 - e1) / 2, 2: (23 e0 - 16 e1 + 5 e2) / 12, 3: (55 e0 - 59 e1 + 37 e2 - 9 e3) / 24
 static void plms_blend(int n_hist, PlmsCoef& c) {
@@ -2860,6 +2967,7 @@ extern "C" int bsg_diffnet_prepare_ragged(bsg_diffnet* h, const float* cond, con
   BSG_HIP(hipStreamSynchronize(st));   // (the previous binding's tables may still be read by launches in flight)
   TRY(grow(h, &h->rg_cap, host.size(), st));
   BSG_HIP(hipMemcpy(h->rg_dev, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice));
+  h->rg_lens.assign(lens, lens + B);
   h->bound.ragged = true;
   return BSG_OK;
 }

@@ -9,7 +9,8 @@ p_sample_plms :168-201 over DiffNet) runs inside libbisinger_hip (``bsg_ddpm_sam
 Noise: the reference draws ``torch.randn`` per step.  Here either the caller supplies the draws
 (``noise=[K_step+1,B,M,T]``: parity mode, see bisinger_amd/synth.py) or they come from the on-device
 Philox4x32-10 stream keyed by ``seed`` and the *global* batch row (so utterance shards reproduce the
-unsharded run).
+unsharded run), or — ``row_seeds`` — every row draws from a seed of its own at its own length: what it
+draws as a lone call under that seed, whatever batch it sits in (``bsg_ddpm_sample_rows``).
 """
 from ctypes import POINTER, byref, c_float, cast
 
@@ -119,18 +120,24 @@ class GaussianDiffusion(nn.Module):
 
     # ------------------------------------------------------------------ samplers
     @torch.no_grad()
-    def sample(self, cond, x, noise=None, seed=0, row0=0, B_total=None, n_steps=None, lengths=None, cond_tok=None, tok=None):
+    def sample(self, cond, x, noise=None, seed=0, row0=0, B_total=None, n_steps=None, lengths=None, cond_tok=None, tok=None,
+               row_seeds=None):
         """Run the inference loop (:258-267) from ``x`` ([B,1,M,T], modified in place) under ``cond`` [B,H,T].
         ``lengths`` (B ints): a ragged batch — row b is decoded on its first lengths[b] frames as if it were alone at T = lengths[b], and x
         beyond is left as given (INTEGRATION.md "Ragged batches").  Philox draws keep their index (global row, padded stride T), so a
         row's frames see the draws of the padded batch; the row-by-row fallback (a handle without the ragged launch:
         DiffNet.ragged_native) runs each row at T = lengths[b] and so draws other values — supplied ``noise`` gives the same result on
-        both paths.
+        both paths, and so does ``row_seeds``.
+        ``row_seeds`` (B ints; not with ``noise``): row b's draws of every step come from the Philox stream of row_seeds[b] at the row's
+        own length — bit for bit the draws of ``sample(seed=row_seeds[b])`` on that row alone at T = lengths[b] (``bsg_ddpm_sample_rows``;
+        the row-by-row fallback calls exactly that).  ``seed``, ``row0`` and ``B_total`` are not read then.
         ``cond_tok`` [B,K,H] with ``tok`` [B,T] (the front's token rows and mel2ph): the same condition per token,
         cond[b, :, f] == cond_tok[b, tok[b, f]]; the WaveNet denoiser then binds the token rows (DiffNet.prepare_tokens) and ``cond`` is
         not read.  Not with ``lengths``."""
-        lib = _lib.load()
         B, _, M, T = x.shape
+        if row_seeds is not None:
+            row_seeds = _lib.row_seeds_list(row_seeds, B, 'sample()', {'noise': noise})
+        lib = _lib.load()
         assert x.is_contiguous() and x.dtype == torch.float32
         if hparams.get('pndm_speedup') and (n_steps is not None or noise is not None):
             raise ValueError('sample(): the PLMS loop (pndm_speedup) is deterministic after x_T and always runs the whole '
@@ -187,6 +194,8 @@ class GaussianDiffusion(nn.Module):
                         i = t - 1 - k
                         eps = self.denoise_fn(x, tt(i), cond)
                         nz = None if noise is None else noise[k].contiguous()
+                        if row_seeds is not None:   # the step's draws, every row from its own stream (stream id i + 1, as in-kernel)
+                            nz = _lib.philox_normal_rows(torch.empty_like(x), M, T, None, row_seeds, i + 1)
                         _lib.check(lib.bsg_ddpm_step(_lib.ptr(x), _lib.ptr(eps.contiguous()), _lib.ptr(nz), byref(s), i, x.numel(), seed,
                                                      row0 * M * T, _lib.stream_ptr()), 'bsg_ddpm_step')
             # this denoiser is GEMMs only: the range guard of the split-fp16 GEMMs (an operand beyond the fp16 range is counted, not
@@ -211,6 +220,9 @@ class GaussianDiffusion(nn.Module):
                         if hparams.get('pndm_speedup'):
                             _lib.check(lib.bsg_plms_sample(h, byref(s), _lib.ptr(xb), t, int(hparams['pndm_speedup']), 1, nf,
                                                            _lib.stream_ptr()), 'bsg_plms_sample')
+                        elif row_seeds is not None:   # the lone call under the row's seed: the native path's draws by construction
+                            _lib.check(lib.bsg_ddpm_sample(h, byref(s), _lib.ptr(xb), None, row_seeds[b], t - 1, n, 1, nf, 0, 1,
+                                                           _lib.stream_ptr()), 'bsg_ddpm_sample')
                         else:
                             nb = None if noise is None else noise[:, b:b + 1, :, :nf].contiguous()
                             _lib.check(lib.bsg_ddpm_sample(h, byref(s), _lib.ptr(xb), _lib.ptr(nb), seed, t - 1, n, 1, nf, row0 + b,
@@ -220,6 +232,9 @@ class GaussianDiffusion(nn.Module):
                 elif hparams.get('pndm_speedup'):
                     _lib.check(lib.bsg_plms_sample(h, byref(s), _lib.ptr(x), t, int(hparams['pndm_speedup']), B, T,
                                                    _lib.stream_ptr()), 'bsg_plms_sample')
+                elif row_seeds is not None:
+                    _lib.check(lib.bsg_ddpm_sample_rows(h, byref(s), _lib.ptr(x), _lib.seeds_array(row_seeds), t - 1, n, B, T,
+                                                        _lib.stream_ptr()), 'bsg_ddpm_sample_rows')
                 else:
                     _lib.check(lib.bsg_ddpm_sample(h, byref(s), _lib.ptr(x), _lib.ptr(noise), seed, t - 1, n, B, T, row0,
                                                    B if B_total is None else B_total, _lib.stream_ptr()), 'bsg_ddpm_sample')
@@ -260,7 +275,7 @@ class GaussianDiffusion(nn.Module):
     # ------------------------------------------------------------------ reference forward (:230-273)
     @torch.no_grad()
     def forward(self, txt_tokens, mel2ph=None, spk_embed=None, ref_mels=None, f0=None, uv=None, energy=None,
-                infer=False, noise=None, seed=None, rows=None, ragged=False, ragged_front=False, **kwargs):
+                infer=False, noise=None, seed=None, rows=None, ragged=False, ragged_front=False, row_seeds=None, **kwargs):
         """Extensions over the reference signature: ``noise`` (supplied draws, parity mode), ``seed`` (Philox
         key, default hparams['seed']) and ``rows`` (slice of the batch this process generates; outputs then
         have len(rows) rows and reproduce the same rows of the unsharded call — SURVEY.md §8e).
@@ -274,9 +289,16 @@ class GaussianDiffusion(nn.Module):
         ``ragged_front=True`` (independent of ``ragged``): the FastSpeech2 front runs every row as that utterance alone
         (``FastSpeech2MIDI.forward(ragged=True)`` / ``FastSpeech2.forward(ragged=True)``): ``decoder_inp``, ``fs2_mel``, the predicted
         durations and pitch no longer depend on the batch around a row.  Not with ``rows``.  The sampler's Philox draws stay indexed by
-        global row and padded stride, so the final ``mel_out`` equals the lone call's only with supplied ``noise``."""
+        global row and padded stride, so the final ``mel_out`` equals the lone call's only with supplied ``noise`` — or with
+        ``row_seeds``.
+        ``row_seeds`` (one int per row of the WHOLE batch — with ``rows`` indexed by global row; not with ``noise``): row b draws x_T
+        (stream 0) and every step's noise from the Philox stream of row_seeds[b] at its own length (``ragged``: its frame count, else
+        T): what ``forward`` draws for that utterance alone under ``seed=row_seeds[b]``.  With every ragged switch on, nothing then
+        ties a batched row to its batch."""
         if not infer:
             raise NotImplementedError('training (p_losses) is outside the accelerated hot path (SURVEY.md §8)')
+        if row_seeds is not None:
+            row_seeds = _lib.row_seeds_list(row_seeds, txt_tokens.shape[0], 'forward()', {'noise': noise})
         if ragged and rows is not None:
             raise NotImplementedError('forward(ragged=True, rows=...): sharded ragged batches are not supported')
         if ragged_front and rows is not None:
@@ -285,12 +307,12 @@ class GaussianDiffusion(nn.Module):
         # split-fp16 GEMMs repeats all of it with THAT handle (FS2's or the denoiser's) on the fp32 matrix pipe (_lib.range_guarded; the nested
         # guards register their handles with this one and leave the check to it)
         return _lib.range_guarded(lambda: self._forward_infer(txt_tokens, mel2ph, spk_embed, ref_mels, f0, uv, energy, noise, seed, rows,
-                                                              ragged=ragged, ragged_front=ragged_front, **kwargs),
+                                                              ragged=ragged, ragged_front=ragged_front, row_seeds=row_seeds, **kwargs),
                                   'GaussianDiffusion.forward', device=self,
                                   owners=tuple(m for m in (self.fs2, self.denoise_fn) if isinstance(m, _lib.GemmGuarded)))
 
     def _forward_infer(self, txt_tokens, mel2ph, spk_embed, ref_mels, f0, uv, energy, noise, seed, rows, ragged=False, ragged_front=False,
-                       **kwargs):
+                       row_seeds=None, **kwargs):
         B_total = txt_tokens.shape[0]
         row0 = 0
         if rows is not None:
@@ -306,6 +328,12 @@ class GaussianDiffusion(nn.Module):
         t = self.K_step
         seed = int(hparams.get('seed', 1234)) if seed is None else int(seed)
         M = self.mel_bins
+        lengths = None
+        if ragged:
+            mel2ph = ret['mel2ph'] if mel2ph is None else mel2ph      # (the predicted one also masks mel_out below)
+            lengths = ragged_lengths(mel2ph)
+        if row_seeds is not None:
+            row_seeds = row_seeds[row0:row0 + B]
         if noise is not None:
             noise = noise.to(cond.device, torch.float32)
             if rows is not None and noise.shape[1] == B_total:
@@ -313,6 +341,9 @@ class GaussianDiffusion(nn.Module):
             # x_T is updated in place by the sampler: it must be a COPY — `noise` may be the caller's own device tensor (.to() and the
             # row slice are views), and a second call with the same tensor would start from the first call's result
             draw0, steps = noise[0][:, None].clone(memory_format=torch.contiguous_format), noise[1:]
+        elif row_seeds is not None:   # x_T of every row from the row's own stream 0, at the row's own length (0 beyond)
+            draw0 = _lib.philox_normal_rows(torch.empty(B, 1, M, T, device=cond.device), M, T, lengths, row_seeds, 0)
+            steps = None
         else:
             off = row0 * M * T
             draw0 = self.philox_normal((B, 1, M, T), cond.device, seed, 0, off)
@@ -328,16 +359,12 @@ class GaussianDiffusion(nn.Module):
                 _lib.check(lib.bsg_mel_start(_lib.ptr(ret['mel_out'].contiguous()), _lib.ptr(smin), _lib.ptr(smax), _lib.ptr(draw0),
                                              float(self.sqrt_alphas_cumprod[t - 1]), float(self.sqrt_one_minus_alphas_cumprod[t - 1]),
                                              _lib.ptr(x), B, M, T, _lib.stream_ptr()), 'bsg_mel_start')
-        lengths = None
-        if ragged:
-            mel2ph = ret['mel2ph'] if mel2ph is None else mel2ph      # (the predicted one also masks mel_out below)
-            lengths = ragged_lengths(mel2ph)
         # the MIDI front without a frame-level pitch embedding gives the condition per token as well: the denoiser binds that
         # (the rows are the front's hand-over to the denoiser, not a result: the returned dict keeps the reference's keys)
         cond_tok = ret.pop('cond_tok', None)
         tok = ret['mel2ph'] if cond_tok is not None and not ragged else None
         x = self.sample(cond, x, noise=None if hparams.get('pndm_speedup') else steps, seed=seed, row0=row0, B_total=B_total,
-                        lengths=lengths, cond_tok=cond_tok if tok is not None else None, tok=tok)
+                        lengths=lengths, cond_tok=cond_tok if tok is not None else None, tok=tok, row_seeds=row_seeds)
         out = torch.empty(B, T, M, device=cond.device)
         m2p = None if mel2ph is None else mel2ph.to(device=cond.device, dtype=torch.long).contiguous()
         with torch.cuda.device(cond.device):

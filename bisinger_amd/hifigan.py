@@ -174,7 +174,7 @@ class HifiGanGenerator(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         return hd
 
     @torch.no_grad()
-    def forward(self, x, f0=None, rand_ini=None, noise=None, seed=0, lengths=None):
+    def forward(self, x, f0=None, rand_ini=None, noise=None, seed=0, lengths=None, row_seeds=None):
         """x [B,80,T] (, f0 [B,T]) -> [B,1,T*hop]   (hifigan.py:144-173).
         NSF draws (source.py:53, :130): supplied (``rand_ini`` [B,9], ``noise`` [B,T*hop,9]) or generated
         (numpy RandomState(seed) for the 9 initial phases, the library's Philox stream 0x4E5346 for the noise).
@@ -182,16 +182,23 @@ class HifiGanGenerator(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
         ``lengths`` (list or tensor of B ints, 1 <= lengths[b] <= T): a ragged batch — row b is vocoded at its own length, as the reference
         vocodes each utterance alone (vocoders/hifigan.py:55-69): ``out[b, 0, :lengths[b]*hop]`` is the generator applied to
         ``x[b, :, :lengths[b]]`` (and ``f0[b, :lengths[b]]``) alone, the rest of the row is 0, and nothing at or beyond a row's end is read.
-        Drawn NSF noise keeps its Philox index (row, padded stride): a row sees the draws it sees in the padded call.  ``None``: the padded
-        call, every row at T frames."""
+        Drawn NSF noise keeps its Philox index (row, padded stride): a row sees the draws it sees in the padded call — unless
+        ``row_seeds`` keys it by row (below).  ``None``: the padded call, every row at T frames.
+
+        ``row_seeds`` (B ints; not with supplied ``rand_ini`` / ``noise``): row b's NSF draws are those of the lone call on that utterance
+        under ``seed=row_seeds[b]`` — its initial phases from RandomState(row_seeds[b] & 0x7FFFFFFF), its noise the first
+        lengths[b]*hop*NH (without ``lengths``: T*hop*NH) values of the Philox stream (row_seeds[b], 0x4E5346), 0 beyond
+        (``bsg_philox_normal_rows``)."""
+        if row_seeds is not None:
+            row_seeds = _lib.row_seeds_list(row_seeds, int(x.shape[0]), 'HifiGanGenerator.forward', {'rand_ini': rand_ini, 'noise': noise})
         if lengths is not None:      # checked before anything touches the GPU: a refused call builds no handle and writes nothing
             lengths = _lib.row_lengths(lengths, int(x.shape[0]), 'HifiGanGenerator.forward', T=int(x.shape[-1]))
         # range guard of the split-fp16 ResBlock pairs (an activation beyond the fp16 range is counted by the kernels, never clipped):
         # read once per outermost call; on an event the call (ragged or not) is repeated on the fp32 matrix pipe (_lib.range_guarded)
-        return _lib.range_guarded(lambda: self._forward(x, f0, rand_ini, noise, seed, lengths), 'HifiGanGenerator.forward', device=self,
+        return _lib.range_guarded(lambda: self._forward(x, f0, rand_ini, noise, seed, lengths, row_seeds), 'HifiGanGenerator.forward', device=self,
                                   owners=(self,))
 
-    def _forward(self, x, f0, rand_ini, noise, seed, lengths=None):
+    def _forward(self, x, f0, rand_ini, noise, seed, lengths=None, row_seeds=None):
         x = x.contiguous().float()
         B, M, T = x.shape
         assert M == 80
@@ -206,6 +213,11 @@ class HifiGanGenerator(nn.Module, _lib.HandleOwner, _lib.GemmGuarded):
                     raise _lib.BsgError('this generator has the NSF source (use_pitch_embed): f0 is required')
                 NH = self.harmonic_num + 1
                 f0 = f0.to(x.device, torch.float32).contiguous()
+                if row_seeds is not None:   # every row's draws as the lone call's under the row's seed (exclusive with supplied ones)
+                    rand_ini = torch.from_numpy(np.concatenate([np.random.RandomState(sd & 0x7FFFFFFF).uniform(size=(1, NH))
+                                                                for sd in row_seeds]).astype(np.float32))
+                    noise = _lib.philox_normal_rows(torch.empty(B, T * hop, NH, device=x.device), 1, T * hop * NH,
+                                                    None if lengths is None else [n * hop * NH for n in lengths], row_seeds, 0x4E5346)
                 if rand_ini is None:       # 9 initial phases per utterance: host draw, reproducible from the seed
                     rand_ini = torch.from_numpy(np.random.RandomState(seed & 0x7FFFFFFF).uniform(size=(B, NH)).astype(np.float32))
                 if noise is None:

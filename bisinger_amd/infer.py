@@ -206,10 +206,12 @@ class DiffSingerE2EInfer(BaseSVSInfer):
             self.pe.eval()
         return model
 
-    def _generate(self, sample, seed=None, ragged=False, ragged_front=False):
+    def _generate(self, sample, seed=None, ragged=False, ragged_front=False, row_seeds=None):
         kw = {'ragged': True} if ragged else {}
         if ragged_front:
             kw['ragged_front'] = True
+        if row_seeds is not None:
+            kw['row_seeds'] = row_seeds
         with torch.no_grad():
             output = self.model(sample['txt_tokens'], spk_embed=sample.get('spk_ids'), ref_mels=None, infer=True,
                                 pitch_midi=sample['pitch_midi'], midi_dur=sample['midi_dur'], is_slur=sample['is_slur'],
@@ -238,14 +240,16 @@ class DiffSingerE2EInfer(BaseSVSInfer):
         new[1:] = (d[1:] != d[:-1]) | (p[1:] != p[:-1])
         return int(np.ceil(d[new].sum() * hparams['audio_sample_rate'] / hparams['hop_size']))
 
-    def _generate_wavs(self, items, seed, ragged=False, denoise_c=None, ragged_vocoder=False, ragged_pitch=False, ragged_front=False):
+    def _generate_wavs(self, items, seed, ragged=False, denoise_c=None, ragged_vocoder=False, ragged_pitch=False, ragged_front=False,
+                       row_seeds=None):
         """One padded batch -> (list of trimmed waveforms, frames per item, padded frame count T).  ``ragged``: the mel decoder runs every
         row at its own length (GaussianDiffusion.forward(ragged=True)).  ``ragged_vocoder``: the HiFi-GAN generator (plain or NSF) runs every
         row at its own length too (HifiGanGenerator.forward(lengths=)), as the reference vocodes each utterance alone; False: it runs the
         padded batch, whose zero frames beyond a row's end reach back into the row's last ~9 frames.  ``ragged_pitch``: the pitch extractor
         runs every row at its own length (PitchExtractor.forward(lengths=)), as the reference extracts each utterance's f0 alone; False: it
         runs the padded mel, whose padding enters GroupNorm's statistics of every shorter row.  ``denoise_c`` > 0: the padded batch of
-        waveforms goes through ONE launch of the spectral post-filter (vocoders.denoise), every row at its own length."""
+        waveforms goes through ONE launch of the spectral post-filter (vocoders.denoise), every row at its own length.  ``row_seeds``
+        (one int per item of THIS batch, in the batch's order): the sampler and the NSF source draw every row from its own seed."""
         if ragged_pitch and not hparams.get('pe_enable'):      # refused before any model runs
             raise ValueError('forward_batch(ragged_pitch=True): there is no pitch extractor to run (pe_enable is off)')
         if ragged_vocoder:      # refused before any model runs
@@ -255,7 +259,8 @@ class DiffSingerE2EInfer(BaseSVSInfer):
                 raise NotImplementedError(f"forward_batch(ragged_vocoder=True): vocoder '{name or type(self.vocoder).__name__}' "
                                           f'({type(self.vocoder).__name__}) has no ragged forward; only the HiFi-GAN generator, plain or NSF, has')
         sample = self.collate(items)
-        output = self._generate(sample, seed, ragged, **({'ragged_front': True} if ragged_front else {}))
+        output = self._generate(sample, seed, ragged, **({'ragged_front': True} if ragged_front else {}),
+                                **({} if row_seeds is None else {'row_seeds': row_seeds}))
         mel, mel2ph = output['mel_out'], output['mel2ph']
         hop = int(np.prod(self.vocoder.h['upsample_rates']))
         n_frames = (mel2ph > 0).sum(-1).tolist()
@@ -266,6 +271,8 @@ class DiffSingerE2EInfer(BaseSVSInfer):
                 f0 = output.get('f0_denorm')
             assert f0 is not None, 'use_nsf needs an f0: enable pe_enable (a-*.py:629-632)'
             vkw = {'lengths': n_frames} if ragged_vocoder else {}
+            if row_seeds is not None:
+                vkw['row_seeds'] = row_seeds
             wav = self.vocoder(mel.transpose(2, 1), f0, seed=int(hparams.get('seed', 1234) if seed is None else seed), **vkw)[:, 0]
         else:
             wav = self.vocoder(mel.transpose(2, 1), **({'lengths': n_frames} if ragged_vocoder else {}))[:, 0]
@@ -275,7 +282,7 @@ class DiffSingerE2EInfer(BaseSVSInfer):
         return [wav[i, :n * hop].cpu().numpy() for i, n in enumerate(n_frames)], n_frames, int(mel.shape[1])
 
     def forward_batch(self, items, seed=None, max_frames=None, max_sentences=None, ragged=False, denoise_c=None, ragged_vocoder=False,
-                      ragged_pitch=False, ragged_front=False):
+                      ragged_pitch=False, ragged_front=False, seeds=None):
         """Batched generation: list of items -> list of 1-D waveforms (in the order given), each trimmed to its utterance.
 
         With ``max_frames`` (budget on padded frames per batch: rows x longest row) and/or ``max_sentences`` the items are
@@ -311,7 +318,17 @@ class DiffSingerE2EInfer(BaseSVSInfer):
         alone (``GaussianDiffusion.forward(ragged_front=True)``): the condition, the predicted durations and the adaptor's f0 are what
         ``forward_model`` computes for the item — its own ESM instead of a softmax over the bucket, zeros instead of LayerNorm's bias in the
         padding the convolutions reach — and no padded token or frame is computed.  The sampler's Philox draws stay indexed by the row's
-        place in the bucket, so the waveform still differs from ``forward_model``'s.  False (default): every result as before."""
+        place in the bucket, so the waveform still differs from ``forward_model``'s — unless ``seeds`` keys them by item (below).
+        False (default): every result as before.
+
+        ``seeds`` (one int per item, in the order given; None: ``seed`` keeps its meaning): item i draws — x_T, every sampler step, the
+        NSF source's phases and noise — from its own seed at its own length, whatever bucket and row it lands in
+        (``GaussianDiffusion.forward(row_seeds=)``, ``HifiGanGenerator.forward(row_seeds=)``).  With all four ragged switches on, item
+        i's waveform is then ``forward_model(items[i], seed=seeds[i])``'s to rounding, and re-bucketing the list (``max_sentences``,
+        another item, another GPU count) no longer changes it."""
+        if seeds is not None:
+            from . import _lib
+            seeds = _lib.row_seeds_list(seeds, len(items), 'forward_batch(seeds=)')
         est = [self.estimate_frames(it) for it in items]
         if ragged and max_frames is not None:
             raise ValueError('forward_batch(ragged=True): buckets by max_sentences only; max_frames budgets padded frames')
@@ -322,7 +339,8 @@ class DiffSingerE2EInfer(BaseSVSInfer):
         wavs, frames = [None] * len(items), [0] * len(items)
         padded = groups = tiles = 0
         for b in buckets:
-            w, nf, T = self._generate_wavs([items[i] for i in b], seed, ragged, denoise_c, ragged_vocoder, ragged_pitch, ragged_front)
+            w, nf, T = self._generate_wavs([items[i] for i in b], seed, ragged, denoise_c, ragged_vocoder, ragged_pitch, ragged_front,
+                                           row_seeds=None if seeds is None else [seeds[i] for i in b])
             padded += T * len(b)
             if ragged:
                 from .diffnet import ragged_plan

@@ -194,7 +194,7 @@ class ParallelWaveGANGenerator(nn.Module, _lib.HandleOwner):
         return int(_lib.load().bsg_pwg_last_tiles(self._h)) if self._h is not None else 0
 
     @torch.no_grad()
-    def forward_ragged(self, x, mel, pitch=None, *, lengths, seed=None):
+    def forward_ragged(self, x, mel, pitch=None, *, lengths, seed=None, row_seeds=None):
         """A ragged batch: x [B,1,T*hop] noise (None: drawn on the device from the Philox stream of ``seed``), mel [B,80,T] UNPADDED,
         pitch [B,T] int64 with use_pitch_embed, ``lengths`` a list or tensor of B ints in 1 .. T -> [B,1,T*hop].
 
@@ -203,8 +203,12 @@ class ParallelWaveGANGenerator(nn.Module, _lib.HandleOwner):
         the rest of the row is 0, and nothing at or beyond a row's end is read.  A separate method, not a keyword of ``forward``: there
         ``c`` is the mel the caller already edge-padded, here the library pads each row at its own end.  With ``x=None`` the draws keep
         the index of the padded call at (B, T), element b*T*hop + t: a batched row with drawn noise is reproducible from the seed but
-        is not the waveform of the lone call with that seed."""
+        is not the waveform of the lone call with that seed.  ``row_seeds`` (B ints; with ``x=None`` only) is the way out: row b's noise
+        is the first lengths[b]*hop values of the Philox stream (row_seeds[b], 0x505747) — what ``forward(None, ..., seed=row_seeds[b])``
+        draws for the utterance alone (``bsg_philox_normal_rows``) — so the row IS that lone call, bit for bit."""
         B, A, T = (int(v) for v in mel.shape)
+        if row_seeds is not None:
+            row_seeds = _lib.row_seeds_list(row_seeds, B, 'ParallelWaveGANGenerator.forward_ragged', {'x': x})
         # checked before the handle is built and before the output exists: without a GPU the refusal is the length's
         lengths = _lib.row_lengths(lengths, B, 'ParallelWaveGANGenerator.forward_ragged', T=T)
         hd = self.handle()
@@ -215,8 +219,10 @@ class ParallelWaveGANGenerator(nn.Module, _lib.HandleOwner):
         if x is not None:
             x = x.to(dev, torch.float32).contiguous()
             assert tuple(x.shape) == (B, 1, L), (tuple(x.shape), (B, 1, L))
+        elif row_seeds is not None:
+            x = _lib.philox_normal_rows(torch.empty(B, 1, L, device=dev), 1, L, [n * self.hop_size for n in lengths], row_seeds, 0x505747)
         elif seed is None:
-            raise _lib.BsgError('ParallelWaveGANGenerator.forward_ragged: x=None needs seed= (the noise is drawn on the device)')
+            raise _lib.BsgError('ParallelWaveGANGenerator.forward_ragged: x=None needs seed= or row_seeds= (the noise is drawn on the device)')
         if self.use_pitch_embed:
             if pitch is None:
                 raise _lib.BsgError('this generator has the pitch front (use_pitch_embed): pitch is required')

@@ -275,13 +275,17 @@ class PWG(BaseVocoder):
             y = self.model(z, c, p, seed=int(hparams.get('seed', 1234) if seed is None else seed)).view(-1)
         return y.cpu().numpy()
 
-    def spec2wav_batch(self, mels, f0s=None, zs=None, seed=None):
+    def spec2wav_batch(self, mels, f0s=None, zs=None, seed=None, seeds=None):
         """Many utterances in ONE ragged forward: mels a list of [T_i,80] (, f0s a list of [T_i], zs a list of [T_i*hop]) -> a list of
         wav [T_i*hop] in the order given.  Per item: the scaler transform and ``f0_to_coarse``, as ``spec2wav`` does them; then the items
         are padded to the longest, run through ``forward_ragged`` (which edge-pads every item at its own end) and trimmed.  With ``zs``
         item i equals ``spec2wav(mels[i], f0=f0s[i], z=zs[i])`` bit for bit.  Without, the noise is drawn on the device from the Philox
         stream of ``seed`` (default hparams['seed']) at the index of the padded batch: reproducible, but item i is then NOT the waveform
-        ``spec2wav(mels[i], seed=seed)`` draws."""
+        ``spec2wav(mels[i], seed=seed)`` draws.  ``seeds`` (one int per item; not with ``zs``) is the way out: item i draws the Philox
+        stream of seeds[i] at its own length (``forward_ragged(row_seeds=)``) and equals ``spec2wav(mels[i], f0=f0s[i], seed=seeds[i])``
+        bit for bit, whatever it is batched with."""
+        if seeds is not None:
+            seeds = _lib.row_seeds_list(seeds, len(mels), 'PWG.spec2wav_batch', {'zs': zs})
         hop = self.config['hop_size']
         cs = [np.asarray(m) for m in mels]
         if self.scaler is not None:
@@ -308,7 +312,7 @@ class PWG(BaseVocoder):
             z = torch.from_numpy(z).to(self.device)
         with torch.no_grad():
             y = self.model.forward_ragged(z, torch.from_numpy(mel).to(self.device), pitch, lengths=lengths,
-                                          seed=int(hparams.get('seed', 1234) if seed is None else seed))
+                                          seed=int(hparams.get('seed', 1234) if seed is None else seed), row_seeds=seeds)
         y = y.cpu().numpy()
         return [y[b, 0, :lengths[b] * hop].copy() for b in range(B)]
 

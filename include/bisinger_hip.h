@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define BSG_ABI_VERSION 21
+#define BSG_ABI_VERSION 22
 
 #define BSG_OK 0
 #define BSG_EINVAL (-22)  /* bad argument / shape the kernels do not support            */
@@ -83,7 +83,8 @@ int bsg_diffnet_forward(bsg_diffnet* h, const float* x, const int64_t* t, float*
  * bsg_diffnet_prepare_ragged binds cond [B,H,T] (as bsg_diffnet_prepare, which it calls) together with lens (HOST [B], 1 <= lens[b] <= T).
  *   The bsg_diffnet_forward / bsg_ddpm_sample / bsg_plms_sample calls that follow at this (B,T) decode row b on frames [0, lens[b]) as if it
  *   were alone at T = lens[b]: nothing of frames >= lens[b] is read by a frame below it.  T stays the row stride of x, eps, noise and cond.
- *   eps is 0 at frames >= lens[b]; the samplers leave x there as the caller gave it.  Philox draws keep their index (global row, stride T).
+ *   eps is 0 at frames >= lens[b]; the samplers leave x there as the caller gave it.  Philox draws keep their index (global row, stride T);
+ *   bsg_ddpm_sample_rows (ABI v22) draws every row from its own seed at its own length instead: the lone call's draws.
  *   Whole rows are packed into launch groups of at most one 64-frame tile per CU (bsg_ragged_plan); the groups run one after another on
  *   `stream`.  BSG_EINVAL for a row longer than one group; BSG_ESTATE under stream capture (binding and calls).  Both configurations:
  *   fp32 (the ragged 16-row stack launch) and bf16 (bsg_diffnet_set_compute BF16: the ragged bf16 stack launch and bf16 step tail).
@@ -168,6 +169,26 @@ int bsg_plms_step(const float* x, float* x_out, const float* e0, const float* e1
  * ((offset+i)/4, stream_id, 0, 0), key = seed (x_T under gaussian_start uses stream_id 0, the step with
  * timestep i uses stream_id i+1).  n and offset must be multiples of 4. */
 int bsg_philox_normal(float* x, int64_t n, uint64_t seed, uint32_t stream_id, uint64_t offset, void* stream);
+
+/* ABI v22, row-keyed draws: a batched row draws what it draws alone.  The unkeyed sampler addresses a step's draws by (global row, padded
+ * stride T) under ONE seed, so a row's noise depends on where it sits in its batch and on the batch's longest row.  Keyed, row b has a seed
+ * of its own and draws element m n_b + c of the stream (seeds[b], stream_id) at frame c of mel bin m — the lone call's draw at T = n_b,
+ * row0 = 0 under seed = seeds[b].
+ * bsg_philox_normal_rows: x [B,M,T]; n_b = lengths_host[b] (HOST [B]; NULL: every row is T long); seeds_host: HOST [B].
+ *   x[b][m][c] for c < n_b is, bit for bit, what bsg_philox_normal(y, M n_b, seeds_host[b], stream_id, 0) writes to y[m n_b + c]; x[b][m][c] = 0
+ *   for n_b <= c < T.  M = 1 covers the flat layouts whose lone prefix is contiguous (the NSF noise [B][L NH], Parallel WaveGAN's z [B][L]).
+ *   Seeds and lengths travel in the launches' arguments (32 rows per launch): no device table, no copy, no host synchronisation — the
+ *   call only enqueues and can be captured.  BSG_EINVAL, naming the row, with nothing enqueued: x or seeds_host NULL, B <= 0, n_b outside
+ *   1..T, M n_b no multiple of 4 (bsg_philox_normal refuses that n as well).
+ * bsg_ddpm_sample_rows: bsg_ddpm_sample(h, s, x, NULL, ., t_start, n_steps, B, T, 0, B, stream) with the draws of the step at timestep i
+ *   from bsg_philox_normal_rows(stream id i + 1) over the row lengths of the handle's binding (bsg_diffnet_prepare_ragged's lens; T behind
+ *   any other prepare): filled into a handle-owned [B,M,T] buffer in front of the step's launches and read by them as supplied noise.  Where
+ *   the loop runs as two half-batch chains each half's draws are enqueued on that half's stream.  The buffer is allocated by the first
+ *   eager call of a shape (BSG_EINVAL under stream capture until then).  The same launch forms as bsg_ddpm_sample with `noise`. */
+int bsg_philox_normal_rows(float* x, int32_t B, int32_t M, int32_t T, const int32_t* lengths_host, const uint64_t* seeds_host,
+                           uint32_t stream_id, void* stream);
+int bsg_ddpm_sample_rows(bsg_diffnet* h, const bsg_schedule* s, float* x, const uint64_t* seeds_host, int32_t t_start, int32_t n_steps,
+                         int32_t B, int32_t T, void* stream);
 
 /* Glue of GaussianDiffusion.forward around the loop (shallow_diffusion_tts.py:244-272), all [B,M,T] <-> [B,T,M]:
  *   bsg_mel_start : x = sqrt_ac * norm_spec(fs2_mel)^T + sqrt_1m_ac * noise      (q_sample at t = K_step-1, :249-252)
