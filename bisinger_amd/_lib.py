@@ -209,6 +209,11 @@ _SIGS = {
     # ABI v22: row-keyed draws; lengths_host / seeds_host: B int32 / B uint64 on the host
     'bsg_philox_normal_rows': (c_int32, [c_void_p, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_uint64), c_uint32, c_void_p]),
     'bsg_ddpm_sample_rows': (c_int32, [c_void_p, POINTER(Schedule), c_void_p, POINTER(c_uint64), c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    # ragged batches through the FFT denoiser, and its sampler loops in the library (additions to ABI v22)
+    'bsg_fftden_prepare_ragged': (c_int32, [c_void_p, c_void_p, POINTER(c_int32), c_int32, c_int32, c_void_p]),
+    'bsg_fftden_ddpm_sample': (c_int32, [c_void_p, POINTER(Schedule), c_void_p, c_void_p, c_uint64, POINTER(c_uint64), c_int32, c_int32, c_int32,
+                                         c_int32, c_int32, c_int32, c_void_p]),
+    'bsg_fftden_plms_sample': (c_int32, [c_void_p, POINTER(Schedule), c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
 }
 
 _lib = None

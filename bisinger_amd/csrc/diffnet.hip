@@ -2289,17 +2289,6 @@ extern "C" int bsg_diffnet_residual_layer(bsg_diffnet* h, int32_t layer, const f
   return launch_layer(h, plan, layer, x_in, (const long long*)t, 0, x_out, skip, B, T, (hipStream_t)stream);
 }
 
-static int check_schedule(const bsg_schedule* s, const char* who, bool plms) {
-  if (!s || s->num_timesteps <= 0) { set_error("%s: bad schedule", who); return BSG_EINVAL; }
-  if (plms ? !s->alphas_cumprod
-           : !(s->sqrt_recip_alphas_cumprod && s->sqrt_recipm1_alphas_cumprod && s->posterior_mean_coef1 &&
-               s->posterior_mean_coef2 && s->sigma)) {
-    set_error("%s: schedule array missing", who);
-    return BSG_EINVAL;
-  }
-  return BSG_OK;
-}
-
 // rows [plan.row0, plan.row0 + B) of a sampler call's batch on stream st: their stack plan, the tail behind it and the tail's arguments
 struct SubBatch { int B; hipStream_t st; StackPlan plan; TailPlan tail; TailArgs args; };
 
@@ -2807,15 +2796,6 @@ extern "C" int bsg_philox_normal_rows(float* x, int32_t B, int32_t M, int32_t T,
     BSG_LAUNCH_CHECK();
   }
   return BSG_OK;
-}
-
-// the multistep blend of the newest noise prediction with n_hist older ones (p_sample_plms :168-201): 0: the prediction itself,
-// 1: (3 e0 - e1) / 2, 2: (23 e0 - 16 e1 + 5 e2) / 12, 3: (55 e0 - 59 e1 + 37 e2 - 9 e3) / 24
-static void plms_blend(int n_hist, PlmsCoef& c) {
-  if (n_hist <= 0) { c.inv = 1.f; }
-  else if (n_hist == 1) { c.w0 = 3.f; c.inv = 2.f; }
-  else if (n_hist == 2) { c.w0 = 23.f; c.w1 = -16.f; c.w2 = 5.f; c.inv = 12.f; }
-  else { c.w0 = 55.f; c.w1 = -59.f; c.w2 = 37.f; c.w3 = -9.f; c.inv = 24.f; }
 }
 
 extern "C" int bsg_plms_sample(bsg_diffnet* h, const bsg_schedule* s, float* x, int32_t K_step, int32_t interval, int32_t B,

@@ -106,6 +106,27 @@ __device__ __forceinline__ float philox_normal1(unsigned long long seed, unsigne
 }
 
 
+// Host side of the sampler entries of both denoisers (diffnet.hip: bsg_ddpm_sample / bsg_plms_sample; fs2.hip: bsg_fftden_*_sample)
+inline int check_schedule(const bsg_schedule* s, const char* who, bool plms) {
+  if (!s || s->num_timesteps <= 0) { set_error("%s: bad schedule", who); return BSG_EINVAL; }
+  if (plms ? !s->alphas_cumprod
+           : !(s->sqrt_recip_alphas_cumprod && s->sqrt_recipm1_alphas_cumprod && s->posterior_mean_coef1 &&
+               s->posterior_mean_coef2 && s->sigma)) {
+    set_error("%s: schedule array missing", who);
+    return BSG_EINVAL;
+  }
+  return BSG_OK;
+}
+
+// the multistep blend of the newest noise prediction with n_hist older ones (p_sample_plms :168-201): 0: the prediction itself,
+// 1: (3 e0 - e1) / 2, 2: (23 e0 - 16 e1 + 5 e2) / 12, 3: (55 e0 - 59 e1 + 37 e2 - 9 e3) / 24
+inline void plms_blend(int n_hist, PlmsCoef& c) {
+  if (n_hist <= 0) { c.inv = 1.f; }
+  else if (n_hist == 1) { c.w0 = 3.f; c.inv = 2.f; }
+  else if (n_hist == 2) { c.w0 = 23.f; c.w1 = -16.f; c.w2 = 5.f; c.inv = 12.f; }
+  else { c.w0 = 55.f; c.w1 = -59.f; c.w2 = 37.f; c.w3 = -9.f; c.inv = 24.f; }
+}
+
 // the split-fp16 tails' weight fragments and scales (diffnet_h2.hip)
 int h2_tail_pack(const float* ws, const float* wo96, const float* wi96, unsigned short* out_ws, unsigned short* out_wo, unsigned short* out_wi,
                  unsigned* maxbits, float* tab, hipStream_t st);

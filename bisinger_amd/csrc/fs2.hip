@@ -24,6 +24,7 @@
 #include "bsg_common.h"
 #include "bsg_ws.h"
 #include "diffnet_res.h"
+#include "diffnet_tail.h"
 
 namespace bsg {
 namespace {
@@ -2380,6 +2381,145 @@ __global__ void gather_rows_kernel(const float* __restrict__ table, const long l
   r = r < 0 ? 0 : (r >= n_rows ? n_rows - 1 : r);
   out[i] = table[r * width + (i % width)];
 }
+
+// Ragged forms of the two layout changes (bsg_fftden_prepare_ragged): row b has lens[b] frames, the pitch of every tensor stays T.
+// in [B][R][T] -> out [B][T][R] on the frames < lens[b]: nothing at or beyond a row's end is read or written, and a tile that lies
+// beyond it returns before its first load.  Grid as transpose_brc_kernel(in, out, R, T).
+__global__ void transpose_in_rag_kernel(const float* __restrict__ in, float* __restrict__ out, int R, int T, const int* __restrict__ lens) {
+  __shared__ float tile[32][33];
+  const int b = blockIdx.z, r0 = blockIdx.y * 32, c0 = blockIdx.x * 32, nb = lens[b];
+  if (c0 >= nb) return;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 256 threads: 32 x 8
+  for (int j = ty; j < 32; j += 8) {
+    const int r = r0 + j, c = c0 + tx;
+    tile[j][tx] = (r < R && c < nb) ? in[((long long)b * R + r) * T + c] : 0.f;
+  }
+  __syncthreads();
+  for (int j = ty; j < 32; j += 8) {
+    const int c = c0 + j, r = r0 + tx;
+    if (c < nb && r < R) out[((long long)b * T + c) * R + r] = tile[tx][j];
+  }
+}
+// in [B][T][Cc] -> out [B][Cc][T]: the frames < lens[b] transposed, the frames from there to T written as 0 without a read.
+// Grid as transpose_brc_kernel(in, out, T, Cc).
+__global__ void transpose_out_rag_kernel(const float* __restrict__ in, float* __restrict__ out, int T, int Cc, const int* __restrict__ lens) {
+  __shared__ float tile[32][33];
+  const int b = blockIdx.z, r0 = blockIdx.y * 32, c0 = blockIdx.x * 32, nb = lens[b];
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  for (int j = ty; j < 32; j += 8) {
+    const int r = r0 + j, c = c0 + tx;
+    tile[j][tx] = (r < nb && c < Cc) ? in[((long long)b * T + r) * Cc + c] : 0.f;
+  }
+  __syncthreads();
+  for (int j = ty; j < 32; j += 8) {
+    const int c = c0 + j, r = r0 + tx;
+    if (c < Cc && r < T) out[((long long)b * Cc + c) * T + r] = tile[tx][j];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The sampler step's tail of the FFT denoiser, one launch (bsg_fftden_ddpm_sample / bsg_fftden_plms_sample): for a tile of 64 frames
+// of one row
+//   eps  = get_mel_out(xs)                 Linear(256 -> M) on the stack's output rows                       (candidate_decoder.py:98)
+//   x   <- p_sample(x, eps, noise)         the arithmetic of ddpm_step_kernel                   (shallow_diffusion_tts.py:149-166)
+//   or   p_sample_plms(x, eps, history)    plms_update, eps stored to the history slot as well                         (:168-201)
+// in place of the Linear launch, the [B][T][M] -> [B][M][T] transpose, the draws' launch and the generic step launch.
+// Lanes run along the frames, so x, the noise and the history are read and written as 256-byte rows of [B][M][T] and the product needs
+// no transpose: the tile of xs goes through LDS in four 64-column pieces (row pitch 65 floats: a column read is conflict free), wave w
+// keeps the M / 4 mel rows w, w + 4, .. of its 64 frames in registers, and the weight row of a mel bin is the same for a whole wave (scalar
+// loads).  Every sum is one fmaf chain in ascending k, in registers, whatever the grid: the same call gives the same bits.  The product
+// is on the vector pipe: 41 kFLOP per frame against 23 MFLOP per frame in the stack, and the fp32 matrix pipe has the same rate.
+// Ragged: a tile beyond its row's end returns before its first load, and the frames beyond it inside a tile are neither read nor written.
+// ------------------------------------------------------------------------------------------------
+constexpr int FT_F = 64, FT_KC = 64, FT_MJ = 20;   // frames per tile; staged columns per piece; mel rows per wave (M <= 4 FT_MJ)
+enum { FT_DDPM = 0, FT_PLMS = 1, FT_PLMS_CORRECT = 2 };
+struct FftTailArgs {
+  const float* xs;      // [B][T][H]: the stack's output
+  const float* w;       // get_mel_out.weight [M][H]
+  const float* bias;    // [M]
+  const float* x_in;    // [B][M][T]
+  float* x_out;         // [B][M][T] (may be x_in)
+  const int* lens;      // device, one frame count per row; null: every row has T frames
+  int T, M, mode;
+  // FT_DDPM
+  const float* noise;   // [B][M][T] supplied draws, or null: Philox
+  const unsigned long long* row_seeds;   // device [B]: row b draws element m n_b + f of the stream (row_seeds[b], stream); null: (seed, stream) at elem0 + flat index
+  unsigned long long seed, elem0;
+  unsigned stream;
+  StepCoef k;
+  // FT_PLMS: eps -> e_new (if set), x_out = plms_update(x_in, eps, h1, h2, h3).  FT_PLMS_CORRECT (the first iteration's second evaluation):
+  // x_out = plms_update(x_in, h1, eps) with the average's weights, eps is not kept
+  int n_hist;
+  PlmsCoef pk;
+  float* e_new;
+  const float *h1, *h2, *h3;
+};
+template <int MODE>   // FT_DDPM / FT_PLMS / FT_PLMS_CORRECT: one update per instantiation, so that the epilogue holds one of the three
+__global__ __launch_bounds__(256) void fftden_tail_kernel(FftTailArgs a) {
+  __shared__ float tile[FT_F][FT_KC + 1];
+  const int b = blockIdx.y, f0 = blockIdx.x * FT_F;
+  const int nb = a.lens ? a.lens[b] : a.T;
+  if (f0 >= nb) return;
+  const int live = nb - f0 < FT_F ? nb - f0 : FT_F;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  float acc[FT_MJ];
+#pragma unroll
+  for (int j = 0; j < FT_MJ; ++j) acc[j] = 0.f;
+  const float* xs = a.xs + ((long long)b * a.T + f0) * H;
+  for (int kc = 0; kc < H; kc += FT_KC) {
+    if (kc) __syncthreads();
+#pragma unroll
+    for (int i = 0; i < FT_F * FT_KC / 4 / 256; ++i) {
+      const int idx = (int)threadIdx.x + i * 256, fr = idx / (FT_KC / 4), q = idx % (FT_KC / 4);
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (fr < live) v = *reinterpret_cast<const f32x4*>(xs + (long long)fr * H + kc + q * 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) tile[fr][q * 4 + e] = v[e];
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int k4 = 0; k4 < FT_KC; k4 += 4) {   // four columns at a time: 20 weight quads fit the scalar registers
+      float av[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) av[e] = tile[lane][k4 + e];
+#pragma unroll
+      for (int j = 0; j < FT_MJ; ++j) {
+        const int m = wave + 4 * j < a.M ? wave + 4 * j : a.M - 1;   // (a row beyond M repeats the last one; its sum is not stored)
+        const float* wr = a.w + (long long)m * H + kc + k4;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[j] = fmaf(av[e], wr[e], acc[j]);
+      }
+    }
+  }
+  if (lane >= live) return;
+  const int f = f0 + lane;
+#pragma unroll
+  for (int j = 0; j < FT_MJ; ++j) {
+    const int m = wave + 4 * j;
+    if (m >= a.M) break;
+    const float eps = acc[j] + a.bias[m];
+    const long long idx = ((long long)b * a.M + m) * a.T + f;
+    const float xv = a.x_in[idx];
+    if constexpr (MODE == FT_DDPM) {
+      float nz = 0.f;
+      if (a.noise) nz = a.noise[idx];
+      else if (a.k.sigma != 0.f)
+        nz = a.row_seeds ? philox_normal1(a.row_seeds[b], a.stream, (unsigned long long)m * nb + f) : philox_normal1(a.seed, a.stream, a.elem0 + (unsigned long long)idx);
+      // every product / sum rounded separately, as ddpm_step_kernel
+      float x0 = __fsub_rn(__fmul_rn(a.k.recip, xv), __fmul_rn(a.k.recipm1, eps));
+      x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+      const float mean = __fadd_rn(__fmul_rn(a.k.pc1, x0), __fmul_rn(a.k.pc2, xv));
+      a.x_out[idx] = __fadd_rn(mean, __fmul_rn(a.k.sigma, nz));
+    } else if constexpr (MODE == FT_PLMS_CORRECT) {
+      a.x_out[idx] = plms_update(xv, a.h1[idx], eps, 0.f, 0.f, 1, a.pk, nullptr);
+    } else {
+      if (a.e_new) a.e_new[idx] = eps;
+      const float e1 = a.n_hist >= 1 ? a.h1[idx] : 0.f, e2 = a.n_hist >= 2 ? a.h2[idx] : 0.f, e3 = a.n_hist >= 3 ? a.h3[idx] : 0.f;
+      a.x_out[idx] = plms_update(xv, eps, e1, e2, e3, a.n_hist, a.pk, nullptr);
+    }
+  }
+}
 }  // namespace
 }  // namespace bsg
 
@@ -2391,15 +2531,33 @@ struct bsg_fftden {
   size_t cap = 0;   // rows (B x T) of the per-call buffers below
   int B = 0, T = 0;
   float *condpart = nullptr, *xT = nullptr, *xp = nullptr, *te = nullptr, *tvec = nullptr, *mel = nullptr;
+  // ragged binding (bsg_fftden_prepare_ragged): the rows' frame counts on the device, filled by the binding call itself (lens_fill), and
+  // once more on the host (the rows a ragged stack computes; what the row-keyed draws need to be multiples of 4)
+  bool ragged = false;
+  size_t cap_lens = 0;   // rows (B) of lens / seeds
+  int* lens = nullptr;
+  unsigned long long* seeds = nullptr;   // bsg_fftden_ddpm_sample with seeds_host: the rows' Philox keys, filled by the call itself
+  std::vector<int32_t> lens_host;
+  // sampler entries: the step part of the concat-Linear for every timestep [S][H] (every row of a sampler call shares t), and the PLMS
+  // history with the predictor's x
+  float* tvtab = nullptr;
+  size_t cap_smp = 0;    // rows (B x T) of hist / xpred
+  float *hist[4] = {nullptr, nullptr, nullptr, nullptr}, *xpred = nullptr;
 };
 
 // the handle's own per-call buffers (the FFT stack's are the core's).  `condpart` is not poisoned: bsg_fftden_prepare's result is an input
-// of every forward.  te: [B][H] used; rows >= B for any later (B,T) that fits
+// of every forward, and so are the lengths of a ragged binding.  te: [B][H] used; rows >= B for any later (B,T) that fits
 static std::vector<WsBuf> ws_table(bsg_fftden* h) {
   const size_t f = sizeof(float);
+  static const char* const smp_lazy = "fftden_plms_sample: the history buffers have to grow for this shape, which a capturing stream cannot do; run the shape once eagerly before capturing";
+  static const char* const seeds_lazy = "fftden_ddpm_sample: the rows' seeds need a buffer of this batch size, which a capturing stream cannot allocate; run the shape once eagerly before capturing";
   return {
       {&h->cap, (void**)&h->condpart, H * f},          {&h->cap, (void**)&h->xT, H * f, 0, WS_POISON},   {&h->cap, (void**)&h->xp, H * f, 0, WS_POISON},
       {&h->cap, (void**)&h->te, H * f, 0, WS_POISON},  {&h->cap, (void**)&h->tvec, H * f, 0, WS_POISON}, {&h->cap, (void**)&h->mel, h->M * f, 0, WS_POISON},
+      {&h->cap_lens, (void**)&h->lens, sizeof(int), 0, 0, seeds_lazy}, {&h->cap_lens, (void**)&h->seeds, sizeof(unsigned long long), 0, 0, seeds_lazy},
+      {&h->cap_smp, (void**)&h->hist[0], h->M * f, 0, WS_POISON, smp_lazy}, {&h->cap_smp, (void**)&h->hist[1], h->M * f, 0, WS_POISON, smp_lazy},
+      {&h->cap_smp, (void**)&h->hist[2], h->M * f, 0, WS_POISON, smp_lazy}, {&h->cap_smp, (void**)&h->hist[3], h->M * f, 0, WS_POISON, smp_lazy},
+      {&h->cap_smp, (void**)&h->xpred, h->M * f, 0, WS_POISON, smp_lazy},
   };
 }
 
@@ -2441,6 +2599,14 @@ static int fftden_load(bsg_fftden* h, int n_layers, const void* const* w, const 
   TRY(own_alloc(c->owned, &h->dtab, (size_t)h->S * H));
   TRY(linear(step_table, m0w, m0b, hid, h->S, 4 * H, H, ACT_MISH, nullptr, nullptr, st));
   TRY(linear(hid, m2w, m2b, h->dtab, h->S, H, 4 * H, ACT_NONE, nullptr, nullptr, st));
+  // ... and its part of the concat-Linear with the bias (:63-70), for the sampler entries: one row per timestep
+  TRY(own_alloc(c->owned, &h->tvtab, (size_t)h->S * H));
+  {
+    GemmArgs g{};
+    g.A = h->dtab; g.B = h->gdi_w + 2 * H; g.C = h->tvtab; g.M = h->S; g.N = H; g.K = H; g.lda = H; g.ldb = 3 * H; g.ldc = H; g.trans_b = 1;
+    g.taps = 1; g.bias_n = h->gdi_b; g.alpha = 1.f; g.batch = 1;
+    TRY(launch_gemm(g, st));
+  }
   return create_tail(c, pos_table, nullptr, nullptr, st);   // the frame position table: c->dec_table
 }
 
@@ -2475,7 +2641,7 @@ extern "C" int bsg_fftden_prepare(bsg_fftden* h, const float* cond, int32_t B, i
   const size_t rows = (size_t)B * T;
   if (rows > h->cap) TRY(ws_grow(ws_table(h), "fftden", &h->cap, rows, st));
   TRY(grow(h->core, &h->core->cap_rows, rows, st));
-  h->B = B; h->T = T;
+  h->B = B; h->T = T; h->ragged = false;
   // cond [B][H][T] -> [B*T][H]; condpart = cond_t * W[:, C:2C]^T                           (candidate_decoder.py:63-70)
   hipLaunchKernelGGL(transpose_brc_kernel, dim3(cdiv(T, 32), cdiv(H, 32), B), dim3(256), 0, st, cond, h->xT, H, T);
   BSG_LAUNCH_CHECK();
@@ -2485,22 +2651,53 @@ extern "C" int bsg_fftden_prepare(bsg_fftden* h, const float* cond, int32_t B, i
   return launch_gemm(g, st);
 }
 
-extern "C" int bsg_fftden_forward(bsg_fftden* h, const float* x, const int64_t* t, float* eps, int32_t B, int32_t T, void* stream) {
+// ABI v22 (addition): bsg_fftden_prepare for a ragged batch.  Row b has lengths_host[b] frames; the calls that follow on the handle decode
+// it as the B = 1 call on those frames alone.  The counts are read and checked before the first device call and reach the kernels through the
+// handle's own device row, which launches of this call fill (lens_fill).  condpart is projected on the live frames only.
+extern "C" int bsg_fftden_prepare_ragged(bsg_fftden* h, const float* cond, const int32_t* lengths_host, int32_t B, int32_t T, void* stream) {
   GuardScope guard_scope(h && h->core ? &h->core->guard : nullptr);
-  BSG_REQUIRE(h && x && t && eps, "fftden_forward: null argument");
-  BSG_REQUIRE(h->cap > 0 && h->B == B && h->T == T, "fftden_forward: (B=%d,T=%d) does not match bsg_fftden_prepare (B=%d,T=%d)", B, T, h->B, h->T);
+  TRY(lens_check(lengths_host, B, T, "fftden_prepare_ragged"));
+  BSG_REQUIRE(h && cond, "fftden_prepare_ragged: null %s", h ? "cond" : "handle");
+  BSG_REQUIRE(T < h->n_pos, "fftden_prepare_ragged: bad argument (T=%d, position table has %d rows)", T, h->n_pos);
   hipStream_t st = (hipStream_t)stream;
+  if (is_capturing(st)) {
+    set_error("fftden_prepare_ragged: a ragged batch cannot be bound under stream capture");
+    return BSG_ESTATE;
+  }
+  TRY(rag_plan_check(h->core, "fftden_prepare_ragged", B, T, h->ksz));
+  const size_t rows = (size_t)B * T;
+  if (rows > h->cap) TRY(ws_grow(ws_table(h), "fftden", &h->cap, rows, st));
+  if ((size_t)B > h->cap_lens) TRY(ws_grow(ws_table(h), "fftden", &h->cap_lens, (size_t)B, st));
+  TRY(grow(h->core, &h->core->cap_rows, rows, st));
+  h->B = B; h->T = T; h->ragged = true;
+  h->lens_host.assign(lengths_host, lengths_host + B);
+  TRY(lens_fill(h->lens, lengths_host, B, st));
+  hipLaunchKernelGGL(transpose_in_rag_kernel, dim3(cdiv(T, 32), cdiv(H, 32), B), dim3(256), 0, st, cond, h->xT, H, T, (const int*)h->lens);
+  BSG_LAUNCH_CHECK();
+  GemmArgs g{};   // one batch item per row, bounded by its length
+  g.A = h->xT; g.B = h->gdi_w + H; g.C = h->condpart; g.M = T; g.N = H; g.K = H; g.lda = H; g.ldb = 3 * H; g.ldc = H;
+  g.trans_b = 1; g.taps = 1; g.alpha = 1.f; g.batch = B; g.sA = (long long)T * H; g.sC = (long long)T * H; g.lens = h->lens;
+  return launch_gemm(g, st);
+}
+
+// The denoiser up to the stack's last LayerNorm: the result [B*T][H] is left in the core's w_x.  `t`: one step per row, on the device
+// (bsg_fftden_forward); null: every row at step t_all, its step vector read from the table of all steps (the sampler entries).  On a
+// ragged binding every launch takes the rows' lengths; the padded call launches exactly what it did.
+static int fftden_stack(bsg_fftden* h, const float* x, const int64_t* t, int t_all, int B, int T, hipStream_t st) {
   const long long rows = (long long)B * T;
   bsg_fs2midi* c = h->core;
+  const int* lens = h->ragged ? h->lens : nullptr;
   c->path.clear();
+  if (lens) path_add(c, "den.", "ragged");
   // x [B][M][T] -> [B*T][M]; xp = input_projection                                        (:57-58)
-  hipLaunchKernelGGL(transpose_brc_kernel, dim3(cdiv(T, 32), cdiv(h->M, 32), B), dim3(256), 0, st, x, h->xT, h->M, T);
+  if (lens) hipLaunchKernelGGL(transpose_in_rag_kernel, dim3(cdiv(T, 32), cdiv(h->M, 32), B), dim3(256), 0, st, x, h->xT, h->M, T, lens);
+  else hipLaunchKernelGGL(transpose_brc_kernel, dim3(cdiv(T, 32), cdiv(h->M, 32), B), dim3(256), 0, st, x, h->xT, h->M, T);
   BSG_LAUNCH_CHECK();
-  TRY(linear(h->xT, h->in_w, h->in_b, h->xp, rows, H, h->M, ACT_NONE, nullptr, nullptr, st));
+  TRY(linear(h->xT, h->in_w, h->in_b, h->xp, rows, H, h->M, ACT_NONE, nullptr, nullptr, st, 1.f, 0, nullptr, "", lens, T));
   // step part: tvec[b] = mlp(emb(t_b)) * W[:, 2C:3C]^T + bias                               (:59-66)
-  hipLaunchKernelGGL(gather_rows_kernel, dim3(cdiv(B * H, 256)), dim3(256), 0, st, (const float*)h->dtab, (const long long*)t, h->te, B, H, h->S);
-  BSG_LAUNCH_CHECK();
-  {
+  if (t) {
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(cdiv(B * H, 256)), dim3(256), 0, st, (const float*)h->dtab, (const long long*)t, h->te, B, H, h->S);
+    BSG_LAUNCH_CHECK();
     GemmArgs g{};
     g.A = h->te; g.B = h->gdi_w + 2 * H; g.C = h->tvec; g.M = B; g.N = H; g.K = H; g.lda = H; g.ldb = 3 * H; g.ldc = H; g.trans_b = 1;
     g.taps = 1; g.bias_n = h->gdi_b; g.alpha = 1.f; g.batch = 1;
@@ -2511,19 +2708,143 @@ extern "C" int bsg_fftden_forward(bsg_fftden* h, const float* x, const int64_t* 
     GemmArgs g{};   // decoder_inp = xp W_x^T + condpart + tvec[b]
     g.A = h->xp; g.B = h->gdi_w; g.C = xs; g.M = T; g.N = H; g.K = H; g.lda = H; g.ldb = 3 * H; g.ldc = H; g.trans_b = 1; g.taps = 1;
     g.bias_n = h->tvec; g.sBiasN = H; g.alpha = 1.f; g.R = h->condpart; g.ldr = H; g.sR = (long long)T * H; g.batch = B;
-    g.sA = (long long)T * H; g.sC = (long long)T * H;
+    g.sA = (long long)T * H; g.sC = (long long)T * H; g.lens = lens;
+    if (!t) { g.bias_n = h->tvtab + (long long)t_all * H; g.sBiasN = 0; }
     TRY(launch_gemm(g, st));
   }
   const dim3 rg(cdiv(rows, 4)), rb(256);
-  hipLaunchKernelGGL(decoder_positions_kernel, dim3(B), dim3(64), 0, st, (const float*)xs, c->w_pos, c->w_keep, T, (const int*)nullptr);
+  hipLaunchKernelGGL(decoder_positions_kernel, dim3(B), dim3(64), 0, st, (const float*)xs, c->w_pos, c->w_keep, T, lens);
   BSG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(decoder_entry_kernel, rg, rb, 0, st, xs, (const int*)c->w_pos, c->dec_table, h->alpha, c->w_keep, rows, h->n_pos,
-                     (const int*)nullptr, T);
+  hipLaunchKernelGGL(decoder_entry_kernel, rg, rb, 0, st, xs, (const int*)c->w_pos, c->dec_table, h->alpha, c->w_keep, rows, h->n_pos, lens, T);
   BSG_LAUNCH_CHECK();
-  TRY(launch_fft(c, h->layers, h->lnw, h->lnb, h->ksz, xs, c->w_keep, B, T, st, "den."));
+  TRY(launch_fft(c, h->layers, h->lnw, h->lnb, h->ksz, xs, c->w_keep, B, T, st, "den.", lens));
+  if (lens) c->last_stack_rows = rag_rows(h->lens_host.data(), B, T);
+  return BSG_OK;
+}
+
+extern "C" int bsg_fftden_forward(bsg_fftden* h, const float* x, const int64_t* t, float* eps, int32_t B, int32_t T, void* stream) {
+  GuardScope guard_scope(h && h->core ? &h->core->guard : nullptr);
+  BSG_REQUIRE(h && x && t && eps, "fftden_forward: null argument");
+  BSG_REQUIRE(h->cap > 0 && h->B == B && h->T == T, "fftden_forward: (B=%d,T=%d) does not match bsg_fftden_prepare (B=%d,T=%d)", B, T, h->B, h->T);
+  hipStream_t st = (hipStream_t)stream;
+  const long long rows = (long long)B * T;
+  TRY(fftden_stack(h, x, t, 0, B, T, st));
+  const float* xs = h->core->w_x;
+  if (h->ragged) {   // get_mel_out on the live frames; eps is written as 0 from a row's end to T
+    TRY(linear(xs, h->mel_w, h->mel_b, h->mel, rows, h->M, H, ACT_NONE, nullptr, nullptr, st, 1.f, 0, nullptr, "", h->lens, T));
+    hipLaunchKernelGGL(transpose_out_rag_kernel, dim3(cdiv(h->M, 32), cdiv(T, 32), B), dim3(256), 0, st, (const float*)h->mel, eps, T, h->M, (const int*)h->lens);
+    BSG_LAUNCH_CHECK();
+    return BSG_OK;
+  }
   TRY(linear(xs, h->mel_w, h->mel_b, h->mel, rows, h->M, H, ACT_NONE, nullptr, nullptr, st));       // get_mel_out (:98)
   hipLaunchKernelGGL(transpose_brc_kernel, dim3(cdiv(h->M, 32), cdiv(T, 32), B), dim3(256), 0, st, (const float*)h->mel, eps, T, h->M);
   BSG_LAUNCH_CHECK();
+  return BSG_OK;
+}
+
+// ---- the sampler loops over this denoiser (ABI v22, additions): every step enqueued on the stream, nothing waited for ------------------
+// What both entries check before anything is enqueued; `plms`: which schedule arrays the loop reads.
+static int fftden_sampler_enter(bsg_fftden* h, const bsg_schedule* s, const float* x, int B, int T, const char* who, bool plms) {
+  BSG_REQUIRE(h, "%s: null handle", who);
+  TRY(check_schedule(s, who, plms));
+  BSG_REQUIRE(x, "%s: null x", who);
+  BSG_REQUIRE(h->cap > 0 && h->B == B && h->T == T, "%s: (B=%d,T=%d) does not match the handle's binding (B=%d,T=%d)", who, B, T, h->B, h->T);
+  BSG_REQUIRE(h->M <= 4 * FT_MJ, "%s: the fused step tail is built for up to %d mel bins (in_dims=%d)", who, 4 * FT_MJ, h->M);
+  return BSG_OK;
+}
+// the step tail on the stack's output of the evaluation just enqueued
+static int fftden_tail(bsg_fftden* h, FftTailArgs a, int B, int T, hipStream_t st) {
+  a.xs = h->core->w_x; a.w = h->mel_w; a.bias = h->mel_b; a.lens = h->ragged ? h->lens : nullptr; a.T = T; a.M = h->M;
+  const dim3 grid(cdiv(T, FT_F), B), block(256);
+  if (a.mode == FT_DDPM) hipLaunchKernelGGL(fftden_tail_kernel<FT_DDPM>, grid, block, 0, st, a);
+  else if (a.mode == FT_PLMS) hipLaunchKernelGGL(fftden_tail_kernel<FT_PLMS>, grid, block, 0, st, a);
+  else hipLaunchKernelGGL(fftden_tail_kernel<FT_PLMS_CORRECT>, grid, block, 0, st, a);
+  BSG_LAUNCH_CHECK();
+  return BSG_OK;
+}
+
+// bsg_ddpm_sample / bsg_ddpm_sample_rows over the FFT denoiser, on the handle's binding (padded or ragged).  Per step: the denoiser up to
+// the stack's last LayerNorm, then ONE launch for get_mel_out, the draw and p_sample (fftden_tail_kernel).  Draws: `noise`
+// [n_steps][B][M][T] · seeds_host (host, B keys): row b from the stream (seeds_host[b], i + 1) at its own bound length, the values of
+// bsg_philox_normal_rows · neither: (seed, i + 1) by global row and padded stride (row0, B_total).  A ragged row's x beyond its end is
+// left as given.
+extern "C" int bsg_fftden_ddpm_sample(bsg_fftden* h, const bsg_schedule* s, float* x, const float* noise, uint64_t seed, const uint64_t* seeds_host,
+                                      int32_t t_start, int32_t n_steps, int32_t B, int32_t T, int32_t row0, int32_t B_total, void* stream) {
+  GuardScope guard_scope(h && h->core ? &h->core->guard : nullptr);
+  const char* who = "fftden_ddpm_sample";
+  TRY(fftden_sampler_enter(h, s, x, B, T, who, false));
+  BSG_REQUIRE(!(noise && seeds_host), "%s: supplied noise and seeds_host exclude each other", who);
+  BSG_REQUIRE(t_start < s->num_timesteps && t_start < h->S && n_steps >= 0 && t_start - n_steps + 1 >= 0,
+              "%s: steps [%d..%d] outside the schedule (%d) / step table (%d)", who, t_start - n_steps + 1, t_start, s->num_timesteps, h->S);
+  BSG_REQUIRE(row0 >= 0 && row0 + B <= B_total, "%s: rows [%d,%d) outside the global batch %d", who, row0, row0 + B, B_total);
+  BSG_REQUIRE((long long)B * h->M * T % 4 == 0, "%s: B*M*T must be a multiple of 4", who);
+  hipStream_t st = (hipStream_t)stream;
+  if (seeds_host) {   // what bsg_philox_normal_rows would refuse is refused here, before a step is enqueued
+    for (int b = 0; b < B; ++b) {
+      const int nb = h->ragged ? h->lens_host[b] : T;
+      BSG_REQUIRE((long long)h->M * nb % 4 == 0, "%s: row %d draws M * n = %d * %d values, no multiple of 4", who, b, h->M, nb);
+    }
+    // (a ragged binding sized the group for its B already: only a padded one grows it here)
+    if ((size_t)B > h->cap_lens) TRY(ws_grow(ws_table(h), "fftden", &h->cap_lens, (size_t)B, st, GROW_LAZY));
+    std::vector<int32_t> words(2 * (size_t)B);   // the keys as 32-bit words, low word first: the order the device reads a 64-bit value in
+    for (int b = 0; b < B; ++b) {
+      words[2 * b] = (int32_t)(uint32_t)(seeds_host[b] & 0xFFFFFFFFull);
+      words[2 * b + 1] = (int32_t)(uint32_t)(seeds_host[b] >> 32);
+    }
+    TRY(lens_fill(reinterpret_cast<int*>(h->seeds), words.data(), 2 * B, st));
+  }
+  const long long n = (long long)B * h->M * T;
+  for (int k = 0; k < n_steps; ++k) {
+    const int i = t_start - k;
+    TRY(fftden_stack(h, x, nullptr, i, B, T, st));
+    FftTailArgs a{};
+    a.mode = FT_DDPM; a.x_in = x; a.x_out = x;
+    a.noise = noise ? noise + k * n : nullptr; a.row_seeds = seeds_host ? h->seeds : nullptr;
+    a.seed = seed; a.elem0 = (unsigned long long)row0 * h->M * T; a.stream = (unsigned)(i + 1);
+    a.k = StepCoef{s->sqrt_recip_alphas_cumprod[i], s->sqrt_recipm1_alphas_cumprod[i], s->posterior_mean_coef1[i], s->posterior_mean_coef2[i], s->sigma[i]};
+    TRY(fftden_tail(h, a, B, T, st));
+  }
+  return BSG_OK;
+}
+
+// bsg_plms_sample over the FFT denoiser (p_sample_plms :168-201), on the handle's binding: the 4-deep history of the noise predictions
+// lives in handle workspace; the first iteration is the predictor / corrector pair (two evaluations); t - interval clamps at 0.  Every
+// evaluation ends in the one tail launch, which also stores eps to the history slot.
+extern "C" int bsg_fftden_plms_sample(bsg_fftden* h, const bsg_schedule* s, float* x, int32_t K_step, int32_t interval, int32_t B, int32_t T,
+                                      void* stream) {
+  GuardScope guard_scope(h && h->core ? &h->core->guard : nullptr);
+  const char* who = "fftden_plms_sample";
+  TRY(fftden_sampler_enter(h, s, x, B, T, who, true));
+  BSG_REQUIRE(interval > 0 && K_step > 0 && K_step <= s->num_timesteps && K_step <= h->S, "%s: K_step=%d interval=%d schedule=%d step table=%d", who,
+              K_step, interval, s->num_timesteps, h->S);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t rows = (size_t)B * T;
+  if (rows > h->cap_smp) TRY(ws_grow(ws_table(h), "fftden", &h->cap_smp, rows, st, GROW_LAZY));
+  float* hist[4] = {h->hist[0], h->hist[1], h->hist[2], h->hist[3]};   // ring: hist[0] = newest
+  int n_hist = 0;
+  const int last = ((K_step - 1) / interval) * interval;
+  for (int i = last; i >= 0; i -= interval) {
+    const int ip = i - interval > 0 ? i - interval : 0;
+    FftTailArgs a{};
+    a.pk.a_t = s->alphas_cumprod[i];
+    a.pk.a_prev = s->alphas_cumprod[ip];
+    float* e_new = hist[3];   // the slot about to be recycled
+    TRY(fftden_stack(h, x, nullptr, i, B, T, st));
+    a.mode = FT_PLMS; a.n_hist = n_hist; a.e_new = e_new; a.x_in = x; a.x_out = x;
+    a.h1 = hist[0]; a.h2 = hist[1]; a.h3 = hist[2];
+    plms_blend(n_hist, a.pk);
+    if (n_hist == 0) {
+      // predictor into xpred (a ragged row: its own frames only; the second evaluation reads no others), then the corrector on x
+      a.x_out = h->xpred;
+      TRY(fftden_tail(h, a, B, T, st));
+      TRY(fftden_stack(h, h->xpred, nullptr, ip, B, T, st));
+      a.mode = FT_PLMS_CORRECT; a.x_out = x; a.h1 = e_new; a.e_new = nullptr;
+      a.pk.w0 = 1.f; a.pk.inv = 2.f;   // (eps + eps_prev) / 2
+    }
+    TRY(fftden_tail(h, a, B, T, st));
+    hist[3] = hist[2]; hist[2] = hist[1]; hist[1] = hist[0]; hist[0] = e_new;
+    if (n_hist < 3) ++n_hist;
+  }
   return BSG_OK;
 }
 

@@ -127,7 +127,8 @@ class GaussianDiffusion(nn.Module):
         beyond is left as given (INTEGRATION.md "Ragged batches").  Philox draws keep their index (global row, padded stride T), so a
         row's frames see the draws of the padded batch; the row-by-row fallback (a handle without the ragged launch:
         DiffNet.ragged_native) runs each row at T = lengths[b] and so draws other values — supplied ``noise`` gives the same result on
-        both paths, and so does ``row_seeds``.
+        both paths, and so does ``row_seeds``.  With the FFT denoiser (``diff_decoder_type: fft``) the handle is bound ragged and the loop
+        is one call of ``bsg_fftden_ddpm_sample`` / ``bsg_fftden_plms_sample``; the draw modes mean the same.
         ``row_seeds`` (B ints; not with ``noise``): row b's draws of every step come from the Philox stream of row_seeds[b] at the row's
         own length — bit for bit the draws of ``sample(seed=row_seeds[b])`` on that row alone at T = lengths[b] (``bsg_ddpm_sample_rows``;
         the row-by-row fallback calls exactly that).  ``seed``, ``row0`` and ``B_total`` are not read then.
@@ -148,7 +149,10 @@ class GaussianDiffusion(nn.Module):
         elif lengths is None:
             self.denoise_fn.prepare(cond)
         elif not isinstance(self.denoise_fn, DiffNet):
-            raise NotImplementedError('sample(lengths=...): ragged batches need the WaveNet denoiser (DiffNet)')
+            from .candidate_decoder import FFT
+            if not isinstance(self.denoise_fn, FFT):
+                raise NotImplementedError('sample(lengths=...): ragged batches need the WaveNet denoiser (DiffNet) or the FFT denoiser')
+            return self._sample_fft_ragged(cond, x, lengths, noise, seed, row0, B if B_total is None else B_total, n_steps, row_seeds)
         else:
             self.denoise_fn.prepare(cond, lengths)
         s, _keep = self._schedule()
@@ -242,6 +246,40 @@ class GaussianDiffusion(nn.Module):
         # workgroup gave up, on the fp32 matrix pipe if a value left the fp16 range — and an invalid x never leaves this function
         keep = None if torch.cuda.is_current_stream_capturing() else x.clone()
         self.denoise_fn.guarded(run, B, T, restore=None if keep is None else (lambda: x.copy_(keep)))
+        return x
+
+    def _sample_fft_ragged(self, cond, x, lengths, noise, seed, row0, B_total, n_steps, row_seeds):
+        """sample(lengths=...) over the FFT denoiser: the handle is bound ragged and the whole loop is ONE call of the library's entry
+        (``bsg_fftden_ddpm_sample`` / ``bsg_fftden_plms_sample``: per step the denoiser and one fused launch for get_mel_out, the draw
+        and the update).  On a range event of the split-fp16 GEMMs x_T is restored, the handle bound again and the call repeated."""
+        B, _, M, T = x.shape
+        lib, den = _lib.load(), self.denoise_fn
+        s, _keep = self._schedule()
+        t = self.K_step
+        n = t if n_steps is None else n_steps
+        interval = int(hparams.get('pndm_speedup') or 0)
+        if noise is not None:
+            noise = noise.contiguous()
+            assert tuple(noise.shape) == (n, B, M, T), noise.shape
+        capturing = torch.cuda.is_current_stream_capturing()
+        keep = None if capturing else x.clone()
+
+        def run():
+            den._ensure_bound(cond, lengths)      # (a new ragged binding under capture is refused by the library, nothing enqueued)
+            with torch.cuda.device(x.device):
+                if interval:
+                    _lib.check(lib.bsg_fftden_plms_sample(den._h, byref(s), _lib.ptr(x), t, interval, B, T, _lib.stream_ptr()),
+                               'bsg_fftden_plms_sample')
+                else:
+                    _lib.check(lib.bsg_fftden_ddpm_sample(den._h, byref(s), _lib.ptr(x), _lib.ptr(noise), seed,
+                                                          None if row_seeds is None else _lib.seeds_array(row_seeds), t - 1, n, B, T,
+                                                          row0, B_total, _lib.stream_ptr()), 'bsg_fftden_ddpm_sample')
+
+        def again():
+            x.copy_(keep)
+            den._bound = None          # the hoisted condition part was projected by the same GEMMs: bind again
+
+        _lib.range_guarded(run, 'FFT denoiser ragged sampler loop', on_retry=None if capturing else again, device=x, owners=(den,))
         return x
 
     @torch.no_grad()

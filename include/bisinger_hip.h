@@ -492,6 +492,36 @@ int bsg_fftden_forward(bsg_fftden* h, const float* x, const int64_t* t, float* e
 /* ABI v11: as bsg_fs2midi_last_path / bsg_fs2midi_debug_poison_workspace, for the stack of the last bsg_fftden_forward ("den." tokens) */
 const char* bsg_fftden_last_path(bsg_fftden* h);
 int bsg_fftden_debug_poison_workspace(bsg_fftden* h, void* stream);
+/* ABI v22 (additions, as the PWG ragged entries were to v20): ragged batches through the FFT denoiser.
+ * bsg_fftden_prepare_ragged binds `cond` [B,256,T] for a batch whose row b has lengths_host[b] frames (HOST array, B ints in 1..T, read
+ * before the call returns; they reach the kernels through a device row of the handle that launches of the call fill).  A bad length or
+ * argument is BSG_EINVAL with a message before any device call; a capturing stream is BSG_ESTATE with nothing enqueued; a head dimension
+ * other than 128 or BSG_NO_FLASH_ATTN (the score-tensor attention has no lengths) is BSG_EINVAL.  The hoisted condition part is projected on
+ * the live frames only.  A later bsg_fftden_prepare makes the handle padded again.
+ * On a ragged-bound handle bsg_fftden_forward(h, x, t, eps, B, T) gives row b ALONE: eps[b, :, :n_b] is the denoiser on x[b:b+1, :, :n_b],
+ * t[b], cond[b:b+1, :, :n_b] (B = 1, T = n_b) — positions count the row's own frames, attention keys end at n_b, the k-tap FFN convolution
+ * reads zeros beyond n_b in every layer, the last LayerNorm and get_mel_out run on live frames only — and eps[b, :, n_b:] = 0.  Nothing at
+ * or beyond a row's end is read (x and cond may hold NaN there; what an earlier call left in the workspaces does not matter) and no dead
+ * frame is computed.  bsg_fftden_last_path of a ragged call starts with the token "den.ragged"; the padded call's record is unchanged. */
+int bsg_fftden_prepare_ragged(bsg_fftden* h, const float* cond, const int32_t* lengths_host, int32_t B, int32_t T, void* stream);
+/* The sampler loops over this denoiser, worded after bsg_ddpm_sample / bsg_ddpm_sample_rows / bsg_plms_sample.  Both run on whatever
+ * binding the handle has (padded or ragged; (B, T) must be the binding's), enqueue every step on `stream` and never synchronise.  Per
+ * evaluation: the denoiser up to its last LayerNorm, then ONE launch that does get_mel_out (256 -> in_dims <= 80), the DDPM or PLMS update
+ * with the schedule values of the step, the draw, and the store into x [B,M,T] (and, PLMS, of eps into the history slot).  The step vector
+ * comes from a table of all timesteps made at create (every row of a sampler call shares t).  A ragged row's x beyond its end is left as
+ * given; dead frames are neither read nor written.
+ * bsg_fftden_ddpm_sample: steps t_start, t_start - 1, .. (n_steps of them).  Draws, as GaussianDiffusion.sample documents them:
+ *   noise      device [n_steps, B, M, T], supplied draws (not with seeds_host);
+ *   seeds_host host, B keys: row b draws from the stream (seeds_host[b], i + 1) at its own bound length — bit for bit the values of
+ *              bsg_philox_normal_rows / bsg_ddpm_sample_rows (M * n_b must be a multiple of 4); seed / row0 / B_total are not read;
+ *   neither    Philox (seed, i + 1) indexed by global row (row0 of B_total) and padded stride T, as bsg_ddpm_step's offset.
+ * bsg_fftden_plms_sample: p_sample_plms (:168-201) over i = last, last - interval, .., 0 with last = floor((K_step - 1) / interval) *
+ * interval; the 4-deep history lives in handle workspace (grown by the call: not under capture until the shape has run once), the first
+ * iteration is the predictor / corrector pair (two evaluations), t - interval clamps at 0. */
+int bsg_fftden_ddpm_sample(bsg_fftden* h, const bsg_schedule* s, float* x, const float* noise, uint64_t seed, const uint64_t* seeds_host,
+                           int32_t t_start, int32_t n_steps, int32_t B, int32_t T, int32_t row0, int32_t B_total, void* stream);
+int bsg_fftden_plms_sample(bsg_fftden* h, const bsg_schedule* s, float* x, int32_t K_step, int32_t interval, int32_t B, int32_t T,
+                           void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * HiFi-GAN generator forward (mel -> waveform).
