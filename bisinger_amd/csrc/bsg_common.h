@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <atomic>
+
 #include "../../include/bisinger_hip.h"
 
 namespace bsg {
@@ -49,6 +51,20 @@ __device__ __forceinline__ int rag_len(const int* __restrict__ lens, int b, int 
 static inline int env_int(const char* name, int dflt) {
   const char* e = getenv(name);
   return e ? atoi(e) : dflt;
+}
+
+// The dynamic-LDS grant of a kernel whose launcher has no handle at hand (gemm.hip, gemm_h2w.hip: the handle-less entries reach them): made
+// once per device.  `granted` is one mask per kernel instantiation (a static of its launcher), bit d = device d has the grant.  Two host
+// threads may pass at once: both grant, which is harmless, and neither skips.  Per launch: one device-id read and one load.  A device id
+// beyond the mask is granted on every launch.
+static inline int grant_lds_per_device(std::atomic<uint64_t>& granted, const void* fn, size_t lds) {
+  int dev = 0;
+  BSG_HIP(hipGetDevice(&dev));
+  const uint64_t bit = dev >= 0 && dev < 64 ? 1ull << dev : 0;
+  if (granted.load(std::memory_order_acquire) & bit) return BSG_OK;
+  BSG_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  granted.fetch_or(bit, std::memory_order_release);
+  return BSG_OK;
 }
 
 // Activation codes shared by the GEMM epilogue.

@@ -1346,6 +1346,7 @@ struct bsg_fs2midi {
   size_t cap_fsk = 0, cap_fcnt = 0;
   unsigned* pack_bad = nullptr;                      // device word: packed weights beyond the fp16 range (then the pre-split GEMMs are not used)
   bool h2w_ok = false;
+  bool planes_lds = false;                           // this handle's device grants flash_attn_planes_kernel<2> its FLP_LDS (asked at create)
   int *w_lens_t = nullptr, *w_lens_f = nullptr;      // ragged calls: the utterances' token and frame counts on the device, filled by the call itself (lens_fill)
   size_t cap_lens = 0;
   float* esm_scr = nullptr;                          // MIDI front: [6][2][H] scratch of the two-row ESM table of the ragged encode (esm_alone_table)
@@ -1490,7 +1491,8 @@ static int load_decoder(bsg_fs2midi* h, const void* const* w, int& i, hipStream_
   return BSG_OK;
 }
 
-// The end of every create: the position tables (tok_table: none for the FFT denoiser), then the read-back of the packing (h2w_ok)
+// The end of every create: the position tables (tok_table: none for the FFT denoiser), the read-back of the packing (h2w_ok), and the
+// question whether this handle's device grants the planes attention its LDS (a refusal is no error: no planes attention on this handle)
 static int create_tail(bsg_fs2midi* h, const float* dec_table, const float* tok_table, const float* pitch_table, hipStream_t st) {
   const bsg_fs2midi_cfg& c = h->cfg;
   TRY(fs2_copy(h, &h->dec_table, dec_table, (size_t)c.n_pos * H, st));
@@ -1500,6 +1502,8 @@ static int create_tail(bsg_fs2midi* h, const float* dec_table, const float* tok_
   BSG_HIP(hipMemcpyAsync(&bad, h->pack_bad, sizeof(unsigned), hipMemcpyDeviceToHost, st));
   BSG_HIP(hipStreamSynchronize(st));
   h->h2w_ok = bad == 0 && c.enc_ffn_kernel_size <= 17 && c.dec_ffn_kernel_size <= 17;
+  h->planes_lds = hipFuncSetAttribute(reinterpret_cast<const void*>(flash_attn_planes_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, FLP_LDS) == hipSuccess;
+  if (!h->planes_lds) (void)hipGetLastError();
   return BSG_OK;
 }
 
@@ -1696,8 +1700,8 @@ static int linear_h2w(bsg_fs2midi* rec, const char* tag, const unsigned short* p
   return h2w_rec(rec, tag, g, st);
 }
 
-// The environment switches of the FFT stack and of the ESM front, with the one device probe among them: read by the first call that asks (an
-// encode or a stack: a device is current then) and never again in the process.  The probe runs then whichever GEMM path that call takes.
+// The environment switches of the FFT stack and of the ESM front: read by the first call that asks and never again in the process.  (What a
+// device answers is no switch: bsg_fs2midi::planes_lds.)
 struct FftSwitches {
   bool gemm_h2w = env_int("BSG_GEMM_H2W", 1);         // =0: gemm_split_kernel (operands split while staged) instead of the pre-split GEMMs
   bool esm_h2w = env_int("BSG_ESM_H2W", 1);           // =0: the ESM's Linear layers on gemm_split_kernel and the thread-per-query attention
@@ -1706,12 +1710,6 @@ struct FftSwitches {
   bool flash_planes = env_int("BSG_FLASH_PLANES", 1); // =0: flash_attn_split_kernel (K / V split while staged) instead of the pre-split attention
   bool qkv_fused = env_int("BSG_QKV_FUSED", 1);       // =0: fp32 QKV tensor + qkv_split_kernel instead of the QKV product's own plane output
   int flash_ks = env_int("BSG_FLASH_KS", 0);          // 0 = auto, 1 = never split, 2 / 4 / 8 = that many key splits whenever the sequence allows
-  FftSwitches() {   // no planes attention either where the device does not grant flash_attn_planes_kernel its LDS
-    if (flash_planes && hipFuncSetAttribute(reinterpret_cast<const void*>(flash_attn_planes_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, FLP_LDS) != hipSuccess) {
-      (void)hipGetLastError();
-      flash_planes = false;
-    }
-  }
 };
 static const FftSwitches& fft_switches() { static const FftSwitches sw; return sw; }
 
@@ -1752,7 +1750,7 @@ static FftPlan plan_fft(const bsg_fs2midi* h, int B, int T, int ksz, bool ragged
   const bool split_ok = gemm_split_enabled(), flash = p.hd == 128 && sw.flash;
   p.h2w = sw.gemm_h2w && h->h2w_ok && split_ok && sw.flash_split && flash && h2w_supports(T, 4 * H, H, ksz, H) &&
           h2w_supports((int)p.rows, 3 * H, H, 1, H) && p.rows * 4 * H * 2 < (1LL << 31);
-  if (p.h2w && sw.flash_planes && p.Tp <= 3 * T && p.rows >= 32 && (!ragged || sw.qkv_fused)) {
+  if (p.h2w && sw.flash_planes && h->planes_lds && p.Tp <= 3 * T && p.rows >= 32 && (!ragged || sw.qkv_fused)) {
     // 2 waves (64 queries) per workgroup at every size: the pipelined loop keeps two score tiles live and does not fit 4 waves x 2 workgroups.
     // Small batches: the keys of a query tile over ks workgroups (a single utterance is 32 workgroups, each a serial chain of 32 key blocks)
     p.attn = ATTN_PLANES; p.nw = 2; p.qkv = sw.qkv_fused ? QKV_FUSED : QKV_SPLIT_KERNEL;

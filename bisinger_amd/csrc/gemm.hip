@@ -584,11 +584,9 @@ int launch_split(const GemmArgs& g, hipStream_t st) {
 template <int BM, int FBK, bool TRANS_B, bool RAG = false>
 int launch_fast(const GemmArgs& g, hipStream_t st) {
   constexpr size_t lds = (size_t)(2 * BM * (FBK + 4) + 2 * (TRANS_B ? FBN * (FBK + 4) : FBK * FLDN)) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    BSG_HIP(hipFuncSetAttribute((const void*)gemm_fast_kernel<BM, FBK, TRANS_B, RAG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  static std::atomic<uint64_t> granted{0};
+  const int rc = grant_lds_per_device(granted, (const void*)gemm_fast_kernel<BM, FBK, TRANS_B, RAG>, lds);
+  if (rc != BSG_OK) return rc;
   hipLaunchKernelGGL((gemm_fast_kernel<BM, FBK, TRANS_B, RAG>), dim3(cdiv(g.N, FBN), cdiv(g.M, BM), g.batch), dim3(256), lds, st, g);
   BSG_LAUNCH_CHECK();
   return BSG_OK;

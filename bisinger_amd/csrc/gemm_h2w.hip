@@ -508,13 +508,10 @@ int h2w_launch(const H2wArgs& g, hipStream_t st) {
   const size_t stages = (size_t)2 * 2 * (BMA + g.taps - 1) * (32 * KK + 16);
   const size_t lds = stages > epi ? stages : epi;
   const int nwg = cdiv(g.rows, BMA) * (g.Wn / 128) * g.batch;
-  static bool attr_set = false;
-  if (!attr_set) {
-    constexpr size_t smax = (size_t)2 * 2 * (BMA + H2W_MAXTAPS - 1) * (32 * KK + 16);
-    BSG_HIP(hipFuncSetAttribute((const void*)gemm_h2w_kernel<ACT_IS_A, MI, KK, NS, RAG>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(smax > epi ? smax : epi)));
-    attr_set = true;
-  }
+  constexpr size_t smax = (size_t)2 * 2 * (BMA + H2W_MAXTAPS - 1) * (32 * KK + 16);   // the stages at the most taps
+  static std::atomic<uint64_t> granted{0};
+  const int rc = grant_lds_per_device(granted, (const void*)gemm_h2w_kernel<ACT_IS_A, MI, KK, NS, RAG>, smax > epi ? smax : epi);
+  if (rc != BSG_OK) return rc;
   hipLaunchKernelGGL((gemm_h2w_kernel<ACT_IS_A, MI, KK, NS, RAG>), dim3(nwg), dim3(256), lds, st, g);
   BSG_LAUNCH_CHECK();
   // what was launched, for the caller's launch record: tile height, then the weight ring (KK = 16: the 256-deep slices of the 32-row tiles)

@@ -796,95 +796,6 @@ __global__ void pack_convT_w_kernel(const float* __restrict__ w, float* __restri
   out[i] = co < Cout ? w[((long long)ci * Cout + co) * (2 * u) + r + (1 - kk) * u] : 0.f;
 }
 
-template <int K, int TT>
-int launch_conv_kt(const ConvArgs& a, int B, hipStream_t st) {
-  constexpr int TILE = 256 * TT;
-  const size_t lds = (size_t)CI_CHUNK * (TILE + (K - 1) * a.dil) * sizeof(float);
-  if (a.Cout >= 16) {
-    dim3 grid(cdiv(a.L, TILE), cdiv(a.Cout, 16), B);
-    if (a.lens) hipLaunchKernelGGL((conv1d_kernel<K, 16, TT, true>), grid, dim3(256), lds, st, a);
-    else hipLaunchKernelGGL((conv1d_kernel<K, 16, TT>), grid, dim3(256), lds, st, a);
-  } else {
-    dim3 grid(cdiv(a.L, TILE), cdiv(a.Cout, 8), B);
-    if (a.lens) hipLaunchKernelGGL((conv1d_kernel<K, 8, TT, true>), grid, dim3(256), lds, st, a);
-    else hipLaunchKernelGGL((conv1d_kernel<K, 8, TT>), grid, dim3(256), lds, st, a);
-  }
-  BSG_LAUNCH_CHECK();
-  return BSG_OK;
-}
-
-template <int K>
-int launch_conv_k(const ConvArgs& a, int tt, int B, hipStream_t st) {
-  if (tt == 4) return launch_conv_kt<K, 4>(a, B, st);
-  if (tt == 2) return launch_conv_kt<K, 2>(a, B, st);
-  return launch_conv_kt<K, 1>(a, B, st);
-}
-
-// polyphase ConvTranspose1d (K = 2u): one launch, blockIdx.z = (batch row, phase), 2-tap convs with strided stores
-template <int TT>
-int launch_convT_t(const ConvArgs& a, int B, hipStream_t st) {
-  constexpr int TILE = 256 * TT;
-  const size_t lds = (size_t)CI_CHUNK * (TILE + 1) * sizeof(float);
-  const dim3 grid(cdiv(a.Lq, TILE), cdiv(a.Cout, a.Cout >= 16 ? 16 : 8), B * a.n_phase);
-  if (a.Cout >= 16) {
-    if (a.lens) hipLaunchKernelGGL((conv1d_kernel<2, 16, TT, true>), grid, dim3(256), lds, st, a);
-    else hipLaunchKernelGGL((conv1d_kernel<2, 16, TT>), grid, dim3(256), lds, st, a);
-  } else {
-    if (a.lens) hipLaunchKernelGGL((conv1d_kernel<2, 8, TT, true>), grid, dim3(256), lds, st, a);
-    else hipLaunchKernelGGL((conv1d_kernel<2, 8, TT>), grid, dim3(256), lds, st, a);
-  }
-  BSG_LAUNCH_CHECK();
-  return BSG_OK;
-}
-int launch_convT(const ConvArgs& a, int tt, int B, hipStream_t st) {
-  if (tt == 4) return launch_convT_t<4>(a, B, st);
-  if (tt == 2) return launch_convT_t<2>(a, B, st);
-  return launch_convT_t<1>(a, B, st);
-}
-
-// Run-time (K, C) -> f(<K>, <C>) for K in {3, 7, 11} and C in Cs, as std::integral_constant arguments of a generic lambda; HG_NO_KERNEL if (K, C) is not in that set.
-constexpr int HG_NO_KERNEL = 1;
-template <int K, int... Cs, class F>
-int dispatch_c(int C, F& f) {
-  int rc = HG_NO_KERNEL;
-  (void)((C == Cs && ((rc = f(std::integral_constant<int, K>{}, std::integral_constant<int, Cs>{})), true)) || ...);
-  return rc;
-}
-template <int... Cs, class F>
-int dispatch_kc(int K, int C, F f) {
-  switch (K) {
-    case 3: return dispatch_c<3, Cs...>(C, f);
-    case 7: return dispatch_c<7, Cs...>(C, f);
-    case 11: return dispatch_c<11, Cs...>(C, f);
-    default: return HG_NO_KERNEL;
-  }
-}
-
-template <int K, int C, int TT, bool RAG>
-int launch_pair_t_r(const PairArgs& a, int B, hipStream_t st) {
-  constexpr int P = 256 * TT, POUT = P - (K - 1);
-  const size_t lds = ((size_t)C * P + 16) * sizeof(float);
-  static bool attr = false;
-  if (!attr) {
-    BSG_HIP(hipFuncSetAttribute((const void*)resblock_pair_kernel<K, C, TT, RAG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr = true;
-  }
-  hipLaunchKernelGGL((resblock_pair_kernel<K, C, TT, RAG>), dim3(cdiv(a.L, POUT), B), dim3(256), lds, st, a);
-  BSG_LAUNCH_CHECK();
-  return BSG_OK;
-}
-template <int K, int C, int TT>
-int launch_pair_t(const PairArgs& a, int B, hipStream_t st) {
-  return a.lens ? launch_pair_t_r<K, C, TT, true>(a, B, st) : launch_pair_t_r<K, C, TT, false>(a, B, st);
-}
-// tt positions per thread (pair_valu_tt): only the widths within the 64-accumulator budget (C TT <= 64) are built
-template <int K, int C>
-int launch_pair_kc(const PairArgs& a, int tt, int B, hipStream_t st) {
-  if constexpr (C * 8 <= 64) { if (tt == 8) return launch_pair_t<K, C, 8>(a, B, st); }
-  if constexpr (C * 4 <= 64) { if (tt == 4) return launch_pair_t<K, C, 4>(a, B, st); }
-  if constexpr (C * 2 <= 64) { if (tt == 2) return launch_pair_t<K, C, 2>(a, B, st); }
-  return launch_pair_t<K, C, 1>(a, B, st);
-}
 // ------------------------------------------------------------------------------------------------
 // The same fused pair with every product on the 16-bit matrix pipe (split-fp16: gemm.hip / diffnet_h2.hip have the argument).  Weights
 // x 2^8 and activations x 2^4 are split exactly into hi + lo fp16 terms — the weights once at create (pack_conv_h2_kernel), lrelu(x) while
@@ -1133,33 +1044,6 @@ __global__ __launch_bounds__(256) void resblock_pair_h2_kernel(PairArgs a) {
       for (int r = 0; r < 16; ++r) a.y[i0 + (long long)((r & 3) + 8 * (r >> 2)) * a.L] = xr[r];
     }
   }
-}
-
-template <int K, int C, int NB, bool RAG>
-int launch_pair_h2_t_r(const PairArgs& a, int B, hipStream_t st) {
-  constexpr int PT = 128 * NB, POUT = PT - (K - 1), ROWB = 2 * C + 16;
-  const int span = PT + 2 * ((K - 1) / 2 * a.dil);
-  const size_t lds = (size_t)2 * (span > PT + 16 ? span : PT + 16) * ROWB;
-  static size_t attr = 0;
-  if (lds > attr) {
-    BSG_HIP(hipFuncSetAttribute((const void*)resblock_pair_h2_kernel<K, C, NB, RAG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr = lds;
-  }
-  hipLaunchKernelGGL((resblock_pair_h2_kernel<K, C, NB, RAG>), dim3(cdiv(a.L, POUT), B), dim3(256), lds, st, a);
-  BSG_LAUNCH_CHECK();
-  return BSG_OK;
-}
-template <int K, int C, int NB>
-int launch_pair_h2_t(const PairArgs& a, int B, hipStream_t st) {
-  return a.lens ? launch_pair_h2_t_r<K, C, NB, true>(a, B, st) : launch_pair_h2_t_r<K, C, NB, false>(a, B, st);
-}
-int launch_pair_h2(const PairArgs& a, int K, int C, int nb, int B, hipStream_t st) {
-  const int rc = dispatch_kc<32, 64>(K, C, [&](auto k, auto c) {
-    return nb == 2 ? launch_pair_h2_t<k.value, c.value, 2>(a, B, st) : launch_pair_h2_t<k.value, c.value, 1>(a, B, st);
-  });
-  if (rc != HG_NO_KERNEL) return rc;
-  set_error("hifigan: no split-fp16 pair kernel for K=%d C=%d", K, C);
-  return BSG_EINVAL;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1445,43 +1329,6 @@ __global__ __launch_bounds__(256) void resblock_pair_h16_kernel(PairArgs a) {
   }
 }
 
-template <int K, int C, int NB, bool RAG>
-int launch_pair_h16_t_r(const PairArgs& a, int B, hipStream_t st) {
-  constexpr int PT = 128 * NB, POUT = PT - (K - 1), ROWB = 2 * C;
-  const int span = PT + 2 * ((K - 1) / 2 * a.dil);
-  const size_t lds = (size_t)2 * (span > PT + 16 ? span : PT + 16) * ROWB;
-  static size_t attr = 0;
-  if (lds > attr) {
-    BSG_HIP(hipFuncSetAttribute((const void*)resblock_pair_h16_kernel<K, C, NB, RAG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr = lds;
-  }
-  hipLaunchKernelGGL((resblock_pair_h16_kernel<K, C, NB, RAG>), dim3(cdiv(a.L, POUT), B), dim3(256), lds, st, a);
-  BSG_LAUNCH_CHECK();
-  return BSG_OK;
-}
-template <int K, int C, int NB>
-int launch_pair_h16_t(const PairArgs& a, int B, hipStream_t st) {
-  return a.lens ? launch_pair_h16_t_r<K, C, NB, true>(a, B, st) : launch_pair_h16_t_r<K, C, NB, false>(a, B, st);
-}
-int launch_pair_h16(const PairArgs& a, int K, int C, int nb, int B, hipStream_t st) {
-  const int rc = dispatch_kc<16, 8>(K, C, [&](auto k, auto c) {
-    return nb == 2 ? launch_pair_h16_t<k.value, c.value, 2>(a, B, st) : launch_pair_h16_t<k.value, c.value, 1>(a, B, st);
-  });
-  if (rc != HG_NO_KERNEL) return rc;
-  set_error("hifigan: no 16-row split-fp16 pair kernel for K=%d, C=%d", K, C);
-  return BSG_EINVAL;
-}
-// (C = 8 — 4 taps x 8 channels per k-step, half of the MFMA's rows unused — measured SLOWER in round 3 than the VALU pairs it would replace: 220 / 208
-// / 150 us against 199 / 153 / 96 us for K = 11 / 7 / 3 at B=16, T=1000; for C = 16: 180 / 161 / 118 against 355 / 223 / 126 us.  With round 4's
-// staging and residual prefetch: 176 / 160 / 120 us — ahead for K = 11 only, which is what the default takes.)
-// BSG_HG_H16_C8: 8-channel pairs on the 16-row matrix form — default 11 = only K = 11 (176 against 195 us; K = 7 / 3 are faster on the vector
-// pipe: 146 / 93 against 160 / 120 us), 0 = never, 1 = every K
-bool pair_h16_supported(int K, int C) {
-  const int c8 = hg_switches().h16_c8;
-  return (K == 3 || K == 7 || K == 11) && (C == 16 || (C == 8 && (c8 == 1 || (c8 == 11 && K == 11))));
-}
-
-
 // ------------------------------------------------------------------------------------------------
 // A whole ResBlock1 of 8 / 16 channels in ONE launch (round 5): its n_dil (dilated conv, conv) pairs run back to back on a
 // tile that carries the block's receptive-field halo, HT = (K - 1) / 2 x sum(d + 1) positions per side (60 for K = 11 and d = 1, 3, 5), so the
@@ -1629,83 +1476,6 @@ __global__ __launch_bounds__(256) void resblock_chain_h16_kernel(ChainArgs a) {
   }
 }
 
-template <int K, int C, int NC, bool RAG>
-int launch_chain_h16_t_r(const ChainArgs& a, int B, hipStream_t st) {
-  constexpr int PT = 64 * NC, H2 = (K - 1) / 2, ROWB = 2 * C;
-  int ht = 0, dmax = 1;
-  for (int m = 0; m < a.n_pairs; ++m) { ht += H2 * (a.dil[m] + 1); dmax = a.dil[m] > dmax ? a.dil[m] : dmax; }
-  const int pout = PT - 2 * ht;
-  const size_t lds = (size_t)2 * (PT + 2 * H2 * dmax) * ROWB + 6 * 16 * sizeof(float);
-  static size_t attr = 0;
-  if (lds > attr) {
-    BSG_HIP(hipFuncSetAttribute((const void*)resblock_chain_h16_kernel<K, C, NC, RAG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr = lds;
-  }
-  hipLaunchKernelGGL((resblock_chain_h16_kernel<K, C, NC, RAG>), dim3(cdiv(a.L, pout), B), dim3(256), lds, st, a);
-  BSG_LAUNCH_CHECK();
-  return BSG_OK;
-}
-template <int K, int C, int NC>
-int launch_chain_h16_t(const ChainArgs& a, int B, hipStream_t st) {
-  return a.lens ? launch_chain_h16_t_r<K, C, NC, true>(a, B, st) : launch_chain_h16_t_r<K, C, NC, false>(a, B, st);
-}
-bool chain_h16_supported(int K, int C, int n_pairs, const int* dil) {
-  if (!((K == 3 || K == 7 || K == 11) && (C == 16 || C == 8)) || n_pairs < 1 || n_pairs > 3) return false;
-  int ht = 0, dmax = 1;
-  for (int m = 0; m < n_pairs; ++m) { ht += (K - 1) / 2 * (dil[m] + 1); dmax = dil[m] > dmax ? dil[m] : dmax; }
-  return 2 * ht <= 128 && (size_t)2 * (512 + (K - 1) * dmax) * 2 * C <= 80 * 1024;   // >= half of a 256-position tile is output; two workgroups per CU
-}
-int launch_chain_h16(const ChainArgs& a, int K, int C, int nc, int B, hipStream_t st) {
-  const int rc = dispatch_kc<16, 8>(K, C, [&](auto k, auto c) {
-    return nc == 8 ? launch_chain_h16_t<k.value, c.value, 8>(a, B, st) : launch_chain_h16_t<k.value, c.value, 4>(a, B, st);
-  });
-  if (rc != HG_NO_KERNEL) return rc;
-  set_error("hifigan: no ResBlock chain kernel for K=%d, C=%d", K, C);
-  return BSG_EINVAL;
-}
-
-template <int K, int C, int NB, bool RAG>
-int launch_pair_mfma_t_r(const PairArgs& a, int B, hipStream_t st) {
-  constexpr int PT = 128 * NB, POUT = PT - (K - 1);
-  const int h1 = (K - 1) / 2 * a.dil;
-  const int XS = (PT + 2 * h1 + 3) & ~3;
-  const size_t lds = (size_t)C * (XS > PT + 16 ? XS : PT + 16) * sizeof(float);
-  static size_t attr = 0;
-  if (lds > attr) {
-    BSG_HIP(hipFuncSetAttribute((const void*)resblock_pair_mfma_kernel<K, C, NB, RAG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr = lds;
-  }
-  hipLaunchKernelGGL((resblock_pair_mfma_kernel<K, C, NB, RAG>), dim3(cdiv(a.L, POUT), B), dim3(256), lds, st, a);
-  BSG_LAUNCH_CHECK();
-  return BSG_OK;
-}
-template <int K, int C, int NB>
-int launch_pair_mfma_t(const PairArgs& a, int B, hipStream_t st) {
-  return a.lens ? launch_pair_mfma_t_r<K, C, NB, true>(a, B, st) : launch_pair_mfma_t_r<K, C, NB, false>(a, B, st);
-}
-int launch_pair_mfma(const PairArgs& a, int K, int C, int nb, int B, hipStream_t st) {
-  const int rc = dispatch_kc<32, 64>(K, C, [&](auto k, auto c) {
-    return nb == 2 ? launch_pair_mfma_t<k.value, c.value, 2>(a, B, st) : launch_pair_mfma_t<k.value, c.value, 1>(a, B, st);
-  });
-  return rc != HG_NO_KERNEL ? rc : BSG_EINVAL;
-}
-bool pair_mfma_supported(int K, int C) { return (K == 3 || K == 7 || K == 11) && (C == 32 || C == 64); }
-bool pair_supported(int K, int C) { return (K == 3 || K == 7 || K == 11) && (C == 8 || C == 16 || C == 32 || C == 64); }
-int launch_pair(const PairArgs& a, int K, int C, int tt, int B, hipStream_t st) {
-  const int rc = dispatch_kc<8, 16, 32, 64>(K, C, [&](auto k, auto c) { return launch_pair_kc<k.value, c.value>(a, tt, B, st); });
-  return rc != HG_NO_KERNEL ? rc : BSG_EINVAL;
-}
-
-int launch_conv(const ConvArgs& a, int K, int tt, int B, hipStream_t st) {
-  switch (K) {
-    case 3: return launch_conv_k<3>(a, tt, B, st);
-    case 5: return launch_conv_k<5>(a, tt, B, st);      // ResBlock2 configurations (HiFi-GAN V3: kernels 3, 5, 7)
-    case 7: return launch_conv_k<7>(a, tt, B, st);
-    case 11: return launch_conv_k<11>(a, tt, B, st);
-    default: set_error("hifigan: conv kernel size %d not built (3, 5, 7, 11)", K); return BSG_EINVAL;
-  }
-}
-
 }  // namespace
 }  // namespace bsg
 
@@ -1746,11 +1516,213 @@ enum HgSite : uint8_t { HG_PRE, HG_UP, HG_SRC, HG_RB, HG_POST };
 // one value per form token of bsg_hifigan_last_path, in the order of HG_FORM_NAME
 enum HgForm : uint8_t { HG_H2W, HG_CONV, HG_UP2, HG_UPK, HG_POLY, HG_CONVT, HG_ADD, HG_CHAIN, HG_PAIR_H16, HG_PAIR_H2, HG_PAIR_MFMA, HG_PAIR_VALU, HG_CONV1, HG_CONV2, HG_POST4 };
 static const char* const HG_FORM_NAME[] = {"h2w", "conv", "up2", "upk", "poly", "convT", "add", "chain", "pair_h16", "pair_h2", "pair_mfma", "pair_valu", "conv1", "conv2", "post4"};
+
+// ------------------------------------------------------------------------------------------------
+// The launch forms.  One HgKernel row per built instantiation, reached through the getters below, which return null where no kernel is
+// built: that IS the support test.  One geometry function per family says what a workgroup puts out, the grid and the dynamic LDS, to the
+// plan and to the launch alike.  plan_hifigan() resolves each step's row, hg_launch() launches it; hifigan_run() names no kernel.
+// ------------------------------------------------------------------------------------------------
+constexpr int HG_MAX_DIL = 16;   // bsg_hifigan_create refuses a larger dilation
+
+struct HgKernel {
+  const void* fn;   // the __global__ function (launched through hipLaunchKernel)
+  int block;        // threads per workgroup
+  int id;           // the index of its entry in a handle's HgMemo
+  size_t lds_max;   // its dynamic LDS at the largest dilation: what the device is asked to grant it (0: it uses none)
+};
+
+constexpr int hg_log2(int v) { return v <= 1 ? 0 : 1 + hg_log2(v >> 1); }
+constexpr int hg_kidx(int K) { return K == 2 ? 0 : K == 3 ? 1 : K == 5 ? 2 : K == 7 ? 3 : 4; }   // kernel sizes 2 (polyphase), 3, 5, 7, 11
+// ids: conv1d_kernel by (K, CO_BLK, TT, ragged), the pair / chain families by (family, K, C, tile variant, ragged), then the small forms
+enum { HG_ID_CONV = 0, HG_ID_PAIR = HG_ID_CONV + 5 * 2 * 3 * 2, HG_ID_UPK = HG_ID_PAIR + 5 * 5 * 4 * 4 * 2, HG_ID_UP2 = HG_ID_UPK + 3 * 2,
+       HG_ID_CONVT = HG_ID_UP2 + 2 * 2, HG_ID_POST = HG_ID_CONVT + 2 * 2, HG_ID_COUNT = HG_ID_POST + 2 };
+
+template <int ID, class Fn>
+static const HgKernel* hg_row(Fn* fn, size_t lds_max) {
+  static_assert(ID >= 0 && ID < HG_ID_COUNT, "row id");
+  static const HgKernel k{(const void*)fn, 256, ID, lds_max};
+  return &k;
+}
+// run-time v -> f(std::integral_constant<int, v>) for v in Vs; null if v is none of them
+template <int... Vs, class F>
+static const HgKernel* hg_pick(int v, F f) {
+  const HgKernel* k = nullptr;
+  (void)((v == Vs && ((k = f(std::integral_constant<int, Vs>{})), true)) || ...);
+  return k;
+}
+
+struct HgGeom {
+  int pout;     // positions a workgroup puts out
+  dim3 grid;
+  size_t lds;   // dynamic LDS at this dilation
+};
+// conv1d_kernel at `tt` samples per lane; the polyphase form is K = 2, dil = 1 on the L + 1 positions of a phase with rows = B u
+static HgGeom conv_geom(int K, int tt, int Cout, int dil, int L, int rows) {
+  const int tile = 256 * tt;
+  return {tile, dim3(cdiv(L, tile), cdiv(Cout, Cout >= 16 ? 16 : 8), rows), (size_t)CI_CHUNK * (tile + (K - 1) * dil) * sizeof(float)};
+}
+// the fused pairs: var = TT positions per thread (pair_valu) or NB column tiles of 32 positions per wave (the matrix forms)
+static HgGeom pair_geom(HgForm form, int K, int C, int var, int dil, int L, int B) {
+  HgGeom g{};
+  if (form == HG_PAIR_VALU) {
+    const int P = 256 * var;
+    g.pout = P - (K - 1);
+    g.lds = ((size_t)C * P + 16) * sizeof(float);
+  } else {
+    const int PT = 128 * var, span = PT + 2 * ((K - 1) / 2 * dil);
+    g.pout = PT - (K - 1);
+    if (form == HG_PAIR_MFMA) {
+      const int XS = (span + 3) & ~3;
+      g.lds = (size_t)C * (XS > PT + 16 ? XS : PT + 16) * sizeof(float);
+    } else {
+      const int ROWB = form == HG_PAIR_H2 ? 2 * C + 16 : 2 * C;
+      g.lds = (size_t)2 * (span > PT + 16 ? span : PT + 16) * ROWB;
+    }
+  }
+  g.grid = dim3(cdiv(L, g.pout), B);
+  return g;
+}
+// resblock_chain_h16_kernel on tiles of 64 nc positions: ht, the ResBlock's halo per side; planes, the LDS image without the bias rows
+struct ChainGeom : HgGeom {
+  int ht;
+  size_t planes;
+};
+static ChainGeom chain_geom(int K, int C, int nc, int n_pairs, const int* dil, int L, int B) {
+  const int PT = 64 * nc, H2 = (K - 1) / 2, ROWB = 2 * C;
+  int ht = 0, dmax = 1;
+  for (int m = 0; m < n_pairs; ++m) { ht += H2 * (dil[m] + 1); dmax = dil[m] > dmax ? dil[m] : dmax; }
+  ChainGeom g{};
+  g.ht = ht;
+  g.pout = PT - 2 * ht;
+  g.planes = (size_t)2 * (PT + 2 * H2 * dmax) * ROWB;
+  g.lds = g.planes + 6 * 16 * sizeof(float);
+  g.grid = dim3(cdiv(L, g.pout), B);
+  return g;
+}
+
+// conv1d_kernel<K, CO_BLK, TT, ragged>: K = 3, 5, 7, 11 (5: ResBlock2 configurations, HiFi-GAN V3) and 2, CO_BLK = 16 | 8, TT = 4 | 2 | 1
+static const HgKernel* conv_kernel(int K, int co_blk, int tt, bool ragged) {
+  return hg_pick<2, 3, 5, 7, 11>(K, [&](auto k) {
+    return hg_pick<16, 8>(co_blk, [&](auto co) {
+      return hg_pick<4, 2, 1>(tt, [&](auto t) {
+        constexpr int KK = decltype(k)::value, CO = decltype(co)::value, TT = decltype(t)::value;
+        constexpr int id = HG_ID_CONV + ((hg_kidx(KK) * 2 + (CO == 16)) * 3 + hg_log2(TT)) * 2;
+        const size_t lds = conv_geom(KK, TT, CO, HG_MAX_DIL, 1, 1).lds;
+        return ragged ? hg_row<id + 1>(conv1d_kernel<KK, CO, TT, true>, lds) : hg_row<id>(conv1d_kernel<KK, CO, TT, false>, lds);
+      });
+    });
+  });
+}
+
+template <HgForm F, int K, int C, int V, bool RAG>
+static const HgKernel* pair_row() {
+  constexpr int id = HG_ID_PAIR + ((((F - HG_CHAIN) * 5 + hg_kidx(K)) * 4 + hg_log2(C / 8)) * 4 + hg_log2(V)) * 2 + RAG;
+  if constexpr (F == HG_CHAIN) {
+    const int d = HG_MAX_DIL;
+    return hg_row<id>(resblock_chain_h16_kernel<K, C, V, RAG>, chain_geom(K, C, V, 1, &d, 1, 1).lds);
+  } else {
+    const size_t lds = pair_geom(F, K, C, V, HG_MAX_DIL, 1, 1).lds;
+    if constexpr (F == HG_PAIR_H16) return hg_row<id>(resblock_pair_h16_kernel<K, C, V, RAG>, lds);
+    else if constexpr (F == HG_PAIR_H2) return hg_row<id>(resblock_pair_h2_kernel<K, C, V, RAG>, lds);
+    else if constexpr (F == HG_PAIR_MFMA) return hg_row<id>(resblock_pair_mfma_kernel<K, C, V, RAG>, lds);
+    else if constexpr (C * V <= 64) return hg_row<id>(resblock_pair_kernel<K, C, V, RAG>, lds);   // only the widths within the 64-accumulator budget are built
+    else return nullptr;
+  }
+}
+template <int... I>
+using HgInts = std::integer_sequence<int, I...>;
+template <HgForm F, int... Cs, int... Vs>
+static const HgKernel* pair_pick(HgInts<Cs...>, HgInts<Vs...>, int K, int C, int var, bool ragged) {
+  return hg_pick<3, 7, 11>(K, [&](auto k) {
+    return hg_pick<Cs...>(C, [&](auto c) {
+      return hg_pick<Vs...>(var, [&](auto v) {
+        constexpr int KK = decltype(k)::value, CC = decltype(c)::value, VV = decltype(v)::value;
+        return ragged ? pair_row<F, KK, CC, VV, true>() : pair_row<F, KK, CC, VV, false>();
+      });
+    });
+  });
+}
+// the fused pairs and the chain, keyed (form, K, C, tile variant, ragged): K = 3, 7, 11; the channel counts and variants of each family below
+static const HgKernel* pair_kernel(HgForm form, int K, int C, int var, bool ragged) {
+  switch (form) {
+    case HG_PAIR_VALU: return pair_pick<HG_PAIR_VALU>(HgInts<8, 16, 32, 64>{}, HgInts<1, 2, 4, 8>{}, K, C, var, ragged);   // TT (C TT <= 64)
+    case HG_PAIR_MFMA: return pair_pick<HG_PAIR_MFMA>(HgInts<32, 64>{}, HgInts<1, 2>{}, K, C, var, ragged);               // NB
+    case HG_PAIR_H2: return pair_pick<HG_PAIR_H2>(HgInts<32, 64>{}, HgInts<1, 2>{}, K, C, var, ragged);                   // NB
+    case HG_PAIR_H16: return pair_pick<HG_PAIR_H16>(HgInts<16, 8>{}, HgInts<1, 2>{}, K, C, var, ragged);                  // NB
+    case HG_CHAIN: return pair_pick<HG_CHAIN>(HgInts<16, 8>{}, HgInts<4, 8>{}, K, C, var, ragged);                        // NC
+    default: return nullptr;
+  }
+}
+// upsample_kernel<U>, U = 8 | 4 | 2
+static const HgKernel* upk_kernel(int u, bool ragged) {
+  return hg_pick<8, 4, 2>(u, [&](auto uu) {
+    constexpr int U = decltype(uu)::value, id = HG_ID_UPK + hg_log2(U / 2) * 2;
+    return ragged ? hg_row<id + 1>(upsample_kernel<U, true>, 0) : hg_row<id>(upsample_kernel<U, false>, 0);
+  });
+}
+// upsample2_kernel<CO>, CO = 16 | 8 output channels
+static const HgKernel* up2_kernel(int cout, bool ragged) {
+  return hg_pick<16, 8>(cout, [&](auto co) {
+    constexpr int CO = decltype(co)::value, id = HG_ID_UP2 + (CO == 16) * 2;
+    return ragged ? hg_row<id + 1>(upsample2_kernel<CO, true>, 0) : hg_row<id>(upsample2_kernel<CO, false>, 0);
+  });
+}
+// conv_transpose1d_kernel<CO_BLK>, CO_BLK = 16 | 8
+static const HgKernel* convt_kernel(int co_blk, bool ragged) {
+  return hg_pick<16, 8>(co_blk, [&](auto co) {
+    constexpr int CO = decltype(co)::value, id = HG_ID_CONVT + (CO == 16) * 2;
+    return ragged ? hg_row<id + 1>(conv_transpose1d_kernel<CO, true>, 0) : hg_row<id>(conv_transpose1d_kernel<CO, false>, 0);
+  });
+}
+// conv_post_kernel<8>: 8 input channels
+static const HgKernel* post_kernel(int cin, bool ragged) {
+  if (cin != 8) return nullptr;
+  return ragged ? hg_row<HG_ID_POST + 1>(conv_post_kernel<8, true>, 0) : hg_row<HG_ID_POST>(conv_post_kernel<8, false>, 0);
+}
+
+// (C = 8 — 4 taps x 8 channels per k-step, half of the MFMA's rows unused — measured SLOWER in round 3 than the VALU pairs it would replace: 220 / 208
+// / 150 us against 199 / 153 / 96 us for K = 11 / 7 / 3 at B=16, T=1000; for C = 16: 180 / 161 / 118 against 355 / 223 / 126 us.  With round 4's
+// staging and residual prefetch: 176 / 160 / 120 us — ahead for K = 11 only, which is what the default takes.)
+// BSG_HG_H16_C8: 8-channel pairs on the 16-row matrix form — default 11 = only K = 11 (176 against 195 us; K = 7 / 3 are faster on the vector
+// pipe: 146 / 93 against 160 / 120 us), 0 = never, 1 = every K
+static bool pair_h16_supported(int K, int C) {
+  const int c8 = hg_switches().h16_c8;
+  return pair_kernel(HG_PAIR_H16, K, C, 1, false) && (C != 8 || c8 == 1 || (c8 == 11 && K == 11));
+}
+// >= half of a 256-position tile is output; two workgroups per CU at 512 positions
+static bool chain_h16_supported(int K, int C, int n_pairs, const int* dil) {
+  if (!pair_kernel(HG_CHAIN, K, C, 8, false) || n_pairs < 1 || n_pairs > 3) return false;
+  const ChainGeom g = chain_geom(K, C, 8, n_pairs, dil, 1, 1);
+  return 2 * g.ht <= 128 && g.planes <= 80 * 1024;
+}
+
+// Per handle, and so per device (a handle lives on one): which rows the device has granted their LDS.  The grant is the row's lds_max, one
+// size per row whatever the dilation launched, so two handles on one device never lower each other's.
+struct HgMemo {
+  bool granted[HG_ID_COUNT] = {};
+  int ready(const HgKernel& k) {   // every launch passes here: one array read
+    if (granted[k.id] || !k.lds_max) return BSG_OK;
+    BSG_HIP(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds_max));
+    granted[k.id] = true;
+    return BSG_OK;
+  }
+};
+
+// one launch of row `k` on `grid` workgroups with `lds` bytes of dynamic LDS; args: a pointer to every kernel argument, in order
+static int hg_launch(HgMemo& memo, const HgKernel& k, dim3 grid, size_t lds, void** args, hipStream_t st) {
+  BSG_REQUIRE(lds <= k.lds_max, "hifigan: a launch with %zu B of LDS, its kernel is granted %zu", lds, k.lds_max);
+  const int rc = memo.ready(k);
+  if (rc != BSG_OK) return rc;
+  BSG_HIP(hipLaunchKernel(k.fn, grid, dim3(k.block), args, lds, st));
+  return BSG_OK;
+}
+
 struct HgStep {
   HgSite site;
   HgForm form;
   int8_t var;       // tile variant, decided by the plan: TT (conv, poly, pair_valu, conv1, conv2), NB (pair_h16 / _h2 / _mfma), NC (chain); 0: the form has none
   int8_t i, j, m;   // stage, ResBlock of the stage, dilation (-1: the whole ResBlock)
+  const HgKernel* k;   // the kernel it launches (null: the form has its own entry point, gemm_h2w or the NSF source)
 };
 
 struct bsg_hifigan {
@@ -1778,6 +1750,7 @@ struct bsg_hifigan {
   size_t lens_cap = 0;
   std::string path;                       // the launches of the last forward (bsg_hifigan_last_path)
   std::vector<HgStep> steps;              // room for the plan of a forward (plan_hifigan), sized at create
+  HgMemo memo;                            // the LDS grants made on this handle's device
 };
 
 // One token "<site>:<form>[/<tile variant>]" per launch, spelled from the plan entry that has just been launched (the thresholds are
@@ -1849,7 +1822,7 @@ static int pack_conv(bsg_hifigan* h, ConvW& c, hipStream_t st, bool pair = false
   TRY(own_alloc(h->owned, &c.wpk, n));
   hipLaunchKernelGGL(pack_conv_w_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, (const float*)c.w, c.wpk, c.cout, c.cin, c.k, CO);
   BSG_LAUNCH_CHECK();
-  if (pair && c.cin == c.cout && pair_supported(c.k, c.cout)) {   // one block of all output channels: [cin][k][cout]
+  if (pair && c.cin == c.cout && pair_kernel(HG_PAIR_VALU, c.k, c.cout, 1, false)) {   // one block of all output channels: [cin][k][cout]
     const int m = c.cin * c.k * c.cout;
     TRY(own_alloc(h->owned, &c.wpc, m));
     hipLaunchKernelGGL(pack_conv_w_kernel, dim3(cdiv(m, 256)), dim3(256), 0, st, (const float*)c.w, c.wpc, c.cout, c.cin, c.k, c.cout);
@@ -1861,14 +1834,14 @@ static int pack_conv(bsg_hifigan* h, ConvW& c, hipStream_t st, bool pair = false
                          c.k, h->w_range_bad);
       BSG_LAUNCH_CHECK();
       c.wp16c = c.wp16;
-    } else if ((c.cout == 8 || c.cout == 16) && (c.k == 3 || c.k == 7 || c.k == 11)) {   // (8 channels, K = 3 / 7: pairs on the vector pipe, chain on the matrix pipe)
+    } else if (pair_kernel(HG_CHAIN, c.k, c.cout, 8, false)) {   // (8 channels, K = 3 / 7: pairs on the vector pipe, chain on the matrix pipe)
       const int tpk = 32 / c.cout, ks = (c.k + tpk - 1) / tpk;
       TRY(own_alloc(h->owned, &c.wp16c, (size_t)ks * 512));
       hipLaunchKernelGGL(pack_conv_h16_kernel, dim3(cdiv(ks * 512, 256)), dim3(256), 0, st, (const float*)c.w, reinterpret_cast<_Float16*>(c.wp16c), c.cout,
                          c.k, h->w_range_bad);
       BSG_LAUNCH_CHECK();
     }
-    if (pair_mfma_supported(c.k, c.cout)) {
+    if (pair_kernel(HG_PAIR_MFMA, c.k, c.cout, 1, false)) {
       TRY(own_alloc(h->owned, &c.wpm, m));
       hipLaunchKernelGGL(pack_conv_mfma_kernel, dim3(cdiv(m, 256)), dim3(256), 0, st, (const float*)c.w, c.wpm, c.cout, c.k);
       BSG_LAUNCH_CHECK();
@@ -2063,18 +2036,25 @@ static int pair_valu_tt(int K, int C, int L, int B) {
   return 1;
 }
 // resblock_chain_h16_kernel: the tile width by the number of tiles: 512 positions (NC8) while that leaves >= 2 workgroups per CU, else 256 (NC4: more, smaller workgroups)
-static int chain_nc(int K, int n_pairs, const int* dil, int L, int B) {
-  int ht = 0;
-  for (int m = 0; m < n_pairs; ++m) ht += (K - 1) / 2 * (dil[m] + 1);
+static int chain_nc(int K, int C, int n_pairs, const int* dil, int L, int B) {
+  const dim3 wgs8 = chain_geom(K, C, 8, n_pairs, dil, L, B).grid;
   const int forced = hg_switches().chain_nc;
-  return (forced ? forced == 8 : (long long)cdiv(L, 512 - 2 * ht) * B >= 512) ? 8 : 4;
+  return (forced ? forced == 8 : (long long)wgs8.x * wgs8.y >= 512) ? 8 : 4;
 }
 
-static int plan_hifigan(const bsg_hifigan* h, int B, int T, bool nsf, HgStep* out) {
+// ragged: the call carries row lengths; every step gets the row of its kernel (HgStep::k)
+static int plan_hifigan(const bsg_hifigan* h, int B, int T, bool nsf, bool ragged, HgStep* out) {
   const bsg_hifigan_cfg& c = h->cfg;
   const HgSwitches& sw = hg_switches();
   int n = 0;
-  auto add = [&](HgSite site, HgForm form, int var = 0, int i = 0, int j = 0, int m = -1) { out[n++] = HgStep{site, form, (int8_t)var, (int8_t)i, (int8_t)j, (int8_t)m}; };
+  auto add = [&](HgSite site, HgForm form, const HgKernel* k, int var = 0, int i = 0, int j = 0, int m = -1) {
+    out[n++] = HgStep{site, form, (int8_t)var, (int8_t)i, (int8_t)j, (int8_t)m, k};
+  };
+  auto add_conv = [&](HgSite site, HgForm form, const ConvW& w, int L, int i = 0, int j = 0, int m = -1) {   // conv1d_kernel on a Conv1d
+    const int tt = conv_tt(L, w.cout, B);
+    add(site, form, conv_kernel(w.k, w.cout >= 16 ? 16 : 8, tt, ragged), tt, i, j, m);
+  };
+  auto add_pair = [&](HgForm form, const ConvW& w, int var, int i, int j, int m) { add(HG_RB, form, pair_kernel(form, w.k, w.cout, var, ragged), var, i, j, m); };
   // split-fp16 products allowed on this handle in this call: not switched off (BSG_HG_SPLIT), every packed weight inside the fp16 range
   // (h2_ok), and the range guard has not demoted the call
   const bool split_ok = sw.split && h->h2_ok && gemm_split_enabled();
@@ -2082,24 +2062,25 @@ static int plan_hifigan(const bsg_hifigan* h, int B, int T, bool nsf, HgStep* ou
   const bool h16_ok = sw.mfma && sw.h16 && split_ok;    // ... for 8 / 16 channels (pair_h16, chain)
 
   // conv_pre: a 7-tap product on the pre-split GEMM, else conv1d_kernel
-  if (h2w_ok && h->pre.h2w.ok && h2w_supports(T, h->pre.cout, h->pre.h2w_kp, h->pre.k, h->pre.h2w_kp)) add(HG_PRE, HG_H2W);
-  else add(HG_PRE, HG_CONV, conv_tt(T, h->pre.cout, B));
+  if (h2w_ok && h->pre.h2w.ok && h2w_supports(T, h->pre.cout, h->pre.h2w_kp, h->pre.k, h->pre.h2w_kp)) add(HG_PRE, HG_H2W, nullptr);
+  else add_conv(HG_PRE, HG_CONV, h->pre, T);
   int L = T;
   for (int i = 0; i < c.n_ups; ++i) {
     const ConvW& up = h->ups[i];
     const int u = c.upsample_rates[i], p = (up.k - u) / 2, Lout = L * u;
     if (h2w_ok && up.h2w.ok && u == 8 && p == 4 && h2w_supports(L + 1, up.cout * 8, up.cin, 2, up.cin)) {
-      add(HG_UP, HG_H2W, 0, i);
+      add(HG_UP, HG_H2W, nullptr, 0, i);
     } else if (sw.up && !sw.no_up2 && u == 2 && up.k == 4 && p == 1 && (up.cout == 16 || up.cout == 8) && (long long)cdiv(Lout, 1024) * B >= 512) {
-      add(HG_UP, HG_UP2, 0, i);   // (single utterances: 125 workgroups of this form are slower than the phase-per-block form, 38 against 28 us)
+      add(HG_UP, HG_UP2, up2_kernel(up.cout, ragged), 0, i);   // (single utterances: 125 workgroups of this form are slower than the phase-per-block form, 38 against 28 us)
     } else if (sw.up && up.wpu && p * 2 == u && (long long)cdiv(L + 1, 256) * cdiv(up.cout, 8) * B >= 512) {
-      add(HG_UP, HG_UPK, 0, i);   // all phases of a position in one lane (short inputs: the phase-per-block form below has u x the workgroups)
+      add(HG_UP, HG_UPK, upk_kernel(u, ragged), 0, i);   // all phases of a position in one lane (short inputs: the phase-per-block form below has u x the workgroups)
     } else if (up.wpk && !sw.no_polyphase) {
-      add(HG_UP, HG_POLY, conv_tt(L + 1, up.cout, (long long)B * u), i);   // u interleaved 2-tap convolutions, blockIdx.z = (batch row, phase)
+      const int tt = conv_tt(L + 1, up.cout, (long long)B * u);   // u interleaved 2-tap convolutions, blockIdx.z = (batch row, phase)
+      add(HG_UP, HG_POLY, conv_kernel(2, up.cout >= 16 ? 16 : 8, tt, ragged), tt, i);
     } else {
-      add(HG_UP, HG_CONVT, 0, i);
+      add(HG_UP, HG_CONVT, convt_kernel(up.cout >= 16 ? 16 : 8, ragged), 0, i);
     }
-    if (nsf) add(HG_SRC, HG_ADD, 0, i);
+    if (nsf) add(HG_SRC, HG_ADD, nullptr, 0, i);
     L = Lout;
     for (int j = 0; j < c.n_kernels; ++j) {
       const ConvW* rb1 = &h->rb1[((size_t)i * c.n_kernels + j) * c.n_dil];
@@ -2108,10 +2089,14 @@ static int plan_hifigan(const bsg_hifigan* h, int B, int T, bool nsf, HgStep* ou
       // chain allowed for this ResBlock: a ResBlock1 of 8 / 16 channels whose halo fits the tile, every conv packed for it with one kernel size
       bool chain = sw.chain && h16_ok && rb2 && c.n_dil <= 3 && chain_h16_supported(K, C, c.n_dil, c.resblock_dilations[j]);
       for (int m = 0; chain && m < c.n_dil; ++m) chain = rb1[m].wp16c && rb2[m].wp16c && rb1[m].k == K && rb2[m].k == K;
-      if (chain) { add(HG_RB, HG_CHAIN, chain_nc(K, c.n_dil, c.resblock_dilations[j], L, B), i, j); continue; }
+      if (chain) {
+        const int nc = chain_nc(K, C, c.n_dil, c.resblock_dilations[j], L, B);
+        add(HG_RB, HG_CHAIN, pair_kernel(HG_CHAIN, K, C, nc, ragged), nc, i, j);
+        continue;
+      }
       for (int m = 0; m < c.n_dil; ++m) {
         const ConvW& c1 = rb1[m];
-        if (!rb2) { add(HG_RB, HG_CONV, conv_tt(L, c1.cout, B), i, j, m); continue; }   // ResBlock2: one conv1d_kernel launch per dilation
+        if (!rb2) { add_conv(HG_RB, HG_CONV, c1, L, i, j, m); continue; }   // ResBlock2: one conv1d_kernel launch per dilation
         const ConvW& c2 = rb2[m];
         // workgroups of a fused pair at 256 positions each.  Fused (one HBM round trip instead of two and a half) unless the launch would leave
         // most CUs without a workgroup (< 128; the matrix forms at every length); 256 positions per workgroup (NB2) unless that leaves CUs
@@ -2120,22 +2105,22 @@ static int plan_hifigan(const bsg_hifigan* h, int B, int T, bool nsf, HgStep* ou
         const int nb = pair_wgs >= 256 ? 2 : 1;
         const bool use_mfma = sw.mfma && c1.wpm && c2.wpm;
         if (!(sw.fused && c1.wpc && c2.wpc && (use_mfma || pair_wgs >= 128 || sw.fused == 2))) {
-          add(HG_RB, HG_CONV1, conv_tt(L, c1.cout, B), i, j, m);
-          add(HG_RB, HG_CONV2, conv_tt(L, c2.cout, B), i, j, m);
+          add_conv(HG_RB, HG_CONV1, c1, L, i, j, m);
+          add_conv(HG_RB, HG_CONV2, c2, L, i, j, m);
         } else if (h16_ok && c1.wp16 && c2.wp16) {
-          add(HG_RB, HG_PAIR_H16, nb, i, j, m);
+          add_pair(HG_PAIR_H16, c1, nb, i, j, m);
         } else if (use_mfma && split_ok && c1.wps && c2.wps) {
-          add(HG_RB, HG_PAIR_H2, nb, i, j, m);
+          add_pair(HG_PAIR_H2, c1, nb, i, j, m);
         } else if (use_mfma) {
-          add(HG_RB, HG_PAIR_MFMA, nb, i, j, m);
+          add_pair(HG_PAIR_MFMA, c1, nb, i, j, m);
         } else {
-          add(HG_RB, HG_PAIR_VALU, pair_valu_tt(c1.k, c1.cout, L, B), i, j, m);
+          add_pair(HG_PAIR_VALU, c1, pair_valu_tt(c1.k, c1.cout, L, B), i, j, m);
         }
       }
     }
   }
-  if (h->post.cin == 8 && h->post.k == 7 && !sw.no_conv_post) add(HG_POST, HG_POST4);
-  else add(HG_POST, HG_CONV, conv_tt(L, h->post.cout, B));
+  if (h->post.cin == 8 && h->post.k == 7 && !sw.no_conv_post) add(HG_POST, HG_POST4, post_kernel(h->post.cin, ragged));
+  else add_conv(HG_POST, HG_CONV, h->post, L);
   return n;
 }
 
@@ -2145,13 +2130,15 @@ struct HgRows {
   int lmul;
 };
 
-static int run_conv(const ConvW& c, const float* x, float* y, int tt, int B, int L, int dil, float in_slope, const float* res,
+static int run_conv(bsg_hifigan* h, const HgStep& s, const ConvW& c, const float* x, float* y, int B, int L, int dil, float in_slope, const float* res,
                     const float* acc_in, float out_div, int out_tanh, HgRows rows, hipStream_t st) {
   ConvArgs a{};
   a.lens = rows.lens; a.lmul = rows.lmul; a.zero_tail = rows.lens && out_tanh;   // (out_tanh: conv_post, whose output is the caller's)
   a.x = x; a.w = c.wpk; a.bias = c.b; a.y = y; a.res = res; a.acc_in = acc_in; a.out_div = out_div; a.in_slope = in_slope;
   a.out_tanh = out_tanh; a.Cin = c.cin; a.Cout = c.cout; a.L = L; a.dil = dil; a.pad = (c.k * dil - dil) / 2;
-  return launch_conv(a, c.k, tt, B, st);
+  const HgGeom g = conv_geom(c.k, s.var, c.cout, dil, L, B);
+  void* args[] = {&a};
+  return hg_launch(h->memo, *s.k, g.grid, g.lds, args, st);
 }
 
 // conv_pre :150 / a u = 8 transposed convolution on the matrix pipe (gemm_h2w): lrelu(src) as planes [rows][Kp] (rows >= Lin: the rest zero),
@@ -2188,7 +2175,7 @@ static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, 
     BSG_REQUIRE(L < (1LL << 31) / 4, "hifigan_forward: output length %lld too large", L);
   }
   TRY(grow(h, &h->cap, need, st));
-  const int n_steps = plan_hifigan(h, B, T, har != nullptr, h->steps.data());
+  const int n_steps = plan_hifigan(h, B, T, har != nullptr, lens != nullptr, h->steps.data());
   // The stage buffers: x holds conv_pre's output and then every stage's output (the MRF running sum), xs the stage's input (the upsampled
   // tensor, plus the source term); inside a ResBlock the running tensor y moves xs -> ya -> yb -> ... and lands in x with the last pair;
   // tmp is the conv1 output of an unfused pair.
@@ -2202,14 +2189,21 @@ static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, 
     const HgStep& s = h->steps[n];
     const int i = s.i, j = s.j, m = s.m;
     const HgRows rg{lens, L / T};   // (L = T x the rates so far)
+    BSG_REQUIRE(s.k || s.form == HG_H2W || s.form == HG_ADD, "hifigan: no %s kernel built for this configuration", HG_FORM_NAME[s.form]);
     if (s.site == HG_PRE) {
       if (s.form == HG_H2W) TRY(run_h2w(h, h->pre, mel, x, B, T, T, h->pre.k, 1.0f, 0, 0, rg, st));
-      else TRY(run_conv(h->pre, mel, x, s.var, B, T, 1, 1.0f, nullptr, nullptr, 1.0f, 0, rg, st));            // conv_pre :150
+      else TRY(run_conv(h, s, h->pre, mel, x, B, T, 1, 1.0f, nullptr, nullptr, 1.0f, 0, rg, st));            // conv_pre :150
     } else if (s.site == HG_POST) {
-      if (s.form == HG_POST4 && lens) hipLaunchKernelGGL((conv_post_kernel<8, true>), dim3(cdiv(L, 1024), B), dim3(256), 0, st, (const float*)x, (const float*)h->post.w, (const float*)h->post.b, wav, L, 0.01f, rg.lens, rg.lmul);
-      else if (s.form == HG_POST4) hipLaunchKernelGGL(conv_post_kernel<8>, dim3(cdiv(L, 1024), B), dim3(256), 0, st, (const float*)x, (const float*)h->post.w, (const float*)h->post.b, wav, L, 0.01f, rg.lens, rg.lmul);
-      else TRY(run_conv(h->post, x, wav, s.var, B, L, 1, 0.01f, nullptr, nullptr, 1.0f, 1, rg, st));          // :169-171 (default slope 0.01)
-      BSG_LAUNCH_CHECK();
+      if (s.form == HG_POST4) {
+        const float* px = x;
+        const float *pw = h->post.w, *pb = h->post.b;
+        float post_slope = 0.01f;
+        HgRows r = rg;
+        void* args[] = {&px, &pw, &pb, &wav, &L, &post_slope, &r.lens, &r.lmul};
+        TRY(hg_launch(h->memo, *s.k, dim3(cdiv(L, 1024), B), 0, args, st));
+      } else {
+        TRY(run_conv(h, s, h->post, x, wav, B, L, 1, 0.01f, nullptr, nullptr, 1.0f, 1, rg, st));          // :169-171 (default slope 0.01)
+      }
     } else if (s.site == HG_SRC) {   // x = x + LayerNorm_C(relu(noise_conv_i(har_source)))                       (hifigan.py:154-160)
       const ConvW& nc = h->noise_convs[i];
       const int stride = i + 1 < c.n_ups ? nc.k / 2 : 1;
@@ -2220,44 +2214,29 @@ static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, 
       UpArgs ua{};
       ua.x = x; ua.w = s.form == HG_UPK ? up.wpu : up.w; ua.bias = up.b; ua.y = xs; ua.slope = slope; ua.Cin = up.cin; ua.Cout = up.cout; ua.Lin = L; ua.p = p;
       ua.lens = rg.lens; ua.lmul = rg.lmul;
+      void* up_args[] = {&ua};
       switch (s.form) {
         case HG_H2W: TRY(run_h2w(h, up, x, xs, B, L, L + 1, 2, slope, 8, p, rg, st)); break;
-        case HG_UP2:
-          if (up.cout == 16 && lens) hipLaunchKernelGGL((upsample2_kernel<16, true>), dim3(cdiv(Lout, 1024), 1, B), dim3(256), 0, st, ua);
-          else if (up.cout == 16) hipLaunchKernelGGL(upsample2_kernel<16>, dim3(cdiv(Lout, 1024), 1, B), dim3(256), 0, st, ua);
-          else if (lens) hipLaunchKernelGGL((upsample2_kernel<8, true>), dim3(cdiv(Lout, 1024), 1, B), dim3(256), 0, st, ua);
-          else hipLaunchKernelGGL(upsample2_kernel<8>, dim3(cdiv(Lout, 1024), 1, B), dim3(256), 0, st, ua);
-          break;
-        case HG_UPK: {
-          const dim3 grid(cdiv(L + 1, 256), cdiv(up.cout, 8), B);
-          if (lens) {
-            if (u == 8) hipLaunchKernelGGL((upsample_kernel<8, true>), grid, dim3(256), 0, st, ua);
-            else if (u == 4) hipLaunchKernelGGL((upsample_kernel<4, true>), grid, dim3(256), 0, st, ua);
-            else hipLaunchKernelGGL((upsample_kernel<2, true>), grid, dim3(256), 0, st, ua);
-          } else if (u == 8) hipLaunchKernelGGL(upsample_kernel<8>, grid, dim3(256), 0, st, ua);
-          else if (u == 4) hipLaunchKernelGGL(upsample_kernel<4>, grid, dim3(256), 0, st, ua);
-          else hipLaunchKernelGGL(upsample_kernel<2>, grid, dim3(256), 0, st, ua);
-          break;
-        }
+        case HG_UP2: TRY(hg_launch(h->memo, *s.k, dim3(cdiv(Lout, 1024), 1, B), 0, up_args, st)); break;
+        case HG_UPK: TRY(hg_launch(h->memo, *s.k, dim3(cdiv(L + 1, 256), cdiv(up.cout, 8), B), 0, up_args, st)); break;
         case HG_POLY: {   // the weights are wave-uniform -> scalar loads
           ConvArgs a{};
           a.x = x; a.w = up.wpk; a.bias = up.b; a.y = xs; a.out_div = 1.0f; a.in_slope = slope;
           a.Cin = up.cin; a.Cout = up.cout; a.L = L; a.dil = 1; a.pad = 1;
           a.n_phase = u; a.ph_off = -p; a.Lq = L + 1; a.Lout = Lout; a.lens = rg.lens; a.lmul = rg.lmul;
           a.w_phase_stride = (long long)cdiv(up.cout, up.cout >= 16 ? 16 : 8) * up.cin * 2 * (up.cout >= 16 ? 16 : 8);
-          TRY(launch_convT(a, s.var, B, st));
+          const HgGeom g = conv_geom(2, s.var, up.cout, 1, a.Lq, B * u);
+          void* args[] = {&a};
+          TRY(hg_launch(h->memo, *s.k, g.grid, g.lds, args, st));
           break;
         }
         default: {
           ConvTArgs t{};
           t.x = x; t.w = up.w; t.bias = up.b; t.y = xs; t.in_slope = slope; t.Cin = up.cin; t.Cout = up.cout; t.Lin = L; t.K = up.k; t.u = u; t.p = p; t.lens = rg.lens; t.lmul = rg.lmul;
-          if (up.cout >= 16 && lens) hipLaunchKernelGGL((conv_transpose1d_kernel<16, true>), dim3(cdiv(Lout, 256), cdiv(up.cout, 16), B), dim3(256), 0, st, t);
-          else if (up.cout >= 16) hipLaunchKernelGGL(conv_transpose1d_kernel<16>, dim3(cdiv(Lout, 256), cdiv(up.cout, 16), B), dim3(256), 0, st, t);
-          else if (lens) hipLaunchKernelGGL((conv_transpose1d_kernel<8, true>), dim3(cdiv(Lout, 256), cdiv(up.cout, 8), B), dim3(256), 0, st, t);
-          else hipLaunchKernelGGL(conv_transpose1d_kernel<8>, dim3(cdiv(Lout, 256), cdiv(up.cout, 8), B), dim3(256), 0, st, t);
+          void* args[] = {&t};
+          TRY(hg_launch(h->memo, *s.k, dim3(cdiv(Lout, 256), cdiv(up.cout, up.cout >= 16 ? 16 : 8), B), 0, args, st));
         }
       }
-      BSG_LAUNCH_CHECK();
       L = Lout;
     } else {   // a ResBlock, or one (dilated conv, conv) pair of it: the MRF sum / mean in the epilogue of the ResBlock's last launch (:161-167)
       const size_t r = ((size_t)i * c.n_kernels + j) * c.n_dil + (m < 0 ? 0 : m);
@@ -2281,30 +2260,25 @@ static int hifigan_run(bsg_hifigan* h, const float* mel, float* wav, int32_t B, 
             ca.w1[q] = h->rb1[r + q].wp16c; ca.b1[q] = h->rb1[r + q].b; ca.w2[q] = h->rb2[r + q].wp16c; ca.b2[q] = h->rb2[r + q].b;
             ca.dil[q] = c.resblock_dilations[j][q];
           }
-          TRY(launch_chain_h16(ca, c1.k, c1.cout, s.var, B, st));
+          const ChainGeom g = chain_geom(c1.k, c1.cout, s.var, ca.n_pairs, ca.dil, L, B);
+          void* args[] = {&ca};
+          TRY(hg_launch(h->memo, *s.k, g.grid, g.lds, args, st));
           break;
         }
         case HG_CONV:   // ResBlock2 (hifigan.py:70-91): x = conv_d(lrelu(x)) + x per dilation
-          TRY(run_conv(c1, y, dst, s.var, B, L, dil, slope, y, acc_in, out_div, 0, rg, st));
+          TRY(run_conv(h, s, c1, y, dst, B, L, dil, slope, y, acc_in, out_div, 0, rg, st));
           break;
-        case HG_PAIR_H16:
-          pa.w1 = c1.wp16; pa.w2 = c2->wp16; pa.range_events = gemm_range_counter();
-          TRY(launch_pair_h16(pa, c1.k, c1.cout, s.var, B, st));
-          break;
-        case HG_PAIR_H2:
-          pa.w1 = c1.wps; pa.w2 = c2->wps; pa.range_events = gemm_range_counter();
-          TRY(launch_pair_h2(pa, c1.k, c1.cout, s.var, B, st));
-          break;
-        case HG_PAIR_MFMA:
-          pa.w1 = c1.wpm; pa.w2 = c2->wpm;
-          TRY(launch_pair_mfma(pa, c1.k, c1.cout, s.var, B, st));
-          break;
-        case HG_PAIR_VALU:
-          pa.w1 = c1.wpc; pa.w2 = c2->wpc;
-          TRY(launch_pair(pa, c1.k, c1.cout, s.var, B, st));
-          break;
-        case HG_CONV1: TRY(run_conv(c1, y, tmp, s.var, B, L, dil, slope, nullptr, nullptr, 1.0f, 0, rg, st)); break;     // :56-57
-        default: TRY(run_conv(*c2, tmp, dst, s.var, B, L, 1, slope, y, acc_in, out_div, 0, rg, st));                      // conv2 :58-60
+        case HG_PAIR_H16: pa.w1 = c1.wp16; pa.w2 = c2->wp16; pa.range_events = gemm_range_counter(); break;
+        case HG_PAIR_H2: pa.w1 = c1.wps; pa.w2 = c2->wps; pa.range_events = gemm_range_counter(); break;
+        case HG_PAIR_MFMA: pa.w1 = c1.wpm; pa.w2 = c2->wpm; break;
+        case HG_PAIR_VALU: pa.w1 = c1.wpc; pa.w2 = c2->wpc; break;
+        case HG_CONV1: TRY(run_conv(h, s, c1, y, tmp, B, L, dil, slope, nullptr, nullptr, 1.0f, 0, rg, st)); break;     // :56-57
+        default: TRY(run_conv(h, s, *c2, tmp, dst, B, L, 1, slope, y, acc_in, out_div, 0, rg, st));                      // conv2 :58-60
+      }
+      if (s.form >= HG_PAIR_H16 && s.form <= HG_PAIR_VALU) {   // a fused pair: its weights are set above
+        const HgGeom g = pair_geom(s.form, c1.k, c1.cout, s.var, dil, L, B);
+        void* args[] = {&pa};
+        TRY(hg_launch(h->memo, *s.k, g.grid, g.lds, args, st));
       }
       if (s.form != HG_CONV1) y = dst;
     }
